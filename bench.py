@@ -22,6 +22,9 @@ gpurun_out/bench_detail.json) and then, as the LAST stdout line, ONE compact JSO
                      it runs on (split mode: 3 fp16 MFMA FLOPs per algorithmic fp32 FLOP against 2.5 PFLOP/s) or the 8 TB/s HBM peak.
   roofline_mfma   -- A2 gate kernels (fwd + dX + dW), the time-dominant contractions.
   secondary_ms_per_step -- step times of the secondary legs (bf16 mode, config 3, one rank of configs 4 / 5, PCIe-inclusive feed).
+
+`--dump-outputs DIR`: what the last timed step computed (rank 0: loss, slide / token embeddings, gradients, updated parameters) as
+DIR/<name>.npy, float32, <= 64 MB in all (larger arrays as a fixed, seeded sample); same arguments -> same inputs in every run.
 """
 import argparse
 import json
@@ -592,6 +595,49 @@ def secondary_inference_leg(dev, MF, MADELEINE, n_patches=30000, bags=20):
     return out
 
 
+DUMP_MAX_BYTES = 60 * 2 ** 20   # --dump-outputs: array bytes in all (< 64 MB with the .npy headers)
+
+
+def timed_step_outputs(loss, fwd, model):
+    """What a caller of the timed step holds after it, copied to host: the loss, the slide / token embeddings of the forward, every
+    parameter's gradient and the parameters after the optimiser step.  name -> float32 numpy array (float64 stays float64)."""
+    out = {"loss": loss}
+    for kind, d in (("emb", fwd.get("embs")), ("tok", fwd.get("toks"))):
+        for k, v in (d or {}).items():
+            if torch.is_tensor(v):
+                out[f"{kind}.{k}"] = v
+    for k, p in model.named_parameters():
+        if p.grad is not None:
+            out["grad." + k] = p.grad
+        out["param." + k] = p
+    res = {}
+    for k, v in out.items():
+        v = v.detach()
+        res[k] = v.to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy()
+    return res
+
+
+def write_outputs(dirname, arrays, max_bytes=DUMP_MAX_BYTES):
+    """DIR/<name>.npy for every array, at most `max_bytes` in all: smallest arrays first, each within an equal share of what is left; an
+    array over its share is replaced by a fixed, seeded sample of its flattened values (the same indices in every run for the same shape)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    left, n_left, sampled, total = max_bytes, len(arrays), [], 0
+    for name in sorted(arrays, key=lambda k: (arrays[k].nbytes, k)):
+        x = arrays[name]
+        share = left // n_left
+        if x.nbytes > share:
+            k = max(1, share // x.itemsize)
+            idx = np.sort(np.random.default_rng(0).choice(x.size, size=k, replace=False))
+            x = x.reshape(-1)[idx]
+            sampled.append(name)
+        np.save(os.path.join(dirname, name + ".npy"), x)
+        left -= x.nbytes
+        total += x.nbytes
+        n_left -= 1
+    return {"dir": dirname, "arrays": len(arrays), "bytes": total, "sampled": sampled}
+
+
 COMPACT_MAX = 4096   # bytes: the driver's record keeps the last ~8 KB of stdout and parses the LAST line -- round 5's 22-KB line was lost
 
 
@@ -684,7 +730,12 @@ def main():
                     help="slides per rank instead of the configuration's (32): a REDUCED workload, named as such in config.workload -- for "
                          "debug runs of many gloo ranks on one GPU (tests); never the metric")
     ap.add_argument("--label-seed", type=int, default=77, help="seed of the ACROBAT stain-presence masks (rank r draws with seed + r)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0: loss, slide and token embeddings, "
+                         "parameter gradients, updated parameters) as DIR/<name>.npy, float32, <= 64 MB in all")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if a.gpus > 1 and "RANK" not in os.environ:
         # turnkey N-GPU run: `python bench.py --gpus N ...` without a launcher re-executes itself as N ranks (one per GPU) under
@@ -772,6 +823,7 @@ def main():
         host_iter = iter(DevicePrefetcher(host_batches(), dev, depth=2))
 
     hgroup = D.host_group()   # gloo group for host-resident control data (None on one rank / when gloo is unavailable)
+    last_fwd = {} if a.dump_outputs and rank == 0 else None   # --dump-outputs: the forward outputs of the latest step (references only)
 
     def step(bf16=(a.precision == "bfloat16")):
         nonlocal data
@@ -783,6 +835,8 @@ def main():
         pending = D.all_gather_labels_async(labels[:, 1:], hgroup)
         with torch.autocast(device_type="cuda", dtype=torch.bfloat16, enabled=bf16):   # as trainer.py:101-103
             embs, toks = net(data, device=dev)
+            if last_fwd is not None:
+                last_fwd.update(embs=embs, toks=toks)
             # ONE data-path collective: all-gather of [slide embeddings | presence mask | GOT extrema] -> replicated global
             # InfoNCE + rank-local GOT with global-batch thresholds ([S,6] all-reduce in backward); DDP all-reduces the grads.
             loss, flag = D.calculate_losses_dp(mods[1:], crit, got_impl, embs, toks, labels[:, 1:], largs,
@@ -822,6 +876,10 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     dev_allocs = torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - dev_allocs0   # hipMalloc calls inside the timed region (0 = steady state)
+    dump_info = None
+    if last_fwd is not None:   # host copies now: the steps after the timed region update the parameters in place
+        dump_info = write_outputs(a.dump_outputs, timed_step_outputs(loss, last_fwd, model))
+        last_fwd = None
     prof_pool, pool_parts = {}, None
     if MF.POOL_TIMER is not None:
         rep = MF.POOL_TIMER.report()          # the dispatches' own begin / end events (hipExtLaunchKernel), read after the region
@@ -989,6 +1047,8 @@ def main():
                        "host_label_exchange": ("gloo" if hgroup is not None else ("device" if dist_on else "none")),
                        "grad_sync": ("none" if not dist_on else ("ddp" if gsync is None else "flat_all_reduce"))},
         }
+        if dump_info is not None:
+            out["outputs_dump"] = dump_info
         if gsync_events:
             torch.cuda.synchronize()
             gms = sorted(e0.elapsed_time(e1) for e0, e1 in gsync_events)

