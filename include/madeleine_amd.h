@@ -56,7 +56,7 @@ const char* mdl_version(void);
 /* ABI revision of this header: bumped whenever an entry point's argument list changes.  A binding compares
  * mdl_abi_version() with the MDL_ABI_VERSION it was written against BEFORE calling anything else, so that a stale
  * shared object fails loudly instead of being called with shifted arguments. */
-#define MDL_ABI_VERSION 24
+#define MDL_ABI_VERSION 25
 int mdl_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -515,6 +515,48 @@ int mdl_abmil_attnpool_bwd_split(const void* E_img, int64_t e_rsb, const float* 
                                  uint64_t seed, const uint8_t* keep_a, const uint8_t* keep_b, const float* scores, const float* stat_m,
                                  const float* stat_l, const float* d_pooled, const int32_t* row_bag, int64_t N, float* dE_absmax, void* ws,
                                  void* stream, int phases, int terms);
+
+/* Dispatch plan (ABI 25): what the launcher of `product` chooses for a problem of T tokens (GOT: T = cases k of the launch), WITHOUT
+ * launching anything -- host only, no device, no device memory.  Every answer comes from the launcher's own selection functions
+ * (splits_for and the per-product split / tile / persistence predicates, the GOT class selection), under the same MADELEINE_*
+ * environment switches the launchers read.  `cus`: compute units of the device the plan is for (only the GOT sweeps depend on it;
+ * the gate / Linear launchers are sized for the 256 CUs of an MI355X).  out[0 .. n_out) receives up to MDL_PLAN_FIELDS fields
+ * (the rest set to 0); returns MDL_E_ARG for an unknown product, bad sizes or n_out < 1, MDL_E_UNSUPPORTED where the launcher
+ * would refuse the geometry.
+ *
+ *   product                      a, b        [VARIANT]                                 [PERSIST]                [EXTRA]
+ *   MDL_PLAN_GATE_FP32_BWD       H, -        0                                         0                        0
+ *   MDL_PLAN_GATE_SPLIT_FWD      H, -        0                                         persistent mode (0,1,2)  0
+ *   MDL_PLAN_GATE_SPLIT_BWD      H, -        0                                         0                        0
+ *   MDL_PLAN_GATE_BF16_FWD       H, -        token tile 128 | 256                      persistent mode (0,1,2)  0
+ *   MDL_PLAN_GATE_BF16_BWD       H, -        dW tile 128 | 256                         0                        dX token tile 128 | 256
+ *   MDL_PLAN_SPLIT_TN            Mi, N       0                                         0                        0
+ *   MDL_PLAN_LINEAR_FP32_BWD     N, K        0 small-T | 1 wide (N % 256) | 2 swapped  0                        0
+ *   MDL_PLAN_LINEAR_BF16_FWD     N, K        2 (128-col) | 4 (256-col) | 256 (256x256) tiles per workgroup       0
+ *   MDL_PLAN_LINEAR_BF16_BWD     N, K        dW tile 128 | 256                         dX tiles per workgroup   dX: 4 (128x256) | 256
+ *   MDL_PLAN_GOT                 n, -        size class 64 | 128 | 192 | 256 | 512     row-half products        split sweeps: 0 off,
+ *                                                                                                               1 (2k WGs), 2 (+ 4k)
+ * [SPLITS] token splits S of the dW-type contraction (1, with TPS = CHUNK = 0, where there are none), [TPS] tokens per split, [EMPTY] splits that hold no
+ * token ((s * tps >= T)), [CHUNK] tokens per chunk of the contraction's main loop (tps is a multiple of it). */
+#define MDL_PLAN_GATE_FP32_BWD 1
+#define MDL_PLAN_GATE_SPLIT_FWD 2
+#define MDL_PLAN_GATE_SPLIT_BWD 3
+#define MDL_PLAN_GATE_BF16_FWD 4
+#define MDL_PLAN_GATE_BF16_BWD 5
+#define MDL_PLAN_SPLIT_TN 6
+#define MDL_PLAN_LINEAR_FP32_BWD 7
+#define MDL_PLAN_LINEAR_BF16_FWD 8
+#define MDL_PLAN_LINEAR_BF16_BWD 9
+#define MDL_PLAN_GOT 10
+#define MDL_PLAN_VARIANT 0
+#define MDL_PLAN_PERSIST 1
+#define MDL_PLAN_SPLITS 2
+#define MDL_PLAN_TPS 3
+#define MDL_PLAN_EMPTY 4
+#define MDL_PLAN_CHUNK 5
+#define MDL_PLAN_EXTRA 6
+#define MDL_PLAN_FIELDS 7
+int mdl_dispatch_plan(int product, int64_t T, int a, int b, int cus, int64_t* out_host, int n_out);
 
 #ifdef __cplusplus
 }

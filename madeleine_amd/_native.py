@@ -13,7 +13,7 @@ from . import _build
 
 _LOCK = threading.Lock()
 _LIB = None
-ABI_VERSION = 24   # == MDL_ABI_VERSION of include/madeleine_amd.h this file's SIGNATURES were written against
+ABI_VERSION = 25   # == MDL_ABI_VERSION of include/madeleine_amd.h this file's SIGNATURES were written against
 
 c_f = ctypes.c_void_p  # float* (device)
 c_p = ctypes.c_void_p
@@ -119,6 +119,7 @@ SIGNATURES = {
                                            f32, u64, c_p, c_p, c_f, c_f, c_f, c_f, c_p, i64, c_f, c_p, c_p, i32, i32]),
     "mdl_abmil_gate_bwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32,
                                       f32, u64, c_p, c_p, c_p, c_p]),
+    "mdl_dispatch_plan": (i32, [i32, i64, i32, i32, i32, c_p, i32]),
 }
 
 
@@ -181,3 +182,18 @@ def check(rc: int, what: str):
     if rc != 0:
         msg = _ERR.get(rc, "hipError_t %d" % rc)
         raise RuntimeError("madeleine_amd: %s failed: %s" % (what, msg))
+
+
+# mdl_dispatch_plan products / fields (include/madeleine_amd.h)
+PLAN_PRODUCTS = {"gate_fp32_bwd": 1, "gate_split_fwd": 2, "gate_split_bwd": 3, "gate_bf16_fwd": 4, "gate_bf16_bwd": 5, "split_tn": 6,
+                 "linear_fp32_bwd": 7, "linear_bf16_fwd": 8, "linear_bf16_bwd": 9, "got": 10}
+PLAN_FIELDS = ("variant", "persist", "splits", "tps", "empty", "chunk", "extra")
+
+
+def dispatch_plan(product: str, T: int, a: int, b: int = 0, cus: int = 256) -> dict:
+    """What the launcher of `product` chooses for T tokens (GOT: T = cases) and sizes a, b on a device of `cus` compute units: a dict
+    over PLAN_FIELDS.  Host only (no device needed)."""
+    out = (ctypes.c_int64 * len(PLAN_FIELDS))()
+    check(lib().mdl_dispatch_plan(PLAN_PRODUCTS[product], T, a, b, cus, ctypes.addressof(out), len(PLAN_FIELDS)),
+          "mdl_dispatch_plan(%s, T=%d, %d, %d)" % (product, T, a, b))
+    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))

@@ -575,3 +575,13 @@ extern "C" int mdl_abmil_gate_dropout_mask(uint8_t* keep, int64_t T, int H, int 
     MDL_LAUNCH_CHECK();
     return MDL_OK;
 }
+
+namespace mdl {
+// mdl_dispatch_plan (dispatch_plan.hip): the token splits of gate_bwd_impl's dW contraction
+int plan_gate_fp32_bwd(int64_t T, int H, int64_t* o) {
+    if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
+    const int S = gate_splits(T, H);
+    plan_splits(o, T, S, gate_tok_per_split(T, S), GBK);
+    return MDL_OK;
+}
+}  // namespace mdl

@@ -607,6 +607,18 @@ __global__ __launch_bounds__(512) void gate_dw256_bf16_kernel(const bf16_t* __re
             for (int ct = 0; ct < 2; ++ct) so[(int64_t)kr * 1024 + n0 + wn * 64 + ct * 32 + l32] = acc[rt][ct][r];
         }
 }
+// the forward on the 256 x 256 x 64 tile from 4096 tokens (MADELEINE_BF16_GATE128: the 128 x 256 tile throughout, A/B switch), and its
+// persistent workgroups (round 5, see gate_fwd256_bf16_kernel) for a grid of `grid_tiles` tile workgroups: MADELEINE_BF16_GATE_PERSIST =
+// 0 | 1 | 2 picks the mode (A/B switch), kept only where gate_persist_pays
+static inline bool gate_fwd_use_q(int64_t T) { return T >= 4096 && !getenv("MADELEINE_BF16_GATE128"); }
+static inline int gate_fwd256_pmode(int64_t grid_tiles) {
+    static const int pmode_env = getenv("MADELEINE_BF16_GATE_PERSIST") ? atoi(getenv("MADELEINE_BF16_GATE_PERSIST")) : MDL_GATE_BF16_PMODE;
+    int pmode = pmode_env;
+    if (pmode == 1 && !gate_persist_pays(grid_tiles, 0.93)) pmode = 0;
+    if (pmode == 2 && !gate_persist_pays(grid_tiles, 0.93, GATE_PT16)) pmode = 0;
+    return pmode;
+}
+static inline bool gate_dx_use_q(int64_t T) { return T >= 4096; }
 static inline bool gate_dw_use_q(int64_t T) {
     static const bool off = getenv("MADELEINE_BF16_TN256") && atoi(getenv("MADELEINE_BF16_TN256")) == 0;   // A/B switch
     return !off && T >= 16384;
@@ -673,12 +685,8 @@ extern "C" int mdl_abmil_gate_fwd_bf16(const uint16_t* E, int64_t ldE, const flo
     hipLaunchKernelGGL((gate_fwd_bf16_kernel<DM, SAVE>), dim3((unsigned)grid), dim3(256), 0, s, (const bf16_t*)E, ldE, (const bf16_t*)WK, \
                        ba, bb, wc, part, (bf16_t*)act_a, (bf16_t*)act_b, T, H, (int)n_tt, d)
     const int64_t n_tt256 = (T + QM - 1) / QM;
-    // persistent workgroups (round 5, see gate_fwd256_bf16_kernel): MADELEINE_BF16_GATE_PERSIST = 0 | 1 | 2 picks the mode (A/B switch)
-    static const int pmode_env = getenv("MADELEINE_BF16_GATE_PERSIST") ? atoi(getenv("MADELEINE_BF16_GATE_PERSIST")) : MDL_GATE_BF16_PMODE;
     const int64_t grid_tiles = xcd_head_grid(n_tt256, GATE_JT, H);
-    int pmode = pmode_env;
-    if (pmode == 1 && !gate_persist_pays(grid_tiles, 0.93)) pmode = 0;
-    if (pmode == 2 && !gate_persist_pays(grid_tiles, 0.93, GATE_PT16)) pmode = 0;
+    const int pmode = gate_fwd256_pmode(grid_tiles);
     const int64_t per_share = (n_tt256 + 8 / H - 1) / (8 / H);
     const int64_t grid256 = pmode == 1 ? grid_tiles / GATE_JT : pmode == 2 ? 8 * ((per_share + GATE_PT16 - 1) / GATE_PT16) * GATE_JT : grid_tiles;
 #define MDL_GATE_FWD256_1(DM, SAVE, PM)                                                                                            \
@@ -690,8 +698,7 @@ extern "C" int mdl_abmil_gate_fwd_bf16(const uint16_t* E, int64_t ldE, const flo
         else if (pmode == 2) MDL_GATE_FWD256_1(DM, SAVE, 2);                                                                       \
         else MDL_GATE_FWD256_1(DM, SAVE, 0);                                                                                       \
     } while (0)
-    const bool big = T >= 4096 && !getenv("MADELEINE_BF16_GATE128");
-    if (big) {   // 256 x 256 x 64 tile
+    if (gate_fwd_use_q(T)) {   // 256 x 256 x 64 tile
         if (act_a) {
             if (dm == 0) MDL_GATE_FWD256(0, true);
             else if (dm == 1) MDL_GATE_FWD256(1, true);
@@ -770,7 +777,7 @@ static int gate_bwd_bf16_impl(const uint16_t* E, int64_t ldE, const float* Wa, c
         if (T > 0) {
             hipLaunchKernelGGL(gate_wn_bf16_kernel, dim3(16, 32, H), dim3(256), 0, s, Wa, Wb, WN);
             MDL_LAUNCH_CHECK();
-            if (T >= 4096) {   // long contraction (K = 1024): the 256 x 256 x 64 tile (measured: 1.58 -> see DESIGN.md)
+            if (gate_dx_use_q(T)) {   // long contraction (K = 1024): the 256 x 256 x 64 tile (measured: 1.58 -> see DESIGN.md)
                 const int64_t n_tt = (T + QM - 1) / QM;
                 const int64_t grid = xcd_head_grid(n_tt, 2, H);
                 if (grid > 0x7fffffff) return MDL_E_UNSUPPORTED;
@@ -836,3 +843,24 @@ extern "C" int mdl_abmil_attnpool_bwd_phases_bf16(const uint16_t* E, int64_t ldE
     return gate_bwd_bf16_impl(E, ldE, Wa, Wb, wc, act_a, act_b, d_scores, dE, accumulate, dWa, dWb, dba, dbb, dwc, dbc, T, H, p_drop, seed,
                               keep_a, keep_b, ws, stream, PoolTerm{scores, stat_m, stat_l, d_pooled, row_bag, N}, phases);
 }
+
+namespace mdl {
+// mdl_dispatch_plan (dispatch_plan.hip): the forward's tile and persistence mode (mdl_abmil_gate_fwd_bf16), the backward's dX / dW tiles
+// and the token splits of its dW contraction (mdl_abmil_gate_bwd_bf16)
+int plan_gate_bf16(int product, int64_t T, int H, int64_t* o) {
+    if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
+    if (product == MDL_PLAN_GATE_BF16_FWD) {
+        const bool q = gate_fwd_use_q(T);
+        o[MDL_PLAN_VARIANT] = q ? QM : BBM;
+        o[MDL_PLAN_PERSIST] = q ? gate_fwd256_pmode(xcd_head_grid((T + QM - 1) / QM, GATE_JT, H)) : 0;
+        o[MDL_PLAN_SPLITS] = 1;
+        return MDL_OK;
+    }
+    const BwdWs L = bwd_ws(T, H);
+    const bool q = gate_dw_use_q(T);
+    o[MDL_PLAN_VARIANT] = q ? 256 : 128;
+    o[MDL_PLAN_EXTRA] = gate_dx_use_q(T) ? QM : BBM;
+    plan_splits(o, T, L.S, L.tps, q ? TQK : TNK);
+    return MDL_OK;
+}
+}  // namespace mdl

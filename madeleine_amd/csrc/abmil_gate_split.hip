@@ -455,6 +455,15 @@ struct SpBwdWs {
     int64_t tps, nblk;
     int64_t oWN, odz, oslabW, oslabV, osc, total;
 };
+// persistent workgroups of the forward (round 5, see sp_gate_fwd_kernel) for a grid of `grid` tile workgroups: MADELEINE_GATE_PERSIST =
+// 0 | 1 | 2 picks the mode (A/B switch), kept only where gate_persist_pays
+static inline int sp_gate_fwd_pmode(int64_t grid) {
+    static const int pmode_env = getenv("MADELEINE_GATE_PERSIST") ? atoi(getenv("MADELEINE_GATE_PERSIST")) : MDL_GATE_SP_PMODE;
+    int pmode = pmode_env;
+    if (pmode == 1 && !gate_persist_pays(grid, 0.96)) pmode = 0;
+    if (pmode == 2 && !gate_persist_pays(grid, 0.96, GATE_PT)) pmode = 0;
+    return pmode;
+}
 static inline SpBwdWs sp_bwd_ws(int64_t T, int H) {
     SpBwdWs w;
     w.S = splits_for(T, 8 * H, 256);   // 2 x 4 tiles per head and split; one workgroup per CU
@@ -517,13 +526,9 @@ extern "C" int mdl_abmil_gate_fwd_split(const void* E_img, int64_t e_rsb, const 
     hipLaunchKernelGGL(sp_gate_wk_kernel, dim3((unsigned)((int64_t)H * 1024 * 64 / 256)), dim3(256), 0, s, Wa, Wb, WK, H, (const float*)sc);
     MDL_LAUNCH_CHECK();
     const int dm = gate_drop_mode(d);
-    // persistent workgroups (round 5, see sp_gate_fwd_kernel): MADELEINE_GATE_PERSIST = 0 | 1 | 2 picks the mode (A/B switch)
-    static const int pmode_env = getenv("MADELEINE_GATE_PERSIST") ? atoi(getenv("MADELEINE_GATE_PERSIST")) : MDL_GATE_SP_PMODE;
     const int nshare = 8 / H;
     const int64_t per_share = (n_tt + nshare - 1) / nshare;
-    int pmode = pmode_env;
-    if (pmode == 1 && !gate_persist_pays(grid, 0.96)) pmode = 0;
-    if (pmode == 2 && !gate_persist_pays(grid, 0.96, GATE_PT)) pmode = 0;
+    const int pmode = sp_gate_fwd_pmode(grid);
     const int64_t pgrid = pmode == 1 ? grid / GATE_JT : pmode == 2 ? 8 * ((per_share + GATE_PT - 1) / GATE_PT) * GATE_JT : grid;
     const bool na3 = sp_nt_stages() == 3;   // sp_nt_mainloop3 (MADELEINE_SP_NT_STAGES, split_engine.hpp)
 #define MDL_GATE_FWD_SP1(DM, SAVE, PM)                                                                                                 \
@@ -649,3 +654,19 @@ extern "C" int mdl_abmil_attnpool_bwd_split(const void* E_img, int64_t e_rsb, co
     }
     return MDL_OK;
 }
+
+namespace mdl {
+// mdl_dispatch_plan (dispatch_plan.hip): the forward's persistence mode (mdl_abmil_gate_fwd_split) and the token splits of the dW
+// contraction (mdl_abmil_attnpool_bwd_split)
+int plan_gate_split(int product, int64_t T, int H, int64_t* o) {
+    if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
+    if (product == MDL_PLAN_GATE_SPLIT_FWD) {
+        o[MDL_PLAN_PERSIST] = sp_gate_fwd_pmode(xcd_head_grid((T + SPM - 1) / SPM, GATE_JT, H));
+        o[MDL_PLAN_SPLITS] = 1;
+        return MDL_OK;
+    }
+    const SpBwdWs L = sp_bwd_ws(T, H);
+    plan_splits(o, T, L.S, L.tps, SPK);
+    return MDL_OK;
+}
+}  // namespace mdl

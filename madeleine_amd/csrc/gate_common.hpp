@@ -200,6 +200,15 @@ static inline int splits_for(int64_t T, int tiles_per_split, int64_t slots = 768
 }
 static inline int gate_splits(int64_t T, int H) { return splits_for(T, 16 * H); }  // 4 k-tiles x 4 column tiles per head
 
+// mdl_dispatch_plan (dispatch_plan.hip): the split fields of a launcher's choice; EMPTY counts the splits s with s * tps >= T
+static inline void plan_splits(int64_t* o, int64_t T, int S, int64_t tps, int chunk) {
+    const int64_t used = tps > 0 ? (T + tps - 1) / tps : S;
+    o[MDL_PLAN_SPLITS] = S;
+    o[MDL_PLAN_TPS] = tps;
+    o[MDL_PLAN_EMPTY] = S > used ? S - used : 0;
+    o[MDL_PLAN_CHUNK] = chunk;
+}
+
 constexpr int DZ_ROWS = 256;  // token rows per workgroup
 // launches KERNEL<..., DM> for the run-time dropout mode dm (gate_drop_mode)
 #define MDL_DISPATCH_DM(dm, LAUNCH) \

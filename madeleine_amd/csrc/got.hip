@@ -13,6 +13,7 @@ namespace mdl {
     int launch_bwd_begin(const GotBatch&, hipStream_t);          \
     int launch_bwd_finish(const GotBatch&, hipStream_t);         \
     int64_t ws_floats(int, int, int);                            \
+    int plan(int, int, int, int64_t*);                           \
     }
 MDL_GOT_DECL(got1024)
 #undef MDL_GOT_DECL
@@ -21,6 +22,16 @@ constexpr int GOT_MAXD = 128;
 }  // namespace mdl
 
 using namespace mdl;
+
+namespace mdl {
+// mdl_dispatch_plan (dispatch_plan.hip): k cases of n tokens in one launch sequence (mdl_got_*; the batched entry points: the sum of the
+// problems' k and the largest n)
+int plan_got(int64_t k, int n, int cus, int64_t* o) {
+    if (k < 1 || n < 1 || k > 0x7fffffff) return MDL_E_ARG;
+    if (n > GOT_MAXN) return MDL_E_UNSUPPORTED;
+    return got1024::plan((int)k, n, cus, o);
+}
+}  // namespace mdl
 
 static int got_check(int k, int n, int d) {
     if (k < 0 || n < 0 || d < 1) return MDL_E_ARG;

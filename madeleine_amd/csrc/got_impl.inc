@@ -2070,7 +2070,17 @@ static int device_cus() {
     }
     return cus;
 }
-static bool split_sweeps(int K) { return GNW == 16 && 2 * K <= device_cus() && !getenv("MADELEINE_GOT_NOSPLIT"); }
+// size class of the launch chain for the largest n of a batch: 64 | 128 (one fused kernel), 192 | 256 (per-phase launches; the IPOT
+// sweeps of 192 on 12 x 3 plan registers per lane), 512 (the workspace-resident class, n > GOT_MAXN)
+static int got_class(int n) {
+    if (n <= 64) return 64;
+    if (n <= 128) return 128;
+    if (n > GOT_MAXN) return 512;
+    return (n <= 192 && GNW == 16 && !getenv("MADELEINE_GOT_NO192")) ? 192 : 256;
+}
+static bool split_sweeps(int K, int cus) { return GNW == 16 && 2 * K <= cus && !getenv("MADELEINE_GOT_NOSPLIT"); }
+static bool split_sweep_4k(int K, int cus) { return 4 * K <= cus; }   // both sweeps of a two-sweep step in ONE launch
+static bool half_products(int K, int cus) { return GNW == 16 && 2 * K <= cus && !getenv("MADELEINE_GOT_NO_HALF_PRODUCTS"); }
 template <class K3, class K4>
 static void launch_split(K3 k3, K4 k4, const GotBatch& B, int K, int n, int o, int mult, hipStream_t s) {
     auto go = [&](int blocks, int mode) {
@@ -2078,7 +2088,7 @@ static void launch_split(K3 k3, K4 k4, const GotBatch& B, int K, int n, int o, i
         else hipLaunchKernelGGL(k4, dim3(blocks), dim3(GNT), 0, s, B, o, mode);
     };
     if (mult == 1) go(2 * K, 0);
-    else if (4 * K <= device_cus()) go(4 * K, 1);
+    else if (split_sweep_4k(K, device_cus())) go(4 * K, 1);
     else {          // both branches would not be resident together: the Wasserstein sweep as its own launch
         go(2 * K, 2);
         go(2 * K, 0);
@@ -2087,12 +2097,12 @@ static void launch_split(K3 k3, K4 k4, const GotBatch& B, int K, int n, int o, i
 int launch_fwd_sweep(const GotBatch& B, int o, int mult, hipStream_t s) {
     const int K = batch_cases(B), n = batch_nmax(B);
     constexpr int R = 256 / GNW, R3 = 192 / GNW;
-    if (split_sweeps(K)) {
+    if (split_sweeps(K, device_cus())) {
         launch_split(got_fwd_sweep_split_kernel<R3 / 2, 3>, got_fwd_sweep_split_kernel<R / 2, 4>, B, K, n, o, mult, s);
         MDL_LAUNCH_CHECK();
         return MDL_OK;
     }
-    if (n <= 192 && GNW == 16 && !getenv("MADELEINE_GOT_NO192"))
+    if (got_class(n) == 192)
         hipLaunchKernelGGL((got_fwd_stage_kernel<R3, 3, 2>), dim3(mult * K), dim3(GNT), 0, s, B, o, mult);
     else
         hipLaunchKernelGGL((got_fwd_stage_kernel<R, 4, 2>), dim3(mult * K), dim3(GNT), 0, s, B, o, mult);
@@ -2102,13 +2112,13 @@ int launch_fwd_sweep(const GotBatch& B, int o, int mult, hipStream_t s) {
 int launch_bwd_sweep(const GotBatch& B, int o, int mult, hipStream_t s) {
     const int K = batch_cases(B), n = batch_nmax(B);
     constexpr int R = 256 / GNW, R3 = 192 / GNW;
-    if (split_sweeps(K)) {
+    if (split_sweeps(K, device_cus())) {
         launch_split(got_bwd_sweep_split_kernel<R3 / 2, 3>, got_bwd_sweep_split_kernel<R / 2, 4>, B, K, n, o, mult, s);
         MDL_LAUNCH_CHECK();
         return MDL_OK;
     }
     // accumulator rows in LDS (16-wave build): 2 of 12 (n <= 192), 7 of 16 (n <= 256); the 8-wave build keeps all of them in registers
-    if (n <= 192 && GNW == 16 && !getenv("MADELEINE_GOT_NO192"))
+    if (got_class(n) == 192)
         hipLaunchKernelGGL((got_bwd_sweep_kernel<R3, 3, MDL_GOT_HLR3>), dim3(mult * K), dim3(GNT), 0, s, B, o, mult);
     else
         hipLaunchKernelGGL((got_bwd_sweep_kernel<R, 4, (GNW == 16 ? MDL_GOT_HLR4 : 0)>), dim3(mult * K), dim3(GNT), 0, s, B, o, mult);
@@ -2117,12 +2127,12 @@ int launch_bwd_sweep(const GotBatch& B, int o, int mult, hipStream_t s) {
 }
 
 int launch_main(const GotBatch& B, hipStream_t s) {
-    const int K = batch_cases(B), n = batch_nmax(B);
-    if (n <= 64) {
+    const int K = batch_cases(B), c = got_class(batch_nmax(B));
+    if (c == 64) {
         hipLaunchKernelGGL((got_main_kernel<64 / GNW, 1>), dim3(2 * K), dim3(GNT), 0, s, B);
-    } else if (n <= 128) {
+    } else if (c == 128) {
         hipLaunchKernelGGL((got_main_kernel<128 / GNW, 2>), dim3(2 * K), dim3(GNT), 0, s, B);
-    } else if (n > GOT_MAXN) {  // big class: one launch per phase, plans in the workspace
+    } else if (c == 512) {  // big class: one launch per phase, plans in the workspace
         hipLaunchKernelGGL((got_fwd_stage_kernel<1, 8, 0, true>), dim3(2 * K), dim3(GNT), 0, s, B, 0, 2);
         for (int o = 0; o < GW_OUTER; ++o) {
             hipLaunchKernelGGL((got_fwd_stage_kernel<1, 8, 1, true>), dim3(K), dim3(GNT), 0, s, B, o, 1);
@@ -2134,7 +2144,7 @@ int launch_main(const GotBatch& B, hipStream_t s) {
         hipLaunchKernelGGL((got_fwd_stage_kernel<R, 4, 0>), dim3(2 * K), dim3(GNT), 0, s, B, 0, 2);
         // the C_gamma products by row halves while two workgroups per case still fit the device (no exchange between the halves, so
         // unlike the split sweeps nothing depends on residency; MADELEINE_GOT_NO_HALF_PRODUCTS=1: A/B switch)
-        const bool halves = GNW == 16 && 2 * K <= device_cus() && !getenv("MADELEINE_GOT_NO_HALF_PRODUCTS");
+        const bool halves = half_products(K, device_cus());
         for (int o = 0; o < GW_OUTER; ++o) {
             if (halves) hipLaunchKernelGGL((got_fwd_stage_kernel<R, 4, 4>), dim3(2 * K), dim3(GNT), 0, s, B, o, 2);
             else hipLaunchKernelGGL((got_fwd_stage_kernel<R, 4, 1>), dim3(K), dim3(GNT), 0, s, B, o, 1);
@@ -2150,12 +2160,12 @@ int launch_main(const GotBatch& B, hipStream_t s) {
 }
 
 int launch_bwd_begin(const GotBatch& B, hipStream_t s) {
-    const int K = batch_cases(B), n = batch_nmax(B);
-    if (n <= 64) {
+    const int K = batch_cases(B), c = got_class(batch_nmax(B));
+    if (c == 64) {
         hipLaunchKernelGGL((got_main_bwd_kernel<64 / GNW, 1>), dim3(2 * K), dim3(GNT), 0, s, B);
-    } else if (n <= 128) {
+    } else if (c == 128) {
         hipLaunchKernelGGL((got_main_bwd_kernel<128 / GNW, 2>), dim3(2 * K), dim3(GNT), 0, s, B);
-    } else if (n > GOT_MAXN) {  // big class
+    } else if (c == 512) {  // big class
         hipLaunchKernelGGL((got_bwd_stage_kernel<1, 8, 0, true>), dim3(K), dim3(GNT), 0, s, B, 0, 1);
         for (int o = GW_OUTER; o >= 0; --o) {
             hipLaunchKernelGGL((got_bwd_stage_kernel<1, 8, 1, true>), dim3(o >= 1 ? 2 * K : K), dim3(GNT), 0, s, B, o, o >= 1 ? 2 : 1);
@@ -2194,6 +2204,18 @@ int launch_bwd_finish(const GotBatch& B, hipStream_t s) {
 }
 
 int64_t ws_floats(int k, int n, int d) { return got_layout(k, n, d).g_cases; }
+
+// mdl_dispatch_plan (dispatch_plan.hip): the class, row-half products and split sweeps launch_main / launch_bwd_begin choose for K cases
+// of largest size n on a device of `cus` compute units
+int plan(int K, int n, int cus, int64_t* o) {
+    const int c = got_class(n);
+    const bool phased = c == 192 || c == 256;
+    o[MDL_PLAN_VARIANT] = c;
+    o[MDL_PLAN_PERSIST] = phased && half_products(K, cus) ? 1 : 0;
+    o[MDL_PLAN_EXTRA] = phased && split_sweeps(K, cus) ? (split_sweep_4k(K, cus) ? 2 : 1) : 0;
+    o[MDL_PLAN_SPLITS] = 1;
+    return MDL_OK;
+}
 
 }  // namespace GOT_NS
 }  // namespace mdl

@@ -177,10 +177,13 @@ __global__ __launch_bounds__(512) void linb_nt256_kernel(const bf16_t* __restric
 // (K = 512, N = 2048: 0.706 -> 0.655 ms, and beats the 128 x 256 x 32 kernel there), and costs on the long one (K = 2048, 2 column tiles:
 // 0.61 -> 0.67 ms: the 1-MiB A tile is re-read in sequence instead of side by side) -- so PER = 4 below 1024, 1 from there on.
 // MADELEINE_BF16_LIN_PERSIST=0 forces PER = 1 (A/B switch).
+static inline int linb_nt256_per(int Kc, int n_ct) {
+    static const bool persist = !(getenv("MADELEINE_BF16_LIN_PERSIST") && atoi(getenv("MADELEINE_BF16_LIN_PERSIST")) == 0);
+    return (persist && Kc < 1024 && n_ct % 4 == 0) ? 4 : 1;
+}
 static inline void linb_launch_nt256(hipStream_t s, const bf16_t* A, int64_t lda, const bf16_t* B, const float* bias, bf16_t* C, int64_t ldc,
                                      int64_t T, int Kc, int n_ct, int64_t tiles) {
-    static const bool persist = !(getenv("MADELEINE_BF16_LIN_PERSIST") && atoi(getenv("MADELEINE_BF16_LIN_PERSIST")) == 0);
-    const int per = (persist && Kc < 1024 && n_ct % 4 == 0) ? 4 : 1;
+    const int per = linb_nt256_per(Kc, n_ct);
     const dim3 grid((unsigned)(tiles / per));
     if (per == 4) hipLaunchKernelGGL(linb_nt256_kernel<4>, grid, dim3(512), 0, s, A, lda, B, bias, C, ldc, T, Kc, n_ct, (int)tiles);
     else if (bf16_lin_stages() == 3 || bf16_lin_stages() == 31) hipLaunchKernelGGL((linb_nt256_kernel<1, 3>), grid, dim3(512), 0, s, A, lda, B, bias, C, ldc, T, Kc, n_ct, (int)tiles);
@@ -415,6 +418,9 @@ static inline bool linb_use_q(int64_t T, int64_t Kc, int64_t n_out) {
     if (T < 4096 || (Kc % QK) != 0 || (n_out % QN) != 0) return false;
     return Kc >= 1024 || (Kc >= mink && (n_out / QN) % 4 == 0);
 }
+// the forward Y = X W^T (contraction K, N output columns) and the backward's dX = dY W (contraction N, K output columns) on that tile
+static inline bool linb_fwd_use_q(int64_t T, int64_t N, int64_t K) { return (N % BBN) == 0 && linb_use_q(T, K, N); }
+static inline bool linb_dx_use_q(int64_t T, int64_t N, int64_t K) { return (K % QN) == 0 && linb_use_q(T, N, K); }
 static inline bool linb_geom_fwd(int64_t N, int64_t K) { return N > 0 && K > 0 && N % 128 == 0 && K % BBK == 0 && N <= (1 << 20) && K <= (1 << 20); }
 static inline bool linb_geom_bwd(int64_t N, int64_t K) { return linb_geom_fwd(N, K); }
 
@@ -443,7 +449,7 @@ extern "C" int mdl_linear_fwd_bf16(const uint16_t* X, int64_t ldx, const float* 
     hipLaunchKernelGGL(linb_w_cast_kernel, dim3((unsigned)((N * K / 4 + 255) / 256)), dim3(256), 0, s, W, Wb, N * K);
     MDL_LAUNCH_CHECK();
     const bool wide = (N % BBN) == 0;
-    if (wide && linb_use_q(T, K, N)) {
+    if (linb_fwd_use_q(T, N, K)) {
         const int n_ct = (int)(N / QN);
         const int64_t tiles = ((T + QM - 1) / QM) * n_ct;
         if (tiles > 0x7fffffff) return MDL_E_UNSUPPORTED;
@@ -499,7 +505,7 @@ extern "C" int mdl_linear_bwd_bf16(const uint16_t* X, int64_t ldx, const float* 
     if (dX) {   // dX = dY W: NT with B = W^T rows [K][N]
         hipLaunchKernelGGL(linb_w_transpose_kernel, dim3((unsigned)(K / 32), (unsigned)(N / 32)), dim3(256), 0, s, W, WT, (int)N, (int)K);
         MDL_LAUNCH_CHECK();
-        if ((K % QN) == 0 && linb_use_q(T, N, K)) {
+        if (linb_dx_use_q(T, N, K)) {
             const int n_ct = (int)(K / QN);
             const int64_t tiles = ((T + QM - 1) / QM) * n_ct;
             if (tiles > 0x7fffffff) return MDL_E_UNSUPPORTED;
@@ -544,3 +550,27 @@ extern "C" int mdl_linear_bwd_bf16(const uint16_t* X, int64_t ldx, const float* 
     }
     return MDL_OK;
 }
+
+namespace mdl {
+// mdl_dispatch_plan (dispatch_plan.hip): the tiles (and persistence) of mdl_linear_fwd_bf16 / mdl_linear_bwd_bf16 and the token splits of
+// the backward's dW contraction
+int plan_linear_bf16(int product, int64_t T, int N, int K, int64_t* o) {
+    const bool bwd = product == MDL_PLAN_LINEAR_BF16_BWD;
+    if (N < 1 || K < 1) return MDL_E_ARG;
+    if (!(bwd ? linb_geom_bwd(N, K) : linb_geom_fwd(N, K))) return MDL_E_UNSUPPORTED;
+    if (!bwd) {
+        const bool q = linb_fwd_use_q(T, N, K);
+        o[MDL_PLAN_VARIANT] = q ? 256 : (N % BBN) == 0 ? 4 : 2;
+        o[MDL_PLAN_PERSIST] = q ? linb_nt256_per(K, N / QN) : 0;
+        o[MDL_PLAN_SPLITS] = 1;
+        return MDL_OK;
+    }
+    const bool dxq = linb_dx_use_q(T, N, K), q = linb_tn_use_q(T, N);
+    o[MDL_PLAN_EXTRA] = dxq ? 256 : 4;
+    o[MDL_PLAN_PERSIST] = dxq ? linb_nt256_per(N, K / QN) : 0;
+    o[MDL_PLAN_VARIANT] = q ? 256 : 128;
+    const LinbWs L = linb_ws(T, N, K);
+    plan_splits(o, T, L.S, L.tps, q ? TQK : TNK);
+    return MDL_OK;
+}
+}  // namespace mdl

@@ -497,3 +497,20 @@ extern "C" int mdl_linear_bwd(const float* X, int64_t ldx, const float* W, const
     }
     return MDL_OK;
 }
+
+namespace mdl {
+// mdl_dispatch_plan (dispatch_plan.hip): mdl_linear_bwd's kernel (the FMA kernel for few rows, the wide tile or the role-swapped tall
+// one) and the token splits of its dW contraction
+int plan_linear_fp32_bwd(int64_t T, int N, int K, int64_t* o) {
+    const int rc = lin_check(T, N, K);
+    if (rc) return rc;
+    if (T <= LIN_SMALL_T) {
+        o[MDL_PLAN_SPLITS] = 1;
+        return MDL_OK;
+    }
+    o[MDL_PLAN_VARIANT] = lin_wide(N) ? 1 : 2;
+    const int S = lin_splits_any(T, N, K);
+    plan_splits(o, T, S, lin_tps(T, S), LBK);
+    return MDL_OK;
+}
+}  // namespace mdl

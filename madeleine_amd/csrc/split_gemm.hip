@@ -632,3 +632,13 @@ extern "C" int mdl_split_gemm_tn(const void* A, int64_t a_rsb, const float* a_sc
     MDL_LAUNCH_CHECK();
     return lin_launch_reduce((const float*)ws, out, Mi, N, S, s);
 }
+
+namespace mdl {
+// mdl_dispatch_plan (dispatch_plan.hip): the token splits of mdl_split_gemm_tn
+int plan_split_tn(int64_t T, int Mi, int N, int64_t* o) {
+    if (Mi < 32 || (Mi % 32) || N < 32 || (N % 32)) return MDL_E_ARG;
+    const int S = sp_tn_splits(T, Mi, N);
+    plan_splits(o, T, S, sp_tn_tps(T, S), SPK);
+    return MDL_OK;
+}
+}  // namespace mdl
