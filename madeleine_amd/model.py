@@ -32,6 +32,7 @@ from .abmil import BatchedABMIL, activate
 
 HE_POSITION = 0
 PRE_DROPOUT_P = 0.1  # Model.py:354,358,362
+SUPPORTED_HEADS = (1, 2, 4, 8)
 
 
 class _PermuteFn(torch.autograd.Function):
@@ -81,6 +82,9 @@ class ABMILEmbedder(nn.Module):
         self.pre_attention_params = pre_attention_params
         self.attention_params = attention_params
         self.n_heads = attention_params['params']["n_heads"]
+        if self.n_heads not in SUPPORTED_HEADS:
+            # every encoder kernel (pooling, gates, the 512*H-wide LayerNorm-GELU-Dropout) is instantiated for these head counts only
+            raise ValueError(f"n_heads must be one of {SUPPORTED_HEADS} (got {self.n_heads!r})")
         self._build_pre_attention_params(params=pre_attention_params)
         if attention_params is not None:
             self._build_attention_params(attn_model=attention_params['model'], params=attention_params['params'])

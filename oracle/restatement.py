@@ -417,9 +417,10 @@ def random_keep_masks(bm: int, n: int, n_heads: int, gen: torch.Generator):
 
 def pretrain_step_loss(feats: torch.Tensor, labels: torch.Tensor, sd: Params, modalities: Sequence[str],
                        temperature: float = 0.001, symmetric: bool = True, use_got: bool = False,
-                       local_weight: float = 1.0, stain_encoding: bool = False, pre_keep=None, gate_keep=None):
+                       local_weight: float = 1.0, stain_encoding: bool = False, pre_keep=None, gate_keep=None,
+                       n_heads: int = 4):
     """fwd + losses of one step (zero_grad/backward/AdamW are the caller's): returns (loss, flag, embs)."""
-    embs, toks = madeleine_forward_train(feats, sd, modalities, stain_encoding=stain_encoding,
+    embs, toks = madeleine_forward_train(feats, sd, modalities, n_heads, stain_encoding=stain_encoding,
                                          pre_keep=pre_keep, gate_keep=gate_keep)
     g = lambda a, b, symmetric=False: info_nce(a, b, temperature, symmetric)
     loc = (lambda a, b, subsample=None: got(a, b, subsample)) if use_got else None

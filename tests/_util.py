@@ -19,8 +19,8 @@ def t(shape, key, lo=-1.0, hi=1.0):
     return torch.from_numpy(recipe.uniform(shape, key, lo, hi))
 
 
-def recipe_params(n_mod, d_in, tag, stain_encoding=False, requires_grad=False):
-    shapes = R.param_shapes(n_mod, d_in, 4, stain_encoding)
+def recipe_params(n_mod, d_in, tag, stain_encoding=False, requires_grad=False, n_heads=4):
+    shapes = R.param_shapes(n_mod, d_in, n_heads, stain_encoding)
     sd = {k: torch.from_numpy(v) for k, v in recipe.state_dict_recipe(shapes, tag).items()}
     if requires_grad:
         for v in sd.values():

@@ -112,3 +112,19 @@ def test_plan_rejects_what_the_launchers_reject():
     out[3] = -7
     assert call(3, 5000, 4, 0, n=3) == 0 and out[2] == 2 and out[3] == -7   # n_out caps what is written
     assert lib.mdl_dispatch_plan(3, 100, 4, 0, 256, None, 7) == -1
+
+
+@defaults_only
+def test_head_count_cases_take_their_branches():
+    """The gate and split-TN cases of tests/test_heads_gpu.py (1, 2 and 8 heads) reach the branches they are named after on a 256-CU
+    device; the GPU tests assert the same with the device's own CU count."""
+    from tests.test_heads_gpu import GATE_CASES, TN_CASES
+    for case in GATE_CASES:
+        _mode, T, H, _p, plans = case.values
+        for product, want in plans.items():
+            p = _plan(product, T, H)
+            assert {k: p[k] for k in want} == want, (case.id, product, p)
+    for case in TN_CASES:
+        T, Mi, N, want = case.values
+        p = _plan("split_tn", T, Mi, N)
+        assert {k: p[k] for k in want} == want, (case.id, p)

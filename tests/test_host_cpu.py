@@ -51,6 +51,35 @@ def test_state_dict_contract(stain_encoding):
     assert n == (4_996_740 + 16_544 if stain_encoding else 4_996_740)   # SURVEY.md section 8(a) row A0 [probed]
 
 
+@pytest.mark.parametrize("H", [1, 2, 8])
+def test_state_dict_contract_other_head_counts(H):
+    """MADELEINE(n_heads=H) has the reference's state_dict keys, order and shapes (heads.npz holds the reference's list)."""
+    from madeleine_amd import MADELEINE
+    g = golden("heads")
+    M, D = int(g["shape"][1]), int(g["shape"][3])
+    cfg = _cfg(MODS5[:M], D)
+    cfg.n_heads = H
+    shapes = [(k, tuple(v.shape)) for k, v in MADELEINE(cfg).state_dict().items()]
+    ref = [(str(k), tuple(int(d) for d in s if d >= 0)) for k, s in zip(g[f"h{H}/state_keys"], g[f"h{H}/state_shapes"])]
+    assert shapes == ref
+    assert dict(shapes) == R.param_shapes(M, D, H)
+
+
+@pytest.mark.parametrize("H", [3, 16])
+def test_unsupported_head_counts_raise_at_construction(H):
+    """The kernels are instantiated for 1, 2, 4 and 8 heads: any other count fails when the model is built, naming those values."""
+    from madeleine_amd import MADELEINE
+    from madeleine_amd.model import ABMILEmbedder
+    cfg = _cfg(MODS5[:2])
+    cfg.n_heads = H
+    with pytest.raises(ValueError, match=r"n_heads must be one of \(1, 2, 4, 8\)"):
+        MADELEINE(cfg)
+    with pytest.raises(ValueError, match="got %d" % H):
+        ABMILEmbedder({"input_dim": 64, "hidden_dim": 512},
+                      {"model": "ABMIL", "params": {"input_dim": 512, "hidden_dim": 512, "dropout": True, "activation": "softmax",
+                                                    "n_heads": H, "n_classes": 1}})
+
+
 def test_no_cpu_fallback_and_errors():
     from madeleine_amd import BatchedABMIL, InfoNCE, MADELEINE
     m = MADELEINE(_cfg(MODS5[:2]))

@@ -622,7 +622,7 @@ def test_three_views_gradients_vs_oracle(dev):
         assert float((p.grad.cpu() - ref_g).norm()) <= TOL * float(ref_g.norm()) + 1e-5 * top, k
 
 
-def _oracle_ragged_step(bags, lens, sd, mods, labels, temperature, use_got, local_weight, n_loss=256):
+def _oracle_ragged_step(bags, lens, sd, mods, labels, temperature, use_got, local_weight, n_loss=256, n_heads=4):
     """The reference run PER BAG (batch 1 -- SURVEY.md section 7 'Ragged bags': the oracle of config 5), with the train branch's
     stain-index quirk r // B, then the reference-shaped dicts and calculate_losses.  sd tensors require grad."""
     B, M = len(bags), len(bags[0])
@@ -631,7 +631,7 @@ def _oracle_ragged_step(bags, lens, sd, mods, labels, temperature, use_got, loca
         for m in range(M):
             sidx = (b * M + m) // B
             x = torch.cat([bags[b][m], sd["embedding.weight"][sidx].expand(lens[b][m], -1)], dim=-1).unsqueeze(0)
-            out = R.abmil_embed(x, sd)
+            out = R.abmil_embed(x, sd, n_heads)
             slides.append(torch.nn.functional.linear(out["slide"].reshape(1, -1), sd["projector.weight"], sd["projector.bias"]))
             toks.append(torch.nn.functional.linear(out["tokens"].reshape(1, lens[b][m], -1)[:, :n_loss],
                                                    sd["token_projector.weight"], sd["token_projector.bias"]))

@@ -238,3 +238,35 @@ def test_full_step():
     loss_g.backward()
     assert abs(float(loss_g) - float(g["global/loss"])) < 1e-5 * abs(float(g["global/loss"]))
     _grads_match(g, sd2, prefix="global/", tol=2e-4)
+
+
+@pytest.mark.parametrize("H", [1, 2, 8])
+def test_other_head_counts(H):
+    """n_heads = 1 (the reference's unsqueeze branch, Model.py:395-398), 2 and 8 against the imported reference (heads.npz): the
+    forward, the embedder's attention and head interleave, the eval / encode_he branches and one full step (InfoNCE + GOT)."""
+    g = golden("heads")
+    B, M, N, D = (int(x) for x in g["shape"])
+    mods = MODS5[:M]
+    pre = f"h{H}/"
+    labels = torch.from_numpy(g["labels"])
+    feats = t((B, M, N, D), f"hd{H}:feats:{int(g[pre + 'trial'])}")    # first well-conditioned recipe key, see oracle/gen_golden.py
+    sd = recipe_params(M, D, f"whd{H}", requires_grad=True, n_heads=H)
+    embs, toks = R.madeleine_forward_train(feats, sd, mods, n_heads=H)
+    for k in mods:
+        assert embs[k].shape == g[f"{pre}emb/{k}"].shape
+        assert rel_err(embs[k], g[f"{pre}emb/{k}"]) < TOL
+        assert rel_err(toks[k][:, :3], g[f"{pre}tok_head/{k}"]) < TOL
+    out = R.abmil_embed(feats.view(B * M, N, D), sd, n_heads=H)
+    assert out["slide"].shape == g[pre + "slide"].shape and rel_err(out["slide"], g[pre + "slide"]) < TOL
+    assert max_rel(out["raw"], g[pre + "raw"]) < 1e-4
+    assert rel_err(out["tokens"][:1, :2], g[pre + "tokens_head"]) < TOL
+    with torch.no_grad():
+        assert rel_err(R.encode_he(feats[:, 0], sd, n_heads=H), g[pre + "encode_he"]) < TOL
+        assert rel_err(R.madeleine_forward_eval(feats[:, :1], sd, mods, n_heads=H)["HE"], g[pre + "eval/HE"]) < TOL
+        assert max_rel(R.abmil_embed(feats[:, 0], sd, n_heads=H)["raw"], g[pre + "att/raw"]) < 1e-4
+    torch.manual_seed(11)
+    loss, flag, _ = R.pretrain_step_loss(feats, labels, sd, mods, 0.001, True, use_got=True, n_heads=H)
+    loss.backward()
+    assert flag
+    assert abs(float(loss) - float(g[pre + "loss"])) < 1e-5 * abs(float(g[pre + "loss"]))
+    _grads_match(g, sd, prefix=pre, tol=2e-4)
