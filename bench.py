@@ -2,6 +2,7 @@
 """bench.py -- slides/sec of the MADELEINE cross-stain pretrain step on MI355X (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W           (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W --full    (+ every secondary measurement below)
 
 A "step" = zero_grad + encoder fwd + losses + bwd + AdamW step, train mode (dropout on), on DEVICE-RESIDENT
 synthetic bags: per rank B=32 slides x M stains x N=4096 patches x D=512 fp32
@@ -11,15 +12,19 @@ global InfoNCE), the configuration the metric is quoted on.  Rank 0 prints ONE J
 `python bench.py --gpus N` with no launcher in the environment re-executes itself as N ranks under torch.distributed.run (loopback
 rendezvous); under a launcher (RANK / WORLD_SIZE set) it joins the group it was given.
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and reports; nothing else is measured.
 Output: rank 0 prints a `BENCH_DETAIL {...}` line (the full record: secondary legs, variants, provenance; also written to
-gpurun_out/bench_detail.json) and then, as the LAST stdout line, ONE compact JSON line (<= 4 KB -- `compact_line`) with the contract keys plus
+bench_detail.json in the run's output directory) and then, as the LAST stdout line, ONE compact JSON line (<= 4 KB -- `compact_line`) with
+the contract keys plus
   roofline        -- A3 softmax-pool forward kernel (the HBM-bound kernel north_star targets at >= 60 %): algorithmic bytes
                      (8,208 B/token + 8 KiB/bag) / the dispatches' own start-stop HIP events inside the timed region; `traffic` from
-                     two in-run rocprofv3 PMC passes.
+                     two in-run rocprofv3 PMC passes under --full (a plain run quotes the committed passes).
+--full adds, after the timed steps (--no-cpu-baseline / --no-bf16-leg / --no-pmc / --no-extra-legs leave parts out):
   cpu_baseline    -- the CPU oracle (oracle/restatement.py, kind "port") timed on this box's host cores on the full 32-slide step
                      (rank 0, N=1 only).
   kernels         -- every kernel family of the headline step: [ms per call, fraction of peak] -- the dense MFMA peak of the instruction
-                     it runs on (split mode: 3 fp16 MFMA FLOPs per algorithmic fp32 FLOP against 2.5 PFLOP/s) or the 8 TB/s HBM peak.
+                     it runs on (split mode: 3 fp16 MFMA FLOPs per algorithmic fp32 FLOP against 2.5 PFLOP/s) or the 8 TB/s HBM peak
+                     (a profiled pass of its own).
   roofline_mfma   -- A2 gate kernels (fwd + dX + dW), the time-dominant contractions.
   secondary_ms_per_step -- step times of the secondary legs (bf16 mode, config 3, one rank of configs 4 / 5, PCIe-inclusive feed).
 
@@ -710,6 +715,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--eval-mode", action="store_true", help="dropout off (parity-mode timing; not the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every secondary measurement: the profiled per-kernel pass, the CPU baseline, "
+                         "the in-run PMC passes, the other precisions / GEMM modes, the PCIe-inclusive, power and secondary-config legs. "
+                         "Off by default: a plain run does only what `value` and `ms_per_step` need")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--host-input", action="store_true",
                     help="batches start in host memory and go through the pinned double-buffered H2D stager "
@@ -889,9 +898,9 @@ def main():
             pool_parts = {"pool_partial_ms": round(sum(r[0] for r in rep) / len(rep), 4),
                           "pool_combine_ms": round(sum(r[1] for r in rep) / len(rep), 4),
                           "first_begin_to_last_end_ms": round(sum(r[2] for r in rep) / len(rep), 4)}
-    # profiled pass (not part of `value`): every C-ABI launch between HIP events, the fused backward in its two phases
+    # profiled pass (--full; not part of `value`): every C-ABI launch between HIP events, the fused backward in its two phases
     prof, work, prof_steps, profiled_ms = {}, {}, max(3, min(5, a.steps)), None
-    if not os.environ.get("BENCH_NO_TIMER"):
+    if a.full and not os.environ.get("BENCH_NO_TIMER"):
         MF.TIMER = MF.KernelTimer()
         tp = time.perf_counter()
         for _ in range(prof_steps):
@@ -900,11 +909,11 @@ def main():
         profiled_ms = 1e3 * (time.perf_counter() - tp) / prof_steps
         prof, work = MF.TIMER.report(), MF.TIMER.work()
         MF.TIMER = None
-        if "pool_fwd" in prof_pool:
-            prof["pool_fwd"] = prof_pool["pool_fwd"]      # the roofline kernel: events of the timed region itself
+    if "pool_fwd" in prof_pool:
+        prof["pool_fwd"] = prof_pool["pool_fwd"]      # the roofline kernel: events of the timed region itself
     final_loss = float(loss.detach())
     bf16_leg = None
-    if a.precision == "float32" and world == 1 and not a.no_bf16_leg and host_iter is None:
+    if a.full and a.precision == "float32" and world == 1 and not a.no_bf16_leg and host_iter is None:
         # short secondary measurement of the bf16 mode (same model, same batch); reported beside, never as, `value`
         nb = max(3, min(10, a.steps))
         eb, lb, pb, wb, _ = measure_leg(MF, lambda: step(True), nb)
@@ -914,7 +923,7 @@ def main():
                     "final_loss": float(lb.detach()), "kernel_ms": {k: round(v[0], 4) for k, v in pb.items()},
                     "kernel_roofline": kernel_rooflines(pb, wb, "bfloat16")}
     f32_leg = None
-    if a.precision == "float32" and world == 1 and not a.no_bf16_leg and host_iter is None and MF.gemm_mode() == "split":
+    if a.full and a.precision == "float32" and world == 1 and not a.no_bf16_leg and host_iter is None and MF.gemm_mode() == "split":
         # the same step with every contraction on the exact-fp32 matrix-core kernels (v_mfma_f32_32x32x2_f32): the 'fp32' GEMM mode
         MF.set_gemm_mode("fp32")
         try:
@@ -928,7 +937,7 @@ def main():
             MF.TIMER = None
             MF.set_gemm_mode("split")
     g2_leg = None
-    if a.precision == "float32" and world == 1 and not a.no_bf16_leg and host_iter is None and MF.gemm_mode() == "split":
+    if a.full and a.precision == "float32" and world == 1 and not a.no_bf16_leg and host_iter is None and MF.gemm_mode() == "split":
         # opt-in variant: backward products with two matrix terms (the non-gradient operand at its hi plane, functional.set_gradient_terms);
         # same forward bits, gradients at ~2^-12 relative.  Reported beside, never as, `value`.
         MF.set_gradient_terms(2)
@@ -946,7 +955,7 @@ def main():
     # batches, as DataLoader(pin_memory=True) delivers them -- through data.DevicePrefetcher (side-stream H2D two batches ahead,
     # the step waits on the upload event only).  Never `value`.
     host_leg = None
-    if a.precision == "float32" and world == 1 and not dist_on and not a.no_extra_legs and host_iter is None and not ragged:
+    if a.full and a.precision == "float32" and world == 1 and not dist_on and not a.no_extra_legs and host_iter is None and not ragged:
         from madeleine_amd.data import DevicePrefetcher
         pool = [torch.randn(B, M, N, Dm).pin_memory() for _ in range(3)]
 
@@ -980,14 +989,14 @@ def main():
     # socket power / shader clock over the same step loop (hwmon reads from a sampling thread; outside the timed region, after the
     # secondary legs of this model so that ~3 s at the power cap do not precede any of them)
     power = None
-    if world == 1 and not dist_on and host_iter is None and not a.no_extra_legs:
+    if a.full and world == 1 and not dist_on and host_iter is None and not a.no_extra_legs:
         with PowerSampler() as ps:
             for _ in range(max(120, a.steps)):   # ~3 s: the hwmon averages update a few times per second
                 step()
             fence()
         power = ps.summary(skip_s=1.0)
     c3_leg = infer_leg = c4_leg = c3ap_leg = c4ap_leg = c5_leg = c5b_leg = c3skip_leg = None
-    if a.config == "c2" and a.precision == "float32" and world == 1 and not a.no_extra_legs and host_iter is None:
+    if a.full and a.config == "c2" and a.precision == "float32" and world == 1 and not a.no_extra_legs and host_iter is None:
         # free the c2 working set first (the c3 step keeps ~60 GiB live)
         feats = data = None
         torch.cuda.empty_cache()
@@ -1065,7 +1074,8 @@ def main():
             ach = alg / (ms * 1e-3) / 1e9
             traffic, traffic_src = None, "not collected (only for c2 at N=1)"
             if a.config == "c2" and world == 1 and a.precision == "float32":
-                if not a.no_pmc:
+                traffic_src = "not collected (in-run passes only under --full without --no-pmc)"
+                if a.full and not a.no_pmc:
                     # the step pools from the split image of E in the split GEMM mode (same bytes): measure that instantiation
                     traffic, traffic_src = measure_pool_traffic(image=MF.gemm_mode() == "split")
                 if traffic is None:
@@ -1126,7 +1136,8 @@ def main():
         out["kernel_calls_per_step"] = {k: v[1] // (min(a.steps, 64) if k == "pool_fwd" and prof_pool else prof_steps) for k, v in prof.items()}
         out["kernel_ms_source"] = ("pool_fwd: the dispatches' start / stop HIP events inside the timed region; all other kernels: a separate profiled "
                                    "pass of %d steps after it (%s ms/step with per-launch events and the backward in two phases)"
-                                   % (prof_steps, "n/a" if profiled_ms is None else "%.3f" % profiled_ms))
+                                   % (prof_steps, "n/a" if profiled_ms is None else "%.3f" % profiled_ms)) if a.full else \
+            "pool_fwd: the dispatches' start / stop HIP events inside the timed region; other kernels: --full only"
         if power is not None:
             out["power_clock"] = power
         out["kernel_roofline"] = kernel_rooflines(prof, work, a.precision, MF.gemm_mode())
@@ -1159,7 +1170,7 @@ def main():
             out["c5_rank_emulation"] = c5_leg
         if c5b_leg is not None:
             out["c5_rank_emulation_bf16"] = c5b_leg
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 nb = min(a.cpu_sample, B)
                 out["cpu_baseline"] = cpu_baseline(nb, M, N, Dm, use_got, steps=1 if nb >= 16 else 2)

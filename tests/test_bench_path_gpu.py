@@ -553,6 +553,39 @@ def test_bench_gpus_2_without_a_launcher_prints_one_valid_line():
     assert out["config"]["grad_sync"] == "flat_all_reduce"
 
 
+def test_bench_plain_run_measures_only_the_headline_and_full_adds_the_rest():
+    """A plain `bench.py` run reports the timed steps and nothing that needs runs of its own (no profiled per-kernel pass, CPU baseline or
+    secondary legs); `--full` adds them.  One GPU, 4 slides per step (--slides), the contract line and the detail record of both."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--slides", "4",
+                            *extra], env=env, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = r.stdout.rstrip().splitlines()
+        assert lines[-1].startswith("{") and sum(ln.startswith("{") for ln in lines) == 1, r.stdout[-2000:]
+        detail = [ln for ln in lines if ln.startswith("BENCH_DETAIL {")]
+        assert len(detail) == 1
+        return json.loads(lines[-1]), json.loads(detail[0][len("BENCH_DETAIL "):])
+
+    legs = ("bf16_mode", "fp32_mfma_mode", "grad_terms2_mode", "host_input_mode", "power_clock", "c3_mode", "inference_mode")
+    out, det = run()
+    assert {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "roofline"} <= set(out)
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["steps"] == 3 and out["warmup"] == 1
+    assert out["config"]["workload"].startswith("REDUCED") and out["roofline"]["launches"] > 0
+    assert not {"cpu_baseline", "kernels", "roofline_mfma", "secondary_ms_per_step"} & set(out)
+    assert not set(legs) & set(det) and set(det["kernel_ms"]) == {"pool_fwd"}
+
+    out, det = run("--full", "--no-cpu-baseline", "--no-pmc", "--no-extra-legs")
+    assert {"kernels", "roofline_mfma"} <= set(out) and "cpu_baseline" not in out
+    assert "bf16_mode" in det and len(det["kernel_ms"]) > 1 and "gate_fwd" in det["kernel_ms"]
+
+
 def test_bench_gpus_8_config3_gloo_ranks_with_empty_stain_shards():
     """the command the first 8-GPU run will use -- `python bench.py --gpus 8 --config c3` -- as 8 gloo ranks, one
     per GPU (4 slides per rank through --slides; the RCCL run of the same command has 32 slides each).  Needs 8 GPUs: eight ranks plus
@@ -579,7 +612,7 @@ def test_bench_gpus_8_config3_gloo_ranks_with_empty_stain_shards():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["MADELEINE_DIST_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--config", "c3", "--slides", "4", "--label-seed", str(seed),
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra-legs", "--no-pmc", "--no-bf16-leg"],
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra-legs", "--no-pmc", "--no-bf16-leg"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

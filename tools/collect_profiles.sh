@@ -16,7 +16,7 @@ run() {  # name, summary-top-n, rocprof args..., -- command
     { echo "# $TAG $name: rocprofv3 $*" | sed "s#$R/##g"; python $R/tools/rocpd_summary.py /tmp/prof_$name/*/*.db $top; } > $OUT/${TAG}_$name.txt 2>&1
     rm -rf /tmp/prof_$name
 }
-B="--no-cpu-baseline --no-bf16-leg --no-pmc --no-extra-legs"
+B="--full --no-cpu-baseline --no-bf16-leg --no-pmc --no-extra-legs"
 if [ $WHAT = all ] || [ $WHAT = bench ]; then
 run bench_c2_kernel_stats 40 --kernel-trace --stats -d /tmp/prof_bench_c2_kernel_stats -- python $R/bench.py --steps 3 --warmup 1 $B
 run bench_c2_bf16_kernel_stats 45 --kernel-trace --stats -d /tmp/prof_bench_c2_bf16_kernel_stats -- python $R/bench.py --steps 3 --warmup 1 $B --precision bfloat16
