@@ -56,7 +56,7 @@ const char* mdl_version(void);
 /* ABI revision of this header: bumped whenever an entry point's argument list changes.  A binding compares
  * mdl_abi_version() with the MDL_ABI_VERSION it was written against BEFORE calling anything else, so that a stale
  * shared object fails loudly instead of being called with shifted arguments. */
-#define MDL_ABI_VERSION 25
+#define MDL_ABI_VERSION 26
 int mdl_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -152,6 +152,27 @@ int mdl_abmil_pool_view_fwd(const float* E, int64_t ldE, const float* scores, fl
 int mdl_abmil_pool_view_bwd(const float* E, int64_t ldE, const float* scores, const float* pooled, const float* stat_m,
                             const float* stat_l, const float* d_pooled, float* dE, float* d_scores, int64_t n_bags, int64_t N,
                             const int32_t* token_idx, int64_t n_idx, int H, void* stream);
+
+/* Ragged views (ABI 26): the same two half-bag views on PACKED bags of unequal length (MADELEINE.forward_ragged with n_views = 3).
+ * perm int32 [T]: absolute rows of the packed E / scores, each bag's rows shuffled within its own range; vcu int64 [2*n_bags + 1]:
+ * prefix over positions in perm -- segment s = 2*b + v (view v in {0, 1} of bag b) is the rows perm[vcu[s] .. vcu[s+1]).  With the
+ * reference's per-bag draw (idx = shuffle(arange(N_b)), mid = N_b // 2) view 0 is idx[:mid], view 1 idx[mid:].  pooled [2*n_bags, H*512]
+ * and stat_m, stat_l [2*n_bags, H] are in segment order.  An empty segment (a 1-token bag's first view) pools to exact zeros and gets
+ * zero gradients.  max_view_len >= every segment's length (it sizes the grid); ws: mdl_abmil_pool_ws_bytes(2*n_bags, max_view_len, H).
+ * Every perm entry must be a row of E (< T) and perm a permutation of the rows it covers.  Bags of any length >= 1 take part (an absent
+ * stain's 2-token zero bag included: the caller decides which outputs a loss reads).  Backward: as mdl_abmil_pool_view_bwd, it
+ * ACCUMULATES into dE and / or d_scores (either may be NULL; d_scores == NULL does not read E); the segments write disjoint rows. */
+int mdl_abmil_pool_rview_fwd(const float* E, int64_t ldE, const float* scores, float* pooled, float* stat_m, float* stat_l,
+                             int64_t n_bags, const int32_t* perm, const int64_t* vcu, int64_t max_view_len, int H, void* ws, void* stream);
+int mdl_abmil_pool_rview_bwd(const float* E, int64_t ldE, const float* scores, const float* pooled, const float* stat_m,
+                             const float* stat_l, const float* d_pooled, float* dE, float* d_scores, int64_t n_bags, const int32_t* perm,
+                             const int64_t* vcu, int64_t max_view_len, int H, void* stream);
+int mdl_abmil_pool_rview_fwd_bf16(const uint16_t* E, int64_t ldE, const float* scores, float* pooled, float* stat_m, float* stat_l,
+                                  int64_t n_bags, const int32_t* perm, const int64_t* vcu, int64_t max_view_len, int H, void* ws,
+                                  void* stream);
+int mdl_abmil_pool_rview_bwd_bf16(const uint16_t* E, int64_t ldE, const float* scores, const float* pooled, const float* stat_m,
+                                  const float* stat_l, const float* d_pooled, uint16_t* dE, float* d_scores, int64_t n_bags,
+                                  const int32_t* perm, const int64_t* vcu, int64_t max_view_len, int H, void* stream);
 
 /* Fused backward of A2 + A3 ("abmil_attnpool_bwd").  Call sequence:
  *   1. mdl_abmil_pool_bwd(..., dE = NULL, ...)   -> d_scores only (one read of E; dE may be NULL in that call)

@@ -13,7 +13,7 @@ from . import _build
 
 _LOCK = threading.Lock()
 _LIB = None
-ABI_VERSION = 25   # == MDL_ABI_VERSION of include/madeleine_amd.h this file's SIGNATURES were written against
+ABI_VERSION = 26   # == MDL_ABI_VERSION of include/madeleine_amd.h this file's SIGNATURES were written against
 
 c_f = ctypes.c_void_p  # float* (device)
 c_p = ctypes.c_void_p
@@ -45,6 +45,10 @@ SIGNATURES = {
     "mdl_abmil_pool_view_bwd": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i64, c_p, i64, i32, c_p]),
     "mdl_abmil_pool_view_fwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, i64, i64, c_p, i64, i32, c_p, c_p]),
     "mdl_abmil_pool_view_bwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i64, c_p, i64, i32, c_p]),
+    "mdl_abmil_pool_rview_fwd": (i32, [c_f, i64, c_f, c_f, c_f, c_f, i64, c_p, c_p, i64, i32, c_p, c_p]),
+    "mdl_abmil_pool_rview_bwd": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, c_p, c_p, i64, i32, c_p]),
+    "mdl_abmil_pool_rview_fwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, i64, c_p, c_p, i64, i32, c_p, c_p]),
+    "mdl_abmil_pool_rview_bwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, c_p, c_p, i64, i32, c_p]),
     "mdl_ln_gelu_drop_fwd": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, f32, u64, c_p, c_p]),
     "mdl_ln_gelu_drop_bwd_ws_bytes": (i64, [i64, i32]),
     "mdl_ln_gelu_drop_bwd": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, u64, c_p, c_p, c_p]),

@@ -73,15 +73,22 @@ constexpr int POOL_CHUNK = 128;  // tokens per forward workgroup
 constexpr int POOL_BWD_TOKENS = 128;  // tokens per backward workgroup (4 waves)
 
 struct BagSpan {
-    int64_t start, len;
+    int64_t start, len, off;   // off: first position of the segment in the index list (views)
 };
 // A "view" (intra-modality half-bag views, reference Model.py:419-440) is a dense bag restricted to the token index list
 // idx[0..n_idx): logical token i of bag b is the physical row b*N + idx[i]; the same list for every bag.
-__device__ __forceinline__ BagSpan bag_span(int b, int64_t N, const int64_t* cu, int64_t n_idx = -1) {
+// A ragged view (idx_cu: an index list together with cu) is segment b of a packed permutation: logical token i is the ABSOLUTE row
+// idx[cu[b] + i], i < cu[b+1] - cu[b] (row base 0) -- segments 2k, 2k+1 are the two halves of bag k, each bag's rows shuffled in place.
+__device__ __forceinline__ BagSpan bag_span(int b, int64_t N, const int64_t* cu, int64_t n_idx = -1, bool idx_cu = false) {
     BagSpan s;
+    s.off = 0;
     if (n_idx >= 0) {
         s.start = (int64_t)b * N;
         s.len = n_idx;
+    } else if (idx_cu && cu) {
+        s.start = 0;
+        s.off = cu[b];
+        s.len = cu[b + 1] - s.off;
     } else if (cu) {
         s.start = cu[b];
         s.len = cu[b + 1] - s.start;
@@ -118,14 +125,14 @@ __global__ __launch_bounds__(H * 128) POOL_FWD_ATTR void pool_partial_kernel(con
     __shared__ int32_t tok_s[IDX ? POOL_CHUNK : 1];   // physical token of each logical token of the chunk (views)
 
     const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
-    const BagSpan sp = bag_span(b, N, cu, IDX ? n_idx : -1);
+    const BagSpan sp = bag_span(b, N, cu, IDX ? n_idx : -1, IDX);
     const int64_t t0 = (int64_t)chunk * POOL_CHUNK;
     if (t0 >= sp.len) return;  // block-uniform
     const int nt = (int)((sp.len - t0 < POOL_CHUNK) ? (sp.len - t0) : POOL_CHUNK);
 
     // ---- chunk softmax statistics: thread tid holds score (t = tid / H, c = tid % H) ----------
     const int st = tid / H, sc = tid % H;
-    const int64_t prow = (st < nt) ? (IDX ? (int64_t)idx[t0 + st] : t0 + st) : 0;
+    const int64_t prow = (st < nt) ? (IDX ? (int64_t)idx[sp.off + t0 + st] : t0 + st) : 0;
     if (IDX && sc == 0 && st < nt) tok_s[st] = (int32_t)prow;
     const float s = (st < nt) ? scores[(sp.start + prow) * H + sc] : (LIN ? 0.f : -INFINITY);
 
@@ -288,7 +295,7 @@ __global__ __launch_bounds__(256) POOL_BWD_ATTR void pool_bwd_kernel(const TE* _
                                                        const float* __restrict__ e_scale = nullptr) {
     const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float inv = e_scale ? 1.f / e_scale[0] : 1.f;
-    const BagSpan sp = bag_span(b, N, cu, IDX ? n_idx : -1);
+    const BagSpan sp = bag_span(b, N, cu, IDX ? n_idx : -1, IDX);
     const int64_t t0 = (int64_t)chunk * POOL_BWD_TOKENS;
     if (t0 >= sp.len) return;
     const int nt = (int)((sp.len - t0 < POOL_BWD_TOKENS) ? (sp.len - t0) : POOL_BWD_TOKENS);
@@ -319,7 +326,7 @@ __global__ __launch_bounds__(256) POOL_BWD_ATTR void pool_bwd_kernel(const TE* _
     }
 
     for (int t = wave; t < nt; t += 4) {
-        const int64_t row = sp.start + (IDX ? (int64_t)idx[t0 + t] : t0 + t);
+        const int64_t row = sp.start + (IDX ? (int64_t)idx[sp.off + t0 + t] : t0 + t);
         float w[H], dw[H];
 #pragma unroll
         for (int c = 0; c < H; ++c) w[c] = LIN ? scores[row * H + c] : expf(scores[row * H + c] - m[c]) * rl[c];
@@ -526,6 +533,81 @@ static int pool_view_bwd_launch(const TE* E, int64_t ldE, const float* scores, c
         MDL_LAUNCH_CHECK();
     });
     return MDL_OK;
+}
+
+// Ragged views: segment s = 2*bag + v is perm[vcu[s] .. vcu[s+1]) (absolute rows of the packed E / scores); pooled, stat_m, stat_l are
+// [2*n_bags, ...] in segment order.  The same kernels as the dense views with the row base 0 and the span taken from vcu.
+template <class TE>
+static int pool_rview_fwd_launch(const TE* E, int64_t ldE, const float* scores, float* pooled, float* stat_m, float* stat_l,
+                                 int64_t n_bags, const int32_t* perm, const int64_t* vcu, int64_t max_view_len, int H, void* ws,
+                                 void* stream) {
+    if (!E || !scores || !pooled || !stat_m || !stat_l || !ws || !perm || !vcu) return MDL_E_ARG;
+    if (n_bags < 0 || max_view_len < 0 || ldE < (int64_t)H * HID || (ldE & 3)) return MDL_E_ARG;
+    if (!host_aligned16(E) || !host_aligned16(pooled) || !host_aligned16(ws)) return MDL_E_ALIGN;
+    if (n_bags == 0) return MDL_OK;
+    if (2 * n_bags > 65535) return MDL_E_UNSUPPORTED;
+    const int64_t n_seg = 2 * n_bags;
+    hipStream_t s = (hipStream_t)stream;
+    const int mc = (int)pool_max_chunks(max_view_len);
+    float* part_acc = (float*)ws;
+    const int64_t st = ((n_seg * (int64_t)mc * H * 4 + 15) / 16) * 16;
+    float* part_m = (float*)((char*)ws + n_seg * (int64_t)mc * H * HID * 4);
+    float* part_l = (float*)((char*)part_m + st);
+    MDL_DISPATCH_H(H, {
+        if (mc > 0) {
+            hipLaunchKernelGGL((pool_partial_kernel<HH, TE, true>), dim3(mc, (unsigned)n_seg), dim3(HH * 128), 0, s, E, ldE, scores,
+                               part_acc, part_m, part_l, (int64_t)0, vcu, mc, perm, (int64_t)-1);
+            MDL_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL((pool_combine_kernel<HH>), dim3((unsigned)n_seg), dim3(HH * 128), 0, s, part_acc, part_m, part_l,
+                           pooled, stat_m, stat_l, (int64_t)0, vcu, mc, (int64_t)-1);
+        MDL_LAUNCH_CHECK();
+    });
+    return MDL_OK;
+}
+
+template <class TE>
+static int pool_rview_bwd_launch(const TE* E, int64_t ldE, const float* scores, const float* pooled, const float* stat_m,
+                                 const float* stat_l, const float* d_pooled, TE* dE, float* d_scores, int64_t n_bags, const int32_t* perm,
+                                 const int64_t* vcu, int64_t max_view_len, int H, void* stream) {
+    if (!E || !scores || !pooled || !stat_m || !stat_l || !d_pooled || !perm || !vcu || (!dE && !d_scores)) return MDL_E_ARG;
+    if (n_bags < 0 || max_view_len < 0 || ldE < (int64_t)H * HID || (ldE & 3)) return MDL_E_ARG;
+    if (!host_aligned16(E) || !host_aligned16(dE) || !host_aligned16(pooled) || !host_aligned16(d_pooled)) return MDL_E_ALIGN;
+    if (n_bags == 0 || max_view_len == 0) return MDL_OK;
+    if (2 * n_bags > 65535) return MDL_E_UNSUPPORTED;
+    const int nc = (int)((max_view_len + POOL_BWD_TOKENS - 1) / POOL_BWD_TOKENS);
+    MDL_DISPATCH_H(H, {
+        // perm is a permutation: the segments write disjoint rows of dE / d_scores, no atomics
+        hipLaunchKernelGGL((pool_bwd_kernel<HH, TE, true>), dim3(nc, (unsigned)(2 * n_bags)), dim3(256), 0, (hipStream_t)stream, E, ldE,
+                           scores, pooled, stat_m, stat_l, d_pooled, dE, 1, d_scores, 1, (int64_t)0, vcu, perm, (int64_t)-1);
+        MDL_LAUNCH_CHECK();
+    });
+    return MDL_OK;
+}
+
+extern "C" int mdl_abmil_pool_rview_fwd(const float* E, int64_t ldE, const float* scores, float* pooled, float* stat_m, float* stat_l,
+                                        int64_t n_bags, const int32_t* perm, const int64_t* vcu, int64_t max_view_len, int H, void* ws,
+                                        void* stream) {
+    return pool_rview_fwd_launch<float>(E, ldE, scores, pooled, stat_m, stat_l, n_bags, perm, vcu, max_view_len, H, ws, stream);
+}
+extern "C" int mdl_abmil_pool_rview_bwd(const float* E, int64_t ldE, const float* scores, const float* pooled, const float* stat_m,
+                                        const float* stat_l, const float* d_pooled, float* dE, float* d_scores, int64_t n_bags,
+                                        const int32_t* perm, const int64_t* vcu, int64_t max_view_len, int H, void* stream) {
+    return pool_rview_bwd_launch<float>(E, ldE, scores, pooled, stat_m, stat_l, d_pooled, dE, d_scores, n_bags, perm, vcu, max_view_len,
+                                        H, stream);
+}
+extern "C" int mdl_abmil_pool_rview_fwd_bf16(const uint16_t* E, int64_t ldE, const float* scores, float* pooled, float* stat_m,
+                                             float* stat_l, int64_t n_bags, const int32_t* perm, const int64_t* vcu, int64_t max_view_len,
+                                             int H, void* ws, void* stream) {
+    return pool_rview_fwd_launch<bf16_t>((const bf16_t*)E, ldE, scores, pooled, stat_m, stat_l, n_bags, perm, vcu, max_view_len, H, ws,
+                                         stream);
+}
+extern "C" int mdl_abmil_pool_rview_bwd_bf16(const uint16_t* E, int64_t ldE, const float* scores, const float* pooled,
+                                             const float* stat_m, const float* stat_l, const float* d_pooled, uint16_t* dE,
+                                             float* d_scores, int64_t n_bags, const int32_t* perm, const int64_t* vcu,
+                                             int64_t max_view_len, int H, void* stream) {
+    return pool_rview_bwd_launch<bf16_t>((const bf16_t*)E, ldE, scores, pooled, stat_m, stat_l, d_pooled, (bf16_t*)dE, d_scores, n_bags,
+                                         perm, vcu, max_view_len, H, stream);
 }
 
 extern "C" int mdl_abmil_pool_view_fwd(const float* E, int64_t ldE, const float* scores, float* pooled, float* stat_m, float* stat_l,

@@ -80,6 +80,15 @@ def collate(batch):
             "slide_ids": [item['slide_id'] for item in batch]}
 
 
+def ragged_collate(batch):
+    """collate for bags of their real length (SlideDataset(sample=-1)), which torch.stack cannot batch -> {'bags': [[N_bm, D] per
+    modality] per case, 'modality_labels': [B, M], 'slide_ids': list}: the input of MADELEINE.forward's 'bags' route (forward_ragged).
+    The bags are the items' own tensors, in item and modality order; an absent stain stays the dataset's 2-token zero bag."""
+    return {"bags": [list(item['feats']) for item in batch],
+            "modality_labels": torch.stack([torch.Tensor(item['modality_labels']) for item in batch]),
+            "slide_ids": [item['slide_id'] for item in batch]}
+
+
 class SimpleDataset(Dataset):
     """Mirror of wsi_dataset.py:102-120 (the extraction-side dataset run_inference iterates): every `*.h5` file of a directory ->
     (features [N, D] float tensor, slide id = file name without the extension)."""

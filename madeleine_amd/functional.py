@@ -362,6 +362,45 @@ def pool_view_bwd_raw(E2d, scores, pooled, stat_m, stat_l, d_pooled, dE, d_score
     _native.check(rc, "mdl_abmil_pool_view_bwd")
 
 
+def pool_rview_fwd_raw(E2d, scores, n_bags, perm, vcu, max_view_len):
+    """The two half-bag views of every packed bag (mdl_abmil_pool_rview_fwd): -> (pooled [n_bags, 2, H*512], stat_m, stat_l [2*n_bags, H])."""
+    lib = _native.lib()
+    H = scores.shape[-1]
+    dev = E2d.device
+    pooled = torch.empty(n_bags, 2, H * HID, device=dev, dtype=torch.float32)
+    stat_m = torch.empty(2 * n_bags, H, device=dev, dtype=torch.float32)
+    stat_l = torch.empty(2 * n_bags, H, device=dev, dtype=torch.float32)
+    ws = _ws(lib.mdl_abmil_pool_ws_bytes(2 * n_bags, max_view_len, H), dev)
+    with _timed("pool_view_fwd"):
+        rc = getattr(lib, "mdl_abmil_pool_rview_fwd" + _sfx(E2d))(_ptr(E2d), E2d.stride(0), _ptr(scores), _ptr(pooled), _ptr(stat_m),
+                                                                 _ptr(stat_l), n_bags, _ptr(perm), _ptr(vcu), int(max_view_len), H,
+                                                                 _ptr(ws), _stream())
+    _native.check(rc, "mdl_abmil_pool_rview_fwd")
+    return pooled, stat_m, stat_l
+
+
+def pool_rview_bwd_raw(E2d, scores, pooled, stat_m, stat_l, d_pooled, dE, d_scores, n_bags, perm, vcu, max_view_len):
+    """Accumulates the ragged views' contribution (d_pooled [n_bags, 2, H*512]) into dE and / or d_scores (either may be None)."""
+    lib = _native.lib()
+    H = scores.shape[-1]
+    with _timed("pool_view_bwd"):
+        rc = getattr(lib, "mdl_abmil_pool_rview_bwd" + _sfx(E2d))(_ptr(E2d), E2d.stride(0), _ptr(scores), _ptr(pooled), _ptr(stat_m),
+                                                                 _ptr(stat_l), _ptr(d_pooled), _ptr(dE), _ptr(d_scores), n_bags,
+                                                                 _ptr(perm), _ptr(vcu), int(max_view_len), H, _stream())
+    _native.check(rc, "mdl_abmil_pool_rview_bwd")
+
+
+def _check_rview(E2d, cu_seqlens, rviews):
+    perm, vcu, max_view_len = rviews
+    if cu_seqlens is None:
+        raise ValueError("ragged views (perm, vcu) need packed bags with cu_seqlens")
+    _require(perm, "view permutation", torch.int32)
+    _require(vcu, "view offsets", torch.int64)
+    if perm.numel() != E2d.shape[0] or vcu.numel() != 2 * (cu_seqlens.numel() - 1) + 1:
+        raise ValueError("ragged views: perm must cover every packed row [T] and vcu hold 2 * n_bags + 1 offsets")
+    return perm, vcu, int(max_view_len)
+
+
 # --------------------------------------------------------------------------------------------------
 # split-fp16 engine (include/madeleine_amd.h, csrc/split_engine.hpp): fp32-accurate contractions on v_mfma_f32_32x32x16_f16
 # --------------------------------------------------------------------------------------------------
@@ -931,20 +970,51 @@ def weighted_pool(E, weights, cu_seqlens=None, max_len=None):
     return WeightedPoolFn.apply(E, weights.contiguous(), cu_seqlens, max_len)
 
 
+class RaggedViewPoolFn(torch.autograd.Function):
+    """The two half-bag views of packed bags on their own (pooled [n_bags, 2, H*512]): the raw scores re-softmaxed over each half
+    (Model.py:419-440, which uses F.softmax there whatever the attention activation) -- the views of the relu / leaky_relu / sigmoid
+    activations, whose whole-bag pooling is the weighted pooling above."""
+
+    @staticmethod
+    def forward(ctx, E2d, scores, cu_seqlens, perm, vcu, max_view_len):
+        _require_act(E2d, "E")
+        _require(scores, "scores")
+        perm, vcu, max_view_len = _check_rview(E2d, cu_seqlens, (perm, vcu, max_view_len))
+        n_bags = cu_seqlens.numel() - 1
+        pooled, m, l = pool_rview_fwd_raw(E2d, scores, n_bags, perm, vcu, max_view_len)
+        ctx.save_for_backward(E2d, scores, pooled, m, l, perm, vcu)
+        ctx.geom = (n_bags, max_view_len)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, d_pooled):
+        E2d, scores, pooled, m, l, perm, vcu = ctx.saved_tensors
+        n_bags, max_view_len = ctx.geom
+        dE = torch.zeros_like(E2d)
+        ds = torch.zeros_like(scores)
+        pool_rview_bwd_raw(E2d, scores, pooled, m, l, d_pooled.float().contiguous(), dE, ds, n_bags, perm, vcu, max_view_len)
+        return dE, ds, None, None, None, None
+
+
+def ragged_view_pool(E2d, scores, cu_seqlens, perm, vcu, max_view_len):
+    return RaggedViewPoolFn.apply(E2d, scores.contiguous(), cu_seqlens, perm, vcu, max_view_len)
+
+
 # --------------------------------------------------------------------------------------------------
 # A2 + A3 chained inside one autograd node: the pooling backward only produces d_scores, and its dE term
 # w * d_pooled is added in the gate backward's dX epilogue -- dE is written exactly once.
 # --------------------------------------------------------------------------------------------------
 class AttnPoolFn(torch.autograd.Function):
     """(pooled [n_bags,(1+V,)H*512], raw scores [T,H], token projections [T,P]) = multi-head gated-ABMIL pooling (Model.py:406-417)
-    and, with `views` = V int32 token-index lists (dense bags only), the V re-softmaxed sub-bag poolings of Model.py:419-440.
+    and, with `views` = V int32 token-index lists (dense bags only), the V re-softmaxed sub-bag poolings of Model.py:419-440; on packed
+    bags `rviews` = (perm, vcu, max_view_len) gives each bag its own two halves (mdl_abmil_pool_rview_*), pooled [n_bags, 3, H*512].
     With Wtok [P, H*512] (+ btok) the token_projector Linear (Model.py:140) -- the other consumer of E -- is part of the node: its dX
     is written into dE first and the gate dX epilogue accumulates onto it, so the two gradients of E are never summed by a separate
     3 x |E| elementwise pass (3.8 ms per config-3 step); without it the third output is an empty tensor."""
 
     @staticmethod
     def forward(ctx, E, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b, cu_seqlens, max_len, Wtok, btok, Eimg, Escale, e_only_image,
-                *views):
+                rviews, *views):
         # e_only_image: E IS the image tensor (Eimg is E, an opaque float32 [.., H*512] tensor written by the last pre_attn block's
         # LayerNorm kernel) -- no fp32 copy of E exists; the pooling kernels read the image, dE is the gradient of that tensor
         _require_act(E, "E")
@@ -955,10 +1025,12 @@ class AttnPoolFn(torch.autograd.Function):
             raise NotImplementedError("token-index views are defined on dense bags (the reference's n_views path stacks equal-N bags)")
         for v in views:
             _require(v, "view token indices", torch.int32)
+        if rviews is not None:
+            rviews = _check_rview(E2d, cu_seqlens, rviews)
         ctx.set_materialize_grads(False)
         need = any(ctx.needs_input_grad[:7]) or any(ctx.needs_input_grad[13:15])   # (inputs 15, 16 = the image of E: no gradient)
         Ei = None
-        if e_only_image and (Eimg is None or views or not _split_gate(E2d)
+        if e_only_image and (Eimg is None or views or rviews is not None or not _split_gate(E2d)
                              or (Wtok is not None and not split_linear_supported(E2d.shape[0], Wtok.shape[0], Wtok.shape[1]))):
             raise RuntimeError("attn_pool: an image-only E needs the split GEMM mode, no token views and a token projection the split "
                                "engine serves")
@@ -972,6 +1044,7 @@ class AttnPoolFn(torch.autograd.Function):
         pooled, m, l = (pool_fwd_img_raw(Ei, scores, n_bags, N, cu_seqlens, max_len) if e_only_image
                         else pool_fwd_raw(E2d, scores, n_bags, N, cu_seqlens, max_len))
         vstate = [pool_view_fwd_raw(E2d, scores, n_bags, N, v) for v in views]
+        rstate = pool_rview_fwd_raw(E2d, scores, n_bags, *rviews) if rviews is not None else ()
         if Wtok is not None:
             _require(Wtok, "token_projector weight")
             if btok is not None:
@@ -995,7 +1068,9 @@ class AttnPoolFn(torch.autograd.Function):
             ctx.save_for_backward(E2d, Wa, Wb, wc, act_a if not recompute else none, act_b if not recompute else none, scores, pooled, m, l,
                                   cu_seqlens if cu_seqlens is not None else none, Wtok if Wtok is not None else none,
                                   Ei.data if Ei is not None else none, Ei.scale if Ei is not None else none,
-                                  ba if recompute else none, bb if recompute else none, bc if recompute else none, *views, *flat)
+                                  ba if recompute else none, bb if recompute else none, bc if recompute else none, *views, *flat,
+                                  *(rviews[:2] if rviews is not None else ()), *rstate)
+            ctx.rview_max = None if rviews is None else rviews[2]
             ctx.recompute = recompute
             ctx.cfg = (p_drop, seed, keep_a, keep_b, n_bags, N, max_len, cu_seqlens is not None, E.shape, len(views),
                        Wtok is not None, btok is not None)
@@ -1003,6 +1078,8 @@ class AttnPoolFn(torch.autograd.Function):
             ctx.has_image = Ei is not None
         if views:
             pooled = torch.stack([pooled] + [st[0] for st in vstate], dim=1)
+        elif rviews is not None:
+            pooled = torch.cat([pooled.unsqueeze(1), rstate[0]], dim=1)
         return pooled, scores, tok
 
     @staticmethod
@@ -1010,7 +1087,9 @@ class AttnPoolFn(torch.autograd.Function):
         p_drop, seed, keep_a, keep_b, n_bags, N, max_len, ragged, e_shape, V, has_tok, has_btok = ctx.cfg
         saved = ctx.saved_tensors
         E2d, Wa, Wb, wc, act_a, act_b, scores, pooled, m, l, cu, Wtok, Eidata, Eiscale, ba, bb, bc = saved[:17]
-        views, vflat = saved[17:17 + V], saved[17 + V:]
+        views, vflat = saved[17:17 + V], saved[17 + V:17 + 4 * V]
+        rview = None if ctx.rview_max is None else tuple(saved[17 + 4 * V:]) + (ctx.rview_max,)   # (perm, vcu, pooled, m, l, max_view_len)
+        n_out = 1 + V + (2 if rview is not None else 0)
         Ei = SplitImage(Eidata, Eiscale, E2d.shape[0], E2d.shape[1]) if ctx.has_image else None
         if ctx.recompute:   # rebuild the activations: the same kernel, seed and masks as the forward -> the same bits
             if Ei is not None:
@@ -1026,9 +1105,10 @@ class AttnPoolFn(torch.autograd.Function):
             ds = torch.empty_like(scores)
             acc_s = 0
         if d_pooled is None:
-            d_pooled = torch.zeros(n_bags, 1 + V, pooled.shape[-1], device=pooled.device) if V else torch.zeros_like(pooled)
+            d_pooled = torch.zeros(n_bags, n_out, pooled.shape[-1], device=pooled.device) if n_out > 1 else torch.zeros_like(pooled)
         d_pooled = d_pooled.float().contiguous()
-        d_main = d_pooled[:, 0].contiguous() if V else d_pooled
+        d_main = d_pooled[:, 0].contiguous() if n_out > 1 else d_pooled
+        d_rview = d_pooled[:, 1:].contiguous() if rview is not None else None
         # the other consumer of E, the token_projector: its dX is accumulated into the same dE buffer (no separate gradient tensor, no
         # add pass).  Split engine: AFTER the gate backward, and only on the 256-token tiles where d_tok is not identically zero (the
         # local loss reads the first <= 256 tokens of a bag, so d_tok is zero on ~94 % of the tiles at N = 4096); the other engines:
@@ -1047,11 +1127,14 @@ class AttnPoolFn(torch.autograd.Function):
         for i in range(V):   # the views' score gradients must be in ds before the gate backward consumes it
             vp, vm, vl = vflat[3 * i:3 * i + 3]
             pool_view_bwd_raw(E2d, scores, vp, vm, vl, d_pooled[:, 1 + i].contiguous(), None, ds, n_bags, N, views[i])
+        if rview is not None:
+            perm, vcu, rp, rm, rl, rmax = rview
+            pool_rview_bwd_raw(E2d, scores, rp, rm, rl, d_rview, None, ds, n_bags, perm, vcu, rmax)
         row_bag = None
         if ragged:   # bag index of every packed token row, on the device (no sync)
             row_bag = torch.searchsorted(cu[1:].contiguous(), torch.arange(E2d.shape[0], device=E2d.device), right=True).to(torch.int32)
         if Ei is not None:
-            am = torch.zeros(1, device=dE.device, dtype=torch.float32) if V == 0 else None   # (views add to dE afterwards)
+            am = torch.zeros(1, device=dE.device, dtype=torch.float32) if n_out == 1 else None   # (views add to dE afterwards)
             dWa, dWb, dba, dbb, dwc, dbc = attnpool_bwd_split_raw(Ei, Wa, Wb, wc, act_a, act_b, ds, dE, p_drop, seed, keep_a, keep_b,
                                                                   scores, m, l, d_main, row_bag, N if not ragged else 0, acc_e, am)
             if tok_after:
@@ -1070,19 +1153,23 @@ class AttnPoolFn(torch.autograd.Function):
         for i in range(V):   # ... and their dE terms are added once dE has been written (no read of E)
             vp, vm, vl = vflat[3 * i:3 * i + 3]
             pool_view_bwd_raw(E2d, scores, vp, vm, vl, d_pooled[:, 1 + i].contiguous(), dE, None, n_bags, N, views[i])
-        return (dE.view(e_shape), dWa, dba, dWb, dbb, dwc, dbc, None, None, None, None, None, None, dWtok, dbtok, None, None, None) + (None,) * V
+        if rview is not None:
+            pool_rview_bwd_raw(E2d, scores, rp, rm, rl, d_rview, dE, None, n_bags, perm, vcu, rmax)
+        return (dE.view(e_shape), dWa, dba, dWb, dbb, dwc, dbc, None, None, None, None, None, None, dWtok, dbtok, None, None, None,
+                None) + (None,) * V
 
 
 def attn_pool(E, Wa, ba, Wb, bb, wc, bc, p_drop=0.0, seed=0, keep_a=None, keep_b=None, cu_seqlens=None, max_len=None, views=(),
-              tok_proj=None, e_img=None, e_only_image=False):
+              tok_proj=None, e_img=None, e_only_image=False, rviews=None):
     """-> (pooled, raw scores), or (pooled, raw scores, token projections [T,P]) with tok_proj = (Wtok [P,H*512], btok or None).
+    rviews = (perm int32 [T], vcu int64 [2*n_bags+1], max_view_len): the two half-bag views of every packed bag (pooled [n_bags,3,H*512]).
     e_img = (image data, scale) of E when the producing kernel wrote one (split GEMM mode); e_only_image: E is that image tensor itself
     (no fp32 E was written) and the node's E-gradient is the image tensor's."""
     Wtok, btok = tok_proj if tok_proj is not None else (None, None)
     Eimg, Escale = e_img if e_img is not None else (None, None)
     pooled, scores, tok = AttnPoolFn.apply(E, Wa, ba, Wb, bb, wc, bc, float(p_drop), int(seed), keep_a, keep_b, cu_seqlens, max_len,
                                            None if Wtok is None else Wtok.contiguous(), None if btok is None else btok.contiguous(),
-                                           Eimg, Escale, bool(e_only_image), *views)
+                                           Eimg, Escale, bool(e_only_image), None if rviews is None else tuple(rviews), *views)
     return (pooled, scores) if tok_proj is None else (pooled, scores, tok)
 
 

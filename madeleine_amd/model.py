@@ -51,6 +51,27 @@ class _PermuteFn(torch.autograd.Function):
         return g.index_select(ctx.dim, inv), None, None, None
 
 
+def ragged_view_plan(lens):
+    """Host side of the intra-modality views on packed bags (Model.py:419-440 applied to each bag on its own): for every bag in packed
+    order, `idx = np.arange(N_b); np.random.shuffle(idx); mid = N_b // 2` -- the reference's draw for one bag -- view 1 = idx[:mid],
+    view 2 = idx[mid:].  Returns (perm int32 [T]: the absolute packed rows cu[b] + idx, bag after bag; vcu int64 [2*n_bags + 1]:
+    positions in perm where each view starts; max_view_len), the inputs of the ragged-view pooling kernels (mdl_abmil_pool_rview_*)."""
+    lens = [int(n) for n in lens]
+    perm = np.empty(sum(lens), dtype=np.int32)
+    vcu = np.empty(2 * len(lens) + 1, dtype=np.int64)
+    start, max_view = 0, 0
+    for b, n in enumerate(lens):
+        idx = np.arange(n)
+        np.random.shuffle(idx)
+        mid = n // 2
+        perm[start:start + n] = start + idx
+        vcu[2 * b], vcu[2 * b + 1] = start, start + mid
+        max_view = max(max_view, n - mid)
+        start += n
+    vcu[-1] = start
+    return torch.from_numpy(perm), torch.from_numpy(vcu), max_view
+
+
 def bf16_mode() -> bool:
     """True inside torch.autocast(device_type='cuda', dtype=torch.bfloat16): selects the kernels' bf16 mode."""
     return torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
@@ -288,9 +309,10 @@ class ABMILEmbedder(nn.Module):
             return out[0], out[1].view(BM, N, self.n_heads)
         return out[0], out[1].view(BM, N, self.n_heads), out[2].view(BM, N, -1)
 
-    def pool_headmajor_ragged(self, E_hm: torch.Tensor, cu_seqlens: torch.Tensor, max_len: int, e_img=None, tok_proj=None):
+    def pool_headmajor_ragged(self, E_hm: torch.Tensor, cu_seqlens: torch.Tensor, max_len: int, e_img=None, tok_proj=None, rviews=None):
         """Packed E_hm [T,H*512] + cu_seqlens int64 [n_bags+1] -> (pooled_hm [n_bags,H*512], raw scores [T,H]) (+ the token projections
-        [T,P] with tok_proj = (W, bias), see pool_headmajor)."""
+        [T,P] with tok_proj = (W, bias), see pool_headmajor).  rviews = (perm, vcu, max_view_len) on the device (ragged_view_plan): pooled_hm
+        is [n_bags, 3, H*512], the whole bag and its two halves with the raw scores re-softmaxed over each half, whatever the activation."""
         for h in self.attn:
             h._check_geometry()
         wa, ba, wb, bb, wc, bc = self.gate_params_stacked()
@@ -304,9 +326,12 @@ class ABMILEmbedder(nn.Module):
                 raise ValueError("activation=%r pools the token embeddings themselves: call embed_tokens_headmajor(want_fp32=True) and project "
                                  "the tokens separately" % act)
             scores = MF.gate_scores(E_hm, wa, ba, wb, bb, wc, bc, p, seed, ka, kb)          # [T, H]
-            return MF.weighted_pool(E_hm, activate(scores, act), cu_seqlens, max_len), scores
+            pooled = MF.weighted_pool(E_hm, activate(scores, act), cu_seqlens, max_len)
+            if rviews is not None:   # (Model.py:435 re-softmaxes the raw scores over each half for every activation)
+                pooled = torch.cat([pooled.unsqueeze(1), MF.ragged_view_pool(E_hm, scores, cu_seqlens, *rviews)], dim=1)
+            return pooled, scores
         return MF.attn_pool(E_hm, wa, ba, wb, bb, wc, bc, p, seed, ka, kb, cu_seqlens, max_len, e_img=e_img, tok_proj=tok_proj,
-                            e_only_image=self.image_only(E_hm, e_img))
+                            e_only_image=self.image_only(E_hm, e_img), rviews=rviews)
 
     def _scores_only(self, E_hm):
         BM, N, _ = E_hm.shape
@@ -500,13 +525,17 @@ class MADELEINE(nn.Module):
         pooled, _ = emb.pool_headmajor_ragged(E, MF.h2d(cu, device), max(lens), e_img=e_img)
         return self._project_slide(pooled)
 
-    def forward_ragged(self, bags, device, n_loss_tokens=None):
+    def forward_ragged(self, bags, device, n_loss_tokens=None, n_views=1, modality_labels=None):
         """Variable-length bags (BASELINE config 5) -- NEW functionality: the reference can only torch.stack equal-N
         bags (wsi_dataset.py:89-92).  `bags` is a list over cases of lists over modalities of [N_bm, D] tensors.
         Semantics = the train branch applied to each bag on its own (incl. the stain-encoding row quirk r // B of
         Model.py:125-131); the pooling kernels take the packed tokens + cu_seqlens, nothing is padded.
         Returns the reference-shaped dicts, with token embeddings restricted to the first `n_loss_tokens` tokens of
-        every bag -- all the local loss ever reads (GOT sub-samples randperm(k)[:256])."""
+        every bag -- all the local loss ever reads (GOT sub-samples randperm(k)[:256]).
+        n_views != 1: the intra-modality views of Model.py:419-440 applied to each bag on its own (ragged_view_plan: one numpy shuffle
+        per bag, in packed order); slide embeddings are then [B, 3, 512] ([B, 3, 512, M-1] for HE), as on the dense path.
+        modality_labels [B, M] (the batch's own tensor): a bag labelled 0 (an absent stain, which the dataset fills with a 2-token zero
+        bag and no loss reads) may be shorter than n_loss_tokens; its token rows past its length are zeros."""
         bs, n_mod = len(bags), len(bags[0])
         if n_loss_tokens is None:
             # GOT draws token indices randperm(k)[:256] with k = the number of participating CASES (reference quirk, loss.py:282,
@@ -514,9 +543,18 @@ class MADELEINE(nn.Module):
             n_loss_tokens = max(256, bs)
         flat = [bags[b][m] for b in range(bs) for m in range(n_mod)]          # case-major rows, like .view(bs*n_mod,...)
         lens = [int(x.shape[0]) for x in flat]
-        if min(lens) < n_loss_tokens:
+        present = [True] * len(lens)
+        if modality_labels is not None:
+            present = [bool(v) for v in torch.as_tensor(modality_labels).detach().cpu().reshape(-1).tolist()]
+            if len(present) != len(lens):
+                raise ValueError("modality_labels must be [B, M] = [%d, %d]" % (bs, n_mod))
+        short = [n for n, pr in zip(lens, present) if pr and n < n_loss_tokens]
+        if short:
             raise ValueError("every bag needs at least n_loss_tokens=%d tokens (shortest has %d): the local loss reads token "
-                             "indices up to min(batch, 256) - 1 of every bag" % (n_loss_tokens, min(lens)))
+                             "indices up to min(batch, 256) - 1 of every bag" % (n_loss_tokens, min(short)))
+        if min(lens) < 1:
+            raise ValueError("every bag needs at least one token (an absent stain's bag included)")
+        rviews = ragged_view_plan(lens) if n_views != 1 else None     # (numpy's RNG, as the reference's view draw)
         cu = torch.zeros(len(flat) + 1, dtype=torch.int64)
         cu[1:] = torch.cumsum(torch.tensor(lens, dtype=torch.int64), 0)
         x = torch.cat([f.to(device) for f in flat], dim=0)                     # packed [T, D]
@@ -531,21 +569,34 @@ class MADELEINE(nn.Module):
         cu_d = MF.h2d(cu, device)
         if stain is not None:
             stain = (stain[0], stain[1], cu_d)
-        head = MF.h2d((cu[:-1].unsqueeze(1) + torch.arange(n_loss_tokens).unsqueeze(0)).reshape(-1), device)
+        pos = torch.arange(n_loss_tokens).unsqueeze(0)
+        lens_t = torch.tensor(lens, dtype=torch.int64).unsqueeze(1)
+        pad = None
+        if min(lens) < n_loss_tokens:
+            # absent bags shorter than n_loss_tokens: their rows past the end repeat the last token and are zeroed after the projection
+            pad = MF.h2d((pos < lens_t).reshape(bs, n_mod, n_loss_tokens, 1).float(), device)
+            pos = torch.minimum(pos, lens_t - 1)
+        head = MF.h2d((cu[:-1].unsqueeze(1) + pos).reshape(-1), device)
         tp = (emb.permuted(self.token_projector.weight, 1), self.token_projector.bias)
         # Split GEMM mode: the token projection is part of the pooling node (every token, on the image of E) and the head tokens are
         # gathered from ITS output -- gathering rows of E instead makes autograd fill a zero [T, 2048] tensor and add it to the node's dE
         # (3 x 11 GB of traffic per config-5 step), and E need not exist in fp32 at all.
         fuse_tok = (not bf16_mode()) and MF.split_linear_supported(x.shape[0], tp[0].shape[0], tp[0].shape[1]) \
-            and emb.attn[0].activation == 'softmax'      # (the other activations pool fp32 tokens through the weighted-pooling kernels)
+            and emb.attn[0].activation == 'softmax' and rviews is None
+        # (the other activations pool fp32 tokens through the weighted-pooling kernels; the views read E in fp32 / bf16, as the dense
+        # n_views = 3 path does)
+        if rviews is not None:
+            rviews = (MF.h2d(rviews[0], device), MF.h2d(rviews[1], device), rviews[2])
         E, e_img = emb.embed_tokens_headmajor(x, return_image=True, want_fp32=not fuse_tok, stain=stain)   # [T, H*512]
         if fuse_tok and e_img is not None:
             pooled, _, tok_all = emb.pool_headmajor_ragged(E, cu_d, max(lens), e_img=e_img, tok_proj=tp)
             tok = tok_all.index_select(0, head).view(bs, n_mod, n_loss_tokens, -1)          # [B,M,n,128]
         else:
-            pooled, _ = emb.pool_headmajor_ragged(E, cu_d, max(lens), e_img=e_img)
+            pooled, _ = emb.pool_headmajor_ragged(E, cu_d, max(lens), e_img=e_img, rviews=rviews)
             tok = self._project_tokens(E.index_select(0, head)).view(bs, n_mod, n_loss_tokens, -1)
-        slide = self._project_slide(pooled).view(bs, n_mod, 1, -1)              # [B,M,1,512]
+        if pad is not None:
+            tok = tok * pad
+        slide = self._project_slide(pooled).view(bs, n_mod, -1, self.projector.weight.shape[0])   # [B,M,V,512]
         all_embeddings, all_token_embeddings = {}, {}
         slides, toks = slide.unbind(1), tok.unbind(1)   # (see forward: one stacked gradient instead of per-stain fills and adds)
         for idx, modality in enumerate(self.modalities):
@@ -559,7 +610,7 @@ class MADELEINE(nn.Module):
 
     def forward(self, data, device, train=True, n_views=1, custom_stain_idx=None, return_attention=False):
         if 'bags' in data and 'feats' not in data:   # ragged extension (see forward_ragged); keeps DDP's forward hook path
-            return self.forward_ragged(data['bags'], device)
+            return self.forward_ragged(data['bags'], device, n_views=n_views, modality_labels=data.get('modality_labels'))
         all_wsi_feats = data['feats'].to(device)
         all_embeddings, all_token_embeddings = {}, {}
         emb = self.wsi_embedders
