@@ -252,6 +252,28 @@ int mdl_infonce_fwd(const float* Q, const float* P, const int32_t* cnt, float* l
 int mdl_infonce_bwd(const float* Q, const float* P, const float* d_loss, const float* d_row_loss, const int32_t* cnt, float* dQ,
                     float* dP, int S, int Kmax, int D, float temperature, int symmetric, void* ws, void* stream);
 
+/* L1 with explicit negatives (ABI 26, additive).  Replaces InfoNCE.info_nce, negative_keys branch (madeleine/utils/loss.py:93-110):
+ * logits [q_hat.p_hat | q_hat.n_hat^T] / temperature with the target in column 0.  The reference branch builds them and then returns
+ * None; the loss computed here is the cross entropy its in-batch branch applies to such logits,
+ * F.cross_entropy(logits / temperature, labels, reduction) (loss.py:125).  x_hat = x / max(|x|, 1e-12) for every row.  `symmetric`
+ * plays no part (the reference branch never reads it).
+ *
+ * Q,P [N,Dq] with Dq = D rounded up to 32, zero-padded columns (16-byte aligned); Neg [M,D] (paired == 0: one bank for every row) or
+ * [N,M,D] (paired != 0: row i against Neg[i]), contiguous, any D >= 1 (read in place; NULL only when M == 0).
+ * loss (NULL, or [1]): mean of the N row losses (N == 0 => 0); row_loss (NULL, or [N]): per-row losses (reduction='none').  At least
+ * one of the two.  M == 0 gives loss 0 and zero gradients (a one-class cross entropy).
+ * ws: mdl_infonce_neg_ws_bytes(N,M,D,paired): normalised Q,P, logits, norms, LSE partials, split partials (kept for bwd).
+ * Returns MDL_E_UNSUPPORTED past the launch-grid limits (unpaired: N or Dq above 2,097,120, M above 67,107,840; paired: M above
+ * 4,194,240). */
+int64_t mdl_infonce_neg_ws_bytes(int N, int M, int D, int paired);
+int mdl_infonce_neg_fwd(const float* Q, const float* P, const float* Neg, float* loss, float* row_loss, int N, int M, int D, int paired,
+                        float temperature, void* ws, void* stream);
+/* d_loss [1] incoming gradient of the mean -- or, when d_row_loss [N] != NULL, of the row losses (d_loss may then be NULL).
+ * dQ,dP [N,Dq] (padding columns get the gradient of their zeros, 0 up to rounding); dNeg (NULL: skipped entirely, no kernel touches it)
+ * same shape as Neg.  ws must be the forward's.  No atomics: splits over M are merged in a fixed order (same bits run to run). */
+int mdl_infonce_neg_bwd(const float* Neg, const float* d_loss, const float* d_row_loss, float* dQ, float* dP, float* dNeg, int N, int M,
+                        int D, int paired, float temperature, void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * N1 -- every Linear of the encoder as an exact-fp32 contraction in hand-written kernels: the three
  * Linears of the pre-attention MLP (madeleine/models/Model.py:351, :355, :359; bias = NULL there: the bias and its gradient
@@ -557,8 +579,12 @@ int mdl_abmil_attnpool_bwd_split(const void* E_img, int64_t e_rsb, const float* 
  *   MDL_PLAN_LINEAR_BF16_BWD     N, K        dW tile 128 | 256                         dX tiles per workgroup   dX: 4 (128x256) | 256
  *   MDL_PLAN_GOT                 n, -        size class 64 | 128 | 192 | 256 | 512     row-half products        split sweeps: 0 off,
  *                                                                                                               1 (2k WGs), 2 (+ 4k)
+ *   MDL_PLAN_INFONCE_NEG         M, D        1: 16-byte loads of Neg (D % 4 == 0)      0                        LSE partials per row
+ *                                            0: 4-byte loads
  * [SPLITS] token splits S of the dW-type contraction (1, with TPS = CHUNK = 0, where there are none), [TPS] tokens per split, [EMPTY] splits that hold no
- * token ((s * tps >= T)), [CHUNK] tokens per chunk of the contraction's main loop (tps is a multiple of it). */
+ * token ((s * tps >= T)), [CHUNK] tokens per chunk of the contraction's main loop (tps is a multiple of it).
+ * MDL_PLAN_INFONCE_NEG (T = N rows): [SPLITS] splits over M of the unpaired dQ contraction (1024 negatives each), [CHUNK] waves per row
+ * of the paired kernels (64 negatives each); MDL_E_UNSUPPORTED where the unpaired launcher would refuse the geometry. */
 #define MDL_PLAN_GATE_FP32_BWD 1
 #define MDL_PLAN_GATE_SPLIT_FWD 2
 #define MDL_PLAN_GATE_SPLIT_BWD 3
@@ -569,6 +595,7 @@ int mdl_abmil_attnpool_bwd_split(const void* E_img, int64_t e_rsb, const float* 
 #define MDL_PLAN_LINEAR_BF16_FWD 8
 #define MDL_PLAN_LINEAR_BF16_BWD 9
 #define MDL_PLAN_GOT 10
+#define MDL_PLAN_INFONCE_NEG 11
 #define MDL_PLAN_VARIANT 0
 #define MDL_PLAN_PERSIST 1
 #define MDL_PLAN_SPLITS 2

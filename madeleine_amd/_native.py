@@ -59,6 +59,9 @@ SIGNATURES = {
     "mdl_infonce_ws_bytes": (i64, [i32, i32, i32]),
     "mdl_infonce_fwd": (i32, [c_f, c_f, c_p, c_f, c_f, i32, i32, i32, f32, i32, c_p, c_p]),
     "mdl_infonce_bwd": (i32, [c_f, c_f, c_f, c_f, c_p, c_f, c_f, i32, i32, i32, f32, i32, c_p, c_p]),
+    "mdl_infonce_neg_ws_bytes": (i64, [i32, i32, i32, i32]),
+    "mdl_infonce_neg_fwd": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, f32, c_p, c_p]),
+    "mdl_infonce_neg_bwd": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, f32, c_p, c_p]),
     "mdl_got_ws_bytes": (i64, [i32, i32, i32]),
     "mdl_got_fwd": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_p, c_p]),
     "mdl_got_extrema": (i32, [c_f, c_f, c_f, i32, i32, i32, c_p, c_p]),
@@ -190,7 +193,7 @@ def check(rc: int, what: str):
 
 # mdl_dispatch_plan products / fields (include/madeleine_amd.h)
 PLAN_PRODUCTS = {"gate_fp32_bwd": 1, "gate_split_fwd": 2, "gate_split_bwd": 3, "gate_bf16_fwd": 4, "gate_bf16_bwd": 5, "split_tn": 6,
-                 "linear_fp32_bwd": 7, "linear_bf16_fwd": 8, "linear_bf16_bwd": 9, "got": 10}
+                 "linear_fp32_bwd": 7, "linear_bf16_fwd": 8, "linear_bf16_bwd": 9, "got": 10, "infonce_neg": 11}
 PLAN_FIELDS = ("variant", "persist", "splits", "tps", "empty", "chunk", "extra")
 
 

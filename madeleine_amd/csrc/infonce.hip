@@ -531,3 +531,540 @@ extern "C" int mdl_infonce_bwd(const float* Q, const float* P, const float* d_lo
     MDL_LAUNCH_CHECK();
     return MDL_OK;
 }
+
+
+// ================================================================================================
+// Explicit negatives: InfoNCE.info_nce with negative_keys (reference madeleine/utils/loss.py:93-110).  That branch builds the logits
+// [q^.p^ | q^.n^T] with the target in column 0 and then falls off the end of the function; what is computed here is the cross entropy
+// its in-batch branch applies to such logits, F.cross_entropy(logits / temperature, labels, reduction) (loss.py:125).
+//   unpaired: Neg [M,D], one bank shared by every row;  paired: Neg [N,M,D], row i against its own M negatives.
+// Q,P [N,Dq] come zero-padded to Dq = D rounded up to 32 (the small operands); Neg is read where it lies, for any D: the row tails are
+// masked in the kernels, 16-byte loads when D % 4 == 0 and the pointers allow them.  Workspace (floats, every segment on 256 B):
+//   Qn,Pn,dQn,dPn [Np,Dq] | rq,rp,z0,m,l [Np] | Z [N,M] logits of the negatives | rn inverse norms of the negatives ([M] | [N,M])
+//   | pm,ps [nlc,N] (max, sum exp) per LSE chunk | part [nsp,Np,Dq] split partials of dQn | cnt (int, = N: the shared kernels' count)
+// Row i: (m_i, l_i) = (max, log sum exp(z - max)) over {z0_i} u {Z_ij}, kept apart from z0_i (see the top of this file);
+// loss_i = l_i - (z0_i - m_i).  Backward, with C_ij = g_i (softmax_ij - [j == 0]) / T:
+//   dQn_i = C_i0 Pn_i + sum_j C_ij N^_j   (unpaired: a K = M contraction split over M)   dPn_i = C_i0 Qn_i
+//   dN^_j = sum_i C_ij Qn_i  (paired: C_ij Qn_i),  and in normalize()'s backward <N^_j, dN^_j> = sum_i C_ij cos_ij = T sum_i C_ij Z_ij
+//   comes from the logits, so dNeg is one pass with no reduction over D.
+// Splits and chunks have fixed sizes and are merged in a fixed order; no atomics: two runs give the same bits.
+// ================================================================================================
+namespace mdl {
+
+constexpr int NEG_LSE_CH = 4096;   // logits per LSE partial
+constexpr int NEG_KCH = 1024;      // unpaired dQn: negatives per split of the K = M contraction
+constexpr int NEG_PCH = 64;        // paired: negatives per wave (lane u keeps the scalars of negative u)
+
+struct NegWs {
+    float *Qn, *Pn, *dQn, *dPn, *rq, *rp, *z0, *m, *l, *Z, *rn, *pm, *ps, *part;
+    int* cnt;
+    int Np, Dq, nlc, nsp;
+    int64_t floats;
+};
+static inline int neg_dq(int D) { return ((D + 31) / 32) * 32; }
+static inline int neg_nlc(int M) { return M > 0 ? (M + NEG_LSE_CH - 1) / NEG_LSE_CH : 1; }
+static inline int neg_nsp(int M, int paired) {
+    const int ch = paired ? NEG_PCH : NEG_KCH;
+    return M > 0 ? (M + ch - 1) / ch : 1;
+}
+static inline NegWs neg_ws(void* ws, int N, int M, int D, int paired) {
+    NegWs w;
+    w.Np = nce_kp(N);
+    w.Dq = neg_dq(D);
+    w.nlc = neg_nlc(M);
+    w.nsp = neg_nsp(M, paired);
+    const int64_t rd = (int64_t)w.Np * w.Dq, nm = (int64_t)N * M;
+    float* base = (float*)ws;
+    int64_t off = 0;
+    auto take = [&](int64_t n) {
+        float* p = base ? base + off : nullptr;
+        off += (n + 63) & ~(int64_t)63;
+        return p;
+    };
+    w.Qn = take(rd);
+    w.Pn = take(rd);
+    w.dQn = take(rd);
+    w.dPn = take(rd);
+    w.rq = take(w.Np);
+    w.rp = take(w.Np);
+    w.z0 = take(w.Np);
+    w.m = take(w.Np);
+    w.l = take(w.Np);
+    w.Z = take(nm);
+    w.rn = take(paired ? nm : M);
+    w.pm = take((int64_t)w.nlc * N);
+    w.ps = take((int64_t)w.nlc * N);
+    w.part = take((int64_t)w.nsp * rd);
+    w.cnt = (int*)take(1);
+    w.floats = off;
+    return w;
+}
+
+// upstream gradient of row i's loss: reduction 'none' (d_row) or the mean's share
+__device__ __forceinline__ float neg_g(const float* __restrict__ d_loss, const float* __restrict__ d_row, int i, int N) {
+    return d_row ? d_row[i] : d_loss[0] / (float)N;
+}
+
+// Unpaired logits: one wave per 32 query rows x 32 negatives of Z = Qn N^T / T, on the exact-fp32 MFMA like nce_logits_kernel.  Each
+// lane (l32, kh) streams negative j0 + l32, 16 B (VEC) or 4 x 4 B at a time, and sums its squares on the way in nce_row_ss's order;
+// the column scale 1/|n_j| is applied to the accumulator.  The first row of workgroups keeps rn for the backward.
+template <bool VEC>
+__global__ __launch_bounds__(64) void nce_neg_logits_kernel(const float* __restrict__ Qn, const float* __restrict__ Ng,
+                                                            float* __restrict__ Z, float* __restrict__ rn, int N, int M, int D, int Dq,
+                                                            float inv_T) {
+    const int lane = threadIdx.x, l32 = lane & 31, kh = lane >> 5;
+    const int j0 = blockIdx.x * 32, i0 = blockIdx.y * 32, j = j0 + l32;
+    const bool live = j < M;
+    const float* __restrict__ a = Qn + (int64_t)(i0 + l32) * Dq + kh * 4;
+    const float* __restrict__ b = Ng + (int64_t)(live ? j : M - 1) * D + kh * 4;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    float ss = 0.f;
+    for (int k0 = 0; k0 < D; k0 += 8) {
+        const f32x4 av = *reinterpret_cast<const f32x4*>(a + k0);   // k0 + kh * 4 + 3 < Dq: Qn is zero-padded
+        f32x4 bv = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (VEC) {
+            if (live && k0 + kh * 4 < D) bv = *reinterpret_cast<const f32x4*>(b + k0);   // D % 4 == 0: whole vectors in or out
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (live && k0 + kh * 4 + i < D) bv[i] = b[k0 + i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ss = fmaf(bv[i], bv[i], ss);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[i], acc, 0, 0, 0);
+    }
+    ss += __shfl_xor(ss, 32, 64);
+    const float r = nce_inv_norm(ss, live);
+    if (blockIdx.y == 0 && kh == 0 && live) rn[j] = r;
+    const float sc = r * inv_T;
+    if (live)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int row = i0 + nce_acc_row(q, kh);
+            if (row < N) Z[(int64_t)row * M + j] = acc[q] * sc;
+        }
+}
+
+// Paired logits: one wave per (row i, NEG_PCH negatives); the wave reads each negative once, coalesced along D, forming <q^, n> and
+// |n|^2 together (four negatives in flight); lane u keeps the logit and inverse norm of negative u for one coalesced store.
+template <bool VEC>
+__global__ __launch_bounds__(64) void nce_neg_paired_fwd_kernel(const float* __restrict__ Qn, const float* __restrict__ Ng,
+                                                                float* __restrict__ Z, float* __restrict__ rn, int M, int D, int Dq,
+                                                                float inv_T) {
+    const int i = blockIdx.x, j0 = blockIdx.y * NEG_PCH, lane = threadIdx.x;
+    const int cnt = min(NEG_PCH, M - j0);
+    const float* __restrict__ q = Qn + (int64_t)i * Dq;
+    const float* __restrict__ nb = Ng + ((int64_t)i * M + j0) * D;
+    float zl = 0.f, rl = 0.f;
+#pragma unroll 1
+    for (int u0 = 0; u0 < cnt; u0 += 4) {
+        float dt[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
+        if (VEC) {
+            for (int d = lane * 4; d < D; d += 256) {
+                const f32x4 qv = ld4(q + d);
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if (u0 + u < cnt) {   // wave-uniform
+                        const f32x4 v = ld4(nb + (int64_t)(u0 + u) * D + d);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            dt[u] = fmaf(qv[e], v[e], dt[u]);
+                            ss[u] = fmaf(v[e], v[e], ss[u]);
+                        }
+                    }
+            }
+        } else {
+            for (int d = lane; d < D; d += 64) {
+                const float qv = q[d];
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if (u0 + u < cnt) {
+                        const float v = nb[(int64_t)(u0 + u) * D + d];
+                        dt[u] = fmaf(qv, v, dt[u]);
+                        ss[u] = fmaf(v, v, ss[u]);
+                    }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float s = wave_sum_dpp(ss[u]), t = wave_sum_dpp(dt[u]);
+            if (lane == u0 + u) {
+                rl = nce_inv_norm(s, true);
+                zl = t * rl * inv_T;
+            }
+        }
+    }
+    if (lane < cnt) {
+        Z[(int64_t)i * M + j0 + lane] = zl;
+        rn[(int64_t)i * M + j0 + lane] = rl;
+    }
+}
+
+__device__ __forceinline__ float nce_block_sum(float v, float* red) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ float nce_block_max(float v, float* red) {
+    v = wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// (max, sum exp(z - max)) of row i over logits chunk c (workgroup (i, c), 256 threads); chunk 0 also forms z0_i = <Qn_i, Pn_i> / T
+__global__ __launch_bounds__(256) void nce_neg_lse_kernel(const float* __restrict__ Z, const float* __restrict__ Qn,
+                                                          const float* __restrict__ Pn, float* __restrict__ z0, float* __restrict__ pm,
+                                                          float* __restrict__ ps, int N, int M, int Dq, float inv_T) {
+    __shared__ float red[4];
+    const int i = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+    const int jb = c * NEG_LSE_CH, je = min(M, jb + NEG_LSE_CH);
+    const float* __restrict__ z = Z + (int64_t)i * M;
+    float mx = -INFINITY;
+    for (int j = jb + tid; j < je; j += 256) mx = fmaxf(mx, z[j]);
+    mx = nce_block_max(mx, red);
+    float s = 0.f;
+    for (int j = jb + tid; j < je; j += 256) s += expf(z[j] - mx);
+    s = nce_block_sum(s, red);
+    if (tid == 0) {
+        pm[(int64_t)c * N + i] = mx;
+        ps[(int64_t)c * N + i] = s;
+    }
+    if (c == 0) {
+        const float* __restrict__ qr = Qn + (int64_t)i * Dq;
+        const float* __restrict__ pr = Pn + (int64_t)i * Dq;
+        float d = 0.f;
+        for (int k = tid; k < Dq; k += 256) d = fmaf(qr[k], pr[k], d);
+        d = nce_block_sum(d, red);
+        if (tid == 0) z0[i] = d * inv_T;
+    }
+}
+
+// one workgroup: merges the chunk partials of every row with z0 in chunk order -> (m, l), row losses and their mean
+__global__ __launch_bounds__(256) void nce_neg_loss_kernel(const float* __restrict__ z0, const float* __restrict__ pm,
+                                                           const float* __restrict__ ps, float* __restrict__ m, float* __restrict__ l,
+                                                           float* __restrict__ loss, float* __restrict__ row_loss, int N, int nlc) {
+    __shared__ float red[4];
+    const int tid = threadIdx.x;
+    float v = 0.f;
+    for (int i = tid; i < N; i += 256) {
+        const float zp = z0[i];
+        float mx = zp;
+        for (int c = 0; c < nlc; ++c) mx = fmaxf(mx, pm[(int64_t)c * N + i]);
+        float s = expf(zp - mx);
+        for (int c = 0; c < nlc; ++c) s += ps[(int64_t)c * N + i] * expf(pm[(int64_t)c * N + i] - mx);
+        const float lg = logf(s), r = lg - (zp - mx);   // -log_softmax(z)[0]
+        m[i] = mx;
+        l[i] = lg;
+        if (row_loss) row_loss[i] = r;
+        v += r;
+    }
+    v = nce_block_sum(v, red);
+    if (tid == 0 && loss) loss[0] = N > 0 ? v / (float)N : 0.f;
+}
+
+// Unpaired dQn partial of split c: block [32 rows x 32 feature cols] of sum_{j in split c} C_ij N^_j, C formed from the logits on the
+// fly (lane l32 owns row i: g_i, m_i, l_i are per lane); N^_j = n_j rn_j.  part[c] is written whole (zeros outside [N) x [D)).
+__global__ __launch_bounds__(64) void nce_neg_dq_kernel(const float* __restrict__ Z, const float* __restrict__ m,
+                                                        const float* __restrict__ l, const float* __restrict__ d_loss,
+                                                        const float* __restrict__ d_row, const float* __restrict__ Ng,
+                                                        const float* __restrict__ rn, float* __restrict__ part, int N, int M, int D,
+                                                        int Dq, int Np, float inv_T) {
+    const int lane = threadIdx.x, l32 = lane & 31, kh = lane >> 5;
+    const int n0 = blockIdx.x * 32, i0 = blockIdx.y * 32, c = blockIdx.z;
+    const int i = i0 + l32, n = n0 + l32;
+    const bool li = i < N, ln = n < D;
+    const float mi = li ? m[i] : 0.f, lgi = li ? l[i] : 0.f, gi = li ? neg_g(d_loss, d_row, i, N) * inv_T : 0.f;
+    const float* __restrict__ zr = Z + (int64_t)(li ? i : 0) * M;
+    const int kb = c * NEG_KCH, ke = min(M, kb + NEG_KCH);
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int k0 = kb; k0 < ke; k0 += 8) {
+        float av[4], bv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = k0 + kh * 4 + u;
+            const bool lk = k < ke;
+            av[u] = (li && lk) ? expf((zr[k] - mi) - lgi) * gi : 0.f;
+            bv[u] = (lk && ln) ? Ng[(int64_t)k * D + n] * rn[k] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc, 0, 0, 0);
+    }
+    float* __restrict__ o = part + ((int64_t)c * Np + i0) * Dq + n;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[(int64_t)nce_acc_row(r, kh) * Dq] = acc[r];
+}
+
+// dQn_i = sum_c part[c]_i (split order) + C_i0 Pn_i ; dPn_i = C_i0 Qn_i.  One wave per row i < N.
+__global__ __launch_bounds__(64) void nce_neg_dqp_kernel(const float* __restrict__ part, const float* __restrict__ Qn,
+                                                         const float* __restrict__ Pn, const float* __restrict__ z0,
+                                                         const float* __restrict__ m, const float* __restrict__ l,
+                                                         const float* __restrict__ d_loss, const float* __restrict__ d_row,
+                                                         float* __restrict__ dQn, float* __restrict__ dPn, int N, int Np, int D, int Dq,
+                                                         int nsp, float inv_T) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    // (softmax - 1) first: exact for a saturated softmax (see nce_coef_kernel)
+    const float c0 = (expf((z0[i] - m[i]) - l[i]) - 1.f) * (neg_g(d_loss, d_row, i, N) * inv_T);
+    const int64_t rb = (int64_t)i * Dq;
+    for (int d = lane; d < Dq; d += 64) {
+        float s = 0.f;
+        if (d < D)
+            for (int c = 0; c < nsp; ++c) s += part[((int64_t)c * Np + i) * Dq + d];
+        dQn[rb + d] = s + c0 * Pn[rb + d];
+        dPn[rb + d] = c0 * Qn[rb + d];
+    }
+}
+
+// Unpaired dNeg: one wave per 32 negatives x 32 feature cols of dN^ = C^T Qn (K = N), C from the logits on the fly; each lane also
+// sums C_ij Z_ij over its half of the rows for the normalize() backward: dNeg_j = rn_j (dN^_j - N^_j T sum_i C_ij Z_ij).
+__global__ __launch_bounds__(64) void nce_neg_dneg_kernel(const float* __restrict__ Z, const float* __restrict__ m,
+                                                          const float* __restrict__ l, const float* __restrict__ d_loss,
+                                                          const float* __restrict__ d_row, const float* __restrict__ Qn,
+                                                          const float* __restrict__ Ng, const float* __restrict__ rn,
+                                                          float* __restrict__ dNg, int N, int M, int D, int Dq, float T, float inv_T) {
+    const int lane = threadIdx.x, l32 = lane & 31, kh = lane >> 5;
+    const int j0 = blockIdx.x * 32, n0 = blockIdx.y * 32, j = j0 + l32, n = n0 + l32;
+    const bool lj = j < M;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    float dot = 0.f;
+    for (int k0 = 0; k0 < N; k0 += 8) {
+        float av[4], bv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = k0 + kh * 4 + u;
+            const bool li = i < N;
+            float c = 0.f;
+            if (li && lj) {
+                const float z = Z[(int64_t)i * M + j];
+                c = expf((z - m[i]) - l[i]) * (neg_g(d_loss, d_row, i, N) * inv_T);
+                dot = fmaf(c, z, dot);
+            }
+            av[u] = c;
+            bv[u] = li ? Qn[(int64_t)i * Dq + n] : 0.f;   // n < Dq
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc, 0, 0, 0);
+    }
+    dot = (dot + __shfl_xor(dot, 32, 64)) * T;
+    const float rj = lj ? rn[j] : 0.f;
+    if (rj >= 0.99e12f) dot = 0.f;   // norm clamped at 1e-12: normalize() is linear there
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int jr = nce_acc_row(r, kh);
+        const float rr = __shfl(rj, jr, 64), dd = __shfl(dot, jr, 64);
+        if (j0 + jr < M && n < D) {
+            const int64_t o = (int64_t)(j0 + jr) * D + n;
+            dNg[o] = rr * (acc[r] - Ng[o] * rr * dd);
+        }
+    }
+}
+
+// Paired backward: one wave per (row i, NEG_PCH negatives), the negatives read once more: part[c]_i = sum_j C_ij N^_ij (chunk c's
+// share of dQn_i) and, with DNEG, dNeg_ij = rn_ij (C_ij Qn_i - N^_ij C_ij cos_ij) written once.  Lane u holds C, rn and C cos of
+// negative u; the loop over them is wave-uniform (v_readlane).
+template <bool VEC, bool DNEG>
+__device__ __forceinline__ void nce_neg_paired_bwd(const float* __restrict__ Z, const float* __restrict__ m, const float* __restrict__ l,
+                                                   const float* __restrict__ d_loss, const float* __restrict__ d_row,
+                                                   const float* __restrict__ Qn, const float* __restrict__ Ng,
+                                                   const float* __restrict__ rn, float* __restrict__ part, float* __restrict__ dNg, int N,
+                                                   int M, int D, int Dq, int Np, float T, float inv_T) {
+    const int i = blockIdx.x, c = blockIdx.y, j0 = c * NEG_PCH, lane = threadIdx.x;
+    const int cnt = min(NEG_PCH, M - j0);
+    float cj = 0.f, rj = 0.f, dj = 0.f;
+    if (lane < cnt) {
+        const int64_t e = (int64_t)i * M + j0 + lane;
+        const float z = Z[e];
+        cj = expf((z - m[i]) - l[i]) * (neg_g(d_loss, d_row, i, N) * inv_T);
+        rj = rn[e];
+        dj = rj >= 0.99e12f ? 0.f : cj * (z * T);
+    }
+    const float* __restrict__ q = Qn + (int64_t)i * Dq;
+    const int64_t nb = ((int64_t)i * M + j0) * D;
+    float* __restrict__ o = part + ((int64_t)c * Np + i) * Dq;
+    auto bcast = [](float v, int u) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), u)); };
+    if (VEC) {
+        for (int d = lane * 4; d < D; d += 256) {
+            const f32x4 qv = ld4(q + d);
+            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int u0 = 0; u0 < cnt; u0 += 4)   // four negatives in flight
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int u = u0 + e;
+                    if (u < cnt) {   // wave-uniform
+                        const float cu = bcast(cj, u), ru = bcast(rj, u);
+                        const f32x4 v = ld4(Ng + nb + (int64_t)u * D + d) * ru;
+                        acc += v * cu;
+                        if (DNEG) st4(dNg + nb + (int64_t)u * D + d, (qv * cu - v * bcast(dj, u)) * ru);
+                    }
+                }
+            st4(o + d, acc);
+        }
+    } else {
+        for (int d = lane; d < D; d += 64) {
+            const float qv = q[d];
+            float acc = 0.f;
+            for (int u0 = 0; u0 < cnt; u0 += 4)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int u = u0 + e;
+                    if (u < cnt) {
+                        const float cu = bcast(cj, u), ru = bcast(rj, u);
+                        const float v = Ng[nb + (int64_t)u * D + d] * ru;
+                        acc += v * cu;
+                        if (DNEG) dNg[nb + (int64_t)u * D + d] = (qv * cu - v * bcast(dj, u)) * ru;
+                    }
+                }
+            o[d] = acc;
+        }
+    }
+}
+template <bool VEC>
+__global__ __launch_bounds__(64) void nce_neg_paired_bwd_kernel(const float* Z, const float* m, const float* l, const float* d_loss,
+                                                                const float* d_row, const float* Qn, const float* Ng, const float* rn,
+                                                                float* part, int N, int M, int D, int Dq, int Np, float T, float inv_T) {
+    nce_neg_paired_bwd<VEC, false>(Z, m, l, d_loss, d_row, Qn, Ng, rn, part, nullptr, N, M, D, Dq, Np, T, inv_T);
+}
+template <bool VEC>
+__global__ __launch_bounds__(64) void nce_neg_paired_bwd_dneg_kernel(const float* Z, const float* m, const float* l, const float* d_loss,
+                                                                     const float* d_row, const float* Qn, const float* Ng, const float* rn,
+                                                                     float* part, float* dNg, int N, int M, int D, int Dq, int Np, float T,
+                                                                     float inv_T) {
+    nce_neg_paired_bwd<VEC, true>(Z, m, l, d_loss, d_row, Qn, Ng, rn, part, dNg, N, M, D, Dq, Np, T, inv_T);
+}
+
+// 16-byte loads of the negatives (VEC) need D % 4 == 0 and 16-byte aligned Neg (and dNeg); otherwise 4-byte loads
+static inline bool neg_vec(int D, const void* Ng, const void* dNg) {
+    return D % 4 == 0 && host_aligned16(Ng) && (!dNg || host_aligned16(dNg));
+}
+// grid limits of the launches below (y, z <= 65535)
+static inline bool neg_fits(int N, int M, int D, int paired) {
+    const int64_t lim = 65535;
+    if (neg_nsp(M, paired) > lim || neg_nlc(M) > lim) return false;
+    return paired || (nce_kp(N) / 32 <= lim && neg_dq(D) / 32 <= lim);
+}
+static inline bool neg_args(int N, int M, int D, float temperature) {
+    return N >= 0 && M >= 0 && D >= 1 && D <= (1 << 30) && N <= (1 << 30) && M <= (1 << 30) && temperature > 0.f;
+}
+
+// mdl_dispatch_plan(MDL_PLAN_INFONCE_NEG, N, M, D): the load width and split counts the launchers below choose
+int plan_infonce_neg(int64_t N, int M, int D, int64_t* o) {
+    if (!neg_args(N > (1 << 30) ? -1 : (int)N, M, D, 1.f)) return MDL_E_ARG;
+    if (!neg_fits((int)N, M, D, 0)) return MDL_E_UNSUPPORTED;
+    o[MDL_PLAN_VARIANT] = D % 4 == 0 ? 1 : 0;
+    o[MDL_PLAN_SPLITS] = neg_nsp(M, 0);
+    o[MDL_PLAN_CHUNK] = neg_nsp(M, 1);
+    o[MDL_PLAN_EXTRA] = neg_nlc(M);
+    return MDL_OK;
+}
+
+}  // namespace mdl
+
+extern "C" int64_t mdl_infonce_neg_ws_bytes(int N, int M, int D, int paired) {
+    if (!neg_args(N, M, D, 1.f)) return MDL_E_ARG;
+    return neg_ws(nullptr, N, M, D, paired).floats * 4 + 64;
+}
+
+extern "C" int mdl_infonce_neg_fwd(const float* Q, const float* P, const float* Neg, float* loss, float* row_loss, int N, int M, int D,
+                                   int paired, float temperature, void* ws, void* stream) {
+    if (!Q || !P || (!Neg && M > 0) || (!loss && !row_loss) || !ws) return MDL_E_ARG;
+    if (!neg_args(N, M, D, temperature)) return MDL_E_ARG;
+    if (!host_aligned16(Q) || !host_aligned16(P) || !host_aligned16(ws)) return MDL_E_ALIGN;
+    if (!neg_fits(N, M, D, paired)) return MDL_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 0) {   // mean over no rows: 0, as the in-batch path for an empty problem
+        if (loss) {
+            const hipError_t e = hipMemsetAsync(loss, 0, sizeof(float), st);
+            if (e != hipSuccess) return (int)e;
+        }
+        return MDL_OK;
+    }
+    const NegWs w = neg_ws(ws, N, M, D, paired);
+    const int Np = w.Np, Dq = w.Dq;
+    const float inv_T = 1.f / temperature;
+    hipError_t e = hipMemsetD32Async((hipDeviceptr_t)w.cnt, N, 1, st);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(nce_normalize_kernel, dim3(Np / 32, 2), dim3(64), 0, st, Q, P, w.cnt, w.Qn, w.Pn, w.rq, w.rp, N, Np, Dq);
+    MDL_LAUNCH_CHECK();
+    if (M > 0) {
+        const bool vec = neg_vec(D, Neg, nullptr);
+        if (paired) {
+            const dim3 g(N, w.nsp);
+            if (vec) hipLaunchKernelGGL(nce_neg_paired_fwd_kernel<true>, g, dim3(64), 0, st, w.Qn, Neg, w.Z, w.rn, M, D, Dq, inv_T);
+            else hipLaunchKernelGGL(nce_neg_paired_fwd_kernel<false>, g, dim3(64), 0, st, w.Qn, Neg, w.Z, w.rn, M, D, Dq, inv_T);
+        } else {
+            const dim3 g(nce_kp(M) / 32, Np / 32);
+            if (vec) hipLaunchKernelGGL(nce_neg_logits_kernel<true>, g, dim3(64), 0, st, w.Qn, Neg, w.Z, w.rn, N, M, D, Dq, inv_T);
+            else hipLaunchKernelGGL(nce_neg_logits_kernel<false>, g, dim3(64), 0, st, w.Qn, Neg, w.Z, w.rn, N, M, D, Dq, inv_T);
+        }
+        MDL_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(nce_neg_lse_kernel, dim3(N, w.nlc), dim3(256), 0, st, w.Z, w.Qn, w.Pn, w.z0, w.pm, w.ps, N, M, Dq, inv_T);
+    MDL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nce_neg_loss_kernel, dim3(1), dim3(256), 0, st, w.z0, w.pm, w.ps, w.m, w.l, loss, row_loss, N, w.nlc);
+    MDL_LAUNCH_CHECK();
+    return MDL_OK;
+}
+
+extern "C" int mdl_infonce_neg_bwd(const float* Neg, const float* d_loss, const float* d_row_loss, float* dQ, float* dP, float* dNeg,
+                                   int N, int M, int D, int paired, float temperature, void* ws, void* stream) {
+    if ((!Neg && M > 0) || (!d_loss && !d_row_loss) || !dQ || !dP || !ws) return MDL_E_ARG;
+    if (!neg_args(N, M, D, temperature)) return MDL_E_ARG;
+    if (!host_aligned16(ws)) return MDL_E_ALIGN;
+    if (!neg_fits(N, M, D, paired)) return MDL_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 0) {   // no rows: the bank (unpaired) still gets its zero gradient
+        if (dNeg && !paired && M > 0) {
+            const hipError_t e = hipMemsetAsync(dNeg, 0, (size_t)M * D * sizeof(float), st);
+            if (e != hipSuccess) return (int)e;
+        }
+        return MDL_OK;
+    }
+    const NegWs w = neg_ws(ws, N, M, D, paired);
+    const int Np = w.Np, Dq = w.Dq;
+    const float inv_T = 1.f / temperature;
+    const bool vec = neg_vec(D, Neg, dNeg);
+    if (paired) {
+        const dim3 g(N, w.nsp);
+        if (dNeg) {
+            if (vec)
+                hipLaunchKernelGGL(nce_neg_paired_bwd_dneg_kernel<true>, g, dim3(64), 0, st, w.Z, w.m, w.l, d_loss, d_row_loss, w.Qn, Neg,
+                                   w.rn, w.part, dNeg, N, M, D, Dq, Np, temperature, inv_T);
+            else
+                hipLaunchKernelGGL(nce_neg_paired_bwd_dneg_kernel<false>, g, dim3(64), 0, st, w.Z, w.m, w.l, d_loss, d_row_loss, w.Qn,
+                                   Neg, w.rn, w.part, dNeg, N, M, D, Dq, Np, temperature, inv_T);
+        } else {
+            if (vec)
+                hipLaunchKernelGGL(nce_neg_paired_bwd_kernel<true>, g, dim3(64), 0, st, w.Z, w.m, w.l, d_loss, d_row_loss, w.Qn, Neg, w.rn,
+                                   w.part, N, M, D, Dq, Np, temperature, inv_T);
+            else
+                hipLaunchKernelGGL(nce_neg_paired_bwd_kernel<false>, g, dim3(64), 0, st, w.Z, w.m, w.l, d_loss, d_row_loss, w.Qn, Neg,
+                                   w.rn, w.part, N, M, D, Dq, Np, temperature, inv_T);
+        }
+    } else {
+        hipLaunchKernelGGL(nce_neg_dq_kernel, dim3(Dq / 32, Np / 32, w.nsp), dim3(64), 0, st, w.Z, w.m, w.l, d_loss, d_row_loss, Neg,
+                           w.rn, w.part, N, M, D, Dq, Np, inv_T);
+    }
+    MDL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nce_neg_dqp_kernel, dim3(N), dim3(64), 0, st, w.part, w.Qn, w.Pn, w.z0, w.m, w.l, d_loss, d_row_loss, w.dQn,
+                       w.dPn, N, Np, D, Dq, w.nsp, inv_T);
+    MDL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nce_norm_bwd_kernel, dim3(N, 2), dim3(64), 0, st, w.Qn, w.Pn, w.rq, w.rp, w.dQn, w.dPn, w.cnt, dQ, dP, N, Np,
+                       Dq);
+    MDL_LAUNCH_CHECK();
+    if (dNeg && !paired && M > 0) {
+        hipLaunchKernelGGL(nce_neg_dneg_kernel, dim3(nce_kp(M) / 32, Dq / 32), dim3(64), 0, st, w.Z, w.m, w.l, d_loss, d_row_loss, w.Qn,
+                           Neg, w.rn, dNeg, N, M, D, Dq, temperature, inv_T);
+        MDL_LAUNCH_CHECK();
+    }
+    return MDL_OK;
+}

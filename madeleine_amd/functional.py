@@ -1427,6 +1427,70 @@ def info_nce_rows(Q, P, cnt, temperature, symmetric):
     return InfoNCEFn.apply(Q, P, cnt, float(temperature), bool(symmetric), True)[1]
 
 
+class InfoNCENegFn(torch.autograd.Function):
+    """(loss [], row_loss [N]) of N queries against their positives and explicit negatives (loss.py:93-110, finished with the cross
+    entropy of loss.py:125).  Q,P [N,Dq] fp32 zero-padded to Dq = D rounded up to 32; Neg [M,D] (unpaired) or [N,M,D] (paired) fp32,
+    contiguous, read in place.  dNeg is computed only when Neg requires grad.  Use ONE of the two outputs downstream."""
+
+    @staticmethod
+    def forward(ctx, Q, P, Neg, temperature, paired, per_row):
+        _require(Q, "query")
+        _require(P, "positive_key")
+        _require(Neg, "negative_keys")
+        lib = _native.lib()
+        N, Dq = Q.shape
+        M, D = Neg.shape[-2], Neg.shape[-1]
+        loss = torch.empty((), device=Q.device, dtype=torch.float32)
+        rows = torch.empty(N, device=Q.device, dtype=torch.float32) if per_row else None
+        ws = _ws(lib.mdl_infonce_neg_ws_bytes(N, M, D, int(paired)), Q.device)
+        work = ("byte", 4.0 * Neg.numel()) if paired else ("flop", 2.0 * N * M * D)
+        with _timed("infonce_neg_fwd", work):
+            rc = lib.mdl_infonce_neg_fwd(_ptr(Q), _ptr(P), _ptr(Neg), _ptr(loss), _ptr(rows), N, M, D, int(paired), float(temperature),
+                                         _ptr(ws), _stream())
+        _native.check(rc, "mdl_infonce_neg_fwd")
+        ctx.save_for_backward(ws, Neg)
+        ctx.cfg = (N, M, D, Dq, float(temperature), bool(paired), bool(per_row))
+        if not per_row:
+            rows = loss.new_empty(0)
+            ctx.mark_non_differentiable(rows)
+        return loss, rows
+
+    @staticmethod
+    def backward(ctx, d_loss, d_rows):
+        ws, Neg = ctx.saved_tensors
+        N, M, D, Dq, temperature, paired, per_row = ctx.cfg
+        lib = _native.lib()
+        dev = Neg.device
+        dQ = torch.empty(N, Dq, device=dev, dtype=torch.float32)
+        dP = torch.empty_like(dQ)
+        dNeg = torch.empty_like(Neg) if ctx.needs_input_grad[2] else None
+        if per_row:
+            # loss = mean of the rows: fold an upstream gradient on it into the per-row gradients
+            g = d_rows.float() if d_rows is not None else torch.zeros(N, device=dev)
+            if d_loss is not None:
+                g = g + d_loss.float() / max(N, 1)
+            dl, dr = None, g.contiguous()
+        else:
+            dl, dr = d_loss.float().reshape(1).contiguous(), None
+        passes = 2 if dNeg is not None else 1
+        work = ("byte", 4.0 * Neg.numel() * (1 + passes)) if paired else ("flop", 2.0 * N * M * D * (1 + passes))
+        with _timed("infonce_neg_bwd", work):
+            rc = lib.mdl_infonce_neg_bwd(_ptr(Neg), _ptr(dl), _ptr(dr), _ptr(dQ), _ptr(dP), _ptr(dNeg), N, M, D, int(paired),
+                                         temperature, _ptr(ws), _stream())
+        _native.check(rc, "mdl_infonce_neg_bwd")
+        return dQ, dP, dNeg, None, None, None
+
+
+def info_nce_neg(Q, P, Neg, temperature, paired):
+    """Mean loss [] of N rows against explicit negatives (InfoNCENegFn)."""
+    return InfoNCENegFn.apply(Q, P, Neg, float(temperature), bool(paired), False)[0]
+
+
+def info_nce_neg_rows(Q, P, Neg, temperature, paired):
+    """Per-row losses [N] against explicit negatives (reduction 'none')."""
+    return InfoNCENegFn.apply(Q, P, Neg, float(temperature), bool(paired), True)[1]
+
+
 # --------------------------------------------------------------------------------------------------
 # G0-G3: graph optimal transport
 # --------------------------------------------------------------------------------------------------

@@ -35,12 +35,10 @@ def _validate(query, positive_key, negative_keys, negative_mode):
 def info_nce(query, positive_key, negative_keys=None, temperature=0.1, reduction='mean', negative_mode='unpaired',
              symmetric=False):
     _validate(query, positive_key, negative_keys, negative_mode)
-    if negative_keys is not None:
-        # In the reference this branch builds logits and then falls off the end of the function, returning None
-        # (loss.py:93-110): it is not a usable code path, so it is not reproduced.
-        raise NotImplementedError("explicit negative_keys: the reference branch (loss.py:93-110) never returns a loss")
     if reduction not in ('mean', 'sum', 'none'):
         raise ValueError("reduction must be 'mean', 'sum' or 'none' (F.cross_entropy's values, loss.py:124)")
+    if negative_keys is not None:
+        return _info_nce_negatives(query, positive_key, negative_keys, temperature, reduction, negative_mode)
     k, d = query.shape
     q, p = query.float().contiguous(), positive_key.float().contiguous()
     if d % 32:   # the similarity kernel works on 32-wide feature blocks: zero columns change neither norms nor cosines
@@ -51,6 +49,28 @@ def info_nce(query, positive_key, negative_keys=None, temperature=0.1, reduction
         return MF.info_nce_rows(q.unsqueeze(0), p.unsqueeze(0), cnt, temperature, symmetric)[0]
     loss = MF.info_nce_batched(q.unsqueeze(0), p.unsqueeze(0), cnt, temperature, symmetric)[0]
     return loss * k if reduction == 'sum' else loss
+
+
+def _info_nce_negatives(query, positive_key, negative_keys, temperature, reduction, negative_mode):
+    """Explicit negatives (loss.py:93-110).  The reference branch builds the logits [q.p | q.n^T] of the normalised rows with the
+    target in column 0, then falls off the end of the function and returns None; the loss computed here is the cross entropy its
+    in-batch branch applies to such logits, F.cross_entropy(logits / temperature, labels, reduction) (loss.py:125).  `symmetric` is
+    not read (neither is it in the reference branch): the result is the same for True and False.  Gradients flow to query,
+    positive_key and negative_keys; the negatives' backward runs only when negative_keys requires grad."""
+    if negative_mode not in ('paired', 'unpaired'):
+        # the reference fails here with an UnboundLocalError (its logits are never formed)
+        raise ValueError("negative_mode must be 'paired' or 'unpaired' (got %r)" % (negative_mode,))
+    n, d = query.shape
+    q, p = query.float().contiguous(), positive_key.float().contiguous()
+    neg = negative_keys.float().contiguous()   # read in place, any width: only the small operands are padded
+    if d % 32:   # the kernels take Q, P in 32-wide feature blocks: zero columns change neither norms nor cosines
+        pad = 32 - d % 32
+        q, p = torch.nn.functional.pad(q, (0, pad)), torch.nn.functional.pad(p, (0, pad))
+    paired = negative_mode == 'paired'
+    if reduction == 'none':
+        return MF.info_nce_neg_rows(q, p, neg, temperature, paired)
+    loss = MF.info_nce_neg(q, p, neg, temperature, paired)
+    return loss * n if reduction == 'sum' else loss
 
 
 class InfoNCE(nn.Module):
