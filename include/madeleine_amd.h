@@ -357,6 +357,23 @@ int mdl_got_bwd_begin_multi(int np, const float* const* d_out, float* const* d_m
 int mdl_got_bwd_finish_multi(int np, const float* const* V, const float* const* Q, float* const* dV, float* const* dQ,
                              const float* const* d_minmax_total, const int* k, const int* n, int d, void* const* ws, void* stream);
 
+/* Tiled class of GOT: the same arguments, return codes, semantics and workspace contract as the six mdl_got_* entry points above, for
+ * 1 <= n <= 4096 and 1 <= d <= 4096 at any k (MDL_E_UNSUPPORTED beyond; n = 0 or k = 0 gives zero outputs and gradients).  The shapes
+ * of the resident classes are included, so the two can be compared.  Many workgroups share one case and meet only at kernel
+ * boundaries (csrc/got_tiled.hip): the IPOT sweeps run as panels of 16 rows per workgroup with the column sums of an iteration merged
+ * by the next launch (two launches per iteration), the products on 128 x 128 matrix-core tiles.  Deterministic (fixed-order merges, no
+ * atomics).  The workspace holds the same tape as the resident classes, ~151 n^2 floats per case (0.6 GB at n = 1024, 10 GB at
+ * n = 4096). */
+int64_t mdl_got_tiled_ws_bytes(int k, int n, int d);
+int mdl_got_tiled_fwd(const float* V, const float* Q, float* out, float* minmax_out, const float* minmax_in,
+                      int k, int n, int d, void* ws, void* stream);
+int mdl_got_tiled_extrema(const float* V, const float* Q, float* minmax_out, int k, int n, int d, void* ws, void* stream);
+int mdl_got_tiled_bwd_begin(const float* d_out, float* d_minmax, int k, int n, int d, void* ws, void* stream);
+int mdl_got_tiled_bwd_finish(const float* V, const float* Q, float* dV, float* dQ, const float* d_minmax_total,
+                             int k, int n, int d, void* ws, void* stream);
+int mdl_got_tiled_bwd(const float* V, const float* Q, const float* d_out, float* dV, float* dQ, int k, int n, int d,
+                      void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * bf16 mode -- the reference's `precision: bfloat16` runs (torch autocast around the forward,
  * madeleine/utils/trainer.py:101-103, scripts/launch_pretrain_withStainEncodings.sh): activations are STORED in
@@ -581,10 +598,15 @@ int mdl_abmil_attnpool_bwd_split(const void* E_img, int64_t e_rsb, const float* 
  *                                                                                                               1 (2k WGs), 2 (+ 4k)
  *   MDL_PLAN_INFONCE_NEG         M, D        1: 16-byte loads of Neg (D % 4 == 0)      0                        LSE partials per row
  *                                            0: 4-byte loads
+ *   MDL_PLAN_GOT_TILED           n, d        rows per sweep panel (16)                 0                        launches per IPOT
+ *                                                                                                               iteration (2)
  * [SPLITS] token splits S of the dW-type contraction (1, with TPS = CHUNK = 0, where there are none), [TPS] tokens per split, [EMPTY] splits that hold no
  * token ((s * tps >= T)), [CHUNK] tokens per chunk of the contraction's main loop (tps is a multiple of it).
  * MDL_PLAN_INFONCE_NEG (T = N rows): [SPLITS] splits over M of the unpaired dQ contraction (1024 negatives each), [CHUNK] waves per row
- * of the paired kernels (64 negatives each); MDL_E_UNSUPPORTED where the unpaired launcher would refuse the geometry. */
+ * of the paired kernels (64 negatives each); MDL_E_UNSUPPORTED where the unpaired launcher would refuse the geometry.
+ * MDL_PLAN_GOT_TILED (T = cases k): [SPLITS] row panels per case (sweep workgroups per case and branch), [TPS] output tile edge of the
+ * products (128), [EMPTY] product tiles per case of an n x n product, [CHUNK] columns per sweep chunk (256); MDL_E_UNSUPPORTED for
+ * n > 4096 or d > 4096. */
 #define MDL_PLAN_GATE_FP32_BWD 1
 #define MDL_PLAN_GATE_SPLIT_FWD 2
 #define MDL_PLAN_GATE_SPLIT_BWD 3
@@ -596,6 +618,7 @@ int mdl_abmil_attnpool_bwd_split(const void* E_img, int64_t e_rsb, const float* 
 #define MDL_PLAN_LINEAR_BF16_BWD 9
 #define MDL_PLAN_GOT 10
 #define MDL_PLAN_INFONCE_NEG 11
+#define MDL_PLAN_GOT_TILED 12
 #define MDL_PLAN_VARIANT 0
 #define MDL_PLAN_PERSIST 1
 #define MDL_PLAN_SPLITS 2

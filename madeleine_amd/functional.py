@@ -1494,54 +1494,74 @@ def info_nce_neg_rows(Q, P, Neg, temperature, paired):
 # --------------------------------------------------------------------------------------------------
 # G0-G3: graph optimal transport
 # --------------------------------------------------------------------------------------------------
+class _GotFamily:
+    """One GOT size class on the C ABI: the prefix of its six entry points (mdl_got / mdl_got_tiled), the _timed names of its calls and
+    the message of its refusal."""
+
+    def __init__(self, prefix, timed, refusal):
+        self.prefix, self.timed, self.refusal = prefix, timed, refusal
+
+    def fn(self, lib, suffix):
+        return getattr(lib, self.prefix + suffix)
+
+
+GOT_RESIDENT = _GotFamily("mdl_got", "got",
+                          "madeleine_amd.GOT supports n <= 512 tokens per bag and d <= 128 (got n=%d, d=%d); "
+                          "the reference calls it with subsample=256 (trainer.py:44)")
+GOT_TILED = _GotFamily("mdl_got_tiled", "got_tiled",
+                       "the tiled GOT class supports n <= 4096 tokens per bag and d <= 4096 (got n=%d, d=%d)")
+
+
 class GOTFn(torch.autograd.Function):
     """out[2] = (sum_b WD_b, sum_b GWD_b) for token sets V,Q [k,n,d] (loss.py:278-302 after the sub-sampling).
 
     minmax_in (optional float[6] device tensor) replaces the batch-local threshold extrema (data-parallel path);
-    the second output is this call's own extrema [6] (non-differentiable)."""
+    the second output is this call's own extrema [6] (non-differentiable).  `fam` selects the size class (entry-point family):
+    GOT_RESIDENT (the default, functional.got) or GOT_TILED (functional.got_tiled)."""
 
     @staticmethod
-    def forward(ctx, V, Q, minmax_in, reduce_dminmax):
+    def forward(ctx, V, Q, minmax_in, reduce_dminmax, fam=GOT_RESIDENT):
         _require(V, "v_")
         _require(Q, "q_")
         if V.shape != Q.shape or V.dim() != 3:
             raise ValueError("GOT expects two token tensors of identical shape [k, n, d]")
         lib = _native.lib()
         k, n, d = V.shape
-        nbytes = lib.mdl_got_ws_bytes(k, n, d)
+        nbytes = fam.fn(lib, "_ws_bytes")(k, n, d)
         if nbytes == -3:
-            raise NotImplementedError("madeleine_amd.GOT supports n <= 512 tokens per bag and d <= 128 (got n=%d, d=%d); "
-                                      "the reference calls it with subsample=256 (trainer.py:44)" % (n, d))
+            raise NotImplementedError(fam.refusal % (n, d))
         ws = _ws(nbytes, V.device)
         out = torch.empty(2, device=V.device, dtype=torch.float32)
         mm = torch.empty(6, device=V.device, dtype=torch.float32)
-        with _timed("got_fwd"):
-            rc = lib.mdl_got_fwd(_ptr(V), _ptr(Q), _ptr(out), _ptr(mm), _ptr(minmax_in), k, n, d, _ptr(ws), _stream())
-        _native.check(rc, "mdl_got_fwd")
+        with _timed(fam.timed + "_fwd"):
+            rc = fam.fn(lib, "_fwd")(_ptr(V), _ptr(Q), _ptr(out), _ptr(mm), _ptr(minmax_in), k, n, d, _ptr(ws), _stream())
+        _native.check(rc, fam.prefix + "_fwd")
         ctx.save_for_backward(V, Q, ws)
         ctx.reduce_dminmax = reduce_dminmax
+        ctx.fam = fam
         ctx.mark_non_differentiable(mm)
         return out, mm
 
     @staticmethod
     def backward(ctx, d_out, _d_mm):
         V, Q, ws = ctx.saved_tensors
+        fam = ctx.fam
         lib = _native.lib()
         k, n, d = V.shape
         dV, dQ = torch.empty_like(V), torch.empty_like(Q)
         d_out = d_out.contiguous()
         if ctx.reduce_dminmax is None:
-            with _timed("got_bwd"):
-                rc = lib.mdl_got_bwd(_ptr(V), _ptr(Q), _ptr(d_out), _ptr(dV), _ptr(dQ), k, n, d, _ptr(ws), _stream())
-            _native.check(rc, "mdl_got_bwd")
+            with _timed(fam.timed + "_bwd"):
+                rc = fam.fn(lib, "_bwd")(_ptr(V), _ptr(Q), _ptr(d_out), _ptr(dV), _ptr(dQ), k, n, d, _ptr(ws), _stream())
+            _native.check(rc, fam.prefix + "_bwd")
         else:
             dmm = torch.empty(6, device=V.device, dtype=torch.float32)
-            rc = lib.mdl_got_bwd_begin(_ptr(d_out), _ptr(dmm), k, n, d, _ptr(ws), _stream())
-            _native.check(rc, "mdl_got_bwd_begin")
+            rc = fam.fn(lib, "_bwd_begin")(_ptr(d_out), _ptr(dmm), k, n, d, _ptr(ws), _stream())
+            _native.check(rc, fam.prefix + "_bwd_begin")
             dmm = ctx.reduce_dminmax(dmm).contiguous()      # e.g. all_reduce(SUM) over ranks
-            rc = lib.mdl_got_bwd_finish(_ptr(V), _ptr(Q), _ptr(dV), _ptr(dQ), _ptr(dmm), k, n, d, _ptr(ws), _stream())
-            _native.check(rc, "mdl_got_bwd_finish")
-        return dV, dQ, None, None
+            rc = fam.fn(lib, "_bwd_finish")(_ptr(V), _ptr(Q), _ptr(dV), _ptr(dQ), _ptr(dmm), k, n, d, _ptr(ws), _stream())
+            _native.check(rc, fam.prefix + "_bwd_finish")
+        return dV, dQ, None, None, None
 
 
 def got_extrema(V, Q):
@@ -1576,6 +1596,22 @@ def _got_set_exchange_timeout(ws, value: float = 1.0) -> None:
 def got(V, Q, minmax_in=None, reduce_dminmax=None, return_extrema=False):
     out, mm = GOTFn.apply(V, Q, minmax_in, reduce_dminmax)
     return (out, mm) if return_extrema else out
+
+
+def got_tiled(V, Q, minmax_in=None, reduce_dminmax=None, return_extrema=False):
+    """functional.got on the tiled size class (1 <= n <= 4096, 1 <= d <= 4096, any k; csrc/got_tiled.hip): same contract."""
+    out, mm = GOTFn.apply(V, Q, minmax_in, reduce_dminmax, GOT_TILED)
+    return (out, mm) if return_extrema else out
+
+
+def got_tiled_supported(k: int, n: int, d: int) -> bool:
+    """True when the tiled class accepts [k, n, d] (mdl_got_tiled_ws_bytes does not refuse it)."""
+    return _native.lib().mdl_got_tiled_ws_bytes(k, n, d) >= 0
+
+
+def got_resident_supported(k: int, n: int, d: int) -> bool:
+    """True when the resident classes accept [k, n, d] (mdl_got_ws_bytes does not refuse it)."""
+    return _native.lib().mdl_got_ws_bytes(k, n, d) >= 0
 
 
 class HipGotImpl:

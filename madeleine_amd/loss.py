@@ -108,5 +108,23 @@ def GOT(v_, q_, subsample=None):
         patch_indices = torch.randperm(v_.shape[0])[:subsample].to(v_.device)
         v_ = v_.index_select(1, patch_indices)
         q_ = q_.index_select(1, patch_indices)
-    out = MF.got(v_.float().contiguous(), q_.float().contiguous())
+    v, q = v_.float().contiguous(), q_.float().contiguous()
+    route = got_route(*v.shape) if v.dim() == 3 else "resident"
+    if route == "resident":
+        out = MF.got(v, q)
+    elif route == "tiled":
+        out = MF.got_tiled(v, q)
+    else:
+        raise NotImplementedError("madeleine_amd.GOT supports n <= 4096 tokens per bag and d <= 4096 (got n=%d, d=%d)"
+                                  % tuple(v.shape[1:]))
     return out[1] + out[0]
+
+
+def got_route(k, n, d):
+    """Size class GOT() uses for [k, n, d] after the sub-sampling: 'resident' where mdl_got_ws_bytes accepts the shape (functional.got,
+    the training path's class), else 'tiled' where the tiled class accepts it, else 'unsupported'."""
+    if MF.got_resident_supported(k, n, d):
+        return "resident"
+    if MF.got_tiled_supported(k, n, d):
+        return "tiled"
+    return "unsupported"
