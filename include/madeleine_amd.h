@@ -373,6 +373,23 @@ int mdl_got_tiled_bwd_finish(const float* V, const float* Q, float* dV, float* d
                              int k, int n, int d, void* ws, void* stream);
 int mdl_got_tiled_bwd(const float* V, const float* Q, const float* d_out, float* dV, float* dQ, int k, int n, int d,
                       void* ws, void* stream);
+/* The tiled class between token sets of different sizes: V [k, n, d], Q and dQ [k, m, d], sizes in the order (k, n, m, d), everything
+ * else as in the six functions above, which are the m = n case of these (same code, same bits).  1 <= n, m <= 4096 and 1 <= d <= 4096
+ * (MDL_E_UNSUPPORTED beyond, for each of them); k = 0, n = 0 or m = 0 gives zero outputs and zero gradients (dV and dQ are cleared).
+ * The cross cost and every transport plan are n x m, the intra costs n x n and m x m; IPOT uses sigma_0 = 1/m,
+ * delta_i = 1 / (n sum_j Q_ij sigma_j), sigma_j = 1 / (m sum_i Q_ij delta_i); Gromov-Wasserstein gamma_0 = 1/(n m), p = 1/n, q = 1/m.
+ * GOT(V, Q) != GOT(Q, V).  The sweeps' row panels run over n: a shape with n << m uses few workgroups per case.  Workspace per case:
+ * ~144 n up4(m) floats (the tape and the n x m intermediates) + 3 n up4(n) + 4 m up4(m) (1.5 GB at n = 4096, m = 512 against 10 GB at
+ * n = m = 4096). */
+int64_t mdl_got_tiled_rect_ws_bytes(int k, int n, int m, int d);
+int mdl_got_tiled_rect_fwd(const float* V, const float* Q, float* out, float* minmax_out, const float* minmax_in,
+                           int k, int n, int m, int d, void* ws, void* stream);
+int mdl_got_tiled_rect_extrema(const float* V, const float* Q, float* minmax_out, int k, int n, int m, int d, void* ws, void* stream);
+int mdl_got_tiled_rect_bwd_begin(const float* d_out, float* d_minmax, int k, int n, int m, int d, void* ws, void* stream);
+int mdl_got_tiled_rect_bwd_finish(const float* V, const float* Q, float* dV, float* dQ, const float* d_minmax_total,
+                                  int k, int n, int m, int d, void* ws, void* stream);
+int mdl_got_tiled_rect_bwd(const float* V, const float* Q, const float* d_out, float* dV, float* dQ, int k, int n, int m, int d,
+                           void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * bf16 mode -- the reference's `precision: bfloat16` runs (torch autocast around the forward,
@@ -600,13 +617,15 @@ int mdl_abmil_attnpool_bwd_split(const void* E_img, int64_t e_rsb, const float* 
  *                                            0: 4-byte loads
  *   MDL_PLAN_GOT_TILED           n, d        rows per sweep panel (16)                 0                        launches per IPOT
  *                                                                                                               iteration (2)
+ *   MDL_PLAN_GOT_TILED_RECT      n, m        as MDL_PLAN_GOT_TILED                     0                        as MDL_PLAN_GOT_TILED
  * [SPLITS] token splits S of the dW-type contraction (1, with TPS = CHUNK = 0, where there are none), [TPS] tokens per split, [EMPTY] splits that hold no
  * token ((s * tps >= T)), [CHUNK] tokens per chunk of the contraction's main loop (tps is a multiple of it).
  * MDL_PLAN_INFONCE_NEG (T = N rows): [SPLITS] splits over M of the unpaired dQ contraction (1024 negatives each), [CHUNK] waves per row
  * of the paired kernels (64 negatives each); MDL_E_UNSUPPORTED where the unpaired launcher would refuse the geometry.
  * MDL_PLAN_GOT_TILED (T = cases k): [SPLITS] row panels per case (sweep workgroups per case and branch), [TPS] output tile edge of the
  * products (128), [EMPTY] product tiles per case of an n x n product, [CHUNK] columns per sweep chunk (256); MDL_E_UNSUPPORTED for
- * n > 4096 or d > 4096. */
+ * n > 4096 or d > 4096.  MDL_PLAN_GOT_TILED_RECT (a = n tokens of V, b = m tokens of Q): the same fields with [SPLITS] = ceil(n / 16)
+ * and [EMPTY] = ceil(n / 128) ceil(m / 128), the tiles of an n x m product; MDL_E_UNSUPPORTED for n > 4096 or m > 4096. */
 #define MDL_PLAN_GATE_FP32_BWD 1
 #define MDL_PLAN_GATE_SPLIT_FWD 2
 #define MDL_PLAN_GATE_SPLIT_BWD 3
@@ -619,6 +638,7 @@ int mdl_abmil_attnpool_bwd_split(const void* E_img, int64_t e_rsb, const float* 
 #define MDL_PLAN_GOT 10
 #define MDL_PLAN_INFONCE_NEG 11
 #define MDL_PLAN_GOT_TILED 12
+#define MDL_PLAN_GOT_TILED_RECT 13
 #define MDL_PLAN_VARIANT 0
 #define MDL_PLAN_PERSIST 1
 #define MDL_PLAN_SPLITS 2

@@ -75,6 +75,13 @@ SIGNATURES = {
     "mdl_got_tiled_bwd": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_p, c_p]),
     "mdl_got_tiled_bwd_begin": (i32, [c_f, c_f, i32, i32, i32, c_p, c_p]),
     "mdl_got_tiled_bwd_finish": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_p, c_p]),
+    # ... between token sets of different sizes: (k, n, m, d)
+    "mdl_got_tiled_rect_ws_bytes": (i64, [i32, i32, i32, i32]),
+    "mdl_got_tiled_rect_fwd": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, c_p, c_p]),
+    "mdl_got_tiled_rect_extrema": (i32, [c_f, c_f, c_f, i32, i32, i32, i32, c_p, c_p]),
+    "mdl_got_tiled_rect_bwd": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, c_p, c_p]),
+    "mdl_got_tiled_rect_bwd_begin": (i32, [c_f, c_f, i32, i32, i32, i32, c_p, c_p]),
+    "mdl_got_tiled_rect_bwd_finish": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, c_p, c_p]),
     # several problems per launch: host arrays of np device pointers / ints
     "mdl_got_extrema_multi": (i32, [i32, c_p, c_p, c_p, c_p, c_p, i32, c_p, c_p]),
     "mdl_got_fwd_multi": (i32, [i32, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p, c_p]),
@@ -201,7 +208,7 @@ def check(rc: int, what: str):
 # mdl_dispatch_plan products / fields (include/madeleine_amd.h)
 PLAN_PRODUCTS = {"gate_fp32_bwd": 1, "gate_split_fwd": 2, "gate_split_bwd": 3, "gate_bf16_fwd": 4, "gate_bf16_bwd": 5, "split_tn": 6,
                  "linear_fp32_bwd": 7, "linear_bf16_fwd": 8, "linear_bf16_bwd": 9, "got": 10, "infonce_neg": 11,
-                 "got_tiled": 12}
+                 "got_tiled": 12, "got_tiled_rect": 13}
 PLAN_FIELDS = ("variant", "persist", "splits", "tps", "empty", "chunk", "extra")
 
 

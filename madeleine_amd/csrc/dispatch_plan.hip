@@ -11,7 +11,7 @@ int plan_linear_fp32_bwd(int64_t T, int N, int K, int64_t* o);       // linear_f
 int plan_linear_bf16(int product, int64_t T, int N, int K, int64_t* o);   // linear_bf16.hip
 int plan_got(int64_t k, int n, int cus, int64_t* o);                 // got.hip
 int plan_infonce_neg(int64_t N, int M, int D, int64_t* o);           // infonce.hip
-int plan_got_tiled(int64_t k, int n, int d, int64_t* o);             // got_tiled.hip
+int plan_got_tiled(int64_t k, int n, int m, int d, int64_t* o);      // got_tiled.hip
 }  // namespace mdl
 
 using namespace mdl;
@@ -38,7 +38,8 @@ extern "C" int mdl_dispatch_plan(int product, int64_t T, int a, int b, int cus, 
     case MDL_PLAN_LINEAR_BF16_BWD: rc = plan_linear_bf16(product, T, a, b, o); break;
     case MDL_PLAN_GOT: rc = plan_got(T, a, cus, o); break;
     case MDL_PLAN_INFONCE_NEG: rc = plan_infonce_neg(T, a, b, o); break;
-    case MDL_PLAN_GOT_TILED: rc = plan_got_tiled(T, a, b, o); break;
+    case MDL_PLAN_GOT_TILED: rc = plan_got_tiled(T, a, a, b, o); break;
+    case MDL_PLAN_GOT_TILED_RECT: rc = plan_got_tiled(T, a, b, 1, o); break;   // a = n, b = m; no field depends on d
     default: rc = MDL_E_ARG;
     }
     if (rc) return rc;

@@ -1,17 +1,22 @@
-// got_tiled.hip -- the TILED size class of GOT (1 <= n <= 4096 tokens, 1 <= d <= 4096): the same forward and reverse sweep as
+// got_tiled.hip -- the TILED size class of GOT (1 <= n, m <= 4096 tokens, 1 <= d <= 4096): the same forward and reverse sweep as
 // got_impl.inc (see its header for the algebra: IPOT, Gromov-Wasserstein, the one-matrix-per-iteration reverse with Y_t = gQ_t . Q_t),
 // organised for shapes where one case holds more work than a workgroup -- or two -- can do.
 //
+// The two token sets may differ in size: V is [k, n, d], Q is [k, m, d] (mdl_got_tiled_rect_*; the square entry points pass m = n).
+// The algebra with the sizes kept apart: C = 1 - V^ Q^T and every plan are n x m, Cs n x n, Ct m x m; IPOT has sigma_0 = 1/m,
+// delta_i = 1 / (n sum_j Q_ij sigma_j), sigma_j = 1 / (m sum_i Q_ij delta_i), so the reverse carries -n delta^2 on the row side and
+// -m sigma^2 on the column side; GW has gamma_0 = 1/(n m), rs = Cs^2 1/n, rt = Ct^2 1/m, C_gamma = rs 1^T + 1 rt^T - 2 Cs gamma Ct^T.
+//
 // Organisation: many workgroups share one case and meet only at kernel boundaries.
 //   * SWEEPS (IPOT forward / reverse): a 256-thread workgroup owns a panel of RP = 16 rows of one case and branch (grid = panels x
-//     cases x branches).  A row's reductions are wave-local (each wave owns 4 rows); the column sums an iteration needs are written as
-//     per-panel partials [panel][n] and merged, in panel order, by the next launch.  Two launches per IPOT iteration: a row pass
-//     (reads A and the previous plan, writes the next plan into the tape, row scaling delta, column partials) and a merge (column
-//     scaling sigma).  The forward fuses "write T_{t-1}" into the row pass of iteration t, so a pass reads A and T_{t-2} once
+//     cases x branches; the panels run over the n rows, whatever m is).  A row's reductions are wave-local (each wave owns 4 rows);
+//     the column sums an iteration needs are written as per-panel partials [panel][m] and merged, in panel order, by the next launch.
+//     Two launches per IPOT iteration: a row pass (reads A and the previous plan, writes the next plan into the tape, row scaling
+//     delta, column partials) and a merge (column scaling sigma).  The forward fuses "write T_{t-1}" into the row pass of iteration t, so a pass reads A and T_{t-2} once
 //     (re-read from L2 by the second phase of the pass, which needs the row sums of the first) and writes T_{t-1} once.
 //     The reverse keeps the accumulator H = sum_t t W_t (+ iters Y_{iters+1}) in the workspace (read-modify-write per iteration) instead
 //     of registers, and the per-row sums of Y in a workspace vector owned by the row's workgroup.
-//   * PRODUCTS (n x n x d costs, C_gamma, their adjoints, the cost backward): 128 x 128 output tiles per 256-thread workgroup on
+//   * PRODUCTS (the costs, C_gamma, their adjoints, the cost backward): 128 x 128 output tiles per 256-thread workgroup on
 //     v_mfma_f32_32x32x2_f32 (each wave a 64 x 64 block of 2 x 2 accumulators), K-chunks of 16 staged through LDS with a register
 //     prefetch of the next chunk; up to three independent products (jobs) per launch, up to three accumulated terms per product.
 //   * No workgroup waits for another one of the same launch, no atomics: every cross-workgroup sum (column sums, extrema, tie counts,
@@ -45,72 +50,91 @@ __host__ __device__ inline int64_t up4(int64_t x) { return (x + 3) & ~(int64_t)3
 __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---------------------------------------------------------------------------------------------------------
-// workspace: k per-case regions, then the global partials.  Every n x n matrix has row stride ld = up4(n) (16-byte rows).
+// workspace: k per-case regions, then the global partials.  V has n tokens, Q has m; a matrix with c columns has row stride up4(c)
+// (16-byte rows).  Three matrix shapes: cross (n x m: C, the plans, the tapes), source (n x n: Cs) and target (m x m: Ct); vectors of
+// length n (row quantities: delta, rs, Rv) and of length m (column quantities: sigma, rt, Cv, ga).  With m = n all of them coincide.
 // ---------------------------------------------------------------------------------------------------------
 struct Lay {
-    int64_t ld, nn, nv, nd, P, tn, tiles;
+    int64_t ldn, ldm;            // row strides of matrices with n / m columns
+    int64_t nm, nn, mm;          // elements of a cross / source / target matrix
+    int64_t nvn, nvm;            // elements of a length-n / length-m vector
+    int64_t P, PX;               // row panels over n (sweeps); over max(n, m) (kernels that walk all three cost matrices)
+    int64_t tm;                  // product tile columns over m
+    int64_t tiles[3], ext[3];    // product tiles per case of C0, Cs0, Ct0; global offsets of their extrema partials
     int64_t oVh, oQh, orV, orQ, oC0, oCs0, oCt0, oC, oCs, oCt, ors, ort, oAw, oAg, oWT, oWd, oWs, oCg, oGT, oGd, oGs, oP1, oP2, oP3,
         oG, ogT, ogCs, ogCt, ogC0, ogVh, ogQh, ogrs, ogrt, oRv, oCv, oga, ocp, ocpr;
     int64_t per_case;
-    int64_t g_ext, g_cnt, g_wd, g_gwd, g_gthr, g_thr, g_end;
+    int64_t g_cnt, g_wd, g_gwd, g_gthr, g_thr, g_end;
 };
 
-__host__ __device__ inline Lay layout(int k, int n, int d) {
+__host__ __device__ inline Lay layout(int k, int n, int m, int d) {
     Lay L;
-    L.ld = up4(n);
-    L.nn = (int64_t)n * L.ld;
-    L.nv = up4(n);
-    L.nd = up4((int64_t)n * d);
+    L.ldn = up4(n);
+    L.ldm = up4(m);
+    L.nm = (int64_t)n * L.ldm;
+    L.nn = (int64_t)n * L.ldn;
+    L.mm = (int64_t)m * L.ldm;
+    L.nvn = up4(n);
+    L.nvm = up4(m);
     L.P = cdiv(n, RP);
-    L.tn = cdiv(n, MT);
-    L.tiles = L.tn * L.tn;
-    const int64_t nn = L.nn, nv = L.nv, nd = L.nd, cp = 2 * L.P * L.ld;
+    L.PX = cdiv(n > m ? n : m, RP);
+    L.tm = cdiv(m, MT);
+    const int64_t tn = cdiv(n, MT);
+    L.tiles[0] = tn * L.tm;
+    L.tiles[1] = tn * tn;
+    L.tiles[2] = L.tm * L.tm;
+    const int64_t nm = L.nm, nn = L.nn, mm = L.mm, nvn = L.nvn, nvm = L.nvm, cp = 2 * L.P * L.ldm;
+    const int64_t ndn = up4((int64_t)n * d), ndm = up4((int64_t)m * d);
     int64_t o = 0;
-    L.oVh = o; o += nd;
-    L.oQh = o; o += nd;
-    L.orV = o; o += nv;
-    L.orQ = o; o += nv;
-    L.oC0 = o; o += nn;                          // raw costs (masks and extremum routing of the backward)
+    L.oVh = o; o += ndn;
+    L.oQh = o; o += ndm;
+    L.orV = o; o += nvn;
+    L.orQ = o; o += nvm;
+    L.oC0 = o; o += nm;                          // raw costs (masks and extremum routing of the backward)
     L.oCs0 = o; o += nn;
-    L.oCt0 = o; o += nn;
-    L.oC = o; o += nn;                           // thresholded costs
+    L.oCt0 = o; o += mm;
+    L.oC = o; o += nm;                           // thresholded costs
     L.oCs = o; o += nn;
-    L.oCt = o; o += nn;
-    L.ors = o; o += nv;                          // Cst vectors
-    L.ort = o; o += nv;
-    L.oAw = o; o += nn;                          // exp(-C / beta) of the Wasserstein IPOT
-    L.oAg = o; o += nn;                          // ... of the GW IPOT in flight
-    L.oWT = o; o += nn * WD_ITERS;               // tape: T_1..T_30
-    L.oWd = o; o += nv * WD_ITERS;               // delta_1..30
-    L.oWs = o; o += nv * (WD_ITERS + 1);         // sigma_0..30
-    L.oCg = o; o += nn * GW_OUTER;               // C_gamma of every outer iteration
-    L.oGT = o; o += nn * GW_OUTER * GW_INNER;
-    L.oGd = o; o += nv * GW_OUTER * GW_INNER;
-    L.oGs = o; o += nv * GW_OUTER * (GW_INNER + 1);
-    L.oP1 = o; o += nn;                          // product intermediates; routed cost gradients in the backward finish
-    L.oP2 = o; o += nn;
-    L.oP3 = o; o += nn;
-    L.oG = o; o += nn;                           // d/dC_gamma (the GW reverse's H accumulator)
-    L.ogT = o; o += nn;                          // d/dgamma
+    L.oCt = o; o += mm;
+    L.ors = o; o += nvn;                         // Cst vectors
+    L.ort = o; o += nvm;
+    L.oAw = o; o += nm;                          // exp(-C / beta) of the Wasserstein IPOT
+    L.oAg = o; o += nm;                          // ... of the GW IPOT in flight
+    L.oWT = o; o += nm * WD_ITERS;               // tape: T_1..T_30
+    L.oWd = o; o += nvn * WD_ITERS;              // delta_1..30
+    L.oWs = o; o += nvm * (WD_ITERS + 1);        // sigma_0..30
+    L.oCg = o; o += nm * GW_OUTER;               // C_gamma of every outer iteration
+    L.oGT = o; o += nm * GW_OUTER * GW_INNER;
+    L.oGd = o; o += nvn * GW_OUTER * GW_INNER;
+    L.oGs = o; o += nvm * GW_OUTER * (GW_INNER + 1);
+    L.oP1 = o; o += nm;                          // product intermediates (n x m); routed cost gradients in the backward finish:
+    L.oP2 = o; o += nm > nn ? nm : nn;           //   P1 = d/dC0 (n x m), P2 = d/dCs0 (n x n), P3 = d/dCt0 (m x m)
+    L.oP3 = o; o += mm;
+    L.oG = o; o += nm;                           // d/dC_gamma (the GW reverse's H accumulator)
+    L.ogT = o; o += nm;                          // d/dgamma
     L.ogCs = o; o += nn;
-    L.ogCt = o; o += nn;
-    L.ogC0 = o; o += nn;                         // d/dC (the WD reverse's H accumulator), then d/dC0
-    L.ogVh = o; o += nd;
-    L.ogQh = o; o += nd;
-    L.ogrs = o; o += nv;
-    L.ogrt = o; o += nv;
-    L.oRv = o; o += 2 * nv;                      // per branch: row sums of Y (reverse), column sums of Y, ga
-    L.oCv = o; o += 2 * nv;
-    L.oga = o; o += 2 * nv;
-    L.ocp = o; o += 2 * cp;                      // per branch: two sets of per-panel column partials [P][ld]
-    L.ocpr = o; o += L.P * L.ld;                 // column partials of the GW products' Cst gradient
+    L.ogCt = o; o += mm;
+    L.ogC0 = o; o += nm;                         // d/dC (the WD reverse's H accumulator), then d/dC0
+    L.ogVh = o; o += ndn;
+    L.ogQh = o; o += ndm;
+    L.ogrs = o; o += nvn;
+    L.ogrt = o; o += nvm;
+    L.oRv = o; o += 2 * nvn;                     // per branch: row sums of Y (reverse), column sums of Y, ga
+    L.oCv = o; o += 2 * nvm;
+    L.oga = o; o += 2 * nvm;
+    L.ocp = o; o += 2 * cp;                      // per branch: two sets of per-panel column partials [P][ldm]
+    L.ocpr = o; o += L.P * L.ldm;                // column partials of the GW products' Cst gradient
     L.per_case = o;
     int64_t g = (int64_t)k * L.per_case;
-    L.g_ext = g; g += up4((int64_t)k * 3 * L.tiles * 2);   // per (kind, case, tile): (min, max)
-    L.g_cnt = g; g += up4((int64_t)k * L.P * 6);           // per (case, panel): tie counts of the six extrema
+    for (int q = 0; q < 3; ++q) {                // per (kind, case, tile): (min, max)
+        L.ext[q] = g;
+        g += (int64_t)k * L.tiles[q] * 2;
+    }
+    g = up4(g);
+    L.g_cnt = g; g += up4((int64_t)k * L.PX * 6);          // per (case, panel): tie counts of the six extrema
     L.g_wd = g; g += up4((int64_t)k * L.P);                // per (case, panel): Wasserstein distance partial
-    L.g_gwd = g; g += up4((int64_t)k * L.tiles);           // per (case, tile): GW distance partial
-    L.g_gthr = g; g += up4((int64_t)k * L.P * 3);          // per (case, panel): threshold-gradient partials
+    L.g_gwd = g; g += up4((int64_t)k * L.tiles[0]);        // per (case, tile): GW distance partial
+    L.g_gthr = g; g += up4((int64_t)k * L.PX * 3);         // per (case, panel): threshold-gradient partials
     L.g_thr = g; g += 32;   // [0..5] extrema used, [6..8] thresholds, [9..14] tie counts, [15..17] threshold gradients
     L.g_end = g;
     return L;
@@ -148,19 +172,39 @@ __device__ __forceinline__ float block_sum_array(const float* src, int64_t cnt, 
     return block_sum4(s, red);
 }
 
+// Walk of the RP x ld elements of a row panel by the workgroup, element e = r ld + j taken by thread e % NT in increasing e (the
+// order the per-thread partial sums of tl_bwd_final_kernel are defined by), without a division per element.
+struct PanelWalk {
+    int e, r, j, ld;
+    __device__ __forceinline__ PanelWalk(int64_t ld_) : e((int)threadIdx.x), ld((int)ld_) {
+        r = e / ld;
+        j = e - r * ld;
+    }
+    __device__ __forceinline__ bool in() const { return r < RP; }
+    __device__ __forceinline__ void next() {
+        e += NT;
+        j += NT;
+        while (j >= ld) {
+            j -= ld;
+            ++r;
+        }
+    }
+};
+
 // ---------------------------------------------------------------------------------------------------------
 // K1: normalised tokens and their norms (one wave per token row)
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NT) void tl_norm_kernel(const float* __restrict__ V, const float* __restrict__ Q, float* ws, const Lay L,
-                                                     int n, int d) {
-    const int64_t R = cdiv(n, 4);
+                                                     int n, int m, int d) {
+    const int64_t R = cdiv(n > m ? n : m, 4);
     const int64_t b = blockIdx.x / R;
     const int i = (int)(blockIdx.x % R) * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (i >= n) return;   // no barrier in this kernel
     float* base = ws + b * L.per_case;
 #pragma unroll 1
     for (int s = 0; s < 2; ++s) {
-        const float* src = (s ? Q : V) + (b * n + i) * (int64_t)d;
+        const int rows = s ? m : n;
+        if (i >= rows) continue;   // wave-uniform; no barrier in this kernel
+        const float* src = (s ? Q : V) + (b * rows + i) * (int64_t)d;
         float ss = 0.f;
         for (int e = lane; e < d; e += 64) ss += src[e] * src[e];
         ss = wave_sum(ss);
@@ -173,17 +217,20 @@ __global__ __launch_bounds__(NT) void tl_norm_kernel(const float* __restrict__ V
 
 // ---------------------------------------------------------------------------------------------------------
 // K2: products on the matrix cores.  C[M x N] (per case) = epilogue(sum over terms of op(A_t) op(B_t)), op = transpose or not.
-// A term operand with offset < 0 is the constant matrix (ca / cb): the uniform plan gamma_0 = 1/n^2 of the first GW iteration.
+// A term operand with offset < 0 is the constant matrix (ca / cb): the uniform plan gamma_0 = 1/(n m) of the first GW iteration.
+// The jobs of a launch may differ in shape (C0 is n x m, Cs0 n x n, Ct0 m x m): the grid covers the job with the most tiles and the
+// workgroups beyond a job's own tiles leave at once.
 // ---------------------------------------------------------------------------------------------------------
 enum { GM_RAW = 0, GM_STORE = 1, GM_ACC = 2, GM_CG = 3, GM_GWD = 4 };
 struct GTerm {
     int64_t oA, oB, lda, ldb;   // per-case offsets (< 0: constant operand); A(i,k) = ta ? A[k lda + i] : A[i lda + k]; B likewise
     float ca, cb;
-    int ta, tb;
+    int ta, tb, K;
 };
 struct GJob {
     GTerm t[3];
     int nt, mode;
+    int M, N, tn, tiles;        // output shape, tile columns, tiles per case
     float alpha;
     int64_t oC, ldc;            // output (per case)
     int64_t oX, oY, oZ;         // GM_CG / GM_GWD: rs, rt (vectors), gamma (GM_GWD)
@@ -193,7 +240,7 @@ constexpr int GMAXJ = 3;
 struct GArgs {
     float* ws;
     int64_t per_case;
-    int M, N, K, tn, tiles;
+    int k;
     GJob j[GMAXJ];
 };
 
@@ -202,13 +249,14 @@ __global__ __launch_bounds__(NT) void tl_gemm_kernel(const GArgs g) {
     __shared__ float ys[MK * LDX];
     __shared__ float red[8];
     const GJob& J = g.j[blockIdx.y];
-    const int64_t b = blockIdx.x / g.tiles;
-    const int tile = (int)(blockIdx.x % g.tiles);
-    const int i0 = (tile / g.tn) * MT, j0 = (tile % g.tn) * MT;
+    const int64_t b = blockIdx.x / J.tiles;
+    if (b >= g.k) return;   // workgroup-uniform, before any barrier
+    const int tile = (int)(blockIdx.x % J.tiles);
+    const int i0 = (tile / J.tn) * MT, j0 = (tile % J.tn) * MT;
     float* base = g.ws + b * g.per_case;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
     const int bi0 = (wave >> 1) * 64, bj0 = (wave & 1) * 64;
-    const int M = g.M, N = g.N, K = g.K;
+    const int M = J.M, N = J.N;
     f32x16 acc[2][2];
 #pragma unroll
     for (int u = 0; u < 2; ++u)
@@ -224,6 +272,7 @@ __global__ __launch_bounds__(NT) void tl_gemm_kernel(const GArgs g) {
         const float* __restrict__ A = T.oA >= 0 ? base + T.oA : nullptr;
         const float* __restrict__ Bm = T.oB >= 0 ? base + T.oB : nullptr;
         const bool ta = T.ta, tb = T.tb;
+        const int K = T.K;
         auto gload = [&](int k0) {
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
@@ -316,13 +365,13 @@ __global__ __launch_bounds__(NT) void tl_gemm_kernel(const GArgs g) {
         }
         __syncthreads();
         if (tid == 0) {
-            float* o = g.ws + J.gpart + (b * g.tiles + tile) * 2;
+            float* o = g.ws + J.gpart + (b * J.tiles + tile) * 2;
             o[0] = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
             o[1] = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
         }
     } else if (mode == GM_GWD) {
         const float s = block_sum4(sacc, red);
-        if (tid == 0) g.ws[J.gpart + b * g.tiles + tile] = s;
+        if (tid == 0) g.ws[J.gpart + b * J.tiles + tile] = s;
     }
 }
 
@@ -333,9 +382,9 @@ __global__ __launch_bounds__(NT) void tl_minmax_kernel(float* ws, const Lay L, i
     __shared__ float red[8];
     __shared__ float ext[6];
     const int tid = threadIdx.x;
-    const int64_t cnt = (int64_t)k * L.tiles;
     for (int m = 0; m < 3; ++m) {
-        const float* src = ws + L.g_ext + (int64_t)m * cnt * 2;
+        const int64_t cnt = (int64_t)k * L.tiles[m];
+        const float* src = ws + L.ext[m];
         float a = INFINITY, z = -INFINITY;
         for (int64_t e = tid; e < cnt; e += NT) {
             a = fminf(a, src[2 * e]);
@@ -368,58 +417,55 @@ __global__ __launch_bounds__(NT) void tl_minmax_kernel(float* ws, const Lay L, i
 // ---------------------------------------------------------------------------------------------------------
 // K4: thresholded costs, tie counts of the six extrema, Cst vectors rs, rt (per panel)
 // ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NT) void tl_thr_kernel(float* ws, const Lay L, int n) {
+// one row of one cost matrix (this wave): dst = relu(src - thr), ties with the two extrema, sum of squares of the result
+__device__ __forceinline__ float thr_row(const float* __restrict__ src, float* __restrict__ dst, int cols, float thr, float lo, float hi,
+                                         float& clo, float& chi) {
+    const int lane = threadIdx.x & 63;
+    float sq = 0.f;
+    for (int j = 4 * lane; j < cols; j += CW) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(src + j);
+        f32x4 c;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const bool ok = j + q < cols;
+            c[q] = ok ? fmaxf(x[q] - thr, 0.f) : 0.f;
+            clo += ok && x[q] == lo;
+            chi += ok && x[q] == hi;
+            sq = __builtin_fmaf(c[q], c[q], sq);   // fused on purpose: the rounding of rs, rt must not depend on how the loop is compiled
+        }
+        *reinterpret_cast<f32x4*>(dst + j) = c;
+    }
+    return wave_sum(sq);
+}
+
+// grid: cases x panels over max(n, m) rows (C0 and Cs0 have n rows, Ct0 has m)
+__global__ __launch_bounds__(NT) void tl_thr_kernel(float* ws, const Lay L, int n, int m) {
     __shared__ float red[4];
-    const int64_t b = blockIdx.x / L.P, panel = blockIdx.x % L.P;
+    const int64_t b = blockIdx.x / L.PX, panel = blockIdx.x % L.PX;
     float* base = ws + b * L.per_case;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t ld = L.ld;
     float ex[6];
 #pragma unroll
-    for (int m = 0; m < 6; ++m) ex[m] = ws[L.g_thr + m];
+    for (int q = 0; q < 6; ++q) ex[q] = ws[L.g_thr + q];
     const float t0 = ws[L.g_thr + 6], t1 = ws[L.g_thr + 7], t2 = ws[L.g_thr + 8];
     float cnt[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
     for (int r = 0; r < RP / 4; ++r) {
-        const int i = (int)panel * RP + wave + 4 * r;
-        if (i >= n) break;   // wave-uniform; no barrier until the loop ends
-        float as = 0.f, at = 0.f;
-        for (int j = 4 * lane; j < n; j += CW) {
-            const int64_t e = i * ld + j;
-            const f32x4 x0 = *reinterpret_cast<const f32x4*>(base + L.oC0 + e);
-            const f32x4 xs = *reinterpret_cast<const f32x4*>(base + L.oCs0 + e);
-            const f32x4 xt = *reinterpret_cast<const f32x4*>(base + L.oCt0 + e);
-            f32x4 c, cs, ct;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const bool ok = j + q < n;
-                c[q] = ok ? fmaxf(x0[q] - t0, 0.f) : 0.f;
-                cs[q] = ok ? fmaxf(xs[q] - t1, 0.f) : 0.f;
-                ct[q] = ok ? fmaxf(xt[q] - t2, 0.f) : 0.f;
-                cnt[0] += ok && x0[q] == ex[0];
-                cnt[1] += ok && x0[q] == ex[1];
-                cnt[2] += ok && xs[q] == ex[2];
-                cnt[3] += ok && xs[q] == ex[3];
-                cnt[4] += ok && xt[q] == ex[4];
-                cnt[5] += ok && xt[q] == ex[5];
-                as += cs[q] * cs[q];
-                at += ct[q] * ct[q];
-            }
-            *reinterpret_cast<f32x4*>(base + L.oC + e) = c;
-            *reinterpret_cast<f32x4*>(base + L.oCs + e) = cs;
-            *reinterpret_cast<f32x4*>(base + L.oCt + e) = ct;
+        const int64_t i = panel * RP + wave + 4 * r;   // wave-uniform; no barrier until the loop ends
+        if (i < n) {
+            thr_row(base + L.oC0 + i * L.ldm, base + L.oC + i * L.ldm, m, t0, ex[0], ex[1], cnt[0], cnt[1]);
+            const float as = thr_row(base + L.oCs0 + i * L.ldn, base + L.oCs + i * L.ldn, n, t1, ex[2], ex[3], cnt[2], cnt[3]);
+            if (lane == 0) base[L.ors + i] = as / (float)n;   // rs_i = (1/n) sum_k Cs_ik^2  (loss.py:240)
         }
-        as = wave_sum(as);
-        at = wave_sum(at);
-        if (lane == 0) {
-            base[L.ors + i] = as / (float)n;   // rs_i = (1/n) sum_k Cs_ik^2 ; rt_j = (1/n) sum_l Ct_jl^2  (loss.py:240-241)
-            base[L.ort + i] = at / (float)n;
+        if (i < m) {
+            const float at = thr_row(base + L.oCt0 + i * L.ldm, base + L.oCt + i * L.ldm, m, t2, ex[4], ex[5], cnt[4], cnt[5]);
+            if (lane == 0) base[L.ort + i] = at / (float)m;   // rt_j = (1/m) sum_l Ct_jl^2  (loss.py:241)
         }
     }
 #pragma unroll
-    for (int m = 0; m < 6; ++m) {
-        const float s = block_sum4(cnt[m], red);
-        if (threadIdx.x == 0) ws[L.g_cnt + (b * L.P + panel) * 6 + m] = s;
+    for (int q = 0; q < 6; ++q) {
+        const float s = block_sum4(cnt[q], red);
+        if (threadIdx.x == 0) ws[L.g_cnt + (b * L.PX + panel) * 6 + q] = s;
     }
 }
 
@@ -435,44 +481,44 @@ struct SJob {
 };
 struct SArgs {
     float* ws;
-    int64_t per_case, ld, nn, nv, P;
-    int n;
+    int64_t per_case, ld, nm, nvn, nvm, P;   // ld = up4(m): the sweeps walk n x m matrices; rows and delta over n, columns and sigma over m
+    int n, m;
     SJob j[2];
 };
 
 // Forward row pass p: T_{p-1} = delta_{p-1} (A . T_{p-2}) sigma_{p-1} is written to the tape (p >= 2; T_0 = 1); for p <= iters the pass
-// continues with Q_p = A . T_{p-1}: delta_p,i = 1 / (n sum_j Q_p,ij sigma_{p-1,j}) and the column partials sum_{i in panel} Q_p,ij delta_p,i.
+// continues with Q_p = A . T_{p-1}: delta_p,i = 1 / (n sum_j Q_p,ij sigma_{p-1,j}) (sigma_0 = 1/m) and the column partials sum_{i in panel} Q_p,ij delta_p,i.
 // p == 1 forms A = exp(-C / beta) from the cost and stores it.  p == iters + 1 only writes T_iters (and the distance partial sum C . T).
 __global__ __launch_bounds__(NT) void tl_fwd_row_kernel(const SArgs a) {
     __shared__ float red[4][CW];
     const SJob& J = a.j[blockIdx.y];
     const int64_t b = blockIdx.x / a.P, panel = blockIdx.x % a.P;
-    const int n = a.n, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t ld = a.ld, nn = a.nn, nv = a.nv;
+    const int n = a.n, m = a.m, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t ld = a.ld, nm = a.nm, nvn = a.nvn, nvm = a.nvm;
     float* base = a.ws + b * a.per_case;
     const int p = J.p, iters = J.iters;
-    const float fn = (float)n, inv_n = 1.f / fn, ib = J.inv_beta;
+    const float fn = (float)n, inv_m = 1.f / (float)m, ib = J.inv_beta;
     float* __restrict__ A = base + J.oA;
     const float* __restrict__ Cm = base + J.oCm;
-    const float* __restrict__ Tpp = base + J.oT + (int64_t)(p >= 3 ? p - 3 : 0) * nn;      // T_{p-2}
-    float* __restrict__ Tw = base + J.oT + (int64_t)(p >= 2 ? p - 2 : 0) * nn;             // T_{p-1}
-    const float* __restrict__ dprev = base + J.od + (int64_t)(p >= 2 ? p - 2 : 0) * nv;    // delta_{p-1}
-    const float* __restrict__ sprev = base + J.os + (int64_t)(p - 1) * nv;                 // sigma_{p-1}
+    const float* __restrict__ Tpp = base + J.oT + (int64_t)(p >= 3 ? p - 3 : 0) * nm;      // T_{p-2}
+    float* __restrict__ Tw = base + J.oT + (int64_t)(p >= 2 ? p - 2 : 0) * nm;             // T_{p-1}
+    const float* __restrict__ dprev = base + J.od + (int64_t)(p >= 2 ? p - 2 : 0) * nvn;   // delta_{p-1}
+    const float* __restrict__ sprev = base + J.os + (int64_t)(p - 1) * nvm;                // sigma_{p-1}
     const bool rowpass = p <= iters;
     const bool dist = p == iters + 1 && J.gpart >= 0;
-    // A and T_{p-1} at row i, columns j .. j + 3 (columns >= n read as 0)
+    // A and T_{p-1} at row i, columns j .. j + 3 (columns >= m read as 0)
     auto elem = [&](int64_t i, int j, float di, f32x4& Av, f32x4& Tv) {
         const int64_t e = i * ld + j;
         if (p == 1) {
             const f32x4 c = *reinterpret_cast<const f32x4*>(Cm + e);
 #pragma unroll
             for (int q = 0; q < 4; ++q) Av[q] = expf(-c[q] * ib);
-            Av = msk4(Av, j, n);
-            Tv = msk4(splat4(1.f), j, n);
+            Av = msk4(Av, j, m);
+            Tv = msk4(splat4(1.f), j, m);
         } else {
-            Av = msk4(*reinterpret_cast<const f32x4*>(A + e), j, n);
-            const f32x4 tp = p >= 3 ? msk4(*reinterpret_cast<const f32x4*>(Tpp + e), j, n) : splat4(1.f);
-            const f32x4 sq = msk4(*reinterpret_cast<const f32x4*>(sprev + j), j, n);
+            Av = msk4(*reinterpret_cast<const f32x4*>(A + e), j, m);
+            const f32x4 tp = p >= 3 ? msk4(*reinterpret_cast<const f32x4*>(Tpp + e), j, m) : splat4(1.f);
+            const f32x4 sq = msk4(*reinterpret_cast<const f32x4*>(sprev + j), j, m);
 #pragma unroll
             for (int q = 0; q < 4; ++q) Tv[q] = di * (Av[q] * tp[q]) * sq[q];
         }
@@ -490,26 +536,26 @@ __global__ __launch_bounds__(NT) void tl_fwd_row_kernel(const SArgs a) {
             const int64_t i = panel * RP + wave + 4 * r;
             if (i < n) {   // wave-uniform
                 float s = 0.f;
-                for (int j = 4 * lane; j < n; j += CW) {
+                for (int j = 4 * lane; j < m; j += CW) {
                     f32x4 Av, Tv;
                     elem(i, j, dp[r], Av, Tv);
-                    const f32x4 sq = p == 1 ? msk4(splat4(inv_n), j, n) : msk4(*reinterpret_cast<const f32x4*>(sprev + j), j, n);
+                    const f32x4 sq = p == 1 ? msk4(splat4(inv_m), j, m) : msk4(*reinterpret_cast<const f32x4*>(sprev + j), j, m);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) s += (Av[q] * Tv[q]) * sq[q];
                 }
                 s = wave_sum(s);
                 dl[r] = 1.f / (fn * s);
-                if (lane == 0) base[J.od + (int64_t)(p - 1) * nv + i] = dl[r];
+                if (lane == 0) base[J.od + (int64_t)(p - 1) * nvn + i] = dl[r];
             }
         }
     }
     // phase 2: write A (p == 1) / T_{p-1} (p >= 2); column partials of Q_p delta_p
     float dsum = 0.f;
 #pragma unroll 1
-    for (int c0 = 0; c0 < n; c0 += CW) {
+    for (int c0 = 0; c0 < m; c0 += CW) {
         const int j = c0 + 4 * lane;
         f32x4 cacc = splat4(0.f);
-        if (j < n) {
+        if (j < m) {
 #pragma unroll
             for (int r = 0; r < RP / 4; ++r) {
                 const int64_t i = panel * RP + wave + 4 * r;
@@ -524,7 +570,7 @@ __global__ __launch_bounds__(NT) void tl_fwd_row_kernel(const SArgs a) {
                         for (int q = 0; q < 4; ++q) cacc[q] += (Av[q] * Tv[q]) * dl[r];
                     }
                     if (dist) {
-                        const f32x4 c = msk4(*reinterpret_cast<const f32x4*>(Cm + e), j, n);
+                        const f32x4 c = msk4(*reinterpret_cast<const f32x4*>(Cm + e), j, m);
 #pragma unroll
                         for (int q = 0; q < 4; ++q) dsum += c[q] * Tv[q];
                     }
@@ -535,7 +581,7 @@ __global__ __launch_bounds__(NT) void tl_fwd_row_kernel(const SArgs a) {
             *reinterpret_cast<f32x4*>(&red[wave][4 * lane]) = cacc;
             __syncthreads();
             const int jj = c0 + threadIdx.x;
-            if (jj < n)
+            if (jj < m)
                 base[J.ocp + panel * ld + jj] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
             __syncthreads();
         }
@@ -548,31 +594,32 @@ __global__ __launch_bounds__(NT) void tl_fwd_row_kernel(const SArgs a) {
 }
 
 // merges of the column partials (grid.x = cases x column blocks, grid.y = job), panels summed in order
-//   mode 0 (forward pass p): sigma_p,j = 1 / (n sum_panels)            (p == 1 also writes sigma_0 = 1/n)
-//   mode 1 (reverse): seed: Cv = colsum(Y), ga = -n sigma_iters Cv;  iteration t: Cv += colsum(W_t), ga = -n so (so gsig + Cv)
+//   mode 0 (forward pass p): sigma_p,j = 1 / (m sum_panels)            (p == 1 also writes sigma_0 = 1/m)
+//   mode 1 (reverse): seed: Cv = colsum(Y), ga = -m sigma_iters Cv;  iteration t: Cv += colsum(W_t), ga = -m so (so gsig + Cv)
+//   (sigma = 1 / (m colsum), so d sigma / d colsum = -m sigma^2: the column side carries m where the row side carries n)
 //   mode 2 (GW products): grt_j += sum_i G_ij
 __global__ __launch_bounds__(NT) void tl_merge_kernel(const SArgs a, int mode) {
     const SJob& J = a.j[blockIdx.y];
-    const int n = a.n;
-    const int64_t R = cdiv(n, NT);
+    const int m = a.m;
+    const int64_t R = cdiv(m, NT);
     const int64_t b = blockIdx.x / R;
     const int j = (int)(blockIdx.x % R) * NT + threadIdx.x;
-    if (j >= n) return;
+    if (j >= m) return;
     float* base = a.ws + b * a.per_case;
-    const int64_t ld = a.ld, nv = a.nv, P = a.P;
-    const float fn = (float)n;
+    const int64_t ld = a.ld, nv = a.nvm, P = a.P;
+    const float fm = (float)m;
     const float* cp = base + J.ocp;
     float s = 0.f;
     for (int64_t pp = 0; pp < P; ++pp) s += cp[pp * ld + j];
     if (mode == 0) {
-        base[J.os + (int64_t)J.p * nv + j] = 1.f / (fn * s);
-        if (J.p == 1) base[J.os + j] = 1.f / fn;
+        base[J.os + (int64_t)J.p * nv + j] = 1.f / (fm * s);
+        if (J.p == 1) base[J.os + j] = 1.f / fm;
     } else if (mode == 1) {
         float* Cv = base + J.oCv;
         float* ga = base + J.oga;
         if (J.p == J.iters + 1) {
             Cv[j] = s;
-            ga[j] = -fn * base[J.os + (int64_t)J.iters * nv + j] * s;
+            ga[j] = -fm * base[J.os + (int64_t)J.iters * nv + j] * s;
         } else {
             const float* cp2 = cp + P * ld;
             float cw = 0.f;
@@ -580,7 +627,7 @@ __global__ __launch_bounds__(NT) void tl_merge_kernel(const SArgs a, int mode) {
             const float cv = Cv[j] + cw;
             Cv[j] = cv;
             const float so = base[J.os + (int64_t)(J.p - 1) * nv + j];
-            ga[j] = -fn * so * (so * s + cv);
+            ga[j] = -fm * so * (so * s + cv);
         }
     } else {
         base[J.oH + j] += s;
@@ -592,12 +639,13 @@ __global__ __launch_bounds__(NT) void tl_merge_kernel(const SArgs a, int mode) {
 //   iteration t: Q_t = T_t / (delta_i sigma_j) ; gr_i = -n delta_i^2 (Rv_i / delta_i + sum_j Q ga) ; W = Q . (delta ga^T + gr so^T) ;
 //                H += t W (t == 1: written as dL/dC = -(1/beta) H) ; Rv_i += delta_i (Q ga)_i + gr_i (Q so)_i ;
 //                column partials of Q gr (set 1) and of W (set 2)
+//   (delta = 1 / (n rowsum) gives the factor -n here; sigma = 1 / (m colsum) gives -m in tl_merge_kernel mode 1)
 __global__ __launch_bounds__(NT) void tl_bwd_row_kernel(const SArgs a) {
     __shared__ float red[2][4][CW];
     const SJob& J = a.j[blockIdx.y];
     const int64_t b = blockIdx.x / a.P, panel = blockIdx.x % a.P;
-    const int n = a.n, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t ld = a.ld, nn = a.nn, nv = a.nv, P = a.P;
+    const int n = a.n, m = a.m, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t ld = a.ld, nm = a.nm, nvn = a.nvn, nvm = a.nvm, P = a.P;
     float* base = a.ws + b * a.per_case;
     const int t = J.p, iters = J.iters;
     const float fn = (float)n;
@@ -608,21 +656,21 @@ __global__ __launch_bounds__(NT) void tl_bwd_row_kernel(const SArgs a) {
     float* __restrict__ cp2 = cp1 + P * ld;
     if (t == iters + 1) {
         const float gs = J.gscale ? *J.gscale : 1.f;
-        const float* __restrict__ Tl = base + J.oT + (int64_t)(iters - 1) * nn;
+        const float* __restrict__ Tl = base + J.oT + (int64_t)(iters - 1) * nm;
         const float* __restrict__ gT = base + J.ogTin;
         float rs[RP / 4] = {};
 #pragma unroll 1
-        for (int c0 = 0; c0 < n; c0 += CW) {
+        for (int c0 = 0; c0 < m; c0 += CW) {
             const int j = c0 + 4 * lane;
             f32x4 cacc = splat4(0.f);
-            if (j < n) {
+            if (j < m) {
 #pragma unroll
                 for (int r = 0; r < RP / 4; ++r) {
                     const int64_t i = panel * RP + wave + 4 * r;
                     if (i < n) {
                         const int64_t e = i * ld + j;
-                        const f32x4 gv = msk4(*reinterpret_cast<const f32x4*>(gT + e), j, n);
-                        const f32x4 tl = msk4(*reinterpret_cast<const f32x4*>(Tl + e), j, n);
+                        const f32x4 gv = msk4(*reinterpret_cast<const f32x4*>(gT + e), j, m);
+                        const f32x4 tl = msk4(*reinterpret_cast<const f32x4*>(Tl + e), j, m);
                         f32x4 y, h;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
@@ -638,7 +686,7 @@ __global__ __launch_bounds__(NT) void tl_bwd_row_kernel(const SArgs a) {
             *reinterpret_cast<f32x4*>(&red[0][wave][4 * lane]) = cacc;
             __syncthreads();
             const int jj = c0 + threadIdx.x;
-            if (jj < n)
+            if (jj < m)
                 cp1[panel * ld + jj] = (red[0][0][threadIdx.x] + red[0][1][threadIdx.x]) + (red[0][2][threadIdx.x] + red[0][3][threadIdx.x]);
             __syncthreads();
         }
@@ -650,17 +698,17 @@ __global__ __launch_bounds__(NT) void tl_bwd_row_kernel(const SArgs a) {
         }
         return;
     }
-    const float* __restrict__ Tt = base + J.oT + (int64_t)(t - 1) * nn;
-    const float* __restrict__ dlv = base + J.od + (int64_t)(t - 1) * nv;
-    const float* __restrict__ sg = base + J.os + (int64_t)t * nv;
-    const float* __restrict__ so = base + J.os + (int64_t)(t - 1) * nv;
+    const float* __restrict__ Tt = base + J.oT + (int64_t)(t - 1) * nm;
+    const float* __restrict__ dlv = base + J.od + (int64_t)(t - 1) * nvn;
+    const float* __restrict__ sg = base + J.os + (int64_t)t * nvm;
+    const float* __restrict__ so = base + J.os + (int64_t)(t - 1) * nvm;
     const float ft = (float)t;
-    auto colvec = [&](const float* v, int j) { return msk4(*reinterpret_cast<const f32x4*>(v + j), j, n); };
+    auto colvec = [&](const float* v, int j) { return msk4(*reinterpret_cast<const f32x4*>(v + j), j, m); };
     auto rsg4 = [&](int j) {
         const f32x4 s = *reinterpret_cast<const f32x4*>(sg + j);
         f32x4 r;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) r[q] = j + q < n ? 1.f / s[q] : 0.f;
+        for (int q = 0; q < 4; ++q) r[q] = j + q < m ? 1.f / s[q] : 0.f;
         return r;
     };
     float di[RP / 4], rdi[RP / 4], gr[RP / 4];
@@ -673,8 +721,8 @@ __global__ __launch_bounds__(NT) void tl_bwd_row_kernel(const SArgs a) {
             di[r] = dlv[i];
             rdi[r] = 1.f / di[r];
             float s1 = 0.f, s2 = 0.f;
-            for (int j = 4 * lane; j < n; j += CW) {
-                const f32x4 tt = msk4(*reinterpret_cast<const f32x4*>(Tt + i * ld + j), j, n);
+            for (int j = 4 * lane; j < m; j += CW) {
+                const f32x4 tt = msk4(*reinterpret_cast<const f32x4*>(Tt + i * ld + j), j, m);
                 const f32x4 rg = rsg4(j), gav = colvec(ga, j), sov = colvec(so, j);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -694,17 +742,17 @@ __global__ __launch_bounds__(NT) void tl_bwd_row_kernel(const SArgs a) {
     // phase 2: W, H, column partials
     const float hs = t == 1 ? -J.inv_beta : 1.f;
 #pragma unroll 1
-    for (int c0 = 0; c0 < n; c0 += CW) {
+    for (int c0 = 0; c0 < m; c0 += CW) {
         const int j = c0 + 4 * lane;
         f32x4 c1 = splat4(0.f), c2 = splat4(0.f);
-        if (j < n) {
+        if (j < m) {
             const f32x4 rg = rsg4(j), gav = colvec(ga, j), sov = colvec(so, j);
 #pragma unroll
             for (int r = 0; r < RP / 4; ++r) {
                 const int64_t i = panel * RP + wave + 4 * r;
                 if (i < n) {
                     const int64_t e = i * ld + j;
-                    const f32x4 tt = msk4(*reinterpret_cast<const f32x4*>(Tt + e), j, n);
+                    const f32x4 tt = msk4(*reinterpret_cast<const f32x4*>(Tt + e), j, m);
                     f32x4 h = *reinterpret_cast<const f32x4*>(H + e);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
@@ -723,7 +771,7 @@ __global__ __launch_bounds__(NT) void tl_bwd_row_kernel(const SArgs a) {
             *reinterpret_cast<f32x4*>(&red[1][wave][4 * lane]) = c2;
             __syncthreads();
             const int jj = c0 + threadIdx.x, x = threadIdx.x;
-            if (jj < n) {
+            if (jj < m) {
                 cp1[panel * ld + jj] = (red[0][0][x] + red[0][1][x]) + (red[0][2][x] + red[0][3][x]);
                 cp2[panel * ld + jj] = (red[1][0][x] + red[1][1][x]) + (red[1][2][x] + red[1][3][x]);
             }
@@ -733,24 +781,24 @@ __global__ __launch_bounds__(NT) void tl_bwd_row_kernel(const SArgs a) {
 }
 
 // GW products: grs_i += sum_j G_ij (rows of the panel), column partials of G (merged by tl_merge_kernel mode 2 into grt)
-__global__ __launch_bounds__(NT) void tl_rowcol_kernel(float* ws, const Lay L, int n) {
+__global__ __launch_bounds__(NT) void tl_rowcol_kernel(float* ws, const Lay L, int n, int m) {
     __shared__ float red[4][CW];
     const int64_t b = blockIdx.x / L.P, panel = blockIdx.x % L.P;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* base = ws + b * L.per_case;
-    const int64_t ld = L.ld;
+    const int64_t ld = L.ldm;
     const float* G = base + L.oG;
     float rs[RP / 4] = {};
 #pragma unroll 1
-    for (int c0 = 0; c0 < n; c0 += CW) {
+    for (int c0 = 0; c0 < m; c0 += CW) {
         const int j = c0 + 4 * lane;
         f32x4 cacc = splat4(0.f);
-        if (j < n) {
+        if (j < m) {
 #pragma unroll
             for (int r = 0; r < RP / 4; ++r) {
                 const int64_t i = panel * RP + wave + 4 * r;
                 if (i < n) {
-                    const f32x4 g = msk4(*reinterpret_cast<const f32x4*>(G + i * ld + j), j, n);
+                    const f32x4 g = msk4(*reinterpret_cast<const f32x4*>(G + i * ld + j), j, m);
                     rs[r] += hsum4(g);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) cacc[q] += g[q];
@@ -760,7 +808,7 @@ __global__ __launch_bounds__(NT) void tl_rowcol_kernel(float* ws, const Lay L, i
         *reinterpret_cast<f32x4*>(&red[wave][4 * lane]) = cacc;
         __syncthreads();
         const int jj = c0 + threadIdx.x, x = threadIdx.x;
-        if (jj < n) base[L.ocpr + panel * ld + jj] = (red[0][x] + red[1][x]) + (red[2][x] + red[3][x]);
+        if (jj < m) base[L.ocpr + panel * ld + jj] = (red[0][x] + red[1][x]) + (red[2][x] + red[3][x]);
         __syncthreads();
     }
 #pragma unroll
@@ -775,7 +823,7 @@ __global__ __launch_bounds__(NT) void tl_rowcol_kernel(float* ws, const Lay L, i
 __global__ __launch_bounds__(NT) void tl_sum_kernel(float* ws, const Lay L, int k, float* out) {
     __shared__ float red[4];
     const float wd = block_sum_array(ws + L.g_wd, (int64_t)k * L.P, 1, red);
-    const float gwd = block_sum_array(ws + L.g_gwd, (int64_t)k * L.tiles, 1, red);
+    const float gwd = block_sum_array(ws + L.g_gwd, (int64_t)k * L.tiles[0], 1, red);
     if (threadIdx.x == 0) {
         out[0] = wd;
         out[1] = gwd;
@@ -783,60 +831,72 @@ __global__ __launch_bounds__(NT) void tl_sum_kernel(float* ws, const Lay L, int 
 }
 
 // reverse seed of the GW branch: G = g1 gamma_5 (the final plan is detached, loss.py:248), zero the accumulated gradients
-__global__ __launch_bounds__(NT) void tl_gw_seed_kernel(float* ws, const Lay L, int n, const float* __restrict__ d_out) {
-    const int64_t b = blockIdx.x / L.P, panel = blockIdx.x % L.P;
+// (grid: cases x panels over max(n, m) rows)
+__global__ __launch_bounds__(NT) void tl_gw_seed_kernel(float* ws, const Lay L, int n, int m, const float* __restrict__ d_out) {
+    const int64_t b = blockIdx.x / L.PX, panel = blockIdx.x % L.PX;
     float* base = ws + b * L.per_case;
     const float g = d_out[1];
-    const float* gam = base + L.oGT + (int64_t)(GW_OUTER * GW_INNER - 1) * L.nn;
-    for (int e = threadIdx.x; e < RP * L.ld; e += NT) {
-        const int64_t i = panel * RP + e / L.ld;
-        if (i >= n) break;
-        const int64_t x = panel * RP * L.ld + e;
-        base[L.oG + x] = g * gam[x];
-        base[L.ogCs + x] = 0.f;
-        base[L.ogCt + x] = 0.f;
+    const float* gam = base + L.oGT + (int64_t)(GW_OUTER * GW_INNER - 1) * L.nm;
+    for (PanelWalk w(L.ldm); w.in(); w.next()) {
+        const int64_t i = panel * RP + w.r;
+        if (i >= n && i >= m) break;
+        const int64_t x = panel * RP * L.ldm + w.e;
+        if (i < n) base[L.oG + x] = g * gam[x];
+        if (i < m) base[L.ogCt + x] = 0.f;
     }
-    if (panel == 0)
-        for (int i = threadIdx.x; i < n; i += NT) {
-            base[L.ogrs + i] = 0.f;
-            base[L.ogrt + i] = 0.f;
-        }
+    for (PanelWalk w(L.ldn); w.in(); w.next()) {
+        if (panel * RP + w.r >= n) break;
+        base[L.ogCs + panel * RP * L.ldn + w.e] = 0.f;
+    }
+    if (panel == 0) {
+        for (int i = threadIdx.x; i < n; i += NT) base[L.ogrs + i] = 0.f;
+        for (int i = threadIdx.x; i < m; i += NT) base[L.ogrt + i] = 0.f;
+    }
 }
 
-// end of the reverse chain: dL/dC0 = relu mask of (g0 T_30 + WD reverse); dL/dCs0, dL/dCt0 = masks of (gCs + (2/n) Cs grs, ...);
-// per-panel threshold-gradient partials (-sum of each masked gradient)
-__global__ __launch_bounds__(NT) void tl_bwd_final_kernel(float* ws, const Lay L, int n, const float* __restrict__ d_out) {
+// end of the reverse chain: dL/dC0 = relu mask of (g0 T_30 + WD reverse); dL/dCs0, dL/dCt0 = masks of (gCs + (2/n) Cs grs,
+// gCt + (2/m) Ct grt); per-panel threshold-gradient partials (-sum of each masked gradient).  Grid: cases x panels over max(n, m) rows.
+__global__ __launch_bounds__(NT) void tl_bwd_final_kernel(float* ws, const Lay L, int n, int m, const float* __restrict__ d_out) {
     __shared__ float red[4];
-    const int64_t b = blockIdx.x / L.P, panel = blockIdx.x % L.P;
+    const int64_t b = blockIdx.x / L.PX, panel = blockIdx.x % L.PX;
     float* base = ws + b * L.per_case;
-    const float g0 = d_out[0], two_n = 2.f / (float)n;
+    const float g0 = d_out[0], two_n = 2.f / (float)n, two_m = 2.f / (float)m;
     const float t0 = ws[L.g_thr + 6], t1 = ws[L.g_thr + 7], t2 = ws[L.g_thr + 8];
-    const float* Tf = base + L.oWT + (int64_t)(WD_ITERS - 1) * L.nn;
+    const float* Tf = base + L.oWT + (int64_t)(WD_ITERS - 1) * L.nm;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    for (int e = threadIdx.x; e < RP * L.ld; e += NT) {
-        const int64_t i = panel * RP + e / L.ld;
-        const int j = (int)(e % L.ld);
+    for (PanelWalk w(L.ldm); w.in(); w.next()) {
+        const int64_t i = panel * RP + w.r;
+        if (i >= n && i >= m) break;
+        if (w.j >= m) continue;
+        const int64_t x = panel * RP * L.ldm + w.e;
+        if (i < n) {
+            const float gc = g0 * Tf[x] + base[L.ogC0 + x];
+            const float m0 = (base[L.oC0 + x] - t0 > 0.f) ? gc : 0.f;
+            base[L.ogC0 + x] = m0;
+            s0 -= m0;
+        }
+        if (i < m) {
+            float at = base[L.ogCt + x] + two_m * base[L.oCt + x] * base[L.ogrt + i];
+            at = (base[L.oCt0 + x] - t2 > 0.f) ? at : 0.f;
+            base[L.ogCt + x] = at;
+            s2 -= at;
+        }
+    }
+    for (PanelWalk w(L.ldn); w.in(); w.next()) {
+        const int64_t i = panel * RP + w.r;
         if (i >= n) break;
-        if (j >= n) continue;
-        const int64_t x = panel * RP * L.ld + e;
-        const float gc = g0 * Tf[x] + base[L.ogC0 + x];
-        const float m0 = (base[L.oC0 + x] - t0 > 0.f) ? gc : 0.f;
-        base[L.ogC0 + x] = m0;
-        s0 -= m0;
+        if (w.j >= n) continue;
+        const int64_t x = panel * RP * L.ldn + w.e;
         float as = base[L.ogCs + x] + two_n * base[L.oCs + x] * base[L.ogrs + i];
-        float at = base[L.ogCt + x] + two_n * base[L.oCt + x] * base[L.ogrt + i];
         as = (base[L.oCs0 + x] - t1 > 0.f) ? as : 0.f;
-        at = (base[L.oCt0 + x] - t2 > 0.f) ? at : 0.f;
         base[L.ogCs + x] = as;
-        base[L.ogCt + x] = at;
         s1 -= as;
-        s2 -= at;
     }
     s0 = block_sum4(s0, red);
     s1 = block_sum4(s1, red);
     s2 = block_sum4(s2, red);
     if (threadIdx.x == 0) {
-        float* o = ws + L.g_gthr + (b * L.P + panel) * 3;
+        float* o = ws + L.g_gthr + (b * L.PX + panel) * 3;
         o[0] = s0;
         o[1] = s1;
         o[2] = s2;
@@ -846,7 +906,7 @@ __global__ __launch_bounds__(NT) void tl_bwd_final_kernel(float* ws, const Lay L
 // threshold gradients -> d_minmax [6]; batch tie counts (fixed order)
 __global__ __launch_bounds__(NT) void tl_thr_bwd_kernel(float* ws, const Lay L, int k, float* d_minmax) {
     __shared__ float red[4];
-    const int64_t cnt = (int64_t)k * L.P;
+    const int64_t cnt = (int64_t)k * L.PX;
     for (int m = 0; m < 3; ++m) {
         const float s = block_sum_array(ws + L.g_gthr + m, cnt, 3, red);
         if (threadIdx.x == 0) {
@@ -865,46 +925,60 @@ __global__ __launch_bounds__(NT) void tl_thr_bwd_kernel(float* ws, const Lay L, 
 
 // the extremum gradients, spread evenly over the local elements that attain them (torch's min()/max() backward) -> routed copies
 // P1 = d/dC0, P2 = d/dCs0, P3 = d/dCt0 (the reverse chain's results stay untouched)
-__global__ __launch_bounds__(NT) void tl_route_kernel(float* ws, const Lay L, int n, const float* __restrict__ d_minmax_total) {
-    const int64_t b = blockIdx.x / L.P, panel = blockIdx.x % L.P;
+__global__ __launch_bounds__(NT) void tl_route_kernel(float* ws, const Lay L, int n, int m, const float* __restrict__ d_minmax_total) {
+    const int64_t b = blockIdx.x / L.PX, panel = blockIdx.x % L.PX;   // panels over max(n, m) rows
     float* base = ws + b * L.per_case;
     float ex[6], sp[6];
 #pragma unroll
-    for (int m = 0; m < 6; ++m) {
-        ex[m] = ws[L.g_thr + m];
-        const float cnt = ws[L.g_thr + 9 + m];
-        const float gthr = ws[L.g_thr + 15 + m / 2];
-        const float gl = d_minmax_total ? d_minmax_total[m] : ((m & 1) ? THR_BETA * gthr : (1.f - THR_BETA) * gthr);
-        sp[m] = cnt > 0.f ? gl / cnt : 0.f;
+    for (int q = 0; q < 6; ++q) {
+        ex[q] = ws[L.g_thr + q];
+        const float cnt = ws[L.g_thr + 9 + q];
+        const float gthr = ws[L.g_thr + 15 + q / 2];
+        const float gl = d_minmax_total ? d_minmax_total[q] : ((q & 1) ? THR_BETA * gthr : (1.f - THR_BETA) * gthr);
+        sp[q] = cnt > 0.f ? gl / cnt : 0.f;
     }
-    for (int e = threadIdx.x; e < RP * L.ld; e += NT) {
-        const int64_t i = panel * RP + e / L.ld;
+    for (PanelWalk w(L.ldm); w.in(); w.next()) {
+        const int64_t i = panel * RP + w.r;
+        if (i >= n && i >= m) break;
+        const int64_t x = panel * RP * L.ldm + w.e;
+        if (i < n) {
+            const float v0 = base[L.oC0 + x];
+            float a = base[L.ogC0 + x];
+            if (v0 == ex[0]) a += sp[0];
+            if (v0 == ex[1]) a += sp[1];
+            base[L.oP1 + x] = a;
+        }
+        if (i < m) {
+            const float v2 = base[L.oCt0 + x];
+            float z = base[L.ogCt + x];
+            if (v2 == ex[4]) z += sp[4];
+            if (v2 == ex[5]) z += sp[5];
+            base[L.oP3 + x] = z;
+        }
+    }
+    for (PanelWalk w(L.ldn); w.in(); w.next()) {
+        const int64_t i = panel * RP + w.r;
         if (i >= n) break;
-        const int64_t x = panel * RP * L.ld + e;
-        const float v0 = base[L.oC0 + x], v1 = base[L.oCs0 + x], v2 = base[L.oCt0 + x];
-        float a = base[L.ogC0 + x], s = base[L.ogCs + x], z = base[L.ogCt + x];
-        if (v0 == ex[0]) a += sp[0];
-        if (v0 == ex[1]) a += sp[1];
+        const int64_t x = panel * RP * L.ldn + w.e;
+        const float v1 = base[L.oCs0 + x];
+        float s = base[L.ogCs + x];
         if (v1 == ex[2]) s += sp[2];
         if (v1 == ex[3]) s += sp[3];
-        if (v2 == ex[4]) z += sp[4];
-        if (v2 == ex[5]) z += sp[5];
-        base[L.oP1 + x] = a;
         base[L.oP2 + x] = s;
-        base[L.oP3 + x] = z;
     }
 }
 
 // x^ = x / (r + eps):  gx = s gx^ - (<x^, gx^> / r) x^   (one wave per token row)
-__global__ __launch_bounds__(NT) void tl_norm_bwd_kernel(float* ws, const Lay L, int n, int d, float* __restrict__ dV,
+__global__ __launch_bounds__(NT) void tl_norm_bwd_kernel(float* ws, const Lay L, int n, int m, int d, float* __restrict__ dV,
                                                          float* __restrict__ dQ) {
-    const int64_t R = cdiv(n, 4);
+    const int64_t R = cdiv(n > m ? n : m, 4);
     const int64_t b = blockIdx.x / R;
     const int i = (int)(blockIdx.x % R) * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (i >= n) return;
     const float* base = ws + b * L.per_case;
 #pragma unroll 1
     for (int s = 0; s < 2; ++s) {
+        const int rows = s ? m : n;
+        if (i >= rows) continue;   // wave-uniform
         const float* gx = base + (s ? L.ogQh : L.ogVh) + (int64_t)i * d;
         const float* xh = base + (s ? L.oQh : L.oVh) + (int64_t)i * d;
         float dot = 0.f;
@@ -913,7 +987,7 @@ __global__ __launch_bounds__(NT) void tl_norm_bwd_kernel(float* ws, const Lay L,
         const float r = base[(s ? L.orQ : L.orV) + i];
         const float sc = 1.f / (r + 1e-12f);
         const float proj = r > 0.f ? dot / r : 0.f;
-        float* out = (s ? dQ : dV) + (b * n + i) * (int64_t)d;
+        float* out = (s ? dQ : dV) + (b * rows + i) * (int64_t)d;
         for (int e = lane; e < d; e += 64) out[e] = sc * gx[e] - proj * xh[e];
     }
 }
@@ -924,12 +998,13 @@ __global__ __launch_bounds__(NT) void tl_norm_bwd_kernel(float* ws, const Lay L,
 struct Ctx {
     float* ws;
     Lay L;
-    int k, n, d;
+    int k, n, m, d;
     hipStream_t s;
 };
 
-static GTerm term(int64_t oA, int64_t lda, bool ta, int64_t oB, int64_t ldb, bool tb, float ca = 0.f, float cb = 0.f) {
+static GTerm term(int K, int64_t oA, int64_t lda, bool ta, int64_t oB, int64_t ldb, bool tb, float ca = 0.f, float cb = 0.f) {
     GTerm t{};
+    t.K = K;
     t.oA = oA;
     t.oB = oB;
     t.lda = lda;
@@ -940,25 +1015,29 @@ static GTerm term(int64_t oA, int64_t lda, bool ta, int64_t oB, int64_t ldb, boo
     t.tb = tb;
     return t;
 }
-static GJob job(int mode, float alpha, int64_t oC, int64_t ldc) {
+static GJob job(int mode, float alpha, int M, int N, int64_t oC, int64_t ldc) {
     GJob j{};
     j.mode = mode;
     j.alpha = alpha;
+    j.M = M;
+    j.N = N;
+    j.tn = (int)cdiv(N, MT);
+    j.tiles = (int)(cdiv(M, MT) * j.tn);
     j.oC = oC;
     j.ldc = ldc;
     return j;
 }
-static int gemm(const Ctx& c, int M, int N, int K, const GJob* jobs, int nj) {
+static int gemm(const Ctx& c, const GJob* jobs, int nj) {
     GArgs g{};
     g.ws = c.ws;
     g.per_case = c.L.per_case;
-    g.M = M;
-    g.N = N;
-    g.K = K;
-    g.tn = (int)cdiv(N, MT);
-    g.tiles = (int)(cdiv(M, MT) * g.tn);
-    for (int i = 0; i < nj; ++i) g.j[i] = jobs[i];
-    hipLaunchKernelGGL(tl_gemm_kernel, dim3((unsigned)((int64_t)c.k * g.tiles), nj), dim3(NT), 0, c.s, g);
+    g.k = c.k;
+    int tiles = 0;
+    for (int i = 0; i < nj; ++i) {
+        g.j[i] = jobs[i];
+        tiles = jobs[i].tiles > tiles ? jobs[i].tiles : tiles;
+    }
+    hipLaunchKernelGGL(tl_gemm_kernel, dim3((unsigned)((int64_t)c.k * tiles), nj), dim3(NT), 0, c.s, g);
     MDL_LAUNCH_CHECK();
     return MDL_OK;
 }
@@ -966,15 +1045,19 @@ static SArgs sargs(const Ctx& c) {
     SArgs a{};
     a.ws = c.ws;
     a.per_case = c.L.per_case;
-    a.ld = c.L.ld;
-    a.nn = c.L.nn;
-    a.nv = c.L.nv;
+    a.ld = c.L.ldm;
+    a.nm = c.L.nm;
+    a.nvn = c.L.nvn;
+    a.nvm = c.L.nvm;
     a.P = c.L.P;
     a.n = c.n;
+    a.m = c.m;
     return a;
 }
-static dim3 panels(const Ctx& c, int nj = 1) { return dim3((unsigned)((int64_t)c.k * c.L.P), nj); }
-static dim3 colblocks(const Ctx& c, int nj = 1) { return dim3((unsigned)((int64_t)c.k * cdiv(c.n, NT)), nj); }
+static dim3 panels(const Ctx& c, int nj = 1) { return dim3((unsigned)((int64_t)c.k * c.L.P), nj); }      // rows of an n x m matrix
+static dim3 xpanels(const Ctx& c) { return dim3((unsigned)((int64_t)c.k * c.L.PX)); }                    // rows of all three cost matrices
+static dim3 colblocks(const Ctx& c, int nj = 1) { return dim3((unsigned)((int64_t)c.k * cdiv(c.m, NT)), nj); }
+static dim3 tokrows(const Ctx& c) { return dim3((unsigned)((int64_t)c.k * cdiv(c.n > c.m ? c.n : c.m, 4))); }
 
 // IPOT jobs of the two branches (forward and reverse use the same descriptor)
 static SJob wd_job(const Ctx& c) {
@@ -999,17 +1082,17 @@ static SJob wd_job(const Ctx& c) {
 static SJob gw_job(const Ctx& c, int o) {
     const Lay& L = c.L;
     SJob j{};
-    j.oCm = L.oCg + (int64_t)o * L.nn;
+    j.oCm = L.oCg + (int64_t)o * L.nm;
     j.oA = L.oAg;
-    j.oT = L.oGT + (int64_t)o * GW_INNER * L.nn;
-    j.od = L.oGd + (int64_t)o * GW_INNER * L.nv;
-    j.os = L.oGs + (int64_t)o * (GW_INNER + 1) * L.nv;
-    j.ocp = L.ocp + 2 * L.P * L.ld;
+    j.oT = L.oGT + (int64_t)o * GW_INNER * L.nm;
+    j.od = L.oGd + (int64_t)o * GW_INNER * L.nvn;
+    j.os = L.oGs + (int64_t)o * (GW_INNER + 1) * L.nvm;
+    j.ocp = L.ocp + 2 * L.P * L.ldm;
     j.oH = L.oG;
     j.ogTin = L.ogT;
-    j.oRv = L.oRv + L.nv;
-    j.oCv = L.oCv + L.nv;
-    j.oga = L.oga + L.nv;
+    j.oRv = L.oRv + L.nvn;
+    j.oCv = L.oCv + L.nvm;
+    j.oga = L.oga + L.nvm;
     j.gpart = -1;
     j.iters = GW_INNER;
     j.inv_beta = GW_INV_BETA;
@@ -1065,82 +1148,84 @@ static int bwd_sweeps(const Ctx& c, const SJob* jobs, int nj, const float* gscal
     return MDL_OK;
 }
 
-// C_gamma of outer iteration o: P1 = gamma_{o-1} Ct^T (gamma_{-1} = 1/n^2), then rs_i + rt_j - 2 Cs P1 (o == GW_OUTER: only the distance
-// partials sum C_gamma . gamma_4)
+// C_gamma of outer iteration o: P1 = gamma_{o-1} Ct^T (gamma_{-1} = 1/(n m)), then rs_i + rt_j - 2 Cs P1 (o == GW_OUTER: only the
+// distance partials sum C_gamma . gamma_4).  Shapes: gamma n x m, Ct m x m, Cs n x n.
 static int gw_cgamma(const Ctx& c, int o) {
     const Lay& L = c.L;
-    const int n = c.n;
-    const int64_t ld = L.ld;
-    const float u = 1.f / ((float)n * (float)n);
-    const int64_t og = o >= 1 ? L.oGT + ((int64_t)(o - 1) * GW_INNER + (GW_INNER - 1)) * L.nn : -1;
-    GJob j1 = job(GM_STORE, 1.f, L.oP1, ld);
-    j1.t[0] = term(og, ld, false, L.oCt, ld, true, u);
+    const int n = c.n, m = c.m;
+    const int64_t ldn = L.ldn, ldm = L.ldm;
+    const float u = 1.f / ((float)n * (float)m);
+    const int64_t og = o >= 1 ? L.oGT + ((int64_t)(o - 1) * GW_INNER + (GW_INNER - 1)) * L.nm : -1;
+    GJob j1 = job(GM_STORE, 1.f, n, m, L.oP1, ldm);
+    j1.t[0] = term(m, og, ldm, false, L.oCt, ldm, true, u);
     j1.nt = 1;
-    int rc = gemm(c, n, n, n, &j1, 1);
+    int rc = gemm(c, &j1, 1);
     if (rc) return rc;
-    GJob j2 = job(o < GW_OUTER ? GM_CG : GM_GWD, 1.f, o < GW_OUTER ? L.oCg + (int64_t)o * L.nn : 0, ld);
-    j2.t[0] = term(L.oCs, ld, false, L.oP1, ld, false);
+    GJob j2 = job(o < GW_OUTER ? GM_CG : GM_GWD, 1.f, n, m, o < GW_OUTER ? L.oCg + (int64_t)o * L.nm : 0, ldm);
+    j2.t[0] = term(n, L.oCs, ldn, false, L.oP1, ldm, false);
     j2.nt = 1;
     j2.oX = L.ors;
     j2.oY = L.ort;
     j2.oZ = og;
     j2.gpart = L.g_gwd;
-    return gemm(c, n, n, n, &j2, 1);
+    return gemm(c, &j2, 1);
 }
 
-// M = Cs gam Ct^T with G = d/dC_gamma (C_gamma = Cst - 2 M):  gCs += -2 G Ct gam^T ; gCt += -2 G^T Cs gam ; d/dgam = -2 Cs^T G Ct
-// (o >= 1);  Cst = rs 1^T + 1 rt^T: grs += rowsum(G), grt += colsum(G)
+// M = Cs gam Ct^T with G = d/dC_gamma (C_gamma = Cst - 2 M):  gCs += -2 (G Ct) gam^T (n x n) ; gCt += -2 G^T (Cs gam) (m x m) ;
+// d/dgam = -2 Cs^T (G Ct) (n x m, o >= 1);  Cst = rs 1^T + 1 rt^T: grs += rowsum(G), grt += colsum(G)
 static int gw_bwd_products(const Ctx& c, int o) {
     const Lay& L = c.L;
-    const int n = c.n;
-    const int64_t ld = L.ld;
-    const float u = 1.f / ((float)n * (float)n);
-    const int64_t og = o >= 1 ? L.oGT + ((int64_t)(o - 1) * GW_INNER + (GW_INNER - 1)) * L.nn : -1;
-    hipLaunchKernelGGL(tl_rowcol_kernel, panels(c), dim3(NT), 0, c.s, c.ws, L, n);
+    const int n = c.n, m = c.m;
+    const int64_t ldn = L.ldn, ldm = L.ldm;
+    const float u = 1.f / ((float)n * (float)m);
+    const int64_t og = o >= 1 ? L.oGT + ((int64_t)(o - 1) * GW_INNER + (GW_INNER - 1)) * L.nm : -1;
+    hipLaunchKernelGGL(tl_rowcol_kernel, panels(c), dim3(NT), 0, c.s, c.ws, L, n, m);
     MDL_LAUNCH_CHECK();
     {
-        SArgs m = sargs(c);
-        m.j[0].ocp = L.ocpr;
-        m.j[0].oH = L.ogrt;
-        hipLaunchKernelGGL(tl_merge_kernel, colblocks(c), dim3(NT), 0, c.s, m, 2);
+        SArgs mg = sargs(c);
+        mg.j[0].ocp = L.ocpr;
+        mg.j[0].oH = L.ogrt;
+        hipLaunchKernelGGL(tl_merge_kernel, colblocks(c), dim3(NT), 0, c.s, mg, 2);
         MDL_LAUNCH_CHECK();
     }
     GJob a[2];
-    a[0] = job(GM_STORE, 1.f, L.oP1, ld);   // P1 = G Ct
-    a[0].t[0] = term(L.oG, ld, false, L.oCt, ld, false);
+    a[0] = job(GM_STORE, 1.f, n, m, L.oP1, ldm);   // P1 = G Ct
+    a[0].t[0] = term(m, L.oG, ldm, false, L.oCt, ldm, false);
     a[0].nt = 1;
-    a[1] = job(GM_STORE, 1.f, L.oP2, ld);   // P2 = Cs gam
-    a[1].t[0] = term(L.oCs, ld, false, og, ld, false, 0.f, u);
+    a[1] = job(GM_STORE, 1.f, n, m, L.oP2, ldm);   // P2 = Cs gam
+    a[1].t[0] = term(n, L.oCs, ldn, false, og, ldm, false, 0.f, u);
     a[1].nt = 1;
-    int rc = gemm(c, n, n, n, a, 2);
+    int rc = gemm(c, a, 2);
     if (rc) return rc;
     GJob z[3];
-    z[0] = job(GM_ACC, -2.f, L.ogCs, ld);   // gCs += -2 P1 gam^T
-    z[0].t[0] = term(L.oP1, ld, false, og, ld, true, 0.f, u);
+    z[0] = job(GM_ACC, -2.f, n, n, L.ogCs, ldn);   // gCs += -2 P1 gam^T
+    z[0].t[0] = term(m, L.oP1, ldm, false, og, ldm, true, 0.f, u);
     z[0].nt = 1;
-    z[1] = job(GM_ACC, -2.f, L.ogCt, ld);   // gCt += -2 G^T P2
-    z[1].t[0] = term(L.oG, ld, true, L.oP2, ld, false);
+    z[1] = job(GM_ACC, -2.f, m, m, L.ogCt, ldm);   // gCt += -2 G^T P2
+    z[1].t[0] = term(n, L.oG, ldm, true, L.oP2, ldm, false);
     z[1].nt = 1;
-    z[2] = job(GM_STORE, -2.f, L.ogT, ld);  // d/dgam = -2 Cs^T P1
-    z[2].t[0] = term(L.oCs, ld, true, L.oP1, ld, false);
+    z[2] = job(GM_STORE, -2.f, n, m, L.ogT, ldm);  // d/dgam = -2 Cs^T P1
+    z[2].t[0] = term(n, L.oCs, ldn, true, L.oP1, ldm, false);
     z[2].nt = 1;
-    return gemm(c, n, n, n, z, o >= 1 ? 3 : 2);
+    return gemm(c, z, o >= 1 ? 3 : 2);
 }
 
 int launch_prep(const Ctx& c, float* minmax_out, const float* minmax_in, const float* V, const float* Q) {
     const Lay& L = c.L;
-    const int n = c.n, d = c.d;
-    hipLaunchKernelGGL(tl_norm_kernel, dim3((unsigned)((int64_t)c.k * cdiv(n, 4))), dim3(NT), 0, c.s, V, Q, c.ws, L, n, d);
+    const int n = c.n, m = c.m, d = c.d;
+    hipLaunchKernelGGL(tl_norm_kernel, tokrows(c), dim3(NT), 0, c.s, V, Q, c.ws, L, n, m, d);
     MDL_LAUNCH_CHECK();
     GJob j[3];
     const int64_t oa[3] = {L.oVh, L.oVh, L.oQh}, ob[3] = {L.oQh, L.oVh, L.oQh}, oc[3] = {L.oC0, L.oCs0, L.oCt0};
-    for (int m = 0; m < 3; ++m) {   // raw costs 1 - <x^_i, y^_j> and per-tile extrema
-        j[m] = job(GM_RAW, 1.f, oc[m], L.ld);
-        j[m].t[0] = term(oa[m], d, false, ob[m], d, true);
-        j[m].nt = 1;
-        j[m].gpart = L.g_ext + (int64_t)m * c.k * L.tiles * 2;
+    const int64_t ldc[3] = {L.ldm, L.ldn, L.ldm};
+    const int rows[3] = {n, n, m}, cols[3] = {m, n, m};
+    for (int q = 0; q < 3; ++q) {   // raw costs 1 - <x^_i, y^_j> and per-tile extrema
+        j[q] = job(GM_RAW, 1.f, rows[q], cols[q], oc[q], ldc[q]);
+        j[q].t[0] = term(d, oa[q], d, false, ob[q], d, true);
+        j[q].nt = 1;
+        j[q].gpart = L.ext[q];
     }
-    int rc = gemm(c, n, n, d, j, 3);
+    int rc = gemm(c, j, 3);
     if (rc) return rc;
     hipLaunchKernelGGL(tl_minmax_kernel, dim3(1), dim3(NT), 0, c.s, c.ws, L, c.k, minmax_out, minmax_in);
     MDL_LAUNCH_CHECK();
@@ -1149,7 +1234,7 @@ int launch_prep(const Ctx& c, float* minmax_out, const float* minmax_in, const f
 
 int launch_main(const Ctx& c, float* out) {
     const Lay& L = c.L;
-    hipLaunchKernelGGL(tl_thr_kernel, panels(c), dim3(NT), 0, c.s, c.ws, L, c.n);
+    hipLaunchKernelGGL(tl_thr_kernel, xpanels(c), dim3(NT), 0, c.s, c.ws, L, c.n, c.m);
     MDL_LAUNCH_CHECK();
     int rc = gw_cgamma(c, 0);
     if (rc) return rc;
@@ -1174,8 +1259,8 @@ int launch_main(const Ctx& c, float* out) {
 
 int launch_bwd_begin(const Ctx& c, const float* d_out, float* d_minmax) {
     const Lay& L = c.L;
-    const int n = c.n;
-    hipLaunchKernelGGL(tl_gw_seed_kernel, panels(c), dim3(NT), 0, c.s, c.ws, L, n, d_out);
+    const int n = c.n, m = c.m;
+    hipLaunchKernelGGL(tl_gw_seed_kernel, xpanels(c), dim3(NT), 0, c.s, c.ws, L, n, m, d_out);
     MDL_LAUNCH_CHECK();
     int rc;
     for (int o = GW_OUTER; o >= 0; --o) {
@@ -1191,51 +1276,51 @@ int launch_bwd_begin(const Ctx& c, const float* d_out, float* d_minmax) {
         }
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(tl_bwd_final_kernel, panels(c), dim3(NT), 0, c.s, c.ws, L, n, d_out);
+    hipLaunchKernelGGL(tl_bwd_final_kernel, xpanels(c), dim3(NT), 0, c.s, c.ws, L, n, m, d_out);
     MDL_LAUNCH_CHECK();
     hipLaunchKernelGGL(tl_thr_bwd_kernel, dim3(1), dim3(NT), 0, c.s, c.ws, L, c.k, d_minmax);
     MDL_LAUNCH_CHECK();
     return MDL_OK;
 }
 
-// C0 = 1 - V^ Q^T, Cs0 = 1 - V^ V^T, Ct0 = 1 - Q^ Q^T:
-//   gV^ = -(G0 Q^ + Gs V^ + Gs^T V^) ;  gQ^ = -(G0^T V^ + Gt Q^ + Gt^T Q^)
+// C0 = 1 - V^ Q^T (n x m), Cs0 = 1 - V^ V^T (n x n), Ct0 = 1 - Q^ Q^T (m x m):
+//   gV^ = -(G0 Q^ + Gs V^ + Gs^T V^) (n x d) ;  gQ^ = -(G0^T V^ + Gt Q^ + Gt^T Q^) (m x d)
 int launch_bwd_finish(const Ctx& c, const float* d_minmax_total, float* dV, float* dQ) {
     const Lay& L = c.L;
-    const int n = c.n, d = c.d;
-    const int64_t ld = L.ld;
-    hipLaunchKernelGGL(tl_route_kernel, panels(c), dim3(NT), 0, c.s, c.ws, L, n, d_minmax_total);
+    const int n = c.n, m = c.m, d = c.d;
+    const int64_t ldn = L.ldn, ldm = L.ldm;
+    hipLaunchKernelGGL(tl_route_kernel, xpanels(c), dim3(NT), 0, c.s, c.ws, L, n, m, d_minmax_total);
     MDL_LAUNCH_CHECK();
     GJob j[2];
-    j[0] = job(GM_STORE, -1.f, L.ogVh, d);
-    j[0].t[0] = term(L.oP1, ld, false, L.oQh, d, false);
-    j[0].t[1] = term(L.oP2, ld, false, L.oVh, d, false);
-    j[0].t[2] = term(L.oP2, ld, true, L.oVh, d, false);
+    j[0] = job(GM_STORE, -1.f, n, d, L.ogVh, d);
+    j[0].t[0] = term(m, L.oP1, ldm, false, L.oQh, d, false);
+    j[0].t[1] = term(n, L.oP2, ldn, false, L.oVh, d, false);
+    j[0].t[2] = term(n, L.oP2, ldn, true, L.oVh, d, false);
     j[0].nt = 3;
-    j[1] = job(GM_STORE, -1.f, L.ogQh, d);
-    j[1].t[0] = term(L.oP1, ld, true, L.oVh, d, false);
-    j[1].t[1] = term(L.oP3, ld, false, L.oQh, d, false);
-    j[1].t[2] = term(L.oP3, ld, true, L.oQh, d, false);
+    j[1] = job(GM_STORE, -1.f, m, d, L.ogQh, d);
+    j[1].t[0] = term(n, L.oP1, ldm, true, L.oVh, d, false);
+    j[1].t[1] = term(m, L.oP3, ldm, false, L.oQh, d, false);
+    j[1].t[2] = term(m, L.oP3, ldm, true, L.oQh, d, false);
     j[1].nt = 3;
-    int rc = gemm(c, n, d, n, j, 2);
+    int rc = gemm(c, j, 2);
     if (rc) return rc;
-    hipLaunchKernelGGL(tl_norm_bwd_kernel, dim3((unsigned)((int64_t)c.k * cdiv(n, 4))), dim3(NT), 0, c.s, c.ws, L, n, d, dV, dQ);
+    hipLaunchKernelGGL(tl_norm_bwd_kernel, tokrows(c), dim3(NT), 0, c.s, c.ws, L, n, m, d, dV, dQ);
     MDL_LAUNCH_CHECK();
     return MDL_OK;
 }
 
 }  // namespace got_tiled
 
-// mdl_dispatch_plan product 12 (dispatch_plan.hip)
-int plan_got_tiled(int64_t k, int n, int d, int64_t* o) {
-    if (k < 1 || n < 1 || d < 1 || k > 0x7fffffff) return MDL_E_ARG;
-    if (n > got_tiled::TMAXN || d > got_tiled::TMAXD) return MDL_E_UNSUPPORTED;
-    const int64_t P = got_tiled::cdiv(n, got_tiled::RP), tn = got_tiled::cdiv(n, got_tiled::MT);
+// mdl_dispatch_plan products 12 (m = n) and 13 (dispatch_plan.hip)
+int plan_got_tiled(int64_t k, int n, int m, int d, int64_t* o) {
+    if (k < 1 || n < 1 || m < 1 || d < 1 || k > 0x7fffffff) return MDL_E_ARG;
+    if (n > got_tiled::TMAXN || m > got_tiled::TMAXN || d > got_tiled::TMAXD) return MDL_E_UNSUPPORTED;
+    const int64_t P = got_tiled::cdiv(n, got_tiled::RP), tn = got_tiled::cdiv(n, got_tiled::MT), tm = got_tiled::cdiv(m, got_tiled::MT);
     o[MDL_PLAN_VARIANT] = got_tiled::RP;      // rows of a sweep panel
     o[MDL_PLAN_PERSIST] = 0;
     o[MDL_PLAN_SPLITS] = P;                   // row panels per case (sweep workgroups per case and branch)
     o[MDL_PLAN_TPS] = got_tiled::MT;          // output tile edge of the products
-    o[MDL_PLAN_EMPTY] = tn * tn;              // product tiles per case of an n x n product
+    o[MDL_PLAN_EMPTY] = tn * tm;              // product tiles per case of an n x m product
     o[MDL_PLAN_CHUNK] = got_tiled::CW;        // columns of a sweep chunk
     o[MDL_PLAN_EXTRA] = 2;                    // launches per IPOT iteration (row pass + column merge)
     return MDL_OK;
@@ -1244,84 +1329,118 @@ int plan_got_tiled(int64_t k, int n, int d, int64_t* o) {
 
 using namespace mdl;
 
-static int tl_check(int k, int n, int d) {
-    if (k < 0 || n < 0 || d < 1) return MDL_E_ARG;
-    if (n > got_tiled::TMAXN || d > got_tiled::TMAXD) return MDL_E_UNSUPPORTED;
+static int tl_check(int k, int n, int m, int d) {
+    if (k < 0 || n < 0 || m < 0 || d < 1) return MDL_E_ARG;
+    if (n > got_tiled::TMAXN || m > got_tiled::TMAXN || d > got_tiled::TMAXD) return MDL_E_UNSUPPORTED;
     return MDL_OK;
 }
 
-static got_tiled::Ctx tl_ctx(void* ws, int k, int n, int d, void* stream) {
+static got_tiled::Ctx tl_ctx(void* ws, int k, int n, int m, int d, void* stream) {
     got_tiled::Ctx c;
     c.ws = (float*)ws;
-    c.L = got_tiled::layout(k, n, d);
+    c.L = got_tiled::layout(k, n, m, d);
     c.k = k;
     c.n = n;
+    c.m = m;
     c.d = d;
     c.s = (hipStream_t)stream;
     return c;
 }
 
-extern "C" int64_t mdl_got_tiled_ws_bytes(int k, int n, int d) {
-    const int rc = tl_check(k, n, d);
+// The rectangular entry points: V [k, n, d], Q [k, m, d].  The square ones below are their m = n case.
+extern "C" int64_t mdl_got_tiled_rect_ws_bytes(int k, int n, int m, int d) {
+    const int rc = tl_check(k, n, m, d);
     if (rc) return rc;
-    return got_tiled::layout(k, n, d).g_end * 4 + 64;
+    return got_tiled::layout(k, n, m, d).g_end * 4 + 64;
 }
 
-extern "C" int mdl_got_tiled_fwd(const float* V, const float* Q, float* out, float* minmax_out, const float* minmax_in, int k, int n,
-                                 int d, void* ws, void* stream) {
-    const int rc = tl_check(k, n, d);
+extern "C" int mdl_got_tiled_rect_fwd(const float* V, const float* Q, float* out, float* minmax_out, const float* minmax_in, int k,
+                                      int n, int m, int d, void* ws, void* stream) {
+    const int rc = tl_check(k, n, m, d);
     if (rc) return rc;
     if (!out || !ws) return MDL_E_ARG;
     if (!host_aligned16(ws)) return MDL_E_ALIGN;
-    if (k == 0 || n == 0) {   // empty token tensors may have no storage
+    if (k == 0 || n == 0 || m == 0) {   // empty token tensors may have no storage
         const hipError_t e = hipMemsetAsync(out, 0, 2 * sizeof(float), (hipStream_t)stream);
         return e == hipSuccess ? MDL_OK : (int)e;
     }
     if (!V || !Q) return MDL_E_ARG;
-    const got_tiled::Ctx c = tl_ctx(ws, k, n, d, stream);
+    const got_tiled::Ctx c = tl_ctx(ws, k, n, m, d, stream);
     const int r = got_tiled::launch_prep(c, minmax_out, minmax_in, V, Q);
     if (r) return r;
     return got_tiled::launch_main(c, out);
 }
 
-extern "C" int mdl_got_tiled_extrema(const float* V, const float* Q, float* minmax_out, int k, int n, int d, void* ws, void* stream) {
-    const int rc = tl_check(k, n, d);
+extern "C" int mdl_got_tiled_rect_extrema(const float* V, const float* Q, float* minmax_out, int k, int n, int m, int d, void* ws,
+                                          void* stream) {
+    const int rc = tl_check(k, n, m, d);
     if (rc) return rc;
     if (!V || !Q || !minmax_out || !ws) return MDL_E_ARG;
     if (!host_aligned16(ws)) return MDL_E_ALIGN;
-    if (k == 0 || n == 0) return MDL_E_ARG;   // extrema of an empty batch are undefined
-    return got_tiled::launch_prep(tl_ctx(ws, k, n, d, stream), minmax_out, nullptr, V, Q);
+    if (k == 0 || n == 0 || m == 0) return MDL_E_ARG;   // extrema of an empty batch are undefined
+    return got_tiled::launch_prep(tl_ctx(ws, k, n, m, d, stream), minmax_out, nullptr, V, Q);
 }
 
-extern "C" int mdl_got_tiled_bwd_begin(const float* d_out, float* d_minmax, int k, int n, int d, void* ws, void* stream) {
-    const int rc = tl_check(k, n, d);
+extern "C" int mdl_got_tiled_rect_bwd_begin(const float* d_out, float* d_minmax, int k, int n, int m, int d, void* ws, void* stream) {
+    const int rc = tl_check(k, n, m, d);
     if (rc) return rc;
     if (!d_out || !ws) return MDL_E_ARG;
     if (!host_aligned16(ws)) return MDL_E_ALIGN;
-    if (k == 0 || n == 0) {
+    if (k == 0 || n == 0 || m == 0) {
         if (d_minmax) {
             const hipError_t e = hipMemsetAsync(d_minmax, 0, 6 * sizeof(float), (hipStream_t)stream);
             if (e != hipSuccess) return (int)e;
         }
         return MDL_OK;
     }
-    return got_tiled::launch_bwd_begin(tl_ctx(ws, k, n, d, stream), d_out, d_minmax);
+    return got_tiled::launch_bwd_begin(tl_ctx(ws, k, n, m, d, stream), d_out, d_minmax);
+}
+
+extern "C" int mdl_got_tiled_rect_bwd_finish(const float* V, const float* Q, float* dV, float* dQ, const float* d_minmax_total, int k,
+                                             int n, int m, int d, void* ws, void* stream) {
+    const int rc = tl_check(k, n, m, d);
+    if (rc) return rc;
+    if (!ws) return MDL_E_ARG;
+    if (!host_aligned16(ws)) return MDL_E_ALIGN;
+    if (k == 0 || n == 0 || m == 0) {   // empty token tensors may have no storage; the other side's gradient is zero
+        const size_t bv = (size_t)k * n * d * sizeof(float), bq = (size_t)k * m * d * sizeof(float);
+        if ((bv && !dV) || (bq && !dQ)) return MDL_E_ARG;
+        hipError_t e = bv ? hipMemsetAsync(dV, 0, bv, (hipStream_t)stream) : hipSuccess;
+        if (e == hipSuccess && bq) e = hipMemsetAsync(dQ, 0, bq, (hipStream_t)stream);
+        return e == hipSuccess ? MDL_OK : (int)e;
+    }
+    if (!V || !Q || !dV || !dQ) return MDL_E_ARG;
+    return got_tiled::launch_bwd_finish(tl_ctx(ws, k, n, m, d, stream), d_minmax_total, dV, dQ);
+}
+
+extern "C" int mdl_got_tiled_rect_bwd(const float* V, const float* Q, const float* d_out, float* dV, float* dQ, int k, int n, int m,
+                                      int d, void* ws, void* stream) {
+    const int rc = mdl_got_tiled_rect_bwd_begin(d_out, nullptr, k, n, m, d, ws, stream);
+    if (rc) return rc;
+    return mdl_got_tiled_rect_bwd_finish(V, Q, dV, dQ, nullptr, k, n, m, d, ws, stream);
+}
+
+extern "C" int64_t mdl_got_tiled_ws_bytes(int k, int n, int d) { return mdl_got_tiled_rect_ws_bytes(k, n, n, d); }
+
+extern "C" int mdl_got_tiled_fwd(const float* V, const float* Q, float* out, float* minmax_out, const float* minmax_in, int k, int n,
+                                 int d, void* ws, void* stream) {
+    return mdl_got_tiled_rect_fwd(V, Q, out, minmax_out, minmax_in, k, n, n, d, ws, stream);
+}
+
+extern "C" int mdl_got_tiled_extrema(const float* V, const float* Q, float* minmax_out, int k, int n, int d, void* ws, void* stream) {
+    return mdl_got_tiled_rect_extrema(V, Q, minmax_out, k, n, n, d, ws, stream);
+}
+
+extern "C" int mdl_got_tiled_bwd_begin(const float* d_out, float* d_minmax, int k, int n, int d, void* ws, void* stream) {
+    return mdl_got_tiled_rect_bwd_begin(d_out, d_minmax, k, n, n, d, ws, stream);
 }
 
 extern "C" int mdl_got_tiled_bwd_finish(const float* V, const float* Q, float* dV, float* dQ, const float* d_minmax_total, int k, int n,
                                         int d, void* ws, void* stream) {
-    const int rc = tl_check(k, n, d);
-    if (rc) return rc;
-    if (!ws) return MDL_E_ARG;
-    if (!host_aligned16(ws)) return MDL_E_ALIGN;
-    if (k == 0 || n == 0) return MDL_OK;   // empty token tensors may have no storage
-    if (!V || !Q || !dV || !dQ) return MDL_E_ARG;
-    return got_tiled::launch_bwd_finish(tl_ctx(ws, k, n, d, stream), d_minmax_total, dV, dQ);
+    return mdl_got_tiled_rect_bwd_finish(V, Q, dV, dQ, d_minmax_total, k, n, n, d, ws, stream);
 }
 
 extern "C" int mdl_got_tiled_bwd(const float* V, const float* Q, const float* d_out, float* dV, float* dQ, int k, int n, int d, void* ws,
                                  void* stream) {
-    const int rc = mdl_got_tiled_bwd_begin(d_out, nullptr, k, n, d, ws, stream);
-    if (rc) return rc;
-    return mdl_got_tiled_bwd_finish(V, Q, dV, dQ, nullptr, k, n, d, ws, stream);
+    return mdl_got_tiled_rect_bwd(V, Q, d_out, dV, dQ, k, n, n, d, ws, stream);
 }

@@ -1495,14 +1495,20 @@ def info_nce_neg_rows(Q, P, Neg, temperature, paired):
 # G0-G3: graph optimal transport
 # --------------------------------------------------------------------------------------------------
 class _GotFamily:
-    """One GOT size class on the C ABI: the prefix of its six entry points (mdl_got / mdl_got_tiled), the _timed names of its calls and
-    the message of its refusal."""
+    """One GOT size class on the C ABI: the prefix of its six entry points (mdl_got / mdl_got_tiled / mdl_got_tiled_rect), the _timed
+    names of its calls and the message of its refusal.  A `rect` family takes V [k, n, d] and Q [k, m, d] with n != m; its entry points
+    take the sizes as (k, n, m, d)."""
 
-    def __init__(self, prefix, timed, refusal):
-        self.prefix, self.timed, self.refusal = prefix, timed, refusal
+    def __init__(self, prefix, timed, refusal, rect=False):
+        self.prefix, self.timed, self.refusal, self.rect = prefix, timed, refusal, rect
 
     def fn(self, lib, suffix):
         return getattr(lib, self.prefix + suffix)
+
+    def sizes(self, V, Q):
+        """The size arguments of this family's entry points."""
+        k, n, d = V.shape
+        return (k, n, Q.shape[1], d) if self.rect else (k, n, d)
 
 
 GOT_RESIDENT = _GotFamily("mdl_got", "got",
@@ -1510,31 +1516,36 @@ GOT_RESIDENT = _GotFamily("mdl_got", "got",
                           "the reference calls it with subsample=256 (trainer.py:44)")
 GOT_TILED = _GotFamily("mdl_got_tiled", "got_tiled",
                        "the tiled GOT class supports n <= 4096 tokens per bag and d <= 4096 (got n=%d, d=%d)")
+GOT_TILED_RECT = _GotFamily("mdl_got_tiled_rect", "got_tiled",
+                            "the tiled GOT class supports n <= 4096 and m <= 4096 tokens per bag and d <= 4096 (got n=%d, m=%d, d=%d)",
+                            rect=True)
 
 
 class GOTFn(torch.autograd.Function):
-    """out[2] = (sum_b WD_b, sum_b GWD_b) for token sets V,Q [k,n,d] (loss.py:278-302 after the sub-sampling).
+    """out[2] = (sum_b WD_b, sum_b GWD_b) for token sets V,Q [k,n,d] (loss.py:278-302 after the sub-sampling); Q may be [k,m,d] with
+    m != n for a family that is rectangular-capable (GOT_TILED_RECT).
 
     minmax_in (optional float[6] device tensor) replaces the batch-local threshold extrema (data-parallel path);
     the second output is this call's own extrema [6] (non-differentiable).  `fam` selects the size class (entry-point family):
-    GOT_RESIDENT (the default, functional.got) or GOT_TILED (functional.got_tiled)."""
+    GOT_RESIDENT (the default, functional.got), GOT_TILED or GOT_TILED_RECT (functional.got_tiled)."""
 
     @staticmethod
     def forward(ctx, V, Q, minmax_in, reduce_dminmax, fam=GOT_RESIDENT):
         _require(V, "v_")
         _require(Q, "q_")
-        if V.shape != Q.shape or V.dim() != 3:
+        if V.dim() != 3 or Q.dim() != 3 or (V.shape[0], V.shape[2]) != (Q.shape[0], Q.shape[2]) or (
+                V.shape[1] != Q.shape[1] and not fam.rect):
             raise ValueError("GOT expects two token tensors of identical shape [k, n, d]")
         lib = _native.lib()
-        k, n, d = V.shape
-        nbytes = fam.fn(lib, "_ws_bytes")(k, n, d)
+        sz = fam.sizes(V, Q)
+        nbytes = fam.fn(lib, "_ws_bytes")(*sz)
         if nbytes == -3:
-            raise NotImplementedError(fam.refusal % (n, d))
+            raise NotImplementedError(fam.refusal % sz[1:])
         ws = _ws(nbytes, V.device)
         out = torch.empty(2, device=V.device, dtype=torch.float32)
         mm = torch.empty(6, device=V.device, dtype=torch.float32)
         with _timed(fam.timed + "_fwd"):
-            rc = fam.fn(lib, "_fwd")(_ptr(V), _ptr(Q), _ptr(out), _ptr(mm), _ptr(minmax_in), k, n, d, _ptr(ws), _stream())
+            rc = fam.fn(lib, "_fwd")(_ptr(V), _ptr(Q), _ptr(out), _ptr(mm), _ptr(minmax_in), *sz, _ptr(ws), _stream())
         _native.check(rc, fam.prefix + "_fwd")
         ctx.save_for_backward(V, Q, ws)
         ctx.reduce_dminmax = reduce_dminmax
@@ -1547,19 +1558,19 @@ class GOTFn(torch.autograd.Function):
         V, Q, ws = ctx.saved_tensors
         fam = ctx.fam
         lib = _native.lib()
-        k, n, d = V.shape
+        sz = fam.sizes(V, Q)
         dV, dQ = torch.empty_like(V), torch.empty_like(Q)
         d_out = d_out.contiguous()
         if ctx.reduce_dminmax is None:
             with _timed(fam.timed + "_bwd"):
-                rc = fam.fn(lib, "_bwd")(_ptr(V), _ptr(Q), _ptr(d_out), _ptr(dV), _ptr(dQ), k, n, d, _ptr(ws), _stream())
+                rc = fam.fn(lib, "_bwd")(_ptr(V), _ptr(Q), _ptr(d_out), _ptr(dV), _ptr(dQ), *sz, _ptr(ws), _stream())
             _native.check(rc, fam.prefix + "_bwd")
         else:
             dmm = torch.empty(6, device=V.device, dtype=torch.float32)
-            rc = fam.fn(lib, "_bwd_begin")(_ptr(d_out), _ptr(dmm), k, n, d, _ptr(ws), _stream())
+            rc = fam.fn(lib, "_bwd_begin")(_ptr(d_out), _ptr(dmm), *sz, _ptr(ws), _stream())
             _native.check(rc, fam.prefix + "_bwd_begin")
             dmm = ctx.reduce_dminmax(dmm).contiguous()      # e.g. all_reduce(SUM) over ranks
-            rc = fam.fn(lib, "_bwd_finish")(_ptr(V), _ptr(Q), _ptr(dV), _ptr(dQ), _ptr(dmm), k, n, d, _ptr(ws), _stream())
+            rc = fam.fn(lib, "_bwd_finish")(_ptr(V), _ptr(Q), _ptr(dV), _ptr(dQ), _ptr(dmm), *sz, _ptr(ws), _stream())
             _native.check(rc, fam.prefix + "_bwd_finish")
         return dV, dQ, None, None, None
 
@@ -1599,14 +1610,17 @@ def got(V, Q, minmax_in=None, reduce_dminmax=None, return_extrema=False):
 
 
 def got_tiled(V, Q, minmax_in=None, reduce_dminmax=None, return_extrema=False):
-    """functional.got on the tiled size class (1 <= n <= 4096, 1 <= d <= 4096, any k; csrc/got_tiled.hip): same contract."""
-    out, mm = GOTFn.apply(V, Q, minmax_in, reduce_dminmax, GOT_TILED)
+    """functional.got on the tiled size class (1 <= n <= 4096, 1 <= d <= 4096, any k; csrc/got_tiled.hip): same contract.  Q may have
+    another token count than V (V [k, n, d], Q [k, m, d], 1 <= m <= 4096): the cross cost and the plans are then n x m, and the
+    data-parallel contract (global extrema in, d_minmax reduced by the caller's function) is unchanged.  GOT(V, Q) != GOT(Q, V)."""
+    fam = GOT_TILED if V.dim() != 3 or Q.dim() != 3 or V.shape[1] == Q.shape[1] else GOT_TILED_RECT
+    out, mm = GOTFn.apply(V, Q, minmax_in, reduce_dminmax, fam)
     return (out, mm) if return_extrema else out
 
 
-def got_tiled_supported(k: int, n: int, d: int) -> bool:
-    """True when the tiled class accepts [k, n, d] (mdl_got_tiled_ws_bytes does not refuse it)."""
-    return _native.lib().mdl_got_tiled_ws_bytes(k, n, d) >= 0
+def got_tiled_supported(k: int, n: int, d: int, m: int = None) -> bool:
+    """True when the tiled class accepts V [k, n, d] with Q [k, m, d] (m omitted: m = n); mdl_got_tiled_rect_ws_bytes does not refuse it."""
+    return _native.lib().mdl_got_tiled_rect_ws_bytes(k, n, n if m is None else m, d) >= 0
 
 
 def got_resident_supported(k: int, n: int, d: int) -> bool:

@@ -103,7 +103,13 @@ def GOT(v_, q_, subsample=None):
 
     The sub-sample quirk of the reference is kept: indices are torch.randperm(v_.shape[0]) -- the (masked)
     BATCH size k, not the token count -- so the first n = min(k, subsample) tokens of each bag are used, in a
-    random order that only changes summation order."""
+    random order that only changes summation order.
+
+    v_ [k, n, d] and q_ [k, m, d] may hold different token counts (n != m, both <= 4096): the cross cost and the transport plans are
+    then n x m, on the tiled size class.  GOT(v, q) != GOT(q, v).  With `subsample` both are indexed with the same indices, as in
+    the reference, and an index beyond the shorter one raises IndexError."""
+    if v_.dim() == 3 and q_.dim() == 3 and v_.shape[1] != q_.shape[1]:
+        return _got_rect(v_, q_, subsample)
     if subsample is not None:
         patch_indices = torch.randperm(v_.shape[0])[:subsample].to(v_.device)
         v_ = v_.index_select(1, patch_indices)
@@ -120,9 +126,30 @@ def GOT(v_, q_, subsample=None):
     return out[1] + out[0]
 
 
-def got_route(k, n, d):
+def _got_rect(v_, q_, subsample):
+    """GOT() for v_ [k, n, d], q_ [k, m, d] with n != m."""
+    if subsample is not None:
+        patch_indices = torch.randperm(v_.shape[0])[:subsample]
+        short = min(v_.shape[1], q_.shape[1])
+        if patch_indices.numel() and int(patch_indices.max()) >= short:
+            # what the reference's v_[:, idx, :] raises; checked on the host so that no device-side bounds assert fires
+            raise IndexError("index %d is out of bounds for dimension 1 with size %d" % (int(patch_indices.max()), short))
+        patch_indices = patch_indices.to(v_.device)
+        return GOT(v_.index_select(1, patch_indices), q_.index_select(1, patch_indices))   # equal token counts from here on
+    v, q = v_.float().contiguous(), q_.float().contiguous()
+    if (v.shape[0], v.shape[2]) == (q.shape[0], q.shape[2]) and got_route(*v.shape, m=q.shape[1]) == "unsupported":
+        raise NotImplementedError("madeleine_amd.GOT supports n <= 4096 and m <= 4096 tokens per bag and d <= 4096 "
+                                  "(got n=%d, m=%d, d=%d)" % (v.shape[1], q.shape[1], v.shape[2]))
+    out = MF.got_tiled(v, q)
+    return out[1] + out[0]
+
+
+def got_route(k, n, d, m=None):
     """Size class GOT() uses for [k, n, d] after the sub-sampling: 'resident' where mdl_got_ws_bytes accepts the shape (functional.got,
-    the training path's class), else 'tiled' where the tiled class accepts it, else 'unsupported'."""
+    the training path's class), else 'tiled' where the tiled class accepts it, else 'unsupported'.  With m given and m != n (q_ holds m
+    tokens per bag) only the tiled class can take the pair: 'tiled' or 'unsupported'."""
+    if m is not None and m != n:
+        return "tiled" if MF.got_tiled_supported(k, n, d, m) else "unsupported"
     if MF.got_resident_supported(k, n, d):
         return "resident"
     if MF.got_tiled_supported(k, n, d):
