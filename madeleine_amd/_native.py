@@ -7,141 +7,68 @@ non-zero return code.
 """
 import ctypes
 import os
+import re
 import threading
 
 from . import _build
 
 _LOCK = threading.Lock()
 _LIB = None
-ABI_VERSION = 26   # == MDL_ABI_VERSION of include/madeleine_amd.h this file's SIGNATURES were written against
 
-c_f = ctypes.c_void_p  # float* (device)
-c_p = ctypes.c_void_p
-i64 = ctypes.c_int64
-i32 = ctypes.c_int
-u64 = ctypes.c_uint64
-f32 = ctypes.c_float
+# The header's scalar types; every pointer is passed as an address (c_void_p).  Anything else is an error, never a guess.
+_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32,
+            "float": ctypes.c_float}
+_POINTEES = frozenset(_SCALARS) | {"void", "char", "uint8_t", "uint16_t", "int32_t"}
+_DECL = re.compile(r"(?P<ret>[\w\s*]+?)\b(?P<name>\w+)\s*\((?P<args>[^()]*)\)")
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", re.M)
 
-# name -> (restype, argtypes); mirrors include/madeleine_amd.h declaration by declaration
-SIGNATURES = {
-    "mdl_version": (ctypes.c_char_p, []),
-    "mdl_abi_version": (i32, []),
-    "mdl_abmil_gate_fwd_ws_bytes": (i64, [i64, i32]),
-    "mdl_abmil_gate_fwd": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, u64, c_p, c_p, c_p, c_p]),
-    "mdl_abmil_gate_bwd_ws_bytes": (i64, [i64, i32]),
-    "mdl_abmil_gate_bwd": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32,
-                                 u64, c_p, c_p, c_p, c_p]),
-    "mdl_abmil_attnpool_bwd": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, u64, c_p, c_p, c_f, c_f,
-                                     c_f, c_f, c_p, i64, c_p, c_p]),
-    "mdl_abmil_attnpool_bwd_phases": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, u64, c_p, c_p,
-                                            c_f, c_f, c_f, c_f, c_p, i64, c_p, c_p, i32]),
-    "mdl_abmil_attnpool_bwd_phases_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, u64, c_p,
-                                                 c_p, c_f, c_f, c_f, c_f, c_p, i64, c_p, c_p, i32]),
-    "mdl_abmil_gate_dropout_mask": (i32, [c_p, i64, i32, i32, f32, u64, c_p]),
-    "mdl_abmil_pool_ws_bytes": (i64, [i64, i64, i32]),
-    "mdl_abmil_pool_fwd": (i32, [c_f, i64, c_f, c_f, c_f, c_f, i64, i64, c_p, i64, i32, c_p, c_p]),
-    "mdl_abmil_pool_bwd": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, i32, c_f, i32, i64, i64, c_p, i64, i32, c_p]),
-    "mdl_abmil_pool_view_fwd": (i32, [c_f, i64, c_f, c_f, c_f, c_f, i64, i64, c_p, i64, i32, c_p, c_p]),
-    "mdl_abmil_pool_view_bwd": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i64, c_p, i64, i32, c_p]),
-    "mdl_abmil_pool_view_fwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, i64, i64, c_p, i64, i32, c_p, c_p]),
-    "mdl_abmil_pool_view_bwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i64, c_p, i64, i32, c_p]),
-    "mdl_abmil_pool_rview_fwd": (i32, [c_f, i64, c_f, c_f, c_f, c_f, i64, c_p, c_p, i64, i32, c_p, c_p]),
-    "mdl_abmil_pool_rview_bwd": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, c_p, c_p, i64, i32, c_p]),
-    "mdl_abmil_pool_rview_fwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, i64, c_p, c_p, i64, i32, c_p, c_p]),
-    "mdl_abmil_pool_rview_bwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, c_p, c_p, i64, i32, c_p]),
-    "mdl_ln_gelu_drop_fwd": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, f32, u64, c_p, c_p]),
-    "mdl_ln_gelu_drop_bwd_ws_bytes": (i64, [i64, i32]),
-    "mdl_ln_gelu_drop_bwd": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, u64, c_p, c_p, c_p]),
-    "mdl_linear_fwd_ws_bytes": (i64, [i64, i32, i32]),
-    "mdl_linear_fwd": (i32, [c_f, i64, c_f, c_f, c_f, i64, i64, i32, i32, c_p, c_p]),
-    "mdl_linear_bwd_ws_bytes": (i64, [i64, i32, i32]),
-    "mdl_linear_bwd": (i32, [c_f, i64, c_f, c_f, i64, c_f, i64, c_f, c_f, i64, i32, i32, c_p, c_p]),
-    "mdl_infonce_ws_bytes": (i64, [i32, i32, i32]),
-    "mdl_infonce_fwd": (i32, [c_f, c_f, c_p, c_f, c_f, i32, i32, i32, f32, i32, c_p, c_p]),
-    "mdl_infonce_bwd": (i32, [c_f, c_f, c_f, c_f, c_p, c_f, c_f, i32, i32, i32, f32, i32, c_p, c_p]),
-    "mdl_infonce_neg_ws_bytes": (i64, [i32, i32, i32, i32]),
-    "mdl_infonce_neg_fwd": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, f32, c_p, c_p]),
-    "mdl_infonce_neg_bwd": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, f32, c_p, c_p]),
-    "mdl_got_ws_bytes": (i64, [i32, i32, i32]),
-    "mdl_got_fwd": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_p, c_p]),
-    "mdl_got_extrema": (i32, [c_f, c_f, c_f, i32, i32, i32, c_p, c_p]),
-    "mdl_got_bwd": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_p, c_p]),
-    "mdl_got_bwd_begin": (i32, [c_f, c_f, i32, i32, i32, c_p, c_p]),
-    "mdl_got_bwd_finish": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_p, c_p]),
-    # tiled class (same argument lists as the mdl_got_* entry points above)
-    "mdl_got_tiled_ws_bytes": (i64, [i32, i32, i32]),
-    "mdl_got_tiled_fwd": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_p, c_p]),
-    "mdl_got_tiled_extrema": (i32, [c_f, c_f, c_f, i32, i32, i32, c_p, c_p]),
-    "mdl_got_tiled_bwd": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_p, c_p]),
-    "mdl_got_tiled_bwd_begin": (i32, [c_f, c_f, i32, i32, i32, c_p, c_p]),
-    "mdl_got_tiled_bwd_finish": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_p, c_p]),
-    # ... between token sets of different sizes: (k, n, m, d)
-    "mdl_got_tiled_rect_ws_bytes": (i64, [i32, i32, i32, i32]),
-    "mdl_got_tiled_rect_fwd": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, c_p, c_p]),
-    "mdl_got_tiled_rect_extrema": (i32, [c_f, c_f, c_f, i32, i32, i32, i32, c_p, c_p]),
-    "mdl_got_tiled_rect_bwd": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, c_p, c_p]),
-    "mdl_got_tiled_rect_bwd_begin": (i32, [c_f, c_f, i32, i32, i32, i32, c_p, c_p]),
-    "mdl_got_tiled_rect_bwd_finish": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, c_p, c_p]),
-    # several problems per launch: host arrays of np device pointers / ints
-    "mdl_got_extrema_multi": (i32, [i32, c_p, c_p, c_p, c_p, c_p, i32, c_p, c_p]),
-    "mdl_got_fwd_multi": (i32, [i32, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p, c_p]),
-    "mdl_got_bwd_begin_multi": (i32, [i32, c_p, c_p, c_p, c_p, i32, c_p, c_p]),
-    "mdl_got_bwd_finish_multi": (i32, [i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p, c_p]),
-    # bf16 mode (same argument lists as the fp32 entry points; activation pointers are bf16)
-    "mdl_ln_gelu_drop_fwd_bf16": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, f32, u64, c_p, c_p]),
-    "mdl_ln_gelu_drop_bwd_bf16": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, u64, c_p, c_p,
-                                        c_p]),
-    "mdl_ln_gelu_drop_fwd_groups": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, f32, u64, c_p, c_p, i32, c_p]),
-    "mdl_ln_gelu_drop_fwd_groups_bf16": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, f32, u64, c_p, c_p, i32, c_p]),
-    "mdl_ln_gelu_drop_bwd_groups": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, u64, c_p, c_p, i32,
-                                          c_p, c_p]),
-    "mdl_ln_gelu_drop_bwd_groups_bf16": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, u64, c_p, c_p, i32,
-                                               c_p, c_p]),
-    "mdl_abmil_pool_fwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, i64, i64, c_p, i64, i32, c_p, c_p]),
-    "mdl_abmil_pool_bwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, i32, c_f, i32, i64, i64, c_p, i64, i32, c_p]),
-    "mdl_abmil_wpool_fwd": (i32, [c_f, i64, c_f, c_f, c_f, c_f, i64, i64, c_p, i64, i32, c_p, c_p]),
-    "mdl_abmil_wpool_bwd": (i32, [c_f, i64, c_f, c_f, c_f, i32, c_f, i64, i64, c_p, i64, i32, c_p]),
-    "mdl_abmil_wpool_fwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, i64, i64, c_p, i64, i32, c_p, c_p]),
-    "mdl_abmil_wpool_bwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, i32, c_f, i64, i64, c_p, i64, i32, c_p]),
-    "mdl_linear_bf16_supported": (i32, [i64, i64, i32]),
-    "mdl_linear_fwd_bf16_ws_bytes": (i64, [i64, i64, i64]),
-    "mdl_linear_fwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, i64, i64, i64, i64, c_p, c_p]),
-    "mdl_linear_bwd_bf16_ws_bytes": (i64, [i64, i64, i64]),
-    "mdl_linear_bwd_bf16": (i32, [c_f, i64, c_f, c_f, i64, c_f, i64, c_f, c_f, i64, i64, i64, c_p, c_p]),
-    "mdl_abmil_gate_fwd_bf16_ws_bytes": (i64, [i64, i32]),
-    "mdl_abmil_gate_fwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, u64, c_p, c_p, c_p,
-                                      c_p]),
-    "mdl_abmil_gate_bwd_bf16_ws_bytes": (i64, [i64, i32]),
-    "mdl_abmil_attnpool_bwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, u64, c_p, c_p, c_f, c_f,
-                                     c_f, c_f, c_p, i64, c_p, c_p]),
-    # split-fp16 engine
-    "mdl_pool_timer_arm": (i32, [i32]),
-    "mdl_pool_timer_read": (i32, [i32, c_f]),
-    "mdl_stream_create_cu_mask": (i32, [ctypes.c_uint32, c_p, c_p]),
-    "mdl_stream_destroy": (i32, [c_p]),
-    "mdl_split_image": (i32, [c_f, i64, i64, i32, c_p, i64, i64, c_f, c_p]),
-    "mdl_abmil_pool_fwd_img": (i32, [c_p, i64, c_f, c_f, c_f, c_f, c_f, i64, i64, c_p, i64, i32, c_p, c_p]),
-    "mdl_abmil_pool_dscores_img": (i32, [c_p, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, i64, i64, c_p, i64, i32, c_p]),
-    "mdl_split_tile_absmax": (i32, [c_f, i64, i64, i32, c_f, c_f, c_p]),
-    "mdl_split_gemm_nt": (i32, [c_p, i64, c_f, c_p, i64, c_f, c_f, i64, i64, i32, i32, c_f, i32, c_f, c_f, c_f, c_f, i32, c_p]),
-    "mdl_split_gemm_nt_group_bias": (i32, [c_p, i64, c_f, c_p, i64, c_f, c_f, i64, i64, i32, i32, c_f, c_f, c_f, c_f, c_p, i32, c_p]),
-    "mdl_ln_gelu_drop_bwd_groups_ws_bytes": (i64, [i64, i32, i32]),
-    "mdl_ln_gelu_drop_bwd_split_groups": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_f, c_f, c_f, c_f, i64, i32, f32, u64, c_p, c_f, c_f,
-                                                c_p, i32, c_f, c_p, c_p]),
-    "mdl_split_image_rows": (i32, [c_f, i64, i64, i32, c_p, i64, i64, c_f, c_f, c_p]),
-    "mdl_split_gemm_tn_ws_bytes": (i64, [i64, i32, i32]),
-    "mdl_split_gemm_tn": (i32, [c_p, i64, c_f, i32, c_p, i64, c_f, i32, c_f, i64, c_f, c_p, i32, c_p]),
-    "mdl_ln_gelu_drop_fwd_split": (i32, [c_f, c_f, c_f, c_f, c_f, c_p, c_f, c_f, c_f, i64, i32, f32, f32, u64, c_p, c_f, c_f, c_p]),
-    "mdl_ln_gelu_drop_bwd_split": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_f, c_f, c_f, c_f, i64, i32, f32, u64, c_p, c_f, c_f, c_p, c_p]),
-    "mdl_abmil_gate_fwd_split_ws_bytes": (i64, [i64, i32]),
-    "mdl_abmil_gate_fwd_split": (i32, [c_p, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, f32, u64, c_p, c_p, c_p, c_p]),
-    "mdl_abmil_gate_bwd_split_ws_bytes": (i64, [i64, i32]),
-    "mdl_abmil_attnpool_bwd_split": (i32, [c_p, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32,
-                                           f32, u64, c_p, c_p, c_f, c_f, c_f, c_f, c_p, i64, c_f, c_p, c_p, i32, i32]),
-    "mdl_abmil_gate_bwd_bf16": (i32, [c_f, i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, c_f, c_f, c_f, c_f, c_f, c_f, i64, i32,
-                                      f32, u64, c_p, c_p, c_p, c_p]),
-    "mdl_dispatch_plan": (i32, [i32, i64, i32, i32, i32, c_p, i32]),
-}
+
+def _ctype(text, decl, named):
+    """ctypes type of one parameter (`named`: the last word is its name) or of a return type."""
+    words = [w for w in text.replace("*", " * ").split() if w != "const"]
+    if named:      # the last word must be the parameter's name: `const float*` or `float x[4]` is not read as a float
+        if not (len(words) >= 2 and words[-1].isidentifier() and words[-1] not in _POINTEES):
+            raise ValueError("madeleine_amd: unknown type %r in the declaration of %s" % (" ".join(text.split()), decl))
+        words = words[:-1]
+    if len(words) == 1 and words[0] in _SCALARS:
+        return _SCALARS[words[0]]
+    if named and len(words) >= 2 and words[0] in _POINTEES and set(words[1:]) == {"*"}:
+        return ctypes.c_void_p
+    if not named and words == ["char", "*"]:      # the version string
+        return ctypes.c_char_p
+    raise ValueError("madeleine_amd: unknown type %r in the declaration of %s" % (" ".join(text.split()), decl))
+
+
+def _parse_header(text):
+    """(SIGNATURES, integer #defines) of the C header `text`.  Strict: every statement must read as `ret name(args);` with types
+    from the tables above, names must be unique and at least one declaration must be found -- a header this cannot read is an
+    import error, not a kernel launched with shifted arguments."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    defines = {m.group(1): int(m.group(2)) for m in _DEFINE.finditer(text)}
+    text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)      # extern "C" { ... }
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    sigs = {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        if not stmt:
+            continue
+        m = _DECL.fullmatch(stmt)
+        if m is None:
+            raise ValueError("madeleine_amd: cannot read the header declaration %r" % stmt[:80])
+        name, args = m.group("name"), m.group("args").strip()
+        if name in sigs:
+            raise ValueError("madeleine_amd: the header declares %s twice" % name)
+        argtypes = [] if args == "void" else [_ctype(a, name, True) for a in args.split(",")]
+        sigs[name] = (_ctype(m.group("ret"), name, False), argtypes)
+    if not sigs:
+        raise ValueError("madeleine_amd: the header declares no entry point")
+    return sigs, defines
+
+
+# name -> (restype, argtypes), and the header's integer #defines: include/madeleine_amd.h is the only source of both
+with open(_build.HEADER) as _f:
+    SIGNATURES, _DEFINES = _parse_header(_f.read())
+ABI_VERSION = _DEFINES["MDL_ABI_VERSION"]
 
 
 def lib_path() -> str:
@@ -180,7 +107,7 @@ def lib():
         except AttributeError:
             raise RuntimeError("madeleine_amd: %s predates the ABI-version check; rebuild it "
                                "(`python -m madeleine_amd._build --force`)" % path) from None
-        abi.restype, abi.argtypes = i32, []
+        abi.restype, abi.argtypes = SIGNATURES["mdl_abi_version"]
         if abi() != ABI_VERSION:
             raise RuntimeError("madeleine_amd: %s implements ABI revision %d, this binding expects %d; rebuild it "
                                "(`python -m madeleine_amd._build --force`)" % (path, abi(), ABI_VERSION))
@@ -195,8 +122,9 @@ def lib():
         return _LIB
 
 
-_ERR = {-1: "MDL_E_ARG (bad size / null pointer)", -2: "MDL_E_ALIGN (pointer not 16-byte aligned)",
-        -3: "MDL_E_UNSUPPORTED"}
+_E_UNSUPPORTED = _DEFINES["MDL_E_UNSUPPORTED"]
+_ERR_TEXT = {"MDL_E_ARG": "MDL_E_ARG (bad size / null pointer)", "MDL_E_ALIGN": "MDL_E_ALIGN (pointer not 16-byte aligned)"}
+_ERR = {v: _ERR_TEXT.get(k, k) for k, v in _DEFINES.items() if k.startswith("MDL_E_")}
 
 
 def check(rc: int, what: str):
@@ -205,11 +133,12 @@ def check(rc: int, what: str):
         raise RuntimeError("madeleine_amd: %s failed: %s" % (what, msg))
 
 
-# mdl_dispatch_plan products / fields (include/madeleine_amd.h)
-PLAN_PRODUCTS = {"gate_fp32_bwd": 1, "gate_split_fwd": 2, "gate_split_bwd": 3, "gate_bf16_fwd": 4, "gate_bf16_bwd": 5, "split_tn": 6,
-                 "linear_fp32_bwd": 7, "linear_bf16_fwd": 8, "linear_bf16_bwd": 9, "got": 10, "infonce_neg": 11,
-                 "got_tiled": 12, "got_tiled_rect": 13}
+# mdl_dispatch_plan: the fields of an answer, in the order of their MDL_PLAN_<FIELD> indices, and the products (every other MDL_PLAN_*)
 PLAN_FIELDS = ("variant", "persist", "splits", "tps", "empty", "chunk", "extra")
+if _DEFINES["MDL_PLAN_FIELDS"] != len(PLAN_FIELDS) or any(_DEFINES["MDL_PLAN_" + f.upper()] != i for i, f in enumerate(PLAN_FIELDS)):
+    raise ImportError("madeleine_amd: PLAN_FIELDS does not match the MDL_PLAN_* field indices of %s" % _build.HEADER)
+PLAN_PRODUCTS = {k[len("MDL_PLAN_"):].lower(): v for k, v in _DEFINES.items()
+                 if k.startswith("MDL_PLAN_") and k[len("MDL_PLAN_"):].lower() not in PLAN_FIELDS + ("fields",)}
 
 
 def dispatch_plan(product: str, T: int, a: int, b: int = 0, cus: int = 256) -> dict:

@@ -19,11 +19,32 @@ HID = 512
 
 
 def _ptr(t: Optional[torch.Tensor]):
+    """What _call passes for one tensor argument (for callers that bind an entry point themselves)."""
     return None if t is None else t.data_ptr()
 
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+_ENTRY = {}   # name -> bound entry point, resolved once: a process loads one library (_native.lib() never replaces its handle)
+
+
+def _entry(name):
+    fn = _ENTRY[name] = getattr(_native.lib(), name)
+    return fn
+
+
+def _call(name, *args, unsupported=None):
+    """The one way into the library: calls entry point `name` (the name actually called, _bf16 suffix included) and raises under that
+    name on a non-zero return code.  A tensor argument goes in as its device address; None (a NULL pointer), numbers and host arrays
+    as they are -- in one comprehension, this runs for every launch of a host-bound step.  unsupported = (text, values...): the
+    NotImplementedError of a call site where MDL_E_UNSUPPORTED is the refusal of a geometry, formatted only when it is raised."""
+    rc = (_ENTRY.get(name) or _entry(name))(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args])
+    if rc != 0:
+        if rc == _native._E_UNSUPPORTED and unsupported is not None:
+            raise NotImplementedError(unsupported[0] % unsupported[1:])
+        _native.check(rc, name)
 
 
 ACT_DTYPES = (torch.float32, torch.bfloat16)   # storage types of the activation tensors (parity mode / bf16 mode)
@@ -101,16 +122,16 @@ class PoolDispatchTimer:
         self.n = 0
 
     def arm(self):
-        _native.check(_native.lib().mdl_pool_timer_arm(self.n % self.SLOTS), "mdl_pool_timer_arm")
+        _call("mdl_pool_timer_arm", self.n % self.SLOTS)
         self.n += 1
 
     def report(self):
         """[(pool_partial ms, pool_combine ms, first start -> last end ms)] of the last min(calls, 64) pooling forwards."""
         import ctypes
-        lib, out = _native.lib(), []
+        out = []
         for i in range(max(0, self.n - self.SLOTS), self.n):
             ms = (ctypes.c_float * 3)()
-            _native.check(lib.mdl_pool_timer_read(i % self.SLOTS, ms), "mdl_pool_timer_read")
+            _call("mdl_pool_timer_read", i % self.SLOTS, ms)
             out.append((float(ms[0]), float(ms[1]), float(ms[2])))
         return out
 
@@ -139,6 +160,37 @@ def _ws(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
+def _ws_for(query, device, *sizes, refusal=None) -> torch.Tensor:
+    """The workspace whose size the mdl_*_ws_bytes entry point `query` gives for `sizes`.  These host-only queries return a byte count,
+    not a return code, which is why they do not go through _call.  refusal = (text, values...): the NotImplementedError where
+    MDL_E_UNSUPPORTED from the query is the refusal of a geometry."""
+    nbytes = (_ENTRY.get(query) or _entry(query))(*sizes)
+    if nbytes == _native._E_UNSUPPORTED and refusal is not None:
+        raise NotImplementedError(refusal[0] % refusal[1:])
+    return _ws(nbytes, device)
+
+
+_LN_WIDTHS = "fused LayerNorm-GELU-Dropout supports widths 256/512/1024/2048/4096 (got %d)"
+
+
+def _gate_grads(Wa, Wb):
+    """Uninitialised (dWa, dWb, dba, dbb, dwc, dbc) of the gate parameters Wa, Wb [H,512,512]."""
+    H, dev = Wa.shape[0], Wa.device
+    dWa, dWb = torch.empty_like(Wa), torch.empty_like(Wb)
+    dba = torch.empty(H, HID, device=dev, dtype=torch.float32)
+    dbb, dwc = torch.empty_like(dba), torch.empty_like(dba)
+    dbc = torch.empty(H, device=dev, dtype=torch.float32)
+    return dWa, dWb, dba, dbb, dwc, dbc
+
+
+def _pool_outputs(n_out, H, device, pooled_shape=None):
+    """Uninitialised (pooled [n_out, H*512] or `pooled_shape`, stat_m, stat_l [n_out, H]) of a pooling forward over n_out bags / views."""
+    pooled = torch.empty(pooled_shape or (n_out, H * HID), device=device, dtype=torch.float32)
+    stat_m = torch.empty(n_out, H, device=device, dtype=torch.float32)
+    stat_l = torch.empty(n_out, H, device=device, dtype=torch.float32)
+    return pooled, stat_m, stat_l
+
+
 def h2d(t: torch.Tensor, device, dtype=None) -> torch.Tensor:
     """Host tensor -> device WITHOUT blocking the host.  A copy from pageable memory (`t.to(device, non_blocking=True)` on an
     ordinary CPU tensor) is stream-ordered AND synchronous for the caller: the host stalls until the GPU has drained everything queued
@@ -162,36 +214,30 @@ def new_dropout_seed() -> int:
 # raw calls (no autograd)
 # --------------------------------------------------------------------------------------------------
 def gate_fwd_raw(E2d, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b, save_act: bool):
-    lib = _native.lib()
     T, H = E2d.shape[0], Wa.shape[0]
     dev = E2d.device
     scores = torch.empty(T, H, device=dev, dtype=torch.float32)
     act_a = torch.empty(T, H, HID, device=dev, dtype=E2d.dtype) if save_act else None
     act_b = torch.empty(T, H, HID, device=dev, dtype=E2d.dtype) if save_act else None
     sfx = _sfx(E2d)
-    ws = _ws(getattr(lib, "mdl_abmil_gate_fwd%s_ws_bytes" % sfx)(T, H), dev)
+    ws = _ws_for("mdl_abmil_gate_fwd%s_ws_bytes" % sfx, dev, T, H)
     with _timed("gate_fwd", ("flop", 2.0 * T * H * HID * 2 * HID)):
-        rc = getattr(lib, "mdl_abmil_gate_fwd" + sfx)(_ptr(E2d), E2d.stride(0), _ptr(Wa), _ptr(ba), _ptr(Wb), _ptr(bb), _ptr(wc), _ptr(bc),
-                                    _ptr(scores), _ptr(act_a), _ptr(act_b), T, H, float(p_drop), int(seed),
-                                    _ptr(keep_a), _ptr(keep_b), _ptr(ws), _stream())
-    _native.check(rc, "mdl_abmil_gate_fwd")
+        _call("mdl_abmil_gate_fwd" + sfx, E2d, E2d.stride(0), Wa, ba, Wb, bb, wc, bc, scores, act_a, act_b, T, H, float(p_drop), int(seed),
+              keep_a, keep_b, ws, _stream())
     return scores, act_a, act_b
 
 
 def gate_fwd_split_raw(Ei, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b, save_act: bool):
     """gate_fwd_raw on the split engine: Ei = SplitImage of the head-major token embeddings [T, H*512]."""
-    lib = _native.lib()
     T, H = Ei.rows, Wa.shape[0]
     dev = Ei.data.device
     scores = torch.empty(T, H, device=dev, dtype=torch.float32)
     act_a = torch.empty(T, H, HID, device=dev, dtype=torch.float32) if save_act else None
     act_b = torch.empty(T, H, HID, device=dev, dtype=torch.float32) if save_act else None
-    ws = _ws(lib.mdl_abmil_gate_fwd_split_ws_bytes(T, H), dev)
+    ws = _ws_for("mdl_abmil_gate_fwd_split_ws_bytes", dev, T, H)
     with _timed("gate_fwd", ("flop", 2.0 * T * H * HID * 2 * HID)):
-        rc = lib.mdl_abmil_gate_fwd_split(_ptr(Ei.data), Ei.K * 4, _ptr(Ei.scale), _ptr(Wa), _ptr(ba), _ptr(Wb), _ptr(bb), _ptr(wc), _ptr(bc),
-                                          _ptr(scores), _ptr(act_a), _ptr(act_b), T, H, float(p_drop), int(seed), _ptr(keep_a), _ptr(keep_b),
-                                          _ptr(ws), _stream())
-    _native.check(rc, "mdl_abmil_gate_fwd_split")
+        _call("mdl_abmil_gate_fwd_split", Ei.data, Ei.K * 4, Ei.scale, Wa, ba, Wb, bb, wc, bc, scores, act_a, act_b, T, H, float(p_drop),
+              int(seed), keep_a, keep_b, ws, _stream())
     return scores, act_a, act_b
 
 
@@ -199,22 +245,14 @@ def attnpool_bwd_split_raw(Ei, Wa, Wb, wc, act_a, act_b, d_scores, dE, p_drop, s
                            row_bag, N, accumulate=0, dE_absmax=None, phases=None):
     """attnpool_bwd_raw (scores None: gate_bwd_raw) on the split engine.  `phases`: a sequence of phase masks issued one after the other
     on the same workspace (include/madeleine_amd.h: 1 = dz pass, 2 = both contractions, 4 = dX alone, 8 = dW alone); None = one call."""
-    lib = _native.lib()
     T, H = Ei.rows, Wa.shape[0]
-    dev = Ei.data.device
-    dWa, dWb = torch.empty_like(Wa), torch.empty_like(Wb)
-    dba = torch.empty(H, HID, device=dev, dtype=torch.float32)
-    dbb, dwc = torch.empty_like(dba), torch.empty_like(dba)
-    dbc = torch.empty(H, device=dev, dtype=torch.float32)
-    ws = _ws(lib.mdl_abmil_gate_bwd_split_ws_bytes(T, H), dev)
+    grads = _gate_grads(Wa, Wb)
+    ws = _ws_for("mdl_abmil_gate_bwd_split_ws_bytes", Ei.data.device, T, H)
 
     def call(phases):
-        rc = lib.mdl_abmil_attnpool_bwd_split(_ptr(Ei.data), Ei.K * 4, _ptr(Ei.scale), _ptr(Wa), _ptr(Wb), _ptr(wc), _ptr(act_a), _ptr(act_b),
-                                              _ptr(d_scores), _ptr(dE), dE.stride(0), int(accumulate), _ptr(dWa), _ptr(dWb), _ptr(dba), _ptr(dbb),
-                                              _ptr(dwc), _ptr(dbc), T, H, float(p_drop), int(seed), _ptr(keep_a), _ptr(keep_b), _ptr(scores),
-                                              _ptr(stat_m), _ptr(stat_l), _ptr(d_pooled), _ptr(row_bag), int(N), _ptr(dE_absmax), _ptr(ws),
-                                              _stream(), phases, GRAD_TERMS)
-        _native.check(rc, "mdl_abmil_attnpool_bwd_split")
+        _call("mdl_abmil_attnpool_bwd_split", Ei.data, Ei.K * 4, Ei.scale, Wa, Wb, wc, act_a, act_b, d_scores, dE, dE.stride(0),
+              int(accumulate), *grads, T, H, float(p_drop), int(seed), keep_a, keep_b, scores, stat_m, stat_l, d_pooled, row_bag, int(N),
+              dE_absmax, ws, _stream(), phases, GRAD_TERMS)
     if phases is not None:
         for ph in phases:
             call(int(ph))
@@ -225,169 +263,115 @@ def attnpool_bwd_split_raw(Ei, Wa, Wb, wc, act_a, act_b, d_scores, dE, p_drop, s
             call(2)
     else:
         call(3)
-    return dWa, dWb, dba, dbb, dwc, dbc
+    return grads
 
 
 def gate_bwd_raw(E2d, Wa, Wb, wc, act_a, act_b, d_scores, dE, accumulate, p_drop, seed, keep_a, keep_b):
-    lib = _native.lib()
     T, H = E2d.shape[0], Wa.shape[0]
-    dev = E2d.device
-    dWa, dWb = torch.empty_like(Wa), torch.empty_like(Wb)
-    dba = torch.empty(H, HID, device=dev, dtype=torch.float32)
-    dbb, dwc = torch.empty_like(dba), torch.empty_like(dba)
-    dbc = torch.empty(H, device=dev, dtype=torch.float32)
+    grads = _gate_grads(Wa, Wb)
     sfx = _sfx(E2d)
-    ws = _ws(getattr(lib, "mdl_abmil_gate_bwd%s_ws_bytes" % sfx)(T, H), dev)
+    ws = _ws_for("mdl_abmil_gate_bwd%s_ws_bytes" % sfx, E2d.device, T, H)
     with _timed("gate_bwd", ("flop", 4.0 * T * H * HID * 2 * HID)):
-        rc = getattr(lib, "mdl_abmil_gate_bwd" + sfx)(_ptr(E2d), E2d.stride(0), _ptr(Wa), _ptr(Wb), _ptr(wc), _ptr(act_a), _ptr(act_b),
-                                    _ptr(d_scores), _ptr(dE), int(accumulate), _ptr(dWa), _ptr(dWb), _ptr(dba), _ptr(dbb),
-                                    _ptr(dwc), _ptr(dbc), T, H, float(p_drop), int(seed), _ptr(keep_a), _ptr(keep_b),
-                                    _ptr(ws), _stream())
-    _native.check(rc, "mdl_abmil_gate_bwd")
-    return dWa, dWb, dba, dbb, dwc, dbc
+        _call("mdl_abmil_gate_bwd" + sfx, E2d, E2d.stride(0), Wa, Wb, wc, act_a, act_b, d_scores, dE, int(accumulate), *grads, T, H,
+              float(p_drop), int(seed), keep_a, keep_b, ws, _stream())
+    return grads
 
 
 def attnpool_bwd_raw(E2d, Wa, Wb, wc, act_a, act_b, d_scores, dE, p_drop, seed, keep_a, keep_b, scores, stat_m, stat_l, d_pooled,
                      row_bag, N, accumulate=0):
     """Gate backward whose dX epilogue also adds the pooling term (mdl_abmil_attnpool_bwd): dE is written once; with
     `accumulate` the epilogue adds to what dE already holds (another consumer's gradient of E)."""
-    lib = _native.lib()
     T, H = E2d.shape[0], Wa.shape[0]
-    dev = E2d.device
-    dWa, dWb = torch.empty_like(Wa), torch.empty_like(Wb)
-    dba = torch.empty(H, HID, device=dev, dtype=torch.float32)
-    dbb, dwc = torch.empty_like(dba), torch.empty_like(dba)
-    dbc = torch.empty(H, device=dev, dtype=torch.float32)
+    grads = _gate_grads(Wa, Wb)
     sfx = _sfx(E2d)
-    ws = _ws(getattr(lib, "mdl_abmil_gate_bwd%s_ws_bytes" % sfx)(T, H), dev)
-    args = (_ptr(E2d), E2d.stride(0), _ptr(Wa), _ptr(Wb), _ptr(wc), _ptr(act_a), _ptr(act_b), _ptr(d_scores), _ptr(dE), int(accumulate), _ptr(dWa),
-            _ptr(dWb), _ptr(dba), _ptr(dbb), _ptr(dwc), _ptr(dbc), T, H, float(p_drop), int(seed), _ptr(keep_a), _ptr(keep_b),
-            _ptr(scores), _ptr(stat_m), _ptr(stat_l), _ptr(d_pooled), _ptr(row_bag), int(N), _ptr(ws), _stream())
+    ws = _ws_for("mdl_abmil_gate_bwd%s_ws_bytes" % sfx, E2d.device, T, H)
+    args = (E2d, E2d.stride(0), Wa, Wb, wc, act_a, act_b, d_scores, dE, int(accumulate), *grads, T, H, float(p_drop), int(seed),
+            keep_a, keep_b, scores, stat_m, stat_l, d_pooled, row_bag, int(N), ws, _stream())
     if TIMER is not None and TIMER.wants("gate_bwd_dz"):
         # profiling: the HBM-bound dz pass and the MFMA-bound contractions as two calls on the same workspace, timed separately
         # ("gate_bwd" stays their sum in KernelTimer.report)
-        fn = getattr(lib, "mdl_abmil_attnpool_bwd_phases" + sfx)
         with _timed("gate_bwd_dz", ("byte", float(T) * H * 4 * HID * E2d.element_size())):   # reads a, b; writes dza | dzb
-            rc = fn(*args, 1)
-        _native.check(rc, "mdl_abmil_attnpool_bwd_phases")
+            _call("mdl_abmil_attnpool_bwd_phases" + sfx, *args, 1)
         with _timed("gate_bwd_gemm", ("flop", 4.0 * T * H * HID * 2 * HID)):
-            rc = fn(*args, 2)
-        _native.check(rc, "mdl_abmil_attnpool_bwd_phases")
+            _call("mdl_abmil_attnpool_bwd_phases" + sfx, *args, 2)
     else:
-        rc = getattr(lib, "mdl_abmil_attnpool_bwd" + sfx)(*args)
-        _native.check(rc, "mdl_abmil_attnpool_bwd")
-    return dWa, dWb, dba, dbb, dwc, dbc
+        _call("mdl_abmil_attnpool_bwd" + sfx, *args)
+    return grads
 
 
 def pool_fwd_raw(E2d, scores, n_bags, N, cu_seqlens, max_len):
-    lib = _native.lib()
     H = scores.shape[-1]
-    dev = E2d.device
-    pooled = torch.empty(n_bags, H * HID, device=dev, dtype=torch.float32)
-    stat_m = torch.empty(n_bags, H, device=dev, dtype=torch.float32)
-    stat_l = torch.empty(n_bags, H, device=dev, dtype=torch.float32)
-    ws = _ws(lib.mdl_abmil_pool_ws_bytes(n_bags, max_len, H), dev)
+    out = _pool_outputs(n_bags, H, E2d.device)
+    ws = _ws_for("mdl_abmil_pool_ws_bytes", E2d.device, n_bags, max_len, H)
     T = E2d.shape[0]
     with _timed("pool_fwd", ("byte", float(T) * H * (HID * E2d.element_size() + 4) + n_bags * H * HID * 4.0)):
-        rc = getattr(lib, "mdl_abmil_pool_fwd" + _sfx(E2d))(_ptr(E2d), E2d.stride(0), _ptr(scores), _ptr(pooled), _ptr(stat_m), _ptr(stat_l), n_bags,
-                                    N, _ptr(cu_seqlens), max_len, H, _ptr(ws), _stream())
-    _native.check(rc, "mdl_abmil_pool_fwd")
-    return pooled, stat_m, stat_l
+        _call("mdl_abmil_pool_fwd" + _sfx(E2d), E2d, E2d.stride(0), scores, *out, n_bags, N, cu_seqlens, max_len, H, ws, _stream())
+    return out
 
 
 def pool_bwd_raw(E2d, scores, pooled, stat_m, stat_l, d_pooled, dE, accumulate, d_scores, accumulate_scores, n_bags, N,
                  cu_seqlens, max_len):
-    lib = _native.lib()
     H = scores.shape[-1]
     T = E2d.shape[0]
     nb = float(T) * H * (HID * E2d.element_size() * (1 if dE is None else 2) + 8) + n_bags * H * HID * 4.0
     with _timed("pool_bwd", ("byte", nb)):
-        rc = getattr(lib, "mdl_abmil_pool_bwd" + _sfx(E2d))(_ptr(E2d), E2d.stride(0), _ptr(scores), _ptr(pooled), _ptr(stat_m), _ptr(stat_l),
-                                    _ptr(d_pooled), _ptr(dE), int(accumulate), _ptr(d_scores), int(accumulate_scores), n_bags, N,
-                                    _ptr(cu_seqlens), max_len, H, _stream())
-    _native.check(rc, "mdl_abmil_pool_bwd")
+        _call("mdl_abmil_pool_bwd" + _sfx(E2d), E2d, E2d.stride(0), scores, pooled, stat_m, stat_l, d_pooled, dE, int(accumulate), d_scores,
+              int(accumulate_scores), n_bags, N, cu_seqlens, max_len, H, _stream())
 
 
 def pool_fwd_img_raw(Ei, scores, n_bags, N, cu_seqlens, max_len):
     """pool_fwd_raw on the split image of E (the split GEMM mode stores E as an image only)."""
-    lib = _native.lib()
     H = scores.shape[-1]
-    dev = scores.device
-    pooled = torch.empty(n_bags, H * HID, device=dev, dtype=torch.float32)
-    stat_m = torch.empty(n_bags, H, device=dev, dtype=torch.float32)
-    stat_l = torch.empty(n_bags, H, device=dev, dtype=torch.float32)
-    ws = _ws(lib.mdl_abmil_pool_ws_bytes(n_bags, max_len, H), dev)
+    out = _pool_outputs(n_bags, H, scores.device)
+    ws = _ws_for("mdl_abmil_pool_ws_bytes", scores.device, n_bags, max_len, H)
     with _timed("pool_fwd", ("byte", float(Ei.rows) * H * (HID * 4 + 4) + n_bags * H * HID * 4.0)):
-        rc = lib.mdl_abmil_pool_fwd_img(_ptr(Ei.data), Ei.K * 4, _ptr(Ei.scale), _ptr(scores), _ptr(pooled), _ptr(stat_m), _ptr(stat_l),
-                                        n_bags, N, _ptr(cu_seqlens), max_len, H, _ptr(ws), _stream())
-    _native.check(rc, "mdl_abmil_pool_fwd_img")
-    return pooled, stat_m, stat_l
+        _call("mdl_abmil_pool_fwd_img", Ei.data, Ei.K * 4, Ei.scale, scores, *out, n_bags, N, cu_seqlens, max_len, H, ws, _stream())
+    return out
 
 
 def pool_dscores_img_raw(Ei, scores, pooled, stat_m, stat_l, d_pooled, d_scores, accumulate_scores, n_bags, N, cu_seqlens, max_len):
     """The score gradients of the pooling from the split image of E (pool_bwd_raw with dE = None)."""
-    lib = _native.lib()
     H = scores.shape[-1]
     with _timed("pool_bwd", ("byte", float(Ei.rows) * H * (HID * 4 + 8) + n_bags * H * HID * 4.0)):
-        rc = lib.mdl_abmil_pool_dscores_img(_ptr(Ei.data), Ei.K * 4, _ptr(Ei.scale), _ptr(scores), _ptr(pooled), _ptr(stat_m), _ptr(stat_l),
-                                            _ptr(d_pooled), _ptr(d_scores), int(accumulate_scores), n_bags, N, _ptr(cu_seqlens), max_len,
-                                            H, _stream())
-    _native.check(rc, "mdl_abmil_pool_dscores_img")
+        _call("mdl_abmil_pool_dscores_img", Ei.data, Ei.K * 4, Ei.scale, scores, pooled, stat_m, stat_l, d_pooled, d_scores,
+              int(accumulate_scores), n_bags, N, cu_seqlens, max_len, H, _stream())
 
 
 def pool_view_fwd_raw(E2d, scores, n_bags, N, token_idx):
-    lib = _native.lib()
     H = scores.shape[-1]
-    dev = E2d.device
     n_idx = token_idx.numel()
-    pooled = torch.empty(n_bags, H * HID, device=dev, dtype=torch.float32)
-    stat_m = torch.empty(n_bags, H, device=dev, dtype=torch.float32)
-    stat_l = torch.empty(n_bags, H, device=dev, dtype=torch.float32)
-    ws = _ws(lib.mdl_abmil_pool_ws_bytes(n_bags, n_idx, H), dev)
+    out = _pool_outputs(n_bags, H, E2d.device)
+    ws = _ws_for("mdl_abmil_pool_ws_bytes", E2d.device, n_bags, n_idx, H)
     with _timed("pool_view_fwd"):
-        rc = getattr(lib, "mdl_abmil_pool_view_fwd" + _sfx(E2d))(_ptr(E2d), E2d.stride(0), _ptr(scores), _ptr(pooled), _ptr(stat_m),
-                                                                _ptr(stat_l), n_bags, N, _ptr(token_idx), n_idx, H, _ptr(ws), _stream())
-    _native.check(rc, "mdl_abmil_pool_view_fwd")
-    return pooled, stat_m, stat_l
+        _call("mdl_abmil_pool_view_fwd" + _sfx(E2d), E2d, E2d.stride(0), scores, *out, n_bags, N, token_idx, n_idx, H, ws, _stream())
+    return out
 
 
 def pool_view_bwd_raw(E2d, scores, pooled, stat_m, stat_l, d_pooled, dE, d_scores, n_bags, N, token_idx):
     """Accumulates the view's contribution into dE and / or d_scores (either may be None)."""
-    lib = _native.lib()
     H = scores.shape[-1]
     with _timed("pool_view_bwd"):
-        rc = getattr(lib, "mdl_abmil_pool_view_bwd" + _sfx(E2d))(_ptr(E2d), E2d.stride(0), _ptr(scores), _ptr(pooled), _ptr(stat_m),
-                                                                _ptr(stat_l), _ptr(d_pooled), _ptr(dE), _ptr(d_scores), n_bags, N,
-                                                                _ptr(token_idx), token_idx.numel(), H, _stream())
-    _native.check(rc, "mdl_abmil_pool_view_bwd")
+        _call("mdl_abmil_pool_view_bwd" + _sfx(E2d), E2d, E2d.stride(0), scores, pooled, stat_m, stat_l, d_pooled, dE, d_scores, n_bags, N,
+              token_idx, token_idx.numel(), H, _stream())
 
 
 def pool_rview_fwd_raw(E2d, scores, n_bags, perm, vcu, max_view_len):
     """The two half-bag views of every packed bag (mdl_abmil_pool_rview_fwd): -> (pooled [n_bags, 2, H*512], stat_m, stat_l [2*n_bags, H])."""
-    lib = _native.lib()
     H = scores.shape[-1]
-    dev = E2d.device
-    pooled = torch.empty(n_bags, 2, H * HID, device=dev, dtype=torch.float32)
-    stat_m = torch.empty(2 * n_bags, H, device=dev, dtype=torch.float32)
-    stat_l = torch.empty(2 * n_bags, H, device=dev, dtype=torch.float32)
-    ws = _ws(lib.mdl_abmil_pool_ws_bytes(2 * n_bags, max_view_len, H), dev)
+    out = _pool_outputs(2 * n_bags, H, E2d.device, pooled_shape=(n_bags, 2, H * HID))
+    ws = _ws_for("mdl_abmil_pool_ws_bytes", E2d.device, 2 * n_bags, max_view_len, H)
     with _timed("pool_view_fwd"):
-        rc = getattr(lib, "mdl_abmil_pool_rview_fwd" + _sfx(E2d))(_ptr(E2d), E2d.stride(0), _ptr(scores), _ptr(pooled), _ptr(stat_m),
-                                                                 _ptr(stat_l), n_bags, _ptr(perm), _ptr(vcu), int(max_view_len), H,
-                                                                 _ptr(ws), _stream())
-    _native.check(rc, "mdl_abmil_pool_rview_fwd")
-    return pooled, stat_m, stat_l
+        _call("mdl_abmil_pool_rview_fwd" + _sfx(E2d), E2d, E2d.stride(0), scores, *out, n_bags, perm, vcu, int(max_view_len), H, ws,
+              _stream())
+    return out
 
 
 def pool_rview_bwd_raw(E2d, scores, pooled, stat_m, stat_l, d_pooled, dE, d_scores, n_bags, perm, vcu, max_view_len):
     """Accumulates the ragged views' contribution (d_pooled [n_bags, 2, H*512]) into dE and / or d_scores (either may be None)."""
-    lib = _native.lib()
     H = scores.shape[-1]
     with _timed("pool_view_bwd"):
-        rc = getattr(lib, "mdl_abmil_pool_rview_bwd" + _sfx(E2d))(_ptr(E2d), E2d.stride(0), _ptr(scores), _ptr(pooled), _ptr(stat_m),
-                                                                 _ptr(stat_l), _ptr(d_pooled), _ptr(dE), _ptr(d_scores), n_bags,
-                                                                 _ptr(perm), _ptr(vcu), int(max_view_len), H, _stream())
-    _native.check(rc, "mdl_abmil_pool_rview_bwd")
+        _call("mdl_abmil_pool_rview_bwd" + _sfx(E2d), E2d, E2d.stride(0), scores, pooled, stat_m, stat_l, d_pooled, dE, d_scores, n_bags,
+              perm, vcu, int(max_view_len), H, _stream())
 
 
 def _check_rview(E2d, cu_seqlens, rviews):
@@ -458,13 +442,11 @@ class SplitImage:
 
 def split_image(x2d, pad_rows=0) -> SplitImage:
     _require(x2d, "x")
-    lib = _native.lib()
     rows, K = x2d.shape
     data = torch.empty(rows + pad_rows, K, device=x2d.device, dtype=torch.float32)
     scale = torch.empty(2, device=x2d.device, dtype=torch.float32)
     with _timed("split_image", ("byte", 12.0 * rows * K)):   # absmax read + convert read + write
-        rc = lib.mdl_split_image(_ptr(x2d), x2d.stride(0), rows, K, _ptr(data), K * 4, pad_rows, _ptr(scale), _stream())
-    _native.check(rc, "mdl_split_image")
+        _call("mdl_split_image", x2d, x2d.stride(0), rows, K, data, K * 4, pad_rows, scale, _stream())
     return SplitImage(data, scale, rows, K)
 
 
@@ -472,15 +454,13 @@ def split_image_rows(x2d, pad_rows=0):
     """Row-scaled image of x2d (mdl_split_image_rows): -> (SplitImage with common scale 1, row_inv [rows] = 1 / the row scales).  For the
     tensor whose rows the caller controls (the patch features): one outlier patch does not cost the other patches their low bits."""
     _require(x2d, "x")
-    lib = _native.lib()
     rows, K = x2d.shape
     data = torch.empty(rows + pad_rows, K, device=x2d.device, dtype=torch.float32)
     row_inv = torch.empty(rows, device=x2d.device, dtype=torch.float32)
     # scale = NULL: nothing consumes the tensor-wide maximum of a row-scaled image, and collecting it is a memset, a scale launch and one
     # atomic per wave on a single address (75 us of a 95-us launch at 30,000 rows: every wave arrives at once)
     with _timed("split_image", ("byte", 8.0 * rows * K)):   # one HBM read + write
-        rc = lib.mdl_split_image_rows(_ptr(x2d), x2d.stride(0), rows, K, _ptr(data), K * 4, pad_rows, _ptr(row_inv), None, _stream())
-    _native.check(rc, "mdl_split_image_rows")
+        _call("mdl_split_image_rows", x2d, x2d.stride(0), rows, K, data, K * 4, pad_rows, row_inv, None, _stream())
     return SplitImage(data, _unit_scale(x2d.device), rows, K), row_inv
 
 
@@ -500,23 +480,20 @@ def weight_image(W) -> SplitImage:
     scale and convert launches of split_image, every forward and backward of every Linear.  As the B operand of split_gemm_nt its row
     factors become per-output-column factors of the product (b_col_mul)."""
     _require(W, "weight")
-    lib = _native.lib()
     rows, K = W.shape
     data = torch.empty(rows, K, device=W.device, dtype=torch.float32)
     row_inv = torch.empty(rows, device=W.device, dtype=torch.float32)
-    rc = lib.mdl_split_image_rows(_ptr(W), W.stride(0), rows, K, _ptr(data), K * 4, 0, _ptr(row_inv), None, _stream())
-    _native.check(rc, "mdl_split_image_rows")
+    _call("mdl_split_image_rows", W, W.stride(0), rows, K, data, K * 4, 0, row_inv, None, _stream())
     return SplitImage(data, _unit_scale(W.device), rows, K, row_inv)
 
 
 def split_tile_absmax(x2d, chunks=False):
     """max |x| of every block of 256 rows (the row gate of split_gemm_nt); chunks=True: also of every 32 rows (split_gemm_tn's
     b_chunk_max) -> (gate, chunk_max)."""
-    lib = _native.lib()
     rows, K = x2d.shape
     gate = torch.empty((rows + 255) // 256, device=x2d.device, dtype=torch.float32)
     cm = torch.empty((rows + 31) // 32, device=x2d.device, dtype=torch.float32) if chunks else None
-    _native.check(lib.mdl_split_tile_absmax(_ptr(x2d), x2d.stride(0), rows, K, _ptr(gate), _ptr(cm), _stream()), "mdl_split_tile_absmax")
+    _call("mdl_split_tile_absmax", x2d, x2d.stride(0), rows, K, gate, cm, _stream())
     return (gate, cm) if chunks else gate
 
 
@@ -525,7 +502,6 @@ def split_gemm_nt(A: SplitImage, B: SplitImage, bias=None, out=None, accumulate=
     """C [A.rows, B.rows] (+)= A B^T (+ bias) on two images with the same K.  row_gate (accumulate mode only): per-256-row maxima of
     the tensor A is the image of; output tiles of all-zero A rows are skipped.  a_row_mul [A.rows]: per-row factor applied to the
     product (row_inv of a row-scaled A image).  terms=2: B enters with its hi plane only (GRAD_TERMS)."""
-    lib = _native.lib()
     M, N, K = A.rows, B.rows, A.K
     if B.K != K:
         raise ValueError("split_gemm_nt: contraction lengths differ")
@@ -533,17 +509,14 @@ def split_gemm_nt(A: SplitImage, B: SplitImage, bias=None, out=None, accumulate=
         a_row_mul = A.row_inv
     C = out if out is not None else torch.empty(M, N, device=A.data.device, dtype=torch.float32)
     with _timed(name, ("flop", 2.0 * M * N * K)):
-        rc = lib.mdl_split_gemm_nt(_ptr(A.data), K * 4, _ptr(A.scale), _ptr(B.data), K * 4, _ptr(B.scale), _ptr(C), C.stride(0), M, N, K,
-                                   _ptr(bias), int(accumulate), _ptr(absmax_out), _ptr(row_gate), _ptr(a_row_mul), _ptr(B.row_inv), int(terms),
-                                   _stream())
-    _native.check(rc, "mdl_split_gemm_nt")
+        _call("mdl_split_gemm_nt", A.data, K * 4, A.scale, B.data, K * 4, B.scale, C, C.stride(0), M, N, K, bias, int(accumulate),
+              absmax_out, row_gate, a_row_mul, B.row_inv, int(terms), _stream())
     return C
 
 
 def split_gemm_nt_group_bias(A: SplitImage, B: SplitImage, group_bias, row_group, bias=None, a_row_mul=None, name="split_nt"):
     """split_gemm_nt with a bias row per GROUP of output rows: C[m] = A[m] B^T (+ bias) + group_bias[row_group[m]] (mdl_split_gemm_nt_group_bias;
     group_bias [G, B.rows] fp32, row_group int32 [A.rows])."""
-    lib = _native.lib()
     M, N, K = A.rows, B.rows, A.K
     if B.K != K:
         raise ValueError("split_gemm_nt_group_bias: contraction lengths differ")
@@ -555,27 +528,23 @@ def split_gemm_nt_group_bias(A: SplitImage, B: SplitImage, group_bias, row_group
         a_row_mul = A.row_inv
     C = torch.empty(M, N, device=A.data.device, dtype=torch.float32)
     with _timed(name, ("flop", 2.0 * M * N * K)):
-        rc = lib.mdl_split_gemm_nt_group_bias(_ptr(A.data), K * 4, _ptr(A.scale), _ptr(B.data), K * 4, _ptr(B.scale), _ptr(C), C.stride(0), M, N, K,
-                                              _ptr(bias), _ptr(a_row_mul), _ptr(B.row_inv), _ptr(group_bias), _ptr(row_group), 3, _stream())
-    _native.check(rc, "mdl_split_gemm_nt_group_bias")
+        _call("mdl_split_gemm_nt_group_bias", A.data, K * 4, A.scale, B.data, K * 4, B.scale, C, C.stride(0), M, N, K, bias, a_row_mul,
+              B.row_inv, group_bias, row_group, 3, _stream())
     return C
 
 
 def split_gemm_tn(A: SplitImage, B: SplitImage, name="split_tn", b_chunk_max=None, terms=3):
     """out [B.K, A.K] = B^T A summed over the rows (tokens) of the two images; B must carry >= 32 zero pad rows.  b_chunk_max: the
     per-32-row maxima (split_tile_absmax(x, chunks=True)) of the tensor B is the image of -- its all-zero chunks are skipped."""
-    lib = _native.lib()
     T, Mi, N = A.rows, A.K, B.K
     if B.row_inv is not None:
         raise ValueError("split_gemm_tn: a row-scaled image cannot be the B operand of a contraction over its rows")
     if B.rows != T or B.data.shape[0] < T + 32:
         raise ValueError("split_gemm_tn: images need the same number of rows and B 32 zero pad rows")
     out = torch.empty(N, Mi, device=A.data.device, dtype=torch.float32)
-    ws = _ws(lib.mdl_split_gemm_tn_ws_bytes(T, Mi, N), A.data.device)
+    ws = _ws_for("mdl_split_gemm_tn_ws_bytes", A.data.device, T, Mi, N)
     with _timed(name, ("flop", 2.0 * T * Mi * N)):
-        rc = lib.mdl_split_gemm_tn(_ptr(A.data), Mi * 4, _ptr(A.scale), Mi, _ptr(B.data), N * 4, _ptr(B.scale), N, _ptr(out), T, _ptr(b_chunk_max),
-                                   _ptr(ws), int(terms), _stream())
-    _native.check(rc, "mdl_split_gemm_tn")
+        _call("mdl_split_gemm_tn", A.data, Mi * 4, A.scale, Mi, B.data, N * 4, B.scale, N, out, T, b_chunk_max, ws, int(terms), _stream())
     return out
 
 
@@ -690,7 +659,6 @@ class PreAttnBlockFn(torch.autograd.Function):
             _require(t_, n_)
         if lin_bias is not None:
             _require(lin_bias, "bias")
-        lib = _native.lib()
         T, K = x.shape
         N = W.shape[0]
         dev = x.device
@@ -718,12 +686,8 @@ class PreAttnBlockFn(torch.autograd.Function):
         needs_bwd = any(ctx.needs_input_grad)
         rstd_max = torch.empty(1, device=dev, dtype=torch.float32) if needs_bwd else None
         with _timed("ln_gelu_drop_fwd", ("byte", (3.0 if want_fp32 else 2.0) * T * N * 4)):
-            rc = lib.mdl_ln_gelu_drop_fwd_split(_ptr(y), _ptr(lin_bias), _ptr(gamma), _ptr(beta), _ptr(out), _ptr(img), _ptr(scale),
-                                                _ptr(mean), _ptr(rstd), T, N, float(eps), float(p_drop), int(seed), _ptr(keep),
-                                                _ptr(row_inv), _ptr(rstd_max), _stream())
-        if rc == -3:
-            raise NotImplementedError("fused LayerNorm-GELU-Dropout supports widths 256/512/1024/2048/4096 (got %d)" % N)
-        _native.check(rc, "mdl_ln_gelu_drop_fwd_split")
+            _call("mdl_ln_gelu_drop_fwd_split", y, lin_bias, gamma, beta, out, img, scale, mean, rstd, T, N, float(eps), float(p_drop),
+                  int(seed), keep, row_inv, rstd_max, _stream(), unsupported=(_LN_WIDTHS, N))
         ctx.save_for_backward(xi.data, xi.scale, W, y, gamma, beta, mean, rstd, lin_bias if lin_bias is not None else torch.empty(0),
                               row_inv if row_inv is not None else torch.empty(0), rstd_max if rstd_max is not None else torch.empty(0))
         ctx.cfg = (float(p_drop), int(seed), keep, lin_bias is not None, bool(want_fp32), T, K, N, x_scale is not None)
@@ -750,7 +714,6 @@ class PreAttnBlockFn(torch.autograd.Function):
         if dy is None:
             dy = torch.zeros(T, N, device=y.device, dtype=torch.float32)
         dy = dy.float().contiguous().view(T, N)
-        lib = _native.lib()
         dev = y.device
         dximg = torch.empty(T + 32, N, device=dev, dtype=torch.float32)
         dxscale = torch.empty(2, device=dev, dtype=torch.float32)
@@ -761,20 +724,15 @@ class PreAttnBlockFn(torch.autograd.Function):
         if ctx.groups is not None:
             cu_groups, G = ctx.groups
             d_gbias = torch.empty(G, N, device=dev, dtype=torch.float32)
-            ws = _ws(lib.mdl_ln_gelu_drop_bwd_groups_ws_bytes(T, N, G), dev)
+            ws = _ws_for("mdl_ln_gelu_drop_bwd_groups_ws_bytes", dev, T, N, G)
             with _timed("ln_gelu_drop_bwd", ("byte", (3.0 if amax is not None else 4.0) * T * N * 4)):
-                rc = lib.mdl_ln_gelu_drop_bwd_split_groups(_ptr(y), _ptr(lin_bias), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(rstd), _ptr(dy),
-                                                           _ptr(amax), _ptr(dximg), _ptr(dxscale), _ptr(dg), _ptr(db), _ptr(dbias), T, N, p_drop, seed,
-                                                           _ptr(keep), _ptr(row_inv), _ptr(rstd_max), _ptr(cu_groups), G, _ptr(d_gbias), _ptr(ws),
-                                                           _stream())
-            _native.check(rc, "mdl_ln_gelu_drop_bwd_split_groups")
+                _call("mdl_ln_gelu_drop_bwd_split_groups", y, lin_bias, gamma, beta, mean, rstd, dy, amax, dximg, dxscale, dg, db, dbias, T, N,
+                      p_drop, seed, keep, row_inv, rstd_max, cu_groups, G, d_gbias, ws, _stream())
         else:
-            ws = _ws(lib.mdl_ln_gelu_drop_bwd_ws_bytes(T, N), dev)
+            ws = _ws_for("mdl_ln_gelu_drop_bwd_ws_bytes", dev, T, N)
             with _timed("ln_gelu_drop_bwd", ("byte", (3.0 if amax is not None else 4.0) * T * N * 4)):
-                rc = lib.mdl_ln_gelu_drop_bwd_split(_ptr(y), _ptr(lin_bias), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(rstd), _ptr(dy), _ptr(amax),
-                                                    _ptr(dximg), _ptr(dxscale), _ptr(dg), _ptr(db), _ptr(dbias), T, N, p_drop, seed, _ptr(keep),
-                                                    _ptr(row_inv), _ptr(rstd_max), _ptr(ws), _stream())
-            _native.check(rc, "mdl_ln_gelu_drop_bwd_split")
+                _call("mdl_ln_gelu_drop_bwd_split", y, lin_bias, gamma, beta, mean, rstd, dy, amax, dximg, dxscale, dg, db, dbias, T, N,
+                      p_drop, seed, keep, row_inv, rstd_max, ws, _stream())
         dyi = SplitImage(dximg, dxscale, T, N)
         dx = None
         if ctx.needs_input_grad[0]:
@@ -788,10 +746,8 @@ class PreAttnBlockFn(torch.autograd.Function):
                 dxscale2 = torch.empty(2, device=dev, dtype=torch.float32)
                 dg2, db2 = torch.empty_like(gamma), torch.empty_like(beta)
                 with _timed("ln_gelu_drop_bwd", ("byte", 3.0 * T * N * 4)):
-                    rc = lib.mdl_ln_gelu_drop_bwd_split(_ptr(y), _ptr(lin_bias), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(rstd), _ptr(dy), _ptr(amax),
-                                                        _ptr(dximg2), _ptr(dxscale2), _ptr(dg2), _ptr(db2), None, T, N, p_drop, seed, _ptr(keep),
-                                                        None, None, _ptr(ws), _stream())   # (no row factors: its own pass over rstd)
-                _native.check(rc, "mdl_ln_gelu_drop_bwd_split")
+                    _call("mdl_ln_gelu_drop_bwd_split", y, lin_bias, gamma, beta, mean, rstd, dy, amax, dximg2, dxscale2, dg2, db2, None, T, N,
+                          p_drop, seed, keep, None, None, ws, _stream())   # (no row factors: its own pass over rstd)
                 dxi = SplitImage(dximg2, dxscale2, T, N)
             dx = split_gemm_nt(dxi, weight_image(W.t().contiguous()), absmax_out=am, name="linear_bwd", terms=GRAD_TERMS)
             if x_is_image:       # the consumer is the previous block's LayerNorm backward (this node's input was its image)
@@ -814,31 +770,26 @@ def preattn_split_supported(x2d, K) -> bool:
 
 def linear_fwd_raw(x2d, W, bias):
     """Y = X W^T (+ bias) through mdl_linear_fwd / mdl_linear_fwd_bf16 (by the storage type of x2d)."""
-    lib = _native.lib()
     T, K = x2d.shape
     N = W.shape[0]
     sfx = _sfx(x2d)
     y = torch.empty(T, N, device=x2d.device, dtype=x2d.dtype)
-    ws = _ws(getattr(lib, "mdl_linear_fwd%s_ws_bytes" % sfx)(T, N, K), x2d.device)
+    ws = _ws_for("mdl_linear_fwd%s_ws_bytes" % sfx, x2d.device, T, N, K)
     with _timed("linear_fwd", ("flop", 2.0 * T * N * K)):
-        rc = getattr(lib, "mdl_linear_fwd" + sfx)(_ptr(x2d), x2d.stride(0), _ptr(W), _ptr(bias), _ptr(y), N, T, N, K, _ptr(ws), _stream())
-    _native.check(rc, "mdl_linear_fwd" + sfx)
+        _call("mdl_linear_fwd" + sfx, x2d, x2d.stride(0), W, bias, y, N, T, N, K, ws, _stream())
     return y
 
 
 def linear_bwd_raw(x2d, W, dy, dx, want_dbias):
     """(dW, dbias) of the Linear; dX is written into `dx` ([T,K], may be None)."""
-    lib = _native.lib()
     T, K = x2d.shape
     N = W.shape[0]
     sfx = _sfx(x2d)
     dW = torch.empty_like(W)
     db = torch.empty(N, device=x2d.device, dtype=torch.float32) if want_dbias else None
-    ws = _ws(getattr(lib, "mdl_linear_bwd%s_ws_bytes" % sfx)(T, N, K), x2d.device)
+    ws = _ws_for("mdl_linear_bwd%s_ws_bytes" % sfx, x2d.device, T, N, K)
     with _timed("linear_bwd", ("flop", 2.0 * T * N * K * (2 if dx is not None else 1))):
-        rc = getattr(lib, "mdl_linear_bwd" + sfx)(_ptr(x2d), x2d.stride(0), _ptr(W), _ptr(dy), N, _ptr(dx), K, _ptr(dW), _ptr(db), T, N, K,
-                                                  _ptr(ws), _stream())
-    _native.check(rc, "mdl_linear_bwd" + sfx)
+        _call("mdl_linear_bwd" + sfx, x2d, x2d.stride(0), W, dy, N, dx, K, dW, db, T, N, K, ws, _stream())
     return dW, db
 
 
@@ -936,16 +887,13 @@ class WeightedPoolFn(torch.autograd.Function):
         _require(weights, "weights")
         n_bags, N, max_len, E2d = _bag_geometry(E, cu_seqlens, max_len)
         w2d = weights.reshape(E2d.shape[0], -1)
-        lib = _native.lib()
         H = w2d.shape[-1]
         pooled = torch.empty(n_bags, H * HID, device=E2d.device, dtype=torch.float32)
         scratch = torch.empty(2, n_bags, H, device=E2d.device, dtype=torch.float32)
-        ws = _ws(lib.mdl_abmil_pool_ws_bytes(n_bags, max_len, H), E2d.device)
+        ws = _ws_for("mdl_abmil_pool_ws_bytes", E2d.device, n_bags, max_len, H)
         with _timed("pool_fwd"):
-            rc = getattr(lib, "mdl_abmil_wpool_fwd" + _sfx(E2d))(_ptr(E2d), E2d.stride(0), _ptr(w2d), _ptr(pooled), _ptr(scratch[0]),
-                                                                 _ptr(scratch[1]), n_bags, N, _ptr(cu_seqlens), max_len, H, _ptr(ws),
-                                                                 _stream())
-        _native.check(rc, "mdl_abmil_wpool_fwd")
+            _call("mdl_abmil_wpool_fwd" + _sfx(E2d), E2d, E2d.stride(0), w2d, pooled, scratch[0], scratch[1], n_bags, N, cu_seqlens, max_len,
+                  H, ws, _stream())
         ctx.save_for_backward(E2d, w2d, cu_seqlens if cu_seqlens is not None else torch.empty(0))
         ctx.geom = (n_bags, N, max_len, cu_seqlens is not None, E.shape, weights.shape)
         return pooled
@@ -957,12 +905,9 @@ class WeightedPoolFn(torch.autograd.Function):
         cu = cu if ragged else None
         dE = torch.empty_like(E2d)
         dw = torch.empty_like(w2d)
-        lib = _native.lib()
         with _timed("pool_bwd"):
-            rc = getattr(lib, "mdl_abmil_wpool_bwd" + _sfx(E2d))(_ptr(E2d), E2d.stride(0), _ptr(w2d), _ptr(d_pooled.float().contiguous()),
-                                                                 _ptr(dE), 0, _ptr(dw), n_bags, N, _ptr(cu), max_len, w2d.shape[-1],
-                                                                 _stream())
-        _native.check(rc, "mdl_abmil_wpool_bwd")
+            _call("mdl_abmil_wpool_bwd" + _sfx(E2d), E2d, E2d.stride(0), w2d, d_pooled.float().contiguous(), dE, 0, dw, n_bags, N, cu, max_len,
+                  w2d.shape[-1], _stream())
         return dE.view(e_shape), dw.view(w_shape), None, None
 
 
@@ -1196,19 +1141,14 @@ class LNGeluDropFn(torch.autograd.Function):
         _require(beta, "beta")
         if bias is not None:
             _require(bias, "bias")
-        lib = _native.lib()
         W = x.shape[-1]
         rows = x.numel() // W
         y = torch.empty_like(x)
         mean = torch.empty(rows, device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
         with _timed("ln_gelu_drop_fwd", ("byte", 2.0 * x.numel() * x.element_size())):
-            rc = getattr(lib, "mdl_ln_gelu_drop_fwd" + _sfx(x))(_ptr(x), _ptr(bias), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(mean),
-                                                              _ptr(rstd), rows, W, float(eps), float(p_drop), int(seed),
-                                                              _ptr(keep), _stream())
-        if rc == -3:
-            raise NotImplementedError("fused LayerNorm-GELU-Dropout supports widths 256/512/1024/2048/4096 (got %d)" % W)
-        _native.check(rc, "mdl_ln_gelu_drop_fwd")
+            _call("mdl_ln_gelu_drop_fwd" + _sfx(x), x, bias, gamma, beta, y, mean, rstd, rows, W, float(eps), float(p_drop), int(seed), keep,
+                  _stream(), unsupported=(_LN_WIDTHS, W))
         ctx.save_for_backward(x, gamma, beta, mean, rstd, bias if bias is not None else torch.empty(0))
         ctx.cfg = (float(p_drop), int(seed), keep, bias is not None)
         return y
@@ -1218,19 +1158,16 @@ class LNGeluDropFn(torch.autograd.Function):
         x, gamma, beta, mean, rstd, bias = ctx.saved_tensors
         p_drop, seed, keep, has_bias = ctx.cfg
         bias = bias if has_bias else None
-        lib = _native.lib()
         W = x.shape[-1]
         rows = x.numel() // W
         dy = dy.to(x.dtype).contiguous()
         dx = torch.empty_like(x)
         dg, db = torch.empty_like(gamma), torch.empty_like(beta)
         dbias = torch.empty_like(bias) if has_bias else None
-        ws = _ws(lib.mdl_ln_gelu_drop_bwd_ws_bytes(rows, W), x.device)
+        ws = _ws_for("mdl_ln_gelu_drop_bwd_ws_bytes", x.device, rows, W)
         with _timed("ln_gelu_drop_bwd", ("byte", 3.0 * x.numel() * x.element_size())):
-            rc = getattr(lib, "mdl_ln_gelu_drop_bwd" + _sfx(x))(_ptr(x), _ptr(bias), _ptr(gamma), _ptr(beta), _ptr(mean),
-                                                              _ptr(rstd), _ptr(dy), _ptr(dx), _ptr(dg), _ptr(db), _ptr(dbias),
-                                                              rows, W, p_drop, seed, _ptr(keep), _ptr(ws), _stream())
-        _native.check(rc, "mdl_ln_gelu_drop_bwd")
+            _call("mdl_ln_gelu_drop_bwd" + _sfx(x), x, bias, gamma, beta, mean, rstd, dy, dx, dg, db, dbias, rows, W, p_drop, seed, keep, ws,
+                  _stream())
         return dx, dg, db, None, None, None, None, dbias
 
 
@@ -1246,7 +1183,6 @@ class LNGeluDropGroupsFn(torch.autograd.Function):
         _require(beta, "beta")
         _require(group_bias, "group_bias")
         _require(cu_groups, "cu_groups", torch.int64)
-        lib = _native.lib()
         W = x.shape[-1]
         rows, G = x.numel() // W, group_bias.shape[0]
         if group_bias.shape != (G, W) or cu_groups.numel() != G + 1:
@@ -1255,12 +1191,9 @@ class LNGeluDropGroupsFn(torch.autograd.Function):
         mean = torch.empty(rows, device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
         with _timed("ln_gelu_drop_fwd", ("byte", 2.0 * x.numel() * x.element_size())):
-            rc = getattr(lib, "mdl_ln_gelu_drop_fwd_groups" + _sfx(x))(_ptr(x), _ptr(group_bias), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(mean),
-                                                                     _ptr(rstd), rows, W, float(eps), float(p_drop), int(seed), _ptr(keep),
-                                                                     _ptr(cu_groups), G, _stream())
-        if rc == -3:
-            raise NotImplementedError("grouped LayerNorm-GELU-Dropout supports widths 256/512/1024 (got %d)" % W)
-        _native.check(rc, "mdl_ln_gelu_drop_fwd_groups")
+            _call("mdl_ln_gelu_drop_fwd_groups" + _sfx(x), x, group_bias, gamma, beta, y, mean, rstd, rows, W, float(eps), float(p_drop),
+                  int(seed), keep, cu_groups, G, _stream(),
+                  unsupported=("grouped LayerNorm-GELU-Dropout supports widths 256/512/1024 (got %d)", W))
         ctx.save_for_backward(x, gamma, beta, mean, rstd, group_bias, cu_groups)
         ctx.cfg = (float(p_drop), int(seed), keep)
         return y
@@ -1269,18 +1202,15 @@ class LNGeluDropGroupsFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, gamma, beta, mean, rstd, group_bias, cu_groups = ctx.saved_tensors
         p_drop, seed, keep = ctx.cfg
-        lib = _native.lib()
         W = x.shape[-1]
         rows, G = x.numel() // W, group_bias.shape[0]
         dy = dy.to(x.dtype).contiguous()
         dx = torch.empty_like(x)
         dg, db, dgb = torch.empty_like(gamma), torch.empty_like(beta), torch.empty_like(group_bias)
-        ws = _ws(lib.mdl_ln_gelu_drop_bwd_groups_ws_bytes(rows, W, G), x.device)
+        ws = _ws_for("mdl_ln_gelu_drop_bwd_groups_ws_bytes", x.device, rows, W, G)
         with _timed("ln_gelu_drop_bwd", ("byte", 3.0 * x.numel() * x.element_size())):
-            rc = getattr(lib, "mdl_ln_gelu_drop_bwd_groups" + _sfx(x))(_ptr(x), _ptr(group_bias), _ptr(gamma), _ptr(beta), _ptr(mean),
-                                                                     _ptr(rstd), _ptr(dy), _ptr(dx), _ptr(dg), _ptr(db), _ptr(dgb), rows, W,
-                                                                     p_drop, seed, _ptr(keep), _ptr(cu_groups), G, _ptr(ws), _stream())
-        _native.check(rc, "mdl_ln_gelu_drop_bwd_groups")
+            _call("mdl_ln_gelu_drop_bwd_groups" + _sfx(x), x, group_bias, gamma, beta, mean, rstd, dy, dx, dg, db, dgb, rows, W, p_drop, seed,
+                  keep, cu_groups, G, ws, _stream())
         return dx, dg, db, None, None, None, None, dgb, None
 
 
@@ -1376,15 +1306,12 @@ class InfoNCEFn(torch.autograd.Function):
         _require(Q, "query")
         _require(P, "positive_key")
         _require(cnt, "cnt", torch.int32)
-        lib = _native.lib()
         S, Kmax, D = Q.shape
         loss = torch.empty(S, device=Q.device, dtype=torch.float32)
         rows = torch.empty(S, Kmax, device=Q.device, dtype=torch.float32) if per_row else None
-        ws = _ws(lib.mdl_infonce_ws_bytes(S, Kmax, D), Q.device)
+        ws = _ws_for("mdl_infonce_ws_bytes", Q.device, S, Kmax, D)
         with _timed("infonce_fwd"):
-            rc = lib.mdl_infonce_fwd(_ptr(Q), _ptr(P), _ptr(cnt), _ptr(loss), _ptr(rows), S, Kmax, D, float(temperature),
-                                     int(symmetric), _ptr(ws), _stream())
-        _native.check(rc, "mdl_infonce_fwd")
+            _call("mdl_infonce_fwd", Q, P, cnt, loss, rows, S, Kmax, D, float(temperature), int(symmetric), ws, _stream())
         ctx.save_for_backward(cnt, ws, Q, P)
         ctx.cfg = (S, Kmax, D, float(temperature), int(symmetric), bool(per_row))
         if not per_row:
@@ -1396,7 +1323,6 @@ class InfoNCEFn(torch.autograd.Function):
     def backward(ctx, d_loss, d_rows):
         cnt, ws, Q, P = ctx.saved_tensors
         S, Kmax, D, temperature, symmetric, per_row = ctx.cfg
-        lib = _native.lib()
         dev = cnt.device
         dQ = torch.empty(S, Kmax, D, device=dev, dtype=torch.float32)
         dP = torch.empty_like(dQ)
@@ -1405,16 +1331,11 @@ class InfoNCEFn(torch.autograd.Function):
             g = d_rows.float().contiguous() if d_rows is not None else torch.zeros(S, Kmax, device=dev)
             if d_loss is not None:
                 g = g + d_loss.float().unsqueeze(1) / cnt.clamp_min(1).unsqueeze(1).float()
-            g = g.contiguous()
-            with _timed("infonce_bwd"):
-                rc = lib.mdl_infonce_bwd(_ptr(Q), _ptr(P), None, _ptr(g), _ptr(cnt), _ptr(dQ), _ptr(dP), S, Kmax, D, temperature,
-                                         symmetric, _ptr(ws), _stream())
+            d_loss, d_rows = None, g.contiguous()
         else:
-            d_loss = d_loss.float().contiguous()
-            with _timed("infonce_bwd"):
-                rc = lib.mdl_infonce_bwd(_ptr(Q), _ptr(P), _ptr(d_loss), None, _ptr(cnt), _ptr(dQ), _ptr(dP), S, Kmax, D, temperature,
-                                         symmetric, _ptr(ws), _stream())
-        _native.check(rc, "mdl_infonce_bwd")
+            d_loss, d_rows = d_loss.float().contiguous(), None
+        with _timed("infonce_bwd"):
+            _call("mdl_infonce_bwd", Q, P, d_loss, d_rows, cnt, dQ, dP, S, Kmax, D, temperature, symmetric, ws, _stream())
         return dQ, dP, None, None, None, None
 
 
@@ -1437,17 +1358,14 @@ class InfoNCENegFn(torch.autograd.Function):
         _require(Q, "query")
         _require(P, "positive_key")
         _require(Neg, "negative_keys")
-        lib = _native.lib()
         N, Dq = Q.shape
         M, D = Neg.shape[-2], Neg.shape[-1]
         loss = torch.empty((), device=Q.device, dtype=torch.float32)
         rows = torch.empty(N, device=Q.device, dtype=torch.float32) if per_row else None
-        ws = _ws(lib.mdl_infonce_neg_ws_bytes(N, M, D, int(paired)), Q.device)
+        ws = _ws_for("mdl_infonce_neg_ws_bytes", Q.device, N, M, D, int(paired))
         work = ("byte", 4.0 * Neg.numel()) if paired else ("flop", 2.0 * N * M * D)
         with _timed("infonce_neg_fwd", work):
-            rc = lib.mdl_infonce_neg_fwd(_ptr(Q), _ptr(P), _ptr(Neg), _ptr(loss), _ptr(rows), N, M, D, int(paired), float(temperature),
-                                         _ptr(ws), _stream())
-        _native.check(rc, "mdl_infonce_neg_fwd")
+            _call("mdl_infonce_neg_fwd", Q, P, Neg, loss, rows, N, M, D, int(paired), float(temperature), ws, _stream())
         ctx.save_for_backward(ws, Neg)
         ctx.cfg = (N, M, D, Dq, float(temperature), bool(paired), bool(per_row))
         if not per_row:
@@ -1459,7 +1377,6 @@ class InfoNCENegFn(torch.autograd.Function):
     def backward(ctx, d_loss, d_rows):
         ws, Neg = ctx.saved_tensors
         N, M, D, Dq, temperature, paired, per_row = ctx.cfg
-        lib = _native.lib()
         dev = Neg.device
         dQ = torch.empty(N, Dq, device=dev, dtype=torch.float32)
         dP = torch.empty_like(dQ)
@@ -1475,9 +1392,7 @@ class InfoNCENegFn(torch.autograd.Function):
         passes = 2 if dNeg is not None else 1
         work = ("byte", 4.0 * Neg.numel() * (1 + passes)) if paired else ("flop", 2.0 * N * M * D * (1 + passes))
         with _timed("infonce_neg_bwd", work):
-            rc = lib.mdl_infonce_neg_bwd(_ptr(Neg), _ptr(dl), _ptr(dr), _ptr(dQ), _ptr(dP), _ptr(dNeg), N, M, D, int(paired),
-                                         temperature, _ptr(ws), _stream())
-        _native.check(rc, "mdl_infonce_neg_bwd")
+            _call("mdl_infonce_neg_bwd", Neg, dl, dr, dQ, dP, dNeg, N, M, D, int(paired), temperature, ws, _stream())
         return dQ, dP, dNeg, None, None, None
 
 
@@ -1502,13 +1417,19 @@ class _GotFamily:
     def __init__(self, prefix, timed, refusal, rect=False):
         self.prefix, self.timed, self.refusal, self.rect = prefix, timed, refusal, rect
 
-    def fn(self, lib, suffix):
-        return getattr(lib, self.prefix + suffix)
-
     def sizes(self, V, Q):
         """The size arguments of this family's entry points."""
         k, n, d = V.shape
         return (k, n, Q.shape[1], d) if self.rect else (k, n, d)
+
+    def workspace(self, V, Q):
+        """The workspace of one problem, kept from the forward to the end of the backward; refuses a shape outside the class."""
+        sz = self.sizes(V, Q)
+        return _ws_for(self.prefix + "_ws_bytes", V.device, *sz, refusal=(self.refusal,) + sz[1:])
+
+    def call(self, stage, sz, ws, *tensors):
+        """<prefix><stage>(tensors..., sizes..., ws, stream): the argument list of every entry point of a family."""
+        _call(self.prefix + stage, *tensors, *sz, ws, _stream())
 
 
 GOT_RESIDENT = _GotFamily("mdl_got", "got",
@@ -1536,17 +1457,11 @@ class GOTFn(torch.autograd.Function):
         if V.dim() != 3 or Q.dim() != 3 or (V.shape[0], V.shape[2]) != (Q.shape[0], Q.shape[2]) or (
                 V.shape[1] != Q.shape[1] and not fam.rect):
             raise ValueError("GOT expects two token tensors of identical shape [k, n, d]")
-        lib = _native.lib()
-        sz = fam.sizes(V, Q)
-        nbytes = fam.fn(lib, "_ws_bytes")(*sz)
-        if nbytes == -3:
-            raise NotImplementedError(fam.refusal % sz[1:])
-        ws = _ws(nbytes, V.device)
+        ws = fam.workspace(V, Q)
         out = torch.empty(2, device=V.device, dtype=torch.float32)
         mm = torch.empty(6, device=V.device, dtype=torch.float32)
         with _timed(fam.timed + "_fwd"):
-            rc = fam.fn(lib, "_fwd")(_ptr(V), _ptr(Q), _ptr(out), _ptr(mm), _ptr(minmax_in), *sz, _ptr(ws), _stream())
-        _native.check(rc, fam.prefix + "_fwd")
+            fam.call("_fwd", fam.sizes(V, Q), ws, V, Q, out, mm, minmax_in)
         ctx.save_for_backward(V, Q, ws)
         ctx.reduce_dminmax = reduce_dminmax
         ctx.fam = fam
@@ -1557,21 +1472,17 @@ class GOTFn(torch.autograd.Function):
     def backward(ctx, d_out, _d_mm):
         V, Q, ws = ctx.saved_tensors
         fam = ctx.fam
-        lib = _native.lib()
         sz = fam.sizes(V, Q)
         dV, dQ = torch.empty_like(V), torch.empty_like(Q)
         d_out = d_out.contiguous()
         if ctx.reduce_dminmax is None:
             with _timed(fam.timed + "_bwd"):
-                rc = fam.fn(lib, "_bwd")(_ptr(V), _ptr(Q), _ptr(d_out), _ptr(dV), _ptr(dQ), *sz, _ptr(ws), _stream())
-            _native.check(rc, fam.prefix + "_bwd")
+                fam.call("_bwd", sz, ws, V, Q, d_out, dV, dQ)
         else:
             dmm = torch.empty(6, device=V.device, dtype=torch.float32)
-            rc = fam.fn(lib, "_bwd_begin")(_ptr(d_out), _ptr(dmm), *sz, _ptr(ws), _stream())
-            _native.check(rc, fam.prefix + "_bwd_begin")
+            fam.call("_bwd_begin", sz, ws, d_out, dmm)
             dmm = ctx.reduce_dminmax(dmm).contiguous()      # e.g. all_reduce(SUM) over ranks
-            rc = fam.fn(lib, "_bwd_finish")(_ptr(V), _ptr(Q), _ptr(dV), _ptr(dQ), _ptr(dmm), *sz, _ptr(ws), _stream())
-            _native.check(rc, fam.prefix + "_bwd_finish")
+            fam.call("_bwd_finish", sz, ws, V, Q, dV, dQ, dmm)
         return dV, dQ, None, None, None
 
 
@@ -1579,12 +1490,10 @@ def got_extrema(V, Q):
     """Extrema [6] (cross min,max | intra-V min,max | intra-Q min,max) of this batch's raw GOT cost tensors."""
     _require(V, "v_")
     _require(Q, "q_")
-    lib = _native.lib()
-    k, n, d = V.shape
-    ws = _ws(lib.mdl_got_ws_bytes(k, n, d), V.device)
+    fam, sz = GOT_RESIDENT, GOT_RESIDENT.sizes(V, Q)
+    ws = _ws_for(fam.prefix + "_ws_bytes", V.device, *sz)     # (its own scratch; a shape outside the class fails as a workspace query)
     mm = torch.empty(6, device=V.device, dtype=torch.float32)
-    rc = lib.mdl_got_extrema(_ptr(V), _ptr(Q), _ptr(mm), k, n, d, _ptr(ws), _stream())
-    _native.check(rc, "mdl_got_extrema")
+    fam.call("_extrema", sz, ws, V, Q, mm)
     return mm
 
 
@@ -1630,7 +1539,9 @@ def got_resident_supported(k: int, n: int, d: int) -> bool:
 
 class HipGotImpl:
     """The four stages of GOT on the C ABI, as used by the multi-problem / data-parallel autograd node
-    (madeleine_amd.distributed.got_multi).  A CPU implementation with the same interface exists only in tests/."""
+    (madeleine_amd.distributed.got_multi): the calls of GOTFn, fixed to the resident size class.  A CPU implementation with the same
+    interface exists only in tests/."""
+    FAM = GOT_RESIDENT
 
     @staticmethod
     def extrema(V, Q):
@@ -1638,40 +1549,31 @@ class HipGotImpl:
 
     @staticmethod
     def forward(V, Q, minmax):
-        lib = _native.lib()
-        k, n, d = V.shape
-        nbytes = lib.mdl_got_ws_bytes(k, n, d)
-        if nbytes == -3:
-            raise NotImplementedError("madeleine_amd.GOT supports n <= 512 tokens per bag and d <= 128 (got n=%d, d=%d)" % (n, d))
-        ws = _ws(nbytes, V.device)
+        fam = HipGotImpl.FAM
+        ws = fam.workspace(V, Q)
         out = torch.empty(2, device=V.device, dtype=torch.float32)
         mm = minmax.contiguous()
         with _timed("got_fwd"):
-            rc = lib.mdl_got_fwd(_ptr(V), _ptr(Q), _ptr(out), None, _ptr(mm), k, n, d, _ptr(ws), _stream())
-        _native.check(rc, "mdl_got_fwd")
+            fam.call("_fwd", fam.sizes(V, Q), ws, V, Q, out, None, mm)
         return out, (V, Q, ws)
 
     @staticmethod
     def backward_begin(state, d_out):
         V, Q, ws = state
-        lib = _native.lib()
-        k, n, d = V.shape
+        fam = HipGotImpl.FAM
         dmm = torch.empty(6, device=V.device, dtype=torch.float32)
         with _timed("got_bwd"):
-            rc = lib.mdl_got_bwd_begin(_ptr(d_out.contiguous()), _ptr(dmm), k, n, d, _ptr(ws), _stream())
-        _native.check(rc, "mdl_got_bwd_begin")
+            fam.call("_bwd_begin", fam.sizes(V, Q), ws, d_out.contiguous(), dmm)
         return dmm
 
     @staticmethod
     def backward_finish(state, dmm_total):
         V, Q, ws = state
-        lib = _native.lib()
-        k, n, d = V.shape
+        fam = HipGotImpl.FAM
         dV, dQ = torch.empty_like(V), torch.empty_like(Q)
         dmm_total = dmm_total.contiguous()
         with _timed("got_bwd_finish"):
-            rc = lib.mdl_got_bwd_finish(_ptr(V), _ptr(Q), _ptr(dV), _ptr(dQ), _ptr(dmm_total), k, n, d, _ptr(ws), _stream())
-        _native.check(rc, "mdl_got_bwd_finish")
+            fam.call("_bwd_finish", fam.sizes(V, Q), ws, V, Q, dV, dQ, dmm_total)
         return dV, dQ
 
     # ---- several problems per launch (mdl_got_*_multi): every kernel launch covers all problems, on the caller's stream alone ----
@@ -1702,51 +1604,40 @@ class HipGotImpl:
 
     @staticmethod
     def extrema_multi(problems):
-        lib = _native.lib()
         dev = problems[0][0].device
-        wss = [_ws(lib.mdl_got_ws_bytes(*V.shape), dev) for V, _ in problems]
+        wss = [_ws_for("mdl_got_ws_bytes", dev, *V.shape) for V, _ in problems]
         np_, Vp, Qp, ks, ns, d, wsp, _ = HipGotImpl._arrays(problems, wss)
         mm = torch.empty(np_, 6, device=dev, dtype=torch.float32)
-        rc = lib.mdl_got_extrema_multi(np_, Vp, Qp, HipGotImpl._rows(mm), ks, ns, d, wsp, _stream())
-        _native.check(rc, "mdl_got_extrema_multi")
+        _call("mdl_got_extrema_multi", np_, Vp, Qp, HipGotImpl._rows(mm), ks, ns, d, wsp, _stream())
         return mm
 
     @staticmethod
     def forward_multi(problems, minmax):
-        lib = _native.lib()
         dev = problems[0][0].device
-        for V, _ in problems:
-            if lib.mdl_got_ws_bytes(*V.shape) == -3:
-                raise NotImplementedError("madeleine_amd.GOT supports n <= 512 tokens per bag and d <= 128")
-        wss = [_ws(lib.mdl_got_ws_bytes(*V.shape), dev) for V, _ in problems]
+        wss = [HipGotImpl.FAM.workspace(V, Q) for V, Q in problems]
         np_, Vp, Qp, ks, ns, d, wsp, _ = HipGotImpl._arrays(problems, wss)
         out = torch.empty(np_, 2, device=dev, dtype=torch.float32)
         mm = minmax.contiguous()
         with _timed("got_fwd"):
-            rc = lib.mdl_got_fwd_multi(np_, Vp, Qp, HipGotImpl._rows(out), HipGotImpl._rows(mm), ks, ns, d, wsp, _stream())
-        _native.check(rc, "mdl_got_fwd_multi")
+            _call("mdl_got_fwd_multi", np_, Vp, Qp, HipGotImpl._rows(out), HipGotImpl._rows(mm), ks, ns, d, wsp, _stream())
         return out, (list(problems), wss)
 
     @staticmethod
     def backward_begin_multi(state, d_outs):
         problems, wss = state
-        lib = _native.lib()
         np_, _Vp, _Qp, ks, ns, d, wsp, _ = HipGotImpl._arrays(problems, wss)
         d_outs = d_outs.contiguous()
         dmm = torch.empty(np_, 6, device=d_outs.device, dtype=torch.float32)
         with _timed("got_bwd"):
-            rc = lib.mdl_got_bwd_begin_multi(np_, HipGotImpl._rows(d_outs), HipGotImpl._rows(dmm), ks, ns, d, wsp, _stream())
-        _native.check(rc, "mdl_got_bwd_begin_multi")
+            _call("mdl_got_bwd_begin_multi", np_, HipGotImpl._rows(d_outs), HipGotImpl._rows(dmm), ks, ns, d, wsp, _stream())
         return dmm
 
     @staticmethod
     def backward_finish_multi(state, dmm_total):
         problems, wss = state
-        lib = _native.lib()
         np_, Vp, Qp, ks, ns, d, wsp, ptrs = HipGotImpl._arrays(problems, wss)
         dVs, dQs = [torch.empty_like(V) for V, _ in problems], [torch.empty_like(Q) for _, Q in problems]
         dmm_total = dmm_total.contiguous()
         with _timed("got_bwd_finish"):
-            rc = lib.mdl_got_bwd_finish_multi(np_, Vp, Qp, ptrs(dVs), ptrs(dQs), HipGotImpl._rows(dmm_total), ks, ns, d, wsp, _stream())
-        _native.check(rc, "mdl_got_bwd_finish_multi")
+            _call("mdl_got_bwd_finish_multi", np_, Vp, Qp, ptrs(dVs), ptrs(dQs), HipGotImpl._rows(dmm_total), ks, ns, d, wsp, _stream())
         return list(zip(dVs, dQs))

@@ -108,39 +108,31 @@ def GOT(v_, q_, subsample=None):
     v_ [k, n, d] and q_ [k, m, d] may hold different token counts (n != m, both <= 4096): the cross cost and the transport plans are
     then n x m, on the tiled size class.  GOT(v, q) != GOT(q, v).  With `subsample` both are indexed with the same indices, as in
     the reference, and an index beyond the shorter one raises IndexError."""
-    if v_.dim() == 3 and q_.dim() == 3 and v_.shape[1] != q_.shape[1]:
-        return _got_rect(v_, q_, subsample)
-    if subsample is not None:
-        patch_indices = torch.randperm(v_.shape[0])[:subsample].to(v_.device)
-        v_ = v_.index_select(1, patch_indices)
-        q_ = q_.index_select(1, patch_indices)
-    v, q = v_.float().contiguous(), q_.float().contiguous()
-    route = got_route(*v.shape) if v.dim() == 3 else "resident"
-    if route == "resident":
-        out = MF.got(v, q)
-    elif route == "tiled":
-        out = MF.got_tiled(v, q)
-    else:
-        raise NotImplementedError("madeleine_amd.GOT supports n <= 4096 tokens per bag and d <= 4096 (got n=%d, d=%d)"
-                                  % tuple(v.shape[1:]))
-    return out[1] + out[0]
-
-
-def _got_rect(v_, q_, subsample):
-    """GOT() for v_ [k, n, d], q_ [k, m, d] with n != m."""
+    rect = v_.dim() == 3 and q_.dim() == 3 and v_.shape[1] != q_.shape[1]
     if subsample is not None:
         patch_indices = torch.randperm(v_.shape[0])[:subsample]
-        short = min(v_.shape[1], q_.shape[1])
-        if patch_indices.numel() and int(patch_indices.max()) >= short:
-            # what the reference's v_[:, idx, :] raises; checked on the host so that no device-side bounds assert fires
-            raise IndexError("index %d is out of bounds for dimension 1 with size %d" % (int(patch_indices.max()), short))
+        if rect:
+            short = min(v_.shape[1], q_.shape[1])
+            if patch_indices.numel() and int(patch_indices.max()) >= short:
+                # what the reference's v_[:, idx, :] raises; checked on the host so that no device-side bounds assert fires
+                raise IndexError("index %d is out of bounds for dimension 1 with size %d" % (int(patch_indices.max()), short))
         patch_indices = patch_indices.to(v_.device)
-        return GOT(v_.index_select(1, patch_indices), q_.index_select(1, patch_indices))   # equal token counts from here on
+        v_ = v_.index_select(1, patch_indices)
+        q_ = q_.index_select(1, patch_indices)
+        rect = False   # equal token counts from here on
     v, q = v_.float().contiguous(), q_.float().contiguous()
-    if (v.shape[0], v.shape[2]) == (q.shape[0], q.shape[2]) and got_route(*v.shape, m=q.shape[1]) == "unsupported":
+    if v.dim() != 3 or (rect and (v.shape[0], v.shape[2]) != (q.shape[0], q.shape[2])):
+        # not two [k, ., d] token sets: no size class to ask for; the autograd node's own shape check raises ValueError
+        out = MF.got_tiled(v, q) if rect else MF.got(v, q)
+        return out[1] + out[0]
+    route = got_route(*v.shape, m=q.shape[1] if rect else None)
+    if route == "unsupported" and rect:
         raise NotImplementedError("madeleine_amd.GOT supports n <= 4096 and m <= 4096 tokens per bag and d <= 4096 "
                                   "(got n=%d, m=%d, d=%d)" % (v.shape[1], q.shape[1], v.shape[2]))
-    out = MF.got_tiled(v, q)
+    if route == "unsupported":
+        raise NotImplementedError("madeleine_amd.GOT supports n <= 4096 tokens per bag and d <= 4096 (got n=%d, d=%d)"
+                                  % tuple(v.shape[1:]))
+    out = MF.got(v, q) if route == "resident" else MF.got_tiled(v, q)
     return out[1] + out[0]
 
 

@@ -36,6 +36,80 @@ def test_library_exports_every_header_symbol():
     assert lib.mdl_abmil_gate_fwd_ws_bytes(-1, 4) < 0 and lib.mdl_abmil_pool_ws_bytes(1, 1, 99) < 0
 
 
+def test_derived_signatures_equal_hand_written_ones():
+    """The binding is parsed from the header; these six are typed here by hand from the same declarations.  Between them: every scalar
+    type (int, int64_t, uint64_t, uint32_t, float), pointers of every kind, the char* return and (void)."""
+    from madeleine_amd import _native
+    p, i32, i64, u32, u64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float
+    expected = {
+        "mdl_version": (ctypes.c_char_p, []),
+        "mdl_abmil_gate_fwd": (i32, [p, i64, p, p, p, p, p, p, p, p, p, i64, i32, f32, u64, p, p, p, p]),
+        "mdl_split_gemm_nt": (i32, [p, i64, p, p, i64, p, p, i64, i64, i32, i32, p, i32, p, p, p, p, i32, p]),
+        "mdl_got_tiled_rect_fwd": (i32, [p, p, p, p, p, i32, i32, i32, i32, p, p]),
+        "mdl_stream_create_cu_mask": (i32, [u32, p, p]),
+        "mdl_dispatch_plan": (i32, [i32, i64, i32, i32, i32, p, i32]),
+        "mdl_abmil_gate_fwd_ws_bytes": (i64, [i64, i32]),
+    }
+    for name, (res, args) in expected.items():
+        got_res, got_args = _native.SIGNATURES[name]
+        assert got_res is res and got_args == args, name
+
+
+@pytest.mark.parametrize("text, message", [
+    ("int mdl_a(const float* x, size_t n);", "unknown type 'size_t n' in the declaration of mdl_a"),
+    ("double mdl_a(int n);", "unknown type 'double' in the declaration of mdl_a"),
+    ("void* mdl_a(int n);", "unknown type 'void*' in the declaration of mdl_a"),
+    ("int mdl_a(int);", "unknown type 'int' in the declaration of mdl_a"),
+    ("int mdl_a(const float*);", "unknown type 'const float*' in the declaration of mdl_a"),
+    ("int mdl_a(int n, const float *);", "unknown type 'const float *' in the declaration of mdl_a"),
+    ("int mdl_a(float x[4]);", "unknown type 'float x[4]' in the declaration of mdl_a"),
+    ("int mdl_a(int64_t int);", "unknown type 'int64_t int' in the declaration of mdl_a"),
+    ("int mdl_a(int n);\nint mdl_b(void);\nint mdl_a(int n);", "declares mdl_a twice"),
+    ("int mdl_a(int n, float x;\nint mdl_b(void);", "cannot read the header declaration 'int mdl_a(int n, float x'"),
+    ("int mdl_a(int n) { return n; }", "cannot read the header declaration"),
+    ("/* int mdl_a(int n); */\n#define MDL_ABI_VERSION 26\n", "declares no entry point"),
+    ("", "declares no entry point"),
+])
+def test_header_parser_is_strict(text, message):
+    """A header the parser cannot read completely is an error that names the declaration -- never a guessed type."""
+    from madeleine_amd import _native
+    with pytest.raises(ValueError, match=re.escape(message)):
+        _native._parse_header(text)
+
+
+def test_header_parser_reads_what_it_should():
+    from madeleine_amd import _native
+    sigs, defines = _native._parse_header(
+        "#ifdef __cplusplus\nextern \"C\" {\n#endif\n#define MDL_E_X (-7) /* why */\n#define MDL_N 3\n"
+        "/* int mdl_gone(int n); */\nconst char* mdl_v(void);\nint64_t mdl_w(const float* const* V, void** out,\n"
+        "              uint64_t seed, float p);\n#ifdef __cplusplus\n}\n#endif\n")
+    assert sigs == {"mdl_v": (ctypes.c_char_p, []),
+                    "mdl_w": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_float])}
+    assert defines == {"MDL_E_X": -7, "MDL_N": 3}
+
+
+def test_constants_come_from_the_header_defines():
+    """ABI_VERSION, the error codes, PLAN_PRODUCTS and the PLAN_FIELDS indices against this test's own reading of the #defines."""
+    from madeleine_amd import _native
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "madeleine_amd.h")).read(), flags=re.S)
+    defs = {k: int(v.strip("()")) for k, v in re.findall(r"^#define\s+(MDL_\w+)\s+(\(?-?\d+\)?)\s*$", src, flags=re.M)}
+    assert _native.ABI_VERSION == defs["MDL_ABI_VERSION"] == 26
+    errs = {k: v for k, v in defs.items() if k.startswith("MDL_E_")}
+    assert sorted(_native._ERR) == sorted(errs.values()) == [-3, -2, -1]
+    for k, v in errs.items():
+        assert _native._ERR[v].startswith(k)
+        with pytest.raises(RuntimeError, match=k):
+            _native.check(v, "mdl_x")
+    assert _native._E_UNSUPPORTED == defs["MDL_E_UNSUPPORTED"]
+    assert defs["MDL_PLAN_FIELDS"] == len(_native.PLAN_FIELDS) == 7
+    for i, f in enumerate(_native.PLAN_FIELDS):
+        assert defs["MDL_PLAN_" + f.upper()] == i
+    fields = {"MDL_PLAN_" + f.upper() for f in _native.PLAN_FIELDS} | {"MDL_PLAN_FIELDS"}
+    products = {k[len("MDL_PLAN_"):].lower(): v for k, v in defs.items() if k.startswith("MDL_PLAN_") and k not in fields}
+    assert _native.PLAN_PRODUCTS == products and len(products) == 13
+    assert _native.PLAN_PRODUCTS["gate_fp32_bwd"] == 1 and _native.PLAN_PRODUCTS["got_tiled_rect"] == 13
+
+
 def _cfg(mods, d_in=64):
     return SimpleNamespace(MODALITIES=list(mods), wsi_encoder="abmil", patch_embedding_dim=d_in,
                            wsi_encoder_hidden_dim=512, activation="softmax", n_heads=4)
