@@ -649,6 +649,47 @@ int mdl_abmil_attnpool_bwd_split(const void* E_img, int64_t e_rsb, const float* 
 #define MDL_PLAN_FIELDS 7
 int mdl_dispatch_plan(int product, int64_t T, int a, int b, int cus, int64_t* out_host, int n_out);
 
+/* ------------------------------------------------------------------------------------------------
+ * O1 -- multi-tensor fp32 AdamW that skips a step with a non-finite gradient and clips by the global gradient norm in-stream.
+ * Replaces optim.AdamW(ssl_model.parameters(), lr=args.lr) (setup_components.py:196) together with the host-side guards that usually
+ * surround it (`if not torch.isfinite(loss): continue`, clip_grad_norm_): nothing is read back, copied to the device or allocated.
+ *
+ * One step of the caller, for each set of nt <= MDL_ADAMW_MAX_TENSORS tensors (a parameter group is one or more sets):
+ *   1. mdl_adamw_grad_stats  (only with MDL_ADAMW_GUARD or MDL_ADAMW_CLIP; statistics launch `slot` of the step's `stat_launches`)
+ *   2. mdl_adamw_update      after EVERY statistics launch of the step: the verdict and the norm are global over all sets
+ *   3. mdl_adamw_commit      after the set's update; MDL_ADAMW_FINAL on the step's last commit
+ * The number of launches does not depend on the outcome.  The *_host arguments are HOST arrays of nt device pointers / sizes, read
+ * during the call and passed to the kernels by value (gradient addresses may change every step).  Every tensor is fp32 and dense;
+ * p, g and the moments need 4-byte alignment only (16-byte accesses where a tensor's pointers allow them).  A tensor of zero
+ * elements is accepted (its step still advances); step[i] is torch's per-parameter `step`, one fp32 value on the device.
+ *
+ * Update of an applied step, per element, t = step[i] + 1:   p *= 1 - lr wd;  m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g'^2;
+ *   p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps),   g' = g min(1, max_norm / (norm + 1e-6)) with MDL_ADAMW_CLIP,
+ *   else g.  g is never written.  lr, beta1, beta2, eps, weight_decay and max_norm are passed as the BIT PATTERNS of doubles
+ *   (*_bits): every derived scalar is formed in double on the device and rounded to fp32 once, as torch.optim.AdamW does on the host.
+ * With MDL_ADAMW_GUARD a step in which any gradient element of any set is inf or NaN (decided per element) is void: update and
+ * commit write nothing except, in the FINAL commit, grad_norm and skipped[0] += 1.
+ *
+ * ws: mdl_adamw_ws_bytes(stat_launches) bytes, 16-byte aligned, shared by all calls of one step: MDL_ADAMW_STAT_BLOCKS partial
+ * {sum of squares, non-finite} pairs per statistics launch, every one of them rewritten by its launch and merged in a fixed order
+ * (no float atomics: two runs give the same bits).  May be NULL with neither GUARD nor CLIP.  grad_norm [1] (the global norm, written
+ * by the FINAL commit when statistics ran) and skipped [1] belong to the caller and persist between steps. */
+#define MDL_ADAMW_MAX_TENSORS 48
+#define MDL_ADAMW_STAT_BLOCKS 512
+#define MDL_ADAMW_MAX_STAT_LAUNCHES 64
+#define MDL_ADAMW_GUARD 1
+#define MDL_ADAMW_CLIP 2
+#define MDL_ADAMW_FINAL 4
+int64_t mdl_adamw_ws_bytes(int64_t stat_launches);
+int mdl_adamw_grad_stats(int nt, const float* const* g_host, const int64_t* numel_host, void* ws, int64_t slot, int64_t stat_launches,
+                         void* stream);
+int mdl_adamw_update(int nt, float* const* p_host, const float* const* g_host, float* const* exp_avg_host,
+                     float* const* exp_avg_sq_host, const float* const* step_host, const int64_t* numel_host, uint64_t lr_bits,
+                     uint64_t beta1_bits, uint64_t beta2_bits, uint64_t eps_bits, uint64_t weight_decay_bits, uint64_t max_norm_bits,
+                     int flags, const void* ws, int64_t stat_launches, void* stream);
+int mdl_adamw_commit(int nt, float* const* step_host, int flags, const void* ws, int64_t stat_launches, float* grad_norm,
+                     int64_t* skipped, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1641,3 +1641,49 @@ class HipGotImpl:
         with _timed("got_bwd_finish"):
             _call("mdl_got_bwd_finish_multi", np_, Vp, Qp, ptrs(dVs), ptrs(dQs), HipGotImpl._rows(dmm_total), ks, ns, d, wsp, _stream())
         return list(zip(dVs, dQs))
+
+
+# ---- O1: multi-tensor AdamW with a device-side non-finite guard and in-stream clipping (mdl_adamw_*) ----
+ADAMW_MAX_TENSORS = _native._DEFINES["MDL_ADAMW_MAX_TENSORS"]      # tensors per launch set
+ADAMW_GUARD, ADAMW_CLIP, ADAMW_FINAL = (_native._DEFINES["MDL_ADAMW_" + k] for k in ("GUARD", "CLIP", "FINAL"))
+
+
+def _f64_bits(x: float) -> int:
+    """The bit pattern of a double: how the C ABI (which has no double) carries the hyperparameters without rounding them to fp32."""
+    import struct
+    return struct.unpack("<Q", struct.pack("<d", float(x)))[0]
+
+
+def adamw_ptrs(tensors):
+    """Host array of the device addresses of `tensors`, as the *_host arguments of mdl_adamw_* take them."""
+    import ctypes
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def adamw_sizes(tensors):
+    import ctypes
+    return (ctypes.c_int64 * len(tensors))(*[t.numel() for t in tensors])
+
+
+def adamw_workspace(stat_launches: int, device) -> torch.Tensor:
+    """Scratch for the gradient statistics of a step with `stat_launches` statistics launches; every slot is rewritten each step."""
+    return _ws_for("mdl_adamw_ws_bytes", device, int(stat_launches))
+
+
+def adamw_grad_stats(nt, g_ptrs, numels, ws, slot, stat_launches):
+    with _timed("adamw_stats"):
+        _call("mdl_adamw_grad_stats", nt, g_ptrs, numels, ws, slot, stat_launches, _stream())
+
+
+def adamw_update(nt, p_ptrs, g_ptrs, m_ptrs, v_ptrs, step_ptrs, numels, lr, beta1, beta2, eps, weight_decay, max_norm, flags, ws,
+                 stat_launches):
+    """p, exp_avg, exp_avg_sq of the set's tensors <- one AdamW step (nothing on a void step).  lr ... max_norm: Python floats."""
+    with _timed("adamw_update"):
+        _call("mdl_adamw_update", nt, p_ptrs, g_ptrs, m_ptrs, v_ptrs, step_ptrs, numels, _f64_bits(lr), _f64_bits(beta1), _f64_bits(beta2),
+              _f64_bits(eps), _f64_bits(weight_decay), _f64_bits(max_norm), flags, ws, stat_launches, _stream())
+
+
+def adamw_commit(nt, step_ptrs, flags, ws, stat_launches, grad_norm, skipped):
+    """step += 1 for the set's tensors unless the step is void; with ADAMW_FINAL also grad_norm <- global norm, skipped += void."""
+    with _timed("adamw_commit"):
+        _call("mdl_adamw_commit", nt, step_ptrs, flags, ws, stat_launches, grad_norm, skipped, _stream())
