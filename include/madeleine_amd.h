@@ -690,6 +690,35 @@ int mdl_adamw_update(int nt, float* const* p_host, const float* const* g_host, f
 int mdl_adamw_commit(int nt, float* const* step_host, int flags, const void* ws, int64_t stat_launches, float* grad_norm,
                      int64_t* skipped, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * S1 -- draw and gather a whole batch of bags from a device-resident feature store, in one launch (ABI 26, additive).
+ * Replaces the input side of the reference (madeleine/datasets/wsi_dataset.py): SlideDataset.sample_n (:42-50), the 2-token zero bag
+ * of an absent stain (:66) and collate's stack (:86-99) -- without the h5 re-reads, the host draw and the per-step host-to-device copy.
+ *
+ * store: T_total rows of D elements, row_stride ELEMENTS apart (>= D), stored as dtype = MDL_STORE_F32 / _F16 / _BF16; 16-byte
+ *   aligned.  off [n_bags + 1] (int64, ascending): bag g is rows off[g] .. off[g + 1] - 1.  All of it is only read.
+ * bag [R] (int32): the stored bag of output row r, or -1 for an absent stain.  key_id [R] (int64) names row r's random stream: the draw
+ *   of row r is a pure function of (seed, counter, key_id[r]) and of the bag's length -- not of R, of r or of the other rows.
+ *   key_id == NULL stands for key_id[r] = bag[r].
+ * out [R, N, D] fp32, dense, 16-byte aligned; every element is written.  idx_out [R, N] (int32) or NULL: the chosen row of the bag
+ *   (0-based inside the bag), -1 in the rows of an absent stain.
+ *
+ * With n = off[bag + 1] - off[bag] (sample_n's semantics, in distribution -- the bits are this kernel's own, not torch's generators'):
+ *   n >= N      N distinct rows: a uniformly random N-subset in uniformly random order (randperm(n)[:N]); a permutation at n == N
+ *   1 <= n < N  N rows drawn independently and uniformly, with replacement (randint(0, n, (N,)))
+ *   bag == -1   N x D zeros (what collate stacks for the dataset's zero bag).  A bag index outside [0, n_bags), an empty bag, a bag
+ *               of more than 2^31 - 1 rows or one that leaves [0, T_total) is written as an absent stain: the kernel never reads
+ *               outside the store.
+ * Rows are copied bit for bit from an fp32 store and converted exactly from fp16 / bf16.  Any D >= 1: 16-byte accesses when D and
+ * row_stride are multiples of 4 (fp32) / 8 (16-bit stores) elements, element-wise accesses otherwise.  No workspace.
+ * MDL_E_UNSUPPORTED: R * N or the grid R * ceil(N / 64) beyond int32. */
+#define MDL_STORE_F32 0
+#define MDL_STORE_F16 1
+#define MDL_STORE_BF16 2
+int mdl_bag_sample(const void* store, int dtype, int64_t row_stride, int64_t T_total, const int64_t* off, int64_t n_bags,
+                   const int32_t* bag, const int64_t* key_id, int64_t R, int N, int D, uint64_t seed, uint64_t counter, float* out,
+                   int32_t* idx_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@ madeleine.utils.loss, madeleine.utils.trainer):
     from madeleine_amd import MADELEINE, ABMILEmbedder, BatchedABMIL, create_model
     from madeleine_amd import InfoNCE, GOT, calculate_losses, train_loop, run_inference
     from madeleine_amd import AdamW          # torch.optim.AdamW's update with a device-side non-finite guard and clipping
+    from madeleine_amd import DeviceSlideStore   # the cohort's features resident on the device, batches drawn by one kernel
 
 The numeric work runs in csrc/libmadeleine_amd.so through the C ABI of include/madeleine_amd.h.
 Importing this package does not load the library (so model construction / state_dict handling works on
@@ -15,10 +16,11 @@ from .abmil import BatchedABMIL
 from .loss import GOT, InfoNCE, info_nce, init_intra_wsi_loss_function
 from .model import ABMILEmbedder, MADELEINE, create_model
 from .optim import AdamW
+from .store import DeviceSlideStore
 from .trainer import calculate_losses, train_loop
 from .utils import create_model_from_pretrained, extract_slide_level_embeddings, load_checkpoint, run_inference
 
 __all__ = ["MADELEINE", "ABMILEmbedder", "BatchedABMIL", "create_model", "InfoNCE", "info_nce", "GOT",
            "init_intra_wsi_loss_function", "calculate_losses", "train_loop", "run_inference", "extract_slide_level_embeddings",
-           "load_checkpoint", "create_model_from_pretrained", "AdamW"]
+           "load_checkpoint", "create_model_from_pretrained", "AdamW", "DeviceSlideStore"]
 __version__ = "0.2"

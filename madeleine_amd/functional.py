@@ -1687,3 +1687,38 @@ def adamw_commit(nt, step_ptrs, flags, ws, stat_launches, grad_norm, skipped):
     """step += 1 for the set's tensors unless the step is void; with ADAMW_FINAL also grad_norm <- global norm, skipped += void."""
     with _timed("adamw_commit"):
         _call("mdl_adamw_commit", nt, step_ptrs, flags, ws, stat_launches, grad_norm, skipped, _stream())
+
+
+# ---- S1: draw and gather a batch of bags from a device-resident feature store (mdl_bag_sample) ----
+STORE_DTYPES = {torch.float32: _native._DEFINES["MDL_STORE_F32"], torch.float16: _native._DEFINES["MDL_STORE_F16"],
+                torch.bfloat16: _native._DEFINES["MDL_STORE_BF16"]}
+_U64 = (1 << 64) - 1
+
+
+def bag_sample(store_rows, off, bag, key_id, n_tokens, seed, counter, return_indices=False):
+    """out [R, n_tokens, D] fp32 <- for every output row r, n_tokens rows of stored bag bag[r] (rows off[bag[r]] .. off[bag[r] + 1] - 1
+    of store_rows [T, D], fp32 / fp16 / bf16, unit column stride): without replacement in random order when the bag has at least
+    n_tokens rows, with replacement when it is shorter, zeros where bag[r] == -1 (SlideDataset.sample_n + collate, in one launch on
+    the current stream).  Row r's draw is a function of (seed, counter, key_id[r]) alone; key_id None: key_id[r] = bag[r].
+    off int64 [n_bags + 1], bag int32 [R], key_id int64 [R], all on the device.  No autograd (features are inputs), no host read,
+    no allocation beyond the outputs.  return_indices: also idx [R, n_tokens] int32, the chosen row inside the bag (-1: absent)."""
+    if store_rows.dim() != 2 or store_rows.dtype not in STORE_DTYPES or (store_rows.shape[1] > 1 and store_rows.stride(1) != 1):
+        raise RuntimeError("madeleine_amd: store_rows must be [T, D] float32 / float16 / bfloat16 with unit column stride")
+    if not store_rows.is_cuda:
+        raise RuntimeError("madeleine_amd: store_rows must live on a ROCm device (got %s); there is no CPU fallback" % store_rows.device)
+    _require(off, "off", torch.int64)
+    _require(bag, "bag", torch.int32)
+    if key_id is not None:
+        _require(key_id, "key_id", torch.int64)
+        if key_id.numel() != bag.numel():
+            raise RuntimeError("madeleine_amd: key_id and bag must have one entry per output row")
+    if off.dim() != 1 or off.numel() < 1:
+        raise RuntimeError("madeleine_amd: off must be [n_bags + 1]")
+    R, N, D = bag.numel(), int(n_tokens), store_rows.shape[1]
+    out = torch.empty(R, N, D, device=store_rows.device, dtype=torch.float32)
+    idx = torch.empty(R, N, device=store_rows.device, dtype=torch.int32) if return_indices else None
+    with _timed("bag_sample", ("byte", R * N * D * (4.0 + store_rows.element_size()))):
+        _call("mdl_bag_sample", store_rows, STORE_DTYPES[store_rows.dtype], store_rows.stride(0) if store_rows.shape[0] > 1 else D,
+              store_rows.shape[0], off, off.numel() - 1, bag, key_id, R, N, D, int(seed) & _U64, int(counter) & _U64, out, idx, _stream(),
+              unsupported=("bag_sample: %d output rows of %d tokens exceed the int32 launch geometry", R, N))
+    return (out, idx) if return_indices else out

@@ -1,0 +1,220 @@
+"""Device-resident slide store: the patch features of a whole pretraining cohort loaded ONCE into one device tensor, and every step's
+`[B, M, N, D]` batch drawn from it on the device by one kernel (functional.bag_sample -> mdl_bag_sample, csrc/bag_sample.hip).
+
+Replaces, for a cohort that fits in HBM, the reference's input side (madeleine/datasets/wsi_dataset.py): SlideDataset.__getitem__
+re-reads every stain's h5 file for every item of every epoch, draws `sample` rows on the host and collate stacks them, and the stacked
+batch then crosses PCIe every step.  Here the only per-step host-to-device traffic is the `[B * M]` int32 table of the batch's bags.
+
+Layout.  `rows [T_total, D]` holds the present bags back to back, case-major then modality-major; `off [n_bags + 1]` (int64, on the
+device and on the host) is the first row of every stored bag; `bag_table [cases, M]` (int32, host) maps (case, modality) to its stored
+bag or -1 for an absent stain; `modality_labels [cases, M]` follow from it.  The dataset's 2-token zero bags of absent stains are not
+stored: the kernel writes their zeros.
+
+The batches iterables yield exactly what collate() / ragged_collate() yield (`feats` already on the device), so train_loop and
+MADELEINE.forward take them unchanged.  There is no CPU fallback: a store may be BUILT on the CPU (packing logic, tests), sampling from
+it raises.
+"""
+from typing import List, Optional
+
+import torch
+
+from . import functional as MF
+
+FP16_MAX = 65504.0
+_MAX_BAG_ROWS = 2 ** 31 - 1
+
+
+class DeviceSlideStore:
+    def __init__(self, bags, slide_ids, modalities, device, dtype=torch.float32):
+        """bags: list over cases of lists over modalities of [n, D] CPU tensors, None for an absent stain.  dtype float16 / bfloat16:
+        an opt-in LOSSY store of half the size (features are rounded once, at load time; fp16 refuses a bag it cannot hold)."""
+        if dtype not in MF.STORE_DTYPES:
+            raise ValueError("DeviceSlideStore: dtype must be float32, float16 or bfloat16 (got %s)" % dtype)
+        self.modalities = list(modalities)
+        self.slide_ids = list(slide_ids)
+        self.device, self.dtype = torch.device(device), dtype
+        n_cases, M = len(bags), len(self.modalities)
+        if len(self.slide_ids) != n_cases:
+            raise ValueError("DeviceSlideStore: %d cases but %d slide ids" % (n_cases, len(self.slide_ids)))
+        table = torch.full((n_cases, M), -1, dtype=torch.int32)
+        lens, present, D = [], [], None
+        for c, case in enumerate(bags):
+            if len(case) != M:
+                raise ValueError("DeviceSlideStore: case %d (%s) has %d bags for %d modalities" % (c, self.slide_ids[c], len(case), M))
+            for m, bag in enumerate(case):
+                if bag is None:
+                    continue
+                where = "bag of case %d (%s), modality %s" % (c, self.slide_ids[c], self.modalities[m])
+                if not torch.is_tensor(bag) or bag.dim() != 2 or not bag.is_floating_point():
+                    raise ValueError("DeviceSlideStore: the %s must be a [n, D] float tensor" % where)
+                if bag.shape[0] < 1 or bag.shape[0] > _MAX_BAG_ROWS:
+                    raise ValueError("DeviceSlideStore: the %s has %d rows (1 .. 2^31 - 1 are supported)" % (where, bag.shape[0]))
+                if D is None:
+                    D = int(bag.shape[1])
+                if bag.shape[1] != D or D < 1:
+                    raise ValueError("DeviceSlideStore: the %s is %d wide, earlier bags are %d wide" % (where, bag.shape[1], D))
+                if dtype == torch.float16:      # the one-off host check of the lossy store: fp16 would turn such a value into inf
+                    absmax = float(bag.abs().max())
+                    if not absmax <= FP16_MAX:
+                        raise ValueError("DeviceSlideStore: the %s has absmax %g, beyond float16's %g; use float32 or bfloat16"
+                                         % (where, absmax, FP16_MAX))
+                table[c, m] = len(lens)
+                lens.append(int(bag.shape[0]))
+                present.append(bag)
+        if D is None:
+            raise ValueError("DeviceSlideStore: no present bag")
+        self.dim = D
+        self.bag_table = table
+        self.modality_labels = (table >= 0).float()
+        self.off_cpu = torch.zeros(len(lens) + 1, dtype=torch.int64)
+        self.off_cpu[1:] = torch.cumsum(torch.tensor(lens, dtype=torch.int64), 0)
+        total = int(self.off_cpu[-1])
+        nbytes = total * D * torch.empty(0, dtype=dtype).element_size()
+        if self.device.type == "cuda":
+            free, capacity = torch.cuda.mem_get_info(self.device)
+            if nbytes > free:
+                raise RuntimeError("DeviceSlideStore: the store needs %d bytes (%d rows x %d x %s) but %s has %d bytes free of %d"
+                                   % (nbytes, total, D, dtype, self.device, free, capacity))
+        self.rows = torch.empty(total, D, dtype=dtype, device=self.device)
+        self._upload(present)
+        self.off = self.off_cpu.to(self.device)
+        self._zero_bag = None
+
+    def _upload(self, present):
+        """One bag at a time through two pinned staging buffers (the cast to the store's dtype happens in the host copy): the cohort is
+        never concatenated on the host."""
+        off = self.off_cpu.tolist()
+        if self.device.type != "cuda":
+            for g, bag in enumerate(present):
+                self.rows[off[g]:off[g + 1]].copy_(bag)
+            return
+        longest = max(int(b.shape[0]) for b in present)
+        stage = [torch.empty(longest, self.dim, dtype=self.dtype).pin_memory() for _ in range(2)]
+        busy = [None, None]
+        with torch.cuda.device(self.device):
+            for g, bag in enumerate(present):
+                s = g & 1
+                if busy[s] is not None:
+                    busy[s].synchronize()          # the slot's previous upload has left the staging buffer
+                n = bag.shape[0]
+                stage[s][:n].copy_(bag)
+                self.rows[off[g]:off[g + 1]].copy_(stage[s][:n], non_blocking=True)
+                busy[s] = torch.cuda.Event()
+                busy[s].record()
+            torch.cuda.current_stream().synchronize()
+
+    @classmethod
+    def from_dataset(cls, dataset, device, dtype=torch.float32):
+        """One pass over a SlideDataset(sample=-1, train=True): keeps feats[m] where the label is 1 and drops the 2-token zero bags."""
+        if getattr(dataset, "sample", -1) != -1 or not getattr(dataset, "train", True):
+            raise ValueError("DeviceSlideStore.from_dataset needs a SlideDataset(sample=-1, train=True): whole bags, every stain")
+        bags, ids = [], []
+        for i in range(len(dataset)):
+            item = dataset[i]
+            bags.append([f if int(lab) == 1 else None for f, lab in zip(item['feats'], item['modality_labels'])])
+            ids.append(item['slide_id'])
+        return cls(bags, ids, dataset.modalities, device, dtype=dtype)
+
+    def __len__(self):
+        return len(self.slide_ids)
+
+    @property
+    def n_bags(self) -> int:
+        return self.off_cpu.numel() - 1
+
+    def nbytes(self) -> int:
+        return self.rows.numel() * self.rows.element_size()
+
+    def _cases(self, case_indices) -> torch.Tensor:
+        idx = torch.as_tensor(case_indices, dtype=torch.int64).reshape(-1)
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= len(self)):
+            raise IndexError("DeviceSlideStore: case index outside [0, %d)" % len(self))
+        return idx
+
+    def sample(self, case_indices, n_tokens, counter, seed=None, return_indices=False):
+        """feats [B, M, n_tokens, D] fp32 on the device: SlideDataset.sample_n of every bag of the cases + collate, absent stains as
+        zeros.  A bag's draw is a function of (seed, counter, its stored bag id): a case draws the same rows whatever its batch mates.
+        The only upload is the batch's [B * M] int32 bag table.  return_indices: also idx [B, M, n_tokens] int32 (row inside the bag,
+        -1 for an absent stain).  seed None is seed 0; batches() passes its own seed."""
+        if self.device.type != "cuda":
+            raise RuntimeError("DeviceSlideStore.sample: the store lives on %s; the HIP kernel is the only backend (no CPU fallback)"
+                               % self.device)
+        idx = self._cases(case_indices)
+        B, M = idx.numel(), len(self.modalities)
+        bag = MF.h2d(self.bag_table.index_select(0, idx).reshape(-1), self.device)
+        res = MF.bag_sample(self.rows, self.off, bag, None, n_tokens, 0 if seed is None else seed, counter, return_indices)
+        if return_indices:
+            return res[0].view(B, M, n_tokens, self.dim), res[1].view(B, M, n_tokens)
+        return res.view(B, M, n_tokens, self.dim)
+
+    def bag_view(self, case: int, modality: int) -> Optional[torch.Tensor]:
+        """The stored rows of one bag as a zero-copy view of the store, None for an absent stain."""
+        g = int(self.bag_table[case, modality])
+        return None if g < 0 else self.rows[int(self.off_cpu[g]):int(self.off_cpu[g + 1])]
+
+    def batches(self, batch_size, n_tokens, shuffle=True, drop_last=False, seed=0, rank=0, world_size=1):
+        """Re-iterable over collate()-shaped dicts {'feats' [B, M, n_tokens, D] on the device, 'modality_labels' CPU float [B, M],
+        'slide_ids'}: the drop-in for DataLoader(SlideDataset(sample=n_tokens), collate_fn=collate)."""
+        return StoreBatches(self, batch_size, n_tokens, shuffle, drop_last, seed, rank, world_size, ragged=False)
+
+    def ragged_batches(self, batch_size, shuffle=True, drop_last=False, seed=0, rank=0, world_size=1):
+        """Re-iterable over ragged_collate()-shaped dicts {'bags', 'modality_labels', 'slide_ids'}: a present stain's bag is a zero-copy
+        view of the store, an absent stain's the dataset's [2, D] zero bag.  Needs an fp32 store (the model reads the views as they are)."""
+        if self.dtype != torch.float32:
+            raise ValueError("DeviceSlideStore.ragged_batches needs a float32 store (this one is %s): the bags are views of it" % self.dtype)
+        return StoreBatches(self, batch_size, None, shuffle, drop_last, seed, rank, world_size, ragged=True)
+
+    def _absent_bag(self) -> torch.Tensor:
+        if self._zero_bag is None:
+            self._zero_bag = torch.zeros(2, self.dim, dtype=torch.float32, device=self.device)
+        return self._zero_bag
+
+
+class StoreBatches:
+    """What DeviceSlideStore.batches / ragged_batches return.  plan(epoch) is host-only and a function of (seed, epoch, rank, world_size):
+    rank r owns the static shard r::world_size of the cases and shuffles inside it.  The draw counter of a batch is (epoch, batch
+    number), so a run resumed at an epoch redraws the same batches.  set_epoch(e) before each epoch, as with DistributedSampler."""
+
+    def __init__(self, store, batch_size, n_tokens, shuffle, drop_last, seed, rank, world_size, ragged):
+        if batch_size < 1 or world_size < 1 or not 0 <= rank < world_size:
+            raise ValueError("StoreBatches: batch_size >= 1 and 0 <= rank < world_size are required")
+        if not ragged and n_tokens < 1:
+            raise ValueError("StoreBatches: n_tokens >= 1 is required")
+        self.store, self.batch_size, self.n_tokens = store, int(batch_size), n_tokens
+        self.shuffle, self.drop_last, self.seed = bool(shuffle), bool(drop_last), int(seed)
+        self.rank, self.world_size, self.ragged = int(rank), int(world_size), bool(ragged)
+        self.epoch = 0
+
+    def set_epoch(self, epoch: int):
+        self.epoch = int(epoch)
+
+    def _shard(self) -> List[int]:
+        return list(range(self.rank, len(self.store), self.world_size))
+
+    def __len__(self):
+        n = len(self._shard())
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def plan(self, epoch: Optional[int] = None) -> List[List[int]]:
+        """The case indices of every batch of `epoch` (default: the current one), in order."""
+        epoch = self.epoch if epoch is None else int(epoch)
+        cases = self._shard()
+        if self.shuffle:
+            g = torch.Generator().manual_seed((self.seed * 1000003 + epoch) % (2 ** 63))
+            cases = [cases[i] for i in torch.randperm(len(cases), generator=g).tolist()]
+        out = [cases[i:i + self.batch_size] for i in range(0, len(cases), self.batch_size)]
+        if self.drop_last and out and len(out[-1]) < self.batch_size:
+            out.pop()
+        return out
+
+    def __iter__(self):
+        st, epoch = self.store, self.epoch
+        for batch_no, cases in enumerate(self.plan(epoch)):
+            out = {"modality_labels": st.modality_labels.index_select(0, torch.tensor(cases, dtype=torch.int64)),
+                   "slide_ids": [st.slide_ids[c] for c in cases]}
+            if self.ragged:
+                out["bags"] = [[st.bag_view(c, m) if int(st.bag_table[c, m]) >= 0 else st._absent_bag()
+                                for m in range(len(st.modalities))] for c in cases]
+            else:
+                out["feats"] = st.sample(cases, self.n_tokens, counter=(epoch << 32) | batch_no, seed=self.seed)
+            yield out
