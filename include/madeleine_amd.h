@@ -719,6 +719,33 @@ int mdl_bag_sample(const void* store, int dtype, int64_t row_stride, int64_t T_t
                    const int32_t* bag, const int64_t* key_id, int64_t R, int N, int D, uint64_t seed, uint64_t counter, float* out,
                    int32_t* idx_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * S2 -- pack a batch of bags of DIFFERENT lengths from the store of S1 into one dense token tensor, in one launch (ABI 26, additive).
+ * Replaces, for ragged batches (MADELEINE.forward_ragged; the reference can only stack equal-N bags, wsi_dataset.py:89-92), the
+ * torch.cat of the bags, the zero bags of absent stains (wsi_dataset.py:66) and the per-token bag map, and bounds a bag by a draw
+ * without replacement on the device.
+ *
+ * store, dtype, row_stride, T_total, off, n_bags, bag [R], key_id [R] or NULL, seed, counter: as in S1.
+ * cu [R + 1] (int64, device, ascending, cu[0] = 0 and cu[R] = T_out): output bag r is rows cu[r] .. cu[r + 1] - 1 of out; its length
+ *   L = cu[r + 1] - cu[r] is the caller's choice (the store passes min(n, max_tokens), and 2 for an absent stain).
+ * chunk_cu [R + 1] (int64, device): the prefix sum of ceil(L_r / 64), chunk_cu[0] = 0; n_chunks = chunk_cu[R] is the grid (one
+ *   workgroup per 64 rows of a bag; the workgroup finds its bag by binary search in chunk_cu).
+ * out [T_out, D] fp32, dense, 16-byte aligned.  row_bag [T_out] (int32) or NULL: r on every row of bag r.  idx_out [T_out] (int32) or
+ *   NULL: the row inside the stored bag, -1 where zeros were written.
+ *
+ * Per output bag r, with n = off[bag + 1] - off[bag]:
+ *   bag absent or invalid by S1's rule   L rows of zeros, idx -1
+ *   L >= n   the bag taken whole: rows t < n are stored rows t in stored order; rows t >= n (inconsistent tables only) zeros, idx -1
+ *   L <  n   row t is the stored row that mdl_bag_sample draws for token t with N = L under the same (seed, counter, key_id[r]) --
+ *            the same bits: L distinct rows, a uniformly random L-subset in uniformly random order
+ * Rows are copied bit for bit from an fp32 store and converted exactly from fp16 / bf16; access widths as in S1.  With consistent
+ * tables every element of out, row_bag and idx_out is written.  With inconsistent ones nothing outside the store is read and nothing at
+ * or beyond row T_out is written (a (bag, chunk) the tables do not agree on writes nothing).  No workspace, no atomics.
+ * MDL_E_UNSUPPORTED: R, T_out or n_chunks beyond int32.  R == 0, T_out == 0 or n_chunks == 0: nothing is launched. */
+int mdl_bag_pack(const void* store, int dtype, int64_t row_stride, int64_t T_total, const int64_t* off, int64_t n_bags,
+                 const int32_t* bag, const int64_t* key_id, const int64_t* cu, const int64_t* chunk_cu, int64_t R, int64_t n_chunks,
+                 int64_t T_out, int D, uint64_t seed, uint64_t counter, float* out, int32_t* row_bag, int32_t* idx_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

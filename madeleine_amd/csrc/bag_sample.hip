@@ -256,3 +256,191 @@ extern "C" int mdl_bag_sample(const void* store, int dtype, int64_t row_stride, 
             return launch<bf16_t>(store, row_stride, T_total, off, n_bags, bag, key_id, R, N, D, chunks, seed, counter, out, idx_out, s);
     }
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// bag_pack (S2 of the header) -- the variable-length form of the gather above: every bag at its own length L_r = cu[r + 1] - cu[r],
+// packed back to back into out [T_out, D], in ONE launch.  A bag that fits (L_r >= n) is taken whole and in stored order; a longer one
+// (L_r < n) is cut to L_r rows by exactly the draw of bag_sample_kernel with N := L_r -- the same keys, the same in-wave sort for
+// n <= 64, the same Feistel walk above -- so the rows and idx are bit-equal to mdl_bag_sample(N = L_r) under the same (seed, counter,
+// key_id).  The with-replacement regime cannot occur: a bag is never asked for more rows than it has.
+//
+// Work split.  chunk_cu [R + 1] is the prefix sum of ceil(L_r / 64): workgroup w finds its bag r, the last one with chunk_cu[r] <= w,
+// by binary search (wave-uniform, ceil(log2 R) reads of a table that stays in L2), owns rows 64 c .. 64 c + 63 of that bag with
+// c = w - chunk_cu[r], and then runs bag_sample's scheme: wave 0 leaves the 64 source rows in LDS, the four waves copy them.
+//
+// Bounds.  The store side is bag_sample's: a bag the tables cannot place inside [0, T_total) is written as an absent stain.  The output
+// side: a workgroup writes packed rows cu[r] + 64 c + i only, and only those inside [0, T_out); a (bag, chunk) that the two tables do
+// not agree on (cu[r] < 0, cu[r + 1] <= cu[r], c outside the bag) writes nothing.  r comes out of a search over [0, R), so every table
+// is read inside its R (+ 1) entries whatever chunk_cu holds.
+namespace mdl {
+namespace {
+
+// rows [0, ncopy) of the chunk from the store rows s_idx names (the copy loops of bag_sample_kernel), rows [ncopy, cnt) zeros
+template <class T, bool VEC>
+__device__ __forceinline__ void pack_rows(const T* __restrict__ bag_rows, int64_t row_stride, const int32_t* s_idx, int ncopy, int cnt, int D,
+                                          float* __restrict__ orow, int tid, int lane, int wave) {
+    if (VEC) {
+        constexpr int E = Vec<T>::E;
+        const int dv = D / E;                                   // 16-byte accesses of the store per row
+        int lpr = 1;                                            // lanes per row: a power of two, <= 64
+        while (lpr < dv && lpr < WAVE) lpr <<= 1;
+        const int sub = lane / lpr, c0 = lane - sub * lpr;
+        const int step = BS_WAVES * (WAVE / lpr);               // rows the workgroup covers per pass
+        for (int row0 = wave * (WAVE / lpr) + sub; row0 < ncopy; row0 += BS_INFLIGHT * step) {
+            const T* src[BS_INFLIGHT];
+            float* dst[BS_INFLIGHT];
+#pragma unroll
+            for (int j = 0; j < BS_INFLIGHT; ++j) {
+                const int row = row0 + j * step;
+                const int safe = row < ncopy ? row : row0;        // a row past the chunk: addresses of a valid one, never used
+                src[j] = bag_rows + (int64_t)s_idx[safe] * row_stride;
+                dst[j] = orow + (int64_t)safe * D;
+            }
+            for (int c = c0; c < dv; c += lpr) {
+                typename Vec<T>::Raw v[BS_INFLIGHT];
+#pragma unroll
+                for (int j = 0; j < BS_INFLIGHT; ++j)
+                    if (row0 + j * step < ncopy) v[j] = Vec<T>::ld(src[j] + c * E);
+#pragma unroll
+                for (int j = 0; j < BS_INFLIGHT; ++j)
+                    if (row0 + j * step < ncopy) Vec<T>::st(dst[j] + c * E, v[j]);
+            }
+        }
+    } else {                                                    // any D, any stride: element-wise
+        for (int row = wave; row < ncopy; row += BS_WAVES) {
+            const T* sa = bag_rows + (int64_t)s_idx[row] * row_stride;
+            float* da = orow + (int64_t)row * D;
+            for (int c = lane; c < D; c += WAVE) da[c] = Vec<T>::up(sa[c]);
+        }
+    }
+    float* zrow = orow + (int64_t)ncopy * D;
+    const int64_t total = (int64_t)(cnt - ncopy) * D;
+    if (VEC) {                                                  // D is a multiple of 4 and out is 16-byte aligned: so is every row
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        for (int64_t e = (int64_t)tid * 4; e < total; e += BS_THREADS * 4) st4(zrow + e, z);
+    } else {
+        for (int64_t e = tid; e < total; e += BS_THREADS) zrow[e] = 0.f;
+    }
+}
+
+template <class T, bool VEC>
+__global__ __launch_bounds__(BS_THREADS) void bag_pack_kernel(const T* __restrict__ store, int64_t row_stride, int64_t T_total,
+                                                              const int64_t* __restrict__ off, int64_t n_bags,
+                                                              const int32_t* __restrict__ bag, const int64_t* __restrict__ key_id,
+                                                              const int64_t* __restrict__ cu, const int64_t* __restrict__ chunk_cu, int R,
+                                                              int64_t T_out, int D, uint64_t seed, uint64_t counter,
+                                                              float* __restrict__ out, int32_t* __restrict__ row_bag,
+                                                              int32_t* __restrict__ idx_out) {
+    __shared__ int32_t s_idx[BS_TOK];
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int64_t w = blockIdx.x;
+    int lo = 0, hi = R - 1;                                     // the last r of [0, R) with chunk_cu[r] <= w (bags of no rows are passed over)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (chunk_cu[mid] <= w) lo = mid; else hi = mid - 1;
+    }
+    const int r = lo;
+    const int64_t p0 = cu[r], p1 = cu[r + 1], c = w - chunk_cu[r];
+    if (p0 < 0 || p0 >= T_out || p1 <= p0 || c < 0 || c > (T_out >> 6)) return;      // uniform over the workgroup, as all that follows
+    const int64_t L = p1 - p0, t0 = c * BS_TOK;                 // no overflow: 0 <= p0 < p1, 0 <= t0 <= T_out < 2^31
+    int64_t lim = L - t0;
+    if (T_out - p0 - t0 < lim) lim = T_out - p0 - t0;
+    if (lim < 1) return;
+    const int cnt = lim < BS_TOK ? (int)lim : BS_TOK;           // packed rows of this workgroup, all inside [0, T_out)
+
+    const int g = bag[r];
+    int64_t base = 0, n64 = 0;
+    if (g >= 0 && g < n_bags) {
+        base = off[g];
+        n64 = off[g + 1] - base;
+        if (base < 0 || n64 < 1 || n64 > 0x7FFFFFFF || base > T_total - n64) n64 = 0;
+    }
+    const uint32_t n = (uint32_t)n64;                           // 0: an absent stain
+    const int64_t prow = p0 + t0;
+
+    int ncopy = 0;                                              // rows of the chunk that come from the store; the others are zeros
+    if (n != 0 && L >= n64) {                                   // the bag taken whole: row t is stored row t
+        const int64_t left = n64 - t0;
+        ncopy = left < 0 ? 0 : left < cnt ? (int)left : cnt;
+        if (wave == 0) s_idx[lane] = (int32_t)t0 + lane;
+    } else if (n != 0) {                                        // L < n: bag_sample_kernel's draw without replacement, N = L
+        ncopy = cnt;
+        if (wave == 0) {
+            const RowKey k = row_key(seed, counter, key_id != nullptr ? (uint64_t)key_id[r] : (uint64_t)(int64_t)g);
+            const int N = (int)L;
+            if (n <= (uint32_t)WAVE) {                          // L < n <= 64: one chunk (t0 == 0), random-key sort in the wave
+                const uint32_t h = token_hash((uint32_t)lane, k);
+                int rank = 0;
+                for (uint32_t j = 0; j < n; ++j) {
+                    const uint32_t hj = (uint32_t)__shfl((int)h, (int)j, WAVE);
+                    rank += (hj < h || (hj == h && j < (uint32_t)lane)) ? 1 : 0;
+                }
+                if ((uint32_t)lane < n && rank < N) s_idx[rank] = lane;
+            } else {                                            // keyed bijection of [0, n), cycle walking
+                int bits = 32 - __builtin_clz(n - 1);
+                bits += bits & 1;
+                const int half = bits >> 1;
+                uint32_t y = (uint32_t)t0 + (uint32_t)lane;
+                if (lane < cnt) {
+                    do {
+                        y = feistel(y, half, k);
+                    } while (y >= n);                           // terminates: see the comment at the head of the file
+                }
+                s_idx[lane] = (int32_t)y;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < cnt) {
+        if (idx_out != nullptr) idx_out[prow + tid] = tid < ncopy ? s_idx[tid] : -1;
+        if (row_bag != nullptr) row_bag[prow + tid] = r;
+    }
+    pack_rows<T, VEC>(store + base * row_stride, row_stride, s_idx, ncopy, cnt, D, out + prow * D, tid, lane, wave);
+}
+
+template <class T>
+int launch_pack(const void* store, int64_t row_stride, int64_t T_total, const int64_t* off, int64_t n_bags, const int32_t* bag,
+                const int64_t* key_id, const int64_t* cu, const int64_t* chunk_cu, int R, int64_t n_chunks, int64_t T_out, int D,
+                uint64_t seed, uint64_t counter, float* out, int32_t* row_bag, int32_t* idx_out, hipStream_t stream) {
+    const bool vec = D % Vec<T>::E == 0 && row_stride % Vec<T>::E == 0;
+    const dim3 grid((unsigned)n_chunks), block(BS_THREADS);
+    if (vec)
+        hipLaunchKernelGGL((bag_pack_kernel<T, true>), grid, block, 0, stream, reinterpret_cast<const T*>(store), row_stride, T_total, off,
+                           n_bags, bag, key_id, cu, chunk_cu, R, T_out, D, seed, counter, out, row_bag, idx_out);
+    else
+        hipLaunchKernelGGL((bag_pack_kernel<T, false>), grid, block, 0, stream, reinterpret_cast<const T*>(store), row_stride, T_total, off,
+                           n_bags, bag, key_id, cu, chunk_cu, R, T_out, D, seed, counter, out, row_bag, idx_out);
+    MDL_LAUNCH_CHECK();
+    return MDL_OK;
+}
+
+}  // namespace
+}  // namespace mdl
+
+extern "C" int mdl_bag_pack(const void* store, int dtype, int64_t row_stride, int64_t T_total, const int64_t* off, int64_t n_bags,
+                            const int32_t* bag, const int64_t* key_id, const int64_t* cu, const int64_t* chunk_cu, int64_t R,
+                            int64_t n_chunks, int64_t T_out, int D, uint64_t seed, uint64_t counter, float* out, int32_t* row_bag,
+                            int32_t* idx_out, void* stream) {
+    if (store == nullptr || off == nullptr || bag == nullptr || cu == nullptr || chunk_cu == nullptr || out == nullptr) return MDL_E_ARG;
+    if (R < 0 || n_chunks < 0 || T_out < 0 || D < 1 || T_total < 0 || n_bags < 0 || row_stride < D) return MDL_E_ARG;
+    if (dtype != MDL_STORE_F32 && dtype != MDL_STORE_F16 && dtype != MDL_STORE_BF16) return MDL_E_ARG;
+    if (!host_aligned16(store) || !host_aligned16(out)) return MDL_E_ALIGN;
+    if ((reinterpret_cast<uintptr_t>(off) & 7u) || (reinterpret_cast<uintptr_t>(bag) & 3u) || (reinterpret_cast<uintptr_t>(key_id) & 7u) ||
+        (reinterpret_cast<uintptr_t>(cu) & 7u) || (reinterpret_cast<uintptr_t>(chunk_cu) & 7u) ||
+        (reinterpret_cast<uintptr_t>(row_bag) & 3u) || (reinterpret_cast<uintptr_t>(idx_out) & 3u))
+        return MDL_E_ALIGN;
+    if (R > 0x7FFFFFFF || T_out > 0x7FFFFFFF || n_chunks > 0x7FFFFFFF) return MDL_E_UNSUPPORTED;
+    if (R == 0 || T_out == 0 || n_chunks == 0) return MDL_OK;
+    hipStream_t s = (hipStream_t)stream;
+    switch (dtype) {
+        case MDL_STORE_F32:
+            return launch_pack<float>(store, row_stride, T_total, off, n_bags, bag, key_id, cu, chunk_cu, (int)R, n_chunks, T_out, D, seed,
+                                      counter, out, row_bag, idx_out, s);
+        case MDL_STORE_F16:
+            return launch_pack<_Float16>(store, row_stride, T_total, off, n_bags, bag, key_id, cu, chunk_cu, (int)R, n_chunks, T_out, D, seed,
+                                         counter, out, row_bag, idx_out, s);
+        default:
+            return launch_pack<bf16_t>(store, row_stride, T_total, off, n_bags, bag, key_id, cu, chunk_cu, (int)R, n_chunks, T_out, D, seed,
+                                       counter, out, row_bag, idx_out, s);
+    }
+}

@@ -1722,3 +1722,43 @@ def bag_sample(store_rows, off, bag, key_id, n_tokens, seed, counter, return_ind
               store_rows.shape[0], off, off.numel() - 1, bag, key_id, R, N, D, int(seed) & _U64, int(counter) & _U64, out, idx, _stream(),
               unsupported=("bag_sample: %d output rows of %d tokens exceed the int32 launch geometry", R, N))
     return (out, idx) if return_indices else out
+
+
+# ---- S2: pack a batch of bags of different lengths from the store into one dense token tensor (mdl_bag_pack) ----
+def bag_pack(store_rows, off, bag, key_id, cu, chunk_cu, n_rows, n_chunks, seed, counter, return_indices=False):
+    """tokens [n_rows, D] fp32, row_bag [n_rows] int32 <- output bag r is rows cu[r] .. cu[r + 1] - 1: stored bag bag[r] taken whole
+    and in stored order when it has at most L_r = cu[r + 1] - cu[r] rows, L_r of its rows drawn without replacement when it is longer
+    (the rows bag_sample draws with n_tokens = L_r under the same seed, counter and key_id), zeros where bag[r] == -1.  row_bag is r
+    on every row of bag r.  cu, chunk_cu int64 [R + 1] on the device (chunk_cu: the prefix sum of ceil(L_r / 64)); n_rows = cu[R] and
+    n_chunks = chunk_cu[R] as host integers.  The other arguments, the checks and the byte accounting are bag_sample's.  No autograd,
+    no host read, no allocation beyond the outputs.  return_indices: also idx [n_rows] int32 (row inside the bag, -1: zeros)."""
+    if store_rows.dim() != 2 or store_rows.dtype not in STORE_DTYPES or (store_rows.shape[1] > 1 and store_rows.stride(1) != 1):
+        raise RuntimeError("madeleine_amd: store_rows must be [T, D] float32 / float16 / bfloat16 with unit column stride")
+    if not store_rows.is_cuda:
+        raise RuntimeError("madeleine_amd: store_rows must live on a ROCm device (got %s); there is no CPU fallback" % store_rows.device)
+    _require(off, "off", torch.int64)
+    _require(bag, "bag", torch.int32)
+    _require(cu, "cu", torch.int64)
+    _require(chunk_cu, "chunk_cu", torch.int64)
+    if key_id is not None:
+        _require(key_id, "key_id", torch.int64)
+        if key_id.numel() != bag.numel():
+            raise RuntimeError("madeleine_amd: key_id and bag must have one entry per output bag")
+    if off.dim() != 1 or off.numel() < 1:
+        raise RuntimeError("madeleine_amd: off must be [n_bags + 1]")
+    R, T, D = bag.numel(), int(n_rows), store_rows.shape[1]
+    if cu.numel() != R + 1 or chunk_cu.numel() != R + 1:
+        raise RuntimeError("madeleine_amd: cu and chunk_cu must be [R + 1] = [%d]" % (R + 1))
+    if T < 0 or n_chunks < 0:
+        raise RuntimeError("madeleine_amd: bag_pack needs n_rows >= 0 and n_chunks >= 0")
+    out = torch.empty(T, D, device=store_rows.device, dtype=torch.float32)
+    row_bag = torch.empty(T, device=store_rows.device, dtype=torch.int32)
+    idx = torch.empty(T, device=store_rows.device, dtype=torch.int32) if return_indices else None
+    if R == 0 or T == 0:       # nothing to pack (an empty tensor has no address to pass)
+        return (out, row_bag, idx) if return_indices else (out, row_bag)
+    with _timed("bag_pack", ("byte", T * D * (4.0 + store_rows.element_size()))):
+        _call("mdl_bag_pack", store_rows, STORE_DTYPES[store_rows.dtype], store_rows.stride(0) if store_rows.shape[0] > 1 else D,
+              store_rows.shape[0], off, off.numel() - 1, bag, key_id, cu, chunk_cu, R, int(n_chunks), T, D, int(seed) & _U64,
+              int(counter) & _U64, out, row_bag, idx, _stream(),
+              unsupported=("bag_pack: %d bags of %d rows in all exceed the int32 launch geometry", R, T))
+    return (out, row_bag, idx) if return_indices else (out, row_bag)

@@ -537,12 +537,35 @@ class MADELEINE(nn.Module):
         modality_labels [B, M] (the batch's own tensor): a bag labelled 0 (an absent stain, which the dataset fills with a 2-token zero
         bag and no loss reads) may be shorter than n_loss_tokens; its token rows past its length are zeros."""
         bs, n_mod = len(bags), len(bags[0])
+        flat = [bags[b][m] for b in range(bs) for m in range(n_mod)]          # case-major rows, like .view(bs*n_mod,...)
+        lens = [int(x.shape[0]) for x in flat]
+        n_loss_tokens = self._check_bag_lens(lens, bs, n_mod, n_loss_tokens, modality_labels)
+        x = torch.cat([f.to(device) for f in flat], dim=0)                     # packed [T, D]
+        return self._forward_packed(x, lens, None, None, bs, n_mod, device, n_loss_tokens, n_views)
+
+    def forward_packed(self, packed, device, n_loss_tokens=None, n_views=1, modality_labels=None):
+        """forward_ragged on a batch that is already packed (DeviceSlideStore.pack / packed_batches: `packed` has tokens [T, D],
+        cu_seqlens [R + 1] on the device, the host tuple lens and row_bag [T], R = B * M bags, case-major): no list of bags, no
+        torch.cat, and the stain-encoding row map is packed.row_bag -- nothing of the size of the tokens is built on the host or
+        uploaded.  Same semantics, arguments and outputs as forward_ragged."""
+        lens = [int(n) for n in packed.lens]
+        n_mod = len(self.modalities)
+        if not lens or len(lens) % n_mod:
+            raise ValueError("a packed batch needs B * M bags for M = %d modalities (got %d)" % (n_mod, len(lens)))
+        bs = len(lens) // n_mod
+        n_loss_tokens = self._check_bag_lens(lens, bs, n_mod, n_loss_tokens, modality_labels)
+        if packed.tokens.dim() != 2 or packed.tokens.shape[0] != sum(lens) or packed.cu_seqlens.numel() != len(lens) + 1:
+            raise ValueError("a packed batch needs tokens [sum(lens), D] and cu_seqlens [len(lens) + 1]")
+        return self._forward_packed(packed.tokens.to(device), lens, packed.cu_seqlens.to(device), packed.row_bag.to(device), bs, n_mod,
+                                    device, n_loss_tokens, n_views)
+
+    @staticmethod
+    def _check_bag_lens(lens, bs, n_mod, n_loss_tokens, modality_labels):
+        """The ragged routes' checks of the bag lengths; returns n_loss_tokens (its default when None)."""
         if n_loss_tokens is None:
             # GOT draws token indices randperm(k)[:256] with k = the number of participating CASES (reference quirk, loss.py:282,
             # SURVEY.md section 8(a) G0): indices reach k - 1, so a batch of more than 256 cases needs that many tokens kept
             n_loss_tokens = max(256, bs)
-        flat = [bags[b][m] for b in range(bs) for m in range(n_mod)]          # case-major rows, like .view(bs*n_mod,...)
-        lens = [int(x.shape[0]) for x in flat]
         present = [True] * len(lens)
         if modality_labels is not None:
             present = [bool(v) for v in torch.as_tensor(modality_labels).detach().cpu().reshape(-1).tolist()]
@@ -554,19 +577,25 @@ class MADELEINE(nn.Module):
                              "indices up to min(batch, 256) - 1 of every bag" % (n_loss_tokens, min(short)))
         if min(lens) < 1:
             raise ValueError("every bag needs at least one token (an absent stain's bag included)")
+        return n_loss_tokens
+
+    def _forward_packed(self, x, lens, cu_d, row_bag, bs, n_mod, device, n_loss_tokens, n_views):
+        """The body shared by forward_ragged and forward_packed: x [T, D] the packed tokens of the bs * n_mod bags of `lens` rows,
+        cu_d / row_bag their device tables (None: built from lens and uploaded)."""
         rviews = ragged_view_plan(lens) if n_views != 1 else None     # (numpy's RNG, as the reference's view draw)
-        cu = torch.zeros(len(flat) + 1, dtype=torch.int64)
+        cu = torch.zeros(len(lens) + 1, dtype=torch.int64)
         cu[1:] = torch.cumsum(torch.tensor(lens, dtype=torch.int64), 0)
-        x = torch.cat([f.to(device) for f in flat], dim=0)                     # packed [T, D]
         stain = None
         if self.stain_encoding:
             row_stain = torch.arange(bs * n_mod) // bs                          # the train-branch quirk
             # one embedding row per BAG; the bag of every packed token as an int32 map (folded into the first Linear on the split engine,
             # gathered + concatenated by the other engines: ABMILEmbedder.embed_tokens_headmajor)
-            bag_of_tok = MF.h2d(torch.repeat_interleave(torch.arange(bs * n_mod, dtype=torch.int32), torch.tensor(lens)), device)
+            bag_of_tok = row_bag if row_bag is not None else \
+                MF.h2d(torch.repeat_interleave(torch.arange(bs * n_mod, dtype=torch.int32), torch.tensor(lens)), device)
             stain = (self.embedding(MF.h2d(row_stain, device)), bag_of_tok, None)
         emb = self.wsi_embedders
-        cu_d = MF.h2d(cu, device)
+        if cu_d is None:
+            cu_d = MF.h2d(cu, device)
         if stain is not None:
             stain = (stain[0], stain[1], cu_d)
         pos = torch.arange(n_loss_tokens).unsqueeze(0)
@@ -609,6 +638,8 @@ class MADELEINE(nn.Module):
         return all_embeddings, all_token_embeddings
 
     def forward(self, data, device, train=True, n_views=1, custom_stain_idx=None, return_attention=False):
+        if 'packed' in data and 'feats' not in data:  # a ragged batch packed on the device (DeviceSlideStore.packed_batches)
+            return self.forward_packed(data['packed'], device, n_views=n_views, modality_labels=data.get('modality_labels'))
         if 'bags' in data and 'feats' not in data:   # ragged extension (see forward_ragged); keeps DDP's forward hook path
             return self.forward_ragged(data['bags'], device, n_views=n_views, modality_labels=data.get('modality_labels'))
         all_wsi_feats = data['feats'].to(device)

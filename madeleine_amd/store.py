@@ -1,5 +1,8 @@
 """Device-resident slide store: the patch features of a whole pretraining cohort loaded ONCE into one device tensor, and every step's
 `[B, M, N, D]` batch drawn from it on the device by one kernel (functional.bag_sample -> mdl_bag_sample, csrc/bag_sample.hip).
+Ragged batches -- every bag at its own length, optionally cut to max_tokens rows drawn without replacement -- come packed out of the
+same store by one launch of its variable-length form (pack / packed_batches: functional.bag_pack -> mdl_bag_pack), from a store of
+any dtype.
 
 Replaces, for a cohort that fits in HBM, the reference's input side (madeleine/datasets/wsi_dataset.py): SlideDataset.__getitem__
 re-reads every stain's h5 file for every item of every epoch, draws `sample` rows on the host and collate stacks them, and the stacked
@@ -14,7 +17,7 @@ The batches iterables yield exactly what collate() / ragged_collate() yield (`fe
 MADELEINE.forward take them unchanged.  There is no CPU fallback: a store may be BUILT on the CPU (packing logic, tests), sampling from
 it raises.
 """
-from typing import List, Optional
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -22,6 +25,17 @@ from . import functional as MF
 
 FP16_MAX = 65504.0
 _MAX_BAG_ROWS = 2 ** 31 - 1
+ABSENT_BAG_ROWS = 2        # the dataset's zero bag of an absent stain (wsi_dataset.py:66)
+
+
+class PackedBags(NamedTuple):
+    """A ragged batch in packed form (DeviceSlideStore.pack): bag r = (case, modality), case-major, is rows cu_seqlens[r] ..
+    cu_seqlens[r + 1] - 1 of tokens.  MADELEINE.forward takes it under the key 'packed'."""
+    tokens: torch.Tensor                 # [T, D] fp32, on the device
+    cu_seqlens: torch.Tensor             # [R + 1] int64, on the device
+    lens: Tuple[int, ...]                # the R bag lengths, on the host
+    row_bag: torch.Tensor                # [T] int32: the bag r of every row
+    idx: Optional[torch.Tensor]          # [T] int32: the row inside the stored bag, -1 where zeros were written; None unless asked for
 
 
 class DeviceSlideStore:
@@ -67,7 +81,8 @@ class DeviceSlideStore:
         self.bag_table = table
         self.modality_labels = (table >= 0).float()
         self.off_cpu = torch.zeros(len(lens) + 1, dtype=torch.int64)
-        self.off_cpu[1:] = torch.cumsum(torch.tensor(lens, dtype=torch.int64), 0)
+        self.bag_lens_cpu = torch.tensor(lens, dtype=torch.int64)
+        self.off_cpu[1:] = torch.cumsum(self.bag_lens_cpu, 0)
         total = int(self.off_cpu[-1])
         nbytes = total * D * torch.empty(0, dtype=dtype).element_size()
         if self.device.type == "cuda":
@@ -164,6 +179,51 @@ class DeviceSlideStore:
             raise ValueError("DeviceSlideStore.ragged_batches needs a float32 store (this one is %s): the bags are views of it" % self.dtype)
         return StoreBatches(self, batch_size, None, shuffle, drop_last, seed, rank, world_size, ragged=True)
 
+    def _pack_plan(self, case_indices, max_tokens):
+        """(bag [R] int32, lens [R] int64) of the packed form of the cases, on the host: case-major, then modality-major."""
+        if max_tokens is not None and max_tokens < 1:
+            raise ValueError("DeviceSlideStore: max_tokens must be at least 1 (got %s)" % max_tokens)
+        bag = self.bag_table.index_select(0, self._cases(case_indices)).reshape(-1)
+        lens = self.bag_lens_cpu.index_select(0, bag.clamp(min=0).long())
+        if max_tokens is not None:
+            lens = lens.clamp(max=int(max_tokens))
+        return bag, torch.where(bag >= 0, lens, torch.full_like(lens, ABSENT_BAG_ROWS))
+
+    def pack_lens(self, case_indices, max_tokens=None) -> List[int]:
+        """The bag lengths of pack(case_indices, max_tokens), case-major then modality-major: a present bag's rows (at most max_tokens
+        of them when a cap is given), 2 for an absent stain (the dataset's zero bag).  Host only."""
+        return self._pack_plan(case_indices, max_tokens)[1].tolist()
+
+    def pack(self, case_indices, max_tokens=None, counter=0, seed=None, return_indices=False) -> PackedBags:
+        """The ragged batch of the cases, packed: every present bag whole and in stored order, or -- when it has more than max_tokens
+        rows -- max_tokens of its rows drawn without replacement (the rows sample(..., max_tokens, counter, seed) draws for it); an
+        absent stain as 2 rows of zeros.  One launch, from a store of any dtype; the only upload is one O(R) table (cu_seqlens, the
+        chunk table of the launch and the bags); no host read and no host work per token."""
+        if self.device.type != "cuda":
+            raise RuntimeError("DeviceSlideStore.pack: the store lives on %s; the HIP kernel is the only backend (no CPU fallback)"
+                               % self.device)
+        bag, lens = self._pack_plan(case_indices, max_tokens)
+        R = bag.numel()
+        host = torch.zeros(2 * (R + 1) + (R + 1) // 2, dtype=torch.int64)        # cu | chunk_cu | bag (int32, two to a word)
+        torch.cumsum(lens, 0, out=host[1:R + 1])
+        torch.cumsum((lens + 63) // 64, 0, out=host[R + 2:2 * R + 2])
+        host[2 * R + 2:].view(torch.int32)[:R] = bag
+        T, n_chunks = int(host[R]), int(host[2 * R + 1])
+        table = MF.h2d(host, self.device)
+        cu = table[:R + 1]
+        res = MF.bag_pack(self.rows, self.off, table[2 * R + 2:].view(torch.int32)[:R], None, cu, table[R + 1:2 * R + 2], T, n_chunks,
+                          0 if seed is None else seed, counter, return_indices)
+        return PackedBags(res[0], cu, tuple(lens.tolist()), res[1], res[2] if return_indices else None)
+
+    def packed_batches(self, batch_size, max_tokens=None, shuffle=True, drop_last=False, seed=0, rank=0, world_size=1):
+        """Re-iterable over {'packed': PackedBags, 'modality_labels', 'slide_ids'}: the ragged batches of ragged_batches() in packed
+        form, from a store of any dtype, every bag cut to at most max_tokens rows.  Plan, sharding, set_epoch and the draw counter are
+        those of batches()."""
+        if max_tokens is not None and max_tokens < 1:
+            raise ValueError("DeviceSlideStore: max_tokens must be at least 1 (got %s)" % max_tokens)
+        return StoreBatches(self, batch_size, None, shuffle, drop_last, seed, rank, world_size, ragged=True, packed=True,
+                            max_tokens=max_tokens)
+
     def _absent_bag(self) -> torch.Tensor:
         if self._zero_bag is None:
             self._zero_bag = torch.zeros(2, self.dim, dtype=torch.float32, device=self.device)
@@ -171,11 +231,13 @@ class DeviceSlideStore:
 
 
 class StoreBatches:
-    """What DeviceSlideStore.batches / ragged_batches return.  plan(epoch) is host-only and a function of (seed, epoch, rank, world_size):
-    rank r owns the static shard r::world_size of the cases and shuffles inside it.  The draw counter of a batch is (epoch, batch
-    number), so a run resumed at an epoch redraws the same batches.  set_epoch(e) before each epoch, as with DistributedSampler."""
+    """What DeviceSlideStore.batches / ragged_batches / packed_batches return.  plan(epoch) is host-only and a function of (seed,
+    epoch, rank, world_size): rank r owns the static shard r::world_size of the cases and shuffles inside it.  The draw counter of a
+    batch is (epoch, batch number), so a run resumed at an epoch redraws the same batches.  set_epoch(e) before each epoch, as with
+    DistributedSampler."""
 
-    def __init__(self, store, batch_size, n_tokens, shuffle, drop_last, seed, rank, world_size, ragged):
+    def __init__(self, store, batch_size, n_tokens, shuffle, drop_last, seed, rank, world_size, ragged, packed=False,
+                 max_tokens=None):
         if batch_size < 1 or world_size < 1 or not 0 <= rank < world_size:
             raise ValueError("StoreBatches: batch_size >= 1 and 0 <= rank < world_size are required")
         if not ragged and n_tokens < 1:
@@ -183,6 +245,7 @@ class StoreBatches:
         self.store, self.batch_size, self.n_tokens = store, int(batch_size), n_tokens
         self.shuffle, self.drop_last, self.seed = bool(shuffle), bool(drop_last), int(seed)
         self.rank, self.world_size, self.ragged = int(rank), int(world_size), bool(ragged)
+        self.packed, self.max_tokens = bool(packed), max_tokens
         self.epoch = 0
 
     def set_epoch(self, epoch: int):
@@ -212,7 +275,9 @@ class StoreBatches:
         for batch_no, cases in enumerate(self.plan(epoch)):
             out = {"modality_labels": st.modality_labels.index_select(0, torch.tensor(cases, dtype=torch.int64)),
                    "slide_ids": [st.slide_ids[c] for c in cases]}
-            if self.ragged:
+            if self.packed:
+                out["packed"] = st.pack(cases, self.max_tokens, counter=(epoch << 32) | batch_no, seed=self.seed)
+            elif self.ragged:
                 out["bags"] = [[st.bag_view(c, m) if int(st.bag_table[c, m]) >= 0 else st._absent_bag()
                                 for m in range(len(st.modalities))] for c in cases]
             else:

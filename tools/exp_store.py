@@ -14,13 +14,27 @@ x 512 fp32, N = 4096 tokens per bag), both with device events:
        const   one constant device-resident batch (what bench.py times)
      median / min / max per step, and the two differences the store is judged by.
 
-Usage: python tools/exp_store.py [--rows 20000] [--launches 20] [--steps 20] [--round-steps 5] [--workers 6] [--out FILE]"""
+--pack runs the packed ragged route instead, at one rank of config 5's shape (32 cases x 5 stains, bag lengths U{1024..16384}, D = 768,
+stain-encoding tokens), with device events after warm-up:
+  3. the pack kernel: DeviceSlideStore.pack of the whole cohort, every bag whole (contiguous reads) and cut to --cap rows (drawn rows),
+     next to DeviceSlideStore.sample of N = 8192 tokens per bag (bags shorter than that are drawn with replacement) and of N = 1024
+     (every row distinct) from the same store in the same loop, as achieved bytes/s over T * D * (4 + element size), for an fp32 and
+     a bf16 store;
+  4. the path pack replaces, for the same batch on the fp32 store: the torch.cat of the 160 bag views plus the host-built per-token
+     bag map and its upload, against pack -- both by the host clock around a device synchronise (they differ in host work), and the
+     cat alone by device events;
+  5. the config-5 training step (InfoNCE + GOT, stain encoding) fed by packed_batches against the same step fed by ragged_batches on
+     the fp32 store, in alternating rounds.
+
+Usage: python tools/exp_store.py [--rows 20000] [--launches 20] [--steps 20] [--round-steps 5] [--workers 6] [--out FILE]
+       python tools/exp_store.py --pack [--launches 20] [--steps 12] [--round-steps 3] [--cap 4096] [--skip-step] [--out FILE]"""
 import argparse
 import json
 import os
 import shutil
 import statistics
 import sys
+import time
 from types import SimpleNamespace
 
 import torch
@@ -28,6 +42,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench as BN  # noqa: E402
 from madeleine_amd import MADELEINE, DeviceSlideStore, InfoNCE, calculate_losses  # noqa: E402
+from madeleine_amd import functional as MF  # noqa: E402
 from madeleine_amd.data import DevicePrefetcher, collate  # noqa: E402
 
 
@@ -75,6 +90,149 @@ def stats(v):
     return {"median": statistics.median(v), "min": min(v), "max": max(v)}
 
 
+def pack_leg(a, dev):
+    """Measurements 3-5 of the module docstring.  Returns (lines, results)."""
+    B, M, _N, D, _got, stain = BN.CONFIGS["c5"]
+    mods = BN.MODS5[:M]
+    lens = torch.randint(1024, 16385, (B, M), generator=torch.Generator().manual_seed(4321))       # bench.py's config-5 lengths
+    base = torch.randn(16384, D, generator=torch.Generator().manual_seed(7))
+    bags = [[base[:int(lens[b, m])] * (1.0 + 0.01 * (b * M + m)) for m in range(M)] for b in range(B)]
+    ids = ["case%05d" % i for i in range(B)]
+    cases, R, T = list(range(B)), B * M, int(lens.sum())
+    n_dense = 8192
+    lines, res = [], {"geometry": {"cases": B, "stains": M, "rows": T, "D": D, "lengths": "U{1024..16384}", "cap": a.cap,
+                                   "dense_tokens": n_dense}}
+
+    # ---- 3. the kernel
+    res["kernel"] = {}
+    for dtype in (torch.float32, torch.bfloat16):
+        st = DeviceSlideStore(bags, ids, mods, dev, dtype=dtype)
+        esz = st.rows.element_size()
+        T_cap = sum(st.pack_lens(cases, a.cap))
+        # sample at N = 8192 redraws rows of the bags shorter than that (with replacement: repeats are served by the caches, not by HBM);
+        # sample_distinct at N = 1024, the shortest possible bag, reads every row once, as the packs do
+        work = {"pack_whole": T * D * (4 + esz), "pack_capped": T_cap * D * (4 + esz), "sample": R * n_dense * D * (4 + esz),
+                "sample_distinct": R * 1024 * D * (4 + esz)}
+        calls = {"pack_whole": lambda i: st.pack(cases, None, counter=i), "pack_capped": lambda i: st.pack(cases, a.cap, counter=i),
+                 "sample": lambda i: st.sample(cases, n_dense, counter=i), "sample_distinct": lambda i: st.sample(cases, 1024, counter=i)}
+        for f in calls.values():
+            for i in range(3):
+                f(i)
+        times = {k: [] for k in calls}
+        for i in range(a.launches):
+            order = sorted(calls) if i % 2 == 0 else sorted(calls, reverse=True)
+            for k in ("pack_whole", "sample"):           # untimed, ~3 ms of device work: the host runs ahead of the device, so the
+                del_me = calls[k](50 + i)                # first timed call of the sequence holds no launch gap either
+                del del_me
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(order) + 1)]
+            ev[0].record()
+            for j, k in enumerate(order):
+                out = calls[k](100 + i)
+                ev[j + 1].record()
+                del out
+            ev[-1].synchronize()
+            for j, k in enumerate(order):
+                times[k].append(ev[j].elapsed_time(ev[j + 1]))
+        res["kernel"][str(dtype)] = {k: {"ms": stats(v), "payload_bytes": work[k], "TBps_median": work[k] / statistics.median(v) * 1e-9}
+                                     for k, v in times.items()}
+        for k, v in sorted(times.items()):
+            lines.append("%-12s %-14s median %.3f ms (min %.3f max %.3f) = %.2f TB/s over %.2f GB"
+                         % (k, str(dtype), statistics.median(v), min(v), max(v), work[k] / statistics.median(v) * 1e-9, work[k] * 1e-9))
+        r = res["kernel"][str(dtype)]
+        r["pack_whole_over_sample"] = r["pack_whole"]["TBps_median"] / r["sample"]["TBps_median"]
+        r["pack_whole_over_sample_distinct"] = r["pack_whole"]["TBps_median"] / r["sample_distinct"]["TBps_median"]
+        lines.append("  pack_whole / sample = %.3f, pack_whole / sample_distinct = %.3f (bytes/s, same run)"
+                     % (r["pack_whole_over_sample"], r["pack_whole_over_sample_distinct"]))
+        if dtype == torch.float32:
+            st32 = st
+    st = st32
+
+    # ---- 4. the path pack replaces: torch.cat of the views + the per-token bag map built on the host and uploaded
+    def parent_path():
+        views = [st.bag_view(c, m) for c in cases for m in range(M)]
+        x = torch.cat(views, dim=0)
+        n = torch.tensor([int(v.shape[0]) for v in views])
+        return x, MF.h2d(torch.repeat_interleave(torch.arange(R, dtype=torch.int32), n), dev)
+
+    def host_clock(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = f()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        del out
+        return (t1 - t0) * 1e3
+    for _ in range(3):
+        parent_path()
+        st.pack(cases)
+    wall = {"cat_and_row_map": [], "pack": []}
+    for i in range(a.launches):
+        for k, f in (("cat_and_row_map", parent_path), ("pack", lambda: st.pack(cases, None, counter=i))):
+            wall[k].append(host_clock(f))
+    cat_ms = []
+    views = [st.bag_view(c, m) for c in cases for m in range(M)]
+    for i in range(a.launches):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        x = torch.cat(views, dim=0)
+        e1.record()
+        e1.synchronize()
+        cat_ms.append(e0.elapsed_time(e1))
+        del x
+    res["parent_path"] = {"host_clock_ms": {k: stats(v) for k, v in wall.items()}, "cat_device_ms": stats(cat_ms),
+                          "row_map_upload_bytes": 4 * T, "pack_upload_bytes": 8 * (2 * (R + 1) + (R + 1) // 2)}
+    for k, v in sorted(wall.items()):
+        lines.append("host clock around a synchronise, %-16s median %.3f ms (min %.3f max %.3f)" % (k, statistics.median(v), min(v), max(v)))
+    lines.append("torch.cat of the %d views alone, device events: median %.3f ms (min %.3f max %.3f); uploads per step: %d B (row map) against %d B (pack)"
+                 % (R, statistics.median(cat_ms), min(cat_ms), max(cat_ms), 4 * T, res["parent_path"]["pack_upload_bytes"]))
+
+    # ---- 5. the config-5 step
+    if not a.skip_step:
+        from madeleine_amd import GOT
+        torch.manual_seed(42)
+        model = MADELEINE(BN.make_cfg(M, D), stain_encoding=stain).to(dev).train()
+        opt = torch.optim.AdamW(model.parameters(), lr=1e-4, fused=True)
+        crit = InfoNCE(temperature=0.001)
+        largs = SimpleNamespace(global_loss="info-nce", symmetric_cl=True, local_loss_weight=1.0)
+
+        def step(data):
+            opt.zero_grad(set_to_none=True)
+            embs, toks = model(data, device=dev)
+            loss, _ = calculate_losses(mods[1:], crit, GOT, None, embs, toks, data["modality_labels"][:, 1:], largs)
+            loss.backward()
+            opt.step()
+        feeds = {"ragged": st.ragged_batches(B, shuffle=True, seed=1), "packed": st.packed_batches(B, None, shuffle=True, seed=1),
+                 "packed_cap": st.packed_batches(B, a.cap, shuffle=True, seed=1)}
+        epoch = [0]
+
+        def batch(k):
+            feeds[k].set_epoch(epoch[0])
+            epoch[0] += 1
+            return next(iter(feeds[k]))
+        for k in feeds:
+            for _ in range(a.warmup):
+                step(batch(k))
+        rounds = max(1, a.steps // a.round_steps)
+        times = {k: [] for k in feeds}
+        for r in range(rounds):
+            for k in (sorted(feeds) if r % 2 == 0 else sorted(feeds, reverse=True)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(a.round_steps):
+                    step(batch(k))
+                e1.record()
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1) / a.round_steps)
+        res["step"] = {"rounds": rounds, "steps_per_round": a.round_steps, "step_ms": {k: stats(v) for k, v in times.items()},
+                       "rounds_ms": times, "packed_minus_ragged_ms": statistics.median(times["packed"]) - statistics.median(times["ragged"])}
+        for k, v in sorted(times.items()):
+            lines.append("config-5 step fed by %-10s median %.3f ms  min %.3f  max %.3f   rounds: %s"
+                         % (k, statistics.median(v), min(v), max(v), " ".join("%.3f" % x for x in v)))
+        lines.append("  packed - ragged = %.3f ms" % res["step"]["packed_minus_ragged_ms"])
+    return lines, res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=20000)
@@ -87,8 +245,14 @@ def main():
     ap.add_argument("--no-h5", action="store_true", help="leave out the feed that reads h5 files")
     ap.add_argument("--h5-dir", default=None, help="where the synthetic cohort's h5 files go (default: the system's temporary directory)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--pack", action="store_true", help="measure the packed ragged route (config 5's shape) instead")
+    ap.add_argument("--cap", type=int, default=4096, help="max_tokens of the capped pack of --pack")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.pack:
+        lines, res = pack_leg(a, dev)
+        report(lines, res, a.out)
+        return
     B, M, N, D, _got, stain = BN.CONFIGS["c2"]
     mods = BN.MODS5[:M]
     g = torch.Generator().manual_seed(7)
@@ -206,12 +370,16 @@ def main():
                              % (k, statistics.median(v), min(v), max(v), " ".join("%.3f" % x for x in v)))
             lines.append("  %s - store = %.3f ms (spread of %s over its rounds: %.3f);  store - const = %.3f ms (gather %.3f + spread of const %.3f)"
                          % (name, med[name] - med["store"], name, spread[name], med["store"] - med["const"], gather, spread["const"]))
+    report(lines, res, a.out)
+
+
+def report(lines, res, out):
     text = "\n".join(lines)
     print(text)
     print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
             f.write(text + "\n" + json.dumps(res) + "\n")
 
 
