@@ -746,6 +746,33 @@ int mdl_bag_pack(const void* store, int dtype, int64_t row_stride, int64_t T_tot
                  const int32_t* bag, const int64_t* key_id, const int64_t* cu, const int64_t* chunk_cu, int64_t R, int64_t n_chunks,
                  int64_t T_out, int D, uint64_t seed, uint64_t counter, float* out, int32_t* row_bag, int32_t* idx_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * S3, S4 -- S1 and S2 over a store in TWO TIERS (ABI 26, additive): rows [0, T_dev) of the store in device memory at `store`, rows
+ * [T_dev, T_total) in pinned host memory at `store_host`, read by the kernel over PCIe.  For a cohort that does not fit in HBM.
+ *
+ * store: the device tier, T_dev rows (NULL allowed when T_dev == 0).  store_host: the host tier, T_total - T_dev rows, as the HOST
+ *   address of registered (pinned) host memory -- hipHostMalloc or hipHostRegister -- or a device address (NULL allowed when T_dev ==
+ *   T_total).  Both tiers share dtype and row_stride; 16-byte aligned.  off, n_bags and bag keep addressing rows of [0, T_total): a
+ *   valid bag g with off[g + 1] <= T_dev is read at store + off[g] * row_stride, one with off[g] >= T_dev at store_host + (off[g] -
+ *   T_dev) * row_stride, and a bag on both sides of T_dev falls under S1's bounds rule (zeros, idx -1; no address is formed from it).
+ * host_wgs: the grid of the host-tier pass, 0 for the built-in default (64).  The work items (output row x 64-token chunk, pack chunk)
+ *   whose bag is in the host tier are walked by host_wgs persistent workgroups in a launch of their own; the items of resident bags
+ *   and of absent stains keep the one-workgroup-per-item grid of S1 / S2 in another.  Both go to `stream`.
+ * Every other argument, the three draw regimes, the whole-bag rule of S2, access widths, exact widening, the bounds on the store and
+ *   on the output side and the refusals are S1's and S2's: the kernels share their code, and with T_dev == T_total the outputs are
+ *   bit-equal to S1 / S2.  A bag's draw does not depend on its tier.
+ * Before any launch the entry points ask the runtime what store_host is (hipPointerGetAttributes on its first and last byte, the
+ *   allocation's extent where hipMemGetAddressRange reports one) and resolve its device-visible address (hipHostGetDevicePointer).
+ *   MDL_E_ARG for pageable, managed or unknown memory, for a tier that leaves its allocation, for T_dev outside [0, T_total] and for
+ *   host_wgs < 0: no kernel is ever launched on a pointer the device cannot read. */
+int mdl_bag_sample_tiered(const void* store, const void* store_host, int dtype, int64_t row_stride, int64_t T_total, int64_t T_dev,
+                          const int64_t* off, int64_t n_bags, const int32_t* bag, const int64_t* key_id, int64_t R, int N, int D,
+                          uint64_t seed, uint64_t counter, float* out, int32_t* idx_out, int host_wgs, void* stream);
+int mdl_bag_pack_tiered(const void* store, const void* store_host, int dtype, int64_t row_stride, int64_t T_total, int64_t T_dev,
+                        const int64_t* off, int64_t n_bags, const int32_t* bag, const int64_t* key_id, const int64_t* cu,
+                        const int64_t* chunk_cu, int64_t R, int64_t n_chunks, int64_t T_out, int D, uint64_t seed, uint64_t counter,
+                        float* out, int32_t* row_bag, int32_t* idx_out, int host_wgs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,11 @@
 //
 // Bounds.  A bag index outside [0, n_bags), an empty or over-long bag and a bag that leaves [0, T_total) are written as absent stains
 // (zeros, idx -1): whatever the tables hold, no address outside the store is formed.
+//
+// One body, several kernels.  sample_item / pack_item below are the whole work of one (output row, 64-token chunk) item; the draw
+// (row_key, token_hash, feistel, draw_distinct), the placement of a bag (locate_bag) and the copy loops (copy_rows) are device
+// functions that every kernel of this file instantiates, so S1, S2 and their tiered forms S3, S4 (at the end of the file) draw and
+// copy with the same code.
 #include "common.hpp"
 
 namespace mdl {
@@ -112,70 +117,65 @@ struct Vec<bf16_t> {
     static __device__ __forceinline__ float up(bf16_t x) { return (float)x; }
 };
 
-// VEC: D and row_stride are multiples of Vec<T>::E and both bases are 16-byte aligned, so every row of both sides is.
-template <class T, bool VEC>
-__global__ __launch_bounds__(BS_THREADS) void bag_sample_kernel(const T* __restrict__ store, int64_t row_stride, int64_t T_total,
-                                                                const int64_t* __restrict__ off, int64_t n_bags,
-                                                                const int32_t* __restrict__ bag, const int64_t* __restrict__ key_id,
-                                                                int N, int D, int chunks, uint64_t seed, uint64_t counter,
-                                                                float* __restrict__ out, int32_t* __restrict__ idx_out) {
-    __shared__ int32_t s_idx[BS_TOK];
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const int r = blockIdx.x / chunks, t0 = (blockIdx.x - r * chunks) * BS_TOK;
-    const int cnt = N - t0 < BS_TOK ? N - t0 : BS_TOK;        // tokens of this workgroup, >= 1
+// Which items a kernel owns.  PASS_ALL: every item, the store is one device tensor (S1, S2).  The tiered entry points split a launch
+// in two: PASS_DEV owns the items of resident bags and of absent stains, PASS_HOST those of the bags in the host tier.
+enum { PASS_ALL = 0, PASS_DEV = 1, PASS_HOST = 2 };
 
-    const int g = bag[r];
+// The rows of stored bag g: returns n, its length, or 0 for an absent stain (by the table or by the bounds rule of the header comment);
+// `rows` is its first row (the tier's base when n == 0: never read).  Tiered (PASS != PASS_ALL): rows [0, T_dev) of the store are in
+// `store`, rows [T_dev, T_total) in `store_host`; a bag on both sides of T_dev is an absent stain; on_host says which pass owns the item.
+template <class T, int PASS>
+__device__ __forceinline__ uint32_t locate_bag(const T* __restrict__ store, const T* __restrict__ store_host, int64_t T_dev,
+                                               int64_t row_stride, int64_t T_total, const int64_t* __restrict__ off, int64_t n_bags, int g,
+                                               const T*& rows, bool& on_host) {
     int64_t base = 0, n64 = 0;
     if (g >= 0 && g < n_bags) {
         base = off[g];
         n64 = off[g + 1] - base;
         if (base < 0 || n64 < 1 || n64 > 0x7FFFFFFF || base > T_total - n64) n64 = 0;
     }
-    const uint32_t n = (uint32_t)n64;                           // 0: an absent stain
-    float* orow = out + ((int64_t)r * N + t0) * D;
-
-    if (n == 0) {                                               // uniform over the workgroup
-        const int64_t total = (int64_t)cnt * D;
-        if (VEC) {
-            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            for (int64_t e = (int64_t)tid * 4; e < total; e += BS_THREADS * 4) st4(orow + e, z);
-        } else {
-            for (int64_t e = tid; e < total; e += BS_THREADS) orow[e] = 0.f;
+    on_host = false;
+    if (PASS != PASS_ALL && n64 != 0) {
+        if (base >= T_dev) {                                    // wholly in the host tier: T_dev <= base, base + n <= T_total
+            on_host = true;
+            rows = store_host + (base - T_dev) * row_stride;
+            return (uint32_t)n64;
         }
-        if (idx_out != nullptr && tid < cnt) idx_out[(int64_t)r * N + t0 + tid] = -1;
-        return;
+        if (base > T_dev - n64) n64 = base = 0;                 // on both sides of T_dev: no address is formed from it
     }
+    rows = store + base * row_stride;
+    return (uint32_t)n64;
+}
 
-    if (wave == 0) {
-        const RowKey k = row_key(seed, counter, key_id != nullptr ? (uint64_t)key_id[r] : (uint64_t)(int64_t)g);
-        const uint32_t t = (uint32_t)(t0 + lane);
-        if (n < (uint32_t)N) {                                  // with replacement
-            s_idx[lane] = (int32_t)(((uint64_t)token_hash(t, k) * n) >> 32);
-        } else if (n <= (uint32_t)WAVE) {                       // N <= n <= 64: one chunk (t0 == 0), random-key sort in the wave
-            const uint32_t h = token_hash((uint32_t)lane, k);
-            int rank = 0;
-            for (uint32_t j = 0; j < n; ++j) {
-                const uint32_t hj = (uint32_t)__shfl((int)h, (int)j, WAVE);
-                rank += (hj < h || (hj == h && j < (uint32_t)lane)) ? 1 : 0;
-            }
-            if ((uint32_t)lane < n && rank < N) s_idx[rank] = lane;      // ranks of lanes < n are a permutation of 0 .. n-1
-        } else {                                                // N <= n, n > 64: keyed bijection of [0, n)
-            int bits = 32 - __builtin_clz(n - 1);              // 2^bits >= n, bits >= 7
-            bits += bits & 1;
-            const int half = bits >> 1;
-            uint32_t y = t;
-            if (lane < cnt) {
-                do {
-                    y = feistel(y, half, k);
-                } while (y >= n);                               // terminates: see the header comment
-            }
-            s_idx[lane] = (int32_t)y;
+// Wave 0, N <= n: the bag rows of tokens t0 .. t0 + 63 of a draw of N distinct rows out of n -> s_idx (see the header comment).
+__device__ __forceinline__ void draw_distinct(RowKey k, uint32_t n, int N, uint32_t t0, int lane, int cnt, int32_t* s_idx) {
+    if (n <= (uint32_t)WAVE) {                                  // N <= n <= 64: one chunk (t0 == 0), random-key sort in the wave
+        const uint32_t h = token_hash((uint32_t)lane, k);
+        int rank = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            const uint32_t hj = (uint32_t)__shfl((int)h, (int)j, WAVE);
+            rank += (hj < h || (hj == h && j < (uint32_t)lane)) ? 1 : 0;
         }
+        if ((uint32_t)lane < n && rank < N) s_idx[rank] = lane;          // ranks of lanes < n are a permutation of 0 .. n-1
+    } else {                                                    // N <= n, n > 64: keyed bijection of [0, n)
+        int bits = 32 - __builtin_clz(n - 1);                  // 2^bits >= n, bits >= 7
+        bits += bits & 1;
+        const int half = bits >> 1;
+        uint32_t y = t0 + (uint32_t)lane;
+        if (lane < cnt) {
+            do {
+                y = feistel(y, half, k);
+            } while (y >= n);                                   // terminates: see the header comment
+        }
+        s_idx[lane] = (int32_t)y;
     }
-    __syncthreads();
-    if (idx_out != nullptr && tid < cnt) idx_out[(int64_t)r * N + t0 + tid] = s_idx[tid];
+}
 
-    const T* bag_rows = store + base * row_stride;
+// The four waves copy rows [0, ncopy) of a chunk from the bag rows s_idx names to orow, INFLIGHT rows in flight per lane.
+// VEC: D and row_stride are multiples of Vec<T>::E and both bases are 16-byte aligned, so every row of both sides is.
+template <class T, bool VEC, int INFLIGHT>
+__device__ __forceinline__ void copy_rows(const T* __restrict__ bag_rows, int64_t row_stride, const int32_t* s_idx, int ncopy, int D,
+                                          float* __restrict__ orow, int lane, int wave) {
     if (VEC) {
         constexpr int E = Vec<T>::E;
         const int dv = D / E;                                   // 16-byte accesses of the store per row
@@ -183,33 +183,93 @@ __global__ __launch_bounds__(BS_THREADS) void bag_sample_kernel(const T* __restr
         while (lpr < dv && lpr < WAVE) lpr <<= 1;
         const int sub = lane / lpr, c0 = lane - sub * lpr;
         const int step = BS_WAVES * (WAVE / lpr);               // rows the workgroup covers per pass
-        for (int row0 = wave * (WAVE / lpr) + sub; row0 < cnt; row0 += BS_INFLIGHT * step) {
-            const T* src[BS_INFLIGHT];
-            float* dst[BS_INFLIGHT];
+        for (int row0 = wave * (WAVE / lpr) + sub; row0 < ncopy; row0 += INFLIGHT * step) {
+            const T* src[INFLIGHT];
+            float* dst[INFLIGHT];
 #pragma unroll
-            for (int j = 0; j < BS_INFLIGHT; ++j) {
+            for (int j = 0; j < INFLIGHT; ++j) {
                 const int row = row0 + j * step;
-                const int safe = row < cnt ? row : row0;          // a row past the chunk: addresses of a valid one, never used
+                const int safe = row < ncopy ? row : row0;        // a row past the chunk: addresses of a valid one, never used
                 src[j] = bag_rows + (int64_t)s_idx[safe] * row_stride;
                 dst[j] = orow + (int64_t)safe * D;
             }
             for (int c = c0; c < dv; c += lpr) {
-                typename Vec<T>::Raw v[BS_INFLIGHT];
+                typename Vec<T>::Raw v[INFLIGHT];
 #pragma unroll
-                for (int j = 0; j < BS_INFLIGHT; ++j)
-                    if (row0 + j * step < cnt) v[j] = Vec<T>::ld(src[j] + c * E);
+                for (int j = 0; j < INFLIGHT; ++j)
+                    if (row0 + j * step < ncopy) v[j] = Vec<T>::ld(src[j] + c * E);
 #pragma unroll
-                for (int j = 0; j < BS_INFLIGHT; ++j)
-                    if (row0 + j * step < cnt) Vec<T>::st(dst[j] + c * E, v[j]);
+                for (int j = 0; j < INFLIGHT; ++j)
+                    if (row0 + j * step < ncopy) Vec<T>::st(dst[j] + c * E, v[j]);
             }
         }
     } else {                                                    // any D, any stride: element-wise
-        for (int row = wave; row < cnt; row += BS_WAVES) {
+        for (int row = wave; row < ncopy; row += BS_WAVES) {
             const T* sa = bag_rows + (int64_t)s_idx[row] * row_stride;
             float* da = orow + (int64_t)row * D;
             for (int c = lane; c < D; c += WAVE) da[c] = Vec<T>::up(sa[c]);
         }
     }
+}
+
+// `count` rows of zeros from zrow on (VEC: D is a multiple of 4 and out is 16-byte aligned, so every row is)
+template <bool VEC>
+__device__ __forceinline__ void zero_rows(float* __restrict__ zrow, int count, int D, int tid) {
+    const int64_t total = (int64_t)count * D;
+    if (VEC) {
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        for (int64_t e = (int64_t)tid * 4; e < total; e += BS_THREADS * 4) st4(zrow + e, z);
+    } else {
+        for (int64_t e = tid; e < total; e += BS_THREADS) zrow[e] = 0.f;
+    }
+}
+
+// Item w = (output row r, chunk c) of the dense gather: the whole of S1's work for tokens 64 c .. 64 c + 63 of row r.  Uniform over the
+// workgroup, the early returns included; a caller that loops over items puts a barrier between two of them (s_idx is reused).
+template <class T, bool VEC, int PASS, int INFLIGHT>
+__device__ __forceinline__ void sample_item(const T* __restrict__ store, const T* __restrict__ store_host, int64_t T_dev, int64_t row_stride,
+                                            int64_t T_total, const int64_t* __restrict__ off, int64_t n_bags,
+                                            const int32_t* __restrict__ bag, const int64_t* __restrict__ key_id, int N, int D, int chunks,
+                                            uint64_t seed, uint64_t counter, float* __restrict__ out, int32_t* __restrict__ idx_out, int w,
+                                            int32_t* s_idx) {
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int r = w / chunks, t0 = (w - r * chunks) * BS_TOK;
+    const int cnt = N - t0 < BS_TOK ? N - t0 : BS_TOK;        // tokens of this item, >= 1
+
+    const int g = bag[r];
+    const T* bag_rows;
+    bool on_host;
+    const uint32_t n = locate_bag<T, PASS>(store, store_host, T_dev, row_stride, T_total, off, n_bags, g, bag_rows, on_host);   // 0: absent
+    if (PASS != PASS_ALL && on_host != (PASS == PASS_HOST)) return;      // the other pass's item
+    float* orow = out + ((int64_t)r * N + t0) * D;
+
+    if (n == 0) {                                               // uniform over the workgroup
+        zero_rows<VEC>(orow, cnt, D, tid);
+        if (idx_out != nullptr && tid < cnt) idx_out[(int64_t)r * N + t0 + tid] = -1;
+        return;
+    }
+
+    if (wave == 0) {
+        const RowKey k = row_key(seed, counter, key_id != nullptr ? (uint64_t)key_id[r] : (uint64_t)(int64_t)g);
+        if (n < (uint32_t)N)                                    // with replacement
+            s_idx[lane] = (int32_t)(((uint64_t)token_hash((uint32_t)(t0 + lane), k) * n) >> 32);
+        else
+            draw_distinct(k, n, N, (uint32_t)t0, lane, cnt, s_idx);
+    }
+    __syncthreads();
+    if (idx_out != nullptr && tid < cnt) idx_out[(int64_t)r * N + t0 + tid] = s_idx[tid];
+    copy_rows<T, VEC, INFLIGHT>(bag_rows, row_stride, s_idx, cnt, D, orow, lane, wave);
+}
+
+template <class T, bool VEC>
+__global__ __launch_bounds__(BS_THREADS) void bag_sample_kernel(const T* __restrict__ store, int64_t row_stride, int64_t T_total,
+                                                                const int64_t* __restrict__ off, int64_t n_bags,
+                                                                const int32_t* __restrict__ bag, const int64_t* __restrict__ key_id,
+                                                                int N, int D, int chunks, uint64_t seed, uint64_t counter,
+                                                                float* __restrict__ out, int32_t* __restrict__ idx_out) {
+    __shared__ int32_t s_idx[BS_TOK];
+    sample_item<T, VEC, PASS_ALL, BS_INFLIGHT>(store, nullptr, T_total, row_stride, T_total, off, n_bags, bag, key_id, N, D, chunks, seed,
+                                               counter, out, idx_out, (int)blockIdx.x, s_idx);
 }
 
 template <class T>
@@ -275,65 +335,16 @@ extern "C" int mdl_bag_sample(const void* store, int dtype, int64_t row_stride, 
 namespace mdl {
 namespace {
 
-// rows [0, ncopy) of the chunk from the store rows s_idx names (the copy loops of bag_sample_kernel), rows [ncopy, cnt) zeros
-template <class T, bool VEC>
-__device__ __forceinline__ void pack_rows(const T* __restrict__ bag_rows, int64_t row_stride, const int32_t* s_idx, int ncopy, int cnt, int D,
-                                          float* __restrict__ orow, int tid, int lane, int wave) {
-    if (VEC) {
-        constexpr int E = Vec<T>::E;
-        const int dv = D / E;                                   // 16-byte accesses of the store per row
-        int lpr = 1;                                            // lanes per row: a power of two, <= 64
-        while (lpr < dv && lpr < WAVE) lpr <<= 1;
-        const int sub = lane / lpr, c0 = lane - sub * lpr;
-        const int step = BS_WAVES * (WAVE / lpr);               // rows the workgroup covers per pass
-        for (int row0 = wave * (WAVE / lpr) + sub; row0 < ncopy; row0 += BS_INFLIGHT * step) {
-            const T* src[BS_INFLIGHT];
-            float* dst[BS_INFLIGHT];
-#pragma unroll
-            for (int j = 0; j < BS_INFLIGHT; ++j) {
-                const int row = row0 + j * step;
-                const int safe = row < ncopy ? row : row0;        // a row past the chunk: addresses of a valid one, never used
-                src[j] = bag_rows + (int64_t)s_idx[safe] * row_stride;
-                dst[j] = orow + (int64_t)safe * D;
-            }
-            for (int c = c0; c < dv; c += lpr) {
-                typename Vec<T>::Raw v[BS_INFLIGHT];
-#pragma unroll
-                for (int j = 0; j < BS_INFLIGHT; ++j)
-                    if (row0 + j * step < ncopy) v[j] = Vec<T>::ld(src[j] + c * E);
-#pragma unroll
-                for (int j = 0; j < BS_INFLIGHT; ++j)
-                    if (row0 + j * step < ncopy) Vec<T>::st(dst[j] + c * E, v[j]);
-            }
-        }
-    } else {                                                    // any D, any stride: element-wise
-        for (int row = wave; row < ncopy; row += BS_WAVES) {
-            const T* sa = bag_rows + (int64_t)s_idx[row] * row_stride;
-            float* da = orow + (int64_t)row * D;
-            for (int c = lane; c < D; c += WAVE) da[c] = Vec<T>::up(sa[c]);
-        }
-    }
-    float* zrow = orow + (int64_t)ncopy * D;
-    const int64_t total = (int64_t)(cnt - ncopy) * D;
-    if (VEC) {                                                  // D is a multiple of 4 and out is 16-byte aligned: so is every row
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        for (int64_t e = (int64_t)tid * 4; e < total; e += BS_THREADS * 4) st4(zrow + e, z);
-    } else {
-        for (int64_t e = tid; e < total; e += BS_THREADS) zrow[e] = 0.f;
-    }
-}
-
-template <class T, bool VEC>
-__global__ __launch_bounds__(BS_THREADS) void bag_pack_kernel(const T* __restrict__ store, int64_t row_stride, int64_t T_total,
-                                                              const int64_t* __restrict__ off, int64_t n_bags,
-                                                              const int32_t* __restrict__ bag, const int64_t* __restrict__ key_id,
-                                                              const int64_t* __restrict__ cu, const int64_t* __restrict__ chunk_cu, int R,
-                                                              int64_t T_out, int D, uint64_t seed, uint64_t counter,
-                                                              float* __restrict__ out, int32_t* __restrict__ row_bag,
-                                                              int32_t* __restrict__ idx_out) {
-    __shared__ int32_t s_idx[BS_TOK];
+// Item w = (output bag r, chunk c) of the pack: the whole of S2's work for packed rows cu[r] + 64 c .. + 63.  Uniform over the workgroup,
+// the early returns included; a caller that loops over items puts a barrier between two of them (s_idx is reused).
+template <class T, bool VEC, int PASS, int INFLIGHT>
+__device__ __forceinline__ void pack_item(const T* __restrict__ store, const T* __restrict__ store_host, int64_t T_dev, int64_t row_stride,
+                                          int64_t T_total, const int64_t* __restrict__ off, int64_t n_bags, const int32_t* __restrict__ bag,
+                                          const int64_t* __restrict__ key_id, const int64_t* __restrict__ cu,
+                                          const int64_t* __restrict__ chunk_cu, int R, int64_t T_out, int D, uint64_t seed, uint64_t counter,
+                                          float* __restrict__ out, int32_t* __restrict__ row_bag, int32_t* __restrict__ idx_out, int64_t w,
+                                          int32_t* s_idx) {
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const int64_t w = blockIdx.x;
     int lo = 0, hi = R - 1;                                     // the last r of [0, R) with chunk_cu[r] <= w (bags of no rows are passed over)
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -346,56 +357,47 @@ __global__ __launch_bounds__(BS_THREADS) void bag_pack_kernel(const T* __restric
     int64_t lim = L - t0;
     if (T_out - p0 - t0 < lim) lim = T_out - p0 - t0;
     if (lim < 1) return;
-    const int cnt = lim < BS_TOK ? (int)lim : BS_TOK;           // packed rows of this workgroup, all inside [0, T_out)
+    const int cnt = lim < BS_TOK ? (int)lim : BS_TOK;           // packed rows of this item, all inside [0, T_out)
 
     const int g = bag[r];
-    int64_t base = 0, n64 = 0;
-    if (g >= 0 && g < n_bags) {
-        base = off[g];
-        n64 = off[g + 1] - base;
-        if (base < 0 || n64 < 1 || n64 > 0x7FFFFFFF || base > T_total - n64) n64 = 0;
-    }
-    const uint32_t n = (uint32_t)n64;                           // 0: an absent stain
-    const int64_t prow = p0 + t0;
+    const T* bag_rows;
+    bool on_host;
+    const uint32_t n = locate_bag<T, PASS>(store, store_host, T_dev, row_stride, T_total, off, n_bags, g, bag_rows, on_host);   // 0: absent
+    if (PASS != PASS_ALL && on_host != (PASS == PASS_HOST)) return;      // the other pass's item
+    const int64_t n64 = n, prow = p0 + t0;
 
     int ncopy = 0;                                              // rows of the chunk that come from the store; the others are zeros
     if (n != 0 && L >= n64) {                                   // the bag taken whole: row t is stored row t
         const int64_t left = n64 - t0;
         ncopy = left < 0 ? 0 : left < cnt ? (int)left : cnt;
         if (wave == 0) s_idx[lane] = (int32_t)t0 + lane;
-    } else if (n != 0) {                                        // L < n: bag_sample_kernel's draw without replacement, N = L
+    } else if (n != 0) {                                        // L < n: sample_item's draw without replacement, N = L
         ncopy = cnt;
-        if (wave == 0) {
-            const RowKey k = row_key(seed, counter, key_id != nullptr ? (uint64_t)key_id[r] : (uint64_t)(int64_t)g);
-            const int N = (int)L;
-            if (n <= (uint32_t)WAVE) {                          // L < n <= 64: one chunk (t0 == 0), random-key sort in the wave
-                const uint32_t h = token_hash((uint32_t)lane, k);
-                int rank = 0;
-                for (uint32_t j = 0; j < n; ++j) {
-                    const uint32_t hj = (uint32_t)__shfl((int)h, (int)j, WAVE);
-                    rank += (hj < h || (hj == h && j < (uint32_t)lane)) ? 1 : 0;
-                }
-                if ((uint32_t)lane < n && rank < N) s_idx[rank] = lane;
-            } else {                                            // keyed bijection of [0, n), cycle walking
-                int bits = 32 - __builtin_clz(n - 1);
-                bits += bits & 1;
-                const int half = bits >> 1;
-                uint32_t y = (uint32_t)t0 + (uint32_t)lane;
-                if (lane < cnt) {
-                    do {
-                        y = feistel(y, half, k);
-                    } while (y >= n);                           // terminates: see the comment at the head of the file
-                }
-                s_idx[lane] = (int32_t)y;
-            }
-        }
+        if (wave == 0)
+            draw_distinct(row_key(seed, counter, key_id != nullptr ? (uint64_t)key_id[r] : (uint64_t)(int64_t)g), n, (int)L, (uint32_t)t0,
+                          lane, cnt, s_idx);
     }
     __syncthreads();
     if (tid < cnt) {
         if (idx_out != nullptr) idx_out[prow + tid] = tid < ncopy ? s_idx[tid] : -1;
         if (row_bag != nullptr) row_bag[prow + tid] = r;
     }
-    pack_rows<T, VEC>(store + base * row_stride, row_stride, s_idx, ncopy, cnt, D, out + prow * D, tid, lane, wave);
+    float* orow = out + prow * D;
+    copy_rows<T, VEC, INFLIGHT>(bag_rows, row_stride, s_idx, ncopy, D, orow, lane, wave);
+    zero_rows<VEC>(orow + (int64_t)ncopy * D, cnt - ncopy, D, tid);
+}
+
+template <class T, bool VEC>
+__global__ __launch_bounds__(BS_THREADS) void bag_pack_kernel(const T* __restrict__ store, int64_t row_stride, int64_t T_total,
+                                                              const int64_t* __restrict__ off, int64_t n_bags,
+                                                              const int32_t* __restrict__ bag, const int64_t* __restrict__ key_id,
+                                                              const int64_t* __restrict__ cu, const int64_t* __restrict__ chunk_cu, int R,
+                                                              int64_t T_out, int D, uint64_t seed, uint64_t counter,
+                                                              float* __restrict__ out, int32_t* __restrict__ row_bag,
+                                                              int32_t* __restrict__ idx_out) {
+    __shared__ int32_t s_idx[BS_TOK];
+    pack_item<T, VEC, PASS_ALL, BS_INFLIGHT>(store, nullptr, T_total, row_stride, T_total, off, n_bags, bag, key_id, cu, chunk_cu, R, T_out, D,
+                                             seed, counter, out, row_bag, idx_out, (int64_t)blockIdx.x, s_idx);
 }
 
 template <class T>
@@ -442,5 +444,236 @@ extern "C" int mdl_bag_pack(const void* store, int dtype, int64_t row_stride, in
         default:
             return launch_pack<bf16_t>(store, row_stride, T_total, off, n_bags, bag, key_id, cu, chunk_cu, (int)R, n_chunks, T_out, D, seed,
                                        counter, out, row_bag, idx_out, s);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The tiered forms (S3, S4 of the header): rows [0, T_dev) of the store in device memory, rows [T_dev, T_total) in pinned host memory
+// that the kernel reads over PCIe.  The items are those of S1 / S2 and so is every bit written (sample_item / pack_item); what changes
+// is who runs an item.  Two launches on the stream, each skipping the other's items:
+//   device pass  one workgroup per item, the chip-wide grid of S1 / S2: the items of resident bags and of absent stains (a bag on both
+//                sides of T_dev is one).  An item of the host tier returns after three table reads.
+//   host pass    a NARROW PERSISTENT grid: host_wgs workgroups walk all items with a grid stride, skip those that are not the host
+//                tier's and run the same draw-then-copy on the others.  A 63 GB/s link is saturated by a few hundred KB in flight
+//                (host_wgs x 256 lanes x BS_HOST_INFLIGHT x 16 B); a chip-wide grid would hold wave slots and registers of every CU
+//                for the milliseconds the link needs, in front of the step's kernels that run beside a prefetching gather.
+// Two launches rather than one kernel that branches per item: one grid cannot be both chip-wide and narrow.
+#ifndef BS_HOST_INFLIGHT
+#define BS_HOST_INFLIGHT 4                  // rows a lane has in flight over PCIe
+#endif
+#ifndef BS_HOST_WGS
+#define BS_HOST_WGS 64                      // the host pass's grid when the caller passes host_wgs = 0
+#endif
+
+namespace mdl {
+namespace {
+
+template <class T, bool VEC, int PASS>
+__global__ __launch_bounds__(BS_THREADS) void bag_sample_tier_kernel(const T* __restrict__ store, const T* __restrict__ store_host,
+                                                                     int64_t T_dev, int64_t row_stride, int64_t T_total,
+                                                                     const int64_t* __restrict__ off, int64_t n_bags,
+                                                                     const int32_t* __restrict__ bag, const int64_t* __restrict__ key_id,
+                                                                     int N, int D, int chunks, int64_t items, uint64_t seed, uint64_t counter,
+                                                                     float* __restrict__ out, int32_t* __restrict__ idx_out) {
+    __shared__ int32_t s_idx[BS_TOK];
+    for (int64_t w = blockIdx.x; w < items; w += gridDim.x) {      // items <= 2^31 - 1; the device pass has one item per workgroup
+        sample_item<T, VEC, PASS, PASS == PASS_HOST ? BS_HOST_INFLIGHT : BS_INFLIGHT>(store, store_host, T_dev, row_stride, T_total, off, n_bags,
+                                                                                      bag, key_id, N, D, chunks, seed, counter, out, idx_out,
+                                                                                      (int)w, s_idx);
+        __syncthreads();                                        // the next item's draw overwrites s_idx
+    }
+}
+
+template <class T, bool VEC, int PASS>
+__global__ __launch_bounds__(BS_THREADS) void bag_pack_tier_kernel(const T* __restrict__ store, const T* __restrict__ store_host, int64_t T_dev,
+                                                                   int64_t row_stride, int64_t T_total, const int64_t* __restrict__ off,
+                                                                   int64_t n_bags, const int32_t* __restrict__ bag,
+                                                                   const int64_t* __restrict__ key_id, const int64_t* __restrict__ cu,
+                                                                   const int64_t* __restrict__ chunk_cu, int R, int64_t items, int64_t T_out,
+                                                                   int D, uint64_t seed, uint64_t counter, float* __restrict__ out,
+                                                                   int32_t* __restrict__ row_bag, int32_t* __restrict__ idx_out) {
+    __shared__ int32_t s_idx[BS_TOK];
+    for (int64_t w = blockIdx.x; w < items; w += gridDim.x) {
+        pack_item<T, VEC, PASS, PASS == PASS_HOST ? BS_HOST_INFLIGHT : BS_INFLIGHT>(store, store_host, T_dev, row_stride, T_total, off, n_bags,
+                                                                                    bag, key_id, cu, chunk_cu, R, T_out, D, seed, counter, out,
+                                                                                    row_bag, idx_out, w, s_idx);
+        __syncthreads();
+    }
+}
+
+// What the runtime knows about the host tier [p, p + bytes): MDL_OK and its device-visible address when both ends lie in registered
+// (pinned) host memory or both in device memory, and -- where the runtime reports the allocation's extent -- inside one allocation.
+// Anything else (pageable, managed, unknown to the runtime) is MDL_E_ARG: no kernel is launched on it.
+int device_view_of_tier(const void* p, int64_t bytes, const void** dev) {
+    const char* first = static_cast<const char*>(p);
+    const char* ends[2] = {first, first + (bytes - 1)};
+    hipMemoryType type[2];
+    for (int i = 0; i < 2; ++i) {
+        hipPointerAttribute_t attr;
+        if (hipPointerGetAttributes(&attr, ends[i]) != hipSuccess) {
+            (void)hipGetLastError();                            // pageable memory on runtimes that answer with an error
+            return MDL_E_ARG;
+        }
+        type[i] = attr.type;
+        if (attr.isManaged) return MDL_E_ARG;
+    }
+    if (type[0] != type[1] || (type[0] != hipMemoryTypeHost && type[0] != hipMemoryTypeDevice)) return MDL_E_ARG;
+    void* d = const_cast<void*>(p);
+    if (type[0] == hipMemoryTypeHost && hipHostGetDevicePointer(&d, const_cast<void*>(p), 0) != hipSuccess) {
+        (void)hipGetLastError();
+        return MDL_E_ARG;
+    }
+    if (d == nullptr) return MDL_E_ARG;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)d) == hipSuccess) {
+        // hipHostMalloc and hipMalloc report base and size; for hipHostRegister-ed memory the runtime reports the registration's size
+        // and a NULL base: the tier must then fit the size, and its place inside the registration rests on the two ends above
+        const uintptr_t b = reinterpret_cast<uintptr_t>(base), a = reinterpret_cast<uintptr_t>(d);
+        if ((uint64_t)bytes > size) return MDL_E_ARG;
+        if (base != nullptr && (a < b || a - b > size - (uint64_t)bytes)) return MDL_E_ARG;
+    } else {
+        (void)hipGetLastError();                                // no extent reported for this kind of memory: the two ends stand
+    }
+    *dev = d;
+    return MDL_OK;
+}
+
+// arguments common to S3 and S4: MDL_OK with *host_dev resolved (NULL without a host tier) and *wgs the host pass's grid (0: no pass)
+int check_tiers(const void* store, const void* store_host, int dtype, int64_t row_stride, int64_t T_total, int64_t T_dev, int D, int host_wgs,
+                int64_t items, const void** host_dev, int* wgs) {
+    if (T_total < 0 || T_dev < 0 || T_dev > T_total || host_wgs < 0 || D < 1 || row_stride < D) return MDL_E_ARG;
+    if (dtype != MDL_STORE_F32 && dtype != MDL_STORE_F16 && dtype != MDL_STORE_BF16) return MDL_E_ARG;
+    if ((T_dev > 0 && store == nullptr) || (T_dev < T_total && store_host == nullptr)) return MDL_E_ARG;
+    if (!host_aligned16(store) || !host_aligned16(store_host)) return MDL_E_ALIGN;
+    *host_dev = nullptr;
+    *wgs = 0;
+    if (T_dev == T_total || items == 0) return MDL_OK;
+    const int64_t esz = dtype == MDL_STORE_F32 ? 4 : 2, rows = T_total - T_dev;
+    if (rows > INT64_MAX / esz / row_stride) return MDL_E_ARG;
+    const int rc = device_view_of_tier(store_host, ((rows - 1) * row_stride + D) * esz, host_dev);
+    if (rc != MDL_OK) return rc;
+    if (!host_aligned16(*host_dev)) return MDL_E_ALIGN;
+    const int64_t want = host_wgs > 0 ? host_wgs : BS_HOST_WGS;
+    *wgs = (int)(want < items ? want : items);
+    return MDL_OK;
+}
+
+template <class T>
+int launch_tiered(const void* store, const void* store_host, int64_t T_dev, int64_t row_stride, int64_t T_total, const int64_t* off,
+                  int64_t n_bags, const int32_t* bag, const int64_t* key_id, int64_t R, int N, int D, int chunks, int host_wgs, uint64_t seed,
+                  uint64_t counter, float* out, int32_t* idx_out, hipStream_t stream) {
+    const bool vec = D % Vec<T>::E == 0 && row_stride % Vec<T>::E == 0;
+    const int64_t items = R * chunks;
+    const T* sd = reinterpret_cast<const T*>(store);
+    const T* sh = reinterpret_cast<const T*>(store_host);
+    const dim3 grid((unsigned)items), narrow((unsigned)host_wgs), block(BS_THREADS);
+    if (vec)
+        hipLaunchKernelGGL((bag_sample_tier_kernel<T, true, PASS_DEV>), grid, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off, n_bags,
+                           bag, key_id, N, D, chunks, items, seed, counter, out, idx_out);
+    else
+        hipLaunchKernelGGL((bag_sample_tier_kernel<T, false, PASS_DEV>), grid, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off, n_bags,
+                           bag, key_id, N, D, chunks, items, seed, counter, out, idx_out);
+    MDL_LAUNCH_CHECK();
+    if (host_wgs == 0) return MDL_OK;                           // no host tier
+    if (vec)
+        hipLaunchKernelGGL((bag_sample_tier_kernel<T, true, PASS_HOST>), narrow, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off,
+                           n_bags, bag, key_id, N, D, chunks, items, seed, counter, out, idx_out);
+    else
+        hipLaunchKernelGGL((bag_sample_tier_kernel<T, false, PASS_HOST>), narrow, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off,
+                           n_bags, bag, key_id, N, D, chunks, items, seed, counter, out, idx_out);
+    MDL_LAUNCH_CHECK();
+    return MDL_OK;
+}
+
+template <class T>
+int launch_pack_tiered(const void* store, const void* store_host, int64_t T_dev, int64_t row_stride, int64_t T_total, const int64_t* off,
+                       int64_t n_bags, const int32_t* bag, const int64_t* key_id, const int64_t* cu, const int64_t* chunk_cu, int R,
+                       int64_t n_chunks, int host_wgs, int64_t T_out, int D, uint64_t seed, uint64_t counter, float* out, int32_t* row_bag,
+                       int32_t* idx_out, hipStream_t stream) {
+    const bool vec = D % Vec<T>::E == 0 && row_stride % Vec<T>::E == 0;
+    const T* sd = reinterpret_cast<const T*>(store);
+    const T* sh = reinterpret_cast<const T*>(store_host);
+    const dim3 grid((unsigned)n_chunks), narrow((unsigned)host_wgs), block(BS_THREADS);
+    if (vec)
+        hipLaunchKernelGGL((bag_pack_tier_kernel<T, true, PASS_DEV>), grid, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off, n_bags,
+                           bag, key_id, cu, chunk_cu, R, n_chunks, T_out, D, seed, counter, out, row_bag, idx_out);
+    else
+        hipLaunchKernelGGL((bag_pack_tier_kernel<T, false, PASS_DEV>), grid, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off, n_bags,
+                           bag, key_id, cu, chunk_cu, R, n_chunks, T_out, D, seed, counter, out, row_bag, idx_out);
+    MDL_LAUNCH_CHECK();
+    if (host_wgs == 0) return MDL_OK;                           // no host tier
+    if (vec)
+        hipLaunchKernelGGL((bag_pack_tier_kernel<T, true, PASS_HOST>), narrow, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off,
+                           n_bags, bag, key_id, cu, chunk_cu, R, n_chunks, T_out, D, seed, counter, out, row_bag, idx_out);
+    else
+        hipLaunchKernelGGL((bag_pack_tier_kernel<T, false, PASS_HOST>), narrow, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off,
+                           n_bags, bag, key_id, cu, chunk_cu, R, n_chunks, T_out, D, seed, counter, out, row_bag, idx_out);
+    MDL_LAUNCH_CHECK();
+    return MDL_OK;
+}
+
+}  // namespace
+}  // namespace mdl
+
+extern "C" int mdl_bag_sample_tiered(const void* store, const void* store_host, int dtype, int64_t row_stride, int64_t T_total, int64_t T_dev,
+                                     const int64_t* off, int64_t n_bags, const int32_t* bag, const int64_t* key_id, int64_t R, int N, int D,
+                                     uint64_t seed, uint64_t counter, float* out, int32_t* idx_out, int host_wgs, void* stream) {
+    if (off == nullptr || bag == nullptr || out == nullptr) return MDL_E_ARG;
+    if (R < 0 || N < 1 || n_bags < 0) return MDL_E_ARG;
+    if (!host_aligned16(out)) return MDL_E_ALIGN;
+    if ((reinterpret_cast<uintptr_t>(off) & 7u) || (reinterpret_cast<uintptr_t>(bag) & 3u) || (reinterpret_cast<uintptr_t>(key_id) & 7u) ||
+        (reinterpret_cast<uintptr_t>(idx_out) & 3u))
+        return MDL_E_ALIGN;
+    const int chunks = (N + BS_TOK - 1) / BS_TOK;
+    if (R > 0x7FFFFFFF / (int64_t)N || R * chunks > 0x7FFFFFFF) return MDL_E_UNSUPPORTED;
+    const void* host_dev;
+    int wgs;
+    const int rc = check_tiers(store, store_host, dtype, row_stride, T_total, T_dev, D, host_wgs, R * chunks, &host_dev, &wgs);
+    if (rc != MDL_OK) return rc;
+    if (R == 0) return MDL_OK;
+    hipStream_t s = (hipStream_t)stream;
+    switch (dtype) {
+        case MDL_STORE_F32:
+            return launch_tiered<float>(store, host_dev, T_dev, row_stride, T_total, off, n_bags, bag, key_id, R, N, D, chunks, wgs, seed,
+                                        counter, out, idx_out, s);
+        case MDL_STORE_F16:
+            return launch_tiered<_Float16>(store, host_dev, T_dev, row_stride, T_total, off, n_bags, bag, key_id, R, N, D, chunks, wgs, seed,
+                                           counter, out, idx_out, s);
+        default:
+            return launch_tiered<bf16_t>(store, host_dev, T_dev, row_stride, T_total, off, n_bags, bag, key_id, R, N, D, chunks, wgs, seed,
+                                         counter, out, idx_out, s);
+    }
+}
+
+extern "C" int mdl_bag_pack_tiered(const void* store, const void* store_host, int dtype, int64_t row_stride, int64_t T_total, int64_t T_dev,
+                                   const int64_t* off, int64_t n_bags, const int32_t* bag, const int64_t* key_id, const int64_t* cu,
+                                   const int64_t* chunk_cu, int64_t R, int64_t n_chunks, int64_t T_out, int D, uint64_t seed, uint64_t counter,
+                                   float* out, int32_t* row_bag, int32_t* idx_out, int host_wgs, void* stream) {
+    if (off == nullptr || bag == nullptr || cu == nullptr || chunk_cu == nullptr || out == nullptr) return MDL_E_ARG;
+    if (R < 0 || n_chunks < 0 || T_out < 0 || n_bags < 0) return MDL_E_ARG;
+    if (!host_aligned16(out)) return MDL_E_ALIGN;
+    if ((reinterpret_cast<uintptr_t>(off) & 7u) || (reinterpret_cast<uintptr_t>(bag) & 3u) || (reinterpret_cast<uintptr_t>(key_id) & 7u) ||
+        (reinterpret_cast<uintptr_t>(cu) & 7u) || (reinterpret_cast<uintptr_t>(chunk_cu) & 7u) ||
+        (reinterpret_cast<uintptr_t>(row_bag) & 3u) || (reinterpret_cast<uintptr_t>(idx_out) & 3u))
+        return MDL_E_ALIGN;
+    if (R > 0x7FFFFFFF || T_out > 0x7FFFFFFF || n_chunks > 0x7FFFFFFF) return MDL_E_UNSUPPORTED;
+    const bool nothing = R == 0 || T_out == 0 || n_chunks == 0;
+    const void* host_dev;
+    int wgs;
+    const int rc = check_tiers(store, store_host, dtype, row_stride, T_total, T_dev, D, host_wgs, nothing ? 0 : n_chunks, &host_dev, &wgs);
+    if (rc != MDL_OK) return rc;
+    if (nothing) return MDL_OK;
+    hipStream_t s = (hipStream_t)stream;
+    switch (dtype) {
+        case MDL_STORE_F32:
+            return launch_pack_tiered<float>(store, host_dev, T_dev, row_stride, T_total, off, n_bags, bag, key_id, cu, chunk_cu, (int)R,
+                                             n_chunks, wgs, T_out, D, seed, counter, out, row_bag, idx_out, s);
+        case MDL_STORE_F16:
+            return launch_pack_tiered<_Float16>(store, host_dev, T_dev, row_stride, T_total, off, n_bags, bag, key_id, cu, chunk_cu, (int)R,
+                                                n_chunks, wgs, T_out, D, seed, counter, out, row_bag, idx_out, s);
+        default:
+            return launch_pack_tiered<bf16_t>(store, host_dev, T_dev, row_stride, T_total, off, n_bags, bag, key_id, cu, chunk_cu, (int)R,
+                                              n_chunks, wgs, T_out, D, seed, counter, out, row_bag, idx_out, s);
     }
 }

@@ -1762,3 +1762,86 @@ def bag_pack(store_rows, off, bag, key_id, cu, chunk_cu, n_rows, n_chunks, seed,
               int(counter) & _U64, out, row_bag, idx, _stream(),
               unsupported=("bag_pack: %d bags of %d rows in all exceed the int32 launch geometry", R, T))
     return (out, row_bag, idx) if return_indices else (out, row_bag)
+
+
+# ---- S3 / S4: the same two gathers over a store in two tiers (mdl_bag_sample_tiered / mdl_bag_pack_tiered) ----
+def _require_tiers(store_rows, host_rows):
+    """(device, D, row stride, T_dev, T_total) of a two-tier store: store_rows [T_dev, D] on the device, host_rows [T_host, D] in PINNED
+    host memory (None or no rows: no host tier), same dtype and row stride.  The pinned check is made here, before any native call: the
+    kernel reads the host tier over PCIe, and a launch on pageable memory is a GPU fault, not an error code."""
+    for t, name in ((store_rows, "store_rows"), (host_rows, "host_rows")):
+        if t is not None and (t.dim() != 2 or t.dtype not in STORE_DTYPES or (t.shape[1] > 1 and t.stride(1) != 1)):
+            raise RuntimeError("madeleine_amd: %s must be [T, D] float32 / float16 / bfloat16 with unit column stride" % name)
+    if host_rows is not None and host_rows.shape[0] == 0:
+        host_rows = None
+    if host_rows is not None:
+        if host_rows.dtype != store_rows.dtype or host_rows.shape[1] != store_rows.shape[1]:
+            raise RuntimeError("madeleine_amd: the two tiers must share dtype and width (got %s x %d and %s x %d)"
+                               % (store_rows.dtype, store_rows.shape[1], host_rows.dtype, host_rows.shape[1]))
+        if host_rows.is_cuda or not host_rows.is_pinned():
+            raise RuntimeError("madeleine_amd: host_rows must be pinned (registered) host memory (got %s, is_pinned() False): the "
+                               "kernel reads it over PCIe and never touches pageable memory" % host_rows.device)
+    if not store_rows.is_cuda:
+        raise RuntimeError("madeleine_amd: store_rows must live on a ROCm device (got %s); there is no CPU fallback" % store_rows.device)
+    D = store_rows.shape[1]
+    strides = {t.stride(0) for t in (store_rows, host_rows) if t is not None and t.shape[0] > 1} or {D}
+    if len(strides) != 1:
+        raise RuntimeError("madeleine_amd: the two tiers must share one row stride (got %s)" % sorted(strides))
+    T_dev = store_rows.shape[0]
+    return host_rows, D, strides.pop(), T_dev, T_dev + (0 if host_rows is None else host_rows.shape[0])
+
+
+def bag_sample_tiered(store_rows, host_rows, off, bag, key_id, n_tokens, seed, counter, return_indices=False, host_wgs=0):
+    """bag_sample over a store whose rows [0, T_dev) are store_rows (device) and rows [T_dev, T_total) host_rows (pinned host memory,
+    read over PCIe by a grid of host_wgs persistent workgroups; 0: the library's default).  off and bag address rows of [0, T_total).
+    The same draw, the same bits as bag_sample on the concatenation.  RuntimeError before any native call when host_rows is not
+    pinned."""
+    host_rows, D, stride, T_dev, T_total = _require_tiers(store_rows, host_rows)
+    _require(off, "off", torch.int64)
+    _require(bag, "bag", torch.int32)
+    if key_id is not None:
+        _require(key_id, "key_id", torch.int64)
+        if key_id.numel() != bag.numel():
+            raise RuntimeError("madeleine_amd: key_id and bag must have one entry per output row")
+    if off.dim() != 1 or off.numel() < 1:
+        raise RuntimeError("madeleine_amd: off must be [n_bags + 1]")
+    R, N = bag.numel(), int(n_tokens)
+    out = torch.empty(R, N, D, device=store_rows.device, dtype=torch.float32)
+    idx = torch.empty(R, N, device=store_rows.device, dtype=torch.int32) if return_indices else None
+    with _timed("bag_sample", ("byte", R * N * D * (4.0 + store_rows.element_size()))):
+        _call("mdl_bag_sample_tiered", store_rows if T_dev else None, host_rows, STORE_DTYPES[store_rows.dtype], stride, T_total, T_dev, off,
+              off.numel() - 1, bag, key_id, R, N, D, int(seed) & _U64, int(counter) & _U64, out, idx, int(host_wgs), _stream(),
+              unsupported=("bag_sample_tiered: %d output rows of %d tokens exceed the int32 launch geometry", R, N))
+    return (out, idx) if return_indices else out
+
+
+def bag_pack_tiered(store_rows, host_rows, off, bag, key_id, cu, chunk_cu, n_rows, n_chunks, seed, counter, return_indices=False,
+                    host_wgs=0):
+    """bag_pack over the two-tier store of bag_sample_tiered: the same outputs, bit for bit, as bag_pack on the concatenation."""
+    host_rows, D, stride, T_dev, T_total = _require_tiers(store_rows, host_rows)
+    _require(off, "off", torch.int64)
+    _require(bag, "bag", torch.int32)
+    _require(cu, "cu", torch.int64)
+    _require(chunk_cu, "chunk_cu", torch.int64)
+    if key_id is not None:
+        _require(key_id, "key_id", torch.int64)
+        if key_id.numel() != bag.numel():
+            raise RuntimeError("madeleine_amd: key_id and bag must have one entry per output bag")
+    if off.dim() != 1 or off.numel() < 1:
+        raise RuntimeError("madeleine_amd: off must be [n_bags + 1]")
+    R, T = bag.numel(), int(n_rows)
+    if cu.numel() != R + 1 or chunk_cu.numel() != R + 1:
+        raise RuntimeError("madeleine_amd: cu and chunk_cu must be [R + 1] = [%d]" % (R + 1))
+    if T < 0 or n_chunks < 0:
+        raise RuntimeError("madeleine_amd: bag_pack_tiered needs n_rows >= 0 and n_chunks >= 0")
+    out = torch.empty(T, D, device=store_rows.device, dtype=torch.float32)
+    row_bag = torch.empty(T, device=store_rows.device, dtype=torch.int32)
+    idx = torch.empty(T, device=store_rows.device, dtype=torch.int32) if return_indices else None
+    if R == 0 or T == 0:       # nothing to pack (an empty tensor has no address to pass)
+        return (out, row_bag, idx) if return_indices else (out, row_bag)
+    with _timed("bag_pack", ("byte", T * D * (4.0 + store_rows.element_size()))):
+        _call("mdl_bag_pack_tiered", store_rows if T_dev else None, host_rows, STORE_DTYPES[store_rows.dtype], stride, T_total, T_dev, off,
+              off.numel() - 1, bag, key_id, cu, chunk_cu, R, int(n_chunks), T, D, int(seed) & _U64, int(counter) & _U64, out, row_bag, idx,
+              int(host_wgs), _stream(),
+              unsupported=("bag_pack_tiered: %d bags of %d rows in all exceed the int32 launch geometry", R, T))
+    return (out, row_bag, idx) if return_indices else (out, row_bag)

@@ -16,7 +16,16 @@ stored: the kernel writes their zeros.
 The batches iterables yield exactly what collate() / ragged_collate() yield (`feats` already on the device), so train_loop and
 MADELEINE.forward take them unchanged.  There is no CPU fallback: a store may be BUILT on the CPU (packing logic, tests), sampling from
 it raises.
+
+Two tiers.  A cohort larger than HBM keeps a prefix of whole bags on the device (`rows`, at most `resident_bytes` bytes) and the rest
+in pinned host memory (`rows_host`); `resident_rows` = T_dev is the split, always at a bag boundary.  The tables and the draw keys
+address rows of [0, T_total) as before, the same kernels read a host-tier bag over PCIe (functional.bag_sample_tiered /
+bag_pack_tiered: a narrow persistent grid), and the batches are bit-equal to those of the resident store.  batches() and
+packed_batches() then gather one batch ahead of the step on a side stream (`prefetch`).
 """
+import collections
+import mmap
+import weakref
 from typing import List, NamedTuple, Optional, Tuple
 
 import torch
@@ -39,11 +48,22 @@ class PackedBags(NamedTuple):
 
 
 class DeviceSlideStore:
-    def __init__(self, bags, slide_ids, modalities, device, dtype=torch.float32):
+    def __init__(self, bags, slide_ids, modalities, device, dtype=torch.float32, resident_bytes=None):
         """bags: list over cases of lists over modalities of [n, D] CPU tensors, None for an absent stain.  dtype float16 / bfloat16:
-        an opt-in LOSSY store of half the size (features are rounded once, at load time; fp16 refuses a bag it cannot hold)."""
+        an opt-in LOSSY store of half the size (features are rounded once, at load time; fp16 refuses a bag it cannot hold).
+
+        resident_bytes None: the whole store in one device tensor.  An integer >= 0: at most that many bytes of rows go to HBM -- the
+        longest prefix of whole bags (stored order) that fits -- and the other bags to the host tier; 0 puts everything on the host, a
+        budget of the store's size or more leaves the host tier empty.  The host tier is ONE ordinary page-aligned host allocation of
+        exactly the tier's bytes (an anonymous mapping), registered with the runtime (hipHostRegister): the pinned size is the
+        tier's size rounded up to a page, not the next power of two that torch's caching host allocator would pin.
+        It is never pageable to the device and never managed memory, and it is unregistered when the store is collected.  Each
+        process pins its own host tier: the ranks of a node do not share one.  On a CPU `device` (build-only mode) the host tier is
+        an ordinary unpinned tensor."""
         if dtype not in MF.STORE_DTYPES:
             raise ValueError("DeviceSlideStore: dtype must be float32, float16 or bfloat16 (got %s)" % dtype)
+        if resident_bytes is not None and (isinstance(resident_bytes, bool) or not isinstance(resident_bytes, int) or resident_bytes < 0):
+            raise ValueError("DeviceSlideStore: resident_bytes must be None or an integer >= 0 (got %r)" % (resident_bytes,))
         self.modalities = list(modalities)
         self.slide_ids = list(slide_ids)
         self.device, self.dtype = torch.device(device), dtype
@@ -84,16 +104,43 @@ class DeviceSlideStore:
         self.bag_lens_cpu = torch.tensor(lens, dtype=torch.int64)
         self.off_cpu[1:] = torch.cumsum(self.bag_lens_cpu, 0)
         total = int(self.off_cpu[-1])
-        nbytes = total * D * torch.empty(0, dtype=dtype).element_size()
+        row_bytes = D * torch.empty(0, dtype=dtype).element_size()
+        n_res = len(lens)                                       # resident bags: the longest prefix of whole bags inside the budget
+        if resident_bytes is not None:
+            n_res = int(torch.searchsorted(self.off_cpu, resident_bytes // row_bytes, right=True)) - 1
+        self.resident_rows = T_dev = int(self.off_cpu[n_res])
+        nbytes = T_dev * row_bytes
         if self.device.type == "cuda":
             free, capacity = torch.cuda.mem_get_info(self.device)
             if nbytes > free:
                 raise RuntimeError("DeviceSlideStore: the store needs %d bytes (%d rows x %d x %s) but %s has %d bytes free of %d"
-                                   % (nbytes, total, D, dtype, self.device, free, capacity))
-        self.rows = torch.empty(total, D, dtype=dtype, device=self.device)
-        self._upload(present)
+                                   % (nbytes, T_dev, D, dtype, self.device, free, capacity))
+        self.rows = torch.empty(T_dev, D, dtype=dtype, device=self.device)
+        self.rows_host = self._host_tier(total - T_dev) if T_dev < total else None
+        self._upload(present[:n_res])
+        off = self.off_cpu.tolist()
+        for g in range(n_res, len(present)):                    # cast straight into place: no second copy of the cohort
+            self.rows_host[off[g] - T_dev:off[g + 1] - T_dev].copy_(present[g])
         self.off = self.off_cpu.to(self.device)
         self._zero_bag = None
+        self._side = None                                       # the prefetch stream: one per store, made on first use
+
+    def _host_tier(self, n_rows):
+        """[n_rows, D] of the store's dtype in host memory: registered (pinned) on a GPU device, an ordinary tensor on the CPU."""
+        if self.device.type != "cuda":
+            return torch.empty(n_rows, self.dim, dtype=self.dtype)
+        nbytes = n_rows * self.dim * torch.empty(0, dtype=self.dtype).element_size()
+        raw = mmap.mmap(-1, nbytes)                             # anonymous, page-aligned, the tier's size rounded up to a page
+        tier = torch.frombuffer(raw, dtype=self.dtype).view(n_rows, self.dim)      # zero-copy: the tensor's storage IS the mapping
+        with torch.cuda.device(self.device):
+            rt = torch.cuda.cudart()
+            err = int(rt.cudaHostRegister(tier.data_ptr(), nbytes, 0))
+        if err != 0:
+            raise RuntimeError("DeviceSlideStore: registering the %d-byte host tier failed (hipError_t %d)" % (nbytes, err))
+        weakref.finalize(self, _unregister, rt, tier.data_ptr(), raw)      # `raw` stays alive until the registration is gone
+        if not tier.is_pinned():
+            raise RuntimeError("DeviceSlideStore: the registered host tier does not report is_pinned()")
+        return tier
 
     def _upload(self, present):
         """One bag at a time through two pinned staging buffers (the cast to the store's dtype happens in the host copy): the cohort is
@@ -102,6 +149,8 @@ class DeviceSlideStore:
         if self.device.type != "cuda":
             for g, bag in enumerate(present):
                 self.rows[off[g]:off[g + 1]].copy_(bag)
+            return
+        if not present:
             return
         longest = max(int(b.shape[0]) for b in present)
         stage = [torch.empty(longest, self.dim, dtype=self.dtype).pin_memory() for _ in range(2)]
@@ -119,7 +168,7 @@ class DeviceSlideStore:
             torch.cuda.current_stream().synchronize()
 
     @classmethod
-    def from_dataset(cls, dataset, device, dtype=torch.float32):
+    def from_dataset(cls, dataset, device, dtype=torch.float32, resident_bytes=None):
         """One pass over a SlideDataset(sample=-1, train=True): keeps feats[m] where the label is 1 and drops the 2-token zero bags."""
         if getattr(dataset, "sample", -1) != -1 or not getattr(dataset, "train", True):
             raise ValueError("DeviceSlideStore.from_dataset needs a SlideDataset(sample=-1, train=True): whole bags, every stain")
@@ -128,7 +177,7 @@ class DeviceSlideStore:
             item = dataset[i]
             bags.append([f if int(lab) == 1 else None for f, lab in zip(item['feats'], item['modality_labels'])])
             ids.append(item['slide_id'])
-        return cls(bags, ids, dataset.modalities, device, dtype=dtype)
+        return cls(bags, ids, dataset.modalities, device, dtype=dtype, resident_bytes=resident_bytes)
 
     def __len__(self):
         return len(self.slide_ids)
@@ -137,8 +186,13 @@ class DeviceSlideStore:
     def n_bags(self) -> int:
         return self.off_cpu.numel() - 1
 
-    def nbytes(self) -> int:
-        return self.rows.numel() * self.rows.element_size()
+    def nbytes(self, tier=None) -> int:
+        """Bytes of stored rows: tier None both tiers, "device" the rows in HBM, "host" the rows in pinned host memory."""
+        if tier not in (None, "device", "host"):
+            raise ValueError("DeviceSlideStore.nbytes: tier must be None, 'device' or 'host' (got %r)" % (tier,))
+        dev = self.rows.numel() * self.rows.element_size()
+        host = 0 if self.rows_host is None else self.rows_host.numel() * self.rows_host.element_size()
+        return dev if tier == "device" else host if tier == "host" else dev + host
 
     def _cases(self, case_indices) -> torch.Tensor:
         idx = torch.as_tensor(case_indices, dtype=torch.int64).reshape(-1)
@@ -146,37 +200,52 @@ class DeviceSlideStore:
             raise IndexError("DeviceSlideStore: case index outside [0, %d)" % len(self))
         return idx
 
-    def sample(self, case_indices, n_tokens, counter, seed=None, return_indices=False):
+    def sample(self, case_indices, n_tokens, counter, seed=None, return_indices=False, host_wgs=0):
         """feats [B, M, n_tokens, D] fp32 on the device: SlideDataset.sample_n of every bag of the cases + collate, absent stains as
         zeros.  A bag's draw is a function of (seed, counter, its stored bag id): a case draws the same rows whatever its batch mates.
         The only upload is the batch's [B * M] int32 bag table.  return_indices: also idx [B, M, n_tokens] int32 (row inside the bag,
-        -1 for an absent stain).  seed None is seed 0; batches() passes its own seed."""
+        -1 for an absent stain).  seed None is seed 0; batches() passes its own seed.  host_wgs: the grid of the pass that reads the
+        host tier (0: the library's default); without a host tier it is not used."""
         if self.device.type != "cuda":
             raise RuntimeError("DeviceSlideStore.sample: the store lives on %s; the HIP kernel is the only backend (no CPU fallback)"
                                % self.device)
         idx = self._cases(case_indices)
         B, M = idx.numel(), len(self.modalities)
         bag = MF.h2d(self.bag_table.index_select(0, idx).reshape(-1), self.device)
-        res = MF.bag_sample(self.rows, self.off, bag, None, n_tokens, 0 if seed is None else seed, counter, return_indices)
+        if self.rows_host is None:
+            res = MF.bag_sample(self.rows, self.off, bag, None, n_tokens, 0 if seed is None else seed, counter, return_indices)
+        else:
+            res = MF.bag_sample_tiered(self.rows, self.rows_host, self.off, bag, None, n_tokens, 0 if seed is None else seed, counter,
+                                       return_indices, host_wgs=host_wgs)
         if return_indices:
             return res[0].view(B, M, n_tokens, self.dim), res[1].view(B, M, n_tokens)
         return res.view(B, M, n_tokens, self.dim)
 
     def bag_view(self, case: int, modality: int) -> Optional[torch.Tensor]:
-        """The stored rows of one bag as a zero-copy view of the store, None for an absent stain."""
+        """The stored rows of one bag as a zero-copy view of the store, None for an absent stain.  ValueError for a bag in the host
+        tier: the model would read such a view over PCIe on every pass."""
         g = int(self.bag_table[case, modality])
+        if g >= 0 and int(self.off_cpu[g + 1]) > self.resident_rows:
+            raise ValueError("DeviceSlideStore.bag_view: the bag of case %d, modality %d is in the host tier; a view of it would be read "
+                             "over PCIe on every pass -- use pack() / packed_batches()" % (case, modality))
         return None if g < 0 else self.rows[int(self.off_cpu[g]):int(self.off_cpu[g + 1])]
 
-    def batches(self, batch_size, n_tokens, shuffle=True, drop_last=False, seed=0, rank=0, world_size=1):
+    def batches(self, batch_size, n_tokens, shuffle=True, drop_last=False, seed=0, rank=0, world_size=1, prefetch=None):
         """Re-iterable over collate()-shaped dicts {'feats' [B, M, n_tokens, D] on the device, 'modality_labels' CPU float [B, M],
-        'slide_ids'}: the drop-in for DataLoader(SlideDataset(sample=n_tokens), collate_fn=collate)."""
-        return StoreBatches(self, batch_size, n_tokens, shuffle, drop_last, seed, rank, world_size, ragged=False)
+        'slide_ids'}: the drop-in for DataLoader(SlideDataset(sample=n_tokens), collate_fn=collate).  prefetch k >= 1: the gathers of
+        the next k batches of the epoch run on the store's side stream while the consumer works (None: 1 with a host tier, else 0 = gather on
+        the current stream when the batch is asked for).  The batches do not depend on it."""
+        return StoreBatches(self, batch_size, n_tokens, shuffle, drop_last, seed, rank, world_size, ragged=False, prefetch=prefetch)
 
     def ragged_batches(self, batch_size, shuffle=True, drop_last=False, seed=0, rank=0, world_size=1):
         """Re-iterable over ragged_collate()-shaped dicts {'bags', 'modality_labels', 'slide_ids'}: a present stain's bag is a zero-copy
         view of the store, an absent stain's the dataset's [2, D] zero bag.  Needs an fp32 store (the model reads the views as they are)."""
         if self.dtype != torch.float32:
             raise ValueError("DeviceSlideStore.ragged_batches needs a float32 store (this one is %s): the bags are views of it" % self.dtype)
+        if self.rows_host is not None:
+            raise ValueError("DeviceSlideStore.ragged_batches: %d of the %d stored bags are in the host tier and the bags are zero-copy "
+                             "views, which the model would read over PCIe on every pass -- use packed_batches()"
+                             % (self.n_bags - int((self.off_cpu[1:] <= self.resident_rows).sum()), self.n_bags))
         return StoreBatches(self, batch_size, None, shuffle, drop_last, seed, rank, world_size, ragged=True)
 
     def _pack_plan(self, case_indices, max_tokens):
@@ -194,11 +263,11 @@ class DeviceSlideStore:
         of them when a cap is given), 2 for an absent stain (the dataset's zero bag).  Host only."""
         return self._pack_plan(case_indices, max_tokens)[1].tolist()
 
-    def pack(self, case_indices, max_tokens=None, counter=0, seed=None, return_indices=False) -> PackedBags:
+    def pack(self, case_indices, max_tokens=None, counter=0, seed=None, return_indices=False, host_wgs=0) -> PackedBags:
         """The ragged batch of the cases, packed: every present bag whole and in stored order, or -- when it has more than max_tokens
         rows -- max_tokens of its rows drawn without replacement (the rows sample(..., max_tokens, counter, seed) draws for it); an
         absent stain as 2 rows of zeros.  One launch, from a store of any dtype; the only upload is one O(R) table (cu_seqlens, the
-        chunk table of the launch and the bags); no host read and no host work per token."""
+        chunk table of the launch and the bags); no host read and no host work per token.  host_wgs: as in sample()."""
         if self.device.type != "cuda":
             raise RuntimeError("DeviceSlideStore.pack: the store lives on %s; the HIP kernel is the only backend (no CPU fallback)"
                                % self.device)
@@ -211,18 +280,29 @@ class DeviceSlideStore:
         T, n_chunks = int(host[R]), int(host[2 * R + 1])
         table = MF.h2d(host, self.device)
         cu = table[:R + 1]
-        res = MF.bag_pack(self.rows, self.off, table[2 * R + 2:].view(torch.int32)[:R], None, cu, table[R + 1:2 * R + 2], T, n_chunks,
-                          0 if seed is None else seed, counter, return_indices)
+        if self.rows_host is None:
+            res = MF.bag_pack(self.rows, self.off, table[2 * R + 2:].view(torch.int32)[:R], None, cu, table[R + 1:2 * R + 2], T, n_chunks,
+                              0 if seed is None else seed, counter, return_indices)
+        else:
+            res = MF.bag_pack_tiered(self.rows, self.rows_host, self.off, table[2 * R + 2:].view(torch.int32)[:R], None, cu,
+                                     table[R + 1:2 * R + 2], T, n_chunks, 0 if seed is None else seed, counter, return_indices,
+                                     host_wgs=host_wgs)
         return PackedBags(res[0], cu, tuple(lens.tolist()), res[1], res[2] if return_indices else None)
 
-    def packed_batches(self, batch_size, max_tokens=None, shuffle=True, drop_last=False, seed=0, rank=0, world_size=1):
+    def packed_batches(self, batch_size, max_tokens=None, shuffle=True, drop_last=False, seed=0, rank=0, world_size=1, prefetch=None):
         """Re-iterable over {'packed': PackedBags, 'modality_labels', 'slide_ids'}: the ragged batches of ragged_batches() in packed
         form, from a store of any dtype, every bag cut to at most max_tokens rows.  Plan, sharding, set_epoch and the draw counter are
-        those of batches()."""
+        those of batches(), and so is prefetch."""
         if max_tokens is not None and max_tokens < 1:
             raise ValueError("DeviceSlideStore: max_tokens must be at least 1 (got %s)" % max_tokens)
         return StoreBatches(self, batch_size, None, shuffle, drop_last, seed, rank, world_size, ragged=True, packed=True,
-                            max_tokens=max_tokens)
+                            max_tokens=max_tokens, prefetch=prefetch)
+
+    def _side_stream(self):
+        """The store's one prefetch stream (a process has few hardware queues: it is never made per epoch or per iterator)."""
+        if self._side is None:
+            self._side = torch.cuda.Stream(self.device)
+        return self._side
 
     def _absent_bag(self) -> torch.Tensor:
         if self._zero_bag is None:
@@ -230,14 +310,25 @@ class DeviceSlideStore:
         return self._zero_bag
 
 
+def _unregister(rt, ptr, raw):
+    rt.cudaHostUnregister(ptr)
+    del raw
+
+
 class StoreBatches:
     """What DeviceSlideStore.batches / ragged_batches / packed_batches return.  plan(epoch) is host-only and a function of (seed,
     epoch, rank, world_size): rank r owns the static shard r::world_size of the cases and shuffles inside it.  The draw counter of a
     batch is (epoch, batch number), so a run resumed at an epoch redraws the same batches.  set_epoch(e) before each epoch, as with
-    DistributedSampler."""
+    DistributedSampler.
+
+    prefetch = k >= 1 (dense and packed batches): when batch i is yielded the gathers of batches i + 1 .. i + k of the same epoch's plan,
+    table uploads included, are already queued on the store's side stream.  At yield the current stream waits on the batch's event and
+    the tensors are recorded for it, so the consumer uses them at once; the host is never synchronised.  Counters are those of
+    prefetch = 0, so the batches are the same bits.  An iterator belongs to the epoch it was made in (prefetch never crosses
+    set_epoch); dropping it mid-epoch leaves at most k gathers finishing into tensors nobody reads."""
 
     def __init__(self, store, batch_size, n_tokens, shuffle, drop_last, seed, rank, world_size, ragged, packed=False,
-                 max_tokens=None):
+                 max_tokens=None, prefetch=None):
         if batch_size < 1 or world_size < 1 or not 0 <= rank < world_size:
             raise ValueError("StoreBatches: batch_size >= 1 and 0 <= rank < world_size are required")
         if not ragged and n_tokens < 1:
@@ -246,6 +337,11 @@ class StoreBatches:
         self.shuffle, self.drop_last, self.seed = bool(shuffle), bool(drop_last), int(seed)
         self.rank, self.world_size, self.ragged = int(rank), int(world_size), bool(ragged)
         self.packed, self.max_tokens = bool(packed), max_tokens
+        if prefetch is None:
+            prefetch = 1 if store.rows_host is not None else 0
+        if isinstance(prefetch, bool) or not isinstance(prefetch, int) or prefetch < 0:
+            raise ValueError("StoreBatches: prefetch must be None or an integer >= 0 (got %r)" % (prefetch,))
+        self.prefetch = prefetch if (self.packed or not self.ragged) else 0      # zero-copy views have nothing to fetch
         self.epoch = 0
 
     def set_epoch(self, epoch: int):
@@ -270,16 +366,39 @@ class StoreBatches:
             out.pop()
         return out
 
+    def _batch(self, epoch, batch_no, cases):
+        """Batch `batch_no` of `epoch`, gathered on the current stream."""
+        st = self.store
+        out = {"modality_labels": st.modality_labels.index_select(0, torch.tensor(cases, dtype=torch.int64)),
+               "slide_ids": [st.slide_ids[c] for c in cases]}
+        if self.packed:
+            out["packed"] = st.pack(cases, self.max_tokens, counter=(epoch << 32) | batch_no, seed=self.seed)
+        elif self.ragged:
+            out["bags"] = [[st.bag_view(c, m) if int(st.bag_table[c, m]) >= 0 else st._absent_bag()
+                            for m in range(len(st.modalities))] for c in cases]
+        else:
+            out["feats"] = st.sample(cases, self.n_tokens, counter=(epoch << 32) | batch_no, seed=self.seed)
+        return out
+
     def __iter__(self):
-        st, epoch = self.store, self.epoch
-        for batch_no, cases in enumerate(self.plan(epoch)):
-            out = {"modality_labels": st.modality_labels.index_select(0, torch.tensor(cases, dtype=torch.int64)),
-                   "slide_ids": [st.slide_ids[c] for c in cases]}
-            if self.packed:
-                out["packed"] = st.pack(cases, self.max_tokens, counter=(epoch << 32) | batch_no, seed=self.seed)
-            elif self.ragged:
-                out["bags"] = [[st.bag_view(c, m) if int(st.bag_table[c, m]) >= 0 else st._absent_bag()
-                                for m in range(len(st.modalities))] for c in cases]
-            else:
-                out["feats"] = st.sample(cases, self.n_tokens, counter=(epoch << 32) | batch_no, seed=self.seed)
+        epoch, plan = self.epoch, self.plan(self.epoch)
+        if self.prefetch == 0:
+            for batch_no, cases in enumerate(plan):
+                yield self._batch(epoch, batch_no, cases)
+            return
+        side, queued = self.store._side_stream(), collections.deque()
+        for batch_no in range(len(plan)):
+            while len(queued) <= self.prefetch and batch_no + len(queued) < len(plan):
+                nxt = batch_no + len(queued)
+                with torch.cuda.stream(side):
+                    out = self._batch(epoch, nxt, plan[nxt])
+                    done = torch.cuda.Event()
+                    done.record(side)
+                queued.append((out, done))
+            out, done = queued.popleft()
+            cur = torch.cuda.current_stream(self.store.device)
+            cur.wait_event(done)
+            p = out.get("packed")
+            for t in (out["feats"],) if p is None else (p.tokens, p.cu_seqlens, p.row_bag):
+                t.record_stream(cur)                            # allocated on the side stream, used on this one
             yield out

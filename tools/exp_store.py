@@ -26,8 +26,19 @@ stain-encoding tokens), with device events after warm-up:
   5. the config-5 training step (InfoNCE + GOT, stain encoding) fed by packed_batches against the same step fed by ragged_batches on
      the fp32 store, in alternating rounds.
 
+--tier measures the two-tier store (rows partly or wholly in pinned host memory, read over PCIe by the gather's narrow persistent grid) on
+config 2's geometry, over --tier-cases cases x 2 stains of --tier-rows rows (an epoch of several batches, so that prefetch has a next
+batch to fetch), with device events after warm-up, medians (min-max), the legs alternating inside one loop:
+  6. the link: a pinned-to-device copy_ of one batch's payload (contiguous; the box's PCIe rate) next to the gather of a whole batch from
+     an all-host fp32 store and from an all-host bf16 store, for host_wgs in {8, 16, 32, 64, 128, 256} and one workgroup per item
+     (chip-wide); rate = payload read over PCIe / time.  And, by the host clock, what a tiered call costs the host per launch.
+  7. the config-2 step fed by (a) the resident store, (b) the all-host fp32 store with prefetch=1, (c) the same with prefetch=0,
+     (d) a store with half its bytes resident, prefetch=1 -- alternating rounds; every round is one epoch whose first step is run
+     untimed (it fills the prefetch queue) -- and (e) the `host` DataLoader feed in a phase of its own, next to (a) and (b).
+
 Usage: python tools/exp_store.py [--rows 20000] [--launches 20] [--steps 20] [--round-steps 5] [--workers 6] [--out FILE]
-       python tools/exp_store.py --pack [--launches 20] [--steps 12] [--round-steps 3] [--cap 4096] [--skip-step] [--out FILE]"""
+       python tools/exp_store.py --pack [--launches 20] [--steps 12] [--round-steps 3] [--cap 4096] [--skip-step] [--out FILE]
+       python tools/exp_store.py --tier [--tier-cases 192] [--tier-rows 4096] [--launches 10] [--steps 20] [--round-steps 5] [--out FILE]"""
 import argparse
 import json
 import os
@@ -233,6 +244,178 @@ def pack_leg(a, dev):
     return lines, res
 
 
+def tier_leg(a, dev):
+    """Measurements 6-7 of the module docstring.  Returns (lines, results)."""
+    B, M, N, D, _got, stain = BN.CONFIGS["c2"]
+    mods = BN.MODS5[:M]
+    n_cases = a.tier_cases
+    g = torch.Generator().manual_seed(7)
+    bags = [[torch.randn(a.tier_rows, D, generator=g) for _ in range(M)] for _ in range(n_cases)]
+    ids = ["case%05d" % i for i in range(n_cases)]
+    cases = list(range(B))
+    lines, res = [], {"geometry": {"cases": n_cases, "stains": M, "rows_per_bag": a.tier_rows, "D": D, "N": N, "batch": B}}
+    fmt = lambda v: "%.3f ms (%.3f-%.3f)" % (statistics.median(v), min(v), max(v))      # noqa: E731
+
+    # ---- 6. the link
+    res["link"] = {}
+    wgs_list = [8, 16, 32, 64, 128, 256, 1 << 30]                # the last: cut to the items, one workgroup per item (chip-wide)
+    for dtype in (torch.float32, torch.bfloat16):
+        st = DeviceSlideStore(bags, ids, mods, dev, dtype=dtype, resident_bytes=0)
+        esz = st.rows_host.element_size()
+        payload = B * M * N * D * esz                            # bytes read over PCIe per batch
+        src = torch.empty(B * M * N * D, dtype=dtype).pin_memory()
+        dst = torch.empty(B * M * N * D, dtype=dtype, device=dev)
+        legs = {"copy": lambda i: dst.copy_(src, non_blocking=True)}
+        for w in wgs_list:
+            legs["wgs%d" % w if w < 1 << 30 else "chip_wide"] = lambda i, w=w: st.sample(cases, N, counter=i, host_wgs=w)
+        for f in legs.values():
+            for i in range(2):
+                f(i)
+        times = {k: [] for k in legs}
+        names = list(legs)
+        for i in range(a.launches):
+            for k in (names if i % 2 == 0 else names[::-1]):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                out = legs[k](100 + i)
+                e1.record()
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1))
+                del out
+        r = {k: {"ms": stats(v), "GBps_median": payload / statistics.median(v) * 1e-6} for k, v in times.items()}
+        grids = [k for k in names if k != "copy"]
+        best = min(grids, key=lambda k: r[k]["ms"]["median"])
+        default = next(k for k in grids if r[best]["ms"]["min"] <= r[k]["ms"]["median"] <= r[best]["ms"]["max"])
+        r["payload_bytes"], r["best"], r["smallest_within_best_range"] = payload, best, default
+        r["gather_over_copy_rate"] = r[default]["GBps_median"] / r["copy"]["GBps_median"]
+        res["link"][str(dtype)] = r
+        lines.append("link, %s, %.3f GB per batch over PCIe:" % (dtype, payload * 1e-9))
+        for k in names:
+            lines.append("  %-10s %s = %.1f GB/s" % (k, fmt(times[k]), r[k]["GBps_median"]))
+        lines.append("  best grid %s; smallest grid whose median is inside the best's min-max: %s, at %.3f of the copy's rate"
+                     % (best, default, r["gather_over_copy_rate"]))
+        if dtype == torch.float32:
+            st_host = st
+        del src, dst, legs
+    del st
+
+    # what a tiered call costs the host: 300 launches of a 1-row, 1-token gather each, host clock, the device drained before and after
+    st_res = DeviceSlideStore(bags, ids, mods, dev)
+    one = MF.h2d(st_res.bag_table[:1, :1].reshape(-1), dev)
+    calls = {"S1 (one launch)": lambda: MF.bag_sample(st_res.rows, st_res.off, one, None, 1, 0, 0),
+             "S3, no host tier (one launch, no query)": lambda: MF.bag_sample_tiered(st_res.rows, None, st_res.off, one, None, 1, 0, 0),
+             "S3, host tier (two launches, the queries)": lambda: MF.bag_sample_tiered(st_host.rows, st_host.rows_host, st_host.off, one, None,
+                                                                                       1, 0, 0)}
+    res["host_cost_us_per_call"] = {}
+    for k, f in calls.items():
+        per = []
+        for rep in range(5):
+            f()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(300):
+                f()
+            per.append((time.perf_counter() - t0) / 300 * 1e6)
+            torch.cuda.synchronize()
+        res["host_cost_us_per_call"][k] = stats(per)
+        lines.append("host clock per call, %-42s median %.2f us (min %.2f max %.2f)" % (k, statistics.median(per), min(per), max(per)))
+
+    # ---- 7. the step
+    if not a.skip_step:
+        torch.manual_seed(42)
+        model = MADELEINE(BN.make_cfg(M, D), stain_encoding=stain).to(dev).train()
+        opt = torch.optim.AdamW(model.parameters(), lr=1e-4, fused=True)
+        crit = InfoNCE(temperature=0.001)
+        largs = SimpleNamespace(global_loss="info-nce", symmetric_cl=True, local_loss_weight=1.0)
+
+        def step(data):
+            opt.zero_grad(set_to_none=True)
+            embs, toks = model(data, device=dev)
+            loss, _ = calculate_losses(mods[1:], crit, None, None, embs, toks, data["modality_labels"][:, 1:], largs)
+            loss.backward()
+            opt.step()
+        st_half = DeviceSlideStore(bags, ids, mods, dev, resident_bytes=st_res.nbytes() // 2)
+        res["stores"] = {"resident": st_res.nbytes("device"), "all_host": st_host.nbytes("host"),
+                         "half": [st_half.nbytes("device"), st_half.nbytes("host")]}
+        loaders = {"a_resident": st_res.batches(B, N, shuffle=True, seed=1), "b_host_prefetch1": st_host.batches(B, N, shuffle=True, seed=1, prefetch=1),
+                   "c_host_prefetch0": st_host.batches(B, N, shuffle=True, seed=1, prefetch=0),
+                   "d_half_prefetch1": st_half.batches(B, N, shuffle=True, seed=1, prefetch=1)}
+        if len(loaders["a_resident"]) <= a.round_steps:
+            raise SystemExit("--tier-cases must give more than --round-steps batches per epoch")
+        epoch = [0]
+
+        def timed_round(k):
+            """One epoch of loader k: the first step untimed (it fills the prefetch queue), then round_steps timed steps."""
+            loaders[k].set_epoch(epoch[0])
+            epoch[0] += 1
+            it = iter(loaders[k])
+            step(next(it))
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(a.round_steps):
+                step(next(it))
+            e1.record()
+            e1.synchronize()
+            it.close()
+            return e0.elapsed_time(e1) / a.round_steps
+        rounds = max(1, a.steps // a.round_steps)
+        for k in loaders:
+            timed_round(k)                                       # warm-up
+        times = {k: [] for k in loaders}
+        for r in range(rounds):
+            for k in (sorted(loaders) if r % 2 == 0 else sorted(loaders, reverse=True)):
+                times[k].append(timed_round(k))
+        med = {k: statistics.median(v) for k, v in times.items()}
+        res["step"] = {"rounds": rounds, "steps_per_round": a.round_steps, "rounds_ms": times, "step_ms": {k: stats(v) for k, v in times.items()},
+                       "b_minus_a_ms": med["b_host_prefetch1"] - med["a_resident"],
+                       "a_round_range_ms": max(times["a_resident"]) - min(times["a_resident"]),
+                       "c_minus_a_ms": med["c_host_prefetch0"] - med["a_resident"], "d_minus_a_ms": med["d_half_prefetch1"] - med["a_resident"]}
+        lines.append("config-2 step, %d rounds of %d timed steps per feed:" % (rounds, a.round_steps))
+        for k, v in sorted(times.items()):
+            lines.append("  fed by %-17s median %.3f ms  min %.3f  max %.3f   rounds: %s" % (k, med[k], min(v), max(v), " ".join("%.3f" % x for x in v)))
+        lines.append("  (b) - (a) = %.3f ms, (a)'s round range %.3f ms;  (c) - (a) = %.3f ms;  (d) - (a) = %.3f ms"
+                     % (res["step"]["b_minus_a_ms"], res["step"]["a_round_range_ms"], res["step"]["c_minus_a_ms"], res["step"]["d_minus_a_ms"]))
+
+        # (e): the host DataLoader feed in a phase of its own, next to (a) and (b)
+        drain = a.workers + 6
+        total = a.warmup + rounds * (drain + a.round_steps) + 4
+        loader = torch.utils.data.DataLoader(HostCohort(bags, N, -(-total * B // n_cases) + 1), batch_size=B, shuffle=False, collate_fn=collate,
+                                             num_workers=a.workers, pin_memory=True, prefetch_factor=1 if a.workers else None)
+        fed = iter(DevicePrefetcher(loader, dev, depth=2))
+        for _ in range(a.warmup):
+            step(next(fed))
+        torch.cuda.synchronize()
+        phase = {"e_host_loader": [], "a_resident": [], "b_host_prefetch1": []}
+        for r in range(rounds):
+            for k in (sorted(phase) if r % 2 == 0 else sorted(phase, reverse=True)):
+                if k != "e_host_loader":
+                    phase[k].append(timed_round(k))
+                    continue
+                for _ in range(drain):
+                    step(next(fed))
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(a.round_steps):
+                    step(next(fed))
+                e1.record()
+                e1.synchronize()
+                phase[k].append(e0.elapsed_time(e1) / a.round_steps)
+        fed.close()
+        b_all = times["b_host_prefetch1"] + phase["b_host_prefetch1"]
+        holds = max(b_all) < min(phase["e_host_loader"])
+        res["host_phase"] = {"rounds_ms": phase, "step_ms": {k: stats(v) for k, v in phase.items()}, "workers": a.workers,
+                             "slowest_b_round_ms": max(b_all), "fastest_e_round_ms": min(phase["e_host_loader"]), "required_holds": holds}
+        lines.append("phase of the host DataLoader feed (%d workers), next to (a) and (b):" % a.workers)
+        for k, v in sorted(phase.items()):
+            lines.append("  fed by %-17s median %.3f ms  min %.3f  max %.3f   rounds: %s"
+                         % (k, statistics.median(v), min(v), max(v), " ".join("%.3f" % x for x in v)))
+        lines.append("  required: slowest round of (b), both phases, %.3f ms < fastest round of (e) %.3f ms: %s"
+                     % (max(b_all), min(phase["e_host_loader"]), "HOLDS" if holds else "DOES NOT HOLD"))
+    return lines, res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=20000)
@@ -247,10 +430,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--pack", action="store_true", help="measure the packed ragged route (config 5's shape) instead")
     ap.add_argument("--cap", type=int, default=4096, help="max_tokens of the capped pack of --pack")
+    ap.add_argument("--tier", action="store_true", help="measure the two-tier store (host tier read over PCIe) instead")
+    ap.add_argument("--tier-cases", type=int, default=192, help="cases of the cohort of --tier: more than --round-steps batches per epoch")
+    ap.add_argument("--tier-rows", type=int, default=4096, help="rows per bag of the cohort of --tier")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    if a.pack:
-        lines, res = pack_leg(a, dev)
+    if a.pack or a.tier:
+        lines, res = (pack_leg if a.pack else tier_leg)(a, dev)
         report(lines, res, a.out)
         return
     B, M, N, D, _got, stain = BN.CONFIGS["c2"]
