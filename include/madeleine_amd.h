@@ -773,6 +773,59 @@ int mdl_bag_pack_tiered(const void* store, const void* store_host, int dtype, in
                         const int64_t* chunk_cu, int64_t R, int64_t n_chunks, int64_t T_out, int D, uint64_t seed, uint64_t counter,
                         float* out, int32_t* row_bag, int32_t* idx_out, int host_wgs, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * P1-P3 -- the few-shot linear probe: P independent L2-regularised logistic fits over one embedding matrix, the decision values of
+ * every case under every fit, and confusion matrix + AUC per fit (ABI 26, additive).  Replaces, for all (task, k, fold) problems of an
+ * evaluation at once, bin/run_linear_probing.py:150-170: LogisticRegression(C=1, max_iter=10000).fit / .predict / .predict_proba
+ * (:150-155), roc_auc_score (:46, :49) and the counts behind balanced_accuracy_score / cohen_kappa_score (:50, :163-164).
+ *
+ * X [S, d] fp32, row stride ldX >= d ELEMENTS, any d >= 1; only read.  C classes, 2 <= C <= MDL_PROBE_MAX_CLASSES; cols = 1 for C == 2
+ * (sklearn's binary form), cols = C otherwise (multinomial).
+ * y (int32): the label vector of problem p is y[p * ldy .. p * ldy + S); ldy == 0 shares one vector among all problems (several tasks
+ *   of equal C go through one call with ldy = S).  Labels are 0 .. C-1; any other value (the reference's -1) marks an unlabeled case,
+ *   which is in neither the training nor the test set.
+ * train_idx [P, n_max] (int32), n_train [P] (int32): problem p trains on cases train_idx[p, 0 .. n_train[p]); the rest of the row is
+ *   never read.  1 <= n_train[p] <= n_max <= MDL_PROBE_MAX_TRAIN.  Every labeled case that is not a training case is a test case.
+ *
+ * mdl_probe_fit minimises, per problem,
+ *   C == 2:  cost * sum_i softplus(-(2 y_i - 1)(w . x_i + b)) + 1/2 |w|^2
+ *   C  > 2:  cost * sum_i CE(softmax(W x_i + b), y_i)        + 1/2 |W|_F^2      (b unpenalised; returned with zero mean)
+ * by Newton-CG in the span of the training rows (W = A^T X_train, Gram matrix in the workspace): one Gram launch, then one workgroup
+ * per problem.  No workgroup waits on another; every loop is bounded (max_iter Newton steps, MDL_PROBE_CG_MAX CG steps each,
+ * MDL_PROBE_LS_MAX step halvings).  A problem has converged when the inf-norm of the primal gradient (with respect to W and b, evaluated
+ * in fp32 from W itself) is <= gtol; it stops after max_iter steps at the latest.  Once below gtol the iteration goes on only while a
+ * step still halves that norm and it is above 0.03 gtol: stopping at the first value below gtol would leave the decision values of the
+ * smallest problems more than 1e-3 off the optimum.
+ * W_out [P, cols, d], b_out [P, cols]; info_out [P, 4] fp32: Newton steps taken, converged (1 / 0), the final inf-norm of the gradient,
+ * CG steps in all.  A problem with n_train outside [1, n_max], a training index outside [0, S) or an unlabeled training case writes
+ * NaN to its W, b and residual and converged = 0; the others are unaffected.  Results depend on the problem alone (not on P or p).
+ *
+ * mdl_probe_scores: z_out [P, S, cols] = X W_p^T + b_p for ALL S cases.  Prediction: z > 0 for C == 2 (z == 0 is class 0), argmax with
+ * the lowest index on ties otherwise.
+ *
+ * mdl_probe_metrics, over the test cases of problem p: confusion_out [P, C, C] int32 (row = truth, column = prediction) and auc_out [P]
+ * fp32 = roc_auc_score: the Mann-Whitney statistic with ties counted 1/2 -- C == 2: cases ranked by z; C > 2: one-vs-rest macro average,
+ * class c ranked by log_softmax(z)[c] evaluated in fp64.  NaN where a class has no test case (C == 2: either class).  Exact pair
+ * counting in integers, S <= MDL_PROBE_MAX_CASES; the order of the atomic additions cannot change a bit of the result.
+ *
+ * Workspaces: 16-byte aligned, sizes from the *_ws_bytes queries, contents need no initialisation.
+ * MDL_E_UNSUPPORTED: n_max > MDL_PROBE_MAX_TRAIN, C outside [2, MDL_PROBE_MAX_CLASSES], S > MDL_PROBE_MAX_CASES (metrics), a launch grid or
+ * an output index beyond int32.  MDL_E_ARG: null pointers, ldX < d, sizes < 1, ldy not 0 or >= S, max_iter < 0. */
+#define MDL_PROBE_MAX_TRAIN 256
+#define MDL_PROBE_MAX_CLASSES 8
+#define MDL_PROBE_MAX_CASES 16384
+#define MDL_PROBE_CG_MAX 400
+#define MDL_PROBE_LS_MAX 24
+int64_t mdl_probe_fit_ws_bytes(int64_t P, int n_max, int d, int C);
+int mdl_probe_fit(const float* X, int64_t ldX, int64_t S, int d, const int32_t* y, int64_t ldy, const int32_t* train_idx,
+                  const int32_t* n_train, int64_t P, int n_max, int C, float cost, float gtol, int max_iter, float* W_out, float* b_out,
+                  float* info_out, void* ws, void* stream);
+int mdl_probe_scores(const float* X, int64_t ldX, int64_t S, int d, const float* W, const float* b, int64_t P, int C, float* z_out,
+                     void* stream);
+int64_t mdl_probe_metrics_ws_bytes(int64_t P, int64_t S, int C);
+int mdl_probe_metrics(const float* z, const int32_t* y, int64_t ldy, const int32_t* train_idx, const int32_t* n_train, int64_t P,
+                      int n_max, int64_t S, int C, int32_t* confusion_out, float* auc_out, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ madeleine.utils.loss, madeleine.utils.trainer):
     from madeleine_amd import InfoNCE, GOT, calculate_losses, train_loop, run_inference
     from madeleine_amd import AdamW          # torch.optim.AdamW's update with a device-side non-finite guard and clipping
     from madeleine_amd import DeviceSlideStore   # the cohort's features resident on the device, batches drawn by one kernel
+    from madeleine_amd import linear_probe       # the few-shot linear-probing protocol, every (task, k, fold) fit in one batch of launches
 
 The numeric work runs in csrc/libmadeleine_amd.so through the C ABI of include/madeleine_amd.h.
 Importing this package does not load the library (so model construction / state_dict handling works on
@@ -22,5 +23,15 @@ from .utils import create_model_from_pretrained, extract_slide_level_embeddings,
 
 __all__ = ["MADELEINE", "ABMILEmbedder", "BatchedABMIL", "create_model", "InfoNCE", "info_nce", "GOT",
            "init_intra_wsi_loss_function", "calculate_losses", "train_loop", "run_inference", "extract_slide_level_embeddings",
-           "load_checkpoint", "create_model_from_pretrained", "AdamW", "DeviceSlideStore", "PackedBags"]
+           "load_checkpoint", "create_model_from_pretrained", "AdamW", "DeviceSlideStore", "PackedBags", "probe_splits", "fit_logistic",
+           "linear_probe"]
 __version__ = "0.2"
+_PROBE = ("probe_splits", "fit_logistic", "linear_probe")
+
+
+def __getattr__(name):
+    """The linear probe's names resolve on first use, so that `python -m madeleine_amd.probe` runs a module nobody imported before."""
+    if name in _PROBE:
+        from . import probe
+        return getattr(probe, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -1845,3 +1845,92 @@ def bag_pack_tiered(store_rows, host_rows, off, bag, key_id, cu, chunk_cu, n_row
               int(host_wgs), _stream(),
               unsupported=("bag_pack_tiered: %d bags of %d rows in all exceed the int32 launch geometry", R, T))
     return (out, row_bag, idx) if return_indices else (out, row_bag)
+
+
+# ---- P1-P3: the few-shot linear probe (mdl_probe_fit / mdl_probe_scores / mdl_probe_metrics).  No autograd: embeddings are inputs ----
+_PROBE_LIMITS = "linear probe supports at most %d training cases per problem, 2..%d classes and %d cases (got n_max %d, C %d, S %d)"
+
+
+def _probe_refusal(n_max, C, S):
+    d = _native._DEFINES
+    return (_PROBE_LIMITS, d["MDL_PROBE_MAX_TRAIN"], d["MDL_PROBE_MAX_CLASSES"], d["MDL_PROBE_MAX_CASES"], n_max, C, S)
+
+
+def _probe_matrix(X):
+    if X.dim() != 2 or X.dtype != torch.float32 or (X.shape[1] > 1 and X.stride(1) != 1):
+        raise RuntimeError("madeleine_amd: X must be [S, d] float32 with unit column stride")
+    if not X.is_cuda:
+        raise RuntimeError("madeleine_amd: X must live on a ROCm device (got %s); there is no CPU fallback" % X.device)
+    S, d = X.shape
+    if S < 1 or d < 1:
+        raise RuntimeError("madeleine_amd: X must have at least one row and one column")
+    return S, d, (X.stride(0) if S > 1 else d)
+
+
+def _probe_problems(y, train_idx, n_train, S):
+    """(P, n_max, ldy) of a problem list: y [S] (shared) or [P, S] int32, train_idx [P, n_max] int32, n_train [P] int32."""
+    _require(y, "y", torch.int32)
+    _require(train_idx, "train_idx", torch.int32)
+    _require(n_train, "n_train", torch.int32)
+    if train_idx.dim() != 2 or train_idx.shape[0] < 1 or train_idx.shape[1] < 1 or n_train.shape != (train_idx.shape[0],):
+        raise RuntimeError("madeleine_amd: train_idx must be [P, n_max] and n_train [P], P >= 1, n_max >= 1")
+    P, n_max = train_idx.shape
+    if y.shape == (S,):
+        return P, n_max, 0
+    if y.shape == (P, S):
+        return P, n_max, S
+    raise RuntimeError("madeleine_amd: y must be [S] or [P, S] = [%d, %d] (got %s)" % (P, S, tuple(y.shape)))
+
+
+def probe_fit(X, y, train_idx, n_train, n_classes, cost=1.0, gtol=1e-4, max_iter=100):
+    """(W [P, cols, d], b [P, cols], info [P, 4]) of P regularised logistic fits (P1 of the header; cols = 1 for two classes).
+    info columns: Newton steps, converged, inf-norm of the gradient, CG steps.  Asynchronous, no host read."""
+    S, d, ldX = _probe_matrix(X)
+    P, n_max, ldy = _probe_problems(y, train_idx, n_train, S)
+    C = int(n_classes)
+    refusal = _probe_refusal(n_max, C, S)
+    ws = _ws_for("mdl_probe_fit_ws_bytes", X.device, P, n_max, d, C, refusal=refusal)
+    cols = 1 if C == 2 else C
+    W = torch.empty(P, cols, d, device=X.device, dtype=torch.float32)
+    b = torch.empty(P, cols, device=X.device, dtype=torch.float32)
+    info = torch.empty(P, 4, device=X.device, dtype=torch.float32)
+    with _timed("probe_fit"):
+        _call("mdl_probe_fit", X, ldX, S, d, y, ldy, train_idx, n_train, P, n_max, C, float(cost), float(gtol), int(max_iter), W, b, info,
+              ws, _stream(), unsupported=refusal)
+    return W, b, info
+
+
+def probe_scores(X, W, b, n_classes):
+    """z [P, S, cols] = X W_p^T + b_p: the decision values of all S cases under every fit (P2)."""
+    S, d, ldX = _probe_matrix(X)
+    C = int(n_classes)
+    cols = 1 if C == 2 else C
+    _require(W, "W")
+    _require(b, "b")
+    if W.dim() != 3 or W.shape[0] < 1 or W.shape[1:] != (cols, d) or b.shape != W.shape[:2]:
+        raise RuntimeError("madeleine_amd: W must be [P, %d, %d] and b [P, %d]" % (cols, d, cols))
+    P = W.shape[0]
+    z = torch.empty(P, S, cols, device=X.device, dtype=torch.float32)
+    with _timed("probe_scores", ("flop", 2.0 * P * S * cols * d)):
+        _call("mdl_probe_scores", X, ldX, S, d, W, b, P, C, z, _stream(), unsupported=_probe_refusal(0, C, S))
+    return z
+
+
+def probe_metrics(z, y, train_idx, n_train, n_classes):
+    """(confusion [P, C, C] int32, auc [P] fp32) over the test cases of every problem (P3): the labeled cases outside its train_idx."""
+    _require(z, "z")
+    C = int(n_classes)
+    cols = 1 if C == 2 else C
+    if z.dim() != 3 or z.shape[0] < 1 or z.shape[1] < 1 or z.shape[2] != cols:
+        raise RuntimeError("madeleine_amd: z must be [P, S, %d]" % cols)
+    S = z.shape[1]
+    P, n_max, ldy = _probe_problems(y, train_idx, n_train, S)
+    if P != z.shape[0]:
+        raise RuntimeError("madeleine_amd: z holds %d problems, train_idx %d" % (z.shape[0], P))
+    refusal = _probe_refusal(n_max, C, S)
+    ws = _ws_for("mdl_probe_metrics_ws_bytes", z.device, P, S, C, refusal=refusal)
+    confusion = torch.empty(P, C, C, device=z.device, dtype=torch.int32)
+    auc = torch.empty(P, device=z.device, dtype=torch.float32)
+    with _timed("probe_metrics"):
+        _call("mdl_probe_metrics", z, y, ldy, train_idx, n_train, P, n_max, S, C, confusion, auc, ws, _stream(), unsupported=refusal)
+    return confusion, auc

@@ -1,0 +1,167 @@
+"""Few-shot linear probe on the device: the reference's bin/run_linear_probing.py (k training cases per class, 10 folds, L2-regularised
+logistic regression, AUC and balanced accuracy) with every (task, k, fold) problem of an evaluation in one batch of HIP launches.
+
+    from madeleine_amd import linear_probe
+    results = linear_probe(embeds, {"er": er, "pr": pr, "her2": her2})       # {(task, k): {"auc": [folds], "bacc": [folds], ...}}
+
+`python -m madeleine_amd.probe --slide_embedding_pkl P --label_path CSV` is the reference's command line."""
+import warnings
+
+import numpy as np
+import torch
+
+from . import functional as F
+
+__all__ = ["probe_splits", "fit_logistic", "linear_probe", "balanced_accuracy", "quadratic_kappa"]
+
+
+def probe_splits(labels, k, fold, seed_base=0):
+    """Training indices (int64 [C * k], class 0's first) of the few-shot split (k, fold): k cases of every class 0 .. C-1, C =
+    max(labels) + 1, drawn by torch.randperm under torch.Generator().manual_seed(seed_base + 1000 * k + fold), classes in increasing
+    order, cases in case order.  Label -1 (unlabeled) is never drawn.  ValueError when a class has no case or fewer than k."""
+    labels = torch.as_tensor(np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels)).long()
+    if labels.dim() != 1 or int(k) < 1 or not bool((labels >= 0).any()):
+        raise ValueError("probe_splits: labels must be a vector with a labeled case, and k >= 1")
+    g = torch.Generator().manual_seed(int(seed_base) + 1000 * int(k) + int(fold))
+    out = []
+    for c in range(int(labels.max()) + 1):
+        idx = torch.nonzero(labels == c)[:, 0]
+        if idx.numel() == 0:
+            raise ValueError("probe_splits: class %d has no case" % c)
+        if idx.numel() < k:
+            raise ValueError("probe_splits: class %d has %d cases, fewer than k = %d" % (c, idx.numel(), k))
+        out.append(idx[torch.randperm(idx.numel(), generator=g)[:k]])
+    return torch.cat(out)
+
+
+def balanced_accuracy(confusion):
+    """sklearn's balanced_accuracy_score from a confusion matrix (row = truth), fp64: the mean recall of the classes that have a case."""
+    cm = np.asarray(confusion, dtype=np.float64)
+    support = cm.sum(1)
+    have = support > 0
+    return float(np.mean(np.diag(cm)[have] / support[have])) if have.any() else float("nan")
+
+
+def quadratic_kappa(confusion):
+    """cohen_kappa_score(weights="quadratic") from a confusion matrix over the grades 0 .. C-1, fp64.  NaN when chance agreement is
+    complete (all cases in one cell's row and column)."""
+    cm = np.asarray(confusion, dtype=np.float64)
+    C = cm.shape[0]
+    w = (np.arange(C)[:, None] - np.arange(C)[None, :]) ** 2.0
+    expected = np.outer(cm.sum(1), cm.sum(0)) / max(cm.sum(), 1.0)
+    den = float((w * expected).sum())
+    return 1.0 - float((w * cm).sum()) / den if den > 0 else float("nan")
+
+
+def _problem_table(train_lists, device):
+    """(train_idx [P, n_max] int32 padded with -1, n_train [P] int32) on `device`, from a list of 1-D index tensors -- one copy each."""
+    n = [int(t.numel()) for t in train_lists]
+    table = torch.full((len(n), max(n)), -1, dtype=torch.int32)
+    for p, t in enumerate(train_lists):
+        table[p, :n[p]] = t.to(torch.int32)
+    return table.to(device), torch.tensor(n, dtype=torch.int32).to(device)
+
+
+def fit_logistic(X, y, train_idx, n_classes, cost=1.0, gtol=1e-4, max_iter=100):
+    """P regularised logistic fits on the device (sklearn's LogisticRegression(C=cost), binary form for two classes, multinomial above).
+    X [S, d] fp32 device tensor; y [S] or [P, S] integer labels (-1: unlabeled); train_idx a list of P index vectors or a [P, n_max]
+    table padded with -1.  Returns (W [P, cols, d], b [P, cols], info) with info = {"iterations", "converged", "residual",
+    "cg_iterations"}, [P] device tensors.  Nothing is read back: the caller decides when to look at `converged`."""
+    if not isinstance(X, torch.Tensor) or not X.is_cuda:
+        raise RuntimeError("madeleine_amd: X must be a tensor on a ROCm device; there is no CPU fallback")
+    y = torch.as_tensor(y).to(device=X.device, dtype=torch.int32).contiguous()
+    if isinstance(train_idx, torch.Tensor) and train_idx.dim() == 2:
+        table = train_idx.to(device=X.device, dtype=torch.int32).contiguous()
+        n_train = (table >= 0).sum(1, dtype=torch.int32)
+    else:
+        table, n_train = _problem_table([torch.as_tensor(t).reshape(-1) for t in train_idx], X.device)
+    W, b, info = F.probe_fit(X, y, table, n_train, n_classes, cost, gtol, max_iter)
+    return W, b, {"iterations": info[:, 0], "converged": info[:, 1] > 0, "residual": info[:, 2], "cg_iterations": info[:, 3]}
+
+
+def linear_probe(embeds, labels, ks=(1, 10, 25), folds=10, cost=1.0, seed_base=0, kappa=False, gtol=1e-4, max_iter=100):
+    """The reference's linear-probing protocol over embeds [S, d] (tensor or array): for every task (labels: one [S] vector -- task
+    "label" -- or a dict task -> [S]; -1 = unlabeled), every k of ks and every fold, fit on probe_splits(labels, k, fold, seed_base) and
+    score on all other labeled cases.  All problems of equal class count share ONE fit, ONE scoring and ONE metrics launch sequence.
+    Returns {(task, k): {"auc": [folds], "bacc": [folds], "converged": [folds] bool, "confusion": [folds, C, C] (+ "q_kappa": [folds]
+    with kappa=True)}} as numpy arrays.  Two host reads: the finiteness check of embeds (ValueError) and the results.  Problems that
+    did not converge are flagged in "converged" and announced by one RuntimeWarning."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("madeleine_amd: linear_probe needs a ROCm device; there is no CPU fallback")
+    X = torch.as_tensor(embeds)
+    X = X.to(device=X.device if X.is_cuda else "cuda", dtype=torch.float32)
+    if X.dim() != 2:
+        raise ValueError("linear_probe: embeds must be [S, d]")
+    if X.stride(-1) != 1:
+        X = X.contiguous()
+    if not bool(torch.isfinite(X).all()):
+        raise ValueError("linear_probe: embeds holds non-finite values")
+    tasks = labels if isinstance(labels, dict) else {"label": labels}
+    groups = {}                                     # C -> [(task, k, fold, y, train indices)]
+    for task, y in tasks.items():
+        y = torch.as_tensor(np.asarray(y.cpu() if isinstance(y, torch.Tensor) else y)).long()
+        if y.shape != (X.shape[0],):
+            raise ValueError("linear_probe: task %r has %s labels for %d embeddings" % (task, tuple(y.shape), X.shape[0]))
+        for k in ks:
+            for fold in range(folds):
+                groups.setdefault(int(y.max()) + 1, []).append((task, k, fold, y, probe_splits(y, k, fold, seed_base)))
+    parts = []
+    for C, probs in groups.items():
+        table, n_train = _problem_table([p[4] for p in probs], X.device)
+        y_dev = torch.stack([p[3] for p in probs]).to(torch.int32).to(X.device)
+        W, b, info = F.probe_fit(X, y_dev, table, n_train, C, cost, gtol, max_iter)
+        confusion, auc = F.probe_metrics(F.probe_scores(X, W, b, C), y_dev, table, n_train, C)
+        parts += [auc.double(), info[:, 1].double(), confusion.reshape(-1).double()]
+    host = torch.cat(parts).cpu().numpy()           # the one read of the results
+    out, at, failed = {}, 0, 0
+    for C, probs in groups.items():
+        P = len(probs)
+        auc, conv, cm = host[at:at + P], host[at + P:at + 2 * P] > 0, host[at + 2 * P:at + 2 * P + P * C * C].reshape(P, C, C)
+        at += 2 * P + P * C * C
+        failed += int((~conv).sum())
+        for p, (task, k, fold, _, _) in enumerate(probs):
+            res = out.setdefault((task, k), {"auc": np.zeros(folds), "bacc": np.zeros(folds), "converged": np.zeros(folds, dtype=bool),
+                                             "confusion": np.zeros((folds, C, C), dtype=np.int64)})
+            res["auc"][fold], res["converged"][fold], res["confusion"][fold] = auc[p], conv[p], np.rint(cm[p])
+            res["bacc"][fold] = balanced_accuracy(cm[p])
+            if kappa:
+                res.setdefault("q_kappa", np.zeros(folds))[fold] = quadratic_kappa(cm[p])
+    if failed:
+        warnings.warn("linear_probe: %d of %d fits did not reach gtol = %g in %d Newton steps" % (failed, sum(map(len, groups.values())),
+                                                                                                   gtol, max_iter), RuntimeWarning)
+    return out
+
+
+def _main(argv=None):
+    import argparse
+    import csv
+    import os
+    import pickle
+    ap = argparse.ArgumentParser(description="few-shot linear probing of slide embeddings (the reference's bin/run_linear_probing.py)")
+    ap.add_argument("--slide_embedding_pkl", required=True)
+    ap.add_argument("--label_path", required=True)
+    ap.add_argument("--tasks", nargs="+", default=["er", "pr", "her2"])
+    args = ap.parse_args(argv)
+    with open(args.slide_embedding_pkl, "rb") as f:
+        obj = pickle.load(f)
+    with open(args.label_path, newline="") as f:
+        rows = {str(r["slide_id"]): r for r in csv.DictReader(f)}
+    keep = [i for i, s in enumerate(obj["slide_ids"]) if str(s) in rows]      # the reference's intersection of labels and embeddings
+    embeds = np.asarray(obj["embeds"], dtype=np.float32)[keep]
+    labels = {t: np.array([int(float(rows[str(obj["slide_ids"][i])][t])) for i in keep]) for t in args.tasks}
+    results = linear_probe(embeds, labels, kappa="isup_grade" in args.tasks)
+    name = os.path.splitext(os.path.basename(args.slide_embedding_pkl))[0]
+    save = os.path.join(os.path.dirname(args.slide_embedding_pkl), "res_linear_probing", name)
+    os.makedirs(save, exist_ok=True)
+    for (task, k), res in results.items():
+        if task == "isup_grade":
+            print("k={}, task={}, quadratic kappa={}".format(k, task, round(float(res["q_kappa"].mean()), 3)))
+        else:
+            print("k={}, task={}, auc={} +/- {}".format(k, task, round(float(res["auc"].mean()), 3), round(float(res["auc"].std()), 3)))
+        store = {m: res[m].tolist() for m in ("auc", "bacc", "q_kappa") if m in res}
+        with open(os.path.join(save, "k=%d_probing_%s.pickle" % (k, task.replace("/", ""))), "wb") as f:
+            pickle.dump({"tangle": store}, f, protocol=pickle.HIGHEST_PROTOCOL)
+
+
+if __name__ == "__main__":
+    _main()
