@@ -17,6 +17,14 @@
  *     synchronisation.
  *   - return value: 0 on success; a positive hipError_t if a launch failed; a negative MDL_E_* code
  *     for argument validation.  Nothing throws across the boundary.
+ *   - row strides (ldE, ldx, ldy, lddx, lddy, ldc in elements; rsb, a_rsb, b_rsb, e_rsb in bytes): any value that is at least the row
+ *     width, keeps every row 16-byte aligned (fp32: a multiple of 4 elements, bf16: of 8 -- 4 on the pooling entry points, whose lanes
+ *     load 4 elements; bytes: of 16) and stays within the entry point's upper limit.  The limits exist where a kernel adds
+ *     (row inside its tile) x stride + column bytes in 32 bits; each is stated beside the argument as that expression, which must not
+ *     exceed 2^31 - 1.  Below the width or misaligned: MDL_E_ARG (the bf16 Linears: MDL_E_UNSUPPORTED for a stride that is not a
+ *     multiple of 8); above the limit: MDL_E_UNSUPPORTED.  All of it is checked before anything is launched, empty problems included.
+ *     A strided operand may be a column slice of a wider buffer: no kernel reads or writes the bytes between the end of a row and
+ *     the start of the next.
  *   - fp32 values everywhere.  Contractions come in three engines: the *_split entry points (the DEFAULT of the Python
  *     mirror: every fp32 operand as an fp16 hi + lo image under a power-of-two scale, three v_mfma_f32_32x32x16_f16 products
  *     per logical product, fp32 accumulation -- error below an fp32 fmaf chain), the plain entry points (exact fp32,
@@ -65,7 +73,7 @@ int mdl_abi_version(void);
  *
  *   s[t,c] = bc[c] + sum_j wc[c,j] * drop(tanh(E[t,c,:].Wa[c,j,:] + ba[c,j])) * drop(sigmoid(E[t,c,:].Wb[c,j,:] + bb[c,j]))
  *
- * E      [T, H*512]  head-major token embeddings (row stride ldE floats, >= H*512)
+ * E      [T, H*512]  head-major token embeddings (row stride ldE floats, >= H*512, % 4 == 0, 127 * 4 ldE + 48 <= 2^31 - 1)
  * Wa,Wb  [H,512,512] torch Linear layout [out,in];  ba,bb [H,512];  wc [H,512];  bc [H]
  * scores [T,H]       raw (pre-softmax) attention, == raw_attention of Model.py:406-411
  * act_a, act_b [T,H,512]  tanh / sigmoid activations BEFORE dropout, saved for backward (may be NULL
@@ -83,7 +91,8 @@ int mdl_abmil_gate_fwd(const float* E, int64_t ldE, const float* Wa, const float
                        const uint8_t* keep_a, const uint8_t* keep_b, void* ws, void* stream);
 
 /* Backward of the above.  d_scores [T,H] incoming gradient.
- * dE [T,H*512] (row stride ldE): gradient wrt the token embeddings through the gates; written when
+ * dE [T,H*512] (row stride ldE, the SAME stride as E: one argument serves both; 15 * 4 ldE + 1020 <= 2^31 - 1 in the backward entry
+ *    points, mdl_abmil_attnpool_bwd(_phases) included): gradient wrt the token embeddings through the gates; written when
  *    accumulate == 0, added to the existing contents when accumulate != 0.
  * dWa,dWb [H,512,512]; dba,dbb,dwc [H,512]; dbc [H] (may be NULL)  -- all overwritten.
  * ws: mdl_abmil_gate_bwd_ws_bytes(T,H) bytes: d(za)|d(zb) [T+16,H,1024] (computed once, then both GEMMs are pure
@@ -109,7 +118,8 @@ int mdl_abmil_gate_dropout_mask(uint8_t* keep, int64_t T, int H, int which, floa
  * Bags: dense (cu_seqlens == NULL: bag b = tokens [b*N, (b+1)*N)) or ragged (cu_seqlens int64
  * [n_bags+1] device array of token offsets into the packed E / scores; max_len = longest bag).
  * An empty bag pools to 0.
- * E [T,H*512] (stride ldE), scores [T,H], pooled [n_bags,H*512],
+ * E [T,H*512] (stride ldE >= H*512, % 4 == 0 for fp32 and bf16 E alike, no upper limit: the pooling kernels form 64-bit row addresses;
+ * the backward's dE shares ldE with E), scores [T,H], pooled [n_bags,H*512],
  * stat_m, stat_l [n_bags,H]: softmax max / sum-of-exp per bag and head (saved for backward).
  * ws: mdl_abmil_pool_ws_bytes(n_bags,max_len,H).
  */
@@ -279,7 +289,10 @@ int mdl_infonce_neg_bwd(const float* Neg, const float* d_loss, const float* d_ro
  * Linears of the pre-attention MLP (madeleine/models/Model.py:351, :355, :359; bias = NULL there: the bias and its gradient
  * are handled by mdl_ln_gelu_drop_*), the token_projector Linear(2048, 128) (Model.py:140) and the slide projector
  * Linear(2048, 512) on the pooled embeddings (Model.py:145).
- * X [T,K] (row stride ldx), W [N,K] contiguous (torch's Linear.weight), bias [N] or NULL, Y [T,N] (row stride ldy).
+ * X [T,K] (row stride ldx), W [N,K] contiguous (torch's Linear.weight), bias [N] or NULL, Y [T,N] (row stride ldy); the backward's dY
+ * has row stride ldy, dX row stride lddx.  Strides % 4 == 0.  Upper limits (for every T):
+ *   mdl_linear_fwd: R * 4 ldx + 48 <= 2^31 - 1 with R = 127 (N % 256 == 0) or 255 (the tall tile); 3 * 4 ldy + 1020 <= 2^31 - 1
+ *   mdl_linear_bwd: 127 * 4 ldy + 48 and 15 * 4 ldy + 4 N <= 2^31 - 1; 15 * 4 ldx + 4 K <= 2^31 - 1; 3 * 4 lddx + 1020 <= 2^31 - 1
  * Supported (MDL_E_UNSUPPORTED otherwise):
  *   T > 256 : N % 256 == 0 with K % 32 == 0 -- matrix-core tile engine, 128 x 256 tile; dX (output width K) runs the
  *             ragged-column variant of the tile when K % 256 != 0 (config 5: K = 768 + 32 stain channels);
@@ -397,7 +410,10 @@ int mdl_got_tiled_rect_bwd(const float* V, const float* Q, const float* d_out, f
  * bf16 (uint16_t bit patterns of torch.bfloat16: E, the gate activations, dE, the LayerNorm input/output), the
  * contractions run on v_mfma_f32_32x32x16_bf16 with fp32 accumulation, every epilogue / reduction / statistic is
  * fp32, parameters and their gradients stay fp32.  Same argument meaning as the fp32 entry points above; ldE counts
- * bf16 elements and must be a multiple of 8.  mdl_abmil_gate_bwd_bf16 requires ldE == H*512 (it transposes E).
+ * bf16 elements and must be a multiple of 8 on the gate entry points (16-byte LDS-DMA granules) and of 4 on the pooling entry points
+ * (mdl_abmil_pool_*_bf16, _wpool_, _pool_view_, _pool_rview_: 8-byte loads), MDL_E_ARG otherwise.  Upper limits:
+ * mdl_abmil_gate_fwd_bf16 255 * 2 ldE + 112 <= 2^31 - 1; mdl_abmil_gate_bwd_bf16 / mdl_abmil_attnpool_bwd(_phases)_bf16
+ * 63 * 2 ldE + 496 <= 2^31 - 1 (dE shares ldE with E; any ldE >= H*512 within these rules: the backward reads E in place).
  * The fp32 entry points remain the parity path (1e-3 rel of the reference's fp32 results); this mode is held to
  * the reference-under-autocast accuracy (tests/test_bf16_gpu.py).
  */
@@ -443,7 +459,9 @@ int mdl_abmil_pool_view_bwd_bf16(const uint16_t* E, int64_t ldE, const float* sc
  * `precision: bfloat16`, trainer.py:101-103): X, Y, dY, dX bf16; W [N,K], bias [N], dW, dbias fp32.  v_mfma_f32_32x32x16_bf16 with
  * fp32 accumulation; dW through the ds_read_b64_tr_b16 "TN" engine (no transposed copies of X / dY).
  * Supported (mdl_linear_bf16_supported; MDL_E_UNSUPPORTED otherwise): N % 128 == 0 and K % 32 == 0 (forward and
- * backward).  Leading dimensions multiples of 8.  Same argument meaning as mdl_linear_fwd / mdl_linear_bwd. */
+ * backward).  Leading dimensions multiples of 8 (MDL_E_UNSUPPORTED otherwise).  Same argument meaning as mdl_linear_fwd / mdl_linear_bwd.
+ * Upper limits: mdl_linear_fwd_bf16 255 * 2 ldx + 112 <= 2^31 - 1, 7 * 2 ldy + 510 <= 2^31 - 1; mdl_linear_bwd_bf16
+ * 255 * 2 lddy + 112 <= 2^31 - 1, 63 * 2 ldx + 496 <= 2^31 - 1, 7 * 2 lddx + 510 <= 2^31 - 1. */
 int mdl_linear_bf16_supported(int64_t N, int64_t K, int backward);
 int64_t mdl_linear_fwd_bf16_ws_bytes(int64_t T, int64_t N, int64_t K);
 int mdl_linear_fwd_bf16(const uint16_t* X, int64_t ldx, const float* W, const float* bias, uint16_t* Y, int64_t ldy, int64_t T,
@@ -477,6 +495,11 @@ int mdl_abmil_attnpool_bwd_bf16(const uint16_t* E, int64_t ldE, const float* Wa,
  * ah bh + ah bl + al bh accumulated in fp32 (measured error below a plain fp32 fmaf chain, tools/micro/split_lab.hip).
  * SPLIT IMAGE of X [rows, K], K % 32 == 0: uint16 [rows][K / 32][2][32] -- the hi and the lo plane of every 32-column block side
  * by side (128 B = the bytes of the fp32 block); row stride rsb bytes (>= 4 K, % 16 == 0).  scale: device float[2] = {scale, absmax}.
+ * Upper limits of an image's row stride where it is an OPERAND (none where mdl_split_image / _rows write it, nor on their ldx, nor on the
+ * ldx of mdl_split_tile_absmax, nor on the e_rsb of mdl_abmil_pool_fwd_img / _dscores_img: 64-bit addresses): mdl_split_gemm_nt(_group_bias)
+ * 256 a_rsb and 256 b_rsb <= 2^31 - 1 (512 a_rsb and 128 b_rsb on the narrow-output tile: N <= 128, M > 256, no row_gate / group_bias),
+ * 4 ldc <= 2^31 - 1; mdl_split_gemm_tn 32 a_rsb, 32 b_rsb <= 2^31 - 1; mdl_abmil_gate_fwd_split 256 e_rsb <= 2^31 - 1;
+ * mdl_abmil_attnpool_bwd_split 32 e_rsb <= 2^31 - 1 and 4 ldE <= 2^31 - 1.
  *   mdl_split_image   : image of a fp32 tensor (exact absmax -> scale with max |scale x| in [2^13, 2^14)), + pad_rows zero rows
  *   mdl_split_gemm_nt : C [M,N] (+)= sum_k A[m][k] B[n][k] (+ bias[n])   A, B images with K columns (rows m, n)
  *   mdl_split_gemm_tn : out [N][Mi] = sum_t B[t][n] A[t][m]              A, B images with T rows (contraction = rows); B must be

@@ -427,6 +427,7 @@ extern "C" int mdl_abmil_gate_fwd(const float* E, int64_t ldE, const float* Wa, 
     if (T < 0 || H < 1 || H > MDL_MAX_HEADS || ldE < (int64_t)H * HID || (ldE & 3)) return MDL_E_ARG;
     if (!(p_drop >= 0.f && p_drop < 1.f)) return MDL_E_ARG;
     if (!host_aligned16(E) || !host_aligned16(Wa) || !host_aligned16(Wb) || !host_aligned16(ws)) return MDL_E_ALIGN;
+    if (!stride_fits32(ldE, 4, GBM - 1, 48)) return MDL_E_UNSUPPORTED;   // rows_voff: rr * ldE * 4 + kq * 16
     if (T == 0) return MDL_OK;
     const int64_t n_tt = (T + GBM - 1) / GBM;
     if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
@@ -487,6 +488,8 @@ static int gate_bwd_impl(const float* E, int64_t ldE, const float* Wa, const flo
     if (!host_aligned16(E) || !host_aligned16(Wa) || !host_aligned16(Wb) || !host_aligned16(act_a) ||
         !host_aligned16(act_b) || !host_aligned16(wc) || !host_aligned16(ws))
         return MDL_E_ALIGN;
+    // gate_bwd_dw_kernel: r * ldE4 + colA, r < GBK, colA <= 31 * 16; gate_bwd_dx_kernel: rl * ld4 + lane_col * 4, rl < 4 (the smaller bound)
+    if (!stride_fits32(ldE, 4, GBK - 1, 1020)) return MDL_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const DropCfg d = make_drop(p_drop, seed, keep_a, keep_b);
     const int S = gate_splits(T, H);

@@ -669,6 +669,7 @@ extern "C" int mdl_abmil_gate_fwd_bf16(const uint16_t* E, int64_t ldE, const flo
     if (T < 0 || H < 1 || H > MDL_MAX_HEADS || ldE < (int64_t)H * HID || (ldE & 7)) return MDL_E_ARG;
     if (!(p_drop >= 0.f && p_drop < 1.f)) return MDL_E_ARG;
     if (!host_aligned16(E) || !host_aligned16(Wa) || !host_aligned16(Wb) || !host_aligned16(ws)) return MDL_E_ALIGN;
+    if (!stride_fits32(ldE, 2, QM - 1, 112)) return MDL_E_UNSUPPORTED;   // gate_fwd256_bf16_kernel: ra * ldE * 2 + ch * 16
     if (T == 0) return MDL_OK;
     if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
     const int64_t n_tt = (T + BBM - 1) / BBM;
@@ -748,6 +749,7 @@ static int gate_bwd_bf16_impl(const uint16_t* E, int64_t ldE, const float* Wa, c
     if (!host_aligned16(E) || !host_aligned16(dE) || !host_aligned16(Wa) || !host_aligned16(Wb) || !host_aligned16(act_a) ||
         !host_aligned16(act_b) || !host_aligned16(wc) || !host_aligned16(ws))
         return MDL_E_ALIGN;
+    if (!stride_fits32(ldE, 2, TQK - 1, 496)) return MDL_E_UNSUPPORTED;   // gate_dw256_bf16_kernel: k * ldA2 + cs, k < TQK, cs <= 31 * 16
     hipStream_t s = (hipStream_t)stream;
     const DropCfg d = make_drop(p_drop, seed, keep_a, keep_b);
     const BwdWs L = bwd_ws(T, H);

@@ -500,9 +500,10 @@ extern "C" int mdl_abmil_gate_fwd_split(const void* E_img, int64_t e_rsb, const 
     if (!E_img || !e_scale || !Wa || !ba || !Wb || !bb || !wc || !bc || !scores || !ws) return MDL_E_ARG;
     if ((act_a == nullptr) != (act_b == nullptr)) return MDL_E_ARG;
     if ((keep_a == nullptr) != (keep_b == nullptr)) return MDL_E_ARG;
-    if (T < 0 || H < 1 || H > MDL_MAX_HEADS || e_rsb < (int64_t)H * HID * 4 || (e_rsb & 15) || e_rsb * SPM > 0x7fffffff) return MDL_E_ARG;
+    if (T < 0 || H < 1 || H > MDL_MAX_HEADS || e_rsb < (int64_t)H * HID * 4 || (e_rsb & 15)) return MDL_E_ARG;
     if (!(p_drop >= 0.f && p_drop < 1.f)) return MDL_E_ARG;
     if (!host_aligned16(E_img) || !host_aligned16(Wa) || !host_aligned16(Wb) || !host_aligned16(ws)) return MDL_E_ALIGN;
+    if (!stride_fits32(e_rsb, 1, SPM, 0)) return MDL_E_UNSUPPORTED;   // ra * e_rsb + ch * 16, ra < SPM, ch * 16 < e_rsb
     if (T == 0) return MDL_OK;
     if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
     const int64_t n_tt = (T + SPM - 1) / SPM;
@@ -581,14 +582,15 @@ extern "C" int mdl_abmil_attnpool_bwd_split(const void* E_img, int64_t e_rsb, co
     const bool do_dx = (phases & (2 | 4)) != 0, do_dw = (phases & (2 | 8)) != 0;   // bit 1 = both contractions; bit 2 = dX only, bit 3 = dW only
     if ((keep_a == nullptr) != (keep_b == nullptr)) return MDL_E_ARG;
     if (scores && (!stat_m || !stat_l || !d_pooled || (!row_bag && N < 1))) return MDL_E_ARG;
-    if (T < 0 || H < 1 || H > MDL_MAX_HEADS || ldE < (int64_t)H * HID || (ldE & 3) || e_rsb < (int64_t)H * HID * 4 || (e_rsb & 15) ||
-        e_rsb * SPK > 0x7fffffff)
+    if (T < 0 || H < 1 || H > MDL_MAX_HEADS || ldE < (int64_t)H * HID || (ldE & 3) || e_rsb < (int64_t)H * HID * 4 || (e_rsb & 15))
         return MDL_E_ARG;
     if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
     if (!(p_drop >= 0.f && p_drop < 1.f)) return MDL_E_ARG;
     if (!host_aligned16(E_img) || !host_aligned16(dE) || !host_aligned16(Wa) || !host_aligned16(Wb) || !host_aligned16(act_a) ||
         !host_aligned16(act_b) || !host_aligned16(wc) || !host_aligned16(ws))
         return MDL_E_ALIGN;
+    // the dW kernel's tk * e_rsb + coA, tk < SPK, coA < e_rsb; the dX epilogue's 32-bit row pitch ld4 = ldE * 4
+    if (!stride_fits32(e_rsb, 1, SPK, 0) || !stride_fits32(ldE, 4, 1, 0)) return MDL_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const DropCfg d = make_drop(p_drop, seed, keep_a, keep_b);
     const SpBwdWs L = sp_bwd_ws(T, H);

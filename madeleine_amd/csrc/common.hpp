@@ -36,6 +36,14 @@ __device__ __forceinline__ void st4(bf16_t* p, f32x4 v) { *reinterpret_cast<bf16
 __device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool host_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// A row stride that enters a 32-bit byte offset (the per-lane offset of an LDS-DMA in the saddr form, the lane part of an epilogue
+// address): `stride` in elements of `elem_bytes` bytes, `rows` = the furthest row that expression reaches from its 64-bit base,
+// `col_bytes` = its largest column term.  rows * stride * elem_bytes + col_bytes has to stay within 0x7fffffff; a launcher refuses a
+// wider stride with MDL_E_UNSUPPORTED before any launch (include/madeleine_amd.h states the limits).
+inline bool stride_fits32(int64_t stride, int elem_bytes, int64_t rows, int64_t col_bytes) {
+    return stride <= (0x7fffffffLL - col_bytes) / (rows * elem_bytes);
+}
+
 // ---- wave-level reductions (wave = 64 lanes) ---------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -443,6 +443,8 @@ extern "C" int mdl_linear_fwd_bf16(const uint16_t* X, int64_t ldx, const float* 
     if (!linb_geom_fwd(N, K) || (ldx & 7) || (ldy & 7)) return MDL_E_UNSUPPORTED;
     if (!host_aligned16(X) || !host_aligned16(W) || !host_aligned16(Y) || !host_aligned16(ws) || (bias && !host_aligned16(bias)))
         return MDL_E_ALIGN;
+    // linb_nt256_kernel: ra * lda * 2 + c * 16, ra < QM, c < 8; epilogues: rl * ldc + lane_col elements, rl < 8, lane_col < 256
+    if (!stride_fits32(ldx, 2, QM - 1, 112) || !stride_fits32(ldy, 2, 7, 510)) return MDL_E_UNSUPPORTED;
     if (T == 0) return MDL_OK;
     hipStream_t s = (hipStream_t)stream;
     bf16_t* Wb = (bf16_t*)ws;
@@ -482,6 +484,10 @@ extern "C" int mdl_linear_bwd_bf16(const uint16_t* X, int64_t ldx, const float* 
     if (!host_aligned16(X) || !host_aligned16(W) || !host_aligned16(dY) || !host_aligned16(dW) || !host_aligned16(ws) ||
         (dX && !host_aligned16(dX)))
         return MDL_E_ALIGN;
+    // dY: the A rows of linb_nt256_kernel (ra * lda * 2 + c * 16, ra < QM; the TN kernels reach TQK rows); X: linb_tn256_kernel's
+    // k * ldB2 + cs, k < TQK, cs <= 31 * 16; dX: the NT epilogues' rl * ldc + lane_col elements, rl < 8, lane_col < 256
+    if (!stride_fits32(lddy, 2, QM - 1, 112) || !stride_fits32(ldx, 2, TQK - 1, 496) || (dX && !stride_fits32(lddx, 2, 7, 510)))
+        return MDL_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const LinbWs L = linb_ws(T, (int)N, (int)K);
     char* base = (char*)ws;

@@ -393,6 +393,9 @@ extern "C" int mdl_linear_fwd(const float* X, int64_t ldx, const float* W, const
     if (!X || !W || !Y || !ws || ldx < K || ldy < N || (ldx & 3) || (ldy & 3)) return MDL_E_ARG;
     if (!host_aligned16(X) || !host_aligned16(W) || !host_aligned16(Y) || !host_aligned16(ws) || !host_aligned16(bias))
         return MDL_E_ALIGN;
+    // X: rr * lda * 4 + kq * 16 over the tile's rows (rows_voff: 128, lin_nn_tall_kernel: 256); Y: the epilogues' rl * ldc4 + lane_col * 4,
+    // rl < 4, lane_col < 256.  (The few-row kernel forms 64-bit addresses; the limits hold for every T all the same.)
+    if (!stride_fits32(ldx, 4, (lin_wide(N) ? LBM : 256) - 1, 48) || !stride_fits32(ldy, 4, 3, 1020)) return MDL_E_UNSUPPORTED;
     if (T == 0) return MDL_OK;
     hipStream_t s = (hipStream_t)stream;
     if (T <= LIN_SMALL_T) return lin_small_launch(X, ldx, 1, W, K, 1, Y, ldy, (int)T, N, K, bias, (float*)ws, s);
@@ -436,6 +439,11 @@ extern "C" int mdl_linear_bwd(const float* X, int64_t ldx, const float* W, const
     if (!host_aligned16(X) || !host_aligned16(W) || !host_aligned16(dY) || !host_aligned16(dW) || !host_aligned16(ws) ||
         !host_aligned16(dX))
         return MDL_E_ALIGN;
+    // dY: the A rows of lin_nn_kernel (rows_voff: rr * lda * 4 + kq * 16, rr < LBM) and lin_tn_kernel's r * ldx4 + colA, r < LBK, colA < 4 N
+    // (roles swapped); X: lin_tn_kernel's r * ldx4 + colA, colA < 4 K; dX: lin_nn_kernel's epilogue rl * ldc4 + lane_col * 4, rl < 4
+    if (!stride_fits32(ldy, 4, LBM - 1, 48) || !stride_fits32(ldy, 4, LBK - 1, 4 * (int64_t)N) || !stride_fits32(ldx, 4, LBK - 1, 4 * (int64_t)K) ||
+        (dX && !stride_fits32(lddx, 4, 3, 1020)))
+        return MDL_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     if (T <= LIN_SMALL_T) {
         int r = MDL_OK;

@@ -475,7 +475,7 @@ extern "C" int mdl_split_image(const float* X, int64_t ldx, int64_t rows, int K,
     hipError_t e = hipMemsetAsync(scale, 0, 2 * sizeof(float), s);
     if (e != hipSuccess) return (int)e;
     if (pad_rows > 0) {
-        e = hipMemsetAsync((char*)img + rows * rsb, 0, (size_t)(pad_rows * rsb), s);
+        e = hipMemset2DAsync((char*)img + rows * rsb, (size_t)rsb, 0, (size_t)K * 4, (size_t)pad_rows, s);   // the 4 K image bytes of each pad row: nothing between rows
         if (e != hipSuccess) return (int)e;
     }
     int rc = sp_launch_absmax(X, ldx, rows, K, scale + 1, s);
@@ -506,7 +506,7 @@ extern "C" int mdl_split_image_rows(const float* X, int64_t ldx, int64_t rows, i
         if (e != hipSuccess) return (int)e;
     }
     if (pad_rows > 0) {
-        e = hipMemsetAsync((char*)img + rows * rsb, 0, (size_t)(pad_rows * rsb), s);
+        e = hipMemset2DAsync((char*)img + rows * rsb, (size_t)rsb, 0, (size_t)K * 4, (size_t)pad_rows, s);   // the 4 K image bytes of each pad row: nothing between rows
         if (e != hipSuccess) return (int)e;
     }
     if (rows > 0) {
@@ -559,10 +559,14 @@ static int sp_gemm_nt_impl(const void* A, int64_t a_rsb, const float* a_scale, c
     if (!A || !B || !C || !a_scale || !b_scale || M < 0 || N < 4 || (N & 3) || K < 32 || (K % 32) || ldc < N || (ldc & 3)) return MDL_E_ARG;
     if (a_rsb < (int64_t)K * 4 || b_rsb < (int64_t)K * 4 || (a_rsb & 15) || (b_rsb & 15)) return MDL_E_ARG;
     if (!host_aligned16(A) || !host_aligned16(B) || !host_aligned16(C) || !host_aligned16(bias)) return MDL_E_ALIGN;
+    const bool tall = N <= SPT_N && !row_gate && !group_bias && M > SPM;   // narrow output (the token_projector): the 512 x 128 tile
+    // ra * a_rsb + c * 16 / rb * b_rsb + c * 16 over the rows of the tile (c * 16 < the row stride); the epilogues' 32-bit row pitch ldc * 4
+    if (!stride_fits32(a_rsb, 1, tall ? SPT_M : SPM, 0) || !stride_fits32(b_rsb, 1, tall ? SPT_N : SPN, 0) || !stride_fits32(ldc, 4, 1, 0))
+        return MDL_E_UNSUPPORTED;
     if (M == 0) return MDL_OK;
-    if (N <= SPT_N && !row_gate && !group_bias && M > SPM) {   // narrow output (the token_projector): the 512 x 128 tile
+    if (tall) {
         const int64_t tt = (M + SPT_M - 1) / SPT_M;
-        if (tt > 0x7fffffff || a_rsb * SPT_M > 0x7fffffff || b_rsb * SPT_N > 0x7fffffff) return MDL_E_UNSUPPORTED;
+        if (tt > 0x7fffffff) return MDL_E_UNSUPPORTED;
         hipLaunchKernelGGL(terms == 2 ? sp_nt_tall_kernel<2> : sp_nt_tall_kernel<3>, dim3((unsigned)tt), dim3(SP_THREADS), 0, (hipStream_t)stream,
                            (const char*)A, a_rsb, a_scale, (const char*)B, b_rsb, b_scale, C, ldc, M, N, K / 32, (int)tt, bias, accumulate,
                            absmax_out, a_row_mul, b_col_mul);
@@ -570,7 +574,7 @@ static int sp_gemm_nt_impl(const void* A, int64_t a_rsb, const float* a_scale, c
         return MDL_OK;
     }
     const int64_t tiles = ((M + SPM - 1) / SPM) * ((N + SPN - 1) / SPN);
-    if (tiles > 0x7fffffff || a_rsb * SPM > 0x7fffffff || b_rsb * SPN > 0x7fffffff) return MDL_E_UNSUPPORTED;
+    if (tiles > 0x7fffffff) return MDL_E_UNSUPPORTED;
     const bool na3 = sp_nt_stages() == 3;   // sp_nt_mainloop3 (split_engine.hpp)
     hipLaunchKernelGGL(terms == 2 ? (na3 ? sp_nt_kernel<2, 3> : sp_nt_kernel<2, 2>) : (na3 ? sp_nt_kernel<3, 3> : sp_nt_kernel<3, 2>),
                        dim3((unsigned)tiles), dim3(SP_THREADS), 0, (hipStream_t)stream,
@@ -610,9 +614,10 @@ extern "C" int mdl_split_gemm_tn(const void* A, int64_t a_rsb, const float* a_sc
                                  void* stream) {
     if (terms != 2 && terms != 3) return MDL_E_ARG;
     if (!A || !B || !out || !ws || !a_scale || !b_scale || T < 0 || Mi < 32 || (Mi % 32) || N < 32 || (N % 32)) return MDL_E_ARG;
-    if (a_rsb < (int64_t)Mi * 4 || b_rsb < (int64_t)N * 4 || (a_rsb & 15) || (b_rsb & 15) || a_rsb * 32 > 0x7fffffff || b_rsb * 32 > 0x7fffffff)
-        return MDL_E_ARG;
+    if (a_rsb < (int64_t)Mi * 4 || b_rsb < (int64_t)N * 4 || (a_rsb & 15) || (b_rsb & 15)) return MDL_E_ARG;
     if (!host_aligned16(A) || !host_aligned16(B) || !host_aligned16(out) || !host_aligned16(ws)) return MDL_E_ALIGN;
+    // tk * a_rsb + coA / tokq * b_rsb + coB, token rows < SPK of a chunk, column terms < the row stride
+    if (!stride_fits32(a_rsb, 1, SPK, 0) || !stride_fits32(b_rsb, 1, SPK, 0)) return MDL_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const int S = sp_tn_splits(T, Mi, N);
     const int64_t tps = sp_tn_tps(T, S);
