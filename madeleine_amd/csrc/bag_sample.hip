@@ -23,11 +23,14 @@
 // Bounds.  A bag index outside [0, n_bags), an empty or over-long bag and a bag that leaves [0, T_total) are written as absent stains
 // (zeros, idx -1): whatever the tables hold, no address outside the store is formed.
 //
-// One body, several kernels.  sample_item / pack_item below are the whole work of one (output row, 64-token chunk) item; the draw
-// (row_key, token_hash, feistel, draw_distinct), the placement of a bag (locate_bag) and the copy loops (copy_rows) are device
-// functions that every kernel of this file instantiates, so S1, S2 and their tiered forms S3, S4 (at the end of the file) draw and
-// copy with the same code.
+// One kernel, one launcher.  A call is described by three records: the Store (both tiers and the bag table), the Draw (which bag under
+// which keys) and one job, SampleJob (S1, S3) or PackJob (S2, S4).  gather_item, overloaded on the job, is the whole work of one
+// (output row, 64-token chunk) item; the draw (row_key, token_hash, feistel, draw_distinct), the placement of a bag (locate_bag) and
+// the copy loops (copy_rows, zero_rows) are device functions under it.  bag_gather_kernel<T, VEC, PASS, Job> is the only __global__
+// function and launch() the only place that launches it, so the four entry points draw and copy with the same code; they differ in
+// the records they fill and in the passes they ask for (PASS_ALL, or PASS_DEV then PASS_HOST: the tiered forms, further down).
 #include "common.hpp"
+#include <type_traits>
 
 namespace mdl {
 namespace {
@@ -121,29 +124,76 @@ struct Vec<bf16_t> {
 // in two: PASS_DEV owns the items of resident bags and of absent stains, PASS_HOST those of the bags in the host tier.
 enum { PASS_ALL = 0, PASS_DEV = 1, PASS_HOST = 2 };
 
+// The store: rows [0, T_dev) at `dev`, rows [T_dev, T_total) at `host` (their device-visible address), D elements of the call's
+// dtype per row, row_stride elements from one row to the next in both tiers; bag g is rows off[g] .. off[g + 1] - 1.  The resident
+// store (S1, S2) is the case host == NULL, T_dev == T_total.  The bases are untyped so that the argument checks, which know no
+// element type, read the same record as the kernels.
+struct Store {
+    const void* dev;
+    const void* host;
+    int64_t T_dev, row_stride, T_total;
+    const int64_t* off;                     // [n_bags + 1]
+    int64_t n_bags;
+    int D;
+};
+
+// The draw: output row (bag) r takes stored bag bag[r] under the keys of (seed, counter, key_id[r]); key_id NULL: key_id[r] = bag[r].
+struct Draw {
+    const int32_t* bag;
+    const int64_t* key_id;
+    uint64_t seed, counter;
+};
+
+// The dense gather (S1, S3): item w is tokens 64 c .. 64 c + 63 of output row r, w = r * chunks + c; out [R, N, D], idx_out [R, N] or NULL.
+struct SampleJob {
+    int N, chunks;
+    int64_t items;                          // R * chunks <= 2^31 - 1: the grid of every pass but the host pass, which walks them
+    float* out;
+    int32_t* idx_out;
+};
+
+// The pack (S2, S4): item w is one 64-row chunk of the output bag that chunk_cu places it in; out [T_out, D], row_bag and idx_out
+// [T_out] or NULL.
+struct PackJob {
+    const int64_t* cu;                      // [R + 1]
+    const int64_t* chunk_cu;                // [R + 1]
+    int R;
+    int64_t T_out;
+    int64_t items;                          // n_chunks <= 2^31 - 1
+    float* out;
+    int32_t* row_bag;
+    int32_t* idx_out;
+};
+
+// One entry of a table of the call (off, bag, key_id, cu, chunk_cu).  No kernel of this file writes a table, but they arrive inside
+// records, where __restrict__ cannot say so.  The constant address space says it: these wave-uniform reads then stay scalar loads in
+// the host pass's loop as well, past the barrier and the stores of the items before (without it they become one vector load per lane).
+template <class V>
+__device__ __forceinline__ V table(const V* p, int64_t i) {
+    return ((const __attribute__((address_space(4))) V*)p)[i];
+}
+
 // The rows of stored bag g: returns n, its length, or 0 for an absent stain (by the table or by the bounds rule of the header comment);
-// `rows` is its first row (the tier's base when n == 0: never read).  Tiered (PASS != PASS_ALL): rows [0, T_dev) of the store are in
-// `store`, rows [T_dev, T_total) in `store_host`; a bag on both sides of T_dev is an absent stain; on_host says which pass owns the item.
+// `rows` is its first row (the tier's base when n == 0: never read).  Tiered (PASS != PASS_ALL): a bag on both sides of T_dev is an
+// absent stain; on_host says which pass owns the item.
 template <class T, int PASS>
-__device__ __forceinline__ uint32_t locate_bag(const T* __restrict__ store, const T* __restrict__ store_host, int64_t T_dev,
-                                               int64_t row_stride, int64_t T_total, const int64_t* __restrict__ off, int64_t n_bags, int g,
-                                               const T*& rows, bool& on_host) {
+__device__ __forceinline__ uint32_t locate_bag(const Store& st, int g, const T*& rows, bool& on_host) {
     int64_t base = 0, n64 = 0;
-    if (g >= 0 && g < n_bags) {
-        base = off[g];
-        n64 = off[g + 1] - base;
-        if (base < 0 || n64 < 1 || n64 > 0x7FFFFFFF || base > T_total - n64) n64 = 0;
+    if (g >= 0 && g < st.n_bags) {
+        base = table(st.off, g);
+        n64 = table(st.off, g + 1) - base;
+        if (base < 0 || n64 < 1 || n64 > 0x7FFFFFFF || base > st.T_total - n64) n64 = 0;
     }
     on_host = false;
     if (PASS != PASS_ALL && n64 != 0) {
-        if (base >= T_dev) {                                    // wholly in the host tier: T_dev <= base, base + n <= T_total
+        if (base >= st.T_dev) {                                 // wholly in the host tier: T_dev <= base, base + n <= T_total
             on_host = true;
-            rows = store_host + (base - T_dev) * row_stride;
+            rows = static_cast<const T*>(st.host) + (base - st.T_dev) * st.row_stride;
             return (uint32_t)n64;
         }
-        if (base > T_dev - n64) n64 = base = 0;                 // on both sides of T_dev: no address is formed from it
+        if (base > st.T_dev - n64) n64 = base = 0;              // on both sides of T_dev: no address is formed from it
     }
-    rows = store + base * row_stride;
+    rows = static_cast<const T*>(st.dev) + base * st.row_stride;
     return (uint32_t)n64;
 }
 
@@ -227,21 +277,19 @@ __device__ __forceinline__ void zero_rows(float* __restrict__ zrow, int count, i
 // Item w = (output row r, chunk c) of the dense gather: the whole of S1's work for tokens 64 c .. 64 c + 63 of row r.  Uniform over the
 // workgroup, the early returns included; a caller that loops over items puts a barrier between two of them (s_idx is reused).
 template <class T, bool VEC, int PASS, int INFLIGHT>
-__device__ __forceinline__ void sample_item(const T* __restrict__ store, const T* __restrict__ store_host, int64_t T_dev, int64_t row_stride,
-                                            int64_t T_total, const int64_t* __restrict__ off, int64_t n_bags,
-                                            const int32_t* __restrict__ bag, const int64_t* __restrict__ key_id, int N, int D, int chunks,
-                                            uint64_t seed, uint64_t counter, float* __restrict__ out, int32_t* __restrict__ idx_out, int w,
-                                            int32_t* s_idx) {
+__device__ __forceinline__ void gather_item(const Store& st, const Draw& dr, const SampleJob& job, int64_t item, int32_t* s_idx) {
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const int r = w / chunks, t0 = (w - r * chunks) * BS_TOK;
+    const int w = (int)item, N = job.N, D = st.D;               // items <= 2^31 - 1
+    const int r = w / job.chunks, t0 = (w - r * job.chunks) * BS_TOK;
     const int cnt = N - t0 < BS_TOK ? N - t0 : BS_TOK;        // tokens of this item, >= 1
 
-    const int g = bag[r];
+    const int g = table(dr.bag, r);
     const T* bag_rows;
     bool on_host;
-    const uint32_t n = locate_bag<T, PASS>(store, store_host, T_dev, row_stride, T_total, off, n_bags, g, bag_rows, on_host);   // 0: absent
+    const uint32_t n = locate_bag<T, PASS>(st, g, bag_rows, on_host);    // 0: absent
     if (PASS != PASS_ALL && on_host != (PASS == PASS_HOST)) return;      // the other pass's item
-    float* orow = out + ((int64_t)r * N + t0) * D;
+    float* orow = job.out + ((int64_t)r * N + t0) * D;
+    int32_t* idx_out = job.idx_out;
 
     if (n == 0) {                                               // uniform over the workgroup
         zero_rows<VEC>(orow, cnt, D, tid);
@@ -250,7 +298,7 @@ __device__ __forceinline__ void sample_item(const T* __restrict__ store, const T
     }
 
     if (wave == 0) {
-        const RowKey k = row_key(seed, counter, key_id != nullptr ? (uint64_t)key_id[r] : (uint64_t)(int64_t)g);
+        const RowKey k = row_key(dr.seed, dr.counter, dr.key_id != nullptr ? (uint64_t)table(dr.key_id, r) : (uint64_t)(int64_t)g);
         if (n < (uint32_t)N)                                    // with replacement
             s_idx[lane] = (int32_t)(((uint64_t)token_hash((uint32_t)(t0 + lane), k) * n) >> 32);
         else
@@ -258,69 +306,13 @@ __device__ __forceinline__ void sample_item(const T* __restrict__ store, const T
     }
     __syncthreads();
     if (idx_out != nullptr && tid < cnt) idx_out[(int64_t)r * N + t0 + tid] = s_idx[tid];
-    copy_rows<T, VEC, INFLIGHT>(bag_rows, row_stride, s_idx, cnt, D, orow, lane, wave);
-}
-
-template <class T, bool VEC>
-__global__ __launch_bounds__(BS_THREADS) void bag_sample_kernel(const T* __restrict__ store, int64_t row_stride, int64_t T_total,
-                                                                const int64_t* __restrict__ off, int64_t n_bags,
-                                                                const int32_t* __restrict__ bag, const int64_t* __restrict__ key_id,
-                                                                int N, int D, int chunks, uint64_t seed, uint64_t counter,
-                                                                float* __restrict__ out, int32_t* __restrict__ idx_out) {
-    __shared__ int32_t s_idx[BS_TOK];
-    sample_item<T, VEC, PASS_ALL, BS_INFLIGHT>(store, nullptr, T_total, row_stride, T_total, off, n_bags, bag, key_id, N, D, chunks, seed,
-                                               counter, out, idx_out, (int)blockIdx.x, s_idx);
-}
-
-template <class T>
-int launch(const void* store, int64_t row_stride, int64_t T_total, const int64_t* off, int64_t n_bags, const int32_t* bag,
-           const int64_t* key_id, int64_t R, int N, int D, int chunks, uint64_t seed, uint64_t counter, float* out, int32_t* idx_out,
-           hipStream_t stream) {
-    const bool vec = D % Vec<T>::E == 0 && row_stride % Vec<T>::E == 0;
-    const dim3 grid((unsigned)(R * chunks)), block(BS_THREADS);
-    if (vec)
-        hipLaunchKernelGGL((bag_sample_kernel<T, true>), grid, block, 0, stream, reinterpret_cast<const T*>(store), row_stride, T_total, off,
-                           n_bags, bag, key_id, N, D, chunks, seed, counter, out, idx_out);
-    else
-        hipLaunchKernelGGL((bag_sample_kernel<T, false>), grid, block, 0, stream, reinterpret_cast<const T*>(store), row_stride, T_total,
-                           off, n_bags, bag, key_id, N, D, chunks, seed, counter, out, idx_out);
-    MDL_LAUNCH_CHECK();
-    return MDL_OK;
-}
-
-}  // namespace
-}  // namespace mdl
-
-using namespace mdl;
-
-extern "C" int mdl_bag_sample(const void* store, int dtype, int64_t row_stride, int64_t T_total, const int64_t* off, int64_t n_bags,
-                              const int32_t* bag, const int64_t* key_id, int64_t R, int N, int D, uint64_t seed, uint64_t counter,
-                              float* out, int32_t* idx_out, void* stream) {
-    if (store == nullptr || off == nullptr || bag == nullptr || out == nullptr) return MDL_E_ARG;
-    if (R < 0 || N < 1 || D < 1 || T_total < 0 || n_bags < 0 || row_stride < D) return MDL_E_ARG;
-    if (dtype != MDL_STORE_F32 && dtype != MDL_STORE_F16 && dtype != MDL_STORE_BF16) return MDL_E_ARG;
-    if (!host_aligned16(store) || !host_aligned16(out)) return MDL_E_ALIGN;
-    if ((reinterpret_cast<uintptr_t>(off) & 7u) || (reinterpret_cast<uintptr_t>(bag) & 3u) || (reinterpret_cast<uintptr_t>(key_id) & 7u) ||
-        (reinterpret_cast<uintptr_t>(idx_out) & 3u))
-        return MDL_E_ALIGN;
-    const int chunks = (N + BS_TOK - 1) / BS_TOK;
-    if (R > 0x7FFFFFFF / (int64_t)N || R * chunks > 0x7FFFFFFF) return MDL_E_UNSUPPORTED;
-    if (R == 0) return MDL_OK;
-    hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case MDL_STORE_F32:
-            return launch<float>(store, row_stride, T_total, off, n_bags, bag, key_id, R, N, D, chunks, seed, counter, out, idx_out, s);
-        case MDL_STORE_F16:
-            return launch<_Float16>(store, row_stride, T_total, off, n_bags, bag, key_id, R, N, D, chunks, seed, counter, out, idx_out, s);
-        default:
-            return launch<bf16_t>(store, row_stride, T_total, off, n_bags, bag, key_id, R, N, D, chunks, seed, counter, out, idx_out, s);
-    }
+    copy_rows<T, VEC, INFLIGHT>(bag_rows, st.row_stride, s_idx, cnt, D, orow, lane, wave);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
 // bag_pack (S2 of the header) -- the variable-length form of the gather above: every bag at its own length L_r = cu[r + 1] - cu[r],
 // packed back to back into out [T_out, D], in ONE launch.  A bag that fits (L_r >= n) is taken whole and in stored order; a longer one
-// (L_r < n) is cut to L_r rows by exactly the draw of bag_sample_kernel with N := L_r -- the same keys, the same in-wave sort for
+// (L_r < n) is cut to L_r rows by exactly the draw of the dense gather with N := L_r -- the same keys, the same in-wave sort for
 // n <= 64, the same Feistel walk above -- so the rows and idx are bit-equal to mdl_bag_sample(N = L_r) under the same (seed, counter,
 // key_id).  The with-replacement regime cannot occur: a bag is never asked for more rows than it has.
 //
@@ -332,26 +324,21 @@ extern "C" int mdl_bag_sample(const void* store, int dtype, int64_t row_stride, 
 // side: a workgroup writes packed rows cu[r] + 64 c + i only, and only those inside [0, T_out); a (bag, chunk) that the two tables do
 // not agree on (cu[r] < 0, cu[r + 1] <= cu[r], c outside the bag) writes nothing.  r comes out of a search over [0, R), so every table
 // is read inside its R (+ 1) entries whatever chunk_cu holds.
-namespace mdl {
-namespace {
 
 // Item w = (output bag r, chunk c) of the pack: the whole of S2's work for packed rows cu[r] + 64 c .. + 63.  Uniform over the workgroup,
 // the early returns included; a caller that loops over items puts a barrier between two of them (s_idx is reused).
 template <class T, bool VEC, int PASS, int INFLIGHT>
-__device__ __forceinline__ void pack_item(const T* __restrict__ store, const T* __restrict__ store_host, int64_t T_dev, int64_t row_stride,
-                                          int64_t T_total, const int64_t* __restrict__ off, int64_t n_bags, const int32_t* __restrict__ bag,
-                                          const int64_t* __restrict__ key_id, const int64_t* __restrict__ cu,
-                                          const int64_t* __restrict__ chunk_cu, int R, int64_t T_out, int D, uint64_t seed, uint64_t counter,
-                                          float* __restrict__ out, int32_t* __restrict__ row_bag, int32_t* __restrict__ idx_out, int64_t w,
-                                          int32_t* s_idx) {
+__device__ __forceinline__ void gather_item(const Store& st, const Draw& dr, const PackJob& job, int64_t w, int32_t* s_idx) {
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    int lo = 0, hi = R - 1;                                     // the last r of [0, R) with chunk_cu[r] <= w (bags of no rows are passed over)
+    const int D = st.D;
+    const int64_t T_out = job.T_out;
+    int lo = 0, hi = job.R - 1;                                 // the last r of [0, R) with chunk_cu[r] <= w (bags of no rows are passed over)
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
-        if (chunk_cu[mid] <= w) lo = mid; else hi = mid - 1;
+        if (table(job.chunk_cu, mid) <= w) lo = mid; else hi = mid - 1;
     }
     const int r = lo;
-    const int64_t p0 = cu[r], p1 = cu[r + 1], c = w - chunk_cu[r];
+    const int64_t p0 = table(job.cu, r), p1 = table(job.cu, r + 1), c = w - table(job.chunk_cu, r);
     if (p0 < 0 || p0 >= T_out || p1 <= p0 || c < 0 || c > (T_out >> 6)) return;      // uniform over the workgroup, as all that follows
     const int64_t L = p1 - p0, t0 = c * BS_TOK;                 // no overflow: 0 <= p0 < p1, 0 <= t0 <= T_out < 2^31
     int64_t lim = L - t0;
@@ -359,10 +346,10 @@ __device__ __forceinline__ void pack_item(const T* __restrict__ store, const T* 
     if (lim < 1) return;
     const int cnt = lim < BS_TOK ? (int)lim : BS_TOK;           // packed rows of this item, all inside [0, T_out)
 
-    const int g = bag[r];
+    const int g = table(dr.bag, r);
     const T* bag_rows;
     bool on_host;
-    const uint32_t n = locate_bag<T, PASS>(store, store_host, T_dev, row_stride, T_total, off, n_bags, g, bag_rows, on_host);   // 0: absent
+    const uint32_t n = locate_bag<T, PASS>(st, g, bag_rows, on_host);    // 0: absent
     if (PASS != PASS_ALL && on_host != (PASS == PASS_HOST)) return;      // the other pass's item
     const int64_t n64 = n, prow = p0 + t0;
 
@@ -371,92 +358,32 @@ __device__ __forceinline__ void pack_item(const T* __restrict__ store, const T* 
         const int64_t left = n64 - t0;
         ncopy = left < 0 ? 0 : left < cnt ? (int)left : cnt;
         if (wave == 0) s_idx[lane] = (int32_t)t0 + lane;
-    } else if (n != 0) {                                        // L < n: sample_item's draw without replacement, N = L
+    } else if (n != 0) {                                        // L < n: the dense gather's draw without replacement, N = L
         ncopy = cnt;
         if (wave == 0)
-            draw_distinct(row_key(seed, counter, key_id != nullptr ? (uint64_t)key_id[r] : (uint64_t)(int64_t)g), n, (int)L, (uint32_t)t0,
-                          lane, cnt, s_idx);
+            draw_distinct(row_key(dr.seed, dr.counter, dr.key_id != nullptr ? (uint64_t)table(dr.key_id, r) : (uint64_t)(int64_t)g), n, (int)L,
+                          (uint32_t)t0, lane, cnt, s_idx);
     }
     __syncthreads();
     if (tid < cnt) {
-        if (idx_out != nullptr) idx_out[prow + tid] = tid < ncopy ? s_idx[tid] : -1;
-        if (row_bag != nullptr) row_bag[prow + tid] = r;
+        if (job.idx_out != nullptr) job.idx_out[prow + tid] = tid < ncopy ? s_idx[tid] : -1;
+        if (job.row_bag != nullptr) job.row_bag[prow + tid] = r;
     }
-    float* orow = out + prow * D;
-    copy_rows<T, VEC, INFLIGHT>(bag_rows, row_stride, s_idx, ncopy, D, orow, lane, wave);
+    float* orow = job.out + prow * D;
+    copy_rows<T, VEC, INFLIGHT>(bag_rows, st.row_stride, s_idx, ncopy, D, orow, lane, wave);
     zero_rows<VEC>(orow + (int64_t)ncopy * D, cnt - ncopy, D, tid);
-}
-
-template <class T, bool VEC>
-__global__ __launch_bounds__(BS_THREADS) void bag_pack_kernel(const T* __restrict__ store, int64_t row_stride, int64_t T_total,
-                                                              const int64_t* __restrict__ off, int64_t n_bags,
-                                                              const int32_t* __restrict__ bag, const int64_t* __restrict__ key_id,
-                                                              const int64_t* __restrict__ cu, const int64_t* __restrict__ chunk_cu, int R,
-                                                              int64_t T_out, int D, uint64_t seed, uint64_t counter,
-                                                              float* __restrict__ out, int32_t* __restrict__ row_bag,
-                                                              int32_t* __restrict__ idx_out) {
-    __shared__ int32_t s_idx[BS_TOK];
-    pack_item<T, VEC, PASS_ALL, BS_INFLIGHT>(store, nullptr, T_total, row_stride, T_total, off, n_bags, bag, key_id, cu, chunk_cu, R, T_out, D,
-                                             seed, counter, out, row_bag, idx_out, (int64_t)blockIdx.x, s_idx);
-}
-
-template <class T>
-int launch_pack(const void* store, int64_t row_stride, int64_t T_total, const int64_t* off, int64_t n_bags, const int32_t* bag,
-                const int64_t* key_id, const int64_t* cu, const int64_t* chunk_cu, int R, int64_t n_chunks, int64_t T_out, int D,
-                uint64_t seed, uint64_t counter, float* out, int32_t* row_bag, int32_t* idx_out, hipStream_t stream) {
-    const bool vec = D % Vec<T>::E == 0 && row_stride % Vec<T>::E == 0;
-    const dim3 grid((unsigned)n_chunks), block(BS_THREADS);
-    if (vec)
-        hipLaunchKernelGGL((bag_pack_kernel<T, true>), grid, block, 0, stream, reinterpret_cast<const T*>(store), row_stride, T_total, off,
-                           n_bags, bag, key_id, cu, chunk_cu, R, T_out, D, seed, counter, out, row_bag, idx_out);
-    else
-        hipLaunchKernelGGL((bag_pack_kernel<T, false>), grid, block, 0, stream, reinterpret_cast<const T*>(store), row_stride, T_total, off,
-                           n_bags, bag, key_id, cu, chunk_cu, R, T_out, D, seed, counter, out, row_bag, idx_out);
-    MDL_LAUNCH_CHECK();
-    return MDL_OK;
-}
-
-}  // namespace
-}  // namespace mdl
-
-extern "C" int mdl_bag_pack(const void* store, int dtype, int64_t row_stride, int64_t T_total, const int64_t* off, int64_t n_bags,
-                            const int32_t* bag, const int64_t* key_id, const int64_t* cu, const int64_t* chunk_cu, int64_t R,
-                            int64_t n_chunks, int64_t T_out, int D, uint64_t seed, uint64_t counter, float* out, int32_t* row_bag,
-                            int32_t* idx_out, void* stream) {
-    if (store == nullptr || off == nullptr || bag == nullptr || cu == nullptr || chunk_cu == nullptr || out == nullptr) return MDL_E_ARG;
-    if (R < 0 || n_chunks < 0 || T_out < 0 || D < 1 || T_total < 0 || n_bags < 0 || row_stride < D) return MDL_E_ARG;
-    if (dtype != MDL_STORE_F32 && dtype != MDL_STORE_F16 && dtype != MDL_STORE_BF16) return MDL_E_ARG;
-    if (!host_aligned16(store) || !host_aligned16(out)) return MDL_E_ALIGN;
-    if ((reinterpret_cast<uintptr_t>(off) & 7u) || (reinterpret_cast<uintptr_t>(bag) & 3u) || (reinterpret_cast<uintptr_t>(key_id) & 7u) ||
-        (reinterpret_cast<uintptr_t>(cu) & 7u) || (reinterpret_cast<uintptr_t>(chunk_cu) & 7u) ||
-        (reinterpret_cast<uintptr_t>(row_bag) & 3u) || (reinterpret_cast<uintptr_t>(idx_out) & 3u))
-        return MDL_E_ALIGN;
-    if (R > 0x7FFFFFFF || T_out > 0x7FFFFFFF || n_chunks > 0x7FFFFFFF) return MDL_E_UNSUPPORTED;
-    if (R == 0 || T_out == 0 || n_chunks == 0) return MDL_OK;
-    hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case MDL_STORE_F32:
-            return launch_pack<float>(store, row_stride, T_total, off, n_bags, bag, key_id, cu, chunk_cu, (int)R, n_chunks, T_out, D, seed,
-                                      counter, out, row_bag, idx_out, s);
-        case MDL_STORE_F16:
-            return launch_pack<_Float16>(store, row_stride, T_total, off, n_bags, bag, key_id, cu, chunk_cu, (int)R, n_chunks, T_out, D, seed,
-                                         counter, out, row_bag, idx_out, s);
-        default:
-            return launch_pack<bf16_t>(store, row_stride, T_total, off, n_bags, bag, key_id, cu, chunk_cu, (int)R, n_chunks, T_out, D, seed,
-                                       counter, out, row_bag, idx_out, s);
-    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
 // The tiered forms (S3, S4 of the header): rows [0, T_dev) of the store in device memory, rows [T_dev, T_total) in pinned host memory
-// that the kernel reads over PCIe.  The items are those of S1 / S2 and so is every bit written (sample_item / pack_item); what changes
-// is who runs an item.  Two launches on the stream, each skipping the other's items:
-//   device pass  one workgroup per item, the chip-wide grid of S1 / S2: the items of resident bags and of absent stains (a bag on both
-//                sides of T_dev is one).  An item of the host tier returns after three table reads.
-//   host pass    a NARROW PERSISTENT grid: host_wgs workgroups walk all items with a grid stride, skip those that are not the host
-//                tier's and run the same draw-then-copy on the others.  A 63 GB/s link is saturated by a few hundred KB in flight
-//                (host_wgs x 256 lanes x BS_HOST_INFLIGHT x 16 B); a chip-wide grid would hold wave slots and registers of every CU
-//                for the milliseconds the link needs, in front of the step's kernels that run beside a prefetching gather.
+// that the kernel reads over PCIe.  The items are those of S1 / S2 and so is every bit written (gather_item); what changes is who runs
+// an item.  Two launches of the one kernel below on the stream, each skipping the other's items:
+//   device pass  PASS_DEV: one workgroup per item, the chip-wide grid of S1 / S2: the items of resident bags and of absent stains (a
+//                bag on both sides of T_dev is one).  An item of the host tier returns after three table reads.
+//   host pass    PASS_HOST: a NARROW PERSISTENT grid: host_wgs workgroups walk all items with a grid stride, skip those that are not
+//                the host tier's and run the same draw-then-copy on the others.  A 63 GB/s link is saturated by a few hundred KB in
+//                flight (host_wgs x 256 lanes x BS_HOST_INFLIGHT x 16 B); a chip-wide grid would hold wave slots and registers of
+//                every CU for the milliseconds the link needs, in front of the step's kernels that run beside a prefetching gather.
 // Two launches rather than one kernel that branches per item: one grid cannot be both chip-wide and narrow.
 #ifndef BS_HOST_INFLIGHT
 #define BS_HOST_INFLIGHT 4                  // rows a lane has in flight over PCIe
@@ -465,39 +392,18 @@ extern "C" int mdl_bag_pack(const void* store, int dtype, int64_t row_stride, in
 #define BS_HOST_WGS 64                      // the host pass's grid when the caller passes host_wgs = 0
 #endif
 
-namespace mdl {
-namespace {
-
-template <class T, bool VEC, int PASS>
-__global__ __launch_bounds__(BS_THREADS) void bag_sample_tier_kernel(const T* __restrict__ store, const T* __restrict__ store_host,
-                                                                     int64_t T_dev, int64_t row_stride, int64_t T_total,
-                                                                     const int64_t* __restrict__ off, int64_t n_bags,
-                                                                     const int32_t* __restrict__ bag, const int64_t* __restrict__ key_id,
-                                                                     int N, int D, int chunks, int64_t items, uint64_t seed, uint64_t counter,
-                                                                     float* __restrict__ out, int32_t* __restrict__ idx_out) {
+// The one kernel of this file: Job (SampleJob or PackJob) selects gather_item and names the gather in a kernel trace.  PASS_ALL and
+// PASS_DEV: the grid is job.items, workgroup w runs item w.  PASS_HOST: any grid, the workgroups share the items out by grid stride.
+template <class T, bool VEC, int PASS, class Job>
+__global__ __launch_bounds__(BS_THREADS) void bag_gather_kernel(Store st, Draw dr, Job job) {
     __shared__ int32_t s_idx[BS_TOK];
-    for (int64_t w = blockIdx.x; w < items; w += gridDim.x) {      // items <= 2^31 - 1; the device pass has one item per workgroup
-        sample_item<T, VEC, PASS, PASS == PASS_HOST ? BS_HOST_INFLIGHT : BS_INFLIGHT>(store, store_host, T_dev, row_stride, T_total, off, n_bags,
-                                                                                      bag, key_id, N, D, chunks, seed, counter, out, idx_out,
-                                                                                      (int)w, s_idx);
-        __syncthreads();                                        // the next item's draw overwrites s_idx
-    }
-}
-
-template <class T, bool VEC, int PASS>
-__global__ __launch_bounds__(BS_THREADS) void bag_pack_tier_kernel(const T* __restrict__ store, const T* __restrict__ store_host, int64_t T_dev,
-                                                                   int64_t row_stride, int64_t T_total, const int64_t* __restrict__ off,
-                                                                   int64_t n_bags, const int32_t* __restrict__ bag,
-                                                                   const int64_t* __restrict__ key_id, const int64_t* __restrict__ cu,
-                                                                   const int64_t* __restrict__ chunk_cu, int R, int64_t items, int64_t T_out,
-                                                                   int D, uint64_t seed, uint64_t counter, float* __restrict__ out,
-                                                                   int32_t* __restrict__ row_bag, int32_t* __restrict__ idx_out) {
-    __shared__ int32_t s_idx[BS_TOK];
-    for (int64_t w = blockIdx.x; w < items; w += gridDim.x) {
-        pack_item<T, VEC, PASS, PASS == PASS_HOST ? BS_HOST_INFLIGHT : BS_INFLIGHT>(store, store_host, T_dev, row_stride, T_total, off, n_bags,
-                                                                                    bag, key_id, cu, chunk_cu, R, T_out, D, seed, counter, out,
-                                                                                    row_bag, idx_out, w, s_idx);
-        __syncthreads();
+    if (PASS != PASS_HOST) {
+        gather_item<T, VEC, PASS, BS_INFLIGHT>(st, dr, job, (int64_t)blockIdx.x, s_idx);
+    } else {
+        for (int64_t w = blockIdx.x; w < job.items; w += gridDim.x) {
+            gather_item<T, VEC, PASS, BS_HOST_INFLIGHT>(st, dr, job, w, s_idx);
+            __syncthreads();                                    // the next item's draw overwrites s_idx
+        }
     }
 }
 
@@ -559,121 +465,152 @@ int check_tiers(const void* store, const void* store_host, int dtype, int64_t ro
     return MDL_OK;
 }
 
-template <class T>
-int launch_tiered(const void* store, const void* store_host, int64_t T_dev, int64_t row_stride, int64_t T_total, const int64_t* off,
-                  int64_t n_bags, const int32_t* bag, const int64_t* key_id, int64_t R, int N, int D, int chunks, int host_wgs, uint64_t seed,
-                  uint64_t counter, float* out, int32_t* idx_out, hipStream_t stream) {
-    const bool vec = D % Vec<T>::E == 0 && row_stride % Vec<T>::E == 0;
-    const int64_t items = R * chunks;
-    const T* sd = reinterpret_cast<const T*>(store);
-    const T* sh = reinterpret_cast<const T*>(store_host);
-    const dim3 grid((unsigned)items), narrow((unsigned)host_wgs), block(BS_THREADS);
-    if (vec)
-        hipLaunchKernelGGL((bag_sample_tier_kernel<T, true, PASS_DEV>), grid, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off, n_bags,
-                           bag, key_id, N, D, chunks, items, seed, counter, out, idx_out);
-    else
-        hipLaunchKernelGGL((bag_sample_tier_kernel<T, false, PASS_DEV>), grid, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off, n_bags,
-                           bag, key_id, N, D, chunks, items, seed, counter, out, idx_out);
-    MDL_LAUNCH_CHECK();
-    if (host_wgs == 0) return MDL_OK;                           // no host tier
-    if (vec)
-        hipLaunchKernelGGL((bag_sample_tier_kernel<T, true, PASS_HOST>), narrow, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off,
-                           n_bags, bag, key_id, N, D, chunks, items, seed, counter, out, idx_out);
-    else
-        hipLaunchKernelGGL((bag_sample_tier_kernel<T, false, PASS_HOST>), narrow, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off,
-                           n_bags, bag, key_id, N, D, chunks, items, seed, counter, out, idx_out);
-    MDL_LAUNCH_CHECK();
+// The sizes and the output side of a call as its entry point received them, before anything is narrowed to int.  A dense gather
+// (S1, S3) states N and brings no table; a pack (S2, S4) states n_chunks and T_out and brings cu, chunk_cu and row_bag.
+struct Call {
+    bool pack;
+    int64_t R;
+    int N;
+    int64_t n_chunks, T_out;
+    const int64_t *cu, *chunk_cu;
+    float* out;
+    int32_t *row_bag, *idx_out;
+};
+
+inline bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
+
+// The refusals all four entry points share, in one order for all of them: NULL / range / dtype (MDL_E_ARG), then alignment
+// (MDL_E_ALIGN), then the int32 launch geometry (MDL_E_UNSUPPORTED).  An optional pointer that is NULL is aligned.  Which of the store's
+// two bases may be NULL differs between the resident and the tiered forms and is the entry point's to say, before this.
+int check_call(const Store& st, const Draw& dr, const Call& c, int dtype) {
+    if (st.off == nullptr || dr.bag == nullptr || c.out == nullptr) return MDL_E_ARG;
+    if (c.pack ? (c.cu == nullptr || c.chunk_cu == nullptr || c.n_chunks < 0 || c.T_out < 0) : c.N < 1) return MDL_E_ARG;
+    if (c.R < 0 || st.D < 1 || st.T_total < 0 || st.n_bags < 0 || st.row_stride < st.D) return MDL_E_ARG;
+    if (dtype != MDL_STORE_F32 && dtype != MDL_STORE_F16 && dtype != MDL_STORE_BF16) return MDL_E_ARG;
+    if (!host_aligned16(st.dev) || !host_aligned16(st.host) || !host_aligned16(c.out)) return MDL_E_ALIGN;
+    if (misaligned(st.off, 8) || misaligned(dr.key_id, 8) || misaligned(c.cu, 8) || misaligned(c.chunk_cu, 8)) return MDL_E_ALIGN;
+    if (misaligned(dr.bag, 4) || misaligned(c.row_bag, 4) || misaligned(c.idx_out, 4)) return MDL_E_ALIGN;
+    // the output rows are indexed in int32, and with them the items: a dense gather has R * ceil(N / 64) <= R * N of them
+    if (c.pack ? (c.R > 0x7FFFFFFF || c.T_out > 0x7FFFFFFF || c.n_chunks > 0x7FFFFFFF) : c.R > 0x7FFFFFFF / (int64_t)c.N)
+        return MDL_E_UNSUPPORTED;
     return MDL_OK;
 }
 
-template <class T>
-int launch_pack_tiered(const void* store, const void* store_host, int64_t T_dev, int64_t row_stride, int64_t T_total, const int64_t* off,
-                       int64_t n_bags, const int32_t* bag, const int64_t* key_id, const int64_t* cu, const int64_t* chunk_cu, int R,
-                       int64_t n_chunks, int host_wgs, int64_t T_out, int D, uint64_t seed, uint64_t counter, float* out, int32_t* row_bag,
-                       int32_t* idx_out, hipStream_t stream) {
-    const bool vec = D % Vec<T>::E == 0 && row_stride % Vec<T>::E == 0;
-    const T* sd = reinterpret_cast<const T*>(store);
-    const T* sh = reinterpret_cast<const T*>(store_host);
-    const dim3 grid((unsigned)n_chunks), narrow((unsigned)host_wgs), block(BS_THREADS);
-    if (vec)
-        hipLaunchKernelGGL((bag_pack_tier_kernel<T, true, PASS_DEV>), grid, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off, n_bags,
-                           bag, key_id, cu, chunk_cu, R, n_chunks, T_out, D, seed, counter, out, row_bag, idx_out);
-    else
-        hipLaunchKernelGGL((bag_pack_tier_kernel<T, false, PASS_DEV>), grid, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off, n_bags,
-                           bag, key_id, cu, chunk_cu, R, n_chunks, T_out, D, seed, counter, out, row_bag, idx_out);
-    MDL_LAUNCH_CHECK();
-    if (host_wgs == 0) return MDL_OK;                           // no host tier
-    if (vec)
-        hipLaunchKernelGGL((bag_pack_tier_kernel<T, true, PASS_HOST>), narrow, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off,
-                           n_bags, bag, key_id, cu, chunk_cu, R, n_chunks, T_out, D, seed, counter, out, row_bag, idx_out);
-    else
-        hipLaunchKernelGGL((bag_pack_tier_kernel<T, false, PASS_HOST>), narrow, block, 0, stream, sd, sh, T_dev, row_stride, T_total, off,
-                           n_bags, bag, key_id, cu, chunk_cu, R, n_chunks, T_out, D, seed, counter, out, row_bag, idx_out);
-    MDL_LAUNCH_CHECK();
-    return MDL_OK;
+// How a call's items are shared out: one PASS_ALL launch (the resident store), or a PASS_DEV launch followed, when host_wgs > 0, by a
+// PASS_HOST launch of host_wgs workgroups.
+struct Passes {
+    bool tiered;
+    int host_wgs;
+};
+
+// The one launcher: the dtype dispatch, the choice of the copy path and every launch of this file.
+template <class Job>
+int launch(const Store& st, const Draw& dr, const Job& job, Passes passes, int dtype, hipStream_t stream) {
+    const auto run = [&](auto elem, auto vec16) -> int {        // the launches of one element type and one copy path
+        using T = decltype(elem);
+        constexpr bool VEC = decltype(vec16)::value;
+        const dim3 grid((unsigned)job.items), narrow((unsigned)passes.host_wgs), block(BS_THREADS);
+        if (!passes.tiered) {
+            hipLaunchKernelGGL((bag_gather_kernel<T, VEC, PASS_ALL, Job>), grid, block, 0, stream, st, dr, job);
+            MDL_LAUNCH_CHECK();
+            return MDL_OK;
+        }
+        hipLaunchKernelGGL((bag_gather_kernel<T, VEC, PASS_DEV, Job>), grid, block, 0, stream, st, dr, job);
+        MDL_LAUNCH_CHECK();
+        if (passes.host_wgs == 0) return MDL_OK;                // no host tier
+        hipLaunchKernelGGL((bag_gather_kernel<T, VEC, PASS_HOST, Job>), narrow, block, 0, stream, st, dr, job);
+        MDL_LAUNCH_CHECK();
+        return MDL_OK;
+    };
+    const auto typed = [&](auto elem) -> int {                  // 16-byte copies when every row of both sides is 16-byte aligned
+        constexpr int E = Vec<decltype(elem)>::E;
+        const bool vec = st.D % E == 0 && st.row_stride % E == 0;
+        return vec ? run(elem, std::true_type()) : run(elem, std::false_type());
+    };
+    switch (dtype) {
+        case MDL_STORE_F32:
+            return typed(float());
+        case MDL_STORE_F16:
+            return typed(_Float16());
+        default:
+            return typed(bf16_t());
+    }
 }
+
+inline int chunks_of(int N) { return (N + BS_TOK - 1) / BS_TOK; }
 
 }  // namespace
 }  // namespace mdl
 
+using namespace mdl;
+
+// The four entry points fill the records, say what is theirs alone -- which store base may be NULL, and for S3 / S4 the tiers' ranges --
+// and then go through the same steps: check_call, nothing to do (MDL_OK), [tiered: the runtime's view of store_host], launch.
+// check_tiers is the safety code in front of a kernel that reads host memory and stays whole: it states the tiers' rules again,
+// none of which can fail by then, before it asks the runtime.
+
+extern "C" int mdl_bag_sample(const void* store, int dtype, int64_t row_stride, int64_t T_total, const int64_t* off, int64_t n_bags,
+                              const int32_t* bag, const int64_t* key_id, int64_t R, int N, int D, uint64_t seed, uint64_t counter,
+                              float* out, int32_t* idx_out, void* stream) {
+    const Store st = {store, nullptr, T_total, row_stride, T_total, off, n_bags, D};
+    const Draw dr = {bag, key_id, seed, counter};
+    const Call call = {false, R, N, 0, 0, nullptr, nullptr, out, nullptr, idx_out};
+    if (store == nullptr) return MDL_E_ARG;
+    const int rc = check_call(st, dr, call, dtype);
+    if (rc != MDL_OK) return rc;
+    if (R == 0) return MDL_OK;
+    const SampleJob job = {N, chunks_of(N), R * chunks_of(N), out, idx_out};
+    return launch(st, dr, job, Passes{false, 0}, dtype, (hipStream_t)stream);
+}
+
+extern "C" int mdl_bag_pack(const void* store, int dtype, int64_t row_stride, int64_t T_total, const int64_t* off, int64_t n_bags,
+                            const int32_t* bag, const int64_t* key_id, const int64_t* cu, const int64_t* chunk_cu, int64_t R,
+                            int64_t n_chunks, int64_t T_out, int D, uint64_t seed, uint64_t counter, float* out, int32_t* row_bag,
+                            int32_t* idx_out, void* stream) {
+    const Store st = {store, nullptr, T_total, row_stride, T_total, off, n_bags, D};
+    const Draw dr = {bag, key_id, seed, counter};
+    const Call call = {true, R, 0, n_chunks, T_out, cu, chunk_cu, out, row_bag, idx_out};
+    if (store == nullptr) return MDL_E_ARG;
+    const int rc = check_call(st, dr, call, dtype);
+    if (rc != MDL_OK) return rc;
+    if (R == 0 || T_out == 0 || n_chunks == 0) return MDL_OK;
+    const PackJob job = {cu, chunk_cu, (int)R, T_out, n_chunks, out, row_bag, idx_out};
+    return launch(st, dr, job, Passes{false, 0}, dtype, (hipStream_t)stream);
+}
+
 extern "C" int mdl_bag_sample_tiered(const void* store, const void* store_host, int dtype, int64_t row_stride, int64_t T_total, int64_t T_dev,
                                      const int64_t* off, int64_t n_bags, const int32_t* bag, const int64_t* key_id, int64_t R, int N, int D,
                                      uint64_t seed, uint64_t counter, float* out, int32_t* idx_out, int host_wgs, void* stream) {
-    if (off == nullptr || bag == nullptr || out == nullptr) return MDL_E_ARG;
-    if (R < 0 || N < 1 || n_bags < 0) return MDL_E_ARG;
-    if (!host_aligned16(out)) return MDL_E_ALIGN;
-    if ((reinterpret_cast<uintptr_t>(off) & 7u) || (reinterpret_cast<uintptr_t>(bag) & 3u) || (reinterpret_cast<uintptr_t>(key_id) & 7u) ||
-        (reinterpret_cast<uintptr_t>(idx_out) & 3u))
-        return MDL_E_ALIGN;
-    const int chunks = (N + BS_TOK - 1) / BS_TOK;
-    if (R > 0x7FFFFFFF / (int64_t)N || R * chunks > 0x7FFFFFFF) return MDL_E_UNSUPPORTED;
-    const void* host_dev;
-    int wgs;
-    const int rc = check_tiers(store, store_host, dtype, row_stride, T_total, T_dev, D, host_wgs, R * chunks, &host_dev, &wgs);
+    Store st = {store, store_host, T_dev, row_stride, T_total, off, n_bags, D};
+    const Draw dr = {bag, key_id, seed, counter};
+    const Call call = {false, R, N, 0, 0, nullptr, nullptr, out, nullptr, idx_out};
+    if (T_dev < 0 || T_dev > T_total || host_wgs < 0) return MDL_E_ARG;
+    if ((T_dev > 0 && store == nullptr) || (T_dev < T_total && store_host == nullptr)) return MDL_E_ARG;      // a tier of no rows has no base
+    int rc = check_call(st, dr, call, dtype);
     if (rc != MDL_OK) return rc;
     if (R == 0) return MDL_OK;
-    hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case MDL_STORE_F32:
-            return launch_tiered<float>(store, host_dev, T_dev, row_stride, T_total, off, n_bags, bag, key_id, R, N, D, chunks, wgs, seed,
-                                        counter, out, idx_out, s);
-        case MDL_STORE_F16:
-            return launch_tiered<_Float16>(store, host_dev, T_dev, row_stride, T_total, off, n_bags, bag, key_id, R, N, D, chunks, wgs, seed,
-                                           counter, out, idx_out, s);
-        default:
-            return launch_tiered<bf16_t>(store, host_dev, T_dev, row_stride, T_total, off, n_bags, bag, key_id, R, N, D, chunks, wgs, seed,
-                                         counter, out, idx_out, s);
-    }
+    const SampleJob job = {N, chunks_of(N), R * chunks_of(N), out, idx_out};
+    Passes passes = {true, 0};
+    rc = check_tiers(store, store_host, dtype, row_stride, T_total, T_dev, D, host_wgs, job.items, &st.host, &passes.host_wgs);
+    if (rc != MDL_OK) return rc;
+    return launch(st, dr, job, passes, dtype, (hipStream_t)stream);
 }
 
 extern "C" int mdl_bag_pack_tiered(const void* store, const void* store_host, int dtype, int64_t row_stride, int64_t T_total, int64_t T_dev,
                                    const int64_t* off, int64_t n_bags, const int32_t* bag, const int64_t* key_id, const int64_t* cu,
                                    const int64_t* chunk_cu, int64_t R, int64_t n_chunks, int64_t T_out, int D, uint64_t seed, uint64_t counter,
                                    float* out, int32_t* row_bag, int32_t* idx_out, int host_wgs, void* stream) {
-    if (off == nullptr || bag == nullptr || cu == nullptr || chunk_cu == nullptr || out == nullptr) return MDL_E_ARG;
-    if (R < 0 || n_chunks < 0 || T_out < 0 || n_bags < 0) return MDL_E_ARG;
-    if (!host_aligned16(out)) return MDL_E_ALIGN;
-    if ((reinterpret_cast<uintptr_t>(off) & 7u) || (reinterpret_cast<uintptr_t>(bag) & 3u) || (reinterpret_cast<uintptr_t>(key_id) & 7u) ||
-        (reinterpret_cast<uintptr_t>(cu) & 7u) || (reinterpret_cast<uintptr_t>(chunk_cu) & 7u) ||
-        (reinterpret_cast<uintptr_t>(row_bag) & 3u) || (reinterpret_cast<uintptr_t>(idx_out) & 3u))
-        return MDL_E_ALIGN;
-    if (R > 0x7FFFFFFF || T_out > 0x7FFFFFFF || n_chunks > 0x7FFFFFFF) return MDL_E_UNSUPPORTED;
-    const bool nothing = R == 0 || T_out == 0 || n_chunks == 0;
-    const void* host_dev;
-    int wgs;
-    const int rc = check_tiers(store, store_host, dtype, row_stride, T_total, T_dev, D, host_wgs, nothing ? 0 : n_chunks, &host_dev, &wgs);
+    Store st = {store, store_host, T_dev, row_stride, T_total, off, n_bags, D};
+    const Draw dr = {bag, key_id, seed, counter};
+    const Call call = {true, R, 0, n_chunks, T_out, cu, chunk_cu, out, row_bag, idx_out};
+    if (T_dev < 0 || T_dev > T_total || host_wgs < 0) return MDL_E_ARG;
+    if ((T_dev > 0 && store == nullptr) || (T_dev < T_total && store_host == nullptr)) return MDL_E_ARG;      // a tier of no rows has no base
+    int rc = check_call(st, dr, call, dtype);
     if (rc != MDL_OK) return rc;
-    if (nothing) return MDL_OK;
-    hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case MDL_STORE_F32:
-            return launch_pack_tiered<float>(store, host_dev, T_dev, row_stride, T_total, off, n_bags, bag, key_id, cu, chunk_cu, (int)R,
-                                             n_chunks, wgs, T_out, D, seed, counter, out, row_bag, idx_out, s);
-        case MDL_STORE_F16:
-            return launch_pack_tiered<_Float16>(store, host_dev, T_dev, row_stride, T_total, off, n_bags, bag, key_id, cu, chunk_cu, (int)R,
-                                                n_chunks, wgs, T_out, D, seed, counter, out, row_bag, idx_out, s);
-        default:
-            return launch_pack_tiered<bf16_t>(store, host_dev, T_dev, row_stride, T_total, off, n_bags, bag, key_id, cu, chunk_cu, (int)R,
-                                              n_chunks, wgs, T_out, D, seed, counter, out, row_bag, idx_out, s);
-    }
+    if (R == 0 || T_out == 0 || n_chunks == 0) return MDL_OK;
+    const PackJob job = {cu, chunk_cu, (int)R, T_out, n_chunks, out, row_bag, idx_out};
+    Passes passes = {true, 0};
+    rc = check_tiers(store, store_host, dtype, row_stride, T_total, T_dev, D, host_wgs, job.items, &st.host, &passes.host_wgs);
+    if (rc != MDL_OK) return rc;
+    return launch(st, dr, job, passes, dtype, (hipStream_t)stream);
 }

@@ -1695,6 +1695,48 @@ STORE_DTYPES = {torch.float32: _native._DEFINES["MDL_STORE_F32"], torch.float16:
 _U64 = (1 << 64) - 1
 
 
+def _require_store(t, name="store_rows", on_device=True):
+    """t is one tier of a store: [T, D] in one of the three store dtypes, unit column stride; on_device: and lives on a device."""
+    if t.dim() != 2 or t.dtype not in STORE_DTYPES or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise RuntimeError("madeleine_amd: %s must be [T, D] float32 / float16 / bfloat16 with unit column stride" % name)
+    if on_device and not t.is_cuda:
+        raise RuntimeError("madeleine_amd: %s must live on a ROCm device (got %s); there is no CPU fallback" % (name, t.device))
+
+
+def _require_draw_tables(off, bag, key_id, per):
+    """The tables of the draw: off int64 [n_bags + 1], bag int32 [R], key_id None or int64 [R] (one entry per output `per`)."""
+    _require(off, "off", torch.int64)
+    _require(bag, "bag", torch.int32)
+    if key_id is not None:
+        _require(key_id, "key_id", torch.int64)
+        if key_id.numel() != bag.numel():
+            raise RuntimeError("madeleine_amd: key_id and bag must have one entry per output %s" % per)
+    if off.dim() != 1 or off.numel() < 1:
+        raise RuntimeError("madeleine_amd: off must be [n_bags + 1]")
+
+
+def _require_pack_tables(cu, chunk_cu, R, n_rows, n_chunks, fn):
+    """The tables of a pack: cu, chunk_cu int64 [R + 1], and their last entries n_rows, n_chunks as the caller `fn` passed them."""
+    _require(cu, "cu", torch.int64)
+    _require(chunk_cu, "chunk_cu", torch.int64)
+    if cu.numel() != R + 1 or chunk_cu.numel() != R + 1:
+        raise RuntimeError("madeleine_amd: cu and chunk_cu must be [R + 1] = [%d]" % (R + 1))
+    if n_rows < 0 or n_chunks < 0:
+        raise RuntimeError("madeleine_amd: %s needs n_rows >= 0 and n_chunks >= 0" % fn)
+
+
+def _sample_outputs(R, N, D, device, return_indices):
+    """out [R, N, D] fp32 and idx [R, N] int32 (None unless asked for)"""
+    return (torch.empty(R, N, D, device=device, dtype=torch.float32),
+            torch.empty(R, N, device=device, dtype=torch.int32) if return_indices else None)
+
+
+def _pack_outputs(T, D, device, return_indices):
+    """out [T, D] fp32, row_bag [T] int32 and idx [T] int32 (None unless asked for)"""
+    return (torch.empty(T, D, device=device, dtype=torch.float32), torch.empty(T, device=device, dtype=torch.int32),
+            torch.empty(T, device=device, dtype=torch.int32) if return_indices else None)
+
+
 def bag_sample(store_rows, off, bag, key_id, n_tokens, seed, counter, return_indices=False):
     """out [R, n_tokens, D] fp32 <- for every output row r, n_tokens rows of stored bag bag[r] (rows off[bag[r]] .. off[bag[r] + 1] - 1
     of store_rows [T, D], fp32 / fp16 / bf16, unit column stride): without replacement in random order when the bag has at least
@@ -1702,21 +1744,10 @@ def bag_sample(store_rows, off, bag, key_id, n_tokens, seed, counter, return_ind
     the current stream).  Row r's draw is a function of (seed, counter, key_id[r]) alone; key_id None: key_id[r] = bag[r].
     off int64 [n_bags + 1], bag int32 [R], key_id int64 [R], all on the device.  No autograd (features are inputs), no host read,
     no allocation beyond the outputs.  return_indices: also idx [R, n_tokens] int32, the chosen row inside the bag (-1: absent)."""
-    if store_rows.dim() != 2 or store_rows.dtype not in STORE_DTYPES or (store_rows.shape[1] > 1 and store_rows.stride(1) != 1):
-        raise RuntimeError("madeleine_amd: store_rows must be [T, D] float32 / float16 / bfloat16 with unit column stride")
-    if not store_rows.is_cuda:
-        raise RuntimeError("madeleine_amd: store_rows must live on a ROCm device (got %s); there is no CPU fallback" % store_rows.device)
-    _require(off, "off", torch.int64)
-    _require(bag, "bag", torch.int32)
-    if key_id is not None:
-        _require(key_id, "key_id", torch.int64)
-        if key_id.numel() != bag.numel():
-            raise RuntimeError("madeleine_amd: key_id and bag must have one entry per output row")
-    if off.dim() != 1 or off.numel() < 1:
-        raise RuntimeError("madeleine_amd: off must be [n_bags + 1]")
+    _require_store(store_rows)
+    _require_draw_tables(off, bag, key_id, "row")
     R, N, D = bag.numel(), int(n_tokens), store_rows.shape[1]
-    out = torch.empty(R, N, D, device=store_rows.device, dtype=torch.float32)
-    idx = torch.empty(R, N, device=store_rows.device, dtype=torch.int32) if return_indices else None
+    out, idx = _sample_outputs(R, N, D, store_rows.device, return_indices)
     with _timed("bag_sample", ("byte", R * N * D * (4.0 + store_rows.element_size()))):
         _call("mdl_bag_sample", store_rows, STORE_DTYPES[store_rows.dtype], store_rows.stride(0) if store_rows.shape[0] > 1 else D,
               store_rows.shape[0], off, off.numel() - 1, bag, key_id, R, N, D, int(seed) & _U64, int(counter) & _U64, out, idx, _stream(),
@@ -1732,28 +1763,11 @@ def bag_pack(store_rows, off, bag, key_id, cu, chunk_cu, n_rows, n_chunks, seed,
     on every row of bag r.  cu, chunk_cu int64 [R + 1] on the device (chunk_cu: the prefix sum of ceil(L_r / 64)); n_rows = cu[R] and
     n_chunks = chunk_cu[R] as host integers.  The other arguments, the checks and the byte accounting are bag_sample's.  No autograd,
     no host read, no allocation beyond the outputs.  return_indices: also idx [n_rows] int32 (row inside the bag, -1: zeros)."""
-    if store_rows.dim() != 2 or store_rows.dtype not in STORE_DTYPES or (store_rows.shape[1] > 1 and store_rows.stride(1) != 1):
-        raise RuntimeError("madeleine_amd: store_rows must be [T, D] float32 / float16 / bfloat16 with unit column stride")
-    if not store_rows.is_cuda:
-        raise RuntimeError("madeleine_amd: store_rows must live on a ROCm device (got %s); there is no CPU fallback" % store_rows.device)
-    _require(off, "off", torch.int64)
-    _require(bag, "bag", torch.int32)
-    _require(cu, "cu", torch.int64)
-    _require(chunk_cu, "chunk_cu", torch.int64)
-    if key_id is not None:
-        _require(key_id, "key_id", torch.int64)
-        if key_id.numel() != bag.numel():
-            raise RuntimeError("madeleine_amd: key_id and bag must have one entry per output bag")
-    if off.dim() != 1 or off.numel() < 1:
-        raise RuntimeError("madeleine_amd: off must be [n_bags + 1]")
+    _require_store(store_rows)
+    _require_draw_tables(off, bag, key_id, "bag")
     R, T, D = bag.numel(), int(n_rows), store_rows.shape[1]
-    if cu.numel() != R + 1 or chunk_cu.numel() != R + 1:
-        raise RuntimeError("madeleine_amd: cu and chunk_cu must be [R + 1] = [%d]" % (R + 1))
-    if T < 0 or n_chunks < 0:
-        raise RuntimeError("madeleine_amd: bag_pack needs n_rows >= 0 and n_chunks >= 0")
-    out = torch.empty(T, D, device=store_rows.device, dtype=torch.float32)
-    row_bag = torch.empty(T, device=store_rows.device, dtype=torch.int32)
-    idx = torch.empty(T, device=store_rows.device, dtype=torch.int32) if return_indices else None
+    _require_pack_tables(cu, chunk_cu, R, T, n_chunks, "bag_pack")
+    out, row_bag, idx = _pack_outputs(T, D, store_rows.device, return_indices)
     if R == 0 or T == 0:       # nothing to pack (an empty tensor has no address to pass)
         return (out, row_bag, idx) if return_indices else (out, row_bag)
     with _timed("bag_pack", ("byte", T * D * (4.0 + store_rows.element_size()))):
@@ -1770,8 +1784,8 @@ def _require_tiers(store_rows, host_rows):
     host memory (None or no rows: no host tier), same dtype and row stride.  The pinned check is made here, before any native call: the
     kernel reads the host tier over PCIe, and a launch on pageable memory is a GPU fault, not an error code."""
     for t, name in ((store_rows, "store_rows"), (host_rows, "host_rows")):
-        if t is not None and (t.dim() != 2 or t.dtype not in STORE_DTYPES or (t.shape[1] > 1 and t.stride(1) != 1)):
-            raise RuntimeError("madeleine_amd: %s must be [T, D] float32 / float16 / bfloat16 with unit column stride" % name)
+        if t is not None:
+            _require_store(t, name, on_device=False)
     if host_rows is not None and host_rows.shape[0] == 0:
         host_rows = None
     if host_rows is not None:
@@ -1781,8 +1795,7 @@ def _require_tiers(store_rows, host_rows):
         if host_rows.is_cuda or not host_rows.is_pinned():
             raise RuntimeError("madeleine_amd: host_rows must be pinned (registered) host memory (got %s, is_pinned() False): the "
                                "kernel reads it over PCIe and never touches pageable memory" % host_rows.device)
-    if not store_rows.is_cuda:
-        raise RuntimeError("madeleine_amd: store_rows must live on a ROCm device (got %s); there is no CPU fallback" % store_rows.device)
+    _require_store(store_rows)      # on a device: asked after the pinned check, which holds whatever else is wrong with the call
     D = store_rows.shape[1]
     strides = {t.stride(0) for t in (store_rows, host_rows) if t is not None and t.shape[0] > 1} or {D}
     if len(strides) != 1:
@@ -1797,17 +1810,9 @@ def bag_sample_tiered(store_rows, host_rows, off, bag, key_id, n_tokens, seed, c
     The same draw, the same bits as bag_sample on the concatenation.  RuntimeError before any native call when host_rows is not
     pinned."""
     host_rows, D, stride, T_dev, T_total = _require_tiers(store_rows, host_rows)
-    _require(off, "off", torch.int64)
-    _require(bag, "bag", torch.int32)
-    if key_id is not None:
-        _require(key_id, "key_id", torch.int64)
-        if key_id.numel() != bag.numel():
-            raise RuntimeError("madeleine_amd: key_id and bag must have one entry per output row")
-    if off.dim() != 1 or off.numel() < 1:
-        raise RuntimeError("madeleine_amd: off must be [n_bags + 1]")
+    _require_draw_tables(off, bag, key_id, "row")
     R, N = bag.numel(), int(n_tokens)
-    out = torch.empty(R, N, D, device=store_rows.device, dtype=torch.float32)
-    idx = torch.empty(R, N, device=store_rows.device, dtype=torch.int32) if return_indices else None
+    out, idx = _sample_outputs(R, N, D, store_rows.device, return_indices)
     with _timed("bag_sample", ("byte", R * N * D * (4.0 + store_rows.element_size()))):
         _call("mdl_bag_sample_tiered", store_rows if T_dev else None, host_rows, STORE_DTYPES[store_rows.dtype], stride, T_total, T_dev, off,
               off.numel() - 1, bag, key_id, R, N, D, int(seed) & _U64, int(counter) & _U64, out, idx, int(host_wgs), _stream(),
@@ -1819,24 +1824,10 @@ def bag_pack_tiered(store_rows, host_rows, off, bag, key_id, cu, chunk_cu, n_row
                     host_wgs=0):
     """bag_pack over the two-tier store of bag_sample_tiered: the same outputs, bit for bit, as bag_pack on the concatenation."""
     host_rows, D, stride, T_dev, T_total = _require_tiers(store_rows, host_rows)
-    _require(off, "off", torch.int64)
-    _require(bag, "bag", torch.int32)
-    _require(cu, "cu", torch.int64)
-    _require(chunk_cu, "chunk_cu", torch.int64)
-    if key_id is not None:
-        _require(key_id, "key_id", torch.int64)
-        if key_id.numel() != bag.numel():
-            raise RuntimeError("madeleine_amd: key_id and bag must have one entry per output bag")
-    if off.dim() != 1 or off.numel() < 1:
-        raise RuntimeError("madeleine_amd: off must be [n_bags + 1]")
+    _require_draw_tables(off, bag, key_id, "bag")
     R, T = bag.numel(), int(n_rows)
-    if cu.numel() != R + 1 or chunk_cu.numel() != R + 1:
-        raise RuntimeError("madeleine_amd: cu and chunk_cu must be [R + 1] = [%d]" % (R + 1))
-    if T < 0 or n_chunks < 0:
-        raise RuntimeError("madeleine_amd: bag_pack_tiered needs n_rows >= 0 and n_chunks >= 0")
-    out = torch.empty(T, D, device=store_rows.device, dtype=torch.float32)
-    row_bag = torch.empty(T, device=store_rows.device, dtype=torch.int32)
-    idx = torch.empty(T, device=store_rows.device, dtype=torch.int32) if return_indices else None
+    _require_pack_tables(cu, chunk_cu, R, T, n_chunks, "bag_pack_tiered")
+    out, row_bag, idx = _pack_outputs(T, D, store_rows.device, return_indices)
     if R == 0 or T == 0:       # nothing to pack (an empty tensor has no address to pass)
         return (out, row_bag, idx) if return_indices else (out, row_bag)
     with _timed("bag_pack", ("byte", T * D * (4.0 + store_rows.element_size()))):

@@ -149,8 +149,9 @@ def test_launchers_refuse_bad_arguments_before_any_query_or_launch():
         assert call(R=-1) == E_ARG and call(D=0) == E_ARG and call(dtype=3) == E_ARG and call(n_bags=-1) == E_ARG and call(stride=7) == E_ARG
         assert call(out=p + 8) == E_ALIGN and call(store=p + 4) == E_ALIGN and call(off=p + 68) == E_ALIGN and call(bag=p + 98) == E_ALIGN
         assert call(key=p + 132) == E_ALIGN and call(idx=p + 386) == E_ALIGN
+        assert call(host=p + 452) == E_ALIGN and call(dtype=-1) == E_ARG           # a misaligned store_host, even with no row in it
         assert call(R=0) == 0 and call(R=0, store=None, T=0, T_dev=0) == 0        # nothing to do: no launch; an empty store needs no tier
-    assert sample(N=0) == E_ARG and sample(R=2 ** 31, N=2) == E_UNSUP
+    assert sample(N=0) == E_ARG and sample(N=-5) == E_ARG and sample(R=2 ** 31, N=2) == E_UNSUP
     assert pack(cu=None) == E_ARG and pack(chunk=None) == E_ARG and pack(T_out=-1) == E_ARG and pack(chunks=-1) == E_ARG
     assert pack(cu=p + 196) == E_ALIGN and pack(chunk=p + 260) == E_ALIGN and pack(row_bag=p + 322) == E_ALIGN
     assert pack(T_out=2 ** 31) == E_UNSUP and pack(chunks=2 ** 31) == E_UNSUP and pack(T_out=0) == 0 and pack(chunks=0) == 0
