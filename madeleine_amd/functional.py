@@ -299,79 +299,85 @@ def attnpool_bwd_raw(E2d, Wa, Wb, wc, act_a, act_b, d_scores, dE, p_drop, seed, 
     return grads
 
 
+def _pool_src(E):
+    """(entry-point suffix, leading arguments) of a pooling call on E: an fp32 / bf16 tensor [T, ldE], or the split image of one."""
+    if isinstance(E, SplitImage):
+        return "_img", (E.data, E.K * 4, E.scale)
+    return _sfx(E), (E, E.stride(0))
+
+
+def _pool_fwd(stem, timed, E, scores, n_out, max_len, bags, pooled_shape=None):
+    """The pooling forward mdl_abmil_<stem><suffix of E> over n_out bags or segments of at most max_len tokens -> (pooled, stat_m,
+    stat_l).  bags: what the entry point takes between its outputs and H; timed: the arguments of _timed."""
+    sfx, src = _pool_src(E)
+    H = scores.shape[-1]
+    out = _pool_outputs(n_out, H, scores.device, pooled_shape)
+    ws = _ws_for("mdl_abmil_pool_ws_bytes", scores.device, n_out, max_len, H)
+    with _timed(*timed):
+        _call("mdl_abmil_%s%s" % (stem, sfx), *src, scores, *out, *bags, H, ws, _stream())
+    return out
+
+
+def _pool_bwd(stem, timed, E, scores, grads, bags):
+    """The pooling backward mdl_abmil_<stem><suffix of E>.  grads: what the entry point takes between the scores and `bags`."""
+    sfx, src = _pool_src(E)
+    with _timed(*timed):
+        _call("mdl_abmil_%s%s" % (stem, sfx), *src, scores, *grads, *bags, scores.shape[-1], _stream())
+
+
+def _pool_bytes(rows, H, row_bytes, n_bags):
+    """("byte", n): the HBM traffic of a whole-bag pooling pass that moves row_bytes per token and head, and one pooled row per bag."""
+    return "byte", float(rows) * H * row_bytes + n_bags * H * HID * 4.0
+
+
 def pool_fwd_raw(E2d, scores, n_bags, N, cu_seqlens, max_len):
     H = scores.shape[-1]
-    out = _pool_outputs(n_bags, H, E2d.device)
-    ws = _ws_for("mdl_abmil_pool_ws_bytes", E2d.device, n_bags, max_len, H)
-    T = E2d.shape[0]
-    with _timed("pool_fwd", ("byte", float(T) * H * (HID * E2d.element_size() + 4) + n_bags * H * HID * 4.0)):
-        _call("mdl_abmil_pool_fwd" + _sfx(E2d), E2d, E2d.stride(0), scores, *out, n_bags, N, cu_seqlens, max_len, H, ws, _stream())
-    return out
+    work = _pool_bytes(E2d.shape[0], H, HID * E2d.element_size() + 4, n_bags)
+    return _pool_fwd("pool_fwd", ("pool_fwd", work), E2d, scores, n_bags, max_len, (n_bags, N, cu_seqlens, max_len))
 
 
 def pool_bwd_raw(E2d, scores, pooled, stat_m, stat_l, d_pooled, dE, accumulate, d_scores, accumulate_scores, n_bags, N,
                  cu_seqlens, max_len):
     H = scores.shape[-1]
-    T = E2d.shape[0]
-    nb = float(T) * H * (HID * E2d.element_size() * (1 if dE is None else 2) + 8) + n_bags * H * HID * 4.0
-    with _timed("pool_bwd", ("byte", nb)):
-        _call("mdl_abmil_pool_bwd" + _sfx(E2d), E2d, E2d.stride(0), scores, pooled, stat_m, stat_l, d_pooled, dE, int(accumulate), d_scores,
-              int(accumulate_scores), n_bags, N, cu_seqlens, max_len, H, _stream())
+    work = _pool_bytes(E2d.shape[0], H, HID * E2d.element_size() * (1 if dE is None else 2) + 8, n_bags)
+    _pool_bwd("pool_bwd", ("pool_bwd", work), E2d, scores,
+              (pooled, stat_m, stat_l, d_pooled, dE, int(accumulate), d_scores, int(accumulate_scores)), (n_bags, N, cu_seqlens, max_len))
 
 
 def pool_fwd_img_raw(Ei, scores, n_bags, N, cu_seqlens, max_len):
     """pool_fwd_raw on the split image of E (the split GEMM mode stores E as an image only)."""
-    H = scores.shape[-1]
-    out = _pool_outputs(n_bags, H, scores.device)
-    ws = _ws_for("mdl_abmil_pool_ws_bytes", scores.device, n_bags, max_len, H)
-    with _timed("pool_fwd", ("byte", float(Ei.rows) * H * (HID * 4 + 4) + n_bags * H * HID * 4.0)):
-        _call("mdl_abmil_pool_fwd_img", Ei.data, Ei.K * 4, Ei.scale, scores, *out, n_bags, N, cu_seqlens, max_len, H, ws, _stream())
-    return out
+    work = _pool_bytes(Ei.rows, scores.shape[-1], HID * 4 + 4, n_bags)
+    return _pool_fwd("pool_fwd", ("pool_fwd", work), Ei, scores, n_bags, max_len, (n_bags, N, cu_seqlens, max_len))
 
 
 def pool_dscores_img_raw(Ei, scores, pooled, stat_m, stat_l, d_pooled, d_scores, accumulate_scores, n_bags, N, cu_seqlens, max_len):
     """The score gradients of the pooling from the split image of E (pool_bwd_raw with dE = None)."""
-    H = scores.shape[-1]
-    with _timed("pool_bwd", ("byte", float(Ei.rows) * H * (HID * 4 + 8) + n_bags * H * HID * 4.0)):
-        _call("mdl_abmil_pool_dscores_img", Ei.data, Ei.K * 4, Ei.scale, scores, pooled, stat_m, stat_l, d_pooled, d_scores,
-              int(accumulate_scores), n_bags, N, cu_seqlens, max_len, H, _stream())
+    work = _pool_bytes(Ei.rows, scores.shape[-1], HID * 4 + 8, n_bags)
+    _pool_bwd("pool_dscores", ("pool_bwd", work), Ei, scores, (pooled, stat_m, stat_l, d_pooled, d_scores, int(accumulate_scores)),
+              (n_bags, N, cu_seqlens, max_len))
 
 
 def pool_view_fwd_raw(E2d, scores, n_bags, N, token_idx):
-    H = scores.shape[-1]
     n_idx = token_idx.numel()
-    out = _pool_outputs(n_bags, H, E2d.device)
-    ws = _ws_for("mdl_abmil_pool_ws_bytes", E2d.device, n_bags, n_idx, H)
-    with _timed("pool_view_fwd"):
-        _call("mdl_abmil_pool_view_fwd" + _sfx(E2d), E2d, E2d.stride(0), scores, *out, n_bags, N, token_idx, n_idx, H, ws, _stream())
-    return out
+    return _pool_fwd("pool_view_fwd", ("pool_view_fwd",), E2d, scores, n_bags, n_idx, (n_bags, N, token_idx, n_idx))
 
 
 def pool_view_bwd_raw(E2d, scores, pooled, stat_m, stat_l, d_pooled, dE, d_scores, n_bags, N, token_idx):
     """Accumulates the view's contribution into dE and / or d_scores (either may be None)."""
-    H = scores.shape[-1]
-    with _timed("pool_view_bwd"):
-        _call("mdl_abmil_pool_view_bwd" + _sfx(E2d), E2d, E2d.stride(0), scores, pooled, stat_m, stat_l, d_pooled, dE, d_scores, n_bags, N,
-              token_idx, token_idx.numel(), H, _stream())
+    _pool_bwd("pool_view_bwd", ("pool_view_bwd",), E2d, scores, (pooled, stat_m, stat_l, d_pooled, dE, d_scores),
+              (n_bags, N, token_idx, token_idx.numel()))
 
 
 def pool_rview_fwd_raw(E2d, scores, n_bags, perm, vcu, max_view_len):
     """The two half-bag views of every packed bag (mdl_abmil_pool_rview_fwd): -> (pooled [n_bags, 2, H*512], stat_m, stat_l [2*n_bags, H])."""
-    H = scores.shape[-1]
-    out = _pool_outputs(2 * n_bags, H, E2d.device, pooled_shape=(n_bags, 2, H * HID))
-    ws = _ws_for("mdl_abmil_pool_ws_bytes", E2d.device, 2 * n_bags, max_view_len, H)
-    with _timed("pool_view_fwd"):
-        _call("mdl_abmil_pool_rview_fwd" + _sfx(E2d), E2d, E2d.stride(0), scores, *out, n_bags, perm, vcu, int(max_view_len), H, ws,
-              _stream())
-    return out
+    return _pool_fwd("pool_rview_fwd", ("pool_view_fwd",), E2d, scores, 2 * n_bags, max_view_len, (n_bags, perm, vcu, int(max_view_len)),
+                     pooled_shape=(n_bags, 2, scores.shape[-1] * HID))
 
 
 def pool_rview_bwd_raw(E2d, scores, pooled, stat_m, stat_l, d_pooled, dE, d_scores, n_bags, perm, vcu, max_view_len):
     """Accumulates the ragged views' contribution (d_pooled [n_bags, 2, H*512]) into dE and / or d_scores (either may be None)."""
-    H = scores.shape[-1]
-    with _timed("pool_view_bwd"):
-        _call("mdl_abmil_pool_rview_bwd" + _sfx(E2d), E2d, E2d.stride(0), scores, pooled, stat_m, stat_l, d_pooled, dE, d_scores, n_bags,
-              perm, vcu, int(max_view_len), H, _stream())
+    _pool_bwd("pool_rview_bwd", ("pool_view_bwd",), E2d, scores, (pooled, stat_m, stat_l, d_pooled, dE, d_scores),
+              (n_bags, perm, vcu, int(max_view_len)))
 
 
 def _check_rview(E2d, cu_seqlens, rviews):
@@ -887,13 +893,7 @@ class WeightedPoolFn(torch.autograd.Function):
         _require(weights, "weights")
         n_bags, N, max_len, E2d = _bag_geometry(E, cu_seqlens, max_len)
         w2d = weights.reshape(E2d.shape[0], -1)
-        H = w2d.shape[-1]
-        pooled = torch.empty(n_bags, H * HID, device=E2d.device, dtype=torch.float32)
-        scratch = torch.empty(2, n_bags, H, device=E2d.device, dtype=torch.float32)
-        ws = _ws_for("mdl_abmil_pool_ws_bytes", E2d.device, n_bags, max_len, H)
-        with _timed("pool_fwd"):
-            _call("mdl_abmil_wpool_fwd" + _sfx(E2d), E2d, E2d.stride(0), w2d, pooled, scratch[0], scratch[1], n_bags, N, cu_seqlens, max_len,
-                  H, ws, _stream())
+        pooled, _, _ = _pool_fwd("wpool_fwd", ("pool_fwd",), E2d, w2d, n_bags, max_len, (n_bags, N, cu_seqlens, max_len))
         ctx.save_for_backward(E2d, w2d, cu_seqlens if cu_seqlens is not None else torch.empty(0))
         ctx.geom = (n_bags, N, max_len, cu_seqlens is not None, E.shape, weights.shape)
         return pooled
@@ -905,9 +905,7 @@ class WeightedPoolFn(torch.autograd.Function):
         cu = cu if ragged else None
         dE = torch.empty_like(E2d)
         dw = torch.empty_like(w2d)
-        with _timed("pool_bwd"):
-            _call("mdl_abmil_wpool_bwd" + _sfx(E2d), E2d, E2d.stride(0), w2d, d_pooled.float().contiguous(), dE, 0, dw, n_bags, N, cu, max_len,
-                  w2d.shape[-1], _stream())
+        _pool_bwd("wpool_bwd", ("pool_bwd",), E2d, w2d, (d_pooled.float().contiguous(), dE, 0, dw), (n_bags, N, cu, max_len))
         return dE.view(e_shape), dw.view(w_shape), None, None
 
 

@@ -35,16 +35,32 @@ def timed(fn):
     return e0.elapsed_time(e1) / a.iters
 
 
+nbytes = BM * N * H * 512 * 4
+
+
+def report(what, ms, out):
+    print(f"{what} {ms:.4f} ms  {nbytes / ms / 1e9:.3f} TB/s  checksum {out.double().sum().item():.10e}")
+
+
 for name, Ex, fwd, bwd in (
     ("image", MF.split_image(E2), MF.pool_fwd_img_raw, MF.pool_dscores_img_raw),
     ("fp32", E2, MF.pool_fwd_raw, None),
+    ("bf16", E2.bfloat16(), MF.pool_fwd_raw, None),
 ):
-    nbytes = BM * N * H * 512 * 4
     out = fwd(Ex, scores, BM, N, None, N)
-    ms = timed(lambda: fwd(Ex, scores, BM, N, None, N))
-    print(f"pool_fwd[{name}] {ms:.4f} ms  {nbytes / ms / 1e9:.3f} TB/s  checksum {out[0].double().sum().item():.10e}")
+    report(f"pool_fwd[{name}]", timed(lambda: fwd(Ex, scores, BM, N, None, N)), out[0])
     if bwd is not None:
         pooled, m, l = out
         ds = torch.empty_like(scores)
-        ms = timed(lambda: bwd(Ex, scores, pooled, m, l, dpool, ds, 0, BM, N, None, N))
-        print(f"pool_dscores[{name}] {ms:.4f} ms  {nbytes / ms / 1e9:.3f} TB/s  checksum {ds.double().sum().item():.10e}")
+        report(f"pool_dscores[{name}]", timed(lambda: bwd(Ex, scores, pooled, m, l, dpool, ds, 0, BM, N, None, N)), ds)
+
+# the ragged half-bag views of the same rows (fp32): every bag shuffled in place and cut in two; the backward is the scores pass
+perm = torch.cat([b * N + torch.randperm(N, device=dev, generator=g) for b in range(BM)]).to(torch.int32)
+vcu = (torch.arange(2 * BM + 1, device=dev, dtype=torch.int64) * N) // 2
+half = N - N // 2
+out = MF.pool_rview_fwd_raw(E2, scores, BM, perm, vcu, half)
+report("pool_rview_fwd[fp32]", timed(lambda: MF.pool_rview_fwd_raw(E2, scores, BM, perm, vcu, half)), out[0])
+dpool2 = torch.randn(BM, 2, H * 512, device=dev, generator=g)
+ds = torch.zeros_like(scores)
+ms = timed(lambda: MF.pool_rview_bwd_raw(E2, scores, *out, dpool2, None, ds, BM, perm, vcu, half))
+report("pool_rview_dscores[fp32]", ms, ds)
