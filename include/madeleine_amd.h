@@ -797,6 +797,51 @@ int mdl_bag_pack_tiered(const void* store, const void* store_host, int dtype, in
                         float* out, int32_t* row_bag, int32_t* idx_out, int host_wgs, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * S5 -- the column means of whole stored bags: one vector per slide without the features leaving the store (ABI 26, additive).
+ * Replaces, for a cohort held in the store of S1 / S3, the loop of bin/extract_mean_embs.py (h5 read, feats.mean(0) per slide): the
+ * mean patch embedding that bin/run_linear_probing.py names as the baseline of every probe.
+ *
+ * store, dtype, row_stride, T_total, off, n_bags, bag [R]: as in S1; store_host, T_dev, host_wgs (mdl_bag_mean_tiered): as in S3.
+ * out [R, D] fp32, dense, 16-byte aligned: out[r, :] is the mean over ALL rows of stored bag bag[r]; a row of zeros (the mean of the
+ *   dataset's zero bag) for bag[r] == -1 and for a bag that is invalid by S1's bounds rule.
+ * chunk_cu [R + 1] (int64, device): the prefix sum of ceil(n_r / MDL_BAG_MEAN_ROWS), n_r the rows of bag[r] (0 for an absent stain),
+ *   chunk_cu[0] = 0; n_chunks = chunk_cu[R].  The same kind of table as S2's, with MDL_BAG_MEAN_ROWS for 64.
+ * ws: n_chunks * D floats (mdl_bag_mean_ws_bytes), 16-byte aligned, contents need no initialisation.
+ *
+ * Two launches, no atomics.  A work item is (output row r, chunk c): rows c * MDL_BAG_MEAN_ROWS .. of the bag, a contiguous range of
+ * the store.  One workgroup of MDL_BAG_MEAN_THREADS threads per item; a thread owns MDL_BAG_MEAN_COLS adjacent columns (16-byte loads
+ * when D and row_stride are multiples of 4 (fp32) / 8 (16-bit stores) elements, element-wise loads otherwise; fp16 / bf16 widened
+ * exactly) in one of G row groups,
+ *     G = MDL_BAG_MEAN_THREADS / min(MDL_BAG_MEAN_THREADS, next_pow2(ceil(D / MDL_BAG_MEAN_COLS)))
+ * and adds rows grp, grp + G, grp + 2 G, .. of the chunk in that order in fp32; the G sums are added in group order through LDS and
+ * the item's partial [D] goes to ws.  The second launch adds a bag's partials in chunk order, divides by n and writes out[r].
+ * Tiered: the items with a row at or beyond T_dev are walked by host_wgs persistent workgroups in a launch of their own, the others
+ * keep the one-workgroup-per-item grid; the tier is chosen per ROW, so a bag on both sides of T_dev is served like any other.
+ *
+ * Bit contract.  The bits of out[r] depend only on the rows of bag bag[r] (their values as stored), on D and on MDL_BAG_MEAN_ROWS
+ * (with _THREADS and _COLS): not on R, on the other bags or their order, on the tier of any row, on host_wgs or on row_stride (the
+ * 16-byte and the element-wise loads feed the same additions).  Addition depth: an element of out[r] of a bag of len rows has passed
+ * through at most
+ *     h(len) = ceil(min(len, MDL_BAG_MEAN_ROWS) / G) + (G - 1) + (ceil(len / MDL_BAG_MEAN_ROWS) - 1)
+ * fp32 additions (its row group's, the merge of the groups, the chunks), each of them rounded once, and one fp32 division.
+ *
+ * MDL_E_ARG: store / off / bag / chunk_cu / out / ws NULL, R, n_chunks, T_total or n_bags < 0, D < 1, row_stride < D, unknown dtype,
+ * (tiered) T_dev outside [0, T_total], host_wgs < 0 or a host tier the device cannot read.  MDL_E_ALIGN: store, out or ws not 16-byte
+ * aligned, a table misaligned for its type.  MDL_E_UNSUPPORTED: R or n_chunks beyond int32.  R == 0 or n_chunks == 0: MDL_OK, nothing
+ * is launched and nothing written (n_chunks == 0 with R > 0 means every bag is absent: the zeros are the caller's).  With inconsistent
+ * tables nothing outside the store is read and nothing outside out [R, D] and ws is written: a (bag, chunk) that chunk_cu and off do
+ * not agree on writes no partial, and a bag whose chunk range disagrees with its length is a row of zeros. */
+#define MDL_BAG_MEAN_ROWS 1024
+#define MDL_BAG_MEAN_THREADS 256
+#define MDL_BAG_MEAN_COLS 8
+int64_t mdl_bag_mean_ws_bytes(int64_t n_chunks, int D);
+int mdl_bag_mean(const void* store, int dtype, int64_t row_stride, int64_t T_total, const int64_t* off, int64_t n_bags, const int32_t* bag,
+                 const int64_t* chunk_cu, int64_t R, int64_t n_chunks, int D, float* out, void* ws, void* stream);
+int mdl_bag_mean_tiered(const void* store, const void* store_host, int dtype, int64_t row_stride, int64_t T_total, int64_t T_dev,
+                        const int64_t* off, int64_t n_bags, const int32_t* bag, const int64_t* chunk_cu, int64_t R, int64_t n_chunks, int D,
+                        float* out, void* ws, int host_wgs, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * P1-P3 -- the few-shot linear probe: P independent L2-regularised logistic fits over one embedding matrix, the decision values of
  * every case under every fit, and confusion matrix + AUC per fit (ABI 26, additive).  Replaces, for all (task, k, fold) problems of an
  * evaluation at once, bin/run_linear_probing.py:150-170: LogisticRegression(C=1, max_iter=10000).fit / .predict / .predict_proba

@@ -27,8 +27,9 @@
 // which keys) and one job, SampleJob (S1, S3) or PackJob (S2, S4).  gather_item, overloaded on the job, is the whole work of one
 // (output row, 64-token chunk) item; the draw (row_key, token_hash, feistel, draw_distinct), the placement of a bag (locate_bag) and
 // the copy loops (copy_rows, zero_rows) are device functions under it.  bag_gather_kernel<T, VEC, PASS, Job> is the only __global__
-// function and launch() the only place that launches it, so the four entry points draw and copy with the same code; they differ in
-// the records they fill and in the passes they ask for (PASS_ALL, or PASS_DEV then PASS_HOST: the tiered forms, further down).
+// function of the gathers and launch() the only place that launches it, so the four entry points draw and copy with the same code; they
+// differ in the records they fill and in the passes they ask for (PASS_ALL, or PASS_DEV then PASS_HOST: the tiered forms, further down).
+// The per-bag column means (S5, further down) are a third job of the same kernel and launcher, followed by a combine kernel.
 #include "common.hpp"
 #include <type_traits>
 
@@ -173,17 +174,26 @@ __device__ __forceinline__ V table(const V* p, int64_t i) {
     return ((const __attribute__((address_space(4))) V*)p)[i];
 }
 
+// Where the tables place stored bag g: returns n, its length, with `base` its first row of [0, T_total), or 0 (and base 0) for an
+// absent stain, by the table or by the bounds rule of the header comment.  A bag with n != 0 lies inside [0, T_total).
+__device__ __forceinline__ int64_t bag_extent(const Store& st, int g, int64_t& base) {
+    int64_t n64 = 0;
+    base = 0;
+    if (g >= 0 && g < st.n_bags) {
+        base = table(st.off, g);
+        n64 = table(st.off, g + 1) - base;
+        if (base < 0 || n64 < 1 || n64 > 0x7FFFFFFF || base > st.T_total - n64) n64 = base = 0;
+    }
+    return n64;
+}
+
 // The rows of stored bag g: returns n, its length, or 0 for an absent stain (by the table or by the bounds rule of the header comment);
 // `rows` is its first row (the tier's base when n == 0: never read).  Tiered (PASS != PASS_ALL): a bag on both sides of T_dev is an
 // absent stain; on_host says which pass owns the item.
 template <class T, int PASS>
 __device__ __forceinline__ uint32_t locate_bag(const Store& st, int g, const T*& rows, bool& on_host) {
-    int64_t base = 0, n64 = 0;
-    if (g >= 0 && g < st.n_bags) {
-        base = table(st.off, g);
-        n64 = table(st.off, g + 1) - base;
-        if (base < 0 || n64 < 1 || n64 > 0x7FFFFFFF || base > st.T_total - n64) n64 = 0;
-    }
+    int64_t base;
+    int64_t n64 = bag_extent(st, g, base);
     on_host = false;
     if (PASS != PASS_ALL && n64 != 0) {
         if (base >= st.T_dev) {                                 // wholly in the host tier: T_dev <= base, base + n <= T_total
@@ -392,7 +402,151 @@ __device__ __forceinline__ void gather_item(const Store& st, const Draw& dr, con
 #define BS_HOST_WGS 64                      // the host pass's grid when the caller passes host_wgs = 0
 #endif
 
-// The one kernel of this file: Job (SampleJob or PackJob) selects gather_item and names the gather in a kernel trace.  PASS_ALL and
+// ------------------------------------------------------------------------------------------------------------------------------------
+// bag_mean (S5 of the header) -- the column means of whole stored bags, the mean-embedding baseline of a cohort: a reduction over the
+// same store, through the same records, passes and launcher, followed by one small combine launch.  No atomics.
+//
+// Work split.  chunk_cu [R + 1] is the prefix sum of ceil(n_r / BM_ROWS): item w is chunk c = w - chunk_cu[r] of output row r (found
+// by the pack's binary search), rows c * BM_ROWS .. of stored bag bag[r] -- a CONTIGUOUS range of the store.  Inside the workgroup a
+// thread owns one slot of BM_COLS adjacent columns (one 16-byte load of a 16-bit store, two of an fp32 store; element-wise loads where
+// D or the stride forbid them) in one row group: lpr = min(256, next_pow2(ceil(D / BM_COLS))) adjacent lanes cover a row and the G =
+// 256 / lpr row groups take the chunk's rows t = grp, grp + G, grp + 2 G, ...  Each thread adds its rows in that order in fp32
+// (BM_INFLIGHT loads in flight, the additions in row order), the groups' sums are merged through LDS in the order 0, 1, .. G - 1, and
+// the fp32 partial [D] of the item goes to ws[w].  D > 256 * BM_COLS: the slots are walked in passes of 256.
+// bag_mean_combine_kernel then adds a bag's partials in chunk order, divides by n and writes out[r]; a bag the tables do not place
+// (absent, invalid, or chunk_cu disagreeing with off about its chunks) is a row of zeros.
+//
+// The order of the additions of a column is a function of (n, D, BM_ROWS) alone: lpr and G depend on D only -- not on the element
+// type, on the copy path (VEC or not: the stride), on the pass that served the chunk, on its grid or on the other bags.
+//
+// Tiers.  The split is per ROW: row a of [0, T_total) is read from the device tier when a < T_dev and from the host tier otherwise, so a
+// bag on both sides of T_dev is served like any other.  A chunk with a row at or beyond T_dev is the host pass's item, every other
+// chunk the device pass's.
+//
+// Bounds.  r comes out of a search over [0, R); the bag's rows are bag_extent's, inside [0, T_total); a chunk index outside the bag
+// writes nothing; ws is written at item w < n_chunks only and read at chunk_cu[r] .. chunk_cu[r + 1] - 1 only when that range lies in
+// [0, n_chunks) and has the length off gives; out is written at rows r < R.
+constexpr int BM_ROWS = MDL_BAG_MEAN_ROWS;
+constexpr int BM_COLS = MDL_BAG_MEAN_COLS;
+constexpr int BM_INFLIGHT = 8;              // rows a lane has in flight, both passes (16 for the 16-bit stores measured the same)
+static_assert(BS_THREADS == MDL_BAG_MEAN_THREADS && BM_COLS == 8, "the header's h(len) and the slot loads are written for these");
+
+struct MeanJob {
+    const int64_t* chunk_cu;                // [R + 1]
+    int R;
+    int64_t items;                          // n_chunks <= 2^31 - 1
+    float* ws;                              // [n_chunks, D]: one partial per item
+    float* out;                             // [R, D]
+};
+
+// lanes that cover one row: a power of two, a function of D alone
+__device__ __forceinline__ int mean_lanes_per_row(int D) {
+    const int ns = (D + BM_COLS - 1) / BM_COLS;
+    int lpr = 1;
+    while (lpr < ns && lpr < BS_THREADS) lpr <<= 1;
+    return lpr;
+}
+
+// columns col .. col + 7 of a store row, widened exactly; columns at or beyond D read as 0 (col < D)
+template <class T, bool VEC>
+__device__ __forceinline__ f32x8 load_slot(const T* __restrict__ row, int col, int D) {
+    f32x8 v;
+    if constexpr (VEC && Vec<T>::E == BM_COLS) {                // D % 8 == 0: the slot is whole
+        v = __builtin_convertvector(Vec<T>::ld(row + col), f32x8);
+    } else if constexpr (VEC) {                                 // fp32, D % 4 == 0
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        v.lo = Vec<T>::ld(row + col);
+        v.hi = col + 4 < D ? Vec<T>::ld(row + col + 4) : z;
+    } else {
+#pragma unroll
+        for (int j = 0; j < BM_COLS; ++j) v[j] = col + j < D ? Vec<T>::up(row[col + j]) : 0.f;
+    }
+    return v;
+}
+
+// Item w = (output row r, chunk c) of the mean: the partial column sums of rows c * BM_ROWS .. of bag bag[r] -> ws[w].  Uniform over the
+// workgroup, the early returns included; a caller that loops over items puts a barrier between two of them (s_part is reused).
+template <class T, bool VEC, int PASS, int INFLIGHT>
+__device__ __forceinline__ void gather_item(const Store& st, const Draw& dr, const MeanJob& job, int64_t w, int32_t*) {
+    __shared__ float s_part[BS_THREADS * BM_COLS];
+    const int tid = threadIdx.x, D = st.D;
+    int lo = 0, hi = job.R - 1;                                 // the last r of [0, R) with chunk_cu[r] <= w (bags of no chunks are passed over)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table(job.chunk_cu, mid) <= w) lo = mid; else hi = mid - 1;
+    }
+    const int r = lo;
+    const int64_t c = w - table(job.chunk_cu, r);
+    int64_t base;
+    const int64_t n = bag_extent(st, table(dr.bag, r), base);  // 0: absent
+    if (c < 0 || c >= (n + BM_ROWS - 1) / BM_ROWS) return;      // not a chunk of this bag (n == 0 included): nothing is read or written
+    const int64_t t_first = c * BM_ROWS, first = base + t_first;     // no overflow: c * BM_ROWS < n + BM_ROWS <= 2^31 + BM_ROWS
+    const int rows = n - t_first < BM_ROWS ? (int)(n - t_first) : BM_ROWS;         // >= 1, all inside the bag
+    if (PASS != PASS_ALL && (first + rows > st.T_dev) != (PASS == PASS_HOST)) return;     // the other pass's item
+
+    const int lpr = mean_lanes_per_row(D), G = BS_THREADS / lpr, grp = tid / lpr, s0 = tid - grp * lpr;
+    const int ns = (D + BM_COLS - 1) / BM_COLS;
+    const T* dev = static_cast<const T*>(st.dev);
+    const T* host = static_cast<const T*>(st.host);
+    const int64_t stride = st.row_stride, T_dev = st.T_dev;
+    float* part = job.ws + w * D;
+    for (int sb = 0; sb < ns; sb += lpr) {                      // one pass unless D > 256 * BM_COLS
+        const int s = sb + s0, col = s * BM_COLS;
+        f32x8 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (s < ns) {
+            for (int t0 = grp; t0 < rows; t0 += BM_INFLIGHT * G) {
+                f32x8 v[BM_INFLIGHT];
+#pragma unroll
+                for (int j = 0; j < BM_INFLIGHT; ++j) {
+                    const int t = t0 + j * G;
+                    if (t < rows) {
+                        const int64_t a = first + t;            // the row of [0, T_total)
+                        const T* row = (PASS == PASS_HOST && a >= T_dev) ? host + (a - T_dev) * stride : dev + a * stride;
+                        v[j] = load_slot<T, VEC>(row, col, D);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < BM_INFLIGHT; ++j)
+                    if (t0 + j * G < rows) acc += v[j];           // in row order
+            }
+        }
+        st4(s_part + tid * BM_COLS, acc.lo);
+        st4(s_part + tid * BM_COLS + 4, acc.hi);
+        __syncthreads();
+        for (int e = tid; e < lpr * BM_COLS; e += BS_THREADS) {  // column sb * 8 + e of the pass: its G group sums, in group order
+            if (sb * BM_COLS + e < D) {
+                float sum = s_part[e];
+                for (int gg = 1; gg < G; ++gg) sum += s_part[gg * lpr * BM_COLS + e];
+                part[sb * BM_COLS + e] = sum;
+            }
+        }
+        __syncthreads();                                        // the next pass overwrites s_part
+    }
+}
+
+// out[r] = (the partials of bag bag[r], added in chunk order) / n; zeros for a bag the tables do not place.  One workgroup per row.
+__global__ __launch_bounds__(BS_THREADS) void bag_mean_combine_kernel(Store st, Draw dr, MeanJob job) {
+    const int r = blockIdx.x, D = st.D;
+    int64_t base;
+    const int64_t n = bag_extent(st, table(dr.bag, r), base);
+    const int64_t nc = (n + BM_ROWS - 1) / BM_ROWS, p0 = table(job.chunk_cu, r), p1 = table(job.chunk_cu, r + 1);
+    const bool placed = n > 0 && p0 >= 0 && p1 >= p0 && p1 <= job.items && p1 - p0 == nc;
+    const float* __restrict__ part = job.ws + (placed ? p0 : 0) * D;
+    float* __restrict__ o = job.out + (int64_t)r * D;
+    const float len = (float)n;
+    for (int col = threadIdx.x; col < D; col += BS_THREADS) {
+        float sum = 0.f;
+        if (placed) {
+            sum = part[col];
+            for (int64_t k = 1; k < nc; ++k) sum += part[k * D + col];
+            sum /= len;
+        }
+        o[col] = sum;
+    }
+}
+
+// The kernel of every pass of this file: Job (SampleJob, PackJob or MeanJob) selects gather_item and names the work in a kernel trace
+// (for a MeanJob the item is a reduction, and bag_mean_combine_kernel above follows the passes).  PASS_ALL and
 // PASS_DEV: the grid is job.items, workgroup w runs item w.  PASS_HOST: any grid, the workgroups share the items out by grid stride.
 template <class T, bool VEC, int PASS, class Job>
 __global__ __launch_bounds__(BS_THREADS) void bag_gather_kernel(Store st, Draw dr, Job job) {
@@ -466,7 +620,8 @@ int check_tiers(const void* store, const void* store_host, int dtype, int64_t ro
 }
 
 // The sizes and the output side of a call as its entry point received them, before anything is narrowed to int.  A dense gather
-// (S1, S3) states N and brings no table; a pack (S2, S4) states n_chunks and T_out and brings cu, chunk_cu and row_bag.
+// (S1, S3) states N and brings no table; a pack (S2, S4) states n_chunks and T_out and brings cu, chunk_cu and row_bag.  A mean (S5)
+// is checked as a pack of no rows whose one table, chunk_cu, stands for both, and brings a workspace.
 struct Call {
     bool pack;
     int64_t R;
@@ -475,11 +630,12 @@ struct Call {
     const int64_t *cu, *chunk_cu;
     float* out;
     int32_t *row_bag, *idx_out;
+    const void* ws;                         // S5's partials, NULL for the gathers
 };
 
 inline bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
 
-// The refusals all four entry points share, in one order for all of them: NULL / range / dtype (MDL_E_ARG), then alignment
+// The refusals all entry points share, in one order for all of them: NULL / range / dtype (MDL_E_ARG), then alignment
 // (MDL_E_ALIGN), then the int32 launch geometry (MDL_E_UNSUPPORTED).  An optional pointer that is NULL is aligned.  Which of the store's
 // two bases may be NULL differs between the resident and the tiered forms and is the entry point's to say, before this.
 int check_call(const Store& st, const Draw& dr, const Call& c, int dtype) {
@@ -487,7 +643,7 @@ int check_call(const Store& st, const Draw& dr, const Call& c, int dtype) {
     if (c.pack ? (c.cu == nullptr || c.chunk_cu == nullptr || c.n_chunks < 0 || c.T_out < 0) : c.N < 1) return MDL_E_ARG;
     if (c.R < 0 || st.D < 1 || st.T_total < 0 || st.n_bags < 0 || st.row_stride < st.D) return MDL_E_ARG;
     if (dtype != MDL_STORE_F32 && dtype != MDL_STORE_F16 && dtype != MDL_STORE_BF16) return MDL_E_ARG;
-    if (!host_aligned16(st.dev) || !host_aligned16(st.host) || !host_aligned16(c.out)) return MDL_E_ALIGN;
+    if (!host_aligned16(st.dev) || !host_aligned16(st.host) || !host_aligned16(c.out) || !host_aligned16(c.ws)) return MDL_E_ALIGN;
     if (misaligned(st.off, 8) || misaligned(dr.key_id, 8) || misaligned(c.cu, 8) || misaligned(c.chunk_cu, 8)) return MDL_E_ALIGN;
     if (misaligned(dr.bag, 4) || misaligned(c.row_bag, 4) || misaligned(c.idx_out, 4)) return MDL_E_ALIGN;
     // the output rows are indexed in int32, and with them the items: a dense gather has R * ceil(N / 64) <= R * N of them
@@ -538,6 +694,13 @@ int launch(const Store& st, const Draw& dr, const Job& job, Passes passes, int d
 }
 
 inline int chunks_of(int N) { return (N + BS_TOK - 1) / BS_TOK; }
+
+// S5's second launch: one workgroup per output row, after the pass(es) that wrote the partials, on the same stream
+int mean_combine(const Store& st, const Draw& dr, const MeanJob& job, hipStream_t stream) {
+    hipLaunchKernelGGL(bag_mean_combine_kernel, dim3((unsigned)job.R), dim3(BS_THREADS), 0, stream, st, dr, job);
+    MDL_LAUNCH_CHECK();
+    return MDL_OK;
+}
 
 }  // namespace
 }  // namespace mdl
@@ -613,4 +776,45 @@ extern "C" int mdl_bag_pack_tiered(const void* store, const void* store_host, in
     rc = check_tiers(store, store_host, dtype, row_stride, T_total, T_dev, D, host_wgs, job.items, &st.host, &passes.host_wgs);
     if (rc != MDL_OK) return rc;
     return launch(st, dr, job, passes, dtype, (hipStream_t)stream);
+}
+
+// S5: the partial sums go through the same steps with a MeanJob, then the combine kernel is launched on the same stream.
+extern "C" int64_t mdl_bag_mean_ws_bytes(int64_t n_chunks, int D) {
+    if (n_chunks < 0 || D < 1) return MDL_E_ARG;
+    if (n_chunks > 0x7FFFFFFF) return MDL_E_UNSUPPORTED;
+    return n_chunks * (int64_t)D * (int64_t)sizeof(float);
+}
+
+extern "C" int mdl_bag_mean(const void* store, int dtype, int64_t row_stride, int64_t T_total, const int64_t* off, int64_t n_bags,
+                            const int32_t* bag, const int64_t* chunk_cu, int64_t R, int64_t n_chunks, int D, float* out, void* ws,
+                            void* stream) {
+    const Store st = {store, nullptr, T_total, row_stride, T_total, off, n_bags, D};
+    const Draw dr = {bag, nullptr, 0, 0};
+    const Call call = {true, R, 0, n_chunks, 0, chunk_cu, chunk_cu, out, nullptr, nullptr, ws};
+    if (store == nullptr || ws == nullptr) return MDL_E_ARG;
+    int rc = check_call(st, dr, call, dtype);
+    if (rc != MDL_OK) return rc;
+    if (R == 0 || n_chunks == 0) return MDL_OK;
+    const MeanJob job = {chunk_cu, (int)R, n_chunks, static_cast<float*>(ws), out};
+    rc = launch(st, dr, job, Passes{false, 0}, dtype, (hipStream_t)stream);
+    return rc != MDL_OK ? rc : mean_combine(st, dr, job, (hipStream_t)stream);
+}
+
+extern "C" int mdl_bag_mean_tiered(const void* store, const void* store_host, int dtype, int64_t row_stride, int64_t T_total, int64_t T_dev,
+                                   const int64_t* off, int64_t n_bags, const int32_t* bag, const int64_t* chunk_cu, int64_t R,
+                                   int64_t n_chunks, int D, float* out, void* ws, int host_wgs, void* stream) {
+    Store st = {store, store_host, T_dev, row_stride, T_total, off, n_bags, D};
+    const Draw dr = {bag, nullptr, 0, 0};
+    const Call call = {true, R, 0, n_chunks, 0, chunk_cu, chunk_cu, out, nullptr, nullptr, ws};
+    if (T_dev < 0 || T_dev > T_total || host_wgs < 0 || ws == nullptr) return MDL_E_ARG;
+    if ((T_dev > 0 && store == nullptr) || (T_dev < T_total && store_host == nullptr)) return MDL_E_ARG;      // a tier of no rows has no base
+    int rc = check_call(st, dr, call, dtype);
+    if (rc != MDL_OK) return rc;
+    if (R == 0 || n_chunks == 0) return MDL_OK;
+    const MeanJob job = {chunk_cu, (int)R, n_chunks, static_cast<float*>(ws), out};
+    Passes passes = {true, 0};
+    rc = check_tiers(store, store_host, dtype, row_stride, T_total, T_dev, D, host_wgs, job.items, &st.host, &passes.host_wgs);
+    if (rc != MDL_OK) return rc;
+    rc = launch(st, dr, job, passes, dtype, (hipStream_t)stream);
+    return rc != MDL_OK ? rc : mean_combine(st, dr, job, (hipStream_t)stream);
 }

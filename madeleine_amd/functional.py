@@ -1836,6 +1836,64 @@ def bag_pack_tiered(store_rows, host_rows, off, bag, key_id, cu, chunk_cu, n_row
     return (out, row_bag, idx) if return_indices else (out, row_bag)
 
 
+# ---- S5: the column means of whole stored bags (mdl_bag_mean / mdl_bag_mean_tiered) ----
+BAG_MEAN_ROWS = _native._DEFINES["MDL_BAG_MEAN_ROWS"]
+
+
+def _require_mean_tables(bag, chunk_cu, n_chunks, fn):
+    """The chunk table of a mean: chunk_cu int64 [R + 1] and its last entry n_chunks as the caller `fn` passed it."""
+    _require(chunk_cu, "chunk_cu", torch.int64)
+    if chunk_cu.numel() != bag.numel() + 1:
+        raise RuntimeError("madeleine_amd: chunk_cu must be [R + 1] = [%d]" % (bag.numel() + 1))
+    if n_chunks < 0:
+        raise RuntimeError("madeleine_amd: %s needs n_chunks >= 0" % fn)
+
+
+def _mean_outputs(R, D, n_chunks, device):
+    """out [R, D] fp32 and the workspace of the partials (None when nothing is launched: out is then the zeros of absent stains)"""
+    if R == 0 or n_chunks == 0:
+        return torch.zeros(R, D, device=device, dtype=torch.float32), None
+    ws = _ws_for("mdl_bag_mean_ws_bytes", device, int(n_chunks), D,
+                 refusal=("bag_mean: %d chunks exceed the int32 launch geometry", int(n_chunks)))
+    return torch.empty(R, D, device=device, dtype=torch.float32), ws
+
+
+def bag_mean(store_rows, off, bag, chunk_cu, n_chunks):
+    """out [R, D] fp32 <- out[r] is the mean over all rows of stored bag bag[r] (rows off[bag[r]] .. off[bag[r] + 1] - 1 of store_rows
+    [T, D], fp32 / fp16 / bf16, unit column stride), zeros where bag[r] == -1.  chunk_cu int64 [R + 1] on the device: the prefix sum of
+    ceil(n_r / BAG_MEAN_ROWS), n_r the rows of bag[r] (0 for -1); n_chunks = chunk_cu[R] as a host integer.  The bits of out[r] depend
+    on the bag's rows alone (include/madeleine_amd.h, S5).  Two launches on the current stream, no autograd, no host read, no allocation
+    beyond out and the workspace of the partials (n_chunks * D floats)."""
+    _require_store(store_rows)
+    _require_draw_tables(off, bag, None, "row")
+    _require_mean_tables(bag, chunk_cu, n_chunks, "bag_mean")
+    R, D = bag.numel(), store_rows.shape[1]
+    out, ws = _mean_outputs(R, D, n_chunks, store_rows.device)
+    if ws is None:
+        return out
+    with _timed("bag_mean"):       # (the bytes read are the listed bags' rows, which only the caller's host tables know)
+        _call("mdl_bag_mean", store_rows, STORE_DTYPES[store_rows.dtype], store_rows.stride(0) if store_rows.shape[0] > 1 else D,
+              store_rows.shape[0], off, off.numel() - 1, bag, chunk_cu, R, int(n_chunks), D, out, ws, _stream(),
+              unsupported=("bag_mean: %d bags in %d chunks exceed the int32 launch geometry", R, int(n_chunks)))
+    return out
+
+
+def bag_mean_tiered(store_rows, host_rows, off, bag, chunk_cu, n_chunks, host_wgs=0):
+    """bag_mean over the two-tier store of bag_sample_tiered: the same output, bit for bit, as bag_mean on the concatenation."""
+    host_rows, D, stride, T_dev, T_total = _require_tiers(store_rows, host_rows)
+    _require_draw_tables(off, bag, None, "row")
+    _require_mean_tables(bag, chunk_cu, n_chunks, "bag_mean_tiered")
+    R = bag.numel()
+    out, ws = _mean_outputs(R, D, n_chunks, store_rows.device)
+    if ws is None:
+        return out
+    with _timed("bag_mean"):
+        _call("mdl_bag_mean_tiered", store_rows if T_dev else None, host_rows, STORE_DTYPES[store_rows.dtype], stride, T_total, T_dev, off,
+              off.numel() - 1, bag, chunk_cu, R, int(n_chunks), D, out, ws, int(host_wgs), _stream(),
+              unsupported=("bag_mean_tiered: %d bags in %d chunks exceed the int32 launch geometry", R, int(n_chunks)))
+    return out
+
+
 # ---- P1-P3: the few-shot linear probe (mdl_probe_fit / mdl_probe_scores / mdl_probe_metrics).  No autograd: embeddings are inputs ----
 _PROBE_LIMITS = "linear probe supports at most %d training cases per problem, 2..%d classes and %d cases (got n_max %d, C %d, S %d)"
 

@@ -512,17 +512,40 @@ class MADELEINE(nn.Module):
         of the path is row-local and the pooling merges a bag's 128-token chunks in bag order, so each row equals encode_he of that bag
         alone BIT FOR BIT as long as every bag is on the same kernel path alone as in the pack (more than 256 patches: the large-M
         engines; run_inference sends smaller bags one by one).  For the extraction loop (utils.run_inference): one bag per call leaves a
-        30,000-patch bag on 235 pooling workgroups and the host bound by ~40 launches per bag."""
-        emb = self.wsi_embedders
-        if emb.attn[0].activation != 'softmax' or len(bags) == 1:     # (the ragged pooling kernels serve the softmax activation)
-            return torch.cat([self.encode_he(b.reshape(1, -1, b.shape[-1]), device) for b in bags])
+        30,000-patch bag on 235 pooling workgroups and the host bound by ~40 launches per bag.  This is the torch.cat of the bags and
+        the upload of cu_seqlens, then encode_packed."""
         flat = [b.reshape(-1, b.shape[-1]) for b in bags]
-        lens = [int(x.shape[0]) for x in flat]
-        cu = torch.zeros(len(flat) + 1, dtype=torch.int64)
-        cu[1:] = torch.cumsum(torch.tensor(lens, dtype=torch.int64), 0)
-        x = torch.cat([f.to(device) for f in flat], dim=0)
-        E, e_img = emb.embed_tokens_headmajor(x, return_image=True, want_fp32=False)
-        pooled, _ = emb.pool_headmajor_ragged(E, MF.h2d(cu, device), max(lens), e_img=e_img)
+        lens = tuple(int(x.shape[0]) for x in flat)
+        x = flat[0].to(device) if len(flat) == 1 else torch.cat([f.to(device) for f in flat], dim=0)
+        cu_d = None
+        if not self._encodes_bag_by_bag(len(lens)):
+            cu = torch.zeros(len(lens) + 1, dtype=torch.int64)
+            cu[1:] = torch.cumsum(torch.tensor(lens, dtype=torch.int64), 0)
+            cu_d = MF.h2d(cu, device)
+        return self.encode_packed((x, cu_d, lens), device)
+
+    def _encodes_bag_by_bag(self, n_bags):
+        """encode_packed's per-bag route: the ragged pooling kernels serve the softmax activation, and one bag is encode_he's own case."""
+        return self.wsi_embedders.attn[0].activation != 'softmax' or n_bags == 1
+
+    def encode_packed(self, packed, device):
+        """encode_he_bags for tokens that are ALREADY packed: `packed` is a PackedBags (DeviceSlideStore.pack_modality) or (tokens
+        [sum N_i, D], cu_seqlens [R + 1] int64 on the device, the host tuple of the R lengths) -> [R, 512].  The kernels and their order
+        are encode_he_bags', without the torch.cat and without an upload: nothing is built on the host.  One bag, and the non-softmax
+        activations, go bag by bag through encode_he on slices of the tokens (cu_seqlens is then not read and may be None)."""
+        tokens, cu_d, lens = (packed.tokens, packed.cu_seqlens, packed.lens) if hasattr(packed, "tokens") else packed
+        lens = [int(n) for n in lens]
+        if tokens.dim() != 2 or not lens or min(lens) < 1 or tokens.shape[0] != sum(lens):
+            raise ValueError("encode_packed needs tokens [sum(lens), D] and at least one bag, every bag of at least one row")
+        tokens = tokens.to(device)
+        if self._encodes_bag_by_bag(len(lens)):
+            ends = np.cumsum(lens).tolist()
+            return torch.cat([self.encode_he(tokens[e - n:e].unsqueeze(0), device) for n, e in zip(lens, ends)])
+        if cu_d is None or cu_d.numel() != len(lens) + 1:
+            raise ValueError("encode_packed needs cu_seqlens [len(lens) + 1] on the device")
+        emb = self.wsi_embedders
+        E, e_img = emb.embed_tokens_headmajor(tokens, return_image=True, want_fp32=False)
+        pooled, _ = emb.pool_headmajor_ragged(E, cu_d.to(device), max(lens), e_img=e_img)
         return self._project_slide(pooled)
 
     def forward_ragged(self, bags, device, n_loss_tokens=None, n_views=1, modality_labels=None):

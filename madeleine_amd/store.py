@@ -2,7 +2,9 @@
 `[B, M, N, D]` batch drawn from it on the device by one kernel (functional.bag_sample -> mdl_bag_sample, csrc/bag_sample.hip).
 Ragged batches -- every bag at its own length, optionally cut to max_tokens rows drawn without replacement -- come packed out of the
 same store by one launch of its variable-length form (pack / packed_batches: functional.bag_pack -> mdl_bag_pack), from a store of
-any dtype.
+any dtype.  One vector per slide comes out of it too, for a downstream cohort: embed() runs the encoder over single-stain packs
+(pack_modality -> MADELEINE.encode_packed) and mean_embeddings() reduces whole bags to their column means where they lie
+(functional.bag_mean -> mdl_bag_mean); both feed probe.linear_probe without the features leaving the device.
 
 Replaces, for a cohort that fits in HBM, the reference's input side (madeleine/datasets/wsi_dataset.py): SlideDataset.__getitem__
 re-reads every stain's h5 file for every item of every epoch, draws `sample` rows on the host and collate stacks them, and the stacked
@@ -35,6 +37,7 @@ from . import functional as MF
 FP16_MAX = 65504.0
 _MAX_BAG_ROWS = 2 ** 31 - 1
 ABSENT_BAG_ROWS = 2        # the dataset's zero bag of an absent stain (wsi_dataset.py:66)
+MEAN_WS_BYTES = 64 << 20   # mean_embeddings: the partial sums of one slice of cases stay inside this
 
 
 class PackedBags(NamedTuple):
@@ -272,6 +275,11 @@ class DeviceSlideStore:
             raise RuntimeError("DeviceSlideStore.pack: the store lives on %s; the HIP kernel is the only backend (no CPU fallback)"
                                % self.device)
         bag, lens = self._pack_plan(case_indices, max_tokens)
+        return self._pack_bags(bag, lens, counter, seed, return_indices, host_wgs)
+
+    def _pack_bags(self, bag, lens, counter, seed, return_indices, host_wgs) -> PackedBags:
+        """The pack of stored bags `bag` [R] int32 (-1: zeros) at `lens` [R] int64 rows each, both on the host: the launch's tables, their
+        one upload and the launch.  What pack() and pack_modality() share."""
         R = bag.numel()
         host = torch.zeros(2 * (R + 1) + (R + 1) // 2, dtype=torch.int64)        # cu | chunk_cu | bag (int32, two to a word)
         torch.cumsum(lens, 0, out=host[1:R + 1])
@@ -288,6 +296,132 @@ class DeviceSlideStore:
                                      table[R + 1:2 * R + 2], T, n_chunks, 0 if seed is None else seed, counter, return_indices,
                                      host_wgs=host_wgs)
         return PackedBags(res[0], cu, tuple(lens.tolist()), res[1], res[2] if return_indices else None)
+
+    def _modality_plan(self, case_indices, modality, max_tokens=None):
+        """(cases [n] int64, bag [n] int32, lens [n] int64) of one stain's bags, on the host: the cases asked for in the order asked, or
+        -- case_indices None -- every case that has the stain, in case order; lens are the bags' rows, at most max_tokens of them.
+        IndexError for a modality outside [0, M) or a case outside the store, ValueError naming the first case asked for that lacks
+        the stain."""
+        M = len(self.modalities)
+        if isinstance(modality, bool) or not isinstance(modality, int) or not 0 <= modality < M:
+            raise IndexError("DeviceSlideStore: modality must be an integer in [0, %d) (got %r)" % (M, modality))
+        if max_tokens is not None and max_tokens < 1:
+            raise ValueError("DeviceSlideStore: max_tokens must be at least 1 (got %s)" % max_tokens)
+        col = self.bag_table[:, modality]
+        if case_indices is None:
+            cases = (col >= 0).nonzero().reshape(-1)
+        else:
+            cases = self._cases(case_indices)
+        bag = col.index_select(0, cases)
+        if bool((bag < 0).any()):
+            c = int(cases[int((bag < 0).nonzero()[0])])
+            raise ValueError("DeviceSlideStore: case %d (%s) has no %s bag" % (c, self.slide_ids[c], self.modalities[modality]))
+        lens = self.bag_lens_cpu.index_select(0, bag.long())
+        if max_tokens is not None:
+            lens = lens.clamp(max=int(max_tokens))
+        return cases, bag, lens
+
+    def _require_device(self, what):
+        if self.device.type != "cuda":
+            raise RuntimeError("DeviceSlideStore.%s: the store lives on %s; the HIP kernel is the only backend (no CPU fallback)"
+                               % (what, self.device))
+
+    def pack_modality(self, case_indices, modality, max_tokens=None, counter=0, seed=None, host_wgs=0) -> PackedBags:
+        """pack() for ONE stain: bag r of the result is the `modality` bag of case case_indices[r], whole and in stored order or cut to
+        max_tokens rows by pack()'s draw (a bag's draw is a function of seed, counter and its stored bag id, so these are the rows
+        pack() and sample() draw for it).  ValueError naming the case when a case lacks the stain (there is no zero bag here: a slide
+        that does not exist has no embedding), IndexError for a modality outside [0, M)."""
+        self._require_device("pack_modality")
+        _, bag, lens = self._modality_plan(case_indices, modality, max_tokens)
+        return self._pack_bags(bag, lens, counter, seed, False, host_wgs)
+
+    def _embedding_result(self, embeds, cases):
+        return {"embeds": embeds, "cases": cases, "slide_ids": [self.slide_ids[c] for c in cases.tolist()]}
+
+    def mean_embeddings(self, modality=0, case_indices=None, host_wgs=0) -> dict:
+        """The mean patch embedding of one stain's bag of every case asked for (None: every case that has the stain): {"embeds" [n, D]
+        fp32 on the device, "cases" [n] int64 on the host, "slide_ids"} -- bin/extract_mean_embs.py for a cohort in the store, the
+        baseline of the linear probe.  Whole bags, read where they lie (both tiers, any store dtype) by functional.bag_mean; the bits
+        of a row depend on that bag alone.  One O(n) upload per call (the bags and the chunk tables); the work goes in slices of cases
+        whose partial sums stay inside MEAN_WS_BYTES (a bag whose own partials exceed it goes alone).  ValueError / IndexError as
+        pack_modality; host_wgs as in sample()."""
+        self._require_device("mean_embeddings")
+        cases, bag, lens = self._modality_plan(case_indices, modality)
+        n, D = bag.numel(), self.dim
+        if n == 0:
+            return self._embedding_result(torch.zeros(0, D, dtype=torch.float32, device=self.device), cases)
+        chunks = (lens + (MF.BAG_MEAN_ROWS - 1)) // MF.BAG_MEAN_ROWS
+        budget = max(1, MEAN_WS_BYTES // (4 * D))                # chunks per slice
+        cuts, used = [0], 0
+        for i, c in enumerate(chunks.tolist()):
+            if used and used + c > budget:
+                cuts.append(i)
+                used = 0
+            used += c
+        cuts.append(n)
+        k = len(cuts) - 1
+        host = torch.zeros(n + k + (n + 1) // 2, dtype=torch.int64)      # per slice chunk_cu [R_s + 1] | bag (int32, two to a word)
+        for j in range(k):
+            a, b = cuts[j], cuts[j + 1]
+            torch.cumsum(chunks[a:b], 0, out=host[a + j + 1:b + j + 1])
+        host[n + k:].view(torch.int32)[:n] = bag
+        totals = [int(host[cuts[j + 1] + j]) for j in range(k)]
+        table = MF.h2d(host, self.device)
+        bag_d = table[n + k:].view(torch.int32)[:n]
+        outs = []
+        for j in range(k):
+            a, b = cuts[j], cuts[j + 1]
+            if self.rows_host is None:
+                outs.append(MF.bag_mean(self.rows, self.off, bag_d[a:b], table[a + j:b + j + 1], totals[j]))
+            else:
+                outs.append(MF.bag_mean_tiered(self.rows, self.rows_host, self.off, bag_d[a:b], table[a + j:b + j + 1], totals[j],
+                                               host_wgs=host_wgs))
+        return self._embedding_result(outs[0] if k == 1 else torch.cat(outs), cases)
+
+    def embed(self, model, modality=0, case_indices=None, bags_per_launch=None, max_tokens=None, precision=None, host_wgs=0) -> dict:
+        """The slide embedding of one stain's bag of every case asked for (None: every case that has the stain), from `model`'s H&E
+        encoder: {"embeds" [n, 512] fp32 on the device, "cases", "slide_ids"} -- utils.run_inference for a cohort in the store, without
+        a dataloader, an h5 read or a host-to-device copy of features.  Eval mode under torch.no_grad() (the model's training flag is
+        restored), under autocast when precision is bfloat16 / float16.  Grouping is run_inference's: up to bags_per_launch bags per
+        launch set (None: 4 in fp32, 1 under autocast, for the reason its docstring gives), a bag of at most 256 rows alone; each
+        group is pack_modality -> model.encode_packed, and every embedding equals model.encode_he of that bag alone bit for bit in
+        fp32.  The embeddings stay on the device and the loop reads nothing back.  max_tokens, counter 0: pack_modality's cut.  A
+        model with stain encoding takes modality 0 only (encode_he is the H&E path)."""
+        self._require_device("embed")
+        if getattr(model, "stain_encoding", False) and modality != 0:
+            raise ValueError("DeviceSlideStore.embed: a model with stain encoding embeds modality 0 only (encode_he is the H&E path; "
+                             "got modality %r)" % (modality,))
+        cases, _, lens = self._modality_plan(case_indices, modality, max_tokens)
+        reduced = precision in (torch.bfloat16, torch.float16)
+        if bags_per_launch is None:
+            bags_per_launch = 1 if reduced else 4
+        groups, pending = [], []
+        for c, n_rows in zip(cases.tolist(), lens.tolist()):
+            if bags_per_launch <= 1 or n_rows <= 256:
+                if pending:
+                    groups.append(pending)
+                groups.append([c])
+                pending = []
+                continue
+            pending.append(c)
+            if len(pending) >= bags_per_launch:
+                groups.append(pending)
+                pending = []
+        if pending:
+            groups.append(pending)
+        was_training = model.training
+        model.eval()
+        outs = []
+        try:
+            with torch.no_grad():
+                for group in groups:
+                    packed = self.pack_modality(group, modality, max_tokens, host_wgs=host_wgs)
+                    with torch.autocast(device_type="cuda", dtype=precision if reduced else None, enabled=reduced):
+                        outs.append(model.encode_packed(packed, self.device).float())
+        finally:
+            model.train(was_training)
+        embeds = torch.cat(outs) if outs else torch.zeros(0, 512, dtype=torch.float32, device=self.device)
+        return self._embedding_result(embeds, cases)
 
     def packed_batches(self, batch_size, max_tokens=None, shuffle=True, drop_last=False, seed=0, rank=0, world_size=1, prefetch=None):
         """Re-iterable over {'packed': PackedBags, 'modality_labels', 'slide_ids'}: the ragged batches of ragged_batches() in packed

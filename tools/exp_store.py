@@ -36,9 +36,21 @@ batch to fetch), with device events after warm-up, medians (min-max), the legs a
      (d) a store with half its bytes resident, prefetch=1 -- alternating rounds; every round is one epoch whose first step is run
      untimed (it fills the prefetch queue) -- and (e) the `host` DataLoader feed in a phase of its own, next to (a) and (b).
 
+--embed measures the route from the store to one vector per slide, over --embed-cases H&E bags of --embed-rows rows x 512, with device
+events after warm-up, medians (min-max), the legs alternating inside one loop:
+  8. the mean kernel: functional.bag_mean of the whole cohort on prepared tables (its two launches, nothing else) from a resident fp32
+     and a resident bf16 store, as achieved bytes/s over the rows read (T * D * element size; the partial sums and the output are
+     0.1 % of that), next to DeviceSlideStore.sample of N = 4096 tokens per bag from the same store (bytes/s over its read + write
+     payload, as in 1.) and to the whole DeviceSlideStore.mean_embeddings call (plan, table upload and launches: the host's share
+     shows as the difference); tools/micro/hbm_rate gives the box's read ceiling for the contiguous pattern;
+  9. extraction: DeviceSlideStore.embed of the cohort (fp32 store, fp32 model, its default 4 bags per launch set) against
+     utils.run_inference over a DataLoader that hands over the same bags from host memory one at a time (pinned, no file is read: the
+     host path at its best), both in bags/s by the host clock around a device synchronise, alternating.
+
 Usage: python tools/exp_store.py [--rows 20000] [--launches 20] [--steps 20] [--round-steps 5] [--workers 6] [--out FILE]
        python tools/exp_store.py --pack [--launches 20] [--steps 12] [--round-steps 3] [--cap 4096] [--skip-step] [--out FILE]
-       python tools/exp_store.py --tier [--tier-cases 192] [--tier-rows 4096] [--launches 10] [--steps 20] [--round-steps 5] [--out FILE]"""
+       python tools/exp_store.py --tier [--tier-cases 192] [--tier-rows 4096] [--launches 10] [--steps 20] [--round-steps 5] [--out FILE]
+       python tools/exp_store.py --embed [--embed-cases 48] [--embed-rows 30000] [--launches 10] [--steps 4] [--out FILE]"""
 import argparse
 import json
 import os
@@ -416,6 +428,101 @@ def tier_leg(a, dev):
     return lines, res
 
 
+class HostBags(torch.utils.data.Dataset):
+    """What a DataLoader(SimpleDataset, batch_size=1) hands run_inference -- (feats [1, N, D], [slide id]) -- over bags held in host
+    memory: a view per item, nothing is read, parsed or stacked."""
+
+    def __init__(self, bags, ids):
+        self.bags, self.ids = bags, ids
+
+    def __len__(self):
+        return len(self.bags)
+
+    def __getitem__(self, i):
+        return self.bags[i][None], [self.ids[i]]
+
+
+def embed_leg(a, dev):
+    """Measurements 8-9 of the module docstring.  Returns (lines, results)."""
+    from madeleine_amd import utils as MU
+    n, rows, D, N = a.embed_cases, a.embed_rows, 512, 4096
+    g = torch.Generator().manual_seed(7)
+    base = torch.randn(rows + n, D, generator=g)
+    bags = [[base[c:c + rows]] for c in range(n)]        # overlapping windows of one tensor: distinct bags, one host allocation
+    ids = ["case%05d" % c for c in range(n)]
+    cases, T = list(range(n)), n * rows
+    lines, res = [], {"geometry": {"cases": n, "rows_per_bag": rows, "D": D, "sample_tokens": N}}
+
+    # ---- 8. the mean kernel
+    res["kernel"] = {}
+    for dtype in (torch.float32, torch.bfloat16):
+        st = DeviceSlideStore(bags, ids, ["HE"], dev, dtype=dtype)
+        esz = st.rows.element_size()
+        work = {"mean": T * D * esz, "mean_embeddings": T * D * esz, "sample": n * N * D * (4 + esz)}
+        chunks = torch.zeros(n + 1, dtype=torch.int64)
+        chunks[1:] = torch.cumsum((st.bag_lens_cpu + MF.BAG_MEAN_ROWS - 1) // MF.BAG_MEAN_ROWS, 0)
+        bag_d, chunk_cu, n_chunks = torch.arange(n, dtype=torch.int32).to(dev), chunks.to(dev), int(chunks[-1])
+        calls = {"mean": lambda i: MF.bag_mean(st.rows, st.off, bag_d, chunk_cu, n_chunks),
+                 "mean_embeddings": lambda i: st.mean_embeddings(0)["embeds"], "sample": lambda i: st.sample(cases, N, counter=i)}
+        for f in calls.values():
+            for i in range(3):
+                f(i)
+        times = {k: [] for k in calls}
+        for i in range(a.launches):
+            order = sorted(calls) if i % 2 == 0 else sorted(calls, reverse=True)
+            for _ in range(4):                           # untimed, ~0.6 ms of device work: the host runs ahead of the device, so the
+                del_me = calls["sample"](50 + i)         # first timed call of the sequence holds no launch gap
+                del del_me
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(order) + 1)]
+            ev[0].record()
+            for j, k in enumerate(order):
+                out = calls[k](100 + i)
+                ev[j + 1].record()
+                del out
+            ev[-1].synchronize()
+            for j, k in enumerate(order):
+                times[k].append(ev[j].elapsed_time(ev[j + 1]))
+        res["kernel"][str(dtype)] = {k: {"ms": stats(v), "payload_bytes": work[k], "TBps_median": work[k] / statistics.median(v) * 1e-9}
+                                     for k, v in times.items()}
+        for k, v in sorted(times.items()):
+            lines.append("%-15s %-14s median %.3f ms (min %.3f max %.3f) = %.2f TB/s over %.2f GB"
+                         % (k, str(dtype), statistics.median(v), min(v), max(v), work[k] / statistics.median(v) * 1e-9, work[k] * 1e-9))
+        if dtype != torch.float32:
+            del st
+        else:
+            st32 = st
+    st = st32
+
+    # ---- 9. extraction: store.embed against run_inference over a host dataloader of the same bags
+    if not a.skip_step:
+        torch.manual_seed(42)
+        model = MADELEINE(BN.make_cfg(2, D)).to(dev).eval()
+        pinned = [case[0].contiguous().pin_memory() for case in bags]
+        loader = torch.utils.data.DataLoader(HostBags(pinned, ids), batch_size=None, shuffle=False, num_workers=0)
+
+        def host_clock(f):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = f()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            del out
+            return t1 - t0
+        feeds = {"store_embed": lambda: st.embed(model), "run_inference": lambda: MU.run_inference(model, loader, torch_precision=torch.float32)}
+        for f in feeds.values():
+            f()
+        wall = {k: [] for k in feeds}
+        for r in range(max(1, a.steps)):
+            for k in (sorted(feeds) if r % 2 == 0 else sorted(feeds, reverse=True)):
+                wall[k].append(n / host_clock(feeds[k]))
+        res["extraction"] = {k: {"bags_per_s": stats(v)} for k, v in wall.items()}
+        res["extraction"]["note"] = "run_inference also copies the embeddings to the host and computes their smooth rank (one SVD of [n, 512])"
+        for k, v in sorted(wall.items()):
+            lines.append("%-13s median %.1f bags/s (min %.1f max %.1f) over %d bags of %d rows, fp32, 4 bags per launch set"
+                         % (k, statistics.median(v), min(v), max(v), n, rows))
+    return lines, res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=20000)
@@ -433,10 +540,13 @@ def main():
     ap.add_argument("--tier", action="store_true", help="measure the two-tier store (host tier read over PCIe) instead")
     ap.add_argument("--tier-cases", type=int, default=192, help="cases of the cohort of --tier: more than --round-steps batches per epoch")
     ap.add_argument("--tier-rows", type=int, default=4096, help="rows per bag of the cohort of --tier")
+    ap.add_argument("--embed", action="store_true", help="measure the mean kernel and store.embed against run_inference instead")
+    ap.add_argument("--embed-cases", type=int, default=48, help="H&E bags of the cohort of --embed")
+    ap.add_argument("--embed-rows", type=int, default=30000, help="rows per bag of the cohort of --embed")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    if a.pack or a.tier:
-        lines, res = (pack_leg if a.pack else tier_leg)(a, dev)
+    if a.pack or a.tier or a.embed:
+        lines, res = (pack_leg if a.pack else tier_leg if a.tier else embed_leg)(a, dev)
         report(lines, res, a.out)
         return
     B, M, N, D, _got, stain = BN.CONFIGS["c2"]
