@@ -12,6 +12,8 @@
 // One wave per row: lane L owns columns {4L + 256 i .. +3}, i < W/256 (W = 512 -> 2 float4, 2048 -> 8 float4), so
 // a row is W/256 coalesced 1 KiB loads, the mean/variance are two 64-lane reductions, and in backward the per-
 // column sums for d(gamma), d(beta) accumulate in registers across the rows a wave walks.
+#include <algorithm>
+
 #include "split_engine.hpp"
 
 namespace mdl {
@@ -190,11 +192,6 @@ __device__ __forceinline__ f32x4 act_keep4_t(const ActDrop& d, uint32_t row_key,
     }
     return f32x4{k[0], k[1], k[2], k[3]};
 }
-static inline int act_drop_mode(const ActDrop& d) { return !d.on ? 0 : (d.keep ? 2 : 1); }
-// the launchers' choice: compile-time mode for the (VALU-bound) bf16 kernels, the run-time form for fp32 storage (HBM-bound; measured
-// no gain there)
-template <class IO>
-static inline int ln_dm(const ActDrop& d) { return sizeof(IO) == 2 ? act_drop_mode(d) : -1; }
 __device__ __forceinline__ uint32_t act_row_key(const ActDrop& d, int64_t row_base) {
     return d.key ^ ((uint32_t)((uint64_t)row_base >> 32) * 0x9E3779B9U);
 }
@@ -288,30 +285,76 @@ __device__ __forceinline__ ActRange act_range(int64_t lo, int64_t hi, int RPB) {
 #endif
 }
 
+// ---- what a call is: a few records, passed to the kernels by value and filled by the entry points ----
+template <class IO>
+struct LnFwd {   // the tensor, forward: y may be NULL when only the image is wanted
+    const IO* x;
+    IO* y;
+    int64_t rows;
+};
+template <class IO>
+struct LnBwd {   // the tensor, backward; part: the workgroups' partial column sums [slot][dgamma W | dbeta W | dbias W]
+    const IO* x;
+    const IO* dy;
+    IO* dx;
+    float* part;
+    int64_t rows;
+};
+struct LnParams {   // bias: of the preceding Linear (or NULL), added here instead of in the GEMM epilogue
+    const float* bias;
+    int bias_gstride;   // grouped: group g's bias row is bias + g * bias_gstride (bf16 / exact-fp32 engines); 0: bias is common (the
+                        // split engine's GEMM epilogue has added the group rows to x)
+    const float *gamma, *beta;
+    float eps;
+};
+template <class F>
+struct LnStats {   // F = float: the forward writes them; const float: the backward reads them
+    F *mean, *rstd;
+};
+// The split-image side (img NULL: none).  Forward: the output as an image, rows of 4 W bytes, under the scale sc[0].  Backward: dx as such
+// an image.  row_mul (or NULL): a factor per row -- the backward's image row r is scaled by sc[0] * row_mul[r], where row_mul[r] = 1 / s_r
+// of the row-scaled image of this layer's input it pairs with in the dW contraction over rows, so that the row factors cancel in the sum.
+// rstd_max (or NULL): the forward raises it to max_r rstd[r] * row_mul[r] -- the factor of the backward's dx-image bound, taken where the
+// statistics are computed instead of by a pass over rstd in every backward; the backward's launcher reads it (F as in LnStats).
+template <class F>
+struct LnImage {
+    char* img;
+    float* sc;
+    const float* row_mul;
+    F* rstd_max;
+};
+// Groups of rows (cu NULL: none): rows [cu[g], cu[g + 1]) of group g = blockIdx.y, each with its own bias row and, in backward, its own
+// partial slots (blockIdx.y * gridDim.x + blockIdx.x): the dbias third of them is the gradient of that group's bias row.  The stain-
+// encoding columns of the first Linear folded into a per-bag bias (Model.py:125-132, :351).  G is the launchers'.
+struct LnGroups {
+    const int64_t* cu;
+    int G;
+};
+// rows [lo, hi) and the bias row of this workgroup: the one place that reads LnGroups
+struct LnSpan {
+    int64_t lo, hi;
+    const float* bias;
+};
+__device__ __forceinline__ LnSpan ln_span(const LnGroups& gr, const LnParams& p, int64_t rows) {
+    if (!gr.cu) return {0, rows, p.bias};
+    return {gr.cu[blockIdx.y], gr.cu[blockIdx.y + 1], p.bias ? p.bias + (int64_t)blockIdx.y * p.bias_gstride : nullptr};
+}
+// the image scale: a scalar load through the constant address space (a record cannot say __restrict__; the launch before wrote it)
+__device__ __forceinline__ float ln_img_scale(const float* sc) { return ((const __attribute__((address_space(4))) float*)sc)[0]; }
+
 // IMG: 0 = y only; 1 = split image only (the output feeds contractions of the split engine only); 2 = both (fp32 kernels only)
-template <int NV, int WPR, class IO, int IMG = 0, int DM = -1>
-__global__ __launch_bounds__(ACT_BLOCK) void ln_gelu_drop_fwd_kernel(const IO* __restrict__ x,
-                                                                     const float* __restrict__ bias,
-                                                                     const float* __restrict__ gamma,
-                                                                     const float* __restrict__ beta,
-                                                                     IO* __restrict__ y, float* __restrict__ mean_o,
-                                                                     float* __restrict__ rstd_o, int64_t rows, float eps,
-                                                                     ActDrop drop, char* __restrict__ img = nullptr,
-                                                                     const float* __restrict__ img_sc = nullptr,
-                                                                     const float* __restrict__ row_mul = nullptr,
-                                                                     float* __restrict__ rstd_max = nullptr,
-                                                                     const int64_t* __restrict__ cu = nullptr, int bias_gstride = 0) {
-    // rstd_max (split variant): raised to max_r rstd[r] * row_mul[r] -- the factor of the backward's dx-image bound, taken here where the
-    // statistics are computed instead of by a pass over rstd in every backward (one atomic per wave)
-    // cu (grouped forward, round 6): rows [cu[g], cu[g + 1]) of group g = blockIdx.y, whose bias row is bias + g * bias_gstride -- the
-    // stain-encoding columns of the first Linear folded into a per-bag bias (Model.py:125-132, :351) for the engines whose GEMM epilogue
-    // does not add it (bf16, exact fp32)
+template <int NV, int WPR, class IO, int IMG, int DM>
+__global__ __launch_bounds__(ACT_BLOCK) void ln_gelu_drop_fwd_kernel(const LnFwd<IO> t, const LnParams p, const LnStats<float> st,
+                                                                     const LnImage<float> im, const LnGroups gr, const ActDrop drop) {
     constexpr int W = NV * 256 * WPR, RPB = 4 / WPR;
-    const int64_t row_lo = cu ? cu[blockIdx.y] : 0;
-    if (cu) {
-        rows = cu[blockIdx.y + 1];
-        if (bias) bias += (int64_t)blockIdx.y * bias_gstride;
-    }
+    const LnSpan sp = ln_span(gr, p, t.rows);
+    const int64_t row_lo = sp.lo, rows = sp.hi;
+    const IO* x = t.x;
+    IO* y = t.y;
+    const float *bias = sp.bias, *gamma = p.gamma, *beta = p.beta, *row_mul = im.row_mul;
+    float *mean_o = st.mean, *rstd_o = st.rstd, *rstd_max = im.rstd_max;
+    char* img = im.img;
+    const float eps = p.eps;
     __shared__ float red[1][4][2];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, slot = wv / WPR, seg = wv % WPR;
     typedef ColMap<IO, NV> CM;
@@ -373,7 +416,7 @@ __global__ __launch_bounds__(ACT_BLOCK) void ln_gelu_drop_fwd_kernel(const IO* _
                 const f32x4 t = (v[i] - mean) * rstd * g[i] + b[i];
                 const f32x4 o = act_gelu4<IO>(t) * kp;
                 if (IMG != 1) group_store<IO, NV>(yr, lane, i, prev, o);
-                if (IMG != 0) img_store4(img + r * (int64_t)(W * 4), ci, o, img_sc[0]);
+                if (IMG != 0) img_store4(img + r * (int64_t)(W * 4), ci, o, ln_img_scale(im.sc));
                 prev = o;
             }
             if (lane == 0 && seg == 0) {
@@ -394,26 +437,19 @@ __global__ __launch_bounds__(ACT_BLOCK) void ln_gelu_drop_fwd_kernel(const IO* _
     }
 }
 
-// IMG: dx is written as a split image (rows of 4 W bytes at `img`, scale img_sc[0]) instead of dx
-template <int NV, int WPR, class IO, bool IMG = false, int DM = -1>
-__global__ __launch_bounds__(ACT_BLOCK) void ln_gelu_drop_bwd_kernel(const IO* __restrict__ x,
-                                                                     const float* __restrict__ bias,
-                                                                     const float* __restrict__ gamma,
-                                                                     const float* __restrict__ beta,
-                                                                     const float* __restrict__ mean_i,
-                                                                     const float* __restrict__ rstd_i,
-                                                                     const IO* __restrict__ dy, IO* __restrict__ dx,
-                                                                     float* __restrict__ part, int64_t rows_all, ActDrop drop,
-                                                                     char* __restrict__ img = nullptr,
-                                                                     const float* __restrict__ img_sc = nullptr,
-                                                                     const float* __restrict__ row_mul = nullptr,
-                                                                     const int64_t* __restrict__ cu = nullptr, int bias_gstride = 0) {
-    // cu (grouped backward, round 5): rows [cu[g], cu[g + 1]) of group g = blockIdx.y are this workgroup's; its partial column sums
-    // (slot blockIdx.y * gridDim.x + blockIdx.x) then belong to ONE group: the dbias third of them is the gradient of that group's bias row
-    // bias_gstride != 0 (round 6): x does NOT hold the group's bias row yet (bf16 / exact-fp32 engines): it is bias + g * bias_gstride
+// IMG: dx is written as a split image (LnImage) instead of dx
+template <int NV, int WPR, class IO, bool IMG, int DM>
+__global__ __launch_bounds__(ACT_BLOCK) void ln_gelu_drop_bwd_kernel(const LnBwd<IO> t, const LnParams p, const LnStats<const float> st,
+                                                                     const LnImage<const float> im, const LnGroups gr, const ActDrop drop) {
     constexpr int W = NV * 256 * WPR, RPB = 4 / WPR;
-    const int64_t row_lo = cu ? cu[blockIdx.y] : 0, rows = cu ? cu[blockIdx.y + 1] : rows_all;
-    if (cu && bias) bias += (int64_t)blockIdx.y * bias_gstride;
+    const LnSpan sp = ln_span(gr, p, t.rows);
+    const int64_t row_lo = sp.lo, rows = sp.hi;
+    const IO *x = t.x, *dy = t.dy;
+    IO* dx = t.dx;
+    const float *bias = sp.bias, *gamma = p.gamma, *beta = p.beta, *row_mul = im.row_mul;
+    const float *mean_i = st.mean, *rstd_i = st.rstd;
+    float* part = t.part;
+    char* img = im.img;
     __shared__ float red[1][4][2];
     __shared__ float csum[WPR < 4 ? 3 * W : 1];  // WPR < 4: several waves own the same columns -> merged through LDS
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, slot = wv / WPR, seg = wv % WPR;
@@ -489,9 +525,8 @@ __global__ __launch_bounds__(ACT_BLOCK) void ln_gelu_drop_bwd_kernel(const IO* _
         if (live) {
             IO* __restrict__ o = dx + r * W + cb;
             f32x4 prev = {0.f, 0.f, 0.f, 0.f};
-            // image row factor: the common scale, times row_mul[r] when the image pairs (in the dW contraction over rows) with a
-            // row-scaled image of this layer's input -- row_mul[r] = that image's 1 / s_r, so that the row factors cancel in the sum
-            const float isc = IMG ? (row_mul ? img_sc[0] * row_mul[r] : img_sc[0]) : 0.f;
+            // image row factor: the common scale, times row_mul[r] (LnImage)
+            const float isc = IMG ? (row_mul ? ln_img_scale(im.sc) * row_mul[r] : ln_img_scale(im.sc)) : 0.f;
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 f32x4 v;
@@ -576,9 +611,8 @@ __global__ __launch_bounds__(256) void ln_reduce_kernel(const float* __restrict_
 // sc[0] = scale, sc[1] = the bound.  aux[0] = max rstd, aux[1] = max |dy| (backward only).
 __global__ __launch_bounds__(256) void ln_bound_scale_kernel(const float* __restrict__ gamma, const float* __restrict__ beta, int W,
                                                              float inv_keep, const float* __restrict__ aux, float* __restrict__ sc,
-                                                             float* __restrict__ zero_me = nullptr,
-                                                             const float* __restrict__ aux1 = nullptr) {
-    // zero_me: a float this launch clears (the forward's rstd_max accumulator); aux1: max |dy| when it does not lie at aux[1]
+                                                             float* __restrict__ zero_me, const float* __restrict__ aux1) {
+    // zero_me (or NULL): a float this launch clears (the forward's rstd_max accumulator); aux1 (or NULL): max |dy| when it does not lie at aux[1]
     if (zero_me && threadIdx.x == 0) *zero_me = 0.f;
     __shared__ float red[2][4];
     float g = 0.f, b = 0.f;
@@ -614,6 +648,7 @@ __global__ __launch_bounds__(256) void absmax_prod_kernel(const float* __restric
 int sp_launch_absmax(const float* X, int64_t ldx, int64_t rows, int K, float* out, hipStream_t s);   // split_gemm.hip
 int sp_launch_absmax_flat(const float* x, int64_t n, float* out, hipStream_t s);
 
+
 static inline ActDrop make_act_drop(float p, uint64_t seed, const uint8_t* keep) {
     ActDrop d;
     d.on = p > 0.f ? 1 : 0;
@@ -623,35 +658,171 @@ static inline ActDrop make_act_drop(float p, uint64_t seed, const uint8_t* keep)
     d.keep = keep;
     return d;
 }
-static inline bool act_width_ok(int W) { return W == 256 || W == 512 || W == 1024 || W == 2048 || W == 4096; }
-static inline int act_rpb(int W) { return W >= 2048 ? 1 : (W == 1024 ? 2 : 4); }  // rows per block iteration (= 4 / WPR)
-static inline int act_blocks(int64_t rows, int W) {
-    int64_t b = (rows + act_rpb(W) - 1) / act_rpb(W);
-    if (b > 2048) b = 2048;  // 256 CUs x 8 blocks; grid-stride over the rest
-    if (b < 1) b = 1;
-    return (int)b;
-}
 
-}  // namespace mdl
-
-using namespace mdl;
-
-extern "C" int64_t mdl_ln_gelu_drop_bwd_ws_bytes(int64_t rows, int W) {
-    if (rows < 0) return MDL_E_ARG;
-    if (!act_width_ok(W)) return MDL_E_UNSUPPORTED;   // 512 * n_heads for n_heads in {1, 2, 4, 8}, and 256
-    return (int64_t)act_blocks(rows, W) * 3 * W * 4 + 128;   // + aux floats of the split variant
-}
-
-#define MDL_DISPATCH_W(W, ...)                                                       \
-    switch (W) {                                                                     \
-        case 256: { constexpr int NV = 1, WPR = 1; __VA_ARGS__; } break;             \
-        case 512: { constexpr int NV = 2, WPR = 1; __VA_ARGS__; } break;             \
-        case 1024: { constexpr int NV = 2, WPR = 2; __VA_ARGS__; } break;            \
-        case 2048: { constexpr int NV = 2, WPR = 4; __VA_ARGS__; } break;            \
-        case 4096: { constexpr int NV = 4, WPR = 4; __VA_ARGS__; } break;            \
-        default: return MDL_E_UNSUPPORTED;                                           \
+// ---- geometry: one table answers, for a width and a direction, which <NV, WPR>, how many rows per block iteration, and the grid cap ----
+// The 2048-wide rows are the exceptions to <2, 4> (one block per row).  Forward: a whole row per wave (<8, 1>: 153 VGPRs, no block
+// barriers) beats 4 waves per row.  Backward: 2 waves per row (<4, 2>, ~226 VGPRs) -- the 4-wave version was bound by its per-row block
+// barriers rather than by VALU or HBM: bf16 0.97 -> 0.82 ms, fp32 1.35 -> 1.25 ms at config 2 (tools/exp_ln.py).  Round 5 swept forward
+// <4,2> / <2,4>, backward <8,1> / <2,4> and grid caps 768 / 1024 on fp32 and bf16 storage through these macros: the shipped values are the
+// best or within noise everywhere (profiles/r05i_ln_2048_geometry_variants.txt, repeated after the polynomial GELU: profiles/r05x_*).
+#ifndef MDL_LN_F_NV
+#define MDL_LN_F_NV 8
+#define MDL_LN_F_WPR 1
+#endif
+#ifndef MDL_LN_B_NV
+#define MDL_LN_B_NV 4
+#define MDL_LN_B_WPR 2
+#endif
+#ifndef MDL_LN_GRID_CAP
+#define MDL_LN_GRID_CAP 2048
+#endif
+constexpr int LN_SLOTS = 2048;   // most partial slots of a backward = most workgroups of a launch (256 CUs x 8 blocks) = most groups
+static_assert(MDL_LN_GRID_CAP <= LN_SLOTS, "every workgroup of the backward owns a partial slot of the workspace");
+enum LnDir { LN_FWD, LN_BWD };
+struct LnGeom {
+    int nv, wpr;     // the kernel's <NV, WPR>; NV = 0: no such width
+    int cap;         // most workgroups of an un-grouped launch, which grid-strides over the rest
+    int slot_rows;   // rows per workgroup as the workspace queries and the grouped launches count them: 4 / WPR of the width's first
+                     // geometry -- at 2048 still the 1 of <2, 4>, which only gives the <4, 2> backward more slots than it fills
+    constexpr int rpb() const { return 4 / wpr; }   // rows per block iteration
+};
+constexpr LnGeom ln_geom(int W, LnDir dir) {
+    switch (W) {
+        case 256: return {1, 1, LN_SLOTS, 4};
+        case 512: return {2, 1, LN_SLOTS, 4};
+        case 1024: return {2, 2, LN_SLOTS, 2};
+        case 2048: return dir == LN_FWD ? LnGeom{MDL_LN_F_NV, MDL_LN_F_WPR, MDL_LN_GRID_CAP, 1} : LnGeom{MDL_LN_B_NV, MDL_LN_B_WPR, MDL_LN_GRID_CAP, 1};
+        case 4096: return {4, 4, LN_SLOTS, 1};   // 512 * n_heads for n_heads in {1, 2, 4, 8}, and 256
+        default: return {0, 0, 0, 0};
     }
+}
+static inline int ln_blocks(int64_t rows, int rpb, int cap) {   // workgroups of an un-grouped launch; 0 for no rows
+    const int64_t b = (rows + rpb - 1) / rpb;
+    return (int)(b > cap ? cap : b);
+}
+static inline int ln_group_nbx(int64_t rows, int W, int G) {   // workgroups per group: G * nbx <= LN_SLOTS partial slots
+    const int rpb = ln_geom(W, LN_BWD).slot_rows;
+    const int64_t nbx = std::min<int64_t>(LN_SLOTS / G, (rows / G + rpb - 1) / rpb);   // no more than an average group has row blocks
+    return nbx < 1 ? 1 : (int)nbx;
+}
+static inline int64_t ln_slots(int64_t rows, int W, int G) {   // partial slots of the backward's workspace; G = 0: no groups
+    const int64_t plain = std::max(ln_blocks(rows, ln_geom(W, LN_BWD).slot_rows, LN_SLOTS), 1);
+    return G ? std::max(plain, (int64_t)ln_group_nbx(rows, W, G) * G) : plain;
+}
+static inline int64_t ln_ws_bytes(int64_t rows, int W, int G) { return ln_slots(rows, W, G) * 3 * W * 4 + 128; }   // + aux floats of the split variant
 
+// ---- the dropout mode a kernel is compiled for (its DM; -1: the run-time form), one rule ----
+// bf16 storage: the kernels are VALU-bound, every mode is fixed at compile time.  fp32 storage: HBM-bound, measured no gain -- except
+// the image-only forward with the counter hash (same-box A/B at config 2, profiles/r05z: forward 0.447 -> 0.435 ms avg, 3 of 3 pairs;
+// the image backward 0.660 -> 0.678, 3 of 3 the other way: MDL_LN_IMG_DM stays off).  img: the kernel's IMG.
+constexpr bool ln_img_hash_dm(int img, LnDir dir) { return dir == LN_FWD ? img == 1 && MDL_LN_IMG_DM_FWD : img != 0 && MDL_LN_IMG_DM; }
+static inline int ln_dm(bool bf16, int img, LnDir dir, const ActDrop& d) {
+    const int mode = !d.on ? 0 : (d.keep ? 2 : 1);
+    if (bf16) return mode;
+    return mode == 1 && ln_img_hash_dm(img, dir) ? 1 : -1;
+}
+// the <IMG, DM> pairs that exist: an image kernel has no DM 0 or 2
+constexpr bool ln_has_dm(int img, LnDir dir, int dm) { return img == 0 || dm == -1 || (dm == 1 && ln_img_hash_dm(img, dir)); }
+
+// ---- run-time (direction, IMG, W, DM) -> kernel ----
+template <class IO, int IMG>
+struct LnFwdKernel {
+    static constexpr LnDir dir = LN_FWD;
+    static constexpr int img = IMG;
+    template <int NV, int WPR, int DM>
+    static constexpr auto get() { return &ln_gelu_drop_fwd_kernel<NV, WPR, IO, IMG, DM>; }
+};
+template <class IO, int IMG>
+struct LnBwdKernel {
+    static constexpr LnDir dir = LN_BWD;
+    static constexpr int img = IMG;
+    template <int NV, int WPR, int DM>
+    static constexpr auto get() { return &ln_gelu_drop_bwd_kernel<NV, WPR, IO, IMG != 0, DM>; }
+};
+template <class K, int W>
+static auto ln_kernel_dm(int dm) {
+    constexpr LnGeom g = ln_geom(W, K::dir);
+    switch (dm) {
+        case 0: if constexpr (ln_has_dm(K::img, K::dir, 0)) return K::template get<g.nv, g.wpr, 0>(); break;
+        case 1: if constexpr (ln_has_dm(K::img, K::dir, 1)) return K::template get<g.nv, g.wpr, 1>(); break;
+        case 2: if constexpr (ln_has_dm(K::img, K::dir, 2)) return K::template get<g.nv, g.wpr, 2>(); break;
+    }
+    return K::template get<g.nv, g.wpr, -1>();
+}
+template <class K>
+static auto ln_kernel(int W, int dm) {   // (ln_check has refused every other width)
+    switch (W) {
+        case 256: return ln_kernel_dm<K, 256>(dm);
+        case 512: return ln_kernel_dm<K, 512>(dm);
+        case 1024: return ln_kernel_dm<K, 1024>(dm);
+        case 2048: return ln_kernel_dm<K, 2048>(dm);
+        default: return ln_kernel_dm<K, 4096>(dm);
+    }
+}
+// one launch of any kernel of this file; its status
+template <class... P, class... A>
+static int ln_launch(void (*kernel)(P...), dim3 grid, hipStream_t s, const A&... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, static_cast<P>(args)...);
+    return (int)hipGetLastError();
+}
+
+// ---- the refusals of all eleven launching entry points, in one order ----
+struct LnKind {
+    bool grouped;   // an entry point with cu_groups
+    bool split;     // an entry point whose output is a split image
+};
+struct LnCall {
+    LnKind kind;
+    bool forward;     // eps is read
+    bool required;    // every pointer this entry point cannot do without is there (with groups: cu_groups and the group rows)
+    bool aligned16;   // every pointer the kernels address in 16-byte units is aligned (NULL is)
+    int64_t rows;
+    int W, G;
+    float p_drop, eps;
+};
+// 1. pointers and ranges, 2. the width (a property of the call's shape alone, as the workspace queries refuse it), 3. alignment,
+// 4. the empty problem (MDL_OK, *empty: what is still to do then is the launcher's to say)
+static int ln_check(const LnCall& c, bool* empty) {
+    *empty = c.rows == 0;
+    if (!c.required || c.rows < 0 || !(c.p_drop >= 0.f && c.p_drop < 1.f) || (c.forward && !(c.eps > 0.f))) return MDL_E_ARG;
+    if (c.kind.grouped && (c.G < 1 || c.G > LN_SLOTS)) return MDL_E_ARG;
+    if (ln_geom(c.W, LN_FWD).nv == 0) return MDL_E_UNSUPPORTED;
+    if (c.kind.grouped && !c.kind.split && c.W > 1024) return MDL_E_UNSUPPORTED;   // (the first block is 512 wide)
+    if (!c.aligned16) return MDL_E_ALIGN;
+    return MDL_OK;
+}
+
+// The forward of every kind.  Split: the image's scale comes first, from the parameters alone (ln_bound_scale_kernel; it also clears the
+// rstd_max accumulator) -- an empty problem still gets it.  IMG: 1 = image only, 2 = y as well.
+template <class IO>
+static int ln_fwd_launch(LnKind kind, const LnFwd<IO>& t, const LnParams& p, const LnStats<float>& st, const LnImage<float>& im,
+                         const LnGroups& gr, int W, float p_drop, uint64_t seed, const uint8_t* keep, void* stream) {
+    const bool required = t.x && p.gamma && p.beta && st.mean && st.rstd && (kind.split ? im.img && im.sc : t.y != nullptr) &&
+                          (!kind.grouped || (gr.cu && p.bias));
+    const bool aligned16 = host_aligned16(t.x) && host_aligned16(t.y) && host_aligned16(im.img) && host_aligned16(p.gamma) &&
+                           host_aligned16(p.beta) && host_aligned16(p.bias);
+    bool empty;
+    if (const int rc = ln_check({kind, true, required, aligned16, t.rows, W, gr.G, p_drop, p.eps}, &empty)) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    const ActDrop d = make_act_drop(p_drop, seed, keep);
+    if (kind.split)
+        if (const int rc = ln_launch(ln_bound_scale_kernel, dim3(1), s, p.gamma, p.beta, W, d.inv, nullptr, im.sc, im.rstd_max, nullptr)) return rc;
+    if (empty) return MDL_OK;
+    const LnGeom g = ln_geom(W, LN_FWD);
+    const dim3 grid = kind.grouped ? dim3(ln_group_nbx(t.rows, W, gr.G), gr.G) : dim3(ln_blocks(t.rows, g.rpb(), g.cap));
+    const int img = !kind.split ? 0 : (t.y ? 2 : 1), dm = ln_dm(sizeof(IO) == 2, img, LN_FWD, d);
+    auto kernel = ln_kernel<LnFwdKernel<IO, 0>>(W, dm);
+    if constexpr (sizeof(IO) == 4) {
+        if (img == 1) kernel = ln_kernel<LnFwdKernel<IO, 1>>(W, dm);
+        if (img == 2) kernel = ln_kernel<LnFwdKernel<IO, 2>>(W, dm);
+    }
+    return ln_launch(kernel, grid, s, t, p, st, im, gr, d);
+}
+
+struct LnSums {   // the backward's reductions over rows; dbias and dgroup_bias (per group, [G][W]) may be NULL
+    float *dgamma, *dbeta, *dbias, *dgroup_bias;
+};
+// gradient of the group bias rows: dgb[g][c] = sum over the nbx partial slots of group g of their dbias third
 __global__ __launch_bounds__(256) void ln_group_bias_kernel(const float* __restrict__ part, float* __restrict__ dgb, int nbx, int W) {
     const int g = blockIdx.x;
     for (int c = threadIdx.x; c < W; c += 256) {
@@ -660,189 +831,113 @@ __global__ __launch_bounds__(256) void ln_group_bias_kernel(const float* __restr
         dgb[(int64_t)g * W + c] = v;
     }
 }
-static inline int ln_group_nbx(int64_t rows, int W, int G) {   // workgroups per group: G * nbx <= 2048 partial slots
-    int nbx = 2048 / (G > 0 ? G : 1);
-    const int64_t per = (rows / (G > 0 ? G : 1) + act_rpb(W) - 1) / act_rpb(W);   // no more than an average group has row blocks
-    if (nbx > per) nbx = (int)per;
-    return nbx < 1 ? 1 : nbx;
-}
 
+// The backward of every kind: [split: the image's zero tail and its scale,] the main kernel, the reduction of the partial sums[, the
+// group rows].  t.part is the caller's workspace (ln_ws_bytes).  An empty problem still runs the reduction: it zeroes the sums.
+// Split: dx goes out as an image followed by 32 all-zero rows (the B operand of mdl_split_gemm_tn), under the scale of the rigorous bound
+// rstd_max 1.13 max|gamma| max|dy| (2 + sqrt(W)) / (1-p) (ln_bound_scale_kernel); each of its two data-dependent factors is either
+// published by the kernel that produced it (im.rstd_max: the forward; dy_absmax: the producer of dy) or taken here by one pass.
 template <class IO>
-static int ln_fwd_launch(const IO* x, const float* bias, const float* gamma, const float* beta, IO* y, float* mean, float* rstd, int64_t rows, int W,
-                         float eps, float p_drop, uint64_t seed, const uint8_t* keep, void* stream, const int64_t* cu_groups = nullptr,
-                         int G = 0) {
-    if (!x || !gamma || !beta || !y || !mean || !rstd || rows < 0) return MDL_E_ARG;
-    if (cu_groups && (G < 1 || G > 2048 || !bias)) return MDL_E_ARG;
-    if (cu_groups && rows > 0) {   // grouped: nbx workgroups per group, the group's bias row (never the one-wave-per-row 2048-wide geometry)
-        if (!(p_drop >= 0.f && p_drop < 1.f) || !(eps > 0.f)) return MDL_E_ARG;
-        if (!host_aligned16(x) || !host_aligned16(y) || !host_aligned16(gamma) || !host_aligned16(beta) || !host_aligned16(bias)) return MDL_E_ALIGN;
-        const ActDrop dg = make_act_drop(p_drop, seed, keep);
-        const dim3 grid(ln_group_nbx(rows, W, G), G);
-#define MDL_LN_FWD_G(DMV)                                                                                                                    \
-    hipLaunchKernelGGL((ln_gelu_drop_fwd_kernel<NV, WPR, IO, 0, DMV>), grid, dim3(ACT_BLOCK), 0, (hipStream_t)stream, x, bias, gamma, beta, y, mean, \
-                       rstd, rows, eps, dg, (char*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, cu_groups, W)
-        const int dmg = ln_dm<IO>(dg);   // (dropout mode fixed at compile time where the un-grouped launch does so)
-        MDL_DISPATCH_W(W, {
-            if (dmg < 0) MDL_LN_FWD_G(-1);
-            else if (dmg == 0) MDL_LN_FWD_G(0);
-            else if (dmg == 1) MDL_LN_FWD_G(1);
-            else MDL_LN_FWD_G(2);
-            MDL_LAUNCH_CHECK();
-        });
-#undef MDL_LN_FWD_G
-        return MDL_OK;
-    }
-    if (!(p_drop >= 0.f && p_drop < 1.f) || !(eps > 0.f)) return MDL_E_ARG;
-    if (!host_aligned16(x) || !host_aligned16(y) || !host_aligned16(gamma) || !host_aligned16(beta) || !host_aligned16(bias))
-        return MDL_E_ALIGN;
-    if (rows == 0) return MDL_OK;
+static int ln_bwd_launch(LnKind kind, const LnBwd<IO>& t, const LnParams& p, const LnStats<const float>& st, const LnImage<const float>& im,
+                         const float* dy_absmax, const LnGroups& gr, const LnSums& out, int W, float p_drop, uint64_t seed,
+                         const uint8_t* keep, void* stream) {
+    const bool required = t.x && p.gamma && p.beta && st.mean && st.rstd && t.dy && out.dgamma && out.dbeta && t.part &&
+                          (kind.split ? im.img && im.sc : t.dx != nullptr) &&
+                          (!kind.grouped || (gr.cu && out.dgroup_bias && (kind.split || p.bias)));
+    const bool aligned16 = host_aligned16(t.x) && host_aligned16(t.dy) && host_aligned16(t.dx) && host_aligned16(im.img) &&
+                           host_aligned16(p.gamma) && host_aligned16(p.beta) && host_aligned16(p.bias) &&
+                           (!kind.split || host_aligned16(t.part));
+    bool empty;
+    if (const int rc = ln_check({kind, false, required, aligned16, t.rows, W, gr.G, p_drop, 0.f}, &empty)) return rc;
+    const hipStream_t s = (hipStream_t)stream;
     const ActDrop d = make_act_drop(p_drop, seed, keep);
-// (geometry of the 2048-wide kernels as macros: round 5 swept forward <4,2> / <2,4>, backward <8,1> / <2,4> and grid caps 768 / 1024 on fp32
-// and bf16 storage -- the shipped <8,1> / <4,2> / 2048 is the best or within noise everywhere, profiles/r05i_ln_2048_geometry_variants.txt;
-// the bf16 kernels (then 4.0 / 3.9 TB/s) were bound by their VALU work, not by the row geometry: see act_gelu4 (polynomial GELU, round 5:
-// 2048-wide forward 4.7 TB/s, backward 4.5; the sweep repeated after that change confirms <8,1> / <4,2>, profiles/r05x_*)
-#ifndef MDL_LN_F_NV
-#define MDL_LN_F_NV 8
-#define MDL_LN_F_WPR 1
-#endif
-#ifndef MDL_LN_GRID_CAP
-#define MDL_LN_GRID_CAP 2048
-#endif
-    if (W == 2048) {  // forward: a whole 2048-wide row per wave (153 VGPRs, no block barriers) beats 4 waves per row
-        int64_t nb = (rows + 4 / MDL_LN_F_WPR - 1) / (4 / MDL_LN_F_WPR);
-        if (nb > MDL_LN_GRID_CAP) nb = MDL_LN_GRID_CAP;
-#define MDL_LN_FWD(NVV, WPRV, DMV)                                                                                                  \
-    hipLaunchKernelGGL((ln_gelu_drop_fwd_kernel<NVV, WPRV, IO, 0, DMV>), dim3((unsigned)nb), dim3(ACT_BLOCK), 0, (hipStream_t)stream, x, \
-                       bias, gamma, beta, y, mean, rstd, rows, eps, d)
-#define MDL_LN_FWD_DM(NVV, WPRV)                  \
-    do {                                          \
-        if (dm < 0) MDL_LN_FWD(NVV, WPRV, -1);    \
-        else if (dm == 0) MDL_LN_FWD(NVV, WPRV, 0); \
-        else if (dm == 1) MDL_LN_FWD(NVV, WPRV, 1); \
-        else MDL_LN_FWD(NVV, WPRV, 2);            \
-    } while (0)
-        const int dm = ln_dm<IO>(d);
-        MDL_LN_FWD_DM(MDL_LN_F_NV, MDL_LN_F_WPR);
-        MDL_LAUNCH_CHECK();
-        return MDL_OK;
-    }
-    MDL_DISPATCH_W(W, {
-        const int nb = act_blocks(rows, W);
-        const int dm = ln_dm<IO>(d);
-        MDL_LN_FWD_DM(NV, WPR);
-        MDL_LAUNCH_CHECK();
-    });
-#undef MDL_LN_FWD_DM
-#undef MDL_LN_FWD
-    return MDL_OK;
-}
-
-template <class IO>
-static int ln_bwd_launch(const IO* x, const float* bias, const float* gamma, const float* beta, const float* mean, const float* rstd,
-                         const IO* dy, IO* dx, float* dgamma, float* dbeta, float* dbias, int64_t rows, int W, float p_drop, uint64_t seed,
-                         const uint8_t* keep, void* ws, void* stream, const int64_t* cu_groups = nullptr, int G = 0,
-                         float* dgroup_bias = nullptr) {
-    if (!x || !gamma || !beta || !mean || !rstd || !dy || !dx || !dgamma || !dbeta || !ws || rows < 0) return MDL_E_ARG;
-    if (cu_groups) {   // grouped: per-group bias rows in, per-group bias gradients out (dbias = their sum over the groups)
-        if (G < 1 || G > 2048 || !bias || !dgroup_bias) return MDL_E_ARG;
-        if (!(p_drop >= 0.f && p_drop < 1.f)) return MDL_E_ARG;
-        if (!host_aligned16(x) || !host_aligned16(dy) || !host_aligned16(dx) || !host_aligned16(gamma) || !host_aligned16(beta) ||
-            !host_aligned16(bias))
-            return MDL_E_ALIGN;
-        hipStream_t sg = (hipStream_t)stream;
-        const ActDrop dd = make_act_drop(p_drop, seed, keep);
-        const int nbx = ln_group_nbx(rows, W, G);
-        const dim3 grid(nbx, G);
-#define MDL_LN_BWD_G(DMV)                                                                                                                    \
-    hipLaunchKernelGGL((ln_gelu_drop_bwd_kernel<NV, WPR, IO, false, DMV>), grid, dim3(ACT_BLOCK), 0, sg, x, bias, gamma, beta, mean, rstd, dy, dx, \
-                       (float*)ws, rows, dd, (char*)nullptr, (const float*)nullptr, (const float*)nullptr, cu_groups, W)
-        const int dmg = ln_dm<IO>(dd);
-        MDL_DISPATCH_W(W, {
-            if (dmg < 0) MDL_LN_BWD_G(-1);
-            else if (dmg == 0) MDL_LN_BWD_G(0);
-            else if (dmg == 1) MDL_LN_BWD_G(1);
-            else MDL_LN_BWD_G(2);
-            MDL_LAUNCH_CHECK();
-        });
-#undef MDL_LN_BWD_G
-        hipLaunchKernelGGL(ln_reduce_kernel, dim3((3 * W + 31) / 32), dim3(256), 0, sg, (const float*)ws, dgamma, dbeta, dbias, nbx * G, W);
-        MDL_LAUNCH_CHECK();
-        hipLaunchKernelGGL(ln_group_bias_kernel, dim3(G), dim3(256), 0, sg, (const float*)ws, dgroup_bias, nbx, W);
-        MDL_LAUNCH_CHECK();
-        return MDL_OK;
-    }
-    if (!(p_drop >= 0.f && p_drop < 1.f)) return MDL_E_ARG;
-    if (!host_aligned16(x) || !host_aligned16(dy) || !host_aligned16(dx) || !host_aligned16(gamma) || !host_aligned16(beta) ||
-        !host_aligned16(bias))
-        return MDL_E_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    const ActDrop d = make_act_drop(p_drop, seed, keep);
-    int nb = rows > 0 ? act_blocks(rows, W) : 0;
-    if (W == 2048 && nb > 0) {
-        // 2048 wide: 2 waves per row (NV = 4, ~226 VGPRs) instead of 4 -- the 4-wave version was bound by its per-row block barriers
-        // rather than by VALU or HBM: bf16 0.97 -> 0.82 ms, fp32 1.35 -> 1.25 ms at config 2 (tools/exp_ln.py)
-#ifndef MDL_LN_B_NV
-#define MDL_LN_B_NV 4
-#define MDL_LN_B_WPR 2
-#endif
-        int64_t b2 = (rows + 4 / MDL_LN_B_WPR - 1) / (4 / MDL_LN_B_WPR);
-        if (b2 > MDL_LN_GRID_CAP) b2 = MDL_LN_GRID_CAP;
-        nb = (int)b2;
-#define MDL_LN_BWD(NVV, WPRV, DMV)                                                                                                  \
-    hipLaunchKernelGGL((ln_gelu_drop_bwd_kernel<NVV, WPRV, IO, false, DMV>), dim3(nb), dim3(ACT_BLOCK), 0, s, x, bias, gamma, beta, mean, \
-                       rstd, dy, dx, (float*)ws, rows, d)
-#define MDL_LN_BWD_DM(NVV, WPRV)                  \
-    do {                                          \
-        if (dm < 0) MDL_LN_BWD(NVV, WPRV, -1);    \
-        else if (dm == 0) MDL_LN_BWD(NVV, WPRV, 0); \
-        else if (dm == 1) MDL_LN_BWD(NVV, WPRV, 1); \
-        else MDL_LN_BWD(NVV, WPRV, 2);            \
-    } while (0)
-        const int dm = ln_dm<IO>(d);
-        MDL_LN_BWD_DM(MDL_LN_B_NV, MDL_LN_B_WPR);
-        MDL_LAUNCH_CHECK();
-    } else
-    MDL_DISPATCH_W(W, {
-        if (nb > 0) {
-            const int dm = ln_dm<IO>(d);
-            MDL_LN_BWD_DM(NV, WPR);
-            MDL_LAUNCH_CHECK();
+    const LnGeom g = ln_geom(W, LN_BWD);
+    const int64_t rows = t.rows;
+    // nbx workgroups per group, one partial slot each: [G][nbx][3 W]; without groups, none for no rows
+    const int nbx = kind.grouped ? ln_group_nbx(rows, W, gr.G) : ln_blocks(rows, g.rpb(), g.cap), ngroups = kind.grouped ? gr.G : 1;
+    if constexpr (sizeof(IO) == 4) {
+        if (kind.split) {
+            float* aux = t.part + ln_slots(rows, W, kind.grouped ? gr.G : 0) * 3 * W;   // [0] max rstd (* row_mul), [1] max |dy|
+            hipError_t e = hipMemsetAsync(im.img + rows * (int64_t)W * 4, 0, (size_t)32 * W * 4, s);
+            if (e != hipSuccess) return (int)e;
+            if (im.rstd_max && dy_absmax) {   // no memset, no pass over rstd, no copy: the bound kernel reads both where they lie
+                if (const int rc = ln_launch(ln_bound_scale_kernel, dim3(1), s, p.gamma, p.beta, W, d.inv, im.rstd_max, im.sc, nullptr, dy_absmax))
+                    return rc;
+            } else {
+                e = hipMemsetAsync(aux, 0, 2 * sizeof(float), s);
+                if (e != hipSuccess) return (int)e;
+                int rc = MDL_OK;
+                if (im.rstd_max)
+                    e = hipMemcpyAsync(aux, im.rstd_max, sizeof(float), hipMemcpyDeviceToDevice, s);
+                else if (im.row_mul && rows > 0)   // the image holds row_mul[r] dx[r][:]: bound through max_r rstd[r] row_mul[r]
+                    rc = ln_launch(absmax_prod_kernel, dim3((unsigned)std::min<int64_t>((rows + 2047) / 2048, 2048)), s, st.rstd, im.row_mul, rows, aux);
+                else
+                    rc = sp_launch_absmax_flat(st.rstd, rows, aux, s);
+                if (e != hipSuccess) return (int)e;
+                if (rc) return rc;
+                if (dy_absmax) {
+                    e = hipMemcpyAsync(aux + 1, dy_absmax, sizeof(float), hipMemcpyDeviceToDevice, s);
+                    if (e != hipSuccess) return (int)e;
+                } else if ((rc = sp_launch_absmax(t.dy, W, rows, W, aux + 1, s)) != MDL_OK) {
+                    return rc;
+                }
+                if ((rc = ln_launch(ln_bound_scale_kernel, dim3(1), s, p.gamma, p.beta, W, d.inv, aux, im.sc, nullptr, nullptr)) != MDL_OK) return rc;
+            }
         }
-    });
-#undef MDL_LN_BWD_DM
-#undef MDL_LN_BWD
-    hipLaunchKernelGGL(ln_reduce_kernel, dim3((3 * W + 31) / 32), dim3(256), 0, s, (const float*)ws, dgamma, dbeta, dbias, nb, W);
-    MDL_LAUNCH_CHECK();
-    return MDL_OK;
+    }
+    if (nbx > 0) {
+        const int img = kind.split ? 1 : 0, dm = ln_dm(sizeof(IO) == 2, img, LN_BWD, d);
+        auto kernel = ln_kernel<LnBwdKernel<IO, 0>>(W, dm);
+        if constexpr (sizeof(IO) == 4)
+            if (img) kernel = ln_kernel<LnBwdKernel<IO, 1>>(W, dm);
+        if (const int rc = ln_launch(kernel, dim3(nbx, ngroups), s, t, p, st, im, gr, d)) return rc;
+    }
+    if (const int rc = ln_launch(ln_reduce_kernel, dim3((3 * W + 31) / 32), s, t.part, out.dgamma, out.dbeta, out.dbias, nbx * ngroups, W)) return rc;
+    return kind.grouped ? ln_launch(ln_group_bias_kernel, dim3(gr.G), s, t.part, out.dgroup_bias, nbx, W) : MDL_OK;
+}
+
+constexpr LnKind LN_PLAIN = {false, false}, LN_GROUPED = {true, false}, LN_SPLIT = {false, true}, LN_SPLIT_GROUPED = {true, true};
+
+}  // namespace mdl
+
+using namespace mdl;
+
+// ---- the entry points: each fills the records and calls one of the two launchers ----
+extern "C" int64_t mdl_ln_gelu_drop_bwd_ws_bytes(int64_t rows, int W) {
+    if (rows < 0) return MDL_E_ARG;
+    if (ln_geom(W, LN_BWD).nv == 0) return MDL_E_UNSUPPORTED;
+    return ln_ws_bytes(rows, W, 0);
+}
+extern "C" int64_t mdl_ln_gelu_drop_bwd_groups_ws_bytes(int64_t rows, int W, int G) {
+    if (rows < 0 || G < 1 || G > LN_SLOTS) return MDL_E_ARG;
+    if (ln_geom(W, LN_BWD).nv == 0) return MDL_E_UNSUPPORTED;
+    return ln_ws_bytes(rows, W, G);
 }
 
 extern "C" int mdl_ln_gelu_drop_fwd(const float* x, const float* bias, const float* gamma, const float* beta, float* y,
                                     float* mean, float* rstd, int64_t rows, int W, float eps, float p_drop, uint64_t seed,
                                     const uint8_t* keep, void* stream) {
-    return ln_fwd_launch<float>(x, bias, gamma, beta, y, mean, rstd, rows, W, eps, p_drop, seed, keep, stream);
+    return ln_fwd_launch<float>(LN_PLAIN, {x, y, rows}, {bias, 0, gamma, beta, eps}, {mean, rstd}, {}, {}, W, p_drop, seed, keep, stream);
 }
-
+extern "C" int mdl_ln_gelu_drop_fwd_bf16(const uint16_t* x, const float* bias, const float* gamma, const float* beta,
+                                         uint16_t* y, float* mean, float* rstd, int64_t rows, int W, float eps, float p_drop,
+                                         uint64_t seed, const uint8_t* keep, void* stream) {
+    return ln_fwd_launch<bf16_t>(LN_PLAIN, {(const bf16_t*)x, (bf16_t*)y, rows}, {bias, 0, gamma, beta, eps}, {mean, rstd}, {}, {}, W, p_drop,
+                                 seed, keep, stream);
+}
 extern "C" int mdl_ln_gelu_drop_bwd(const float* x, const float* bias, const float* gamma, const float* beta, const float* mean,
                                     const float* rstd, const float* dy, float* dx, float* dgamma, float* dbeta, float* dbias,
                                     int64_t rows, int W, float p_drop, uint64_t seed, const uint8_t* keep, void* ws,
                                     void* stream) {
-    return ln_bwd_launch<float>(x, bias, gamma, beta, mean, rstd, dy, dx, dgamma, dbeta, dbias, rows, W, p_drop, seed, keep, ws,
-                                stream);
+    return ln_bwd_launch<float>(LN_PLAIN, {x, dy, dx, (float*)ws, rows}, {bias, 0, gamma, beta, 0.f}, {mean, rstd}, {}, nullptr, {},
+                                {dgamma, dbeta, dbias, nullptr}, W, p_drop, seed, keep, stream);
 }
-
-extern "C" int mdl_ln_gelu_drop_fwd_bf16(const uint16_t* x, const float* bias, const float* gamma, const float* beta,
-                                         uint16_t* y, float* mean, float* rstd, int64_t rows, int W, float eps, float p_drop,
-                                         uint64_t seed, const uint8_t* keep, void* stream) {
-    return ln_fwd_launch<bf16_t>((const bf16_t*)x, bias, gamma, beta, (bf16_t*)y, mean, rstd, rows, W, eps, p_drop, seed, keep,
-                                 stream);
-}
-
 extern "C" int mdl_ln_gelu_drop_bwd_bf16(const uint16_t* x, const float* bias, const float* gamma, const float* beta,
                                          const float* mean, const float* rstd, const uint16_t* dy, uint16_t* dx, float* dgamma,
                                          float* dbeta, float* dbias, int64_t rows, int W, float p_drop, uint64_t seed,
                                          const uint8_t* keep, void* ws, void* stream) {
-    return ln_bwd_launch<bf16_t>((const bf16_t*)x, bias, gamma, beta, mean, rstd, (const bf16_t*)dy, (bf16_t*)dx, dgamma, dbeta,
-                                 dbias, rows, W, p_drop, seed, keep, ws, stream);
+    return ln_bwd_launch<bf16_t>(LN_PLAIN, {(const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, (float*)ws, rows}, {bias, 0, gamma, beta, 0.f},
+                                 {mean, rstd}, {}, nullptr, {}, {dgamma, dbeta, dbias, nullptr}, W, p_drop, seed, keep, stream);
 }
 
 /* Grouped forms for the engines whose GEMM epilogue adds no bias (exact fp32, bf16): rows [cu_groups[g], cu_groups[g + 1]) of group g take
@@ -852,35 +947,29 @@ extern "C" int mdl_ln_gelu_drop_bwd_bf16(const uint16_t* x, const float* bias, c
 extern "C" int mdl_ln_gelu_drop_fwd_groups(const float* x, const float* group_bias, const float* gamma, const float* beta, float* y, float* mean,
                                            float* rstd, int64_t rows, int W, float eps, float p_drop, uint64_t seed, const uint8_t* keep,
                                            const int64_t* cu_groups, int G, void* stream) {
-    if (!cu_groups) return MDL_E_ARG;
-    if (W > 1024) return MDL_E_UNSUPPORTED;
-    return ln_fwd_launch<float>(x, group_bias, gamma, beta, y, mean, rstd, rows, W, eps, p_drop, seed, keep, stream, cu_groups, G);
+    return ln_fwd_launch<float>(LN_GROUPED, {x, y, rows}, {group_bias, W, gamma, beta, eps}, {mean, rstd}, {}, {cu_groups, G}, W, p_drop, seed,
+                                keep, stream);
 }
 extern "C" int mdl_ln_gelu_drop_fwd_groups_bf16(const uint16_t* x, const float* group_bias, const float* gamma, const float* beta, uint16_t* y,
                                                 float* mean, float* rstd, int64_t rows, int W, float eps, float p_drop, uint64_t seed,
                                                 const uint8_t* keep, const int64_t* cu_groups, int G, void* stream) {
-    if (!cu_groups) return MDL_E_ARG;
-    if (W > 1024) return MDL_E_UNSUPPORTED;
-    return ln_fwd_launch<bf16_t>((const bf16_t*)x, group_bias, gamma, beta, (bf16_t*)y, mean, rstd, rows, W, eps, p_drop, seed, keep, stream,
-                                 cu_groups, G);
+    return ln_fwd_launch<bf16_t>(LN_GROUPED, {(const bf16_t*)x, (bf16_t*)y, rows}, {group_bias, W, gamma, beta, eps}, {mean, rstd}, {},
+                                 {cu_groups, G}, W, p_drop, seed, keep, stream);
 }
 extern "C" int mdl_ln_gelu_drop_bwd_groups(const float* x, const float* group_bias, const float* gamma, const float* beta, const float* mean,
                                            const float* rstd, const float* dy, float* dx, float* dgamma, float* dbeta, float* dgroup_bias,
                                            int64_t rows, int W, float p_drop, uint64_t seed, const uint8_t* keep, const int64_t* cu_groups, int G,
                                            void* ws, void* stream) {
-    if (!cu_groups) return MDL_E_ARG;
-    if (W > 1024) return MDL_E_UNSUPPORTED;
-    return ln_bwd_launch<float>(x, group_bias, gamma, beta, mean, rstd, dy, dx, dgamma, dbeta, (float*)nullptr, rows, W, p_drop, seed, keep, ws,
-                                stream, cu_groups, G, dgroup_bias);
+    return ln_bwd_launch<float>(LN_GROUPED, {x, dy, dx, (float*)ws, rows}, {group_bias, W, gamma, beta, 0.f}, {mean, rstd}, {}, nullptr,
+                                {cu_groups, G}, {dgamma, dbeta, nullptr, dgroup_bias}, W, p_drop, seed, keep, stream);
 }
 extern "C" int mdl_ln_gelu_drop_bwd_groups_bf16(const uint16_t* x, const float* group_bias, const float* gamma, const float* beta,
                                                 const float* mean, const float* rstd, const uint16_t* dy, uint16_t* dx, float* dgamma,
                                                 float* dbeta, float* dgroup_bias, int64_t rows, int W, float p_drop, uint64_t seed,
                                                 const uint8_t* keep, const int64_t* cu_groups, int G, void* ws, void* stream) {
-    if (!cu_groups) return MDL_E_ARG;
-    if (W > 1024) return MDL_E_UNSUPPORTED;
-    return ln_bwd_launch<bf16_t>((const bf16_t*)x, group_bias, gamma, beta, mean, rstd, (const bf16_t*)dy, (bf16_t*)dx, dgamma, dbeta,
-                                 (float*)nullptr, rows, W, p_drop, seed, keep, ws, stream, cu_groups, G, dgroup_bias);
+    return ln_bwd_launch<bf16_t>(LN_GROUPED, {(const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, (float*)ws, rows},
+                                 {group_bias, W, gamma, beta, 0.f}, {mean, rstd}, {}, nullptr, {cu_groups, G},
+                                 {dgamma, dbeta, nullptr, dgroup_bias}, W, p_drop, seed, keep, stream);
 }
 
 /* mdl_ln_gelu_drop_fwd whose output is written as a SPLIT IMAGE (rows of 4 W bytes at img; scale[2] = {scale, bound} from the
@@ -888,168 +977,32 @@ extern "C" int mdl_ln_gelu_drop_bwd_groups_bf16(const uint16_t* x, const float* 
 extern "C" int mdl_ln_gelu_drop_fwd_split(const float* x, const float* bias, const float* gamma, const float* beta, float* y, void* img,
                                           float* scale, float* mean, float* rstd, int64_t rows, int W, float eps, float p_drop,
                                           uint64_t seed, const uint8_t* keep, const float* row_mul, float* rstd_max, void* stream) {
-    if (!x || !gamma || !beta || !img || !scale || !mean || !rstd || rows < 0) return MDL_E_ARG;
-    if (!(p_drop >= 0.f && p_drop < 1.f) || !(eps > 0.f)) return MDL_E_ARG;
-    if (!act_width_ok(W) || W > 4096) return MDL_E_UNSUPPORTED;
-    if (!host_aligned16(x) || !host_aligned16(y) || !host_aligned16(img) || !host_aligned16(gamma) || !host_aligned16(beta) ||
-        !host_aligned16(bias))
-        return MDL_E_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    const ActDrop d = make_act_drop(p_drop, seed, keep);
-    hipLaunchKernelGGL(ln_bound_scale_kernel, dim3(1), dim3(256), 0, s, gamma, beta, W, d.inv, (const float*)nullptr, scale, rstd_max,
-                       (const float*)nullptr);
-    MDL_LAUNCH_CHECK();
-    if (rows == 0) return MDL_OK;
-#define MDL_LN_FWD_IMG(NVV, WPRV, NB)                                                                                                    \
-    do {                                                                                                                               \
-        if (y) hipLaunchKernelGGL((ln_gelu_drop_fwd_kernel<NVV, WPRV, float, 2>), dim3((unsigned)(NB)), dim3(ACT_BLOCK), 0, s, x, bias, \
-                                  gamma, beta, y, mean, rstd, rows, eps, d, (char*)img, (const float*)scale, row_mul, rstd_max);        \
-        else if (MDL_LN_IMG_DM_FWD && act_drop_mode(d) == 1)                                                                            \
-            hipLaunchKernelGGL((ln_gelu_drop_fwd_kernel<NVV, WPRV, float, 1, MDL_LN_IMG_DM_FWD ? 1 : -1>), dim3((unsigned)(NB)), dim3(ACT_BLOCK), 0, \
-                               s, x, bias, gamma, beta, y, mean, rstd, rows, eps, d, (char*)img, (const float*)scale, row_mul, rstd_max); \
-        else hipLaunchKernelGGL((ln_gelu_drop_fwd_kernel<NVV, WPRV, float, 1>), dim3((unsigned)(NB)), dim3(ACT_BLOCK), 0, s, x, bias,   \
-                                gamma, beta, y, mean, rstd, rows, eps, d, (char*)img, (const float*)scale, row_mul, rstd_max);          \
-    } while (0)
-    if (W == 2048) {
-        int64_t nb = (rows + 3) / 4;
-        if (nb > 2048) nb = 2048;
-        MDL_LN_FWD_IMG(8, 1, nb);
-    } else {
-        MDL_DISPATCH_W(W, { MDL_LN_FWD_IMG(NV, WPR, act_blocks(rows, W)); });
-    }
-#undef MDL_LN_FWD_IMG
-    MDL_LAUNCH_CHECK();
-    return MDL_OK;
+    return ln_fwd_launch<float>(LN_SPLIT, {x, y, rows}, {bias, 0, gamma, beta, eps}, {mean, rstd}, {(char*)img, scale, row_mul, rstd_max}, {}, W,
+                                p_drop, seed, keep, stream);
 }
 
-/* mdl_ln_gelu_drop_bwd whose dx is written as a SPLIT IMAGE followed by 32 all-zero rows (the B operand of mdl_split_gemm_tn);
- * dx_scale[2] = {scale, bound} from the rigorous bound rstd_max 1.13 max|gamma| max|dy| (2 + sqrt(W)) / (1-p).  dy_absmax: device
+/* mdl_ln_gelu_drop_bwd whose dx is written as a SPLIT IMAGE followed by 32 all-zero rows; dx_scale[2] = {scale, bound}.  dy_absmax: device
  * float holding max |dy| (e.g. from the epilogue of the kernel that produced dy), or NULL: computed here by one pass over dy.
- * ws: mdl_ln_gelu_drop_bwd_ws_bytes(rows, W) + 64 bytes. */
-// gradient of the group bias rows: dgb[g][c] = sum over the nbx partial slots of group g of their dbias third
-static int ln_bwd_split_impl(const float* x, const float* bias, const float* gamma, const float* beta, const float* mean,
-                             const float* rstd, const float* dy, const float* dy_absmax, void* dx_img, float* dx_scale,
-                             float* dgamma, float* dbeta, float* dbias, int64_t rows, int W, float p_drop, uint64_t seed,
-                             const uint8_t* keep, const float* row_mul, const float* rstd_max, void* ws, void* stream,
-                             const int64_t* cu_groups, int G, float* dgroup_bias) {
-    if (!x || !gamma || !beta || !mean || !rstd || !dy || !dx_img || !dx_scale || !dgamma || !dbeta || !ws || rows < 0) return MDL_E_ARG;
-    if (cu_groups && (G < 1 || G > 2048 || !dgroup_bias)) return MDL_E_ARG;
-    if (!(p_drop >= 0.f && p_drop < 1.f)) return MDL_E_ARG;
-    if (!act_width_ok(W) || W > 4096) return MDL_E_UNSUPPORTED;
-    if (!host_aligned16(x) || !host_aligned16(dy) || !host_aligned16(dx_img) || !host_aligned16(gamma) || !host_aligned16(beta) ||
-        !host_aligned16(bias) || !host_aligned16(ws))
-        return MDL_E_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    const ActDrop d = make_act_drop(p_drop, seed, keep);
-    int nb = rows > 0 ? act_blocks(rows, W) : 0;
-    if (W == 2048 && nb > 0) {
-        int64_t b2 = (rows + 1) / 2;
-        if (b2 > 2048) b2 = 2048;
-        nb = (int)b2;
-    }
-    int slots = act_blocks(rows, W);
-    dim3 grid(nb > 0 ? nb : 1);
-    if (cu_groups) {   // nbx workgroups per group, one partial slot each: [G][nbx][3 W]
-        const int nbx = ln_group_nbx(rows, W, G);
-        grid = dim3(nbx, G);
-        nb = nbx * G;
-        slots = slots > nb ? slots : nb;
-    }
-    float* part = (float*)ws;
-    float* aux = (float*)((char*)ws + (((int64_t)slots * 3 * W * 4 + 15) & ~(int64_t)15));   // [0] max rstd, [1] max |dy|
-    hipError_t e = hipMemsetAsync((char*)dx_img + rows * (int64_t)W * 4, 0, (size_t)32 * W * 4, s);
-    if (e != hipSuccess) return (int)e;
-    int rc = MDL_OK;
-    if (rstd_max && dy_absmax) {
-        // both factors of the bound were published by the kernels that produced them (the forward: max rstd * row_mul; the producer of
-        // dy: max |dy|): no memset, no pass over rstd, no copy -- the bound kernel reads them where they lie
-        hipLaunchKernelGGL(ln_bound_scale_kernel, dim3(1), dim3(256), 0, s, gamma, beta, W, d.inv, rstd_max, dx_scale, (float*)nullptr,
-                           dy_absmax);
-        MDL_LAUNCH_CHECK();
-    } else {
-        e = hipMemsetAsync(aux, 0, 2 * sizeof(float), s);
-        if (e != hipSuccess) return (int)e;
-        if (rstd_max) {
-            e = hipMemcpyAsync(aux, rstd_max, sizeof(float), hipMemcpyDeviceToDevice, s);
-            if (e != hipSuccess) return (int)e;
-        } else if (row_mul && rows > 0) {   // the image holds row_mul[r] dx[r][:]: bound through max_r rstd[r] row_mul[r]
-            int nbm = (int)((rows + 2047) / 2048);
-            if (nbm > 2048) nbm = 2048;
-            hipLaunchKernelGGL(absmax_prod_kernel, dim3(nbm), dim3(256), 0, s, rstd, row_mul, rows, aux);
-            MDL_LAUNCH_CHECK();
-        } else {
-            rc = sp_launch_absmax_flat(rstd, rows, aux, s);
-        }
-        if (rc) return rc;
-        if (dy_absmax) {
-            e = hipMemcpyAsync(aux + 1, dy_absmax, sizeof(float), hipMemcpyDeviceToDevice, s);
-            if (e != hipSuccess) return (int)e;
-        } else {
-            rc = sp_launch_absmax(dy, W, rows, W, aux + 1, s);
-            if (rc) return rc;
-        }
-        hipLaunchKernelGGL(ln_bound_scale_kernel, dim3(1), dim3(256), 0, s, gamma, beta, W, d.inv, (const float*)aux, dx_scale, (float*)nullptr,
-                           (const float*)nullptr);
-        MDL_LAUNCH_CHECK();
-    }
-    const bool hash_dm = MDL_LN_IMG_DM && act_drop_mode(d) == 1;   // (A/B: the counter-hash mode fixed at compile time)
-#define MDL_LN_BWD_IMG(NVV, WPRV)                                                                                                       \
-    do {                                                                                                                                \
-        if (hash_dm)                                                                                                                    \
-            hipLaunchKernelGGL((ln_gelu_drop_bwd_kernel<NVV, WPRV, float, true, MDL_LN_IMG_DM ? 1 : -1>), grid, dim3(ACT_BLOCK), 0, s, x, bias, \
-                               gamma, beta, mean, rstd, dy, (float*)nullptr, part, rows, d, (char*)dx_img, (const float*)dx_scale, row_mul, \
-                               cu_groups);                                                                                              \
-        else                                                                                                                            \
-            hipLaunchKernelGGL((ln_gelu_drop_bwd_kernel<NVV, WPRV, float, true>), grid, dim3(ACT_BLOCK), 0, s, x, bias, gamma, beta, mean, \
-                               rstd, dy, (float*)nullptr, part, rows, d, (char*)dx_img, (const float*)dx_scale, row_mul, cu_groups);    \
-    } while (0)
-    if (W == 2048 && nb > 0) {
-        MDL_LN_BWD_IMG(4, 2);
-        MDL_LAUNCH_CHECK();
-    } else
-    MDL_DISPATCH_W(W, {
-        if (nb > 0) {
-            MDL_LN_BWD_IMG(NV, WPR);
-            MDL_LAUNCH_CHECK();
-        }
-    });
-#undef MDL_LN_BWD_IMG
-    hipLaunchKernelGGL(ln_reduce_kernel, dim3((3 * W + 31) / 32), dim3(256), 0, s, (const float*)part, dgamma, dbeta, dbias, nb, W);
-    MDL_LAUNCH_CHECK();
-    if (cu_groups) {
-        hipLaunchKernelGGL(ln_group_bias_kernel, dim3(G), dim3(256), 0, s, (const float*)part, dgroup_bias, nb / G, W);
-        MDL_LAUNCH_CHECK();
-    }
-    return MDL_OK;
-}
-
+ * ws: mdl_ln_gelu_drop_bwd_ws_bytes(rows, W). */
 extern "C" int mdl_ln_gelu_drop_bwd_split(const float* x, const float* bias, const float* gamma, const float* beta, const float* mean,
                                           const float* rstd, const float* dy, const float* dy_absmax, void* dx_img, float* dx_scale,
                                           float* dgamma, float* dbeta, float* dbias, int64_t rows, int W, float p_drop, uint64_t seed,
                                           const uint8_t* keep, const float* row_mul, const float* rstd_max, void* ws, void* stream) {
-    return ln_bwd_split_impl(x, bias, gamma, beta, mean, rstd, dy, dy_absmax, dx_img, dx_scale, dgamma, dbeta, dbias, rows, W, p_drop, seed, keep,
-                             row_mul, rstd_max, ws, stream, nullptr, 0, nullptr);
+    return ln_bwd_launch<float>(LN_SPLIT, {x, dy, nullptr, (float*)ws, rows}, {bias, 0, gamma, beta, 0.f}, {mean, rstd},
+                                {(char*)dx_img, dx_scale, row_mul, rstd_max}, dy_absmax, {}, {dgamma, dbeta, dbias, nullptr}, W, p_drop, seed,
+                                keep, stream);
 }
-
 /* The same for a pre-LN tensor that carries a per-GROUP bias row (x[r] = product[r] + group_bias[g(r)], rows of a group contiguous:
  * cu_groups int64 [G + 1] on the device, G <= 2048): additionally dgroup_bias [G][W] = sum over the rows of each group of dx -- the
  * gradient of the group rows (MADELEINE's stain-encoding columns folded out of the first Linear: Model.py:125-132, :351).  The launch
  * is organised by group (rows of one group per workgroup), so the per-group sums are the existing per-workgroup dbias partials, merged
  * in a fixed order.  ws: mdl_ln_gelu_drop_bwd_groups_ws_bytes(rows, W, G). */
-extern "C" int64_t mdl_ln_gelu_drop_bwd_groups_ws_bytes(int64_t rows, int W, int G) {
-    if (rows < 0 || G < 1 || G > 2048) return MDL_E_ARG;
-    if (!act_width_ok(W)) return MDL_E_UNSUPPORTED;
-    int64_t slots = act_blocks(rows, W);
-    const int64_t nb = (int64_t)ln_group_nbx(rows, W, G) * G;
-    if (nb > slots) slots = nb;
-    return slots * 3 * W * 4 + 128;
-}
 extern "C" int mdl_ln_gelu_drop_bwd_split_groups(const float* x, const float* bias, const float* gamma, const float* beta, const float* mean,
                                                  const float* rstd, const float* dy, const float* dy_absmax, void* dx_img, float* dx_scale,
                                                  float* dgamma, float* dbeta, float* dbias, int64_t rows, int W, float p_drop, uint64_t seed,
                                                  const uint8_t* keep, const float* row_mul, const float* rstd_max, const int64_t* cu_groups,
                                                  int G, float* dgroup_bias, void* ws, void* stream) {
-    if (!cu_groups) return MDL_E_ARG;
-    return ln_bwd_split_impl(x, bias, gamma, beta, mean, rstd, dy, dy_absmax, dx_img, dx_scale, dgamma, dbeta, dbias, rows, W, p_drop, seed, keep,
-                             row_mul, rstd_max, ws, stream, cu_groups, G, dgroup_bias);
+    return ln_bwd_launch<float>(LN_SPLIT_GROUPED, {x, dy, nullptr, (float*)ws, rows}, {bias, 0, gamma, beta, 0.f}, {mean, rstd},
+                                {(char*)dx_img, dx_scale, row_mul, rstd_max}, dy_absmax, {cu_groups, G}, {dgamma, dbeta, dbias, dgroup_bias}, W,
+                                p_drop, seed, keep, stream);
 }

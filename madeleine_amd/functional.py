@@ -726,19 +726,20 @@ class PreAttnBlockFn(torch.autograd.Function):
         dg, db = torch.empty_like(gamma), torch.empty_like(beta)
         dbias = torch.empty_like(lin_bias) if has_bias else None
         amax = _take_absmax(dy)
-        d_gbias = None
+        groups, d_gbias = (), None
         if ctx.groups is not None:
             cu_groups, G = ctx.groups
             d_gbias = torch.empty(G, N, device=dev, dtype=torch.float32)
-            ws = _ws_for("mdl_ln_gelu_drop_bwd_groups_ws_bytes", dev, T, N, G)
-            with _timed("ln_gelu_drop_bwd", ("byte", (3.0 if amax is not None else 4.0) * T * N * 4)):
-                _call("mdl_ln_gelu_drop_bwd_split_groups", y, lin_bias, gamma, beta, mean, rstd, dy, amax, dximg, dxscale, dg, db, dbias, T, N,
-                      p_drop, seed, keep, row_inv, rstd_max, cu_groups, G, d_gbias, ws, _stream())
-        else:
-            ws = _ws_for("mdl_ln_gelu_drop_bwd_ws_bytes", dev, T, N)
-            with _timed("ln_gelu_drop_bwd", ("byte", (3.0 if amax is not None else 4.0) * T * N * 4)):
-                _call("mdl_ln_gelu_drop_bwd_split", y, lin_bias, gamma, beta, mean, rstd, dy, amax, dximg, dxscale, dg, db, dbias, T, N,
-                      p_drop, seed, keep, row_inv, rstd_max, ws, _stream())
+            groups = (cu_groups, G, d_gbias)
+        ws = _ws_for("mdl_ln_gelu_drop_bwd%s_ws_bytes" % ("_groups" if groups else ""), dev, T, N, *groups[1:2])
+
+        def ln_bwd(passes, dximg, dxscale, dg, db, dbias, row_mul, rstd_max, *groups):
+            # d(pre-LN) as an image under (dxscale, row_mul), and the parameter gradients
+            with _timed("ln_gelu_drop_bwd", ("byte", passes * T * N * 4)):
+                _call("mdl_ln_gelu_drop_bwd_split" + ("_groups" if groups else ""), y, lin_bias, gamma, beta, mean, rstd, dy, amax, dximg,
+                      dxscale, dg, db, dbias, T, N, p_drop, seed, keep, row_mul, rstd_max, *groups, ws, _stream())
+
+        ln_bwd(3.0 if amax is not None else 4.0, dximg, dxscale, dg, db, dbias, row_inv, rstd_max, *groups)   # (4: its own pass over dy for max |dy|)
         dyi = SplitImage(dximg, dxscale, T, N)
         dx = None
         if ctx.needs_input_grad[0]:
@@ -751,9 +752,7 @@ class PreAttnBlockFn(torch.autograd.Function):
                 dximg2 = torch.empty(T + 32, N, device=dev, dtype=torch.float32)
                 dxscale2 = torch.empty(2, device=dev, dtype=torch.float32)
                 dg2, db2 = torch.empty_like(gamma), torch.empty_like(beta)
-                with _timed("ln_gelu_drop_bwd", ("byte", 3.0 * T * N * 4)):
-                    _call("mdl_ln_gelu_drop_bwd_split", y, lin_bias, gamma, beta, mean, rstd, dy, amax, dximg2, dxscale2, dg2, db2, None, T, N,
-                          p_drop, seed, keep, None, None, ws, _stream())   # (no row factors: its own pass over rstd)
+                ln_bwd(3.0, dximg2, dxscale2, dg2, db2, None, None, None)   # (no row factors: its own pass over rstd)
                 dxi = SplitImage(dximg2, dxscale2, T, N)
             dx = split_gemm_nt(dxi, weight_image(W.t().contiguous()), absmax_out=am, name="linear_bwd", terms=GRAD_TERMS)
             if x_is_image:       # the consumer is the previous block's LayerNorm backward (this node's input was its image)
@@ -1130,31 +1129,45 @@ def softmax_pool(E, scores, cu_seqlens=None, max_len=None):
 class LNGeluDropFn(torch.autograd.Function):
     """y = Dropout_p(GELU(LayerNorm(x + bias; gamma, beta, eps)))  over the last axis (Model.py:351-354).
     `bias` (optional) is the bias of the preceding Linear: the GEMM then runs bias-free and the bias gradient (column
-    sums of dx) comes out of the same backward pass instead of a separate reduction over dx."""
+    sums of dx) comes out of the same backward pass instead of a separate reduction over dx.
+    With `cu_groups` (int64 [G + 1]), `bias` is [G, W], one row per GROUP of rows (rows [cu_groups[g], cu_groups[g + 1]) take bias[g]):
+    the first block of the pre-attention MLP when the stain encoding is folded out of its Linear (Model.py:125-132, :351) on the bf16 /
+    exact-fp32 engines -- the split engine adds the row in its GEMM epilogue instead (PreAttnBlockFn).  The bias gradient is then the
+    per-group sums of dx."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps, p_drop, seed, keep, bias):
+    def forward(ctx, x, gamma, beta, eps, p_drop, seed, keep, bias, cu_groups):
         _require_act(x, "x")
         _require(gamma, "gamma")
         _require(beta, "beta")
-        if bias is not None:
-            _require(bias, "bias")
         W = x.shape[-1]
         rows = x.numel() // W
+        if cu_groups is None:
+            if bias is not None:
+                _require(bias, "bias")
+            name, groups, unsupported = "mdl_ln_gelu_drop_fwd", (), (_LN_WIDTHS, W)
+        else:
+            _require(bias, "group_bias")
+            _require(cu_groups, "cu_groups", torch.int64)
+            G = bias.shape[0]
+            if bias.shape != (G, W) or cu_groups.numel() != G + 1:
+                raise ValueError("group_bias must be [G, W] with cu_groups [G + 1]")
+            name, groups = "mdl_ln_gelu_drop_fwd_groups", (cu_groups, G)
+            unsupported = ("grouped LayerNorm-GELU-Dropout supports widths 256/512/1024 (got %d)", W)
         y = torch.empty_like(x)
         mean = torch.empty(rows, device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
         with _timed("ln_gelu_drop_fwd", ("byte", 2.0 * x.numel() * x.element_size())):
-            _call("mdl_ln_gelu_drop_fwd" + _sfx(x), x, bias, gamma, beta, y, mean, rstd, rows, W, float(eps), float(p_drop), int(seed), keep,
-                  _stream(), unsupported=(_LN_WIDTHS, W))
+            _call(name + _sfx(x), x, bias, gamma, beta, y, mean, rstd, rows, W, float(eps), float(p_drop), int(seed), keep, *groups, _stream(),
+                  unsupported=unsupported)
         ctx.save_for_backward(x, gamma, beta, mean, rstd, bias if bias is not None else torch.empty(0))
-        ctx.cfg = (float(p_drop), int(seed), keep, bias is not None)
+        ctx.cfg = (float(p_drop), int(seed), keep, bias is not None, groups)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, gamma, beta, mean, rstd, bias = ctx.saved_tensors
-        p_drop, seed, keep, has_bias = ctx.cfg
+        p_drop, seed, keep, has_bias, groups = ctx.cfg
         bias = bias if has_bias else None
         W = x.shape[-1]
         rows = x.numel() // W
@@ -1162,64 +1175,22 @@ class LNGeluDropFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         dg, db = torch.empty_like(gamma), torch.empty_like(beta)
         dbias = torch.empty_like(bias) if has_bias else None
-        ws = _ws_for("mdl_ln_gelu_drop_bwd_ws_bytes", x.device, rows, W)
+        g = "_groups" if groups else ""
+        ws = _ws_for("mdl_ln_gelu_drop_bwd%s_ws_bytes" % g, x.device, rows, W, *groups[1:])
         with _timed("ln_gelu_drop_bwd", ("byte", 3.0 * x.numel() * x.element_size())):
-            _call("mdl_ln_gelu_drop_bwd" + _sfx(x), x, bias, gamma, beta, mean, rstd, dy, dx, dg, db, dbias, rows, W, p_drop, seed, keep, ws,
-                  _stream())
-        return dx, dg, db, None, None, None, None, dbias
-
-
-class LNGeluDropGroupsFn(torch.autograd.Function):
-    """LNGeluDropFn with one bias row per GROUP of rows (rows [cu_groups[g], cu_groups[g + 1]) take group_bias[g]): the first block of
-    the pre-attention MLP when the stain encoding is folded out of its Linear (Model.py:125-132, :351) on the bf16 / exact-fp32 engines --
-    the split engine adds the row in its GEMM epilogue instead (PreAttnBlockFn).  The backward returns the per-group sums of dx."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, eps, p_drop, seed, keep, group_bias, cu_groups):
-        _require_act(x, "x")
-        _require(gamma, "gamma")
-        _require(beta, "beta")
-        _require(group_bias, "group_bias")
-        _require(cu_groups, "cu_groups", torch.int64)
-        W = x.shape[-1]
-        rows, G = x.numel() // W, group_bias.shape[0]
-        if group_bias.shape != (G, W) or cu_groups.numel() != G + 1:
-            raise ValueError("group_bias must be [G, W] with cu_groups [G + 1]")
-        y = torch.empty_like(x)
-        mean = torch.empty(rows, device=x.device, dtype=torch.float32)
-        rstd = torch.empty_like(mean)
-        with _timed("ln_gelu_drop_fwd", ("byte", 2.0 * x.numel() * x.element_size())):
-            _call("mdl_ln_gelu_drop_fwd_groups" + _sfx(x), x, group_bias, gamma, beta, y, mean, rstd, rows, W, float(eps), float(p_drop),
-                  int(seed), keep, cu_groups, G, _stream(),
-                  unsupported=("grouped LayerNorm-GELU-Dropout supports widths 256/512/1024 (got %d)", W))
-        ctx.save_for_backward(x, gamma, beta, mean, rstd, group_bias, cu_groups)
-        ctx.cfg = (float(p_drop), int(seed), keep)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, gamma, beta, mean, rstd, group_bias, cu_groups = ctx.saved_tensors
-        p_drop, seed, keep = ctx.cfg
-        W = x.shape[-1]
-        rows, G = x.numel() // W, group_bias.shape[0]
-        dy = dy.to(x.dtype).contiguous()
-        dx = torch.empty_like(x)
-        dg, db, dgb = torch.empty_like(gamma), torch.empty_like(beta), torch.empty_like(group_bias)
-        ws = _ws_for("mdl_ln_gelu_drop_bwd_groups_ws_bytes", x.device, rows, W, G)
-        with _timed("ln_gelu_drop_bwd", ("byte", 3.0 * x.numel() * x.element_size())):
-            _call("mdl_ln_gelu_drop_bwd_groups" + _sfx(x), x, group_bias, gamma, beta, mean, rstd, dy, dx, dg, db, dgb, rows, W, p_drop, seed,
-                  keep, cu_groups, G, ws, _stream())
-        return dx, dg, db, None, None, None, None, dgb, None
+            _call("mdl_ln_gelu_drop_bwd" + g + _sfx(x), x, bias, gamma, beta, mean, rstd, dy, dx, dg, db, dbias, rows, W, p_drop, seed, keep,
+                  *groups, ws, _stream())
+        return dx, dg, db, None, None, None, None, dbias, None
 
 
 def ln_gelu_drop_groups(x, gamma, beta, eps, p_drop, seed, keep, group_bias, cu_groups):
-    return LNGeluDropGroupsFn.apply(x.contiguous(), gamma.contiguous(), beta.contiguous(), eps, p_drop, seed, keep,
-                                    group_bias.float().contiguous(), cu_groups)
+    return LNGeluDropFn.apply(x.contiguous(), gamma.contiguous(), beta.contiguous(), eps, p_drop, seed, keep,
+                              group_bias.float().contiguous(), cu_groups)
 
 
 def ln_gelu_drop(x, gamma, beta, eps=1e-5, p_drop=0.0, seed=0, keep=None, bias=None):
     return LNGeluDropFn.apply(x.contiguous(), gamma.contiguous(), beta.contiguous(), eps, p_drop, seed, keep,
-                              None if bias is None else bias.contiguous())
+                              None if bias is None else bias.contiguous(), None)
 
 
 # --------------------------------------------------------------------------------------------------

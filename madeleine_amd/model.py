@@ -219,7 +219,7 @@ class ABMILEmbedder(nn.Module):
             if cu_groups is not None and Wfull.shape[0] in (256, 512, 1024) and e_rows.shape[0] <= 2048 \
                     and not os.environ.get("MADELEINE_STAIN_CONCAT"):      # (A/B switch: the round-5 concatenation)
                 # bf16 / exact-fp32 engines (round 6): the same fold with the bag's row as a per-group bias of the fused
-                # LayerNorm-GELU-Dropout pass (functional.LNGeluDropGroupsFn) -- their GEMM epilogues add no bias
+                # LayerNorm-GELU-Dropout pass (functional.ln_gelu_drop_groups) -- their GEMM epilogues add no bias
                 lowp = bf16_mode()          # (read before autocast is switched off for the kernels' own dtype handling)
                 with torch.autocast(device_type="cuda", enabled=False):
                     gb = MF.linear(e_rows.float(), Wfull[:, d_feat:].contiguous()) + pa[0].bias          # [G, 512]
