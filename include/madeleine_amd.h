@@ -894,6 +894,58 @@ int64_t mdl_probe_metrics_ws_bytes(int64_t P, int64_t S, int C);
 int mdl_probe_metrics(const float* z, const int32_t* y, int64_t ldy, const int32_t* train_idx, const int32_t* n_train, int64_t P,
                       int n_max, int64_t S, int C, int32_t* confusion_out, float* auc_out, void* ws, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * A-map -- the attention read-out: per bag and head the softmax of the raw scores with its statistics, an exact stable descending
+ * order, percentile ranks and the k best rows, for all bags of a pack in one launch sequence (ABI 26, additive).  Replaces, for the
+ * raw scores MADELEINE.forward(..., return_attention=True) returns (Model.py:205-216), the per-bag, per-head host loop of
+ * softmax / argsort / scipy.stats.rankdata(scores, 'average') / n * 100 that a heatmap is coloured by.
+ *
+ * scores [T, H] fp32, row stride ld >= H ELEMENTS; only read.  cu [R + 1] (int64, device): bag r is rows cu[r] .. cu[r + 1] - 1, n =
+ *   cu[r + 1] - cu[r] of them.  H in {1, 2, 4, 8}; T and R within int32.  A SEGMENT is one (bag, head) pair.
+ * ws: mdl_attn_map_ws_bytes(T, R, H) bytes for either call, 16-byte aligned, contents need no initialisation.
+ *
+ * mdl_attn_softmax: attn [T, H] (dense), m [R, H], l [R, H].  m is the exact maximum of the segment (fmaxf: a NaN is passed over
+ *   unless every score is one), l = sum expf(s - m), attn = expf(s - m) / l (one fp32 division).  An empty bag writes m = -inf, l = 0
+ *   and no attn.  A chunk is MDL_ATTN_ROWS consecutive rows of a segment and one workgroup of 256 threads: thread t adds its rows t,
+ *   t + 256, .. in row order, the 64 lanes of a wave are added by xor butterflies, the four waves as (0 + 1) + (2 + 3), and one thread
+ *   adds a segment's chunk partials in chunk order.  No atomics.  Addition depth: l of a segment of n rows has passed through at most
+ *       h(n) = (MDL_ATTN_ROWS / 256 - 1) + 6 + 2 + (ceil(n / MDL_ATTN_ROWS) - 1)
+ *   fp32 additions, each rounded once.
+ *   Bit contract: the bits of a segment's attn, m and l depend on its own scores only -- not on R, on the other bags or their
+ *   order, on where the bag lies in the pack or on ld.  Six launches.
+ *
+ * mdl_attn_rank: an exact, stable segmented sort of the raw scores.
+ *   Comparison rule: ordinary float order; -0.0 equals +0.0; every NaN ties with every other NaN and ranks above +inf.  The result
+ *   is therefore defined for any bit pattern.
+ *   order [H, T] (int32): order[h, cu[r] + j] is the row INSIDE bag r (0-based) of its j-th highest score in head h; ties are broken
+ *     by the lower row.
+ *   pct [T, H] (dense fp32) or NULL: with L the count of the segment's scores strictly below this one and E the count equal to it,
+ *     itself included, pct = (float)(100.0 * (2 L + E + 1) / (2.0 * n)), evaluated in double and rounded once: scipy's
+ *     rankdata(scores, 'average') / n * 100.
+ *   topk_idx [R, H, k] (int32), topk_val [R, H, k] (fp32), k >= 0 (both may be NULL for k == 0): the first min(k, n) entries of the
+ *     segment's order and their raw scores (bit for bit), padded with -1 and -inf.
+ *   An LSD radix sort on a 32-bit key (the usual float-to-unsigned transform after canonicalising -0 and NaN, inverted, so that the
+ *   ascending stable sort gives the descending order with ties in row order), 8-bit digits, four passes of three launches: per-chunk
+ *   digit counts (MDL_ATTN_SORT_KEYS keys per workgroup, a chunk never crosses a segment), a per-segment exclusive scan (digit-major,
+ *   chunk-minor), a stable scatter (one wave per chunk, 64 keys a round, the rank among equal digits from 64-bit ballot matches).
+ *   pct finds the run of equal keys by binary search in the sorted segment.  1 + 1 + 12 + (pct) 1 + (k > 0) 1 launches, whatever R
+ *   and T.  The results are exact, so they depend on the segment's scores alone.
+ *
+ * No workgroup waits on another (launch order is the only dependency), no float atomics, no library sort.
+ * Refusals, in this order.  MDL_E_ARG: scores / cu / ws or a required output NULL, T < 0, R < 0, ld < H, k < 0.  MDL_E_UNSUPPORTED:
+ * H outside {1, 2, 4, 8}, T or R beyond int32, a launch grid (T / MDL_ATTN_SORT_KEYS + R chunks, R * H segments, R * H * k / 256)
+ * beyond int32.  MDL_E_ALIGN: ws not 16-byte aligned, cu not 8-byte, a float / int32 buffer not 4-byte aligned.  R == 0 or T == 0:
+ * MDL_OK, nothing is launched and nothing written.
+ * With a cu that is not monotone or that leaves [0, T], nothing outside the given buffers is read or written: a bag with cu[r] < 0,
+ * cu[r + 1] < cu[r] or cu[r + 1] > T is served as an empty bag (and bags that overlap write each other's rows). */
+#define MDL_ATTN_ROWS 1024
+#define MDL_ATTN_SORT_KEYS 1024
+int64_t mdl_attn_map_ws_bytes(int64_t T, int64_t R, int H);
+int mdl_attn_softmax(const float* scores, int64_t ld, const int64_t* cu, int64_t T, int64_t R, int H, float* attn, float* m, float* l,
+                     void* ws, void* stream);
+int mdl_attn_rank(const float* scores, int64_t ld, const int64_t* cu, int64_t T, int64_t R, int H, int64_t k, int32_t* order, float* pct,
+                  int32_t* topk_idx, float* topk_val, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

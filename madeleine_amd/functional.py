@@ -1952,3 +1952,67 @@ def probe_metrics(z, y, train_idx, n_train, n_classes):
     with _timed("probe_metrics"):
         _call("mdl_probe_metrics", z, y, ldy, train_idx, n_train, P, n_max, S, C, confusion, auc, ws, _stream(), unsupported=refusal)
     return confusion, auc
+
+
+# ---- A-map: the attention read-out (mdl_attn_softmax / mdl_attn_rank).  Forward only, no autograd: raw scores are inputs ----
+ATTN_ROWS = _native._DEFINES["MDL_ATTN_ROWS"]
+ATTN_SORT_KEYS = _native._DEFINES["MDL_ATTN_SORT_KEYS"]
+_ATTN_LIMITS = "attention read-out supports 1, 2, 4 or 8 heads and T, R and its launch grids within int32 (got T %d, R %d, H %d, k %d)"
+
+
+def _attn_args(scores, cu, fn):
+    """(T, H, ld, R) of a read-out call: scores [T, H] fp32 on the device with unit column stride (any row stride), cu int64 [R + 1]."""
+    if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+        raise RuntimeError("madeleine_amd: %s needs scores [T, H] float32 with unit column stride" % fn)
+    if not scores.is_cuda:
+        raise RuntimeError("madeleine_amd: scores must live on a ROCm device (got %s); there is no CPU fallback" % scores.device)
+    _require(cu, "cu_seqlens", torch.int64)
+    if cu.dim() != 1 or cu.numel() < 1:
+        raise RuntimeError("madeleine_amd: cu_seqlens must be [R + 1]")
+    T, H = scores.shape
+    if H < 1:
+        raise RuntimeError("madeleine_amd: %s needs at least one head" % fn)
+    return T, H, (scores.stride(0) if T > 1 else H), cu.numel() - 1
+
+
+def attn_softmax(scores, cu):
+    """(attn [T, H], m [R, H], l [R, H]) of raw scores [T, H] (fp32, any row stride) over the bags of cu int64 [R + 1] on the device: per
+    bag and head the maximum, l = sum expf(s - m) and attn = expf(s - m) / l.  A bag's bits depend on its own scores alone (include/
+    madeleine_amd.h, A-map).  An empty bag has m = -inf, l = 0.  Six launches on the current stream, no host read."""
+    T, H, ld, R = _attn_args(scores, cu, "attn_softmax")
+    dev = scores.device
+    refusal = (_ATTN_LIMITS, T, R, H, 0)
+    attn = torch.empty(T, H, device=dev, dtype=torch.float32)
+    if R == 0 or T == 0:
+        return attn, torch.full((R, H), float("-inf"), device=dev), torch.zeros(R, H, device=dev)
+    m = torch.empty(R, H, device=dev, dtype=torch.float32)
+    l = torch.empty(R, H, device=dev, dtype=torch.float32)
+    ws = _ws_for("mdl_attn_map_ws_bytes", dev, T, R, H, refusal=refusal)
+    with _timed("attn_softmax", ("byte", 16.0 * T * H)):
+        _call("mdl_attn_softmax", scores, ld, cu, T, R, H, attn, m, l, ws, _stream(), unsupported=refusal)
+    return attn, m, l
+
+
+def attn_rank(scores, cu, k=0, percentile=True):
+    """(order [H, T] int32, pct [T, H] fp32 or None, topk_idx [R, H, k] int32 or None, topk_val [R, H, k] fp32 or None) of raw scores
+    [T, H] over the bags of cu: order[h, cu[r] + j] is the row inside bag r of its j-th highest score in head h (ties: the lower row
+    first; -0 == +0, NaNs equal and above +inf), pct the percentile rank rankdata(s, 'average') / n * 100 of every row, topk_* the
+    first min(k, n) entries of order with their raw scores, padded with -1 / -inf (None for k == 0).  Exact: an LSD radix sort on HIP
+    kernels, the same launches for any number of bags; no host read."""
+    T, H, ld, R = _attn_args(scores, cu, "attn_rank")
+    k = int(k)
+    if k < 0:
+        raise RuntimeError("madeleine_amd: attn_rank needs k >= 0 (got %d)" % k)
+    dev = scores.device
+    refusal = (_ATTN_LIMITS, T, R, H, k)
+    order = torch.empty(H, T, device=dev, dtype=torch.int32)
+    pct = torch.empty(T, H, device=dev, dtype=torch.float32) if percentile else None
+    if R == 0 or T == 0:      # nothing is launched: the padding of empty bags is written here
+        return order, pct, (torch.full((R, H, k), -1, device=dev, dtype=torch.int32) if k else None), \
+            (torch.full((R, H, k), float("-inf"), device=dev, dtype=torch.float32) if k else None)
+    ti = torch.empty(R, H, k, device=dev, dtype=torch.int32) if k else None
+    tv = torch.empty(R, H, k, device=dev, dtype=torch.float32) if k else None
+    ws = _ws_for("mdl_attn_map_ws_bytes", dev, T, R, H, refusal=refusal)
+    with _timed("attn_rank", ("byte", 40.0 * T * H)):
+        _call("mdl_attn_rank", scores, ld, cu, T, R, H, k, order, pct, ti, tv, ws, _stream(), unsupported=refusal)
+    return order, pct, ti, tv

@@ -548,6 +548,46 @@ class MADELEINE(nn.Module):
         pooled, _ = emb.pool_headmajor_ragged(E, cu_d.to(device), max(lens), e_img=e_img)
         return self._project_slide(pooled)
 
+    def attend_packed(self, packed, device, stain_idx=None):
+        """encode_packed with the attention kept: -> (embeds [R, 512], raw scores [T, H]), row t of `raw` the scores of packed token t in
+        every head, before the activation (what forward(..., return_attention=True) returns for a dense H&E batch, Model.py:205-216).
+        The kernels and their order are encode_packed's -- the bag-by-bag route for one bag and for the non-softmax activations
+        included -- so `embeds` is encode_packed's result.  With stain_encoding=True the eval branch's rule applies (Model.py:162-203):
+        every bag of the pack gets embedding(stain_idx), the TRUE stain index (default 0), not the train branch's r // B; it is folded
+        in through the per-group route of embed_tokens_headmajor (the engines that cannot fold it concatenate, as in training).
+        stain_idx on a model without stain encoding is ignored, as custom_stain_idx is in the reference.  functional.attn_softmax /
+        attn_rank turn `raw` into attention maps, percentile ranks and top-k patches."""
+        tokens, cu_d, lens = (packed.tokens, packed.cu_seqlens, packed.lens) if hasattr(packed, "tokens") else packed
+        lens = [int(n) for n in lens]
+        if tokens.dim() != 2 or not lens or min(lens) < 1 or tokens.shape[0] != sum(lens):
+            raise ValueError("attend_packed needs tokens [sum(lens), D] and at least one bag, every bag of at least one row")
+        tokens = tokens.to(device)
+        emb = self.wsi_embedders
+        R, H = len(lens), emb.n_heads
+        key = 0 if stain_idx is None else int(stain_idx)
+        if self.stain_encoding and not 0 <= key < len(self.modalities):
+            raise IndexError("attend_packed: stain_idx must be in [0, %d) (got %r)" % (len(self.modalities), stain_idx))
+        if self._encodes_bag_by_bag(R):
+            embeds, raws = [], []
+            for n, e in zip(lens, np.cumsum(lens).tolist()):
+                stain = self._stain_groups(torch.full((1,), key, dtype=torch.long), 1, n, device) if self.stain_encoding else None
+                pooled, _, scores = emb.forward_headmajor(tokens[e - n:e].unsqueeze(0), need_tokens=False, stain=stain)
+                embeds.append(self._project_slide(pooled))
+                raws.append(scores.reshape(n, H))
+            return torch.cat(embeds), torch.cat(raws)
+        if cu_d is None or cu_d.numel() != R + 1:
+            raise ValueError("attend_packed needs cu_seqlens [len(lens) + 1] on the device")
+        cu_d = cu_d.to(device)
+        stain = None
+        if self.stain_encoding:
+            row_bag = getattr(packed, "row_bag", None)
+            if row_bag is None:
+                row_bag = MF.h2d(torch.repeat_interleave(torch.arange(R, dtype=torch.int32), torch.tensor(lens)), device)
+            stain = (self.embedding(MF.h2d(torch.full((R,), key, dtype=torch.long), device)), row_bag.to(device), cu_d)
+        E, e_img = emb.embed_tokens_headmajor(tokens, return_image=True, want_fp32=False, stain=stain)
+        pooled, scores = emb.pool_headmajor_ragged(E, cu_d, max(lens), e_img=e_img)
+        return self._project_slide(pooled), scores.reshape(tokens.shape[0], H)
+
     def forward_ragged(self, bags, device, n_loss_tokens=None, n_views=1, modality_labels=None):
         """Variable-length bags (BASELINE config 5) -- NEW functionality: the reference can only torch.stack equal-N
         bags (wsi_dataset.py:89-92).  `bags` is a list over cases of lists over modalities of [N_bm, D] tensors.

@@ -5,6 +5,9 @@ same store by one launch of its variable-length form (pack / packed_batches: fun
 any dtype.  One vector per slide comes out of it too, for a downstream cohort: embed() runs the encoder over single-stain packs
 (pack_modality -> MADELEINE.encode_packed) and mean_embeddings() reduces whole bags to their column means where they lie
 (functional.bag_mean -> mdl_bag_mean); both feed probe.linear_probe without the features leaving the device.
+attention() is embed() with the attention kept (MADELEINE.attend_packed): raw scores, per-bag softmax, percentile ranks, order and
+top-k patches per head for the whole cohort, any stain (functional.attn_softmax / attn_rank -> mdl_attn_softmax / mdl_attn_rank,
+csrc/attn_map.hip).
 
 Replaces, for a cohort that fits in HBM, the reference's input side (madeleine/datasets/wsi_dataset.py): SlideDataset.__getitem__
 re-reads every stain's h5 file for every item of every epoch, draws `sample` rows on the host and collate stacks them, and the stacked
@@ -393,6 +396,25 @@ class DeviceSlideStore:
                              "got modality %r)" % (modality,))
         cases, _, lens = self._modality_plan(case_indices, modality, max_tokens)
         reduced = precision in (torch.bfloat16, torch.float16)
+        groups = self._launch_groups(cases, lens, bags_per_launch, reduced)
+        was_training = model.training
+        model.eval()
+        outs = []
+        try:
+            with torch.no_grad():
+                for group in groups:
+                    packed = self.pack_modality(group, modality, max_tokens, host_wgs=host_wgs)
+                    with torch.autocast(device_type="cuda", dtype=precision if reduced else None, enabled=reduced):
+                        outs.append(model.encode_packed(packed, self.device).float())
+        finally:
+            model.train(was_training)
+        embeds = torch.cat(outs) if outs else torch.zeros(0, 512, dtype=torch.float32, device=self.device)
+        return self._embedding_result(embeds, cases)
+
+    @staticmethod
+    def _launch_groups(cases, lens, bags_per_launch, reduced):
+        """embed's grouping (run_inference's): up to bags_per_launch bags per launch set (None: 4 in fp32, 1 under autocast), a bag of at
+        most 256 rows alone."""
         if bags_per_launch is None:
             bags_per_launch = 1 if reduced else 4
         groups, pending = [], []
@@ -409,19 +431,58 @@ class DeviceSlideStore:
                 pending = []
         if pending:
             groups.append(pending)
+        return groups
+
+    def attention(self, model, modality=0, case_indices=None, topk=0, percentile=True, bags_per_launch=None, precision=None,
+                  host_wgs=0) -> dict:
+        """The attention maps of one stain's bag of every case asked for (None: every case that has the stain), with the embeddings
+        they belong to: embed()'s planning, grouping, eval mode under torch.no_grad() (the training flag is restored) and autocast rule,
+        through model.attend_packed, whole bags only.  A model with stain encoding is given stain_idx=modality (the reference's eval
+        branch), so any stain works.  Returns, on the device unless said otherwise,
+          embeds [n, 512], cases (host), slide_ids      as embed()
+          cu_seqlens [n + 1] int64, lens (host list)    bag i of the result is rows cu_seqlens[i] .. cu_seqlens[i + 1] - 1 below
+          raw [T, H]                                    the scores before the activation; row j of a bag is row j of its stored bag
+                                                        (of its h5 `features` and `coords`)
+          attention [T, H]                              the softmax over the bag per head; for the relu, leaky_relu and sigmoid
+                                                        activations abmil.activate applied element-wise
+          percentile [T, H] or None                     rankdata(raw, 'average') / n * 100 per bag and head
+          order [H, T] int32                            order[h, cu_seqlens[i] + j]: the row of bag i with its j-th highest raw score
+          topk_idx, topk_val [n, H, topk] or None       the first topk of order and their raw scores, padded with -1 / -inf
+        Ranks and top-k are always of the raw scores.  The softmax, the ranks and the top-k of the whole result come from one launch
+        sequence each (functional.attn_softmax / attn_rank); the loop reads nothing back and the result does not depend on
+        bags_per_launch."""
+        from .abmil import activate
+        self._require_device("attention")
+        cases, _, lens = self._modality_plan(case_indices, modality)
+        reduced = precision in (torch.bfloat16, torch.float16)
+        groups = self._launch_groups(cases, lens, bags_per_launch, reduced)
+        stain_idx = modality if getattr(model, "stain_encoding", False) else None
         was_training = model.training
         model.eval()
-        outs = []
+        embeds, raws = [], []
         try:
             with torch.no_grad():
                 for group in groups:
-                    packed = self.pack_modality(group, modality, max_tokens, host_wgs=host_wgs)
+                    packed = self.pack_modality(group, modality, host_wgs=host_wgs)
                     with torch.autocast(device_type="cuda", dtype=precision if reduced else None, enabled=reduced):
-                        outs.append(model.encode_packed(packed, self.device).float())
+                        e, s = model.attend_packed(packed, self.device, stain_idx=stain_idx)
+                    embeds.append(e.float())
+                    raws.append(s.float())
         finally:
             model.train(was_training)
-        embeds = torch.cat(outs) if outs else torch.zeros(0, 512, dtype=torch.float32, device=self.device)
-        return self._embedding_result(embeds, cases)
+        H = model.wsi_embedders.n_heads
+        n = cases.numel()
+        cu = torch.zeros(n + 1, dtype=torch.int64)
+        torch.cumsum(lens, 0, out=cu[1:])
+        res = self._embedding_result(torch.cat(embeds) if embeds else torch.zeros(0, 512, dtype=torch.float32, device=self.device), cases)
+        raw = torch.cat(raws).contiguous() if raws else torch.zeros(0, H, dtype=torch.float32, device=self.device)
+        cu_d = MF.h2d(cu, self.device)
+        act = model.wsi_embedders.attn[0].activation
+        attention = MF.attn_softmax(raw, cu_d)[0] if act == 'softmax' else activate(raw, act)
+        order, pct, ti, tv = MF.attn_rank(raw, cu_d, k=topk, percentile=percentile)
+        res.update(cu_seqlens=cu_d, lens=lens.tolist(), raw=raw, attention=attention, percentile=pct, order=order, topk_idx=ti,
+                   topk_val=tv)
+        return res
 
     def packed_batches(self, batch_size, max_tokens=None, shuffle=True, drop_last=False, seed=0, rank=0, world_size=1, prefetch=None):
         """Re-iterable over {'packed': PackedBags, 'modality_labels', 'slide_ids'}: the ragged batches of ragged_batches() in packed
