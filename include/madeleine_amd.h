@@ -83,6 +83,12 @@ int mdl_abi_version(void);
  *          p_drop == 0 (module.eval()) => identity.
  * ws     workspace of mdl_abmil_gate_fwd_ws_bytes(T,H) bytes (K-major copy of the weights + score partials per
  *        128-wide j tile).
+ * Refusals of every gate entry point -- the forwards and backwards here, in the bf16 mode and on the split engine, mdl_abmil_attnpool_bwd
+ * (_phases) included -- come in one order: (1) MDL_E_ARG: a required pointer is NULL, one of act_a / act_b (forward) or of keep_a / keep_b
+ * is, the pooling term is incomplete, phases, terms, T < 0, H outside 1 .. MDL_MAX_HEADS, a stride below the row width or off its
+ * alignment, p_drop outside [0,1); (2) MDL_E_ALIGN: E, Wa, Wb, wc, act_a, act_b, dE or ws is not 16-byte aligned; (3) MDL_E_UNSUPPORTED:
+ * H not in {1,2,4,8}, a stride above its 32-bit limit; (4) a forward with T == 0 returns MDL_OK before any launch (an empty backward
+ * still zeroes its gradients); (5) MDL_E_UNSUPPORTED: a launch grid above 2^31 - 1.
  */
 int64_t mdl_abmil_gate_fwd_ws_bytes(int64_t T, int H);
 int mdl_abmil_gate_fwd(const float* E, int64_t ldE, const float* Wa, const float* ba, const float* Wb,
@@ -602,7 +608,7 @@ int mdl_ln_gelu_drop_bwd_split_groups(const float* x, const float* bias, const f
  * phases of mdl_abmil_attnpool_bwd_split (bit mask, 1 .. 15): 1 = the dz pass (+ bias / wc column sums), 2 = both contractions,
  * 4 = the dX contraction alone, 8 = the dW contraction alone (dWa, dWb) -- the two contractions only read what the dz pass wrote into
  * `ws`, so a caller may queue 8 on another stream behind an event recorded after 1 while 4 and the rest of the backward proceed
- * (measured null on MI355X; the Python mirror issues 3, functional.attnpool_bwd_split_raw(phases=...) issues any
+ * (measured null on MI355X; the Python mirror issues 3, functional.gate_bwd_raw(phases=...) issues any
  * sequence -- tests/test_split_gpu.py holds 1, 4, 8 == 3 bit for bit). */
 int64_t mdl_abmil_gate_fwd_split_ws_bytes(int64_t T, int H);
 int mdl_abmil_gate_fwd_split(const void* E_img, int64_t e_rsb, const float* e_scale, const float* Wa, const float* ba, const float* Wb,

@@ -17,6 +17,7 @@
 // software-pipelined one of tile_engine.hpp (fragment requests one step ahead, the chunk barrier before the last step, the
 // next DMA between that step's MFMAs), 3 workgroups per CU.
 #include "tile_engine.hpp"
+#include "gate_host.hpp"
 
 namespace mdl {
 
@@ -386,161 +387,111 @@ __global__ void gate_mask_kernel(uint8_t* __restrict__ keep, int64_t n, int whic
     }
 }
 
-static inline int64_t gate_tok_per_split(int64_t T, int S) {
-    int64_t tps = (T + S - 1) / S;
-    return ((tps + GBK - 1) / GBK) * GBK;
-}
-
+// ================================================================================================
+// host side (gate_host.hpp: the records, the checks, the dispatch and the phases of the backward)
+// ================================================================================================
 int gate_launch_finalize(const float* part, const float* bc, float* scores, int64_t n, int H, hipStream_t s) {
-    hipLaunchKernelGGL(gate_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, bc, scores, n, H);
-    MDL_LAUNCH_CHECK();
-    return MDL_OK;
+    return gate_launch(gate_finalize_kernel, dim3((unsigned)((n + 255) / 256)), 256, s, part, bc, scores, n, H);
 }
 int gate_launch_reduce_w(const float* slabW, float* dWa, float* dWb, int H, int S, hipStream_t s) {
-    hipLaunchKernelGGL(gate_reduce_w_kernel, dim3(32, 16, H), dim3(256), 0, s, slabW, dWa, dWb, H, S);
-    MDL_LAUNCH_CHECK();
-    return MDL_OK;
+    return gate_launch(gate_reduce_w_kernel, dim3(32, 16, H), 256, s, slabW, dWa, dWb, H, S);
 }
 int gate_launch_reduce_v(const float* slabV, float* dba, float* dbb, float* dwc, float* dbc, int H, int S, hipStream_t s) {
-    hipLaunchKernelGGL(gate_reduce_v_kernel, dim3((H * 4 * HID + 31) / 32), dim3(256), 0, s, slabV, dba, dbb, dwc, dbc, H, S);
-    MDL_LAUNCH_CHECK();
-    return MDL_OK;
+    return gate_launch(gate_reduce_v_kernel, dim3((H * 4 * HID + 31) / 32), 256, s, slabV, dba, dbb, dwc, dbc, H, S);
+}
+
+static GateFwdGeom fwd_geom(int64_t T, int H) { return gate_fwd_grid(T, H, GBM, 0, 1); }
+// dW: 4 k-tiles x 4 column tiles per head and split (gate_splits); an empty problem has splits of no tokens
+static GateBwdGeom bwd_geom(int64_t T, int H) {
+    GateBwdGeom g{};
+    g.S = gate_splits(T, H), g.chunk = g.pad = GBK, g.min_chunks = 0, g.dz_rows = DZ_ROWS;
+    g.dx_tile = GBM, g.dw_tile = 128, g.dw_per = 4 * GATE_JT;
+    return gate_bwd_grid(g, T, H);
+}
+static GateFwdWs fwd_ws(int64_t T, int H) { return gate_fwd_ws(T, H, 4, 0); }                      // WT [H][512][1024] fp32
+static GateBwdWs bwd_ws(int64_t T, int H) { return gate_bwd_ws(T, H, bwd_geom(T, H), 0, 4, 0); }   // no weight image: Wa, Wb are K-major
+static const GateEngine ENGINE = {
+    /*image*/ false, /*elem_bytes*/ 4, /*stride_unit*/ 4, /*head_units*/ HID,
+    {GBM - 1, 48},     // fwd: rows_voff: rr * ldE * 4 + kq * 16
+    {GBK - 1, 1020},   // bwd: gate_bwd_dw_kernel: r * ldE4 + colA, r < GBK, colA <= 31 * 16; gate_bwd_dx_kernel: rl * ld4 + lane_col * 4, rl < 4 (smaller)
+    /*max_phases*/ 3,
+    [](int64_t T, int H) { return fwd_geom(T, H).grid; },
+    [](int64_t T, int H, int phases) { return gate_bwd_max_grid(bwd_geom(T, H), H, phases); },
+};
+
+static int gate_fwd(const GateFwdCall& c) {
+    bool empty;
+    if (const int rc = gate_check_fwd(ENGINE, c, &empty)) return rc;
+    if (empty) return MDL_OK;
+    const int64_t T = c.pb.T;
+    const int H = c.pb.H;
+    const GateParams& p = c.par;
+    const DropCfg d = make_drop(c.drop);
+    const GateFwdGeom g = fwd_geom(T, H);
+    const GateFwdWs L = fwd_ws(T, H);
+    float* WT = (float*)((char*)c.ws + L.oW);
+    float* part = (float*)((char*)c.ws + L.opart);
+    if (const int rc = gate_launch(gate_wt_kernel, dim3(16, 32, H), 256, c.s, p.Wa, p.Wb, WT)) return rc;
+    const int rc = gate_pick_fwd(d, c.act.a != nullptr, [&](auto dm, auto save) {
+        return gate_launch(gate_fwd_kernel<decltype(dm)::value, decltype(save)::value != 0>, dim3((unsigned)g.grid), 256, c.s, c.src.p,
+                           c.src.ld, WT, p.ba, p.bb, p.wc, part, c.act.a, c.act.b, T, H, g.n_tt, d);
+    });
+    if (rc) return rc;
+    return gate_launch_finalize(part, p.bc, c.scores, T * H, H, c.s);
+}
+
+static int gate_bwd(const GateBwdCall& c) {
+    if (const int rc = gate_check_bwd(ENGINE, c)) return rc;
+    const int64_t T = c.pb.T;
+    const int H = c.pb.H;
+    const GateParams& p = c.par;
+    const DropCfg d = make_drop(c.drop);
+    const GateBwdGeom g = bwd_geom(T, H);
+    const GateBwdWs L = bwd_ws(T, H);
+    char* base = (char*)c.ws;
+    float* dz = (float*)(base + L.odz);
+    float* slabW = (float*)(base + L.oslabW);
+    float* slabV = (float*)(base + L.oslabV);
+    return gate_bwd_phases(
+        c, g, slabW, slabV, [&] { return gate_zero_pad_rows((char*)dz, T, H, g, 4, c.s); },
+        [&] {
+            return gate_pick_dm(d, [&](auto dm) {
+                return gate_launch(gate_dz_kernel<float, float, decltype(dm)::value>, dim3((unsigned)g.nblk), 64 * H, c.s, p.wc, c.act.a, c.act.b,
+                                   c.d_scores, dz, slabV, T, H, d);
+            });
+        },
+        [&] {
+            return gate_launch(gate_bwd_dx_kernel, dim3((unsigned)g.dx_grid), 256, c.s, dz, p.Wa, p.Wb, c.de.p, c.de.ld, c.de.accumulate, T, H,
+                               c.pt);
+        },
+        [&] { return gate_launch(gate_bwd_dw_kernel, dim3((unsigned)g.dw_grid), 256, c.s, c.src.p, c.src.ld, dz, slabW, T, H, g.tps, g.S); });
 }
 
 }  // namespace mdl
 
 using namespace mdl;
 
-extern "C" int64_t mdl_abmil_gate_fwd_ws_bytes(int64_t T, int H) {
-    if (T < 0 || H < 1 || H > MDL_MAX_HEADS) return MDL_E_ARG;
-    // WT [H][512][1024] (transposed weights) | score partials [T][H][4]
-    return ((int64_t)H * HID * 1024 + T * H * GATE_JT) * 4 + 64;
-}
+extern "C" int64_t mdl_abmil_gate_fwd_ws_bytes(int64_t T, int H) { return gate_ws_bytes(T, H, fwd_ws); }
 
 extern "C" int mdl_abmil_gate_fwd(const float* E, int64_t ldE, const float* Wa, const float* ba, const float* Wb,
                                   const float* bb, const float* wc, const float* bc, float* scores, float* act_a,
                                   float* act_b, int64_t T, int H, float p_drop, uint64_t seed, const uint8_t* keep_a,
                                   const uint8_t* keep_b, void* ws, void* stream) {
-    if (!E || !Wa || !ba || !Wb || !bb || !wc || !bc || !scores || !ws) return MDL_E_ARG;
-    if ((act_a == nullptr) != (act_b == nullptr)) return MDL_E_ARG;
-    if ((keep_a == nullptr) != (keep_b == nullptr)) return MDL_E_ARG;
-    if (T < 0 || H < 1 || H > MDL_MAX_HEADS || ldE < (int64_t)H * HID || (ldE & 3)) return MDL_E_ARG;
-    if (!(p_drop >= 0.f && p_drop < 1.f)) return MDL_E_ARG;
-    if (!host_aligned16(E) || !host_aligned16(Wa) || !host_aligned16(Wb) || !host_aligned16(ws)) return MDL_E_ALIGN;
-    if (!stride_fits32(ldE, 4, GBM - 1, 48)) return MDL_E_UNSUPPORTED;   // rows_voff: rr * ldE * 4 + kq * 16
-    if (T == 0) return MDL_OK;
-    const int64_t n_tt = (T + GBM - 1) / GBM;
-    if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
-    const int64_t grid = xcd_head_grid(n_tt, GATE_JT, H);
-    if (grid > 0x7fffffff) return MDL_E_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const DropCfg d = make_drop(p_drop, seed, keep_a, keep_b);
-    float* WT = (float*)ws;
-    float* part = WT + (int64_t)H * HID * 1024;
-    hipLaunchKernelGGL(gate_wt_kernel, dim3(16, 32, H), dim3(256), 0, s, Wa, Wb, WT);
-    MDL_LAUNCH_CHECK();
-    const int dm = gate_drop_mode(d);
-#define MDL_GATE_FWD(DM, SAVE)                                                                                                  \
-    hipLaunchKernelGGL((gate_fwd_kernel<DM, SAVE>), dim3((unsigned)grid), dim3(256), 0, s, E, ldE, (const float*)WT, ba, bb, wc, part, \
-                       act_a, act_b, T, H, (int)n_tt, d)
-    if (act_a) {
-        if (dm == 0) MDL_GATE_FWD(0, true);
-        else if (dm == 1) MDL_GATE_FWD(1, true);
-        else if (dm == 3) MDL_GATE_FWD(3, true);
-        else MDL_GATE_FWD(2, true);
-    } else {
-        if (dm == 0) MDL_GATE_FWD(0, false);
-        else if (dm == 1) MDL_GATE_FWD(1, false);
-        else if (dm == 3) MDL_GATE_FWD(3, false);
-        else MDL_GATE_FWD(2, false);
-    }
-#undef MDL_GATE_FWD
-    MDL_LAUNCH_CHECK();
-    const int64_t n = T * H;
-    hipLaunchKernelGGL(gate_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)part, bc, scores,
-                       n, H);
-    MDL_LAUNCH_CHECK();
-    return MDL_OK;
+    return gate_fwd({{E, ldE, nullptr}, {Wa, ba, Wb, bb, wc, bc}, scores, {act_a, act_b}, {p_drop, seed, keep_a, keep_b}, {T, H, 3, 3}, ws,
+                     (hipStream_t)stream});
 }
 
-static inline int64_t dz_blocks(int64_t T) { return (T + DZ_ROWS - 1) / DZ_ROWS; }
+extern "C" int64_t mdl_abmil_gate_bwd_ws_bytes(int64_t T, int H) { return gate_ws_bytes(T, H, bwd_ws); }
 
-extern "C" int64_t mdl_abmil_gate_bwd_ws_bytes(int64_t T, int H) {
-    if (T < 0 || H < 1 || H > MDL_MAX_HEADS) return MDL_E_ARG;
-    const int S = gate_splits(T, H);
-    // dz [(T + GBK)][H][1024] | slabW [S][H][512][1024] | slabV [dz_blocks][H][4][512]
-    return ((T + GBK) * H * 1024 + (int64_t)S * H * HID * 1024 + dz_blocks(T) * H * 4 * HID) * 4 + 64;
-}
-
-static int gate_bwd_impl(const float* E, int64_t ldE, const float* Wa, const float* Wb, const float* wc, const float* act_a,
-                         const float* act_b, const float* d_scores, float* dE, int accumulate, float* dWa, float* dWb, float* dba,
-                         float* dbb, float* dwc, float* dbc, int64_t T, int H, float p_drop, uint64_t seed, const uint8_t* keep_a,
-                         const uint8_t* keep_b, void* ws, void* stream, const PoolTerm& pt, int phases = 3) {
-    // phases: bit 0 = dz pass (HBM-bound) + its column-sum reduction, bit 1 = the dX / dW contractions (MFMA-bound) + slab reduction.
-    // The product path passes 3; the *_phases entry points let a profiler time the two halves separately on the same workspace.
-    if (!E || !Wa || !Wb || !wc || !act_a || !act_b || !d_scores || !dE || !dWa || !dWb || !dba || !dbb || !dwc || !ws)
-        return MDL_E_ARG;
-    if (phases < 1 || phases > 3) return MDL_E_ARG;
-    if ((keep_a == nullptr) != (keep_b == nullptr)) return MDL_E_ARG;
-    if (T < 0 || H < 1 || H > MDL_MAX_HEADS || ldE < (int64_t)H * HID || (ldE & 3)) return MDL_E_ARG;
-    if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
-    if (!(p_drop >= 0.f && p_drop < 1.f)) return MDL_E_ARG;
-    if (!host_aligned16(E) || !host_aligned16(Wa) || !host_aligned16(Wb) || !host_aligned16(act_a) ||
-        !host_aligned16(act_b) || !host_aligned16(wc) || !host_aligned16(ws))
-        return MDL_E_ALIGN;
-    // gate_bwd_dw_kernel: r * ldE4 + colA, r < GBK, colA <= 31 * 16; gate_bwd_dx_kernel: rl * ld4 + lane_col * 4, rl < 4 (the smaller bound)
-    if (!stride_fits32(ldE, 4, GBK - 1, 1020)) return MDL_E_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const DropCfg d = make_drop(p_drop, seed, keep_a, keep_b);
-    const int S = gate_splits(T, H);
-    const int64_t tps = gate_tok_per_split(T, S);
-    float* dz = (float*)ws;
-    float* slabW = dz + (T + GBK) * H * 1024;
-    float* slabV = slabW + (int64_t)S * H * HID * 1024;
-    const int64_t nblk = dz_blocks(T);
-    if (phases & 1) {
-        {   // zero pad rows of dz (K-tail of the dW GEMM)
-            const hipError_t e = hipMemsetAsync(dz + T * H * 1024, 0, (size_t)GBK * H * 1024 * sizeof(float), s);
-            if (e != hipSuccess) return (int)e;
-        }
-        if (T > 0) {
-            if (nblk * H > 0x7fffffff) return MDL_E_UNSUPPORTED;
-#define MDL_GATE_DZ(DM)                                                                                                              \
-    hipLaunchKernelGGL((gate_dz_kernel<float, float, DM>), dim3((unsigned)nblk), dim3(64 * H), 0, s, wc, act_a, act_b, d_scores, dz, slabV, \
-                       T, H, d)
-            MDL_DISPATCH_DM(gate_drop_mode(d), MDL_GATE_DZ);
-#undef MDL_GATE_DZ
-            MDL_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(gate_reduce_v_kernel, dim3((H * 4 * HID + 31) / 32), dim3(256), 0, s, (const float*)slabV, dba, dbb,
-                           dwc, dbc, H, (int)nblk);
-        MDL_LAUNCH_CHECK();
-    }
-    if (phases & 2) {
-        if (T > 0) {
-            const int64_t n_tt = (T + GBM - 1) / GBM;
-            const int64_t grid = xcd_head_grid(n_tt, 2, H);
-            if (grid > 0x7fffffff) return MDL_E_UNSUPPORTED;
-            hipLaunchKernelGGL(gate_bwd_dx_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const float*)dz, Wa, Wb, dE, ldE,
-                               accumulate, T, H, pt);
-            MDL_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(gate_bwd_dw_kernel, dim3((unsigned)xcd_head_grid(S, 4 * GATE_JT, H)), dim3(256), 0, s, E, ldE,
-                           (const float*)dz, slabW, T, H, tps, S);
-        MDL_LAUNCH_CHECK();
-        hipLaunchKernelGGL(gate_reduce_w_kernel, dim3(32, 16, H), dim3(256), 0, s, (const float*)slabW, dWa, dWb, H, S);
-        MDL_LAUNCH_CHECK();
-    }
-    return MDL_OK;
-}
-
+// phases: bit 0 = dz pass (HBM-bound) + its column-sum reduction, bit 1 = the dX / dW contractions (MFMA-bound) + slab reduction.
+// The product path runs 3; the *_phases entry points let a profiler time the two halves separately on the same workspace.
 extern "C" int mdl_abmil_gate_bwd(const float* E, int64_t ldE, const float* Wa, const float* Wb, const float* wc,
                                   const float* act_a, const float* act_b, const float* d_scores, float* dE,
                                   int accumulate, float* dWa, float* dWb, float* dba, float* dbb, float* dwc, float* dbc,
                                   int64_t T, int H, float p_drop, uint64_t seed, const uint8_t* keep_a,
                                   const uint8_t* keep_b, void* ws, void* stream) {
-    return gate_bwd_impl(E, ldE, Wa, Wb, wc, act_a, act_b, d_scores, dE, accumulate, dWa, dWb, dba, dbb, dwc, dbc, T, H, p_drop,
-                         seed, keep_a, keep_b, ws, stream, PoolTerm{nullptr, nullptr, nullptr, nullptr, nullptr, 1});
+    return gate_bwd(gate_bwd_call(E, ldE, Wa, Wb, wc, act_a, act_b, d_scores, dE, accumulate, dWa, dWb, dba, dbb, dwc, dbc, T, H, p_drop, seed,
+                                  keep_a, keep_b, ws, stream));
 }
 
 extern "C" int mdl_abmil_attnpool_bwd(const float* E, int64_t ldE, const float* Wa, const float* Wb, const float* wc,
@@ -549,9 +500,9 @@ extern "C" int mdl_abmil_attnpool_bwd(const float* E, int64_t ldE, const float* 
                                       float p_drop, uint64_t seed, const uint8_t* keep_a, const uint8_t* keep_b,
                                       const float* scores, const float* stat_m, const float* stat_l, const float* d_pooled,
                                       const int32_t* row_bag, int64_t N, void* ws, void* stream) {
-    if (!scores || !stat_m || !stat_l || !d_pooled || (!row_bag && N < 1)) return MDL_E_ARG;
-    return gate_bwd_impl(E, ldE, Wa, Wb, wc, act_a, act_b, d_scores, dE, accumulate, dWa, dWb, dba, dbb, dwc, dbc, T, H, p_drop, seed, keep_a,
-                         keep_b, ws, stream, PoolTerm{scores, stat_m, stat_l, d_pooled, row_bag, N});
+    return gate_bwd(with_pool(gate_bwd_call(E, ldE, Wa, Wb, wc, act_a, act_b, d_scores, dE, accumulate, dWa, dWb, dba, dbb, dwc, dbc, T, H,
+                                            p_drop, seed, keep_a, keep_b, ws, stream),
+                              {scores, stat_m, stat_l, d_pooled, row_bag, N}));
 }
 
 extern "C" int mdl_abmil_attnpool_bwd_phases(const float* E, int64_t ldE, const float* Wa, const float* Wb, const float* wc,
@@ -561,30 +512,28 @@ extern "C" int mdl_abmil_attnpool_bwd_phases(const float* E, int64_t ldE, const 
                                              const uint8_t* keep_b, const float* scores, const float* stat_m, const float* stat_l,
                                              const float* d_pooled, const int32_t* row_bag, int64_t N, void* ws, void* stream,
                                              int phases) {
-    if (!scores || !stat_m || !stat_l || !d_pooled || (!row_bag && N < 1)) return MDL_E_ARG;
-    return gate_bwd_impl(E, ldE, Wa, Wb, wc, act_a, act_b, d_scores, dE, accumulate, dWa, dWb, dba, dbb, dwc, dbc, T, H, p_drop, seed, keep_a,
-                         keep_b, ws, stream, PoolTerm{scores, stat_m, stat_l, d_pooled, row_bag, N}, phases);
+    return gate_bwd(with_pool(gate_bwd_call(E, ldE, Wa, Wb, wc, act_a, act_b, d_scores, dE, accumulate, dWa, dWb, dba, dbb, dwc, dbc, T, H,
+                                            p_drop, seed, keep_a, keep_b, ws, stream),
+                              {scores, stat_m, stat_l, d_pooled, row_bag, N}, phases));
 }
 
+// The masks the counter hash stands for (either field width), for a caller that wants them as bytes.  No head-count rule: the kernel is
+// elementwise.  Nothing to do for no elements.
 extern "C" int mdl_abmil_gate_dropout_mask(uint8_t* keep, int64_t T, int H, int which, float p_drop, uint64_t seed,
                                            void* stream) {
-    if (!keep || T < 0 || H < 1 || H > MDL_MAX_HEADS || (which != 0 && which != 1)) return MDL_E_ARG;
-    if (!(p_drop >= 0.f && p_drop < 1.f)) return MDL_E_ARG;
+    if (!keep || T < 0 || H < 1 || H > MDL_MAX_HEADS || (which != 0 && which != 1) || !(p_drop >= 0.f && p_drop < 1.f)) return MDL_E_ARG;
     const int64_t n = T * H * HID;
     if (n == 0) return MDL_OK;
     DropCfg d = make_drop(p_drop, seed, nullptr, nullptr);
     d.on = 1;   // (p = 0: threshold 0, every element kept)
-    hipLaunchKernelGGL(gate_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, keep, n, which, d);
-    MDL_LAUNCH_CHECK();
-    return MDL_OK;
+    return gate_launch(gate_mask_kernel, dim3((unsigned)((n + 255) / 256)), 256, (hipStream_t)stream, keep, n, which, d);
 }
 
 namespace mdl {
-// mdl_dispatch_plan (dispatch_plan.hip): the token splits of gate_bwd_impl's dW contraction
+// mdl_dispatch_plan (dispatch_plan.hip): the token splits of the backward's dW contraction
 int plan_gate_fp32_bwd(int64_t T, int H, int64_t* o) {
-    if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
-    const int S = gate_splits(T, H);
-    plan_splits(o, T, S, gate_tok_per_split(T, S), GBK);
+    if (!gate_heads_ok(H)) return MDL_E_UNSUPPORTED;
+    plan_splits(o, T, bwd_geom(T, H));
     return MDL_OK;
 }
 }  // namespace mdl

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "tile_engine_bf16.hpp"
+#include "gate_host.hpp"
 
 namespace mdl {
 
@@ -547,9 +548,6 @@ __global__ __launch_bounds__(256, 2) void gate_dw_bf16_kernel(const bf16_t* __re
         }
 }
 
-// ---- workspace layouts -------------------------------------------------------------------------------
-static inline int64_t up16(int64_t b) { return (b + 15) & ~(int64_t)15; }
-
 // dW on the 256 x 256 tile (round 5; tn256_mainloop, 64-token chunks): tile = 256 of the head's 512 E columns x 256 of its 1024 dz columns,
 // 8 tiles per head and split.  E rows past T - 1 re-read row T - 1: their dz rows are the zero pad (TQK rows).
 template <int NA>   // NA = 3: tn256_mainloop3 on SmemQ3
@@ -607,220 +605,137 @@ __global__ __launch_bounds__(512) void gate_dw256_bf16_kernel(const bf16_t* __re
             for (int ct = 0; ct < 2; ++ct) so[(int64_t)kr * 1024 + n0 + wn * 64 + ct * 32 + l32] = acc[rt][ct][r];
         }
 }
+
+// ================================================================================================
+// host side (gate_host.hpp: the records, the checks, the dispatch and the phases of the backward)
+// ================================================================================================
 // the forward on the 256 x 256 x 64 tile from 4096 tokens (MADELEINE_BF16_GATE128: the 128 x 256 tile throughout, A/B switch), and its
-// persistent workgroups (round 5, see gate_fwd256_bf16_kernel) for a grid of `grid_tiles` tile workgroups: MADELEINE_BF16_GATE_PERSIST =
-// 0 | 1 | 2 picks the mode (A/B switch), kept only where gate_persist_pays
+// persistent workgroups (round 5, see gate_fwd256_bf16_kernel): MADELEINE_BF16_GATE_PERSIST = 0 | 1 | 2 picks the mode (A/B switch), kept
+// only where gate_persist_pays
 static inline bool gate_fwd_use_q(int64_t T) { return T >= 4096 && !getenv("MADELEINE_BF16_GATE128"); }
-static inline int gate_fwd256_pmode(int64_t grid_tiles) {
+static inline int gate_fwd256_pmode(int64_t T, int H) {
     static const int pmode_env = getenv("MADELEINE_BF16_GATE_PERSIST") ? atoi(getenv("MADELEINE_BF16_GATE_PERSIST")) : MDL_GATE_BF16_PMODE;
-    int pmode = pmode_env;
-    if (pmode == 1 && !gate_persist_pays(grid_tiles, 0.93)) pmode = 0;
-    if (pmode == 2 && !gate_persist_pays(grid_tiles, 0.93, GATE_PT16)) pmode = 0;
-    return pmode;
+    return gate_pmode(pmode_env, T, H, QM, 0.93, GATE_PT16);
 }
-static inline bool gate_dx_use_q(int64_t T) { return T >= 4096; }
+static inline bool gate_dx_use_q(int64_t T) { return T >= 4096; }   // long contraction (K = 1024): the 256 x 256 x 64 tile
 static inline bool gate_dw_use_q(int64_t T) {
     static const bool off = getenv("MADELEINE_BF16_TN256") && atoi(getenv("MADELEINE_BF16_TN256")) == 0;   // A/B switch
     return !off && T >= 16384;
 }
 
-struct BwdWs {
-    int S;
-    int64_t tps, Tpad, nblk;
-    int64_t oWN, odz, oslabW, oslabV, total;  // byte offsets
-};
-static inline BwdWs bwd_ws(int64_t T, int H) {
-    BwdWs w;
+static GateFwdGeom fwd_geom(int64_t T, int H) {
+    const int pmode = gate_fwd256_pmode(T, H);
+    return gate_fwd_use_q(T) ? gate_fwd_grid(T, H, QM, pmode, GATE_PT16) : gate_fwd_grid(T, H, BBM, 0, 1);
+}
+static GateBwdGeom bwd_geom(int64_t T, int H) {
+    // gate_dw256_bf16_kernel: 8 tiles per head and split, one workgroup per CU; gate_dw_bf16_kernel: 16, 200 VGPRs = two workgroups per CU.
+    // A split is whole chunks of tokens: a chunk never straddles two splits.  The pad behind dz is TQK rows for either kernel.
     const bool q = gate_dw_use_q(T);
-    const int chunk = q ? TQK : TNK;
-    w.S = q ? splits_for(T, 8 * H, 256)     // gate_dw256_bf16_kernel: one workgroup per CU
-            : splits_for(T, 16 * H, 512);   // gate_dw_bf16_kernel: 200 VGPRs = two workgroups per CU
-    int64_t tps = (T + w.S - 1) / w.S;
-    w.tps = ((tps + chunk - 1) / chunk) * chunk;  // whole chunks of tokens: a chunk never straddles two splits
-    if (w.tps < chunk) w.tps = chunk;
-    w.Tpad = w.tps * w.S;
-    w.nblk = (T + DZ_ROWS - 1) / DZ_ROWS;
-    int64_t o = 0;
-    w.oWN = o; o += up16((int64_t)H * HID * 1024 * 2);
-    w.odz = o; o += up16((T + TQK) * H * 1024 * 2);   // + TQK zero rows: K-tail of the dW contraction
-    w.oslabW = o; o += up16((int64_t)w.S * H * HID * 1024 * 4);
-    w.oslabV = o; o += up16(w.nblk * H * 4 * HID * 4);
-    w.total = o + 64;
-    return w;
+    GateBwdGeom g{};
+    g.dw_tile = q ? 256 : 128, g.dw_per = q ? 8 : 16, g.chunk = q ? TQK : TNK, g.min_chunks = 1, g.pad = TQK;
+    g.S = q ? splits_for(T, 8 * H, 256) : splits_for(T, 16 * H, 512);
+    g.dz_rows = DZ_ROWS, g.dx_tile = gate_dx_use_q(T) ? QM : BBM;
+    return gate_bwd_grid(g, T, H);
+}
+static GateFwdWs fwd_ws(int64_t T, int H) { return gate_fwd_ws(T, H, 2, 0); }                      // WK [H][1024][512] bf16
+static GateBwdWs bwd_ws(int64_t T, int H) { return gate_bwd_ws(T, H, bwd_geom(T, H), 2, 2, 0); }   // WN and dz in bf16
+static const GateEngine ENGINE = {
+    /*image*/ false, /*elem_bytes*/ 2, /*stride_unit*/ 8, /*head_units*/ HID,
+    {QM - 1, 112},    // fwd: gate_fwd256_bf16_kernel: ra * ldE * 2 + ch * 16
+    {TQK - 1, 496},   // bwd: gate_dw256_bf16_kernel: k * ldA2 + cs, k < TQK, cs <= 31 * 16
+    /*max_phases*/ 3,
+    [](int64_t T, int H) { return gate_fwd_grid(T, H, BBM, 0, 1).grid; },   // the 128-row tiles: never fewer workgroups than the 256-row ones
+    [](int64_t T, int H, int phases) { return gate_bwd_max_grid(bwd_geom(T, H), H, phases); },
+};
+
+static int gate_fwd(const GateFwdCall& c) {
+    bool empty;
+    if (const int rc = gate_check_fwd(ENGINE, c, &empty)) return rc;
+    if (empty) return MDL_OK;
+    const int64_t T = c.pb.T;
+    const int H = c.pb.H;
+    const GateParams& p = c.par;
+    const DropCfg d = make_drop(c.drop);
+    const GateFwdGeom g = fwd_geom(T, H);
+    const GateFwdWs L = fwd_ws(T, H);
+    bf16_t* WK = (bf16_t*)((char*)c.ws + L.oW);
+    float* part = (float*)((char*)c.ws + L.opart);
+    if (const int rc = gate_launch(gate_wk_bf16_kernel, dim3((unsigned)((int64_t)H * 1024 * HID / 4 / 256)), 256, c.s, p.Wa, p.Wb, WK, H)) return rc;
+    const int rc = gate_pick_fwd(d, c.act.a != nullptr, [&](auto dm, auto save) {
+        constexpr int DM = decltype(dm)::value;
+        constexpr bool SAVE = decltype(save)::value != 0;
+        const auto launch = [&](auto kernel, int threads) {
+            return gate_launch(kernel, dim3((unsigned)g.grid), threads, c.s, c.src.p, c.src.ld, WK, p.ba, p.bb, p.wc, part, c.act.a, c.act.b, T, H,
+                               g.n_tt, d);
+        };
+        if (g.tile == BBM) return launch(gate_fwd_bf16_kernel<DM, SAVE>, 256);
+        return gate_pick<1, 2, 0>(g.pmode, [&](auto pm) { return launch(gate_fwd256_bf16_kernel<DM, SAVE, decltype(pm)::value>, 512); });
+    });
+    if (rc) return rc;
+    return gate_launch_finalize(part, p.bc, c.scores, T * H, H, c.s);
+}
+
+static int gate_bwd(const GateBwdCall& c) {
+    if (const int rc = gate_check_bwd(ENGINE, c)) return rc;
+    const int64_t T = c.pb.T;
+    const int H = c.pb.H;
+    const GateParams& p = c.par;
+    const DropCfg d = make_drop(c.drop);
+    const GateBwdGeom g = bwd_geom(T, H);
+    const GateBwdWs L = bwd_ws(T, H);
+    char* base = (char*)c.ws;
+    bf16_t* WN = (bf16_t*)(base + L.oWN);
+    bf16_t* dz = (bf16_t*)(base + L.odz);
+    float* slabW = (float*)(base + L.oslabW);
+    float* slabV = (float*)(base + L.oslabV);
+    const auto dx = [&](auto kernel, int threads) {
+        return gate_launch(kernel, dim3((unsigned)g.dx_grid), threads, c.s, dz, WN, c.de.p, c.de.ld, c.de.accumulate, T, H, c.pt);
+    };
+    const auto dw = [&](auto kernel, int threads) {
+        return gate_launch(kernel, dim3((unsigned)g.dw_grid), threads, c.s, c.src.p, c.src.ld, dz, slabW, T, H, g.tps, g.S);
+    };
+    return gate_bwd_phases(
+        c, g, slabW, slabV, [&] { return gate_zero_pad_rows((char*)dz, T, H, g, 2, c.s); },
+        [&] {
+            return gate_pick_dm(d, [&](auto dm) {
+                return gate_launch(gate_dz_kernel<bf16_t, bf16_t, decltype(dm)::value>, dim3((unsigned)g.nblk), 64 * H, c.s, p.wc, c.act.a, c.act.b,
+                                   c.d_scores, dz, slabV, T, H, d);
+            });
+        },
+        [&] {
+            if (const int rc = gate_launch(gate_wn_bf16_kernel, dim3(16, 32, H), 256, c.s, p.Wa, p.Wb, WN)) return rc;
+            if (g.dx_tile == BBM) return dx(gate_dx_bf16_kernel, 256);
+            return gate_pick<3, 2>(bf16_stages(), [&](auto na) { return dx(gate_dx256_bf16_kernel<decltype(na)::value>, 512); });
+        },
+        [&] {
+            if (g.dw_tile == 128) return dw(gate_dw_bf16_kernel, 256);
+            return gate_pick<3, 2>(bf16_stages(), [&](auto na) { return dw(gate_dw256_bf16_kernel<decltype(na)::value>, 512); });
+        });
 }
 
 }  // namespace mdl
 
 using namespace mdl;
 
-extern "C" int64_t mdl_abmil_gate_fwd_bf16_ws_bytes(int64_t T, int H) {
-    if (T < 0 || H < 1 || H > MDL_MAX_HEADS) return MDL_E_ARG;
-    // WK [H][1024][512] bf16 | score partials [T][H][4] fp32
-    return (int64_t)H * 1024 * HID * 2 + T * H * GATE_JT * 4 + 64;
-}
+extern "C" int64_t mdl_abmil_gate_fwd_bf16_ws_bytes(int64_t T, int H) { return gate_ws_bytes(T, H, fwd_ws); }
 
 extern "C" int mdl_abmil_gate_fwd_bf16(const uint16_t* E, int64_t ldE, const float* Wa, const float* ba, const float* Wb,
                                        const float* bb, const float* wc, const float* bc, float* scores, uint16_t* act_a,
                                        uint16_t* act_b, int64_t T, int H, float p_drop, uint64_t seed, const uint8_t* keep_a,
                                        const uint8_t* keep_b, void* ws, void* stream) {
-    if (!E || !Wa || !ba || !Wb || !bb || !wc || !bc || !scores || !ws) return MDL_E_ARG;
-    if ((act_a == nullptr) != (act_b == nullptr)) return MDL_E_ARG;
-    if ((keep_a == nullptr) != (keep_b == nullptr)) return MDL_E_ARG;
-    if (T < 0 || H < 1 || H > MDL_MAX_HEADS || ldE < (int64_t)H * HID || (ldE & 7)) return MDL_E_ARG;
-    if (!(p_drop >= 0.f && p_drop < 1.f)) return MDL_E_ARG;
-    if (!host_aligned16(E) || !host_aligned16(Wa) || !host_aligned16(Wb) || !host_aligned16(ws)) return MDL_E_ALIGN;
-    if (!stride_fits32(ldE, 2, QM - 1, 112)) return MDL_E_UNSUPPORTED;   // gate_fwd256_bf16_kernel: ra * ldE * 2 + ch * 16
-    if (T == 0) return MDL_OK;
-    if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
-    const int64_t n_tt = (T + BBM - 1) / BBM;
-    const int64_t grid = xcd_head_grid(n_tt, GATE_JT, H);
-    if (grid > 0x7fffffff) return MDL_E_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const DropCfg d = make_drop(p_drop, seed, keep_a, keep_b);
-    bf16_t* WK = (bf16_t*)ws;
-    float* part = (float*)((char*)ws + (int64_t)H * 1024 * HID * 2);
-    hipLaunchKernelGGL(gate_wk_bf16_kernel, dim3((unsigned)((int64_t)H * 1024 * HID / 4 / 256)), dim3(256), 0, s, Wa, Wb, WK, H);
-    MDL_LAUNCH_CHECK();
-    const int dm = gate_drop_mode(d);
-#define MDL_GATE_FWD16(DM, SAVE)                                                                                                   \
-    hipLaunchKernelGGL((gate_fwd_bf16_kernel<DM, SAVE>), dim3((unsigned)grid), dim3(256), 0, s, (const bf16_t*)E, ldE, (const bf16_t*)WK, \
-                       ba, bb, wc, part, (bf16_t*)act_a, (bf16_t*)act_b, T, H, (int)n_tt, d)
-    const int64_t n_tt256 = (T + QM - 1) / QM;
-    const int64_t grid_tiles = xcd_head_grid(n_tt256, GATE_JT, H);
-    const int pmode = gate_fwd256_pmode(grid_tiles);
-    const int64_t per_share = (n_tt256 + 8 / H - 1) / (8 / H);
-    const int64_t grid256 = pmode == 1 ? grid_tiles / GATE_JT : pmode == 2 ? 8 * ((per_share + GATE_PT16 - 1) / GATE_PT16) * GATE_JT : grid_tiles;
-#define MDL_GATE_FWD256_1(DM, SAVE, PM)                                                                                            \
-    hipLaunchKernelGGL((gate_fwd256_bf16_kernel<DM, SAVE, PM>), dim3((unsigned)grid256), dim3(512), 0, s, (const bf16_t*)E, ldE,   \
-                       (const bf16_t*)WK, ba, bb, wc, part, (bf16_t*)act_a, (bf16_t*)act_b, T, H, (int)n_tt256, d)
-#define MDL_GATE_FWD256(DM, SAVE)                                                                                                  \
-    do {                                                                                                                           \
-        if (pmode == 1) MDL_GATE_FWD256_1(DM, SAVE, 1);                                                                            \
-        else if (pmode == 2) MDL_GATE_FWD256_1(DM, SAVE, 2);                                                                       \
-        else MDL_GATE_FWD256_1(DM, SAVE, 0);                                                                                       \
-    } while (0)
-    if (gate_fwd_use_q(T)) {   // 256 x 256 x 64 tile
-        if (act_a) {
-            if (dm == 0) MDL_GATE_FWD256(0, true);
-            else if (dm == 1) MDL_GATE_FWD256(1, true);
-            else if (dm == 3) MDL_GATE_FWD256(3, true);
-            else MDL_GATE_FWD256(2, true);
-        } else {
-            if (dm == 0) MDL_GATE_FWD256(0, false);
-            else if (dm == 1) MDL_GATE_FWD256(1, false);
-            else if (dm == 3) MDL_GATE_FWD256(3, false);
-            else MDL_GATE_FWD256(2, false);
-        }
-    } else if (act_a) {
-        if (dm == 0) MDL_GATE_FWD16(0, true);
-        else if (dm == 1) MDL_GATE_FWD16(1, true);
-        else if (dm == 3) MDL_GATE_FWD16(3, true);
-        else MDL_GATE_FWD16(2, true);
-    } else {
-        if (dm == 0) MDL_GATE_FWD16(0, false);
-        else if (dm == 1) MDL_GATE_FWD16(1, false);
-        else if (dm == 3) MDL_GATE_FWD16(3, false);
-        else MDL_GATE_FWD16(2, false);
-    }
-#undef MDL_GATE_FWD256
-#undef MDL_GATE_FWD256_1
-#undef MDL_GATE_FWD16
-    MDL_LAUNCH_CHECK();
-    return gate_launch_finalize(part, bc, scores, T * H, H, s);
+    return gate_fwd({{E, ldE, nullptr}, {Wa, ba, Wb, bb, wc, bc}, scores, {act_a, act_b}, {p_drop, seed, keep_a, keep_b}, {T, H, 3, 3}, ws,
+                     (hipStream_t)stream});
 }
 
-extern "C" int64_t mdl_abmil_gate_bwd_bf16_ws_bytes(int64_t T, int H) {
-    if (T < 0 || H < 1 || H > MDL_MAX_HEADS) return MDL_E_ARG;
-    return bwd_ws(T, H).total;
-}
-
-static int gate_bwd_bf16_impl(const uint16_t* E, int64_t ldE, const float* Wa, const float* Wb, const float* wc,
-                              const uint16_t* act_a, const uint16_t* act_b, const float* d_scores, uint16_t* dE, int accumulate,
-                              float* dWa, float* dWb, float* dba, float* dbb, float* dwc, float* dbc, int64_t T, int H, float p_drop,
-                              uint64_t seed, const uint8_t* keep_a, const uint8_t* keep_b, void* ws, void* stream,
-                              const PoolTerm& pt, int phases = 3) {
-    if (!E || !Wa || !Wb || !wc || !act_a || !act_b || !d_scores || !dE || !dWa || !dWb || !dba || !dbb || !dwc || !ws)
-        return MDL_E_ARG;
-    if (phases < 1 || phases > 3) return MDL_E_ARG;   // bit 0: dz pass + its reduction, bit 1: dX / dW contractions (see abmil_gate.hip)
-    if ((keep_a == nullptr) != (keep_b == nullptr)) return MDL_E_ARG;
-    if (T < 0 || H < 1 || H > MDL_MAX_HEADS || ldE < (int64_t)H * HID || (ldE & 7)) return MDL_E_ARG;
-    if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
-    if (!(p_drop >= 0.f && p_drop < 1.f)) return MDL_E_ARG;
-    if (!host_aligned16(E) || !host_aligned16(dE) || !host_aligned16(Wa) || !host_aligned16(Wb) || !host_aligned16(act_a) ||
-        !host_aligned16(act_b) || !host_aligned16(wc) || !host_aligned16(ws))
-        return MDL_E_ALIGN;
-    if (!stride_fits32(ldE, 2, TQK - 1, 496)) return MDL_E_UNSUPPORTED;   // gate_dw256_bf16_kernel: k * ldA2 + cs, k < TQK, cs <= 31 * 16
-    hipStream_t s = (hipStream_t)stream;
-    const DropCfg d = make_drop(p_drop, seed, keep_a, keep_b);
-    const BwdWs L = bwd_ws(T, H);
-    char* base = (char*)ws;
-    bf16_t* WN = (bf16_t*)(base + L.oWN);
-    bf16_t* dz = (bf16_t*)(base + L.odz);
-    float* slabW = (float*)(base + L.oslabW);
-    float* slabV = (float*)(base + L.oslabV);
-    if (L.nblk * H > 0x7fffffff) return MDL_E_UNSUPPORTED;
-    if (phases & 1) {
-        {   // zero pad rows of dz (K-tail of the dW contraction)
-            const hipError_t e = hipMemsetAsync(dz + T * H * 1024, 0, (size_t)TQK * H * 1024 * 2, s);
-            if (e != hipSuccess) return (int)e;
-        }
-        if (T > 0) {
-#define MDL_GATE_DZ16(DM)                                                                                                            \
-    hipLaunchKernelGGL((gate_dz_kernel<bf16_t, bf16_t, DM>), dim3((unsigned)L.nblk), dim3(64 * H), 0, s, wc, (const bf16_t*)act_a,        \
-                       (const bf16_t*)act_b, d_scores, dz, slabV, T, H, d)
-            MDL_DISPATCH_DM(gate_drop_mode(d), MDL_GATE_DZ16);
-#undef MDL_GATE_DZ16
-            MDL_LAUNCH_CHECK();
-        }
-        const int rc = gate_launch_reduce_v(slabV, dba, dbb, dwc, dbc, H, (int)L.nblk, s);
-        if (rc) return rc;
-    }
-    if (phases & 2) {
-        if (T > 0) {
-            hipLaunchKernelGGL(gate_wn_bf16_kernel, dim3(16, 32, H), dim3(256), 0, s, Wa, Wb, WN);
-            MDL_LAUNCH_CHECK();
-            if (gate_dx_use_q(T)) {   // long contraction (K = 1024): the 256 x 256 x 64 tile (measured: 1.58 -> see DESIGN.md)
-                const int64_t n_tt = (T + QM - 1) / QM;
-                const int64_t grid = xcd_head_grid(n_tt, 2, H);
-                if (grid > 0x7fffffff) return MDL_E_UNSUPPORTED;
-                if (bf16_stages() == 3)
-                    hipLaunchKernelGGL(gate_dx256_bf16_kernel<3>, dim3((unsigned)grid), dim3(512), 0, s, (const bf16_t*)dz, (const bf16_t*)WN,
-                                       (bf16_t*)dE, ldE, accumulate, T, H, pt);
-                else
-                    hipLaunchKernelGGL(gate_dx256_bf16_kernel<2>, dim3((unsigned)grid), dim3(512), 0, s, (const bf16_t*)dz, (const bf16_t*)WN,
-                                       (bf16_t*)dE, ldE, accumulate, T, H, pt);
-            } else {
-                const int64_t n_tt = (T + BBM - 1) / BBM;
-                const int64_t grid = xcd_head_grid(n_tt, 2, H);
-                if (grid > 0x7fffffff) return MDL_E_UNSUPPORTED;
-                hipLaunchKernelGGL(gate_dx_bf16_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const bf16_t*)dz, (const bf16_t*)WN,
-                                   (bf16_t*)dE, ldE, accumulate, T, H, pt);
-            }
-            MDL_LAUNCH_CHECK();
-        }
-        if (gate_dw_use_q(T) && bf16_stages() == 3)
-            hipLaunchKernelGGL(gate_dw256_bf16_kernel<3>, dim3((unsigned)xcd_head_grid(L.S, 8, H)), dim3(512), 0, s, (const bf16_t*)E, ldE,
-                               (const bf16_t*)dz, slabW, T, H, L.tps, L.S);
-        else if (gate_dw_use_q(T))
-            hipLaunchKernelGGL(gate_dw256_bf16_kernel<2>, dim3((unsigned)xcd_head_grid(L.S, 8, H)), dim3(512), 0, s, (const bf16_t*)E, ldE,
-                               (const bf16_t*)dz, slabW, T, H, L.tps, L.S);
-        else
-        hipLaunchKernelGGL(gate_dw_bf16_kernel, dim3((unsigned)xcd_head_grid(L.S, 16, H)), dim3(256), 0, s, (const bf16_t*)E, ldE,
-                           (const bf16_t*)dz, slabW, T, H, L.tps, L.S);
-        MDL_LAUNCH_CHECK();
-        const int rc = gate_launch_reduce_w(slabW, dWa, dWb, H, L.S, s);
-        if (rc) return rc;
-    }
-    return MDL_OK;
-}
+extern "C" int64_t mdl_abmil_gate_bwd_bf16_ws_bytes(int64_t T, int H) { return gate_ws_bytes(T, H, bwd_ws); }
 
 extern "C" int mdl_abmil_gate_bwd_bf16(const uint16_t* E, int64_t ldE, const float* Wa, const float* Wb, const float* wc,
                                        const uint16_t* act_a, const uint16_t* act_b, const float* d_scores, uint16_t* dE,
                                        int accumulate, float* dWa, float* dWb, float* dba, float* dbb, float* dwc, float* dbc,
                                        int64_t T, int H, float p_drop, uint64_t seed, const uint8_t* keep_a,
                                        const uint8_t* keep_b, void* ws, void* stream) {
-    return gate_bwd_bf16_impl(E, ldE, Wa, Wb, wc, act_a, act_b, d_scores, dE, accumulate, dWa, dWb, dba, dbb, dwc, dbc, T, H, p_drop,
-                              seed, keep_a, keep_b, ws, stream, PoolTerm{nullptr, nullptr, nullptr, nullptr, nullptr, 1});
+    return gate_bwd(gate_bwd_call(E, ldE, Wa, Wb, wc, act_a, act_b, d_scores, dE, accumulate, dWa, dWb, dba, dbb, dwc, dbc, T, H, p_drop, seed,
+                                  keep_a, keep_b, ws, stream));
 }
 
 extern "C" int mdl_abmil_attnpool_bwd_bf16(const uint16_t* E, int64_t ldE, const float* Wa, const float* Wb, const float* wc,
@@ -829,9 +744,9 @@ extern "C" int mdl_abmil_attnpool_bwd_bf16(const uint16_t* E, int64_t ldE, const
                                            int64_t T, int H, float p_drop, uint64_t seed, const uint8_t* keep_a, const uint8_t* keep_b,
                                            const float* scores, const float* stat_m, const float* stat_l, const float* d_pooled,
                                            const int32_t* row_bag, int64_t N, void* ws, void* stream) {
-    if (!scores || !stat_m || !stat_l || !d_pooled || (!row_bag && N < 1)) return MDL_E_ARG;
-    return gate_bwd_bf16_impl(E, ldE, Wa, Wb, wc, act_a, act_b, d_scores, dE, accumulate, dWa, dWb, dba, dbb, dwc, dbc, T, H, p_drop, seed,
-                              keep_a, keep_b, ws, stream, PoolTerm{scores, stat_m, stat_l, d_pooled, row_bag, N});
+    return gate_bwd(with_pool(gate_bwd_call(E, ldE, Wa, Wb, wc, act_a, act_b, d_scores, dE, accumulate, dWa, dWb, dba, dbb, dwc, dbc, T, H,
+                                            p_drop, seed, keep_a, keep_b, ws, stream),
+                              {scores, stat_m, stat_l, d_pooled, row_bag, N}));
 }
 
 extern "C" int mdl_abmil_attnpool_bwd_phases_bf16(const uint16_t* E, int64_t ldE, const float* Wa, const float* Wb, const float* wc,
@@ -841,28 +756,27 @@ extern "C" int mdl_abmil_attnpool_bwd_phases_bf16(const uint16_t* E, int64_t ldE
                                                   const uint8_t* keep_b, const float* scores, const float* stat_m,
                                                   const float* stat_l, const float* d_pooled, const int32_t* row_bag, int64_t N,
                                                   void* ws, void* stream, int phases) {
-    if (!scores || !stat_m || !stat_l || !d_pooled || (!row_bag && N < 1)) return MDL_E_ARG;
-    return gate_bwd_bf16_impl(E, ldE, Wa, Wb, wc, act_a, act_b, d_scores, dE, accumulate, dWa, dWb, dba, dbb, dwc, dbc, T, H, p_drop, seed,
-                              keep_a, keep_b, ws, stream, PoolTerm{scores, stat_m, stat_l, d_pooled, row_bag, N}, phases);
+    return gate_bwd(with_pool(gate_bwd_call(E, ldE, Wa, Wb, wc, act_a, act_b, d_scores, dE, accumulate, dWa, dWb, dba, dbb, dwc, dbc, T, H,
+                                            p_drop, seed, keep_a, keep_b, ws, stream),
+                              {scores, stat_m, stat_l, d_pooled, row_bag, N}, phases));
 }
 
 namespace mdl {
-// mdl_dispatch_plan (dispatch_plan.hip): the forward's tile and persistence mode (mdl_abmil_gate_fwd_bf16), the backward's dX / dW tiles
-// and the token splits of its dW contraction (mdl_abmil_gate_bwd_bf16)
+// mdl_dispatch_plan (dispatch_plan.hip): the forward's tile and persistence mode, the backward's dX / dW tiles and the token splits of
+// its dW contraction
 int plan_gate_bf16(int product, int64_t T, int H, int64_t* o) {
-    if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
+    if (!gate_heads_ok(H)) return MDL_E_UNSUPPORTED;
     if (product == MDL_PLAN_GATE_BF16_FWD) {
-        const bool q = gate_fwd_use_q(T);
-        o[MDL_PLAN_VARIANT] = q ? QM : BBM;
-        o[MDL_PLAN_PERSIST] = q ? gate_fwd256_pmode(xcd_head_grid((T + QM - 1) / QM, GATE_JT, H)) : 0;
+        const GateFwdGeom g = fwd_geom(T, H);
+        o[MDL_PLAN_VARIANT] = g.tile;
+        o[MDL_PLAN_PERSIST] = g.pmode;
         o[MDL_PLAN_SPLITS] = 1;
         return MDL_OK;
     }
-    const BwdWs L = bwd_ws(T, H);
-    const bool q = gate_dw_use_q(T);
-    o[MDL_PLAN_VARIANT] = q ? 256 : 128;
-    o[MDL_PLAN_EXTRA] = gate_dx_use_q(T) ? QM : BBM;
-    plan_splits(o, T, L.S, L.tps, q ? TQK : TNK);
+    const GateBwdGeom g = bwd_geom(T, H);
+    o[MDL_PLAN_VARIANT] = g.dw_tile;
+    o[MDL_PLAN_EXTRA] = g.dx_tile;
+    plan_splits(o, T, g);
     return MDL_OK;
 }
 }  // namespace mdl

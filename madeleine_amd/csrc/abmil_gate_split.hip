@@ -8,6 +8,7 @@
 //   dX      : A = image(dz) rows (t, c) (K = 1024)       B = image([Wa;Wb]^T) rows e              dE (+)= . + pooling term
 //   dW      : TN over tokens: A = image(E) head columns, B = image(dz) head columns              slabs -> gate_reduce_w
 #include "split_engine.hpp"
+#include "gate_host.hpp"
 
 namespace mdl {
 
@@ -438,58 +439,138 @@ __global__ __launch_bounds__(SP_THREADS) void sp_gate_dw_kernel(const char* __re
     sp_epilogue_rows<true>(acc, sm, wave, wm, wn, lane, SPM, emit);
 }
 
+// ================================================================================================
+// host side (gate_host.hpp: the records, the checks, the dispatch and the phases of the backward)
+// ================================================================================================
 // split_gemm.hip
 int sp_launch_absmax(const float* X, int64_t ldx, int64_t rows, int K, float* out, hipStream_t s);
 int sp_launch_absmax_flat(const float* x, int64_t n, float* out, hipStream_t s);
 int sp_launch_scale(float* sc, hipStream_t s);
 
-static inline int64_t up16s(int64_t b) { return (b + 15) & ~(int64_t)15; }
 // token rows per workgroup of the dz pass: a workgroup walks its rows two at a time (~1.3 us per pair of rows, latency), so 256 rows
 // only pay when there are thousands of workgroups to overlap them; a 2,048-token step (config 1) spent 340 us in 8 workgroups
 #ifndef MDL_DZ_ROWS_BIG
 #define MDL_DZ_ROWS_BIG DZ_ROWS
 #endif
 static inline int sp_dz_rows(int64_t T) { return T >= 131072 ? MDL_DZ_ROWS_BIG : (T >= 16384 ? 64 : 16); }
-struct SpBwdWs {
-    int S;
-    int64_t tps, nblk;
-    int64_t oWN, odz, oslabW, oslabV, osc, total;
-};
-// persistent workgroups of the forward (round 5, see sp_gate_fwd_kernel) for a grid of `grid` tile workgroups: MADELEINE_GATE_PERSIST =
-// 0 | 1 | 2 picks the mode (A/B switch), kept only where gate_persist_pays
-static inline int sp_gate_fwd_pmode(int64_t grid) {
+// persistent workgroups of the forward (round 5, see sp_gate_fwd_kernel): MADELEINE_GATE_PERSIST = 0 | 1 | 2 picks the mode (A/B switch),
+// kept only where gate_persist_pays
+static inline int sp_gate_fwd_pmode(int64_t T, int H) {
     static const int pmode_env = getenv("MADELEINE_GATE_PERSIST") ? atoi(getenv("MADELEINE_GATE_PERSIST")) : MDL_GATE_SP_PMODE;
-    int pmode = pmode_env;
-    if (pmode == 1 && !gate_persist_pays(grid, 0.96)) pmode = 0;
-    if (pmode == 2 && !gate_persist_pays(grid, 0.96, GATE_PT)) pmode = 0;
-    return pmode;
+    return gate_pmode(pmode_env, T, H, SPM, 0.96, GATE_PT);
 }
-static inline SpBwdWs sp_bwd_ws(int64_t T, int H) {
-    SpBwdWs w;
-    w.S = splits_for(T, 8 * H, 256);   // 2 x 4 tiles per head and split; one workgroup per CU
-    int64_t tps = (T + w.S - 1) / w.S;
-    w.tps = ((tps + SPK - 1) / SPK) * SPK;
-    if (w.tps < SPK) w.tps = SPK;
-    w.nblk = (T + sp_dz_rows(T) - 1) / sp_dz_rows(T);
-    int64_t o = 0;
-    w.oWN = o; o += up16s((int64_t)H * HID * 1024 * 4);
-    w.odz = o; o += up16s((T + SPK) * H * 1024 * 4);       // + 32 zero rows: token tail of the dW contraction
-    w.oslabW = o; o += up16s((int64_t)w.S * H * HID * 1024 * 4);
-    w.oslabV = o; o += up16s(w.nblk * H * 4 * HID * 4);
-    w.osc = o; o += 64;                                      // floats: [0,1] W scale / absmax | [2,3] max|ds|, max|wc| | [4,5] dz scale / bound
-    w.total = o + 64;
-    return w;
+
+static GateFwdGeom fwd_geom(int64_t T, int H) { return gate_fwd_grid(T, H, SPM, sp_gate_fwd_pmode(T, H), GATE_PT); }
+// dW: 2 x 4 tiles per head and split, one workgroup per CU; + SPK zero rows behind dz
+static GateBwdGeom bwd_geom(int64_t T, int H) {
+    GateBwdGeom g{};
+    g.S = splits_for(T, 8 * H, 256), g.chunk = g.pad = SPK, g.min_chunks = 1, g.dz_rows = sp_dz_rows(T);
+    g.dx_tile = SPM, g.dw_tile = 256, g.dw_per = 8;
+    return gate_bwd_grid(g, T, H);
+}
+// scale floats: [0,1] W scale / absmax | [2,3] max|ds|, max|wc| | [4,5] dz scale / bound
+static GateFwdWs fwd_ws(int64_t T, int H) { return gate_fwd_ws(T, H, 4, 64); }                      // WK image [H][1024][512]
+static GateBwdWs bwd_ws(int64_t T, int H) { return gate_bwd_ws(T, H, bwd_geom(T, H), 4, 4, 64); }   // WN and dz as images
+static const GateEngine ENGINE = {
+    /*image*/ true, /*elem_bytes*/ 1, /*stride_unit*/ 16, /*head_units*/ HID * 4,
+    {SPM, 0},   // fwd: ra * e_rsb + ch * 16, ra < SPM, ch * 16 < e_rsb
+    {SPK, 0},   // bwd: the dW kernel's tk * e_rsb + coA, tk < SPK, coA < e_rsb
+    /*max_phases*/ 15,
+    [](int64_t T, int H) { return gate_fwd_grid(T, H, SPM, 0, 1).grid; },   // a workgroup per tile: never fewer than the persistent grids
+    [](int64_t T, int H, int phases) { return gate_bwd_max_grid(bwd_geom(T, H), H, phases); },
+};
+
+// the weights' scale from their exact absmax: sc[1] = max |Wa|, |Wb| -> sc[0] (sc zeroed by the caller)
+static int sp_weight_scale(const GateParams& p, int H, float* sc, hipStream_t s) {
+    if (const int rc = sp_launch_absmax(p.Wa, HID, (int64_t)H * HID, HID, sc + 1, s)) return rc;
+    if (const int rc = sp_launch_absmax(p.Wb, HID, (int64_t)H * HID, HID, sc + 1, s)) return rc;
+    return sp_launch_scale(sc, s);
+}
+
+static int gate_fwd(const GateFwdCall& c) {
+    bool empty;
+    if (const int rc = gate_check_fwd(ENGINE, c, &empty)) return rc;
+    if (empty) return MDL_OK;
+    const int64_t T = c.pb.T;
+    const int H = c.pb.H;
+    const GateParams& p = c.par;
+    const DropCfg d = make_drop(c.drop);
+    const GateFwdGeom g = fwd_geom(T, H);
+    const GateFwdWs L = fwd_ws(T, H);
+    char* WK = (char*)c.ws + L.oW;
+    float* part = (float*)((char*)c.ws + L.opart);
+    float* sc = (float*)((char*)c.ws + L.osc);
+    if (const int rc = (int)hipMemsetAsync(sc, 0, 2 * sizeof(float), c.s)) return rc;
+    if (const int rc = sp_weight_scale(p, H, sc, c.s)) return rc;
+    if (const int rc = gate_launch(sp_gate_wk_kernel, dim3((unsigned)((int64_t)H * 1024 * 64 / 256)), 256, c.s, p.Wa, p.Wb, WK, H, sc)) return rc;
+    // <PMODE, NA>: the persistent modes exist with two stages only, the three-stage ring (sp_nt_mainloop3, MADELEINE_SP_NT_STAGES) with
+    // one tile per workgroup only
+    const int variant = g.pmode ? g.pmode : (sp_nt_stages() == 3 ? 3 : 0);
+    const int rc = gate_pick_fwd(d, c.act.a != nullptr, [&](auto dm, auto save) {
+        return gate_pick<1, 2, 3, 0>(variant, [&](auto v) {
+            constexpr int PM = decltype(v)::value == 3 ? 0 : decltype(v)::value, NA = decltype(v)::value == 3 ? 3 : 2;
+            return gate_launch(sp_gate_fwd_kernel<decltype(dm)::value, decltype(save)::value != 0, PM, NA>, dim3((unsigned)g.grid), SP_THREADS,
+                               c.s, c.src.p, c.src.ld, c.src.scale, WK, sc, p.ba, p.bb, p.wc, part, c.act.a, c.act.b, T, H, g.n_tt, d);
+        });
+    });
+    if (rc) return rc;
+    return gate_launch_finalize(part, p.bc, c.scores, T * H, H, c.s);
+}
+
+static int gate_bwd(const GateBwdCall& c) {
+    if (const int rc = gate_check_bwd(ENGINE, c)) return rc;
+    const int64_t T = c.pb.T;
+    const int H = c.pb.H;
+    const GateParams& p = c.par;
+    const DropCfg d = make_drop(c.drop);
+    const GateBwdGeom g = bwd_geom(T, H);
+    const GateBwdWs L = bwd_ws(T, H);
+    char* base = (char*)c.ws;
+    char* WN = base + L.oWN;
+    char* dzi = base + L.odz;
+    float* slabW = (float*)(base + L.oslabW);
+    float* slabV = (float*)(base + L.oslabV);
+    float* sc = (float*)(base + L.osc);
+    return gate_bwd_phases(
+        c, g, slabW, slabV,
+        [&] {   // scales: weights from their exact absmax; dz from the bound |dz| <= max|ds| max|wc| / (1-p)^2
+            if (const int rc = (int)hipMemsetAsync(sc, 0, 8 * sizeof(float), c.s)) return rc;
+            if (const int rc = gate_zero_pad_rows(dzi, T, H, g, 4, c.s)) return rc;
+            if (const int rc = sp_weight_scale(p, H, sc, c.s)) return rc;
+            if (const int rc = sp_launch_absmax_flat(c.d_scores, T * H, sc + 2, c.s)) return rc;
+            if (const int rc = sp_launch_absmax_flat(p.wc, (int64_t)H * HID, sc + 3, c.s)) return rc;
+            return gate_launch(sp_bound_scale_kernel, dim3(1), 1, c.s, sc + 2, d.inv * d.inv, sc + 4);
+        },
+        [&] {
+            return gate_pick_dm(d, [&](auto dm) {
+                return gate_launch(sp_gate_dz_kernel<decltype(dm)::value>, dim3((unsigned)g.nblk), 64 * H, c.s, p.wc, c.act.a, c.act.b, c.d_scores,
+                                   dzi, sc + 4, slabV, T, H, d, g.dz_rows);
+            });
+        },
+        [&] {
+            if (const int rc = gate_launch(sp_gate_wn_kernel, dim3(16, 32, H), 256, c.s, p.Wa, p.Wb, WN, sc)) return rc;
+            return gate_pick<2, 3>(c.pb.terms, [&](auto terms) {
+                return gate_pick<3, 2>(sp_nt_stages(), [&](auto na) {
+                    return gate_launch(sp_gate_dx_kernel<decltype(terms)::value, decltype(na)::value>, dim3((unsigned)g.dx_grid), SP_THREADS, c.s,
+                                       dzi, sc + 4, WN, sc, c.de.p, c.de.ld, c.de.accumulate, T, H, c.pt, c.de.absmax);
+                });
+            });
+        },
+        [&] {
+            return gate_pick<2, 3>(c.pb.terms, [&](auto terms) {
+                return gate_pick<3, 2>(sp_tn_stages(), [&](auto na) {
+                    return gate_launch(sp_gate_dw_kernel<decltype(terms)::value, decltype(na)::value>, dim3((unsigned)g.dw_grid), SP_THREADS, c.s,
+                                       c.src.p, c.src.ld, c.src.scale, dzi, sc + 4, slabW, T, H, g.tps, g.S);
+                });
+            });
+        });
 }
 
 }  // namespace mdl
 
 using namespace mdl;
 
-extern "C" int64_t mdl_abmil_gate_fwd_split_ws_bytes(int64_t T, int H) {
-    if (T < 0 || H < 1 || H > MDL_MAX_HEADS) return MDL_E_ARG;
-    // WK image [H][1024][512] | score partials [T][H][4] | scale floats
-    return (int64_t)H * 1024 * HID * 4 + T * H * GATE_JT * 4 + 128;
-}
+extern "C" int64_t mdl_abmil_gate_fwd_split_ws_bytes(int64_t T, int H) { return gate_ws_bytes(T, H, fwd_ws); }
 
 /* mdl_abmil_gate_fwd on the split engine: E as a split image (rows of e_rsb bytes holding the H*512 head-major channels, scale e_scale);
  * everything else as mdl_abmil_gate_fwd (fp32 parameters, scores, saved activations). */
@@ -497,77 +578,15 @@ extern "C" int mdl_abmil_gate_fwd_split(const void* E_img, int64_t e_rsb, const 
                                         const float* Wb, const float* bb, const float* wc, const float* bc, float* scores, float* act_a,
                                         float* act_b, int64_t T, int H, float p_drop, uint64_t seed, const uint8_t* keep_a,
                                         const uint8_t* keep_b, void* ws, void* stream) {
-    if (!E_img || !e_scale || !Wa || !ba || !Wb || !bb || !wc || !bc || !scores || !ws) return MDL_E_ARG;
-    if ((act_a == nullptr) != (act_b == nullptr)) return MDL_E_ARG;
-    if ((keep_a == nullptr) != (keep_b == nullptr)) return MDL_E_ARG;
-    if (T < 0 || H < 1 || H > MDL_MAX_HEADS || e_rsb < (int64_t)H * HID * 4 || (e_rsb & 15)) return MDL_E_ARG;
-    if (!(p_drop >= 0.f && p_drop < 1.f)) return MDL_E_ARG;
-    if (!host_aligned16(E_img) || !host_aligned16(Wa) || !host_aligned16(Wb) || !host_aligned16(ws)) return MDL_E_ALIGN;
-    if (!stride_fits32(e_rsb, 1, SPM, 0)) return MDL_E_UNSUPPORTED;   // ra * e_rsb + ch * 16, ra < SPM, ch * 16 < e_rsb
-    if (T == 0) return MDL_OK;
-    if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
-    const int64_t n_tt = (T + SPM - 1) / SPM;
-    const int64_t grid = xcd_head_grid(n_tt, GATE_JT, H);
-    if (grid > 0x7fffffff) return MDL_E_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const DropCfg d = make_drop(p_drop, seed, keep_a, keep_b);
-    char* WK = (char*)ws;
-    float* part = (float*)(WK + (int64_t)H * 1024 * HID * 4);
-    float* sc = part + T * H * GATE_JT;
-    {
-        const hipError_t e = hipMemsetAsync(sc, 0, 2 * sizeof(float), s);
-        if (e != hipSuccess) return (int)e;
-    }
-    int rc = sp_launch_absmax(Wa, HID, (int64_t)H * HID, HID, sc + 1, s);
-    if (rc) return rc;
-    rc = sp_launch_absmax(Wb, HID, (int64_t)H * HID, HID, sc + 1, s);
-    if (rc) return rc;
-    rc = sp_launch_scale(sc, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(sp_gate_wk_kernel, dim3((unsigned)((int64_t)H * 1024 * 64 / 256)), dim3(256), 0, s, Wa, Wb, WK, H, (const float*)sc);
-    MDL_LAUNCH_CHECK();
-    const int dm = gate_drop_mode(d);
-    const int nshare = 8 / H;
-    const int64_t per_share = (n_tt + nshare - 1) / nshare;
-    const int pmode = sp_gate_fwd_pmode(grid);
-    const int64_t pgrid = pmode == 1 ? grid / GATE_JT : pmode == 2 ? 8 * ((per_share + GATE_PT - 1) / GATE_PT) * GATE_JT : grid;
-    const bool na3 = sp_nt_stages() == 3;   // sp_nt_mainloop3 (MADELEINE_SP_NT_STAGES, split_engine.hpp)
-#define MDL_GATE_FWD_SP1(DM, SAVE, PM)                                                                                                 \
-    hipLaunchKernelGGL((sp_gate_fwd_kernel<DM, SAVE, PM>), dim3((unsigned)pgrid), dim3(SP_THREADS), 0, s, (const char*)E_img, e_rsb,   \
-                       e_scale, (const char*)WK, (const float*)sc, ba, bb, wc, part, act_a, act_b, T, H, (int)n_tt, d)
-#define MDL_GATE_FWD_SP(DM, SAVE)                                                                                                     \
-    do {                                                                                                                              \
-        if (pmode == 1) MDL_GATE_FWD_SP1(DM, SAVE, 1);                                                                                \
-        else if (pmode == 2) MDL_GATE_FWD_SP1(DM, SAVE, 2);                                                                           \
-        else if (na3) hipLaunchKernelGGL((sp_gate_fwd_kernel<DM, SAVE, 0, 3>), dim3((unsigned)pgrid), dim3(SP_THREADS), 0, s,             \
-                                         (const char*)E_img, e_rsb, e_scale, (const char*)WK, (const float*)sc, ba, bb, wc, part, act_a,  \
-                                         act_b, T, H, (int)n_tt, d);                                                                  \
-        else MDL_GATE_FWD_SP1(DM, SAVE, 0);                                                                                           \
-    } while (0)
-    if (act_a) {
-        if (dm == 0) MDL_GATE_FWD_SP(0, true);
-        else if (dm == 1) MDL_GATE_FWD_SP(1, true);
-        else if (dm == 3) MDL_GATE_FWD_SP(3, true);
-        else MDL_GATE_FWD_SP(2, true);
-    } else {
-        if (dm == 0) MDL_GATE_FWD_SP(0, false);
-        else if (dm == 1) MDL_GATE_FWD_SP(1, false);
-        else if (dm == 3) MDL_GATE_FWD_SP(3, false);
-        else MDL_GATE_FWD_SP(2, false);
-    }
-#undef MDL_GATE_FWD_SP
-#undef MDL_GATE_FWD_SP1
-    MDL_LAUNCH_CHECK();
-    return gate_launch_finalize(part, bc, scores, T * H, H, s);
+    return gate_fwd({{E_img, e_rsb, e_scale}, {Wa, ba, Wb, bb, wc, bc}, scores, {act_a, act_b}, {p_drop, seed, keep_a, keep_b}, {T, H, 3, 3},
+                     ws, (hipStream_t)stream});
 }
 
-extern "C" int64_t mdl_abmil_gate_bwd_split_ws_bytes(int64_t T, int H) {
-    if (T < 0 || H < 1 || H > MDL_MAX_HEADS) return MDL_E_ARG;
-    return sp_bwd_ws(T, H).total;
-}
+extern "C" int64_t mdl_abmil_gate_bwd_split_ws_bytes(int64_t T, int H) { return gate_ws_bytes(T, H, bwd_ws); }
 
 /* mdl_abmil_attnpool_bwd (scores == NULL: plain mdl_abmil_gate_bwd) on the split engine; E as a split image.  dE_absmax (device float,
- * may be NULL; zeroed by the caller) is raised to max |dE|.  phases as mdl_abmil_attnpool_bwd_phases. */
+ * may be NULL; zeroed by the caller) is raised to max |dE|.  phases: bit 0 as mdl_abmil_attnpool_bwd_phases, bit 1 = both contractions,
+ * bit 2 = dX only, bit 3 = dW only. */
 extern "C" int mdl_abmil_attnpool_bwd_split(const void* E_img, int64_t e_rsb, const float* e_scale, const float* Wa, const float* Wb,
                                             const float* wc, const float* act_a, const float* act_b, const float* d_scores, float* dE,
                                             int64_t ldE, int accumulate, float* dWa, float* dWb, float* dba, float* dbb, float* dwc,
@@ -575,100 +594,21 @@ extern "C" int mdl_abmil_attnpool_bwd_split(const void* E_img, int64_t e_rsb, co
                                             const uint8_t* keep_b, const float* scores, const float* stat_m, const float* stat_l,
                                             const float* d_pooled, const int32_t* row_bag, int64_t N, float* dE_absmax, void* ws,
                                             void* stream, int phases, int terms) {
-    if (terms != 2 && terms != 3) return MDL_E_ARG;
-    if (!E_img || !e_scale || !Wa || !Wb || !wc || !act_a || !act_b || !d_scores || !dE || !dWa || !dWb || !dba || !dbb || !dwc || !ws)
-        return MDL_E_ARG;
-    if (phases < 1 || phases > 15) return MDL_E_ARG;
-    const bool do_dx = (phases & (2 | 4)) != 0, do_dw = (phases & (2 | 8)) != 0;   // bit 1 = both contractions; bit 2 = dX only, bit 3 = dW only
-    if ((keep_a == nullptr) != (keep_b == nullptr)) return MDL_E_ARG;
-    if (scores && (!stat_m || !stat_l || !d_pooled || (!row_bag && N < 1))) return MDL_E_ARG;
-    if (T < 0 || H < 1 || H > MDL_MAX_HEADS || ldE < (int64_t)H * HID || (ldE & 3) || e_rsb < (int64_t)H * HID * 4 || (e_rsb & 15))
-        return MDL_E_ARG;
-    if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
-    if (!(p_drop >= 0.f && p_drop < 1.f)) return MDL_E_ARG;
-    if (!host_aligned16(E_img) || !host_aligned16(dE) || !host_aligned16(Wa) || !host_aligned16(Wb) || !host_aligned16(act_a) ||
-        !host_aligned16(act_b) || !host_aligned16(wc) || !host_aligned16(ws))
-        return MDL_E_ALIGN;
-    // the dW kernel's tk * e_rsb + coA, tk < SPK, coA < e_rsb; the dX epilogue's 32-bit row pitch ld4 = ldE * 4
-    if (!stride_fits32(e_rsb, 1, SPK, 0) || !stride_fits32(ldE, 4, 1, 0)) return MDL_E_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const DropCfg d = make_drop(p_drop, seed, keep_a, keep_b);
-    const SpBwdWs L = sp_bwd_ws(T, H);
-    char* base = (char*)ws;
-    char* WN = base + L.oWN;
-    char* dzi = base + L.odz;
-    float* slabW = (float*)(base + L.oslabW);
-    float* slabV = (float*)(base + L.oslabV);
-    float* sc = (float*)(base + L.osc);
-    if (L.nblk * H > 0x7fffffff) return MDL_E_UNSUPPORTED;
-    const PoolTerm pt{scores, stat_m, stat_l, d_pooled, row_bag, N};
-    if (phases & 1) {
-        hipError_t e = hipMemsetAsync(sc, 0, 8 * sizeof(float), s);
-        if (e != hipSuccess) return (int)e;
-        e = hipMemsetAsync(dzi + T * H * (int64_t)4096, 0, (size_t)SPK * H * 4096, s);   // zero pad rows of dz
-        if (e != hipSuccess) return (int)e;
-        // scales: weights from their exact absmax; dz from the bound |dz| <= max|ds| max|wc| / (1-p)^2
-        int rc = sp_launch_absmax(Wa, HID, (int64_t)H * HID, HID, sc + 1, s);
-        if (rc) return rc;
-        rc = sp_launch_absmax(Wb, HID, (int64_t)H * HID, HID, sc + 1, s);
-        if (rc) return rc;
-        rc = sp_launch_scale(sc, s);
-        if (rc) return rc;
-        rc = sp_launch_absmax_flat(d_scores, T * H, sc + 2, s);
-        if (rc) return rc;
-        rc = sp_launch_absmax_flat(wc, (int64_t)H * HID, sc + 3, s);
-        if (rc) return rc;
-        hipLaunchKernelGGL(sp_bound_scale_kernel, dim3(1), dim3(1), 0, s, (const float*)(sc + 2), d.inv * d.inv, sc + 4);
-        MDL_LAUNCH_CHECK();
-        if (T > 0) {
-            const int dm = gate_drop_mode(d);
-#define MDL_GATE_DZ_SP(DM)                                                                                                    \
-    hipLaunchKernelGGL(sp_gate_dz_kernel<DM>, dim3((unsigned)L.nblk), dim3(64 * H), 0, s, wc, act_a, act_b, d_scores, dzi,    \
-                       (const float*)(sc + 4), slabV, T, H, d, sp_dz_rows(T))
-            if (dm == 0) MDL_GATE_DZ_SP(0);
-            else if (dm == 1) MDL_GATE_DZ_SP(1);
-            else if (dm == 3) MDL_GATE_DZ_SP(3);
-            else MDL_GATE_DZ_SP(2);
-#undef MDL_GATE_DZ_SP
-            MDL_LAUNCH_CHECK();
-        }
-        rc = gate_launch_reduce_v(slabV, dba, dbb, dwc, dbc, H, (int)L.nblk, s);
-        if (rc) return rc;
-    }
-    if (do_dx && T > 0) {
-        hipLaunchKernelGGL(sp_gate_wn_kernel, dim3(16, 32, H), dim3(256), 0, s, Wa, Wb, WN, (const float*)sc);
-        MDL_LAUNCH_CHECK();
-        const int64_t n_tt = (T + SPM - 1) / SPM;
-        const int64_t grid = xcd_head_grid(n_tt, 2, H);
-        if (grid > 0x7fffffff) return MDL_E_UNSUPPORTED;
-        const bool na3 = sp_nt_stages() == 3;
-        hipLaunchKernelGGL(terms == 2 ? (na3 ? sp_gate_dx_kernel<2, 3> : sp_gate_dx_kernel<2, 2>) : (na3 ? sp_gate_dx_kernel<3, 3> : sp_gate_dx_kernel<3, 2>), dim3((unsigned)grid), dim3(SP_THREADS), 0, s, (const char*)dzi, (const float*)(sc + 4),
-                           (const char*)WN, (const float*)sc, dE, ldE, accumulate, T, H, pt, dE_absmax);
-        MDL_LAUNCH_CHECK();
-    }
-    if (do_dw) {
-        const bool tn3 = sp_tn_stages() == 3;
-        hipLaunchKernelGGL(terms == 2 ? (tn3 ? sp_gate_dw_kernel<2, 3> : sp_gate_dw_kernel<2, 2>) : (tn3 ? sp_gate_dw_kernel<3, 3> : sp_gate_dw_kernel<3, 2>), dim3((unsigned)xcd_head_grid(L.S, 8, H)), dim3(SP_THREADS), 0, s, (const char*)E_img, e_rsb, e_scale,
-                           (const char*)dzi, (const float*)(sc + 4), slabW, T, H, L.tps, L.S);
-        MDL_LAUNCH_CHECK();
-        const int rc = gate_launch_reduce_w(slabW, dWa, dWb, H, L.S, s);
-        if (rc) return rc;
-    }
-    return MDL_OK;
+    return gate_bwd({{E_img, e_rsb, e_scale}, {Wa, nullptr, Wb, nullptr, wc, nullptr}, {act_a, act_b}, d_scores,
+                     {dE, ldE, accumulate, dE_absmax}, {dWa, dWb, dba, dbb, dwc, dbc}, {p_drop, seed, keep_a, keep_b},
+                     {scores, stat_m, stat_l, d_pooled, row_bag, N}, false, {T, H, phases, terms}, ws, (hipStream_t)stream});
 }
 
 namespace mdl {
-// mdl_dispatch_plan (dispatch_plan.hip): the forward's persistence mode (mdl_abmil_gate_fwd_split) and the token splits of the dW
-// contraction (mdl_abmil_attnpool_bwd_split)
+// mdl_dispatch_plan (dispatch_plan.hip): the forward's persistence mode and the token splits of the backward's dW contraction
 int plan_gate_split(int product, int64_t T, int H, int64_t* o) {
-    if (H != 1 && H != 2 && H != 4 && H != 8) return MDL_E_UNSUPPORTED;
+    if (!gate_heads_ok(H)) return MDL_E_UNSUPPORTED;
     if (product == MDL_PLAN_GATE_SPLIT_FWD) {
-        o[MDL_PLAN_PERSIST] = sp_gate_fwd_pmode(xcd_head_grid((T + SPM - 1) / SPM, GATE_JT, H));
+        o[MDL_PLAN_PERSIST] = fwd_geom(T, H).pmode;
         o[MDL_PLAN_SPLITS] = 1;
         return MDL_OK;
     }
-    const SpBwdWs L = sp_bwd_ws(T, H);
-    plan_splits(o, T, L.S, L.tps, SPK);
+    plan_splits(o, T, bwd_geom(T, H));
     return MDL_OK;
 }
 }  // namespace mdl

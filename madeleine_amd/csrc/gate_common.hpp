@@ -210,14 +210,6 @@ static inline void plan_splits(int64_t* o, int64_t T, int S, int64_t tps, int ch
 }
 
 constexpr int DZ_ROWS = 256;  // token rows per workgroup
-// launches KERNEL<..., DM> for the run-time dropout mode dm (gate_drop_mode)
-#define MDL_DISPATCH_DM(dm, LAUNCH) \
-    do {                            \
-        if ((dm) == 0) LAUNCH(0);   \
-        else if ((dm) == 1) LAUNCH(1); \
-        else if ((dm) == 3) LAUNCH(3); \
-        else LAUNCH(2);             \
-    } while (0)
 
 // dz pass of the fp32-MFMA / bf16 modes (gate_dz_kernel below).  slabV [nblk][H][4][512]: dba | dbb | dwc | (dbc at [0]).
 template <class T>
@@ -386,10 +378,5 @@ __device__ __forceinline__ void st8_bf16(bf16_t* p, const f32x4& lo, const f32x4
     }
     *reinterpret_cast<bf16x8v*>(p) = o;
 }
-
-// launchers of the reduction / finalize kernels defined in abmil_gate.hip (shared with the bf16 path)
-int gate_launch_finalize(const float* part, const float* bc, float* scores, int64_t n, int H, hipStream_t s);
-int gate_launch_reduce_w(const float* slabW, float* dWa, float* dWb, int H, int S, hipStream_t s);
-int gate_launch_reduce_v(const float* slabV, float* dba, float* dbb, float* dwc, float* dbc, int H, int S, hipStream_t s);
 
 }  // namespace mdl

@@ -213,89 +213,70 @@ def new_dropout_seed() -> int:
 # --------------------------------------------------------------------------------------------------
 # raw calls (no autograd)
 # --------------------------------------------------------------------------------------------------
-def gate_fwd_raw(E2d, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b, save_act: bool):
-    T, H = E2d.shape[0], Wa.shape[0]
-    dev = E2d.device
+def _gate_src(E):
+    """(entry-point suffix, leading arguments, token rows, element type of the saved activations) of a gate call on E: an fp32 / bf16
+    tensor [T, ldE], or the split image of one."""
+    if isinstance(E, SplitImage):
+        return "_split", (E.data, E.K * 4, E.scale), E.rows, torch.float32
+    return _sfx(E), (E, E.stride(0)), E.shape[0], E.dtype
+
+
+def gate_fwd_raw(E, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b, save_act: bool):
+    """scores [T, H] (and the activations when save_act) of the gate on E: a tensor, or a SplitImage for the split engine."""
+    sfx, src, T, act_dtype = _gate_src(E)
+    H, dev = Wa.shape[0], Wa.device
     scores = torch.empty(T, H, device=dev, dtype=torch.float32)
-    act_a = torch.empty(T, H, HID, device=dev, dtype=E2d.dtype) if save_act else None
-    act_b = torch.empty(T, H, HID, device=dev, dtype=E2d.dtype) if save_act else None
-    sfx = _sfx(E2d)
+    act_a = torch.empty(T, H, HID, device=dev, dtype=act_dtype) if save_act else None
+    act_b = torch.empty(T, H, HID, device=dev, dtype=act_dtype) if save_act else None
     ws = _ws_for("mdl_abmil_gate_fwd%s_ws_bytes" % sfx, dev, T, H)
     with _timed("gate_fwd", ("flop", 2.0 * T * H * HID * 2 * HID)):
-        _call("mdl_abmil_gate_fwd" + sfx, E2d, E2d.stride(0), Wa, ba, Wb, bb, wc, bc, scores, act_a, act_b, T, H, float(p_drop), int(seed),
-              keep_a, keep_b, ws, _stream())
+        _call("mdl_abmil_gate_fwd" + sfx, *src, Wa, ba, Wb, bb, wc, bc, scores, act_a, act_b, T, H, float(p_drop), int(seed), keep_a, keep_b,
+              ws, _stream())
     return scores, act_a, act_b
 
 
-def gate_fwd_split_raw(Ei, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b, save_act: bool):
-    """gate_fwd_raw on the split engine: Ei = SplitImage of the head-major token embeddings [T, H*512]."""
-    T, H = Ei.rows, Wa.shape[0]
-    dev = Ei.data.device
-    scores = torch.empty(T, H, device=dev, dtype=torch.float32)
-    act_a = torch.empty(T, H, HID, device=dev, dtype=torch.float32) if save_act else None
-    act_b = torch.empty(T, H, HID, device=dev, dtype=torch.float32) if save_act else None
-    ws = _ws_for("mdl_abmil_gate_fwd_split_ws_bytes", dev, T, H)
-    with _timed("gate_fwd", ("flop", 2.0 * T * H * HID * 2 * HID)):
-        _call("mdl_abmil_gate_fwd_split", Ei.data, Ei.K * 4, Ei.scale, Wa, ba, Wb, bb, wc, bc, scores, act_a, act_b, T, H, float(p_drop),
-              int(seed), keep_a, keep_b, ws, _stream())
-    return scores, act_a, act_b
-
-
-def attnpool_bwd_split_raw(Ei, Wa, Wb, wc, act_a, act_b, d_scores, dE, p_drop, seed, keep_a, keep_b, scores, stat_m, stat_l, d_pooled,
-                           row_bag, N, accumulate=0, dE_absmax=None, phases=None):
-    """attnpool_bwd_raw (scores None: gate_bwd_raw) on the split engine.  `phases`: a sequence of phase masks issued one after the other
-    on the same workspace (include/madeleine_amd.h: 1 = dz pass, 2 = both contractions, 4 = dX alone, 8 = dW alone); None = one call."""
-    T, H = Ei.rows, Wa.shape[0]
+def gate_bwd_raw(E, Wa, Wb, wc, act_a, act_b, d_scores, dE, p_drop, seed, keep_a, keep_b, pool=None, accumulate=0, dE_absmax=None,
+                 phases=None):
+    """Gate backward on E (a tensor, or a SplitImage for the split engine) -> (dWa, dWb, dba, dbb, dwc, dbc); dE is written, or added to
+    with `accumulate` (another consumer's gradient of E already sits there).  pool = (scores, stat_m, stat_l, d_pooled, row_bag, N): the
+    dX epilogue also adds the pooling term (mdl_abmil_attnpool_bwd), so dE is written once.  dE_absmax (split engine): raised to
+    max |dE|.  phases: a sequence of phase masks issued one after the other on the same workspace (include/madeleine_amd.h: 1 = dz pass,
+    2 = both contractions; split engine also 4 = dX alone, 8 = dW alone); None = one call.  A tensor without a pooling term goes through
+    mdl_abmil_gate_bwd, which has no phases."""
+    sfx, src, T, _ = _gate_src(E)
+    H = Wa.shape[0]
+    split = isinstance(E, SplitImage)
+    if not split and (dE_absmax is not None or (pool is None and phases is not None)):
+        raise ValueError("gate_bwd_raw: dE_absmax needs a SplitImage, phases a SplitImage or a pooling term")
     grads = _gate_grads(Wa, Wb)
-    ws = _ws_for("mdl_abmil_gate_bwd_split_ws_bytes", Ei.data.device, T, H)
+    ws = _ws_for("mdl_abmil_gate_bwd%s_ws_bytes" % sfx, dE.device, T, H)
+    args = (Wa, Wb, wc, act_a, act_b, d_scores, dE) + ((dE.stride(0),) if split else ()) + (int(accumulate), *grads, T, H, float(p_drop),
+                                                                                           int(seed), keep_a, keep_b)
+    if not split and pool is None:
+        with _timed("gate_bwd", ("flop", 4.0 * T * H * HID * 2 * HID)):
+            _call("mdl_abmil_gate_bwd" + sfx, *src, *args, ws, _stream())
+        return grads
+    pool = tuple(pool[:5]) + (int(pool[5]),) if pool is not None else (None,) * 5 + (0,)
 
-    def call(phases):
-        _call("mdl_abmil_attnpool_bwd_split", Ei.data, Ei.K * 4, Ei.scale, Wa, Wb, wc, act_a, act_b, d_scores, dE, dE.stride(0),
-              int(accumulate), *grads, T, H, float(p_drop), int(seed), keep_a, keep_b, scores, stat_m, stat_l, d_pooled, row_bag, int(N),
-              dE_absmax, ws, _stream(), phases, GRAD_TERMS)
+    def call(ph):
+        if split:
+            _call("mdl_abmil_attnpool_bwd_split", *src, *args, *pool, dE_absmax, ws, _stream(), 3 if ph is None else ph, GRAD_TERMS)
+        elif ph is None:
+            _call("mdl_abmil_attnpool_bwd" + sfx, *src, *args, *pool, ws, _stream())
+        else:
+            _call("mdl_abmil_attnpool_bwd_phases" + sfx, *src, *args, *pool, ws, _stream(), ph)
     if phases is not None:
         for ph in phases:
             call(int(ph))
     elif TIMER is not None and TIMER.wants("gate_bwd_dz"):
-        with _timed("gate_bwd_dz", ("byte", float(T) * H * 4 * HID * 4)):
+        # profiling: the HBM-bound dz pass and the MFMA-bound contractions as two calls on the same workspace, timed separately
+        # ("gate_bwd" stays their sum in KernelTimer.report)
+        with _timed("gate_bwd_dz", ("byte", float(T) * H * 4 * HID * act_a.element_size())):   # reads a, b; writes dza | dzb
             call(1)
         with _timed("gate_bwd_gemm", ("flop", 4.0 * T * H * HID * 2 * HID)):
             call(2)
     else:
-        call(3)
-    return grads
-
-
-def gate_bwd_raw(E2d, Wa, Wb, wc, act_a, act_b, d_scores, dE, accumulate, p_drop, seed, keep_a, keep_b):
-    T, H = E2d.shape[0], Wa.shape[0]
-    grads = _gate_grads(Wa, Wb)
-    sfx = _sfx(E2d)
-    ws = _ws_for("mdl_abmil_gate_bwd%s_ws_bytes" % sfx, E2d.device, T, H)
-    with _timed("gate_bwd", ("flop", 4.0 * T * H * HID * 2 * HID)):
-        _call("mdl_abmil_gate_bwd" + sfx, E2d, E2d.stride(0), Wa, Wb, wc, act_a, act_b, d_scores, dE, int(accumulate), *grads, T, H,
-              float(p_drop), int(seed), keep_a, keep_b, ws, _stream())
-    return grads
-
-
-def attnpool_bwd_raw(E2d, Wa, Wb, wc, act_a, act_b, d_scores, dE, p_drop, seed, keep_a, keep_b, scores, stat_m, stat_l, d_pooled,
-                     row_bag, N, accumulate=0):
-    """Gate backward whose dX epilogue also adds the pooling term (mdl_abmil_attnpool_bwd): dE is written once; with
-    `accumulate` the epilogue adds to what dE already holds (another consumer's gradient of E)."""
-    T, H = E2d.shape[0], Wa.shape[0]
-    grads = _gate_grads(Wa, Wb)
-    sfx = _sfx(E2d)
-    ws = _ws_for("mdl_abmil_gate_bwd%s_ws_bytes" % sfx, E2d.device, T, H)
-    args = (E2d, E2d.stride(0), Wa, Wb, wc, act_a, act_b, d_scores, dE, int(accumulate), *grads, T, H, float(p_drop), int(seed),
-            keep_a, keep_b, scores, stat_m, stat_l, d_pooled, row_bag, int(N), ws, _stream())
-    if TIMER is not None and TIMER.wants("gate_bwd_dz"):
-        # profiling: the HBM-bound dz pass and the MFMA-bound contractions as two calls on the same workspace, timed separately
-        # ("gate_bwd" stays their sum in KernelTimer.report)
-        with _timed("gate_bwd_dz", ("byte", float(T) * H * 4 * HID * E2d.element_size())):   # reads a, b; writes dza | dzb
-            _call("mdl_abmil_attnpool_bwd_phases" + sfx, *args, 1)
-        with _timed("gate_bwd_gemm", ("flop", 4.0 * T * H * HID * 2 * HID)):
-            _call("mdl_abmil_attnpool_bwd_phases" + sfx, *args, 2)
-    else:
-        _call("mdl_abmil_attnpool_bwd" + sfx, *args)
+        call(None)
     return grads
 
 
@@ -828,9 +809,7 @@ class GateScoresFn(torch.autograd.Function):
         Ei = None
         if _split_gate(E2d):
             Ei = split_image(E2d)
-            scores, act_a, act_b = gate_fwd_split_raw(Ei, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b, need)
-        else:
-            scores, act_a, act_b = gate_fwd_raw(E2d, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b, need)
+        scores, act_a, act_b = gate_fwd_raw(Ei if Ei is not None else E2d, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b, need)
         if need:
             none = torch.empty(0)
             ctx.save_for_backward(E2d, Wa, Wb, wc, act_a, act_b, Ei.data if Ei is not None else none, Ei.scale if Ei is not None else none)
@@ -844,13 +823,8 @@ class GateScoresFn(torch.autograd.Function):
         p_drop, seed, keep_a, keep_b = ctx.drop
         d_scores = d_scores.float().contiguous()
         dE = torch.empty_like(E2d)
-        if ctx.has_image:
-            Ei = SplitImage(Eidata, Eiscale, E2d.shape[0], E2d.shape[1])
-            dWa, dWb, dba, dbb, dwc, dbc = attnpool_bwd_split_raw(Ei, Wa, Wb, wc, act_a, act_b, d_scores, dE, p_drop, seed, keep_a,
-                                                                  keep_b, None, None, None, None, None, 0)
-        else:
-            dWa, dWb, dba, dbb, dwc, dbc = gate_bwd_raw(E2d, Wa, Wb, wc, act_a, act_b, d_scores, dE, 0, p_drop, seed, keep_a,
-                                                        keep_b)
+        src = SplitImage(Eidata, Eiscale, E2d.shape[0], E2d.shape[1]) if ctx.has_image else E2d
+        dWa, dWb, dba, dbb, dwc, dbc = gate_bwd_raw(src, Wa, Wb, wc, act_a, act_b, d_scores, dE, p_drop, seed, keep_a, keep_b)
         return dE, dWa, dba, dWb, dbb, dwc, dbc, None, None, None, None
 
 
@@ -980,9 +954,8 @@ class AttnPoolFn(torch.autograd.Function):
         if _split_gate(E2d):
             # the image of E: written by the producing LayerNorm kernel (Eimg / Escale), else built here (3 passes over E)
             Ei = SplitImage(Eimg, Escale, E2d.shape[0], E2d.shape[1]) if Eimg is not None else split_image(E2d)
-            scores, act_a, act_b = gate_fwd_split_raw(Ei, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b, need and not recompute)
-        else:
-            scores, act_a, act_b = gate_fwd_raw(E2d, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b, need and not recompute)
+        scores, act_a, act_b = gate_fwd_raw(Ei if Ei is not None else E2d, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b,
+                                            need and not recompute)
         pooled, m, l = (pool_fwd_img_raw(Ei, scores, n_bags, N, cu_seqlens, max_len) if e_only_image
                         else pool_fwd_raw(E2d, scores, n_bags, N, cu_seqlens, max_len))
         vstate = [pool_view_fwd_raw(E2d, scores, n_bags, N, v) for v in views]
@@ -1034,10 +1007,7 @@ class AttnPoolFn(torch.autograd.Function):
         n_out = 1 + V + (2 if rview is not None else 0)
         Ei = SplitImage(Eidata, Eiscale, E2d.shape[0], E2d.shape[1]) if ctx.has_image else None
         if ctx.recompute:   # rebuild the activations: the same kernel, seed and masks as the forward -> the same bits
-            if Ei is not None:
-                _s, act_a, act_b = gate_fwd_split_raw(Ei, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b, True)
-            else:
-                _s, act_a, act_b = gate_fwd_raw(E2d, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b, True)
+            _s, act_a, act_b = gate_fwd_raw(Ei if Ei is not None else E2d, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b, True)
         cu = cu if ragged else None
         dE = torch.empty_like(E2d)
         if d_scores_in is not None:
@@ -1075,10 +1045,11 @@ class AttnPoolFn(torch.autograd.Function):
         row_bag = None
         if ragged:   # bag index of every packed token row, on the device (no sync)
             row_bag = torch.searchsorted(cu[1:].contiguous(), torch.arange(E2d.shape[0], device=E2d.device), right=True).to(torch.int32)
+        pool = (scores, m, l, d_main, row_bag, N if not ragged else 0)
         if Ei is not None:
             am = torch.zeros(1, device=dE.device, dtype=torch.float32) if n_out == 1 else None   # (views add to dE afterwards)
-            dWa, dWb, dba, dbb, dwc, dbc = attnpool_bwd_split_raw(Ei, Wa, Wb, wc, act_a, act_b, ds, dE, p_drop, seed, keep_a, keep_b,
-                                                                  scores, m, l, d_main, row_bag, N if not ragged else 0, acc_e, am)
+            dWa, dWb, dba, dbb, dwc, dbc = gate_bwd_raw(Ei, Wa, Wb, wc, act_a, act_b, ds, dE, p_drop, seed, keep_a, keep_b, pool=pool,
+                                                        accumulate=acc_e, dE_absmax=am)
             if tok_after:
                 d_tok = d_tok.float().contiguous()
                 dti = split_image(d_tok, pad_rows=32)
@@ -1090,8 +1061,8 @@ class AttnPoolFn(torch.autograd.Function):
             if am is not None:
                 _put_absmax(dE, am)
         else:
-            dWa, dWb, dba, dbb, dwc, dbc = attnpool_bwd_raw(E2d, Wa, Wb, wc, act_a, act_b, ds, dE, p_drop, seed, keep_a, keep_b,
-                                                            scores, m, l, d_main, row_bag, N if not ragged else 0, acc_e)
+            dWa, dWb, dba, dbb, dwc, dbc = gate_bwd_raw(E2d, Wa, Wb, wc, act_a, act_b, ds, dE, p_drop, seed, keep_a, keep_b, pool=pool,
+                                                        accumulate=acc_e)
         for i in range(V):   # ... and their dE terms are added once dE has been written (no read of E)
             vp, vm, vl = vflat[3 * i:3 * i + 3]
             pool_view_bwd_raw(E2d, scores, vp, vm, vl, d_pooled[:, 1 + i].contiguous(), dE, None, n_bags, N, views[i])

@@ -339,11 +339,11 @@ def test_gate_backward_phase_masks_compose(dev):
     wc, bc = (t((H, 512), "ph:wc") * 0.1).to(dev), (t((H,), "ph:bc") * 0.1).to(dev)
     ds = t((T, H), "ph:ds").to(dev)
     Ei = MF.split_image(E)
-    _s, a, b = MF.gate_fwd_split_raw(Ei, Wa, ba, Wb, bb, wc, bc, 0.25, 1234, None, None, True)
+    _s, a, b = MF.gate_fwd_raw(Ei, Wa, ba, Wb, bb, wc, bc, 0.25, 1234, None, None, True)
     outs = []
     for phases in (None, (3,), (1, 4, 8), (1, 8, 4)):
         dE = torch.zeros_like(E)
-        g = MF.attnpool_bwd_split_raw(Ei, Wa, Wb, wc, a, b, ds, dE, 0.25, 1234, None, None, None, None, None, None, None, 0, phases=phases)
+        g = MF.gate_bwd_raw(Ei, Wa, Wb, wc, a, b, ds, dE, 0.25, 1234, None, None, phases=phases)
         outs.append((dE,) + tuple(g))
     for o in outs[1:]:
         for x, y in zip(outs[0], o):

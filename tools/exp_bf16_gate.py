@@ -25,7 +25,7 @@ sc, a, b = MF.gate_fwd_raw(E, Wa, ba, Wb, bb, wc, bc, 0.25, 7, None, None, True)
 ds = torch.randn(T, H, device=dev)
 dE = torch.zeros_like(E)
 for acc in (0, 1):
-    ms = timeit(lambda: MF.gate_bwd_raw(E, Wa, Wb, wc, a, b, ds, dE, acc, 0.25, 7, None, None))
+    ms = timeit(lambda: MF.gate_bwd_raw(E, Wa, Wb, wc, a, b, ds, dE, 0.25, 7, None, None, accumulate=acc))
     print(f"bf16 gate bwd accumulate={acc}: {ms:.3f} ms")
 E32 = E.float()
 ms = timeit(lambda: MF.gate_fwd_raw(E32, Wa, ba, Wb, bb, wc, bc, 0.25, 7, None, None, True))

@@ -29,7 +29,7 @@ bc = torch.zeros(H, device=dev)
 if a.split:
     Ei = MF.split_image(E)
     for it in range(a.iters):
-        MF.gate_fwd_split_raw(Ei, Wa, ba, Wb, bb, wc, bc, a.p, 7 + it, None, None, True)
+        MF.gate_fwd_raw(Ei, Wa, ba, Wb, bb, wc, bc, a.p, 7 + it, None, None, True)
 else:
     Eb = E.to(torch.bfloat16)
     for it in range(a.iters):

@@ -50,8 +50,8 @@ for it in range(a.iters):
         if a.only == "gate":
             dE = torch.empty_like(E2)
             ds = torch.randn(BM * N, H, device=dev, generator=g)
-            MF.gate_bwd_raw(E2, Wa, Wb, wc, aa, ab, ds, dE, 0, 0.25, 123 + it, None, None)
+            MF.gate_bwd_raw(E2, Wa, Wb, wc, aa, ab, ds, dE, 0.25, 123 + it, None, None)
         else:
-            MF.attnpool_bwd_raw(E2, Wa, Wb, wc, aa, ab, ds, dE, 0.25, 123 + it, None, None, scores, m, l, dpool, None, N)
+            MF.gate_bwd_raw(E2, Wa, Wb, wc, aa, ab, ds, dE, 0.25, 123 + it, None, None, pool=(scores, m, l, dpool, None, N))
 torch.cuda.synchronize()
 print("done", a.iters)
