@@ -952,6 +952,55 @@ int mdl_attn_softmax(const float* scores, int64_t ld, const int64_t* cu, int64_t
 int mdl_attn_rank(const float* scores, int64_t ld, const int64_t* cu, int64_t T, int64_t R, int H, int64_t k, int32_t* order, float* pct,
                   int32_t* topk_idx, float* topk_val, void* ws, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * R1 -- the smooth rank: exp(entropy of the normalised singular values) of an embedding matrix, on the device (ABI 26, additive).
+ * Replaces smooth_rank_measure (madeleine/utils/utils.py:180-201): S = svd(E), p = S / |S|_1 + eps, p = p[:d], exp(-sum p ln p) --
+ * the model-selection criterion of bin/pretrain.py:69-72, returned by train_loop and run_inference.
+ *
+ * E [n, d] fp32, row stride ldE >= d ELEMENTS (any such value: every offset into E is formed in 64 bits, there is no 32-bit limit;
+ *   a column slice of a wider buffer is fine), 4-byte aligned; only read.  k = min(n, d) <= MDL_RANK_MAX_K; n, d <= 2^31 - 1.
+ * eps_bits: the bit pattern of the fp64 eps (the header has no double; as mdl_adamw_update's scalars).
+ * sigma [k] fp64 (8-byte aligned): the singular values, descending, >= 0.  out [2] fp64: exp(H) (unrounded; the reference rounds it to
+ *   2 decimals) and H = -sum_i p_i ln p_i, p_i = sigma_i / sum(sigma) + eps over all k values.
+ * ws: mdl_smooth_rank_ws_bytes(n, d) bytes, 16-byte aligned, contents need no initialisation ((chunks + 1) k^2 + 4 k doubles).
+ *
+ * Arithmetic, all fp64:
+ *   1. Gram matrix G = E^T E (n >= d) or E E^T (n < d), k x k.  The fp32 inputs are widened first, so every product is exact and only
+ *      the additions round.  The contraction (length L = max(n, d)) is cut into chunks of MDL_RANK_GRAM_ROWS rows -- or, beyond
+ *      MDL_RANK_GRAM_MAX_CHUNKS of those, into that many equal chunks (a multiple of 16 rows each); a workgroup adds one chunk's
+ *      rows in order into a MDL_RANK_GRAM_TILE-square tile of that chunk's partial, and a second launch adds the partials in chunk
+ *      order.  Tiles on or below the diagonal are formed, the others mirrored: G is symmetric bit for bit.
+ *   2. Householder reduction to tridiagonal form: k - 2 steps, each a launch for p = beta A v and a launch for the symmetric rank-2
+ *      update of the trailing block, over blocks of MDL_RANK_TRI_ROWS rows.  Every workgroup rebuilds the step's reflector (and
+ *      p^T v) from the k numbers involved, in the same fixed order.
+ *   3. Every eigenvalue of the tridiagonal matrix by Sturm-count bisection from the Gershgorin interval: one thread each, 64 halvings,
+ *      pivots inside (-pivmin, pivmin) taken as -pivmin, pivmin = DBL_MIN max(1, max e^2) (LAPACK dstebz).
+ *   4. One workgroup: sigma_i = sqrt(max(lambda_i, 0)), their sum, p, H, in a fixed order.
+ *   The tridiagonalisation perturbs G by O(k 2^-52) lambda_max: relative error of a singular value that is not tiny against sigma_max
+ *   ~1e-13; singular values that are exactly zero come out as noise of at most sqrt(k 2^-52) sigma_max.
+ *   Launches: 2 k (k >= 2; 4 for k == 1), a function of (n, d) alone.  No atomics, no host read, no workgroup waits on another, every
+ *   loop's trip count is a function of (n, d).
+ *   Bit contract: sigma and out depend on (E, n, d, ldE, eps) alone.
+ * Edge values: an all-zero E gives sigma = 0 and out = NaN (0 / 0, as the reference).  A NaN or Inf anywhere in E gives NaN in out (and
+ * in sigma); the call returns normally.  Squares of G's entries must stay finite in fp64 (|E| sqrt(L) below 1e37 is enough).
+ *
+ * Refusals, in this order, before any launch.  MDL_E_ARG: n < 1, d < 1, ldE < d, a NULL pointer.  MDL_E_ALIGN: E not 4-byte, sigma /
+ * out not 8-byte, ws not 16-byte aligned.  MDL_E_UNSUPPORTED: k > MDL_RANK_MAX_K, n or d beyond int32, n * ldE beyond 2^61.
+ * mdl_smooth_rank_ws_bytes returns the same negative codes for its sizes.
+ *
+ * mdl_smooth_rank_marked: the same call, which also records four caller-created hipEvent_t (marks_host [4], a HOST array of event
+ * handles) on the stream: before the Gram launches, after them, after the tridiagonalisation and after the finish -- the stage times
+ * of tools/exp_rank.py.  MDL_E_ARG for a NULL array or handle. */
+#define MDL_RANK_MAX_K 1024
+#define MDL_RANK_GRAM_ROWS 512
+#define MDL_RANK_GRAM_MAX_CHUNKS 16
+#define MDL_RANK_GRAM_TILE 64
+#define MDL_RANK_TRI_ROWS 16
+int64_t mdl_smooth_rank_ws_bytes(int64_t n, int64_t d);
+int mdl_smooth_rank(const float* E, int64_t ldE, int64_t n, int64_t d, uint64_t eps_bits, void* sigma, void* out, void* ws, void* stream);
+int mdl_smooth_rank_marked(const float* E, int64_t ldE, int64_t n, int64_t d, uint64_t eps_bits, void* sigma, void* out, void* ws,
+                           void* const* marks_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ madeleine.utils.loss, madeleine.utils.trainer):
     from madeleine_amd import AdamW          # torch.optim.AdamW's update with a device-side non-finite guard and clipping
     from madeleine_amd import DeviceSlideStore   # the cohort's features resident on the device, batches drawn by one kernel
     from madeleine_amd import linear_probe       # the few-shot linear-probing protocol, every (task, k, fold) fit in one batch of launches
+    from madeleine_amd import device_smooth_rank # the model-selection criterion (smooth rank of the embeddings) without a host SVD
 
 The numeric work runs in csrc/libmadeleine_amd.so through the C ABI of include/madeleine_amd.h.
 Importing this package does not load the library (so model construction / state_dict handling works on
@@ -19,12 +20,12 @@ from .model import ABMILEmbedder, MADELEINE, create_model
 from .optim import AdamW
 from .store import DeviceSlideStore, PackedBags
 from .trainer import calculate_losses, train_loop
-from .utils import create_model_from_pretrained, extract_slide_level_embeddings, load_checkpoint, run_inference
+from .utils import create_model_from_pretrained, device_smooth_rank, extract_slide_level_embeddings, load_checkpoint, run_inference
 
 __all__ = ["MADELEINE", "ABMILEmbedder", "BatchedABMIL", "create_model", "InfoNCE", "info_nce", "GOT",
            "init_intra_wsi_loss_function", "calculate_losses", "train_loop", "run_inference", "extract_slide_level_embeddings",
            "load_checkpoint", "create_model_from_pretrained", "AdamW", "DeviceSlideStore", "PackedBags", "probe_splits", "fit_logistic",
-           "linear_probe"]
+           "linear_probe", "device_smooth_rank"]
 __version__ = "0.2"
 _PROBE = ("probe_splits", "fit_logistic", "linear_probe")
 

@@ -1987,3 +1987,69 @@ def attn_rank(scores, cu, k=0, percentile=True):
     with _timed("attn_rank", ("byte", 40.0 * T * H)):
         _call("mdl_attn_rank", scores, ld, cu, T, R, H, k, order, pct, ti, tv, ws, _stream(), unsupported=refusal)
     return order, pct, ti, tv
+
+
+# ---- R1: the smooth rank (mdl_smooth_rank).  fp64 Gram, tridiagonal eigenvalues, entropy.  No autograd: embeddings are inputs ----
+RANK_MAX_K = _native._DEFINES["MDL_RANK_MAX_K"]
+RANK_GRAM_ROWS, RANK_GRAM_MAX_CHUNKS, RANK_GRAM_TILE, RANK_TRI_ROWS = (
+    _native._DEFINES["MDL_RANK_" + k] for k in ("GRAM_ROWS", "GRAM_MAX_CHUNKS", "GRAM_TILE", "TRI_ROWS"))
+_RANK_LIMIT = "smooth_rank supports min(n, d) <= %d (got E [%d, %d])"
+
+
+def smooth_rank_supported(E) -> bool:
+    """Whether smooth_rank takes E: a non-empty 2-D fp32 tensor on a ROCm device with unit column stride, min(n, d) <= RANK_MAX_K."""
+    return (torch.is_tensor(E) and E.is_cuda and E.dtype == torch.float32 and E.dim() == 2 and min(E.shape) >= 1
+            and min(E.shape) <= RANK_MAX_K and (E.shape[1] == 1 or E.stride(1) == 1) and (E.shape[0] == 1 or E.stride(0) >= E.shape[1]))
+
+
+def _rank_call(E, eps, marks=None):
+    """(out [2] fp64: exp(H), H; sigma [k] fp64) of mdl_smooth_rank -- or, with four event handles in `marks`, of _marked."""
+    if not torch.is_tensor(E) or E.dtype != torch.float32 or E.dim() != 2:
+        raise ValueError("madeleine_amd: smooth_rank needs a 2-D float32 tensor (got %s)"
+                         % ("%s %s" % (E.dtype, tuple(E.shape)) if torch.is_tensor(E) else type(E).__name__))
+    n, d = E.shape
+    if n < 1 or d < 1:
+        raise ValueError("madeleine_amd: smooth_rank needs at least one row and one column (got [%d, %d])" % (n, d))
+    k = min(n, d)
+    if k > RANK_MAX_K:
+        raise NotImplementedError("madeleine_amd: " + _RANK_LIMIT % (RANK_MAX_K, n, d))
+    if not E.is_cuda:
+        raise ValueError("madeleine_amd: E must live on a ROCm device (got %s); smooth_rank_measure is the host function" % E.device)
+    ld = E.stride(0) if n > 1 else d
+    if (d > 1 and E.stride(1) != 1) or ld < d:
+        raise ValueError("madeleine_amd: smooth_rank needs unit column stride and a row stride >= d (got strides %s)" % (tuple(E.stride()),))
+    dev = E.device
+    refusal = (_RANK_LIMIT, RANK_MAX_K, n, d)
+    ws = _ws_for("mdl_smooth_rank_ws_bytes", dev, n, d, refusal=refusal)
+    sigma = torch.empty(k, device=dev, dtype=torch.float64)
+    out = torch.empty(2, device=dev, dtype=torch.float64)
+    with _timed("smooth_rank", ("flop", 2.0 * max(n, d) * k * k)):
+        if marks is None:
+            _call("mdl_smooth_rank", E, ld, n, d, _f64_bits(eps), sigma, out, ws, _stream(), unsupported=refusal)
+        else:
+            _call("mdl_smooth_rank_marked", E, ld, n, d, _f64_bits(eps), sigma, out, ws, marks, _stream(), unsupported=refusal)
+    return out, sigma
+
+
+def smooth_rank(E, eps=1e-7):
+    """(rank, sigma) of E [n, d] fp32 on the device (unit column stride, any row stride >= d): rank a 0-d fp64 device tensor, the
+    UNROUNDED exp(entropy of p), p = sigma / sum(sigma) + eps; sigma [min(n, d)] fp64 on the device, the singular values, descending.
+    utils.smooth_rank_measure without the rounding, the copy to the host or the CPU SVD (include/madeleine_amd.h, R1): 2 min(n, d)
+    launches on the current stream, no host read, no upload; the workspace comes from torch's allocator.  ValueError for a tensor that is
+    not 2-D float32 on a ROCm device, NotImplementedError for min(n, d) > RANK_MAX_K."""
+    out, sigma = _rank_call(E, eps)
+    return out[0], sigma
+
+
+def smooth_rank_stages(E, eps=1e-7):
+    """smooth_rank with its three stages timed by device events: (rank, sigma, {"gram", "tridiagonal", "eigen_finish"} in ms).
+    Synchronises the stream: for tools/exp_rank.py, not for a training loop."""
+    import ctypes
+    events = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    for ev in events:
+        ev.record()                    # an event's handle exists once it has been recorded
+    marks = (ctypes.c_void_p * 4)(*[ev.cuda_event for ev in events])
+    out, sigma = _rank_call(E, eps, marks)
+    events[3].synchronize()
+    ms = [events[i].elapsed_time(events[i + 1]) for i in range(3)]
+    return out[0], sigma, dict(zip(("gram", "tridiagonal", "eigen_finish"), ms))

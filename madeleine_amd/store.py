@@ -338,21 +338,25 @@ class DeviceSlideStore:
         _, bag, lens = self._modality_plan(case_indices, modality, max_tokens)
         return self._pack_bags(bag, lens, counter, seed, False, host_wgs)
 
-    def _embedding_result(self, embeds, cases):
-        return {"embeds": embeds, "cases": cases, "slide_ids": [self.slide_ids[c] for c in cases.tolist()]}
+    def _embedding_result(self, embeds, cases, rank=False):
+        res = {"embeds": embeds, "cases": cases, "slide_ids": [self.slide_ids[c] for c in cases.tolist()]}
+        if rank:      # the number the reference prints beside every extraction (utils.py:70), from the HIP kernels: one host read
+            res["rank"] = round(MF.smooth_rank(embeds)[0].item(), 2)
+        return res
 
-    def mean_embeddings(self, modality=0, case_indices=None, host_wgs=0) -> dict:
+    def mean_embeddings(self, modality=0, case_indices=None, host_wgs=0, rank=False) -> dict:
         """The mean patch embedding of one stain's bag of every case asked for (None: every case that has the stain): {"embeds" [n, D]
         fp32 on the device, "cases" [n] int64 on the host, "slide_ids"} -- bin/extract_mean_embs.py for a cohort in the store, the
         baseline of the linear probe.  Whole bags, read where they lie (both tiers, any store dtype) by functional.bag_mean; the bits
         of a row depend on that bag alone.  One O(n) upload per call (the bags and the chunk tables); the work goes in slices of cases
         whose partial sums stay inside MEAN_WS_BYTES (a bag whose own partials exceed it goes alone).  ValueError / IndexError as
-        pack_modality; host_wgs as in sample()."""
+        pack_modality; host_wgs as in sample().  rank=True adds "rank": the smooth rank of the embeddings as a Python float rounded to 2
+        decimals (functional.smooth_rank on the device; NotImplementedError past min(n, D) = 1024, ValueError for no case at all)."""
         self._require_device("mean_embeddings")
         cases, bag, lens = self._modality_plan(case_indices, modality)
         n, D = bag.numel(), self.dim
         if n == 0:
-            return self._embedding_result(torch.zeros(0, D, dtype=torch.float32, device=self.device), cases)
+            return self._embedding_result(torch.zeros(0, D, dtype=torch.float32, device=self.device), cases, rank)
         chunks = (lens + (MF.BAG_MEAN_ROWS - 1)) // MF.BAG_MEAN_ROWS
         budget = max(1, MEAN_WS_BYTES // (4 * D))                # chunks per slice
         cuts, used = [0], 0
@@ -379,9 +383,10 @@ class DeviceSlideStore:
             else:
                 outs.append(MF.bag_mean_tiered(self.rows, self.rows_host, self.off, bag_d[a:b], table[a + j:b + j + 1], totals[j],
                                                host_wgs=host_wgs))
-        return self._embedding_result(outs[0] if k == 1 else torch.cat(outs), cases)
+        return self._embedding_result(outs[0] if k == 1 else torch.cat(outs), cases, rank)
 
-    def embed(self, model, modality=0, case_indices=None, bags_per_launch=None, max_tokens=None, precision=None, host_wgs=0) -> dict:
+    def embed(self, model, modality=0, case_indices=None, bags_per_launch=None, max_tokens=None, precision=None, host_wgs=0,
+              rank=False) -> dict:
         """The slide embedding of one stain's bag of every case asked for (None: every case that has the stain), from `model`'s H&E
         encoder: {"embeds" [n, 512] fp32 on the device, "cases", "slide_ids"} -- utils.run_inference for a cohort in the store, without
         a dataloader, an h5 read or a host-to-device copy of features.  Eval mode under torch.no_grad() (the model's training flag is
@@ -389,7 +394,8 @@ class DeviceSlideStore:
         launch set (None: 4 in fp32, 1 under autocast, for the reason its docstring gives), a bag of at most 256 rows alone; each
         group is pack_modality -> model.encode_packed, and every embedding equals model.encode_he of that bag alone bit for bit in
         fp32.  The embeddings stay on the device and the loop reads nothing back.  max_tokens, counter 0: pack_modality's cut.  A
-        model with stain encoding takes modality 0 only (encode_he is the H&E path)."""
+        model with stain encoding takes modality 0 only (encode_he is the H&E path).  rank=True adds "rank" as in mean_embeddings: what
+        run_inference returns beside the embeddings, without their copy to the host or the CPU SVD."""
         self._require_device("embed")
         if getattr(model, "stain_encoding", False) and modality != 0:
             raise ValueError("DeviceSlideStore.embed: a model with stain encoding embeds modality 0 only (encode_he is the H&E path; "
@@ -409,7 +415,7 @@ class DeviceSlideStore:
         finally:
             model.train(was_training)
         embeds = torch.cat(outs) if outs else torch.zeros(0, 512, dtype=torch.float32, device=self.device)
-        return self._embedding_result(embeds, cases)
+        return self._embedding_result(embeds, cases, rank)
 
     @staticmethod
     def _launch_groups(cases, lens, bags_per_launch, reduced):

@@ -20,7 +20,7 @@ from .loss import GOT as _GOT
 
 from .functional import h2d
 from .loss import InfoNCE as _HipInfoNCE
-from .utils import set_model_precision, smooth_rank_measure
+from .utils import rounded_device_rank, set_model_precision, smooth_rank_measure
 
 DEVICE = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 HE_POSITION = 0
@@ -173,12 +173,17 @@ def calculate_losses(STAINS, loss_fn_interMod, loss_fn_interMod_local, loss_fn_i
 
 def train_loop(args, loss_fn_interMod, loss_fn_interMod_local, loss_fn_intraMod, ssl_model, epoch, dataloader, optimizer,
                scheduler_warmup, scheduler):
-    """One epoch (trainer.py:80-144): returns (summed batch losses, smooth rank of the epoch's H&E slide embeddings)."""
+    """One epoch (trainer.py:80-144): returns (summed batch losses, smooth rank of the epoch's H&E slide embeddings).
+    With args.device_rank set the step makes no copy of the embeddings to the host: they are concatenated on the device at the end of
+    the epoch and the rank is read once from the HIP kernels, rounded to 2 decimals like the host function's.  Unset (the default),
+    the reference's per-step copy and CPU SVD."""
     n_views = 3 if loss_fn_intraMod else 1        # the intra loss needs the two extra half-bag views
     precision = set_model_precision(args.precision)
     use_autocast = precision in (torch.bfloat16, torch.float16)   # for fp32/fp64 torch disables autocast anyway
     in_warmup = epoch <= args.warmup_epochs       # note `<=`, as the reference (trainer.py:128)
     ssl_model.train()
+    # args.device_rank: the epoch's H&E embeddings stay on the device and the rank comes from the HIP kernels (utils.device_smooth_rank)
+    device_rank = bool(getattr(args, "device_rank", False))
 
     epoch_loss, busy_seconds, he_embeddings = 0.0, 0.0, []
     for batch_no, data in enumerate(dataloader):
@@ -192,7 +197,11 @@ def train_loop(args, loss_fn_interMod, loss_fn_interMod_local, loss_fn_intraMod,
             wsi_embs, token_embs = ssl_model(data, device=DEVICE, n_views=n_views)
             loss, has_pairs = calculate_losses(args.STAINS, loss_fn_interMod, loss_fn_interMod_local, loss_fn_intraMod,
                                                wsi_embs, token_embs, present, args)
-        he_embeddings.extend(wsi_embs['HE'][:, WHOLE_VIEW_POSITION, :, 0].detach().float().cpu().numpy())
+        he_step = wsi_embs['HE'][:, WHOLE_VIEW_POSITION, :, 0].detach().float()
+        if device_rank:
+            he_embeddings.append(he_step)                  # stays on the device: no copy, no synchronisation in the step
+        else:
+            he_embeddings.extend(he_step.cpu().numpy())
         if not has_pairs:
             print("Skipping batch with only HE")
             continue
@@ -206,5 +215,11 @@ def train_loop(args, loss_fn_interMod, loss_fn_interMod_local, loss_fn_intraMod,
         epoch_loss += loss.item()
         busy_seconds += time.time() - tick
 
+    if device_rank:
+        epoch_embeddings = torch.cat(he_embeddings) if he_embeddings else torch.zeros(0, 0)
+        rank = rounded_device_rank(epoch_embeddings)       # one host read per epoch
+        if rank is None:                                   # min(n, d) > 1024, or not on a ROCm device: the host function
+            rank = smooth_rank_measure(epoch_embeddings.cpu())
+        return epoch_loss, rank
     rank = smooth_rank_measure(torch.Tensor(np.array(he_embeddings)))
     return epoch_loss, rank

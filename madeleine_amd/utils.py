@@ -12,7 +12,7 @@ import torch
 DEVICE = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
 
-def run_inference(ssl_model, val_dataloader, config=None, torch_precision=None, bags_per_launch=None):
+def run_inference(ssl_model, val_dataloader, config=None, torch_precision=None, bags_per_launch=None, device_rank=False):
     """Slide-embedding extraction loop (utils.py:27-66): eval mode, no gradients, full bags through `ssl_model.encode_he` under the
     configured precision; returns ({"embeds": [n,512] fp32 array, "slide_ids": [...]}, smooth rank of the embeddings).  The dataloader
     yields (feats [1,N,D], slide_ids) like the reference's SimpleDataset (wsi_dataset.py:102-124).  Forward-only use of the HIP path:
@@ -24,7 +24,10 @@ def run_inference(ssl_model, val_dataloader, config=None, torch_precision=None, 
     `bags_per_launch` = None: 4 in fp32, where packing is bit-identical to one bag per call, and 1 under bf16 / fp16 autocast, where the
     Linear and gate kernels pick their tile from the packed row count: a slide's embedding then depends (at the bf16 rounding level,
     < 1e-2 relative) on which bags it is packed with, so extraction would not be reproducible across dataloader orders.  Pass
-    bags_per_launch > 1 explicitly to trade that for throughput (2.2k instead of ~1k bags/s on 30,000-patch bags)."""
+    bags_per_launch > 1 explicitly to trade that for throughput (2.2k instead of ~1k bags/s on 30,000-patch bags).
+    `device_rank=True`: the returned rank comes from the HIP kernels (device_smooth_rank) on the concatenated device embeddings, before
+    they are copied to the host, rounded like the reference's; min(n, 512) > 1024 or embeddings that are not on a ROCm device take
+    the host function as before."""
     ssl_model.eval()
     precision = torch_precision if torch_precision is not None else set_model_precision(config.precision)
     reduced = precision in (torch.bfloat16, torch.float16)      # for fp32 / fp64 torch disables autocast (SURVEY.md section 5)
@@ -57,8 +60,10 @@ def run_inference(ssl_model, val_dataloader, config=None, torch_precision=None, 
             if len(pending) >= bags_per_launch:
                 flush()
         flush()
-        embeds = torch.cat(outs).cpu().numpy() if outs else np.zeros((0, 512), dtype=np.float32)
-    return {"embeds": embeds, "slide_ids": slide_ids}, smooth_rank_measure(torch.Tensor(embeds))
+        on_device = torch.cat(outs) if outs else None
+        rank = rounded_device_rank(on_device) if device_rank and on_device is not None else None
+        embeds = on_device.cpu().numpy() if outs else np.zeros((0, 512), dtype=np.float32)
+    return {"embeds": embeds, "slide_ids": slide_ids}, rank if rank is not None else smooth_rank_measure(torch.Tensor(embeds))
 
 
 def extract_slide_level_embeddings(args, val_dataloaders, ssl_model):
@@ -127,6 +132,22 @@ def set_deterministic_mode(SEED, disable_cudnn=False):
     np.random.seed(SEED)
     if torch.cuda.is_available():
         torch.cuda.manual_seed_all(SEED)
+
+
+def device_smooth_rank(E, eps=1e-7):
+    """smooth_rank_measure's quantity from the HIP kernels: E [n, d] fp32 on a ROCm device (any row stride, min(n, d) <= 1024) -> a 0-d
+    fp64 device tensor, the UNROUNDED exp(entropy of the normalised singular values).  No host read (functional.smooth_rank)."""
+    from .functional import smooth_rank
+    return smooth_rank(E, eps)[0]
+
+
+def rounded_device_rank(E, eps=1e-7):
+    """round(device_smooth_rank(E), 2) as a Python float -- one host read -- or None where the kernels do not take E (not on a ROCm
+    device, min(n, d) > 1024): the caller then uses smooth_rank_measure."""
+    from .functional import smooth_rank_supported
+    if not smooth_rank_supported(E):
+        return None
+    return round(device_smooth_rank(E, eps).item(), 2)
 
 
 def smooth_rank_measure(embedding_matrix, eps=1e-7):
