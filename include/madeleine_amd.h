@@ -1001,6 +1001,60 @@ int mdl_smooth_rank(const float* E, int64_t ldE, int64_t n, int64_t d, uint64_t 
 int mdl_smooth_rank_marked(const float* E, int64_t ldE, int64_t n, int64_t d, uint64_t eps_bits, void* sigma, void* out, void* ws,
                            void* const* marks_host, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * X1 -- cross-stain retrieval: pair ranks and top-k neighbours over embedding matrices, on the device (ABI 26, additive).
+ * The label-free measure of what the contrastive loss optimises: at which rank does the embedding of a case's own IHC slide come back
+ * among all the others, given its H&E embedding -- and the "most similar slides" query over the same matrices.
+ *
+ * Q [n, d] queries, K [m, d] gallery: fp32, row strides ldq, ldk >= d ELEMENTS (every offset is formed in 64 bits), 4-byte aligned,
+ *   only read; Q and K may be the same pointer.  metric MDL_RETR_COSINE: rows scaled by 1 / max(|x|_2, 1e-12) (InfoNCE's rule);
+ *   MDL_RETR_DOT: rows as they are.  The similarities s_ij come from the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32) with fp32
+ *   accumulation, in tiles that are consumed where they are produced: the [n, m] matrix is never written to memory.
+ * ws: mdl_retrieval_ws_bytes(n, m, d, k, col_chunks) bytes, 16-byte aligned, contents need no initialisation: the scaled, zero-padded
+ *   copies of Q and K (rows to multiples of MDL_RETR_ROW_BLOCK / MDL_RETR_COL_TILE, columns to a multiple of 32) and, per column
+ *   chunk, two int32 counts and k 8-byte list entries per query row.  O((n + m) d + n k chunks), never O(n m).
+ * col_chunks: the gallery's MDL_RETR_COL_TILE-row tiles are cut into this many equal column ranges, each streamed by its own workgroup
+ *   per block of MDL_RETR_ROW_BLOCK queries (at most one chunk per tile); 0: enough of them for MDL_RETR_TARGET_WGS workgroups.
+ *   No output depends on it.
+ *
+ * Bits depend on the two rows alone.  s_ij is one fmaf chain over the d products (zero-padded to a multiple of 32, in an order fixed
+ *   by that length) of row i of Q and row j of K, each scaled by a factor computed from that row and d alone: not a function of n, m,
+ *   the strides, the tile or chunk geometry or the position of either row.  Two identical gallery rows give bit-identical
+ *   similarities: ties are real ties.
+ * Order.  Every comparison is made on an ordered 32-bit key of the similarity: descending by value, -0 = +0, and every NaN is one
+ *   key BELOW -inf, so a NaN similarity is never retrieved ahead of a number (the opposite of mdl_attn_rank's choice, deliberately:
+ *   a model that emits NaN must score worst).  Ties are broken by the lower gallery index.  A total order: every output is
+ *   independent of scheduling and of col_chunks.
+ * paired = 1 (n <= m; the partner of query i is gallery row i):
+ *   pair_sim [n] fp32   s_ii, from the same tile code as every other similarity
+ *   greater  [n] int32  #{j != i : key(s_ij) before key(s_ii)}
+ *   equal    [n] int32  #{j != i : key(s_ij) == key(s_ii)}
+ *   A NaN s_ii gives greater = m - 1, equal = 0.  The rank of the partner is 1 + greater (optimistic) .. 1 + greater + equal.
+ * k >= 1: topk_idx [n, k] int32 and topk_val [n, k] fp32, the first k gallery rows of every query in the order above with their
+ *   similarities (-0 as +0, a NaN as the canonical quiet NaN); with exclude_diag = 1 (neighbours inside one cohort, Q is K) column i is
+ *   skipped for row i.  Entries past the number of candidates are -1 / -inf.  k = 0 skips it.
+ * Output pointers of a mode that is off may be NULL (greater / equal / pair_sim with paired = 0, topk_* with k = 0).
+ * Three launches (scale, stream, finish) on the caller's stream; no allocation, no atomics, no host read, no workgroup waits on another.
+ *
+ * Refusals, in this order, before any launch.  MDL_E_ARG: Q, K, ws or an output of a mode that is on NULL; n, m or d < 1; ldq or
+ *   ldk < d; k < 0; col_chunks < 0; an unknown metric; paired or exclude_diag not 0 / 1; both of them set; paired with n > m; neither
+ *   paired nor k >= 1.  MDL_E_ALIGN: Q, K or an output not 4-byte, ws not 16-byte aligned.  MDL_E_UNSUPPORTED: n or m above
+ *   MDL_RETR_MAX_ROWS, d above MDL_RETR_MAX_D, k above MDL_RETR_MAX_K, col_chunks above MDL_RETR_MAX_CHUNKS, n * ldq or m * ldk
+ *   beyond 2^61.  mdl_retrieval_ws_bytes returns the same negative codes for its sizes. */
+#define MDL_RETR_COSINE 0
+#define MDL_RETR_DOT 1
+#define MDL_RETR_MAX_ROWS 1048576
+#define MDL_RETR_MAX_D 2048
+#define MDL_RETR_MAX_K 64
+#define MDL_RETR_MAX_CHUNKS 64
+#define MDL_RETR_ROW_BLOCK 128
+#define MDL_RETR_COL_TILE 128
+#define MDL_RETR_TARGET_WGS 512
+int64_t mdl_retrieval_ws_bytes(int64_t n, int64_t m, int64_t d, int k, int col_chunks);
+int mdl_retrieval(const float* Q, int64_t ldq, const float* K, int64_t ldk, int64_t n, int64_t m, int64_t d, int metric, int paired,
+                  int exclude_diag, int k, int col_chunks, int32_t* greater, int32_t* equal, float* pair_sim, int32_t* topk_idx,
+                  float* topk_val, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

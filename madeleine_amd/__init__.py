@@ -9,6 +9,7 @@ madeleine.utils.loss, madeleine.utils.trainer):
     from madeleine_amd import DeviceSlideStore   # the cohort's features resident on the device, batches drawn by one kernel
     from madeleine_amd import linear_probe       # the few-shot linear-probing protocol, every (task, k, fold) fit in one batch of launches
     from madeleine_amd import device_smooth_rank # the model-selection criterion (smooth rank of the embeddings) without a host SVD
+    from madeleine_amd import cross_stain_retrieval  # at which rank a case's own IHC slide comes back for its H&E slide, and the reverse
 
 The numeric work runs in csrc/libmadeleine_amd.so through the C ABI of include/madeleine_amd.h.
 Importing this package does not load the library (so model construction / state_dict handling works on
@@ -18,6 +19,7 @@ from .abmil import BatchedABMIL
 from .loss import GOT, InfoNCE, info_nce, init_intra_wsi_loss_function
 from .model import ABMILEmbedder, MADELEINE, create_model
 from .optim import AdamW
+from .retrieval import cross_stain_retrieval, retrieval_metrics, slide_neighbours
 from .store import DeviceSlideStore, PackedBags
 from .trainer import calculate_losses, train_loop
 from .utils import create_model_from_pretrained, device_smooth_rank, extract_slide_level_embeddings, load_checkpoint, run_inference
@@ -25,7 +27,7 @@ from .utils import create_model_from_pretrained, device_smooth_rank, extract_sli
 __all__ = ["MADELEINE", "ABMILEmbedder", "BatchedABMIL", "create_model", "InfoNCE", "info_nce", "GOT",
            "init_intra_wsi_loss_function", "calculate_losses", "train_loop", "run_inference", "extract_slide_level_embeddings",
            "load_checkpoint", "create_model_from_pretrained", "AdamW", "DeviceSlideStore", "PackedBags", "probe_splits", "fit_logistic",
-           "linear_probe", "device_smooth_rank"]
+           "linear_probe", "device_smooth_rank", "cross_stain_retrieval", "retrieval_metrics", "slide_neighbours"]
 __version__ = "0.2"
 _PROBE = ("probe_splits", "fit_logistic", "linear_probe")
 

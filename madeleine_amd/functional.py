@@ -7,6 +7,7 @@ points; anything else raises (there is no CPU or eager fallback).
 
 Layouts (see include/madeleine_amd.h): token embeddings are head-major [T, H*512]; scores [T, H].
 """
+import collections
 import os
 import threading
 from typing import Optional
@@ -2053,3 +2054,82 @@ def smooth_rank_stages(E, eps=1e-7):
     events[3].synchronize()
     ms = [events[i].elapsed_time(events[i + 1]) for i in range(3)]
     return out[0], sigma, dict(zip(("gram", "tridiagonal", "eigen_finish"), ms))
+
+
+# ---- X1: cross-stain retrieval (mdl_retrieval).  Pair ranks and top-k neighbours from streamed similarity tiles.  No autograd ----
+RETR_MAX_ROWS, RETR_MAX_D, RETR_MAX_K, RETR_MAX_CHUNKS, RETR_ROW_BLOCK, RETR_COL_TILE, RETR_TARGET_WGS = (
+    _native._DEFINES["MDL_RETR_" + k] for k in ("MAX_ROWS", "MAX_D", "MAX_K", "MAX_CHUNKS", "ROW_BLOCK", "COL_TILE", "TARGET_WGS"))
+RETR_METRICS = {"cosine": _native._DEFINES["MDL_RETR_COSINE"], "dot": _native._DEFINES["MDL_RETR_DOT"]}
+_RETR_LIMIT = ("retrieval supports n, m <= %d, d <= %d, k <= %d and col_chunks <= %d "
+               "(got Q [%d, %d], K [%d, %d], k %d, col_chunks %d)")
+
+Retrieval = collections.namedtuple("Retrieval", ("greater", "equal", "pair_sim", "topk_idx", "topk_val"))
+
+
+def retrieval_chunks(n, m, col_chunks=0):
+    """(chunks, tiles_per_chunk) the launcher uses for n queries and m gallery rows: col_chunks (0: its own choice) cut down to whole
+    RETR_COL_TILE-row tiles.  Host arithmetic, the same as csrc/retrieval.hip's."""
+    row_blocks, col_tiles = -(-n // RETR_ROW_BLOCK), -(-m // RETR_COL_TILE)
+    c = col_chunks if col_chunks > 0 else -(-RETR_TARGET_WGS // row_blocks)
+    c = max(1, min(c, RETR_MAX_CHUNKS, col_tiles))
+    per = -(-col_tiles // c)
+    return -(-col_tiles // per), per
+
+
+def _retr_matrix(t, name):
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2:
+        raise ValueError("madeleine_amd: retrieval needs %s as a 2-D float32 tensor (got %s)"
+                         % (name, "%s %s" % (t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__))
+    rows, d = t.shape
+    if rows < 1 or d < 1:
+        raise ValueError("madeleine_amd: retrieval needs at least one row and one column in %s (got [%d, %d])" % (name, rows, d))
+    ld = t.stride(0) if rows > 1 else d
+    if (d > 1 and t.stride(1) != 1) or ld < d:
+        raise ValueError("madeleine_amd: retrieval needs unit column stride and a row stride >= d in %s (got strides %s)"
+                         % (name, tuple(t.stride())))
+    return rows, d, ld
+
+
+def retrieval(Q, K=None, k=0, metric='cosine', paired=True, exclude_diag=False, col_chunks=0):
+    """Retrieval of the rows of K [m, d] by the rows of Q [n, d] (fp32 on the device, unit column stride, any row stride >= d; K None: Q
+    itself) -> Retrieval(greater, equal, pair_sim, topk_idx, topk_val) on the device.  metric 'cosine' (rows scaled by 1 / max(|x|,
+    1e-12)) or 'dot'.  paired (n <= m, the partner of query i is gallery row i): pair_sim [n] fp32 = s_ii, greater / equal [n] int32 =
+    the gallery rows j != i whose similarity comes before / ties with s_ii; a NaN s_ii gives m - 1 and 0.  k >= 1: topk_idx [n, k]
+    int32, topk_val [n, k] fp32, the k best gallery rows of every query (padding -1 / -inf), column i skipped for row i with
+    exclude_diag (not together with paired).  Order: descending value, -0 = +0, NaNs below -inf, ties by the lower index.  Fields of a
+    mode that is off are None.  Exact-fp32 MFMA similarities from streamed tiles (include/madeleine_amd.h, X1): the [n, m] matrix is
+    never formed, the bits of s_ij depend on the two rows alone and no output depends on col_chunks (0: the launcher's choice).  Three
+    launches on the current stream, no host read.  ValueError for dtype / device / shape / arguments, NotImplementedError past the
+    limits."""
+    K = Q if K is None else K
+    n, d, ldq = _retr_matrix(Q, "Q")
+    m, dk, ldk = _retr_matrix(K, "K")
+    if dk != d:
+        raise ValueError("madeleine_amd: retrieval needs Q and K of one width (got %d and %d)" % (d, dk))
+    if metric not in RETR_METRICS:
+        raise ValueError("madeleine_amd: retrieval metric must be 'cosine' or 'dot' (got %r)" % (metric,))
+    k, col_chunks, paired, exclude_diag = int(k), int(col_chunks), bool(paired), bool(exclude_diag)
+    if k < 0 or col_chunks < 0:
+        raise ValueError("madeleine_amd: retrieval needs k >= 0 and col_chunks >= 0 (got %d, %d)" % (k, col_chunks))
+    if paired and exclude_diag:
+        raise ValueError("madeleine_amd: retrieval takes paired or exclude_diag, not both")
+    if paired and n > m:
+        raise ValueError("madeleine_amd: paired retrieval needs n <= m (got %d queries, %d gallery rows)" % (n, m))
+    if not paired and k == 0:
+        raise ValueError("madeleine_amd: retrieval needs paired=True or k >= 1")
+    refusal = (_RETR_LIMIT, RETR_MAX_ROWS, RETR_MAX_D, RETR_MAX_K, RETR_MAX_CHUNKS, n, d, m, d, k, col_chunks)
+    if max(n, m) > RETR_MAX_ROWS or d > RETR_MAX_D or k > RETR_MAX_K or col_chunks > RETR_MAX_CHUNKS:
+        raise NotImplementedError("madeleine_amd: " + refusal[0] % refusal[1:])
+    if not Q.is_cuda or K.device != Q.device:
+        raise ValueError("madeleine_amd: Q and K must live on one ROCm device (got %s, %s); there is no CPU fallback" % (Q.device, K.device))
+    dev = Q.device
+    ws = _ws_for("mdl_retrieval_ws_bytes", dev, n, m, d, k, col_chunks, refusal=refusal)
+    greater = torch.empty(n, device=dev, dtype=torch.int32) if paired else None
+    equal = torch.empty(n, device=dev, dtype=torch.int32) if paired else None
+    pair_sim = torch.empty(n, device=dev, dtype=torch.float32) if paired else None
+    ti = torch.empty(n, k, device=dev, dtype=torch.int32) if k else None
+    tv = torch.empty(n, k, device=dev, dtype=torch.float32) if k else None
+    with _timed("retrieval", ("flop", 2.0 * n * m * d)):
+        _call("mdl_retrieval", Q, ldq, K, ldk, n, m, d, RETR_METRICS[metric], int(paired), int(exclude_diag), k, col_chunks, greater, equal,
+              pair_sim, ti, tv, ws, _stream(), unsupported=refusal)
+    return Retrieval(greater, equal, pair_sim, ti, tv)

@@ -417,6 +417,34 @@ class DeviceSlideStore:
         embeds = torch.cat(outs) if outs else torch.zeros(0, 512, dtype=torch.float32, device=self.device)
         return self._embedding_result(embeds, cases, rank)
 
+    def embed_modality(self, model, modality, case_indices=None, bags_per_launch=None, max_tokens=None, precision=None,
+                       host_wgs=0) -> dict:
+        """embed() for ANY stain of any model: the same result dict, planning, grouping, eval mode under torch.no_grad() (the training
+        flag is restored) and autocast rule.  A model without stain encoding goes through encode_packed, as embed() does.  A model with
+        stain encoding goes through attend_packed(..., stain_idx=modality): every bag gets embedding(modality), H&E index 0 -- the
+        reference's eval-branch rule (Model.py:162-203) -- which is what embed() refuses for modality != 0.  What cross-stain retrieval
+        (madeleine_amd.retrieval.cross_stain_retrieval) embeds both sides with."""
+        self._require_device("embed_modality")
+        cases, _, lens = self._modality_plan(case_indices, modality, max_tokens)
+        reduced = precision in (torch.bfloat16, torch.float16)
+        groups = self._launch_groups(cases, lens, bags_per_launch, reduced)
+        stained = bool(getattr(model, "stain_encoding", False))
+        was_training = model.training
+        model.eval()
+        outs = []
+        try:
+            with torch.no_grad():
+                for group in groups:
+                    packed = self.pack_modality(group, modality, max_tokens, host_wgs=host_wgs)
+                    with torch.autocast(device_type="cuda", dtype=precision if reduced else None, enabled=reduced):
+                        e = model.attend_packed(packed, self.device, stain_idx=modality)[0] if stained \
+                            else model.encode_packed(packed, self.device)
+                    outs.append(e.float())
+        finally:
+            model.train(was_training)
+        embeds = torch.cat(outs) if outs else torch.zeros(0, 512, dtype=torch.float32, device=self.device)
+        return self._embedding_result(embeds, cases)
+
     @staticmethod
     def _launch_groups(cases, lens, bags_per_launch, reduced):
         """embed's grouping (run_inference's): up to bags_per_launch bags per launch set (None: 4 in fp32, 1 under autocast), a bag of at
