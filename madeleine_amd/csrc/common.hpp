@@ -114,7 +114,10 @@ __device__ __forceinline__ float fast_tanh(float x) { return 1.f - 2.f * __built
 // (round 5: the gate epilogue is VALU-bound beside the matrix cores, every instruction removed is wall time):
 //   tanh(z)    = 1 - 2 / (1 + 2^(acc * (2 log2e s) + 2 log2e bias))       -> gate_tanh_pre(acc, 2 log2e s, 2 log2e bias)
 //   sigmoid(z) = 1 / (1 + 2^(acc * (-log2e s) - log2e bias))              -> gate_sigmoid_pre(acc, -log2e s, -log2e bias)
-// one fma + v_exp_f32 + add + v_rcp_f32 (+ fma): 5 and 4 instructions instead of 7 and 6.
+// one fma + v_exp_f32 + add + v_rcp_f32 (+ fma): 5 and 4 instructions instead of 7 and 6.  Measured on the device against fp64
+// (tests/test_activation_domain_gpu.py): tanh within 1.9e-7, sigmoid within 9.2e-8 when the argument comes through the bias alone; the
+// folded bias is rounded before the FMA, so where acc s and bias cancel the error in z is up to 2^-24 (|bias| + |z|): 4.3e-7 for tanh at
+// |bias| <= 8.  Exactly +-1 / 1 from |z| = 20 on, sigmoid exactly 0 from z = -100 down, no NaN at any finite argument.
 constexpr float MDL_LOG2E = 1.4426950408889634f;
 __device__ __forceinline__ float gate_tanh_pre(float acc, float s2, float b2) {
     return fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(fmaf(acc, s2, b2))), 1.f);
