@@ -508,6 +508,8 @@ class _GOTMulti(torch.autograd.Function):
         dev = tensors[0].device
         outs, states = [], []
         ctx.shapes = [(V.shape, Q.shape) for V, Q in probs]
+        # the implementation's state holds the token tensors by address; saving them here puts them under autograd's version check
+        ctx.save_for_backward(*[x for pair in probs for x in pair])
         live = [s for s in range(S) if probs[s][0].shape[0] > 0]
         ctx.batched = None
         if getattr(impl, "can_batch", None) and impl.can_batch([probs[s] for s in live]):
@@ -535,6 +537,7 @@ class _GOTMulti(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_outs):
         impl = ctx.impl
+        ctx.saved_tensors      # (raises when a token tensor was modified in place since the forward)
         dev = d_outs.device
         d_outs = d_outs.contiguous()
         if ctx.batched is not None:

@@ -676,10 +676,13 @@ class PreAttnBlockFn(torch.autograd.Function):
         with _timed("ln_gelu_drop_fwd", ("byte", (3.0 if want_fp32 else 2.0) * T * N * 4)):
             _call("mdl_ln_gelu_drop_fwd_split", y, lin_bias, gamma, beta, out, img, scale, mean, rstd, T, N, float(eps), float(p_drop),
                   int(seed), keep, row_inv, rstd_max, _stream(), unsupported=(_LN_WIDTHS, N))
-        ctx.save_for_backward(xi.data, xi.scale, W, y, gamma, beta, mean, rstd, lin_bias if lin_bias is not None else torch.empty(0),
-                              row_inv if row_inv is not None else torch.empty(0), rstd_max if rstd_max is not None else torch.empty(0))
-        ctx.cfg = (float(p_drop), int(seed), keep, lin_bias is not None, bool(want_fp32), T, K, N, x_scale is not None)
-        ctx.groups = None if gbias is None else (cu_groups, int(gbias.shape[0]))
+        none = torch.empty(0)
+        # (the keep mask and the group offsets are saved tensors too: an in-place change before the backward raises instead of being read)
+        ctx.save_for_backward(xi.data, xi.scale, W, y, gamma, beta, mean, rstd, lin_bias if lin_bias is not None else none,
+                              row_inv if row_inv is not None else none, rstd_max if rstd_max is not None else none,
+                              keep if keep is not None else none, cu_groups if gbias is not None else none)
+        ctx.cfg = (float(p_drop), int(seed), keep is not None, lin_bias is not None, bool(want_fp32), T, K, N, x_scale is not None)
+        ctx.groups = None if gbias is None else int(gbias.shape[0])
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(scale)
         if want_fp32:
@@ -691,8 +694,9 @@ class PreAttnBlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_img, _d_scale, d_out):
-        xdata, xscale, W, y, gamma, beta, mean, rstd, lin_bias, row_inv, rstd_max = ctx.saved_tensors
-        p_drop, seed, keep, has_bias, want_fp32, T, K, N, x_is_image = ctx.cfg
+        xdata, xscale, W, y, gamma, beta, mean, rstd, lin_bias, row_inv, rstd_max, keep, cu_groups = ctx.saved_tensors
+        p_drop, seed, has_keep, has_bias, want_fp32, T, K, N, x_is_image = ctx.cfg
+        keep = keep if has_keep else None
         lin_bias = lin_bias if has_bias else None
         rstd_max = rstd_max if rstd_max.numel() else None
         # first block (row-scaled input image): the gradient image carries row_inv[r] dx[r][:], so that the row factors of the two images
@@ -710,7 +714,7 @@ class PreAttnBlockFn(torch.autograd.Function):
         amax = _take_absmax(dy)
         groups, d_gbias = (), None
         if ctx.groups is not None:
-            cu_groups, G = ctx.groups
+            G = ctx.groups
             d_gbias = torch.empty(G, N, device=dev, dtype=torch.float32)
             groups = (cu_groups, G, d_gbias)
         ws = _ws_for("mdl_ln_gelu_drop_bwd%s_ws_bytes" % ("_groups" if groups else ""), dev, T, N, *groups[1:2])
@@ -813,15 +817,17 @@ class GateScoresFn(torch.autograd.Function):
         scores, act_a, act_b = gate_fwd_raw(Ei if Ei is not None else E2d, Wa, ba, Wb, bb, wc, bc, p_drop, seed, keep_a, keep_b, need)
         if need:
             none = torch.empty(0)
-            ctx.save_for_backward(E2d, Wa, Wb, wc, act_a, act_b, Ei.data if Ei is not None else none, Ei.scale if Ei is not None else none)
-            ctx.drop = (p_drop, seed, keep_a, keep_b)
+            ctx.save_for_backward(E2d, Wa, Wb, wc, act_a, act_b, Ei.data if Ei is not None else none, Ei.scale if Ei is not None else none,
+                                  keep_a if keep_a is not None else none, keep_b if keep_b is not None else none)
+            ctx.drop = (p_drop, seed, keep_a is not None, keep_b is not None)
             ctx.has_image = Ei is not None
         return scores
 
     @staticmethod
     def backward(ctx, d_scores):
-        E2d, Wa, Wb, wc, act_a, act_b, Eidata, Eiscale = ctx.saved_tensors
-        p_drop, seed, keep_a, keep_b = ctx.drop
+        E2d, Wa, Wb, wc, act_a, act_b, Eidata, Eiscale, keep_a, keep_b = ctx.saved_tensors
+        p_drop, seed, has_keep_a, has_keep_b = ctx.drop
+        keep_a, keep_b = keep_a if has_keep_a else None, keep_b if has_keep_b else None
         d_scores = d_scores.float().contiguous()
         dE = torch.empty_like(E2d)
         src = SplitImage(Eidata, Eiscale, E2d.shape[0], E2d.shape[1]) if ctx.has_image else E2d
@@ -842,13 +848,17 @@ class SoftmaxPoolFn(torch.autograd.Function):
         n_bags, N, max_len, E2d = _bag_geometry(E, cu_seqlens, max_len)
         s2d = scores.reshape(E2d.shape[0], -1)
         pooled, m, l = pool_fwd_raw(E2d, s2d, n_bags, N, cu_seqlens, max_len)
-        ctx.save_for_backward(E2d, s2d, pooled, m, l, cu_seqlens if cu_seqlens is not None else torch.empty(0))
+        # (the inputs themselves are saved, not the 2-D views made here: a view made inside forward fails the version check of a
+        # modified base with an error about no_grad views instead of "modified by an inplace operation")
+        ctx.save_for_backward(E, scores, pooled, m, l, cu_seqlens if cu_seqlens is not None else torch.empty(0))
         ctx.geom = (n_bags, N, max_len, cu_seqlens is not None, E.shape, scores.shape)
         return pooled
 
     @staticmethod
     def backward(ctx, d_pooled):
-        E2d, s2d, pooled, m, l, cu = ctx.saved_tensors
+        E, scores, pooled, m, l, cu = ctx.saved_tensors
+        E2d = E.reshape(-1, E.shape[-1])
+        s2d = scores.reshape(E2d.shape[0], -1)
         n_bags, N, max_len, ragged, e_shape, s_shape = ctx.geom
         cu = cu if ragged else None
         dE = torch.empty_like(E2d)
@@ -868,13 +878,15 @@ class WeightedPoolFn(torch.autograd.Function):
         n_bags, N, max_len, E2d = _bag_geometry(E, cu_seqlens, max_len)
         w2d = weights.reshape(E2d.shape[0], -1)
         pooled, _, _ = _pool_fwd("wpool_fwd", ("pool_fwd",), E2d, w2d, n_bags, max_len, (n_bags, N, cu_seqlens, max_len))
-        ctx.save_for_backward(E2d, w2d, cu_seqlens if cu_seqlens is not None else torch.empty(0))
+        ctx.save_for_backward(E, weights, cu_seqlens if cu_seqlens is not None else torch.empty(0))     # (the inputs, as SoftmaxPoolFn)
         ctx.geom = (n_bags, N, max_len, cu_seqlens is not None, E.shape, weights.shape)
         return pooled
 
     @staticmethod
     def backward(ctx, d_pooled):
-        E2d, w2d, cu = ctx.saved_tensors
+        E, weights, cu = ctx.saved_tensors
+        E2d = E.reshape(-1, E.shape[-1])
+        w2d = weights.reshape(E2d.shape[0], -1)
         n_bags, N, max_len, ragged, e_shape, w_shape = ctx.geom
         cu = cu if ragged else None
         dE = torch.empty_like(E2d)
@@ -981,14 +993,16 @@ class AttnPoolFn(torch.autograd.Function):
             flat = [t for st in vstate for t in st]
             none = torch.empty(0)
             # (the image of E travels as saved tensors like everything else: saved-tensor hooks, retain_graph and version checks apply)
-            ctx.save_for_backward(E2d, Wa, Wb, wc, act_a if not recompute else none, act_b if not recompute else none, scores, pooled, m, l,
+            # (E itself, not the 2-D view of it made here: see SoftmaxPoolFn)
+            ctx.save_for_backward(E, Wa, Wb, wc, act_a if not recompute else none, act_b if not recompute else none, scores, pooled, m, l,
                                   cu_seqlens if cu_seqlens is not None else none, Wtok if Wtok is not None else none,
                                   Ei.data if Ei is not None else none, Ei.scale if Ei is not None else none,
-                                  ba if recompute else none, bb if recompute else none, bc if recompute else none, *views, *flat,
+                                  ba if recompute else none, bb if recompute else none, bc if recompute else none,
+                                  keep_a if keep_a is not None else none, keep_b if keep_b is not None else none, *views, *flat,
                                   *(rviews[:2] if rviews is not None else ()), *rstate)
             ctx.rview_max = None if rviews is None else rviews[2]
             ctx.recompute = recompute
-            ctx.cfg = (p_drop, seed, keep_a, keep_b, n_bags, N, max_len, cu_seqlens is not None, E.shape, len(views),
+            ctx.cfg = (p_drop, seed, keep_a is not None, keep_b is not None, n_bags, N, max_len, cu_seqlens is not None, E.shape, len(views),
                        Wtok is not None, btok is not None)
             ctx.e_only_image = bool(e_only_image)
             ctx.has_image = Ei is not None
@@ -1000,11 +1014,13 @@ class AttnPoolFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_pooled, d_scores_in, d_tok):
-        p_drop, seed, keep_a, keep_b, n_bags, N, max_len, ragged, e_shape, V, has_tok, has_btok = ctx.cfg
+        p_drop, seed, has_keep_a, has_keep_b, n_bags, N, max_len, ragged, e_shape, V, has_tok, has_btok = ctx.cfg
         saved = ctx.saved_tensors
-        E2d, Wa, Wb, wc, act_a, act_b, scores, pooled, m, l, cu, Wtok, Eidata, Eiscale, ba, bb, bc = saved[:17]
-        views, vflat = saved[17:17 + V], saved[17 + V:17 + 4 * V]
-        rview = None if ctx.rview_max is None else tuple(saved[17 + 4 * V:]) + (ctx.rview_max,)   # (perm, vcu, pooled, m, l, max_view_len)
+        E, Wa, Wb, wc, act_a, act_b, scores, pooled, m, l, cu, Wtok, Eidata, Eiscale, ba, bb, bc, keep_a, keep_b = saved[:19]
+        E2d = E.reshape(-1, E.shape[-1])
+        keep_a, keep_b = keep_a if has_keep_a else None, keep_b if has_keep_b else None
+        views, vflat = saved[19:19 + V], saved[19 + V:19 + 4 * V]
+        rview = None if ctx.rview_max is None else tuple(saved[19 + 4 * V:]) + (ctx.rview_max,)   # (perm, vcu, pooled, m, l, max_view_len)
         n_out = 1 + V + (2 if rview is not None else 0)
         Ei = SplitImage(Eidata, Eiscale, E2d.shape[0], E2d.shape[1]) if ctx.has_image else None
         if ctx.recompute:   # rebuild the activations: the same kernel, seed and masks as the forward -> the same bits
@@ -1132,14 +1148,18 @@ class LNGeluDropFn(torch.autograd.Function):
         with _timed("ln_gelu_drop_fwd", ("byte", 2.0 * x.numel() * x.element_size())):
             _call(name + _sfx(x), x, bias, gamma, beta, y, mean, rstd, rows, W, float(eps), float(p_drop), int(seed), keep, *groups, _stream(),
                   unsupported=unsupported)
-        ctx.save_for_backward(x, gamma, beta, mean, rstd, bias if bias is not None else torch.empty(0))
-        ctx.cfg = (float(p_drop), int(seed), keep, bias is not None, groups)
+        none = torch.empty(0)
+        ctx.save_for_backward(x, gamma, beta, mean, rstd, bias if bias is not None else none, keep if keep is not None else none,
+                              cu_groups if cu_groups is not None else none)
+        ctx.cfg = (float(p_drop), int(seed), keep is not None, bias is not None, groups[1:])
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, gamma, beta, mean, rstd, bias = ctx.saved_tensors
-        p_drop, seed, keep, has_bias, groups = ctx.cfg
+        x, gamma, beta, mean, rstd, bias, keep, cu_groups = ctx.saved_tensors
+        p_drop, seed, has_keep, has_bias, groups = ctx.cfg
+        keep = keep if has_keep else None
+        groups = (cu_groups,) + groups if groups else ()
         bias = bias if has_bias else None
         W = x.shape[-1]
         rows = x.numel() // W
@@ -1307,7 +1327,7 @@ class InfoNCENegFn(torch.autograd.Function):
         work = ("byte", 4.0 * Neg.numel()) if paired else ("flop", 2.0 * N * M * D)
         with _timed("infonce_neg_fwd", work):
             _call("mdl_infonce_neg_fwd", Q, P, Neg, loss, rows, N, M, D, int(paired), float(temperature), ws, _stream())
-        ctx.save_for_backward(ws, Neg)
+        ctx.save_for_backward(ws, Neg, Q, P)     # (Q, P: the backward reads what the forward left of them in ws; saved for the version check)
         ctx.cfg = (N, M, D, Dq, float(temperature), bool(paired), bool(per_row))
         if not per_row:
             rows = loss.new_empty(0)
@@ -1316,7 +1336,7 @@ class InfoNCENegFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_loss, d_rows):
-        ws, Neg = ctx.saved_tensors
+        ws, Neg, _Q, _P = ctx.saved_tensors
         N, M, D, Dq, temperature, paired, per_row = ctx.cfg
         dev = Neg.device
         dQ = torch.empty(N, Dq, device=dev, dtype=torch.float32)
