@@ -1055,6 +1055,74 @@ int mdl_retrieval(const float* Q, int64_t ldq, const float* K, int64_t ldk, int6
                   int exclude_diag, int k, int col_chunks, int32_t* greater, int32_t* equal, float* pair_sim, int32_t* topk_idx,
                   float* topk_val, void* ws, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * S1-S2 -- the survival probe: P independent ridge-penalised Cox proportional-hazards fits over one embedding matrix and, per fit,
+ * Harrell's concordance index and a median-split log-rank statistic over the held-out cases (ABI 26, additive).  The reference names
+ * patient stratification and prognostic prediction as uses of a slide embedding and ships no code for them; all problems of a
+ * protocol (cross-validation folds x repeats x endpoints) go through one launch sequence.  The decision values between the two calls
+ * come from mdl_probe_scores with C = 2 and a zero intercept: z [P, S] = X W_p^T for ALL S cases.
+ *
+ * X [S, d] fp32, row stride ldX >= d ELEMENTS, any d >= 1; only read.
+ * time (fp32), event (int32): the vectors of problem p are time[p * ldt .. p * ldt + S) and event[p * lde .. p * lde + S); a stride of 0
+ *   shares one vector among all problems (several endpoints go through one call with strides S).  event: 1 = event, 0 = censored, any
+ *   other value (-1) = no follow-up: such a case is in neither the training nor the test set.
+ * train_idx [P, n_max] (int32), n_train [P] (int32): problem p trains on cases train_idx[p, 0 .. n_train[p]); the rest of the row is
+ *   never read.  1 <= n_train[p] <= n_max <= MDL_COX_MAX_TRAIN.  Every case with event 0 / 1 that is not a training case is a test case.
+ *
+ * mdl_cox_fit minimises, per problem, with Breslow ties, no intercept and the risk set R_i = {j in training : t_j >= t_i},
+ *   F(w) = cost * sum_{i : event_i = 1} [ log sum_{j in R_i} exp(x_j . w) - x_i . w ] + 1/2 |w|^2
+ * by Newton-CG in the span of the training rows (w = X_t^T a).  Three launches: an order kernel checks every training list and sorts it
+ * by (time descending, case index ascending) -- a total order, so the result's bits do not depend on the order of the caller's list --,
+ * a Gram kernel forms G = X_t X_t^T over the sorted rows in the workspace, and one workgroup per problem iterates; after the sort the
+ * risk-set sums are prefix sums read at the end of a row's tie group, the sums over event times suffix sums read at its start.  The
+ * decision values of every Newton step are formed from w itself, G only serves the Hessian-vector products.  No workgroup waits on
+ * another; every loop is bounded (max_iter Newton steps, MDL_COX_CG_MAX CG steps each, MDL_COX_LS_MAX step halvings).
+ * Stop rule, relative: with g0 the inf-norm of the primal gradient at w = 0, a problem has converged when that norm at w (evaluated in
+ * fp32 from w itself) is <= gtol * g0.  The iteration aims at 0.03 gtol g0 and, once below gtol g0, goes on only while a step still
+ * halves the norm; it stops after max_iter steps at the latest.  (The fp32 floor of the norm grows with cost and n; no absolute bound
+ * fits all problems.)  A training list without an event has g0 = 0 and the optimum w = 0: zeros, converged = 1.
+ * Range of the decision values: the exponentials are shifted by the maximum over ALL training rows, so no exp overflows; but the
+ * risk-set sum of an event whose whole risk set lies more than ~87 below that maximum underflows to 0 in fp32.  Along the line search
+ * that only halves the step; at an accepted iterate it ends the fit with a NaN residual and converged = 0 (never a wrong result reported
+ * as converged).  Decision values of a ridge fit on embeddings span a few units, far from it; there is no per-risk-set shift.
+ * W_out [P, d]; thr_out [P]: the median of the training rows' final decision values (the mean of the two middle values for even n,
+ * in fp32) -- formed in the summation order of mdl_probe_scores, so it is the median of that call's z over the training rows bit for bit;
+ * info_out [P, 4] fp32: Newton steps taken, converged (1 / 0), the final inf-norm of the gradient (absolute), CG steps in all.
+ * A problem is refused -- NaN in its W, threshold and residual, converged = 0, the others unaffected -- when n_train is outside
+ * [1, n_max], a training index is outside [0, S) or repeated, a training case has an event other than 0 / 1 or a time that is NaN,
+ * infinite or negative.  Results depend on the problem alone (not on P, p, n_max or the order of its list).
+ *
+ * mdl_surv_metrics, over the test cases of problem p, from z [P, S] and thr [P] (only read).  Here n_train[p] = 0 is legal too (no
+ * training list: every case with follow-up is a test case); a value outside [0, n_max] is clamped into it, and training indices
+ * outside [0, S) are passed over:
+ *   concordance: the pair (i, j) is comparable iff event_i = 1 and (t_i < t_j, or t_i = t_j and event_j = 0); it counts 2 if z_i > z_j,
+ *     1 if z_i = z_j.  c_index_out [P] fp64 = count / (2 comparable), NaN without a comparable pair.
+ *   stratification: a test case is high risk iff z > thr[p].  With, per test event case i, n_i = #{test j : t_j >= t_i}, h_i the same
+ *     count inside the high group and d_i = #{test events j : t_j = t_i}:  O - E = sum_i [1(i high) - h_i / n_i],
+ *     V = sum_{i : n_i > 1} (h_i / n_i)(1 - h_i / n_i)(n_i - d_i) / (n_i - 1) -- the log-rank sums over distinct event times, written
+ *     per individual -- and chi2_out [P] fp64 = (O - E)^2 / V, NaN when V = 0.  One degree of freedom: p = erfc(sqrt(chi2 / 2)).
+ *   counts_out [P, 6] int32: concordance numerator, comparable pairs, test cases, high-group size, events in the low group, events in
+ *     the high group.
+ *   All counting is exact, in integers (S <= MDL_PROBE_MAX_CASES keeps every count inside int32); one integer atomic per workgroup, whose
+ *   order cannot change a bit.  The two sums run in double in a fixed order.  A NaN thr[p] (a refused fit) gives NaN in both doubles.
+ *   c_index_out and chi2_out are fp64 arrays (the header has no double), 8-byte aligned.
+ *
+ * Workspaces: 16-byte aligned, sizes from the *_ws_bytes queries, contents need no initialisation.
+ * MDL_E_UNSUPPORTED: n_max > MDL_COX_MAX_TRAIN, S > MDL_PROBE_MAX_CASES (metrics), a launch grid or an output index beyond int32.
+ * MDL_E_ARG: null pointers, ldX < d, sizes < 1, ldt / lde not 0 or >= S, max_iter < 0, cost <= 0, gtol < 0.  MDL_E_ALIGN: ws not
+ * 16-byte, c_index_out / chi2_out not 8-byte aligned.  All of it is checked before anything is launched. */
+#define MDL_COX_MAX_TRAIN 1024
+#define MDL_COX_CG_MAX 400
+#define MDL_COX_LS_MAX 24
+int64_t mdl_cox_order_fit_ws_bytes(int64_t P, int n_max, int d);
+int mdl_cox_fit(const float* X, int64_t ldX, int64_t S, int d, const float* time, int64_t ldt, const int32_t* event, int64_t lde,
+                const int32_t* train_idx, const int32_t* n_train, int64_t P, int n_max, float cost, float gtol, int max_iter,
+                float* W_out, float* thr_out, float* info_out, void* ws, void* stream);
+int64_t mdl_surv_metrics_ws_bytes(int64_t P, int64_t S);
+int mdl_surv_metrics(const float* z, const float* time, int64_t ldt, const int32_t* event, int64_t lde, const int32_t* train_idx,
+                     const int32_t* n_train, int64_t P, int n_max, int64_t S, const float* thr, void* c_index_out, void* chi2_out,
+                     int32_t* counts_out, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

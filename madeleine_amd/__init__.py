@@ -10,6 +10,7 @@ madeleine.utils.loss, madeleine.utils.trainer):
     from madeleine_amd import linear_probe       # the few-shot linear-probing protocol, every (task, k, fold) fit in one batch of launches
     from madeleine_amd import device_smooth_rank # the model-selection criterion (smooth rank of the embeddings) without a host SVD
     from madeleine_amd import cross_stain_retrieval  # at which rank a case's own IHC slide comes back for its H&E slide, and the reverse
+    from madeleine_amd import survival_probe     # do the embeddings stratify patients: cross-validated Cox fits, C-index, log-rank
 
 The numeric work runs in csrc/libmadeleine_amd.so through the C ABI of include/madeleine_amd.h.
 Importing this package does not load the library (so model construction / state_dict handling works on
@@ -21,13 +22,15 @@ from .model import ABMILEmbedder, MADELEINE, create_model
 from .optim import AdamW
 from .retrieval import cross_stain_retrieval, retrieval_metrics, slide_neighbours
 from .store import DeviceSlideStore, PackedBags
+from .survival import fit_cox, survival_probe, survival_splits
 from .trainer import calculate_losses, train_loop
 from .utils import create_model_from_pretrained, device_smooth_rank, extract_slide_level_embeddings, load_checkpoint, run_inference
 
 __all__ = ["MADELEINE", "ABMILEmbedder", "BatchedABMIL", "create_model", "InfoNCE", "info_nce", "GOT",
            "init_intra_wsi_loss_function", "calculate_losses", "train_loop", "run_inference", "extract_slide_level_embeddings",
            "load_checkpoint", "create_model_from_pretrained", "AdamW", "DeviceSlideStore", "PackedBags", "probe_splits", "fit_logistic",
-           "linear_probe", "device_smooth_rank", "cross_stain_retrieval", "retrieval_metrics", "slide_neighbours"]
+           "linear_probe", "device_smooth_rank", "cross_stain_retrieval", "retrieval_metrics", "slide_neighbours",
+           "survival_splits", "fit_cox", "survival_probe"]
 __version__ = "0.2"
 _PROBE = ("probe_splits", "fit_logistic", "linear_probe")
 

@@ -1946,6 +1946,76 @@ def probe_metrics(z, y, train_idx, n_train, n_classes):
     return confusion, auc
 
 
+# ---- S1-S2: the survival probe (mdl_cox_fit / mdl_surv_metrics; the scores between them are probe_scores).  No autograd ----
+_SURV_LIMITS = "survival probe supports at most %d training cases per fit and %d cases (got n_max %d, S %d)"
+
+
+def _surv_refusal(n_max, S):
+    d = _native._DEFINES
+    return (_SURV_LIMITS, d["MDL_COX_MAX_TRAIN"], d["MDL_PROBE_MAX_CASES"], n_max, S)
+
+
+def _surv_problems(time, event, train_idx, n_train, S):
+    """(P, n_max, ldt, lde) of a problem list: time fp32 and event int32, each [S] (shared) or [P, S]; train_idx [P, n_max] int32,
+    n_train [P] int32."""
+    _require(time, "time")
+    _require(event, "event", torch.int32)
+    _require(train_idx, "train_idx", torch.int32)
+    _require(n_train, "n_train", torch.int32)
+    if train_idx.dim() != 2 or train_idx.shape[0] < 1 or train_idx.shape[1] < 1 or n_train.shape != (train_idx.shape[0],):
+        raise RuntimeError("madeleine_amd: train_idx must be [P, n_max] and n_train [P], P >= 1, n_max >= 1")
+    P, n_max = train_idx.shape
+    strides = []
+    for name, v in (("time", time), ("event", event)):
+        if v.shape == (S,):
+            strides.append(0)
+        elif v.shape == (P, S):
+            strides.append(S)
+        else:
+            raise RuntimeError("madeleine_amd: %s must be [S] or [P, S] = [%d, %d] (got %s)" % (name, P, S, tuple(v.shape)))
+    return P, n_max, strides[0], strides[1]
+
+
+def cox_fit(X, time, event, train_idx, n_train, cost=1.0, gtol=1e-3, max_iter=100):
+    """(W [P, d], thr [P], info [P, 4]) of P ridge-penalised Cox fits (S1 of the header): thr the median of the training rows' decision
+    values; info columns: Newton steps, converged, inf-norm of the gradient, CG steps.  gtol is relative to the gradient at w = 0.
+    Asynchronous, no host read."""
+    S, d, ldX = _probe_matrix(X)
+    P, n_max, ldt, lde = _surv_problems(time, event, train_idx, n_train, S)
+    refusal = _surv_refusal(n_max, S)
+    ws = _ws_for("mdl_cox_order_fit_ws_bytes", X.device, P, n_max, d, refusal=refusal)
+    W = torch.empty(P, d, device=X.device, dtype=torch.float32)
+    thr = torch.empty(P, device=X.device, dtype=torch.float32)
+    info = torch.empty(P, 4, device=X.device, dtype=torch.float32)
+    with _timed("cox_fit"):
+        _call("mdl_cox_fit", X, ldX, S, d, time, ldt, event, lde, train_idx, n_train, P, n_max, float(cost), float(gtol), int(max_iter), W,
+              thr, info, ws, _stream(), unsupported=refusal)
+    return W, thr, info
+
+
+def survival_metrics(z, time, event, train_idx, n_train, thr):
+    """(c_index [P] fp64, chi2 [P] fp64, counts [P, 6] int32) over the test cases of every problem (S2): the cases with follow-up outside
+    its train_idx.  z [P, S]; counts columns: concordance numerator, comparable pairs, test cases, high-group size (z > thr), events in
+    the low group, events in the high group."""
+    _require(z, "z")
+    _require(thr, "thr")
+    if z.dim() != 2 or z.shape[0] < 1 or z.shape[1] < 1 or thr.shape != (z.shape[0],):
+        raise RuntimeError("madeleine_amd: z must be [P, S] and thr [P]")
+    S = z.shape[1]
+    P, n_max, ldt, lde = _surv_problems(time, event, train_idx, n_train, S)
+    if P != z.shape[0]:
+        raise RuntimeError("madeleine_amd: z holds %d problems, train_idx %d" % (z.shape[0], P))
+    refusal = _surv_refusal(n_max, S)
+    ws = _ws_for("mdl_surv_metrics_ws_bytes", z.device, P, S, refusal=refusal)
+    c_index = torch.empty(P, device=z.device, dtype=torch.float64)
+    chi2 = torch.empty(P, device=z.device, dtype=torch.float64)
+    counts = torch.empty(P, 6, device=z.device, dtype=torch.int32)
+    with _timed("survival_metrics"):
+        _call("mdl_surv_metrics", z, time, ldt, event, lde, train_idx, n_train, P, n_max, S, thr, c_index, chi2, counts, ws, _stream(),
+              unsupported=refusal)
+    return c_index, chi2, counts
+
+
 # ---- A-map: the attention read-out (mdl_attn_softmax / mdl_attn_rank).  Forward only, no autograd: raw scores are inputs ----
 ATTN_ROWS = _native._DEFINES["MDL_ATTN_ROWS"]
 ATTN_SORT_KEYS = _native._DEFINES["MDL_ATTN_SORT_KEYS"]
