@@ -901,6 +901,46 @@ int mdl_probe_metrics(const float* z, const int32_t* y, int64_t ldy, const int32
                       int n_max, int64_t S, int C, int32_t* confusion_out, float* auc_out, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * L1-L2 -- the full-label linear probe: the fits of P1 with any number of training rows, and the metrics of P3 over problem tables
+ * of that width (ABI 26, additive).  For the cross-validated linear probe trained on all labels (K folds of a cohort): n > d, where the
+ * n x n Gram matrix of P1 is the wrong form.  X, y, ldy, train_idx, n_train, cost, gtol, max_iter, W_out, b_out, info_out mean what
+ * they mean in P1-P3, with 1 <= n_train[p] <= n_max <= MDL_LOGIT_MAX_TRAIN and 1 <= d <= MDL_LOGIT_MAX_DIM.  The decision values between
+ * the two calls come from mdl_probe_scores.
+ *
+ * mdl_logit_fit minimises the objective of mdl_probe_fit in the primal unknowns (W [cols, d], b [cols]) by Newton-CG, one workgroup
+ * per problem, one launch.  Every product with X is one sweep over the training rows (n d 4 bytes): a wave takes a few rows into
+ * registers, dots them with the vector in LDS, applies the row's loss Hessian (or residual) and accumulates x_i u_i^T in wave-private
+ * registers; the waves are added through LDS in a fixed order.  The row -> wave assignment is a function of n alone.  One sweep per CG
+ * step, one for the gradient and the decision values of every Newton step -- always from W itself, so the stop rule sees the gradient
+ * of what is returned --, one for the change of the decision values along the step; the step length halves on the directional
+ * derivative along the line, O(n cols) per trial.  No workgroup waits on another, no floating-point atomic, every sum in a fixed order;
+ * every loop is bounded (max_iter Newton steps, MDL_LOGIT_CG_MAX CG steps each, MDL_LOGIT_LS_MAX step halvings).  Stop rule, meaning of
+ * gtol and of `converged`, info_out [P, 4] and the zero-mean multinomial intercept: as mdl_probe_fit.  A problem with n_train outside
+ * [1, n_max], a training index outside [0, S) or an unlabeled training case writes NaN to its W, b and residual and converged = 0 and
+ * reads nothing of X; the others are unaffected.  A problem's bits depend on that problem alone (not on P, p, n_max or the others' sizes).
+ * ws: mdl_logit_fit_ws_bytes = P * (3 * n4 * cols + d * nc) * 4 bytes with n4 = n_max rounded up to a multiple of 4 and nc = 1, 4 or 8
+ * (cols rounded up to a width the kernel is built for): the decision values, the Hessian weights and the change of the decision values
+ * along the step of every training row (n cols 4 bytes each: 512 KiB at n = 16384, cols = 8, more than the LDS holds), and W during the
+ * iteration.
+ *
+ * mdl_logit_metrics: mdl_probe_metrics (the same three kernels, the same workspace size) for n_max <= MDL_LOGIT_MAX_TRAIN.
+ *
+ * Workspaces: 16-byte aligned, contents need no initialisation.  MDL_E_UNSUPPORTED: n_max > MDL_LOGIT_MAX_TRAIN, d > MDL_LOGIT_MAX_DIM
+ * (fit), C outside [2, MDL_PROBE_MAX_CLASSES], S > MDL_PROBE_MAX_CASES (metrics), a launch grid or an output index beyond int32.
+ * MDL_E_ARG, MDL_E_ALIGN: as P1-P3.  All of it is checked before anything is launched. */
+#define MDL_LOGIT_MAX_TRAIN 16384
+#define MDL_LOGIT_MAX_DIM 1024
+#define MDL_LOGIT_CG_MAX 400
+#define MDL_LOGIT_LS_MAX 24
+int64_t mdl_logit_fit_ws_bytes(int64_t P, int n_max, int d, int C);
+int mdl_logit_fit(const float* X, int64_t ldX, int64_t S, int d, const int32_t* y, int64_t ldy, const int32_t* train_idx,
+                  const int32_t* n_train, int64_t P, int n_max, int C, float cost, float gtol, int max_iter, float* W_out, float* b_out,
+                  float* info_out, void* ws, void* stream);
+int64_t mdl_logit_metrics_ws_bytes(int64_t P, int64_t S, int C);
+int mdl_logit_metrics(const float* z, const int32_t* y, int64_t ldy, const int32_t* train_idx, const int32_t* n_train, int64_t P,
+                      int n_max, int64_t S, int C, int32_t* confusion_out, float* auc_out, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A-map -- the attention read-out: per bag and head the softmax of the raw scores with its statistics, an exact stable descending
  * order, percentile ranks and the k best rows, for all bags of a pack in one launch sequence (ABI 26, additive).  Replaces, for the
  * raw scores MADELEINE.forward(..., return_attention=True) returns (Model.py:205-216), the per-bag, per-head host loop of

@@ -8,6 +8,7 @@ madeleine.utils.loss, madeleine.utils.trainer):
     from madeleine_amd import AdamW          # torch.optim.AdamW's update with a device-side non-finite guard and clipping
     from madeleine_amd import DeviceSlideStore   # the cohort's features resident on the device, batches drawn by one kernel
     from madeleine_amd import linear_probe       # the few-shot linear-probing protocol, every (task, k, fold) fit in one batch of launches
+    from madeleine_amd import linear_probe_cv    # the probe trained on all labels: stratified K folds, primal Newton-CG fits of any size
     from madeleine_amd import device_smooth_rank # the model-selection criterion (smooth rank of the embeddings) without a host SVD
     from madeleine_amd import cross_stain_retrieval  # at which rank a case's own IHC slide comes back for its H&E slide, and the reverse
     from madeleine_amd import survival_probe     # do the embeddings stratify patients: cross-validated Cox fits, C-index, log-rank
@@ -30,9 +31,9 @@ __all__ = ["MADELEINE", "ABMILEmbedder", "BatchedABMIL", "create_model", "InfoNC
            "init_intra_wsi_loss_function", "calculate_losses", "train_loop", "run_inference", "extract_slide_level_embeddings",
            "load_checkpoint", "create_model_from_pretrained", "AdamW", "DeviceSlideStore", "PackedBags", "probe_splits", "fit_logistic",
            "linear_probe", "device_smooth_rank", "cross_stain_retrieval", "retrieval_metrics", "slide_neighbours",
-           "survival_splits", "fit_cox", "survival_probe"]
+           "survival_splits", "fit_cox", "survival_probe", "cv_splits", "linear_probe_cv"]
 __version__ = "0.2"
-_PROBE = ("probe_splits", "fit_logistic", "linear_probe")
+_PROBE = ("probe_splits", "fit_logistic", "linear_probe", "cv_splits", "linear_probe_cv")
 
 
 def __getattr__(name):

@@ -17,6 +17,8 @@
 //   probe_pairs_kernel    exact Mann-Whitney counting, 2 per (positive, negative) pair ranked right and 1 per tie, one integer atomic
 //                         per workgroup: the sum is the same whatever the order.
 //   probe_auc_kernel      a thread per problem: the counts to AUC, in double.
+// mdl_logit_metrics (L2 of the header) is the same three metrics kernels behind a launcher that accepts problem tables of up to
+// MDL_LOGIT_MAX_TRAIN columns; the fits of that width are in probe_primal.hip.
 // No workgroup waits on another; every loop has a bound that is an argument or a constant of the header.
 #include "common.hpp"
 
@@ -594,10 +596,10 @@ __global__ __launch_bounds__(PB_THREADS) void probe_auc_kernel(const int32_t* __
 inline bool i32(int64_t v) { return v >= 0 && v <= 0x7FFFFFFF; }
 
 // shared argument checks of the entry points that take the problem list
-inline int check_problems(int64_t P, int n_max, int64_t S, int C, int64_t ldy) {
+inline int check_problems(int64_t P, int n_max, int64_t S, int C, int64_t ldy, int n_limit = PB_NMAX) {
     if (P < 1 || n_max < 1 || S < 1) return MDL_E_ARG;
     if (ldy != 0 && ldy < S) return MDL_E_ARG;
-    if (n_max > PB_NMAX || C < 2 || C > PB_CMAX) return MDL_E_UNSUPPORTED;
+    if (n_max > n_limit || C < 2 || C > PB_CMAX) return MDL_E_UNSUPPORTED;
     if (!i32(S) || !i32(P) || !i32(P * n_max)) return MDL_E_UNSUPPORTED;
     return MDL_OK;
 }
@@ -663,10 +665,11 @@ extern "C" int64_t mdl_probe_metrics_ws_bytes(int64_t P, int64_t S, int C) {
     return P * s8_of(S) + P * PB_CMAX * (int64_t)sizeof(unsigned long long) + (C > 2 ? P * C * S * (int64_t)sizeof(double) : 0);
 }
 
-extern "C" int mdl_probe_metrics(const float* z, const int32_t* y, int64_t ldy, const int32_t* train_idx, const int32_t* n_train,
-                                 int64_t P, int n_max, int64_t S, int C, int32_t* confusion_out, float* auc_out, void* ws, void* stream) {
+// the three metrics launches behind mdl_probe_metrics and mdl_logit_metrics, which differ in the widest problem table they accept
+static int launch_metrics(const float* z, const int32_t* y, int64_t ldy, const int32_t* train_idx, const int32_t* n_train, int64_t P,
+                          int n_max, int n_limit, int64_t S, int C, int32_t* confusion_out, float* auc_out, void* ws, void* stream) {
     if (!z || !y || !train_idx || !n_train || !confusion_out || !auc_out || !ws) return MDL_E_ARG;
-    if (const int rc = check_problems(P, n_max, S, C, ldy)) return rc;
+    if (const int rc = check_problems(P, n_max, S, C, ldy, n_limit)) return rc;
     if (S > MDL_PROBE_MAX_CASES) return MDL_E_UNSUPPORTED;
     if (!host_aligned16(ws)) return MDL_E_ALIGN;
     const int ncls = C == 2 ? 1 : C;
@@ -684,4 +687,16 @@ extern "C" int mdl_probe_metrics(const float* z, const int32_t* y, int64_t ldy, 
                        (const int32_t*)confusion_out, (int)P, C, m, auc_out);
     MDL_LAUNCH_CHECK();
     return MDL_OK;
+}
+
+extern "C" int mdl_probe_metrics(const float* z, const int32_t* y, int64_t ldy, const int32_t* train_idx, const int32_t* n_train,
+                                 int64_t P, int n_max, int64_t S, int C, int32_t* confusion_out, float* auc_out, void* ws, void* stream) {
+    return launch_metrics(z, y, ldy, train_idx, n_train, P, n_max, PB_NMAX, S, C, confusion_out, auc_out, ws, stream);
+}
+
+extern "C" int64_t mdl_logit_metrics_ws_bytes(int64_t P, int64_t S, int C) { return mdl_probe_metrics_ws_bytes(P, S, C); }
+
+extern "C" int mdl_logit_metrics(const float* z, const int32_t* y, int64_t ldy, const int32_t* train_idx, const int32_t* n_train,
+                                 int64_t P, int n_max, int64_t S, int C, int32_t* confusion_out, float* auc_out, void* ws, void* stream) {
+    return launch_metrics(z, y, ldy, train_idx, n_train, P, n_max, MDL_LOGIT_MAX_TRAIN, S, C, confusion_out, auc_out, ws, stream);
 }

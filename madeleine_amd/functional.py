@@ -1946,6 +1946,57 @@ def probe_metrics(z, y, train_idx, n_train, n_classes):
     return confusion, auc
 
 
+# ---- L1-L2: the full-label linear probe (mdl_logit_fit / mdl_logit_metrics; the scores between them are probe_scores).  No autograd ----
+_LOGIT_LIMITS = ("full-label linear probe supports at most %d training cases per problem, %d dimensions, 2..%d classes and %d cases "
+                 "(got n_max %d, d %d, C %d, S %d)")
+
+
+def _logit_refusal(n_max, d, C, S):
+    lim = _native._DEFINES
+    return (_LOGIT_LIMITS, lim["MDL_LOGIT_MAX_TRAIN"], lim["MDL_LOGIT_MAX_DIM"], lim["MDL_PROBE_MAX_CLASSES"], lim["MDL_PROBE_MAX_CASES"],
+            n_max, d, C, S)
+
+
+def logit_fit(X, y, train_idx, n_train, n_classes, cost=1.0, gtol=1e-4, max_iter=100):
+    """(W [P, cols, d], b [P, cols], info [P, 4]) of P regularised logistic fits in the primal unknowns (L1 of the header): the objective,
+    the stop rule and the info columns of probe_fit, for up to MDL_LOGIT_MAX_TRAIN training cases per problem.  Asynchronous, no host
+    read."""
+    S, d, ldX = _probe_matrix(X)
+    P, n_max, ldy = _probe_problems(y, train_idx, n_train, S)
+    C = int(n_classes)
+    refusal = _logit_refusal(n_max, d, C, S)
+    ws = _ws_for("mdl_logit_fit_ws_bytes", X.device, P, n_max, d, C, refusal=refusal)
+    cols = 1 if C == 2 else C
+    W = torch.empty(P, cols, d, device=X.device, dtype=torch.float32)
+    b = torch.empty(P, cols, device=X.device, dtype=torch.float32)
+    info = torch.empty(P, 4, device=X.device, dtype=torch.float32)
+    with _timed("logit_fit"):
+        _call("mdl_logit_fit", X, ldX, S, d, y, ldy, train_idx, n_train, P, n_max, C, float(cost), float(gtol), int(max_iter), W, b, info,
+              ws, _stream(), unsupported=refusal)
+    return W, b, info
+
+
+def logit_metrics(z, y, train_idx, n_train, n_classes):
+    """probe_metrics for problem tables of up to MDL_LOGIT_MAX_TRAIN columns (L2): (confusion [P, C, C] int32, auc [P] fp32) over the
+    test cases of every problem."""
+    _require(z, "z")
+    C = int(n_classes)
+    cols = 1 if C == 2 else C
+    if z.dim() != 3 or z.shape[0] < 1 or z.shape[1] < 1 or z.shape[2] != cols:
+        raise RuntimeError("madeleine_amd: z must be [P, S, %d]" % cols)
+    S = z.shape[1]
+    P, n_max, ldy = _probe_problems(y, train_idx, n_train, S)
+    if P != z.shape[0]:
+        raise RuntimeError("madeleine_amd: z holds %d problems, train_idx %d" % (z.shape[0], P))
+    refusal = _logit_refusal(n_max, 1, C, S)
+    ws = _ws_for("mdl_logit_metrics_ws_bytes", z.device, P, S, C, refusal=refusal)
+    confusion = torch.empty(P, C, C, device=z.device, dtype=torch.int32)
+    auc = torch.empty(P, device=z.device, dtype=torch.float32)
+    with _timed("logit_metrics"):
+        _call("mdl_logit_metrics", z, y, ldy, train_idx, n_train, P, n_max, S, C, confusion, auc, ws, _stream(), unsupported=refusal)
+    return confusion, auc
+
+
 # ---- S1-S2: the survival probe (mdl_cox_fit / mdl_surv_metrics; the scores between them are probe_scores).  No autograd ----
 _SURV_LIMITS = "survival probe supports at most %d training cases per fit and %d cases (got n_max %d, S %d)"
 

@@ -4,15 +4,19 @@ logistic regression, AUC and balanced accuracy) with every (task, k, fold) probl
     from madeleine_amd import linear_probe
     results = linear_probe(embeds, {"er": er, "pr": pr, "her2": her2})       # {(task, k): {"auc": [folds], "bacc": [folds], ...}}
 
-`python -m madeleine_amd.probe --slide_embedding_pkl P --label_path CSV` is the reference's command line."""
+`python -m madeleine_amd.probe --slide_embedding_pkl P --label_path CSV` is the reference's command line.
+
+The probe trained on all labels, cross-validated, is linear_probe_cv (stratified K folds by cv_splits, `--cv_folds K` on the command
+line): the same objective solved in the primal unknowns, for up to MDL_LOGIT_MAX_TRAIN training cases per fold."""
 import warnings
 
 import numpy as np
 import torch
 
+from . import _native
 from . import functional as F
 
-__all__ = ["probe_splits", "fit_logistic", "linear_probe", "balanced_accuracy", "quadratic_kappa"]
+__all__ = ["probe_splits", "cv_splits", "fit_logistic", "linear_probe", "linear_probe_cv", "balanced_accuracy", "quadratic_kappa"]
 
 
 def probe_splits(labels, k, fold, seed_base=0):
@@ -32,6 +36,33 @@ def probe_splits(labels, k, fold, seed_base=0):
             raise ValueError("probe_splits: class %d has %d cases, fewer than k = %d" % (c, idx.numel(), k))
         out.append(idx[torch.randperm(idx.numel(), generator=g)[:k]])
     return torch.cat(out)
+
+
+def cv_splits(labels, folds=5, repeat=0, seed_base=0):
+    """The training indices (a list of `folds` int64 vectors, each ascending) of a class-stratified K-fold: for every class 0 .. C-1 in
+    increasing order, C = max(labels) + 1, its cases are shuffled by torch.randperm under ONE torch.Generator().manual_seed(seed_base +
+    1000 * folds + repeat) and dealt to the folds in turn, each class starting at the fold after the previous class's last; fold f trains
+    on every labeled case outside its own share.  Label -1 (unlabeled) is never drawn.  ValueError without a labeled case, when a class
+    has fewer cases than folds, or when a fold's training part exceeds MDL_LOGIT_MAX_TRAIN."""
+    labels = torch.as_tensor(np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels)).long()
+    folds = int(folds)
+    if labels.dim() != 1 or folds < 2 or not bool((labels >= 0).any()):
+        raise ValueError("cv_splits: labels must be a vector with a labeled case, and folds >= 2")
+    g = torch.Generator().manual_seed(int(seed_base) + 1000 * folds + int(repeat))
+    fold_of = torch.full_like(labels, -1)
+    dealt = 0
+    for c in range(int(labels.max()) + 1):
+        idx = torch.nonzero(labels == c)[:, 0]
+        if idx.numel() < folds:
+            raise ValueError("cv_splits: class %d has %d cases, fewer than %d folds" % (c, idx.numel(), folds))
+        idx = idx[torch.randperm(idx.numel(), generator=g)]
+        fold_of[idx] = (torch.arange(idx.numel()) + dealt) % folds
+        dealt += idx.numel()
+    out = [torch.nonzero((fold_of >= 0) & (fold_of != f))[:, 0] for f in range(folds)]
+    limit = _native._DEFINES["MDL_LOGIT_MAX_TRAIN"]
+    if max(t.numel() for t in out) > limit:
+        raise ValueError("cv_splits: a fold trains on %d cases, more than the %d a fit supports" % (max(t.numel() for t in out), limit))
+    return out
 
 
 def balanced_accuracy(confusion):
@@ -66,7 +97,9 @@ def fit_logistic(X, y, train_idx, n_classes, cost=1.0, gtol=1e-4, max_iter=100):
     """P regularised logistic fits on the device (sklearn's LogisticRegression(C=cost), binary form for two classes, multinomial above).
     X [S, d] fp32 device tensor; y [S] or [P, S] integer labels (-1: unlabeled); train_idx a list of P index vectors or a [P, n_max]
     table padded with -1.  Returns (W [P, cols, d], b [P, cols], info) with info = {"iterations", "converged", "residual",
-    "cg_iterations"}, [P] device tensors.  Nothing is read back: the caller decides when to look at `converged`."""
+    "cg_iterations"}, [P] device tensors.  Nothing is read back: the caller decides when to look at `converged`.  A table of at most
+    MDL_PROBE_MAX_TRAIN columns goes to the few-shot solver (probe_fit, in the span of the training rows), a wider one to the primal
+    solver (logit_fit, up to MDL_LOGIT_MAX_TRAIN columns)."""
     if not isinstance(X, torch.Tensor) or not X.is_cuda:
         raise RuntimeError("madeleine_amd: X must be a tensor on a ROCm device; there is no CPU fallback")
     y = torch.as_tensor(y).to(device=X.device, dtype=torch.int32).contiguous()
@@ -75,7 +108,8 @@ def fit_logistic(X, y, train_idx, n_classes, cost=1.0, gtol=1e-4, max_iter=100):
         n_train = (table >= 0).sum(1, dtype=torch.int32)
     else:
         table, n_train = _problem_table([torch.as_tensor(t).reshape(-1) for t in train_idx], X.device)
-    W, b, info = F.probe_fit(X, y, table, n_train, n_classes, cost, gtol, max_iter)
+    fit = F.probe_fit if table.shape[1] <= _native._DEFINES["MDL_PROBE_MAX_TRAIN"] else F.logit_fit
+    W, b, info = fit(X, y, table, n_train, n_classes, cost, gtol, max_iter)
     return W, b, {"iterations": info[:, 0], "converged": info[:, 1] > 0, "residual": info[:, 2], "cg_iterations": info[:, 3]}
 
 
@@ -132,6 +166,60 @@ def linear_probe(embeds, labels, ks=(1, 10, 25), folds=10, cost=1.0, seed_base=0
     return out
 
 
+def linear_probe_cv(embeds, labels, folds=5, repeats=1, cost=1.0, seed_base=0, kappa=False, gtol=1e-4, max_iter=100):
+    """The linear probe trained on all labels, cross-validated, over embeds [S, d] (tensor or array): for every task (labels: one [S]
+    vector -- task "label" -- or a dict task -> [S]; -1 = unlabeled), every repeat and every fold of cv_splits(labels, folds, repeat,
+    seed_base), fit on the fold's training cases and score on its held-out labeled cases.  All problems of equal class count share ONE
+    fit, ONE scoring and ONE metrics launch sequence.  Returns {(task, repeat): {"auc": [folds], "bacc": [folds], "converged": [folds]
+    bool, "confusion": [folds, C, C] (+ "q_kappa": [folds] with kappa=True)}} as numpy arrays.  Two host reads: the finiteness check of
+    embeds (ValueError) and the results.  Problems that did not converge are flagged in "converged" and announced by one
+    RuntimeWarning."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("madeleine_amd: linear_probe_cv needs a ROCm device; there is no CPU fallback")
+    X = torch.as_tensor(embeds)
+    X = X.to(device=X.device if X.is_cuda else "cuda", dtype=torch.float32)
+    if X.dim() != 2:
+        raise ValueError("linear_probe_cv: embeds must be [S, d]")
+    if X.stride(-1) != 1:
+        X = X.contiguous()
+    if not bool(torch.isfinite(X).all()):
+        raise ValueError("linear_probe_cv: embeds holds non-finite values")
+    tasks = labels if isinstance(labels, dict) else {"label": labels}
+    groups = {}                                     # C -> [(task, repeat, fold, y, train indices)]
+    for task, y in tasks.items():
+        y = torch.as_tensor(np.asarray(y.cpu() if isinstance(y, torch.Tensor) else y)).long()
+        if y.shape != (X.shape[0],):
+            raise ValueError("linear_probe_cv: task %r has %s labels for %d embeddings" % (task, tuple(y.shape), X.shape[0]))
+        for repeat in range(repeats):
+            for fold, idx in enumerate(cv_splits(y, folds, repeat, seed_base)):
+                groups.setdefault(int(y.max()) + 1, []).append((task, repeat, fold, y, idx))
+    parts = []
+    for C, probs in groups.items():
+        table, n_train = _problem_table([p[4] for p in probs], X.device)
+        y_dev = torch.stack([p[3] for p in probs]).to(torch.int32).to(X.device)
+        W, b, info = F.logit_fit(X, y_dev, table, n_train, C, cost, gtol, max_iter)
+        confusion, auc = F.logit_metrics(F.probe_scores(X, W, b, C), y_dev, table, n_train, C)
+        parts += [auc.double(), info[:, 1].double(), confusion.reshape(-1).double()]
+    host = torch.cat(parts).cpu().numpy()           # the one read of the results
+    out, at, failed = {}, 0, 0
+    for C, probs in groups.items():
+        P = len(probs)
+        auc, conv, cm = host[at:at + P], host[at + P:at + 2 * P] > 0, host[at + 2 * P:at + 2 * P + P * C * C].reshape(P, C, C)
+        at += 2 * P + P * C * C
+        failed += int((~conv).sum())
+        for p, (task, repeat, fold, _, _) in enumerate(probs):
+            res = out.setdefault((task, repeat), {"auc": np.zeros(folds), "bacc": np.zeros(folds), "converged": np.zeros(folds, dtype=bool),
+                                                  "confusion": np.zeros((folds, C, C), dtype=np.int64)})
+            res["auc"][fold], res["converged"][fold], res["confusion"][fold] = auc[p], conv[p], np.rint(cm[p])
+            res["bacc"][fold] = balanced_accuracy(cm[p])
+            if kappa:
+                res.setdefault("q_kappa", np.zeros(folds))[fold] = quadratic_kappa(cm[p])
+    if failed:
+        warnings.warn("linear_probe_cv: %d of %d fits did not reach gtol = %g in %d Newton steps" % (
+            failed, sum(map(len, groups.values())), gtol, max_iter), RuntimeWarning)
+    return out
+
+
 def _main(argv=None):
     import argparse
     import csv
@@ -141,6 +229,9 @@ def _main(argv=None):
     ap.add_argument("--slide_embedding_pkl", required=True)
     ap.add_argument("--label_path", required=True)
     ap.add_argument("--tasks", nargs="+", default=["er", "pr", "her2"])
+    ap.add_argument("--cv_folds", type=int, default=0, help="train on all labels, cross-validated in this many stratified folds, "
+                                                            "instead of the few-shot protocol")
+    ap.add_argument("--cv_repeats", type=int, default=1)
     args = ap.parse_args(argv)
     with open(args.slide_embedding_pkl, "rb") as f:
         obj = pickle.load(f)
@@ -149,6 +240,14 @@ def _main(argv=None):
     keep = [i for i, s in enumerate(obj["slide_ids"]) if str(s) in rows]      # the reference's intersection of labels and embeddings
     embeds = np.asarray(obj["embeds"], dtype=np.float32)[keep]
     labels = {t: np.array([int(float(rows[str(obj["slide_ids"][i])][t])) for i in keep]) for t in args.tasks}
+    if args.cv_folds:
+        results = linear_probe_cv(embeds, labels, folds=args.cv_folds, repeats=args.cv_repeats, kappa="isup_grade" in args.tasks)
+        for task in args.tasks:                     # mean +/- std over every fold of every repeat
+            metric = "q_kappa" if task == "isup_grade" else "auc"
+            v = np.concatenate([results[(task, r)][metric] for r in range(args.cv_repeats)])
+            print("cv_folds={}, task={}, {}={} +/- {}".format(args.cv_folds, task, "quadratic kappa" if metric == "q_kappa" else "auc",
+                                                              round(float(v.mean()), 3), round(float(v.std()), 3)))
+        return
     results = linear_probe(embeds, labels, kappa="isup_grade" in args.tasks)
     name = os.path.splitext(os.path.basename(args.slide_embedding_pkl))[0]
     save = os.path.join(os.path.dirname(args.slide_embedding_pkl), "res_linear_probing", name)
