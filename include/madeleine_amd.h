@@ -249,7 +249,9 @@ int mdl_ln_gelu_drop_bwd(const float* x, const float* bias, const float* gamma, 
  * (madeleine/utils/loss.py:92,111-127) for S independent problems in one launch (the reference
  * calls it once per stain from trainer.py:33).
  *
- * Q,P [S,Kmax,D] padded row blocks (problem s uses rows [0,cnt[s])); cnt int32 [S] device array.
+ * Q,P [S,Kmax,D] padded row blocks (problem s uses rows [0,cnt[s])); cnt int32 [S] device array.  D >= 8 and a multiple of 32
+ *          (MDL_E_ARG otherwise, from the workspace query too): a narrower embedding is passed with zero columns behind it, which change
+ *          neither the norms nor the products.
  * loss [S]: mean-reduced cross entropy of Q_hat P_hat^T / temperature against the diagonal
  *           (symmetric != 0: 0.5*rows + 0.5*columns, loss.py:120-123).  cnt[s] == 0 => loss 0.
  * ws: mdl_infonce_ws_bytes(S,Kmax,D): normalised rows, inverse norms, logits, LSEs (kept for bwd).

@@ -173,17 +173,31 @@ def test_empty_bags_and_an_empty_pack(dev):
 
 
 def test_a_cu_that_is_not_consistent_stays_inside_the_buffers(dev):
-    """bags that run backwards or leave [0, T] are served as empty bags; the guard rows around every buffer keep their values"""
-    H, T = 4, 600
+    """bags that run backwards or leave [0, T] are served as empty bags; the guard rows around every buffer keep their values: scores,
+    cu, every output and both workspaces (at exactly mdl_attn_map_ws_bytes) are carved from one guarded arena (tests/_arena.py), under
+    both of its fills, and the outputs do not depend on the fill"""
+    from tests._extent_cases import run_case
+    H, T, k = 4, 600, 4
     s = scores_of("normals", H)[:T]
-    cu = torch.tensor([0, 300, 200, 700, -5, 300, 600], dtype=torch.int64, device=dev)      # valid: [0, 300) and [300, 600)
-    sd = on_device(s, dev, 0)
-    order, pct, ti, tv = MF.attn_rank(sd, cu, k=4)
-    attn, m, l = MF.attn_softmax(sd, cu)
-    torch.cuda.synchronize()
-    assert ti[:, 0, 0].tolist()[1:5] == [-1, -1, -1, -1] and bool(torch.isneginf(m[1:5]).all()) and not bool(l[1:5].any())
-    assert np.array_equal(ti[0].cpu().numpy(), ref.readout(s[:300], cu_of([300]), 4)["topk_idx"][0])
-    assert np.array_equal(ti[5].cpu().numpy(), ref.readout(s[300:600], cu_of([300]), 4)["topk_idx"][0])
+    cu_host = torch.tensor([0, 300, 200, 700, -5, 300, 600], dtype=torch.int64)               # valid: [0, 300) and [300, 600)
+    R_ = cu_host.numel() - 1
+    i32, f32 = torch.int32, torch.float32
+
+    def case(r):
+        sd, cu = r.inp("scores", (T, H), f32, torch.from_numpy(s.copy())), r.inp("cu", (R_ + 1,), torch.int64, cu_host)
+        order, pct = r.out("order", (H, T), i32), r.out("pct", (T, H))
+        ti, tv = r.out("topk_idx", (R_, H, k), i32), r.out("topk_val", (R_, H, k))
+        r.call("mdl_attn_rank", sd, H, cu, T, R_, H, k, order, pct, ti, tv, r.ws("ws_rank", "mdl_attn_map_ws_bytes", T, R_, H), r.stream())
+        attn, m, l = r.out("attn", (T, H)), r.out("m", (R_, H)), r.out("l", (R_, H))
+        r.call("mdl_attn_softmax", sd, H, cu, T, R_, H, attn, m, l, r.ws("ws_softmax", "mdl_attn_map_ws_bytes", T, R_, H), r.stream())
+        return dict(order=order, pct=pct, ti=ti, tv=tv, attn=attn, m=m, l=l)
+
+    def check(got):
+        ti, m, l = got["ti"], got["m"], got["l"]
+        assert ti[:, 0, 0].tolist()[1:5] == [-1, -1, -1, -1] and bool(torch.isneginf(m[1:5]).all()) and not bool(l[1:5].any())
+        assert np.array_equal(ti[0].numpy(), ref.readout(s[:300], cu_of([300]), 4)["topk_idx"][0])
+        assert np.array_equal(ti[5].numpy(), ref.readout(s[300:600], cu_of([300]), 4)["topk_idx"][0])
+    run_case(dev, case, check)
 
 
 def test_the_read_out_does_not_synchronise_the_host(dev):
