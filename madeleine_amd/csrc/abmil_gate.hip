@@ -379,8 +379,7 @@ __global__ __launch_bounds__(256) void gate_reduce_v_kernel(const float* __restr
 }
 
 __global__ void gate_mask_kernel(uint8_t* __restrict__ keep, int64_t n, int which, DropCfg d) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         bool ka, kb;
         drop_keep2(d, i, drop_row_key(d, i), ka, kb);     // the very function the forward / backward kernels evaluate (either field width)
         keep[i] = (which ? kb : ka) ? 1 : 0;
@@ -526,7 +525,10 @@ extern "C" int mdl_abmil_gate_dropout_mask(uint8_t* keep, int64_t T, int H, int 
     if (n == 0) return MDL_OK;
     DropCfg d = make_drop(p_drop, seed, nullptr, nullptr);
     d.on = 1;   // (p = 0: threshold 0, every element kept)
-    return gate_launch(gate_mask_kernel, dim3((unsigned)((n + 255) / 256)), 256, (hipStream_t)stream, keep, n, which, d);
+    // A launch carries its work-items per dimension in 32 bits: one thread per element dropped the blocks past 2^32 elements without an
+    // error (T = 2^20 + 8 at H = 8 wrote 32768 of its bytes).  At most 2^22 workgroups, which stride over the rest.
+    const int64_t cap = (int64_t)1 << 22, blocks = (n + 255) / 256 < cap ? (n + 255) / 256 : cap;
+    return gate_launch(gate_mask_kernel, dim3((unsigned)blocks), 256, (hipStream_t)stream, keep, n, which, d);
 }
 
 namespace mdl {
