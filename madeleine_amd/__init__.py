@@ -12,8 +12,10 @@ madeleine.utils.loss, madeleine.utils.trainer):
     from madeleine_amd import device_smooth_rank # the model-selection criterion (smooth rank of the embeddings) without a host SVD
     from madeleine_amd import cross_stain_retrieval  # at which rank a case's own IHC slide comes back for its H&E slide, and the reverse
     from madeleine_amd import survival_probe     # do the embeddings stratify patients: cross-validated Cox fits, C-index, log-rank
+    from madeleine_amd import heatmap            # attention heatmaps on the device: render, gaussian_taps, colormap, save_png
 
-The numeric work runs in csrc/libmadeleine_amd.so through the C ABI of include/madeleine_amd.h.
+The numeric work runs in csrc/libmadeleine_amd.so through the C ABI of include/madeleine_amd.h (the heatmap renderer: of
+include/madeleine_amd_view.h).
 Importing this package does not load the library (so model construction / state_dict handling works on
 any box); the first forward does, and raises if it is unavailable -- there is no fallback path.
 """
@@ -31,8 +33,10 @@ __all__ = ["MADELEINE", "ABMILEmbedder", "BatchedABMIL", "create_model", "InfoNC
            "init_intra_wsi_loss_function", "calculate_losses", "train_loop", "run_inference", "extract_slide_level_embeddings",
            "load_checkpoint", "create_model_from_pretrained", "AdamW", "DeviceSlideStore", "PackedBags", "probe_splits", "fit_logistic",
            "linear_probe", "device_smooth_rank", "cross_stain_retrieval", "retrieval_metrics", "slide_neighbours",
-           "survival_splits", "fit_cox", "survival_probe", "cv_splits", "linear_probe_cv"]
+           "survival_splits", "fit_cox", "survival_probe", "cv_splits", "linear_probe_cv", "heatmap", "render_heatmaps", "gaussian_taps",
+           "colormap", "save_png"]
 __version__ = "0.2"
+_HEATMAP = ("render_heatmaps", "gaussian_taps", "colormap", "save_png")
 _PROBE = ("probe_splits", "fit_logistic", "linear_probe", "cv_splits", "linear_probe_cv")
 
 
@@ -41,4 +45,8 @@ def __getattr__(name):
     if name in _PROBE:
         from . import probe
         return getattr(probe, name)
+    if name == "heatmap" or name in _HEATMAP:      # the renderer binds the library's #defines: resolved on first use as well
+        import importlib
+        mod = importlib.import_module(".heatmap", __name__)
+        return mod if name == "heatmap" else getattr(mod, "render" if name == "render_heatmaps" else name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -1,5 +1,5 @@
 """Builds libmadeleine_amd.so (gfx950) in-tree with hipcc.  No torch headers, no libtorch linkage:
-the library is a plain C-ABI shared object (include/madeleine_amd.h)."""
+the library is a plain C-ABI shared object (include/madeleine_amd.h and, for the viewing side, include/madeleine_amd_view.h)."""
 import contextlib
 import fcntl
 import os
@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libmadeleine_amd.so")
 HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "madeleine_amd.h"))
+VIEW_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "madeleine_amd_view.h"))      # csrc/heat_map.hip's entry points
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
 
@@ -20,7 +21,7 @@ def sources():
 
 
 def _deps():
-    return [HEADER] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))]
+    return [HEADER, VIEW_HEADER] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))]
 
 
 def _stale(target, deps):

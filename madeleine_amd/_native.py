@@ -1,4 +1,4 @@
-"""ctypes binding of libmadeleine_amd.so (the C ABI of include/madeleine_amd.h).
+"""ctypes binding of libmadeleine_amd.so (the C ABI of include/madeleine_amd.h and include/madeleine_amd_view.h).
 
 Single backend: there is no CPU / eager fallback.  `lib()` raises if the shared object cannot be
 loaded (it is built in-tree by `python -m madeleine_amd._build` / __graft_entry__.build(); if it is
@@ -69,6 +69,12 @@ def _parse_header(text):
 with open(_build.HEADER) as _f:
     SIGNATURES, _DEFINES = _parse_header(_f.read())
 ABI_VERSION = _DEFINES["MDL_ABI_VERSION"]
+# the second header (include/madeleine_amd_view.h: the heatmap entry points) is read the same way into a table of its own: SIGNATURES
+# stays exactly the main header's set, and the revision above is the main header's alone
+with open(_build.VIEW_HEADER) as _f:
+    VIEW_SIGNATURES, VIEW_DEFINES = _parse_header(_f.read())
+if set(VIEW_SIGNATURES) & set(SIGNATURES) or set(VIEW_DEFINES) & set(_DEFINES):
+    raise ImportError("madeleine_amd: %s repeats a name of %s" % (_build.VIEW_HEADER, _build.HEADER))
 
 
 def lib_path() -> str:
@@ -111,7 +117,7 @@ def lib():
         if abi() != ABI_VERSION:
             raise RuntimeError("madeleine_amd: %s implements ABI revision %d, this binding expects %d; rebuild it "
                                "(`python -m madeleine_amd._build --force`)" % (path, abi(), ABI_VERSION))
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(VIEW_SIGNATURES.items()):
             try:
                 fn = getattr(handle, name)
             except AttributeError:

@@ -2131,6 +2131,92 @@ def attn_rank(scores, cu, k=0, percentile=True):
     return order, pct, ti, tv
 
 
+# ---- V1: attention heatmaps (mdl_heat_render, include/madeleine_amd_view.h).  Forward only, exact integer arithmetic ----
+HEAT_REC = _native.VIEW_DEFINES["MDL_HEAT_REC"]
+HEAT_MAX_R = _native.VIEW_DEFINES["MDL_HEAT_MAX_R"]
+HEAT_MAX_SIDE = _native.VIEW_DEFINES["MDL_HEAT_MAX_SIDE"]
+HEAT_TAP_SUM = _native.VIEW_DEFINES["MDL_HEAT_TAP_SUM"]
+HEAT_WS_PER_PLANE_PIXEL = _native.VIEW_DEFINES["MDL_HEAT_WS_PER_PLANE_PIXEL"]
+_HEAT_LIMITS = ("heat_render supports a blur radius <= %d, canvases <= %d a side, patch sizes <= 2^24, T < 2^24 and C * pixels within "
+                "int32 (got T %d, R %d, C %d, pixels %d, r %d)")
+
+
+HEAT_MARKS = _native.VIEW_DEFINES["MDL_HEAT_MARKS"]
+# bytes per pixel and channel of the tile passes: the memset writes 8; hv_blur_rows reads acc (8) and writes S1, N1 (16); hv_blur_cols
+# reads acc, S1, N1 (24) and writes level, covered, rgba (2 + 1 + 4).  Halo re-reads and the footprint atomics are not in it.
+HEAT_PLANE_BYTES = {"clear": 8, "blur_rows": 8 + 16, "blur_cols_colour": 24 + 7}
+
+
+def heat_render(xy, cu, values, records, n_pixels, ds, taps, lut, alpha=255, base=None, records_dev=None, marks=None):
+    """(level uint16 [C * P], covered uint8 [C * P], rgba uint8 [C * P, 4]) of R bags x C channels: the render contract of
+    include/madeleine_amd_view.h.  xy [T, 2] int32, cu [R + 1] int64, values [T, C] fp32 (unit column stride, any row stride), lut
+    [256, 4] uint8 and base ([P, 3] uint8 or None) on the device; records [R, 6] int64 (ps, ox, oy, W, H, first pixel) and taps
+    [2 r + 1] int32 on the HOST (they are validated there; records_dev: their device copy when the caller already has one, else one
+    non-blocking upload).  P = n_pixels.  Bag b's block of every output is [C, H, W] from element C * off.  One memset and four
+    launches on the current stream, no host read.  marks: a host array of HEAT_MARKS event handles for mdl_heat_render_marked
+    (heat_render_stages)."""
+    if xy.dim() != 2 or xy.shape[1] != 2:
+        raise RuntimeError("madeleine_amd: heat_render needs xy [T, 2] int32")
+    _require(xy, "xy", torch.int32)
+    _require(cu, "cu_seqlens", torch.int64)
+    if cu.dim() != 1 or cu.numel() < 1:
+        raise RuntimeError("madeleine_amd: cu_seqlens must be [R + 1]")
+    T, R = xy.shape[0], cu.numel() - 1
+    if values.dim() != 2 or values.dtype != torch.float32 or not values.is_cuda or values.shape[0] != T or values.shape[1] < 1 or \
+            (values.shape[1] > 1 and values.stride(1) != 1):
+        raise RuntimeError("madeleine_amd: heat_render needs values [T, C] float32 on the device with unit column stride")
+    C = values.shape[1]
+    ld = values.stride(0) if T > 1 else C
+    if records.device.type != "cpu" or records.dtype != torch.int64 or tuple(records.shape) != (R, HEAT_REC) or not records.is_contiguous():
+        raise RuntimeError("madeleine_amd: heat_render needs records [R, %d] int64, contiguous, on the host" % HEAT_REC)
+    if taps.device.type != "cpu" or taps.dtype != torch.int32 or taps.dim() != 1 or taps.numel() % 2 != 1 or not taps.is_contiguous():
+        raise RuntimeError("madeleine_amd: heat_render needs taps [2 r + 1] int32, contiguous, on the host")
+    r, P, dev = taps.numel() // 2, int(n_pixels), xy.device
+    _require(lut, "lut", torch.uint8)
+    if tuple(lut.shape) != (256, 4):
+        raise RuntimeError("madeleine_amd: heat_render needs lut [256, 4] uint8")
+    if base is not None:
+        _require(base, "base", torch.uint8)
+        if base.numel() != 3 * P:
+            raise RuntimeError("madeleine_amd: heat_render needs base [P, 3] uint8 (P = %d, got %d bytes)" % (P, base.numel()))
+    if records_dev is None:
+        records_dev = h2d(records, dev)
+    _require(records_dev, "records_dev", torch.int64)
+    if tuple(records_dev.shape) != (R, HEAT_REC):
+        raise RuntimeError("madeleine_amd: records_dev must be the [R, %d] device copy of records" % HEAT_REC)
+    refusal = (_HEAT_LIMITS, HEAT_MAX_R, HEAT_MAX_SIDE, T, R, C, P, r)
+    ws = _ws_for("mdl_heat_ws_bytes", dev, P, R, C, refusal=refusal)
+    level = torch.empty(C * P, device=dev, dtype=torch.uint16)
+    covered = torch.empty(C * P, device=dev, dtype=torch.uint8)
+    rgba = torch.empty(C * P, 4, device=dev, dtype=torch.uint8)
+    with _timed("heat_render", ("byte", float(C) * P * sum(HEAT_PLANE_BYTES.values()) + (8.0 + 4.0 * C) * T)):
+        if marks is None:
+            _call("mdl_heat_render", xy, cu, values, ld, T, R, C, records, records_dev, P, int(ds), taps, r, lut, base, int(alpha), level,
+                  covered, rgba, ws, _stream(), unsupported=refusal)
+        else:
+            _call("mdl_heat_render_marked", xy, cu, values, ld, T, R, C, records, records_dev, P, int(ds), taps, r, lut, base, int(alpha),
+                  level, covered, rgba, ws, marks, _stream(), unsupported=refusal)
+    return level, covered, rgba
+
+
+HEAT_STAGES = ("clear", "accumulate", "blur_rows", "blur_cols_colour")
+
+
+def heat_render_stages(*args, **kwargs):
+    """heat_render with its stages timed by device events: (level, covered, rgba, {"clear": the memset and the tile table,
+    "accumulate", "blur_rows", "blur_cols_colour": the column pass with level and colour} in ms).  Needs R >= 1 and P >= 1.
+    Synchronises the stream: for tools/exp_heatmap.py, not for a pipeline."""
+    import ctypes
+    events = [torch.cuda.Event(enable_timing=True) for _ in range(HEAT_MARKS)]
+    for ev in events:
+        ev.record()                    # an event's handle exists once it has been recorded
+    marks = (ctypes.c_void_p * HEAT_MARKS)(*[ev.cuda_event for ev in events])
+    out = heat_render(*args, marks=marks, **kwargs)
+    events[-1].synchronize()
+    ms = [events[i].elapsed_time(events[i + 1]) for i in range(HEAT_MARKS - 1)]
+    return out + (dict(zip(HEAT_STAGES, ms)),)
+
+
 # ---- R1: the smooth rank (mdl_smooth_rank).  fp64 Gram, tridiagonal eigenvalues, entropy.  No autograd: embeddings are inputs ----
 RANK_MAX_K = _native._DEFINES["MDL_RANK_MAX_K"]
 RANK_GRAM_ROWS, RANK_GRAM_MAX_CHUNKS, RANK_GRAM_TILE, RANK_TRI_ROWS = (

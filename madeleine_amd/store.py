@@ -7,7 +7,8 @@ any dtype.  One vector per slide comes out of it too, for a downstream cohort: e
 (functional.bag_mean -> mdl_bag_mean); both feed probe.linear_probe without the features leaving the device.
 attention() is embed() with the attention kept (MADELEINE.attend_packed): raw scores, per-bag softmax, percentile ranks, order and
 top-k patches per head for the whole cohort, any stain (functional.attn_softmax / attn_rank -> mdl_attn_softmax / mdl_attn_rank,
-csrc/attn_map.hip).
+csrc/attn_map.hip).  heatmaps() goes on from there to RGBA images: the store holds the patch coordinates of every row (set_coords) and
+madeleine_amd.heatmap renders the values over them (functional.heat_render -> mdl_heat_render, csrc/heat_map.hip).
 
 Replaces, for a cohort that fits in HBM, the reference's input side (madeleine/datasets/wsi_dataset.py): SlideDataset.__getitem__
 re-reads every stain's h5 file for every item of every epoch, draws `sample` rows on the host and collate stacks them, and the stacked
@@ -39,6 +40,7 @@ from . import functional as MF
 
 FP16_MAX = 65504.0
 _MAX_BAG_ROWS = 2 ** 31 - 1
+_MAX_COORD = 1 << 24       # set_coords: 0 <= value < 2^24, the integers float32 (h5io.read_dataset) holds exactly
 ABSENT_BAG_ROWS = 2        # the dataset's zero bag of an absent stain (wsi_dataset.py:66)
 MEAN_WS_BYTES = 64 << 20   # mean_embeddings: the partial sums of one slice of cases stay inside this
 
@@ -54,9 +56,11 @@ class PackedBags(NamedTuple):
 
 
 class DeviceSlideStore:
-    def __init__(self, bags, slide_ids, modalities, device, dtype=torch.float32, resident_bytes=None):
+    def __init__(self, bags, slide_ids, modalities, device, dtype=torch.float32, resident_bytes=None, coords=None, patch_size=None):
         """bags: list over cases of lists over modalities of [n, D] CPU tensors, None for an absent stain.  dtype float16 / bfloat16:
         an opt-in LOSSY store of half the size (features are rounded once, at load time; fp16 refuses a bag it cannot hold).
+        coords, patch_size: the patch coordinates of every bag (set_coords, which may also be called later); without them the store
+        holds none and heatmaps() refuses.
 
         resident_bytes None: the whole store in one device tensor.  An integer >= 0: at most that many bytes of rows go to HBM -- the
         longest prefix of whole bags (stored order) that fits -- and the other bags to the host tier; 0 puts everything on the host, a
@@ -130,6 +134,83 @@ class DeviceSlideStore:
         self.off = self.off_cpu.to(self.device)
         self._zero_bag = None
         self._side = None                                       # the prefetch stream: one per store, made on first use
+        self.coords = self.coord_extents = self.patch_sizes = None
+        if coords is not None:
+            self.set_coords(coords, patch_size)
+        elif patch_size is not None:
+            raise ValueError("DeviceSlideStore: patch_size without coords")
+
+    def set_coords(self, coords, patch_size):
+        """The level-0 top-left corner (x, y) of every stored row: coords is a list over cases of lists over modalities of [n, 2]
+        integer arrays or tensors -- the h5 `coords` dataset beside `features` -- None where the stain is absent; row j of an array
+        belongs to row j of the bag.  patch_size: the level-0 pixels of a patch side, one int for the whole store or a list over
+        cases of lists over modalities (None where absent).
+        Checked on the host: n equals the bag's rows, every value is integral and 0 <= value < 2^24 -- h5io.read_dataset reads through
+        float32, which holds exactly the integers of that range, so a coordinate beyond it may already have been rounded.  ValueError
+        names the bag.  Kept as ONE int32 [T_total, 2] device tensor in store-row order (self.coords), always resident -- in a tiered
+        store too: 8 bytes a row beside at least 1 KB of features -- with the per-bag extents (self.coord_extents [n_bags, 4] int64 =
+        xmin, ymin, xmax, ymax) and patch sizes (self.patch_sizes [n_bags] int64) on the host, from which heatmaps() plans its
+        canvases without a device read."""
+        n_cases, M = len(self), len(self.modalities)
+        if len(coords) != n_cases:
+            raise ValueError("DeviceSlideStore.set_coords: %d cases but %d coordinate lists" % (n_cases, len(coords)))
+        per_bag = not isinstance(patch_size, int) or isinstance(patch_size, bool)
+        if per_bag and (not isinstance(patch_size, (list, tuple)) or len(patch_size) != n_cases):
+            raise ValueError("DeviceSlideStore.set_coords: patch_size must be one int or a list over cases of lists over modalities")
+        total = int(self.off_cpu[-1])
+        xy = torch.empty(total, 2, dtype=torch.int32)
+        ext = torch.empty(self.n_bags, 4, dtype=torch.int64)
+        sizes = torch.empty(self.n_bags, dtype=torch.int64)
+        off = self.off_cpu.tolist()
+        for c in range(n_cases):
+            if len(coords[c]) != M or (per_bag and len(patch_size[c]) != M):
+                raise ValueError("DeviceSlideStore.set_coords: case %d (%s) needs one entry per modality (%d)" % (c, self.slide_ids[c], M))
+            for m in range(M):
+                g = int(self.bag_table[c, m])
+                where = "bag of case %d (%s), modality %s" % (c, self.slide_ids[c], self.modalities[m])
+                if g < 0:
+                    if coords[c][m] is not None:
+                        raise ValueError("DeviceSlideStore.set_coords: coordinates for the absent %s" % where)
+                    continue
+                if coords[c][m] is None:
+                    raise ValueError("DeviceSlideStore.set_coords: the %s is present and has no coordinates" % where)
+                a = torch.as_tensor(coords[c][m])
+                n = off[g + 1] - off[g]
+                if a.dim() != 2 or a.shape[1] != 2 or a.shape[0] != n:
+                    raise ValueError("DeviceSlideStore.set_coords: the %s has %d rows, its coordinates are %s (need [%d, 2])"
+                                     % (where, n, tuple(a.shape), n))
+                if a.dtype == torch.bool or a.is_complex():
+                    raise ValueError("DeviceSlideStore.set_coords: the coordinates of the %s must be numbers (got %s)" % (where, a.dtype))
+                if a.is_floating_point():
+                    a = a.double()
+                    if not bool(torch.isfinite(a).all()) or not bool((a == a.round()).all()):
+                        raise ValueError("DeviceSlideStore.set_coords: the coordinates of the %s are not integral" % where)
+                a = a.cpu()
+                lo_xy, hi_xy = a.min(0).values.long(), a.max(0).values.long()
+                lo, hi = int(lo_xy.min()), int(hi_xy.max())
+                if lo < 0 or hi >= _MAX_COORD:
+                    raise ValueError("DeviceSlideStore.set_coords: the coordinates of the %s span %d .. %d; 0 <= value < 2^24 is the "
+                                     "range float32 reads exactly" % (where, lo, hi))
+                ps = patch_size[c][m] if per_bag else patch_size
+                if isinstance(ps, bool) or not isinstance(ps, int) or not 1 <= ps <= _MAX_COORD:
+                    raise ValueError("DeviceSlideStore.set_coords: the patch size of the %s must be an int in [1, 2^24] (got %r)"
+                                     % (where, ps))
+                xy[off[g]:off[g + 1]] = a.to(torch.int32)
+                ext[g] = torch.cat([lo_xy, hi_xy])
+                sizes[g] = ps
+        self.coords = MF.h2d(xy, self.device)
+        self.coord_extents, self.patch_sizes = ext, sizes
+
+    def coords_of(self, case_indices, modality) -> torch.Tensor:
+        """xy [T, 2] int32 on the device: the coordinates of the rows of pack_modality(case_indices, modality) with whole bags, in its
+        order (case_indices None: every case that has the stain).  A gather of contiguous row ranges (torch.cat of views): host work
+        per bag, none per row."""
+        if self.coords is None:
+            raise RuntimeError("DeviceSlideStore.coords_of: the store holds no coordinates (set_coords)")
+        _, bag, _ = self._modality_plan(case_indices, modality)
+        off = self.off_cpu
+        views = [self.coords[int(off[g]):int(off[g + 1])] for g in bag.tolist()]
+        return torch.cat(views) if views else self.coords[:0]
 
     def _host_tier(self, n_rows):
         """[n_rows, D] of the store's dtype in host memory: registered (pinned) on a GPU device, an ordinary tensor on the CPU."""
@@ -174,16 +255,30 @@ class DeviceSlideStore:
             torch.cuda.current_stream().synchronize()
 
     @classmethod
-    def from_dataset(cls, dataset, device, dtype=torch.float32, resident_bytes=None):
-        """One pass over a SlideDataset(sample=-1, train=True): keeps feats[m] where the label is 1 and drops the 2-token zero bags."""
+    def from_dataset(cls, dataset, device, dtype=torch.float32, resident_bytes=None, coords=False, patch_size=None):
+        """One pass over a SlideDataset(sample=-1, train=True): keeps feats[m] where the label is 1 and drops the 2-token zero bags.
+        coords=True: also reads the `coords` dataset of every present stain from the h5 path SlideDataset builds for its features
+        (h5io.read_dataset(path, "coords")) and hands them to set_coords with patch_size, which is then required."""
         if getattr(dataset, "sample", -1) != -1 or not getattr(dataset, "train", True):
             raise ValueError("DeviceSlideStore.from_dataset needs a SlideDataset(sample=-1, train=True): whole bags, every stain")
-        bags, ids = [], []
+        if coords and patch_size is None:
+            raise ValueError("DeviceSlideStore.from_dataset: coords=True needs patch_size (level-0 pixels of a patch side)")
+        bags, ids, xy = [], [], []
+        if coords:
+            import os
+            from . import h5io
         for i in range(len(dataset)):
             item = dataset[i]
-            bags.append([f if int(lab) == 1 else None for f, lab in zip(item['feats'], item['modality_labels'])])
+            present = [int(lab) == 1 for lab in item['modality_labels']]
+            bags.append([f if p else None for f, p in zip(item['feats'], present)])
             ids.append(item['slide_id'])
-        return cls(bags, ids, dataset.modalities, device, dtype=dtype, resident_bytes=resident_bytes)
+            if coords:
+                split = dataset.dataframe.iloc[i]['split']
+                special = "" if split == "train" else "_%s" % split
+                xy.append([h5io.read_dataset(os.path.join(dataset.features_path, "%s_%s%s.h5" % (item['slide_id'], m, special)),
+                                             "coords").reshape(-1, 2) if p else None for m, p in zip(dataset.modalities, present)])
+        return cls(bags, ids, dataset.modalities, device, dtype=dtype, resident_bytes=resident_bytes, coords=xy if coords else None,
+                   patch_size=patch_size if coords else None)
 
     def __len__(self):
         return len(self.slide_ids)
@@ -516,6 +611,45 @@ class DeviceSlideStore:
         order, pct, ti, tv = MF.attn_rank(raw, cu_d, k=topk, percentile=percentile)
         res.update(cu_seqlens=cu_d, lens=lens.tolist(), raw=raw, attention=attention, percentile=pct, order=order, topk_idx=ti,
                    topk_val=tv)
+        return res
+
+    def heatmaps(self, model, modality=0, case_indices=None, source='percentile', heads='mean', downsample=None, sigma=0.0, cmap='jet',
+                 alpha=255, thumbnails=None, crop=False, max_bytes=None, bags_per_launch=None, precision=None, host_wgs=0) -> dict:
+        """The attention heatmaps of one stain's bag of every case asked for (None: every case that has the stain), on the device:
+        attention()'s planning and read-out, then heatmap.render over the store's coordinates (set_coords).
+          source 'percentile'         the value of a patch is its percentile rank / 100 (the CLAM convention)
+                 'attention' | 'raw'  the softmax weights | raw scores, min-max per bag and channel on the device (a constant bag: 0.5)
+          heads  'mean' | 'all' | h   one channel from the mean over the head axis (taken first, before the min-max and the quantiser),
+                                      one channel per head, or head h alone
+          downsample                  level-0 pixels per canvas pixel; None: the patch size (the bags asked for must then share one), so
+                                      that without overlap a patch is exactly one pixel
+          sigma, cmap, alpha, crop    as heatmap.render; thumbnails: per bag an [H, W, 3] uint8 image of its canvas, or None
+          max_bytes                   workspace + outputs of one render group stay inside it (None: heatmap.RENDER_BYTES); the images
+                                      do not depend on it
+        Returns embeds, cases, slide_ids as attention() plus, per bag, rgba [C, H, W, 4] uint8, level [C, H, W] uint16, covered
+        [C, H, W] uint8 (lists, on the device) and canvas (W, H, ox, oy), with the downsample used and values [T, C], cu_seqlens."""
+        from . import heatmap as HM
+        self._require_device("heatmaps")
+        if self.coords is None:
+            raise RuntimeError("DeviceSlideStore.heatmaps: the store holds no coordinates (set_coords)")
+        if source not in ('percentile', 'attention', 'raw'):
+            raise ValueError("DeviceSlideStore.heatmaps: source must be 'percentile', 'attention' or 'raw' (got %r)" % (source,))
+        att = self.attention(model, modality, case_indices, topk=0, percentile=source == 'percentile', bags_per_launch=bags_per_launch,
+                             precision=precision, host_wgs=host_wgs)
+        cases, cu = att["cases"], att["cu_seqlens"]
+        values = HM.heat_values(att, source, heads)
+        bag = self.bag_table[:, modality].index_select(0, cases).long()
+        sizes = self.patch_sizes.index_select(0, bag)
+        if downsample is None:
+            if sizes.numel() and int(sizes.min()) != int(sizes.max()):
+                raise ValueError("DeviceSlideStore.heatmaps: downsample None means the patch size, and the bags asked for have patch "
+                                 "sizes %d .. %d" % (int(sizes.min()), int(sizes.max())))
+            downsample = int(sizes[0]) if sizes.numel() else 1
+        out = HM.render(self.coords_of(cases, modality), cu, values, sizes, downsample, sigma, cmap, alpha, thumbnails, crop,
+                        extents=self.coord_extents.index_select(0, bag), max_bytes=HM.RENDER_BYTES if max_bytes is None else max_bytes,
+                        lens=att["lens"])
+        res = {k: att[k] for k in ("embeds", "cases", "slide_ids", "cu_seqlens", "lens")}
+        res.update(out, values=values)
         return res
 
     def packed_batches(self, batch_size, max_tokens=None, shuffle=True, drop_last=False, seed=0, rank=0, world_size=1, prefetch=None):
