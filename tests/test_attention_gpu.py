@@ -105,6 +105,20 @@ def permuted(s, lens, perm):
 
 
 # ------------------------------------------------------------------------------------------------ rank
+def check_rank(name, H, k, order, pct, ti, tv):
+    """The outputs of one attn_rank call on scores_of(name, H) against the reference, exactly."""
+    s, want = scores_of(name, H), reference(name, H)
+    assert order.shape == (H, len(s)) and order.dtype == torch.int32 and pct.shape == s.shape and pct.dtype == torch.float32
+    assert np.array_equal(order.cpu().numpy(), want["order"]), k
+    assert np.array_equal(bits(pct), want["pct"].view(np.int32)), k
+    if k == 0:
+        assert ti is None and tv is None
+        return
+    assert ti.shape == tv.shape == (len(LENS), H, k) and ti.dtype == torch.int32 and tv.dtype == torch.float32
+    assert np.array_equal(ti.cpu().numpy(), want["topk_idx"][:, :, :k]), k
+    assert np.array_equal(bits(tv), np.ascontiguousarray(want["topk_val"][:, :, :k]).view(np.int32)), k
+
+
 @pytest.mark.parametrize("pad", [0, 3], ids=["ld=H", "ld=H+3"])
 @pytest.mark.parametrize("H", [1, 4])
 @pytest.mark.parametrize("name", SETS)
@@ -115,15 +129,7 @@ def test_rank_equals_the_reference_exactly(dev, name, H, pad):
     before = sd.clone()
     for k in (0, 1, 16, KMAX):
         order, pct, ti, tv = MF.attn_rank(sd, cu, k=k)
-        assert order.shape == (H, len(s)) and order.dtype == torch.int32 and pct.shape == s.shape and pct.dtype == torch.float32
-        assert np.array_equal(order.cpu().numpy(), want["order"]), k
-        assert np.array_equal(bits(pct), want["pct"].view(np.int32)), k
-        if k == 0:
-            assert ti is None and tv is None
-            continue
-        assert ti.shape == tv.shape == (len(LENS), H, k) and ti.dtype == torch.int32 and tv.dtype == torch.float32
-        assert np.array_equal(ti.cpu().numpy(), want["topk_idx"][:, :, :k]), k
-        assert np.array_equal(bits(tv), np.ascontiguousarray(want["topk_val"][:, :, :k]).view(np.int32)), k
+        check_rank(name, H, k, order, pct, ti, tv)
     again = MF.attn_rank(sd, cu, k=KMAX)
     for a, b in zip(again, (order, pct, ti, tv)):
         assert np.array_equal(bits(a), bits(b)), "two calls"
@@ -221,8 +227,14 @@ def test_the_read_out_does_not_synchronise_the_host(dev):
 def test_softmax_is_accurate_to_its_addition_depth(dev, name, H):
     """|attn - a64| <= (h(n) + |s - m| + K) 2^-24 a64 per element, m the exact maximum, l the sum, attn monotone in raw."""
     s = scores_of(name, H)
+    attn, m, l = MF.attn_softmax(on_device(s, dev, 0), torch.from_numpy(cu_of(LENS)).to(dev))
+    check_softmax(name, H, attn, m, l)
+
+
+def check_softmax(name, H, attn, m, l):
+    """The bound of test_softmax_is_accurate_to_its_addition_depth on the outputs (attn, m, l) of one call on scores_of(name, H)."""
+    s = scores_of(name, H)
     cu = cu_of(LENS)
-    attn, m, l = MF.attn_softmax(on_device(s, dev, 0), torch.from_numpy(cu).to(dev))
     assert attn.shape == s.shape and m.shape == l.shape == (len(LENS), H)
     attn, m, l = attn.cpu().numpy(), m.cpu().numpy(), l.cpu().numpy()
     worst, k_obs = -np.inf, 0.0

@@ -29,7 +29,9 @@ high-word term fail (b) and nothing else.
 
 Not covered, because the operands would be tens of GB: the gate forward / backward kernels and every LayerNorm kernel above element index
 2^32 (drop_row_key in the epilogues, act_row_key).  Dropping the high-word term there makes no test fail; for the gate only (b), the
-export, sees it."""
+export, sees it.  tests/test_stride_limits_gpu.py does not change this: it runs the gates with rows of E and dE past byte 2^32 and
+element 2^31 of their buffers (wide row strides, at the launchers' limits), which holds their ADDRESSES to 64 bits, but the hash index
+is token * H * 512 + column, a function of T and not of the stride, and T stays a few hundred there."""
 import numpy as np
 import pytest
 import torch
@@ -102,7 +104,8 @@ def test_exported_gate_mask_across_index_2_pow_32(dev, monkeypatch):
     starts exactly there.  Token rows [0, 8) and [2^20 - 8, 2^20 + 8) against the model at p = 0.1 (16-bit fields) and, into the same
     buffer, p = 0.25 (byte fields), both masks.  This is the only test that executes drop_row_key's high-word term: the gate forward /
     backward kernels and the LayerNorm kernels (act_row_key) are not run there -- their operands would be tens of GB -- so a wrong high
-    word in those is not seen by any test."""
+    word in those is not seen by any test (the wide strides of tests/test_stride_limits_gpu.py move addresses past 2^32, not the hash
+    index, which depends on T alone)."""
     monkeypatch.delenv("MADELEINE_DROP_16BIT", raising=False)
     free = torch.cuda.mem_get_info(dev)[0]
     if free < 6 * 2 ** 30:

@@ -62,9 +62,11 @@ def records_of(canvases):
 def device_render(dev, xy, cu, values, canvases, ds, taps, lut, alpha, bases=None, ld=None):
     """mdl_heat_render through functional.heat_render; per bag (level, covered, rgba) as device tensors."""
     rec, P = records_of(canvases)
-    v = torch.from_numpy(np.asarray(values, dtype=np.float32))
+    v = values if torch.is_tensor(values) else torch.from_numpy(np.asarray(values, dtype=np.float32))
     T, C = v.shape
-    if ld is not None:                                        # a wider row, NaN between the rows
+    if torch.is_tensor(values):                               # the caller's own view of the values on the device, at its row stride
+        assert ld is None and v.is_cuda
+    elif ld is not None:                                      # a wider row, NaN between the rows
         wide = torch.full((T, ld), float("nan"))
         wide[:, :C] = v
         v = wide.to(dev)[:, :C]

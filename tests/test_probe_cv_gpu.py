@@ -73,7 +73,10 @@ def _E(z, z64):
 def test_optimality(name):
     """Every fold converges, and the fp64 gradient of the primal objective at the returned (W, b) is within max(2 gtol, 2 r32): the stop
     rule plus the kernel's own fp32 evaluation error, or twice what the same algorithm reaches in fp32 on the host."""
-    co, out = _cohort_run(name)
+    _optimality(name, *_cohort_run(name))
+
+
+def _optimality(name, co, out):
     X32 = co["X"].float()
     worst = 0.0
     for p, pr in enumerate(co["problems"]):
@@ -92,7 +95,10 @@ def test_decision_values(name):
     """E_p = max_S |z - z64| / max_S |z64| <= 1e-3 (the project's parity contract) for every fold.
     Worst E_p measured on the MI355X: FA 1.7e-7, FB 3.0e-6, FC2 3.2e-7, FC4 1.5e-6, FC8 4.6e-6 (5 to 12 Newton and 40 to 354 CG steps per
     binary fit, 6 to 11 and 82 to 732 per multinomial fit)."""
-    co, out = _cohort_run(name)
+    _decision_values(name, *_cohort_run(name))
+
+
+def _decision_values(name, co, out):
     worst = 0.0
     for p, pr in enumerate(co["problems"]):
         E = _E(out["z"][p], pr["z64"])
@@ -124,7 +130,10 @@ def test_metrics_against_fp64_optimum(name):
     """With D = max_S |z - z64|: the confusion matrix differs from the fp64 one in at most as many test cases as have an fp64 margin
     below 2 D (never more than 4 % of them), and the AUC by at most the share of (positive, negative) pairs whose fp64 score gap is below
     2 D, plus 1e-6 for the fp32 format of auc_out."""
-    co, out = _cohort_run(name)
+    _metrics_against_fp64_optimum(name, *_cohort_run(name))
+
+
+def _metrics_against_fp64_optimum(name, co, out):
     for p, pr in enumerate(co["problems"]):
         n_test, close = _check_metrics(name, pr["fold"], co["C"], co["y"], pr["idx"], out["z"][p], pr["z64"], out["conf"][p], out["auc"][p])
         print("%s fold=%d: %d test cases, %d within 2 D of the boundary" % (name, pr["fold"], n_test, close))

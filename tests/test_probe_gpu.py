@@ -60,7 +60,10 @@ def _margin(z64, C):
 def test_optimality(name):
     """Every problem converges, and the fp64 gradient of the primal objective at the returned (W, b) is within max(2 gtol, 2 r32):
     the stop rule plus the kernel's own fp32 evaluation error, or twice what the reference algorithm reaches in fp32."""
-    co, out = _cohort_run(name)
+    _optimality(name, *_cohort_run(name))
+
+
+def _optimality(name, co, out):
     X32 = co["X"].float()
     worst = 0.0
     for p, pr in enumerate(co["problems"]):
@@ -78,7 +81,10 @@ def test_optimality(name):
 def test_decision_values(name):
     """E_p = max_S |z - z64| / max_S |z64| <= 1e-3 (the project's parity contract) for every problem.
     Worst E_p measured on the MI355X: A 2.6e-6, B 1.2e-5, C2 7.5e-6, C4 3.3e-5."""
-    co, out = _cohort_run(name)
+    _decision_values(name, *_cohort_run(name))
+
+
+def _decision_values(name, co, out):
     worst = 0.0
     for p, pr in enumerate(co["problems"]):
         E = float((out["z"][p].double() - pr["z64"]).abs().max() / pr["z64"].abs().max())
@@ -92,7 +98,10 @@ def test_metrics_against_fp64_optimum(name):
     """With D = max_S |z - z64|: the confusion matrix differs from the fp64 one in at most as many test cases as have an fp64 margin
     below 2 D (never more than 4 % of them), and the AUC by at most the share of (positive, negative) pairs whose fp64 score gap is below
     2 D, plus 1e-6 for the fp32 format of auc_out."""
-    co, out = _cohort_run(name)
+    _metrics_against_fp64_optimum(name, *_cohort_run(name))
+
+
+def _metrics_against_fp64_optimum(name, co, out):
     C, y = co["C"], co["y"]
     for p, pr in enumerate(co["problems"]):
         test = R.test_mask(y.clone(), pr["idx"])

@@ -32,8 +32,13 @@ def run(E):
 
 def check(E_np, dev, tol, label):
     """One matrix against the oracle: rank to tol relative, sigma^2 to SIGMA_TOL sigma_max^2, sigma descending and >= 0, H = ln rank."""
-    want, S = RR.oracle(E_np)
     rank, H, sigma = run(torch.from_numpy(np.array(E_np)).to(dev))      # a writable, contiguous copy
+    return check_result(E_np, rank, H, sigma, tol, label)
+
+
+def check_result(E_np, rank, H, sigma, tol, label):
+    """The bounds of check() on the results (exp(H), H, sigma) of one call on E_np."""
+    want, S = RR.oracle(E_np)
     dev_rank = abs(rank - want) / want
     dev_sigma = float(np.abs(sigma ** 2 - S ** 2).max() / S.max() ** 2)
     print("%s: oracle %.6f device %.6f rel. dev. %.2e, sigma^2 dev. %.2e" % (label, want, rank, dev_rank, dev_sigma))

@@ -92,10 +92,16 @@ def cosine_case(n, m, d, noise):
 
 
 def check_cosine(dev, n, m, d, noise, k, col_chunks=0):
+    Q, K, _, _ = cosine_case(n, m, d, noise)
+    return check_cosine_result(n, m, d, noise, k, host(MF.retrieval(torch.from_numpy(Q).to(dev), torch.from_numpy(K).to(dev), k=k, col_chunks=col_chunks)))
+
+
+def check_cosine_result(n, m, d, noise, k, res):
+    """The bounds of check_cosine on `res`, the host() of one retrieval of cosine_case(n, m, d, noise) with this k."""
     Q, K, S64, (lo, hi, pair) = cosine_case(n, m, d, noise)
     t = RR.tol(d)
     assert int((lo != hi).sum()) == 0      # the cohort excuses nothing (asserted on the CPU too)
-    g, e, ps, ti, tv = host(MF.retrieval(torch.from_numpy(Q).to(dev), torch.from_numpy(K).to(dev), k=k, col_chunks=col_chunks))
+    g, e, ps, ti, tv = res
     err = float(np.abs(ps.astype(np.float64) - pair).max())
     print("(%d, %d, %d, %s): max |pair_sim - s64| %.3e, tol %.3e; median rank %.1f, worst %d"
           % (n, m, d, noise, err, t, np.median(1 + g + e), (1 + g + e).max()))

@@ -78,17 +78,23 @@ def test_mean_is_accurate_to_its_addition_depth(dev, D, dtype):
              MF._stream())
     assert not bool(torch.isnan(out).any())
     assert torch.equal(out, MF.bag_mean(store, off, bag_d, ch, n_chunks))
+    check_mean(store, off, out)
+    assert torch.equal(store, before)
+
+
+def check_mean(store, off, out, lens=LENS, bag=BAG):
+    """The depth bound of test_mean_is_accurate_to_its_addition_depth on `out`, the means of the bags `bag` of a store of `lens` rows."""
+    D, dtype = store.shape[1], store.dtype
     wide, offs = store.double(), off.tolist()
-    for r, g in enumerate(BAG):
+    for r, g in enumerate(bag):
         if g < 0:
             assert not bool(out[r].any()) and not bool(torch.signbit(out[r]).any())
             continue
         x = wide[offs[g]:offs[g + 1]]
         err = (out[r].double() - x.mean(0)).abs()
-        bound = 2.0 * depth(LENS[g], D) * U * x.abs().mean(0)
-        print("D %d %s len %d: h %d, max err / bound %.3f" % (D, dtype, LENS[g], depth(LENS[g], D), float((err / bound).max())))
-        assert bool((err <= bound).all()), (LENS[g], float((err / bound).max()))
-    assert torch.equal(store, before)
+        bound = 2.0 * depth(lens[g], D) * U * x.abs().mean(0)
+        print("D %d %s len %d: h %d, max err / bound %.3f" % (D, dtype, lens[g], depth(lens[g], D), float((err / bound).max())))
+        assert bool((err <= bound).all()), (lens[g], float((err / bound).max()))
 
 
 @pytest.mark.parametrize("width,D", [(40, 32), (36, 32), (33, 32), (40, 33)])

@@ -2,7 +2,7 @@
 launch, a stride below the row width, a stride that breaks the documented alignment and a stride above the limit its 32-bit offsets
 allow (include/madeleine_amd.h states each limit as rows * stride bytes + column bytes <= 2^31 - 1; the table below carries the same
 rows / column terms).  Every call is an EMPTY problem (T = 0, rows = 0, M = 0 or n_bags = 0) on fake host pointers: a missing refusal
-returns MDL_OK instead of launching a kernel on host memory.  Entry points that return MDL_OK on an empty problem without touching
+returns MDL_OK instead of launching a kernel on host memory (one exception, marked below: the narrow-output tile of mdl_split_gemm_nt).  Entry points that return MDL_OK on an empty problem without touching
 their pointers (`empty_ok`) are also called with valid strides -- the padded ones, and the largest aligned stride within the limit --
 so that a refusal is known to come from the stride and from nothing else in the argument list."""
 import ctypes
@@ -103,9 +103,9 @@ def _lin_bwd(N, K, ldy="ldy"):
     return lambda s: [P(0), s["ldx"], P(1), P(2), s[ldy], P(3), s["lddx"], P(4), P(5), 0, N, K, P(6), None]
 
 
-def _nt(N, K, group):
+def _nt(N, K, group, M=0):
     def args(s):
-        a = [P(0), s["a_rsb"], P(1), P(2), s["b_rsb"], P(3), P(4), s["ldc"], 0, N, K, P(5)]
+        a = [P(0), s["a_rsb"], P(1), P(2), s["b_rsb"], P(3), P(4), s["ldc"], M, N, K, P(5)]
         a += [None, None, P(6), P(7), 3, None] if group else [0, None, None, None, None, 3, None]
         return a
     return args
@@ -150,6 +150,10 @@ def _entries():
     nt = [S("a_rsb", 256, 16, 1, 256), S("b_rsb", 256, 16, 1, 256), S("ldc", 256, 4, 4, 1)]
     add("mdl_split_gemm_nt", _nt(256, 64, False), nt, True)
     add("mdl_split_gemm_nt_group_bias", _nt(256, 64, True), nt, True)
+    # the narrow-output tile (N <= 128, M > 256, no row_gate, no group_bias) has limits of its own; the launcher picks it by M, so
+    # this one entry is not an empty problem: every call made for it (empty_ok = False) is one the launcher refuses
+    add("mdl_split_gemm_nt", _nt(128, 64, False, M=257), [S("a_rsb", 256, 16, 1, 512), S("b_rsb", 256, 16, 1, 128), S("ldc", 128, 4, 4, 1)],
+        False, "-narrow")
     add("mdl_split_gemm_tn", lambda s: [P(0), s["a_rsb"], P(1), 64, P(2), s["b_rsb"], P(3), 128, P(4), 0, None, P(5), 3, None],
         [S("a_rsb", 256, 16, 1, 32), S("b_rsb", 512, 16, 1, 32)], False)
     return out
@@ -200,5 +204,6 @@ def test_header_states_the_stride_rules():
     with open(_build.HEADER) as f:
         header = f.read()
     assert "requires ldE == H*512" not in header            # the bf16 gate backward reads E in place, at any stride
-    for text in ("127 * 4 ldE + 48 <= 2^31 - 1", "63 * 2 ldE + 496 <= 2^31 - 1", "256 a_rsb and 256 b_rsb <= 2^31 - 1", "of 4 on the pooling entry points"):
+    for text in ("127 * 4 ldE + 48 <= 2^31 - 1", "63 * 2 ldE + 496 <= 2^31 - 1", "256 a_rsb and 256 b_rsb <= 2^31 - 1", "512 a_rsb and 128 b_rsb on the narrow-output tile",
+                 "of 4 on the pooling entry points"):
         assert text in header, text

@@ -11,7 +11,13 @@ the valid region only.  Every case asserts
   (b) every padding element of every output buffer still holds its fill pattern (compared as integers);
   (c) the valid region agrees with a plain fp64 CPU reference within the bound the suite already states for that kernel
       (tests/test_dispatch_edges_gpu.py, tests/test_hip_kernels.py, tests/test_bf16_gpu.py, tests/test_ragged_views_gpu.py).
-Shapes are the smallest that reach each tile and a ragged tail; where a shape is chosen for a branch the plan query is asserted first."""
+Shapes are the smallest that reach each tile and a ragged tail; where a shape is chosen for a branch the plan query is asserted first.
+
+The pads here are 4 to 40 elements: they show that a kernel uses the stride it is given, not that its 32-bit offsets hold up to the limit
+the launcher accepts.  tests/test_stride_limits_gpu.py runs the runners of this file (_run_gate, _run_linear, the *_runner functions) a
+second time on the layout of tests/_wide_cases.py: every stride argument with a limit AT its limit, with rows past byte 2^32, and every
+limit-free one (the pooling family, the image writers) with rows past element 2^31.  Still not run anywhere: the exact 32-bit edge of
+the kernels listed in _wide_cases.ARGUED, whose smallest T times the limit stride exceeds any buffer a test should take."""
 import functools
 
 import numpy as np
@@ -89,20 +95,23 @@ class Lay:
             assert torch.equal(after, before), "a kernel wrote outside the valid columns of an output"
 
 
-def _strided_vs_contiguous(dev, mode, run, check_ref):
+def _strided_vs_contiguous(dev, mode, run, check_ref, lay=None):
     """run(lay) -> {name: output tensor (valid region)}: runs it contiguously and in `mode`, asserts (a), (b) and, through
-    check_ref(outputs as CPU tensors), (c)."""
+    check_ref(outputs as CPU tensors), (c).  `lay`: a layout object of the caller's (tests/test_stride_limits_gpu.py) in place of
+    Lay(mode); its check_padding() may clear the buffers it scans, so the outputs are copied out first."""
     base = run(Lay("contig", dev))
     torch.cuda.synchronize()
     base = {k: v.clone() for k, v in base.items()}
-    lay = Lay(mode, dev)
+    lay = Lay(mode, dev) if lay is None else lay
     got = run(lay)
     torch.cuda.synchronize()
+    got = {k: v.clone() for k, v in got.items()}
     assert set(got) == set(base)
     for k in sorted(got):
         assert torch.equal(_bits(got[k]), _bits(base[k])), "%s differs from the contiguous call (%s)" % (k, mode)
     lay.check_padding()
-    check_ref({k: v.float().cpu() for k, v in got.items()})
+    # (fp32 and bf16 outputs reach the check as fp32, as they always did; fp64 and integer outputs of the newer families as they are)
+    check_ref({k: v.float().cpu() if v.is_floating_point() and v.dtype != torch.float64 else v.cpu() for k, v in got.items()})
 
 
 def _nan(dev, *shape, dtype=F32):
@@ -183,9 +192,10 @@ def _gate_ref_dE(case, acc, pterm):
     return want
 
 
-def _run_gate(dev, lay, case, dtype, T, H, p, forward=True):
+def _run_gate(dev, lay, case, dtype, T, H, p, forward=True, fwd_contig=False):
     """mdl_abmil_gate_fwd, mdl_abmil_gate_bwd, mdl_abmil_attnpool_bwd and mdl_abmil_attnpool_bwd_phases (phases 1, then 2) of one
-    storage type on the layout `lay`: E and dE strided (one ldE serves both), everything else contiguous as the ABI has it."""
+    storage type on the layout `lay`: E and dE strided (one ldE serves both), everything else contiguous as the ABI has it.
+    fwd_contig: the forward that supplies act_a / act_b reads a contiguous copy of E (for an ldE that only the backward accepts)."""
     from madeleine_amd import _native
     from madeleine_amd import functional as MF
     E, w, ds, ka, kb, _, dE0, pool = case
@@ -198,7 +208,8 @@ def _run_gate(dev, lay, case, dtype, T, H, p, forward=True):
     dsd = ds.to(dev)
     out = {}
     _poison(dev, getattr(lib, "mdl_abmil_gate_fwd%s_ws_bytes" % sfx)(T, H) + 3 * T * H * 512 * 4)
-    sc, a, b = MF.gate_fwd_raw(Ev, Wa, ba, Wb, bb, wc, bc, p, 11, kad, kbd, True)
+    assert not (forward and fwd_contig)
+    sc, a, b = MF.gate_fwd_raw(Ev.contiguous() if fwd_contig else Ev, Wa, ba, Wb, bb, wc, bc, p, 11, kad, kbd, True)
     if forward:
         out.update(scores=sc, act_a=a.view(T, -1), act_b=b.view(T, -1))
     for name, acc, pterm, entry in _gate_variants(T):
@@ -226,19 +237,33 @@ def _run_gate(dev, lay, case, dtype, T, H, p, forward=True):
 GRAD_ORDER = ("dWa", "dba", "dWb", "dbb", "dwc", "dbc")     # the order of _gate64's results after scores and dE
 
 
+def _check_gate_f32(case, T, got, forward=True):
+    """The bounds of the fp32 gate (and of the split one); without the forward, the scores slot of _check_gate_fp32 gets the reference."""
+    ref = case[5]
+    if forward:
+        assert rel_err(got["scores"], ref[0]) < 1e-5 and max_rel(got["scores"], ref[0]) < TOL, "scores"
+    for name, acc, pterm, _ in _gate_variants(T):
+        res = [got["scores"] if forward else ref[0].float(), got[name + ".dE"]]
+        res += [got[name + "." + n].reshape(r.shape) for n, r in zip(GRAD_ORDER, ref[2:])]
+        _check_gate_fp32(res, [ref[0], _gate_ref_dE(case, acc, pterm)] + list(ref[2:]))
+
+
+def _check_gate_b16(case, T, got, forward=True):
+    ref = case[5]
+    if forward:
+        assert float((got["scores"].double() - ref[0]).abs().max()) < 2 * EPS_BF16 * float(ref[0].abs().max()), "scores"
+    for name, acc, pterm, _ in _gate_variants(T):
+        assert rel_err(got[name + ".dE"], _gate_ref_dE(case, acc, pterm)) < 5e-3, name + ".dE"
+        for n, r in zip(GRAD_ORDER, ref[2:]):
+            assert rel_err(got[name + "." + n].reshape(r.shape), r) < (1e-5 if n == "dbc" else 5e-3), name + "." + n
+
+
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("T,H,p", [(40, 1, 0.0), (40, 4, 0.25), (300, 1, 0.0), (300, 4, 0.0)])
 def test_gate_fp32(dev, mode, T, H, p):
     _expect_plan("gate_fp32_bwd", T, H, 0, dict(splits=1))
     case = _gate_case(T, H, p, False)
-    ref = case[5]
-
-    def check(got):
-        assert rel_err(got["scores"], ref[0]) < 1e-5 and max_rel(got["scores"], ref[0]) < TOL, "scores"
-        for name, acc, pterm, _ in _gate_variants(T):
-            res = [got["scores"], got[name + ".dE"]] + [got[name + "." + n].reshape(r.shape) for n, r in zip(GRAD_ORDER, ref[2:])]
-            _check_gate_fp32(res, [ref[0], _gate_ref_dE(case, acc, pterm)] + list(ref[2:]))
-    _strided_vs_contiguous(dev, mode, lambda lay: _run_gate(dev, lay, case, F32, T, H, p), check)
+    _strided_vs_contiguous(dev, mode, lambda lay: _run_gate(dev, lay, case, F32, T, H, p), lambda got: _check_gate_f32(case, T, got))
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -253,16 +278,7 @@ def test_gate_bf16(dev, mode, T, H, fwd, want_fwd, want_bwd):
     _expect_plan("gate_bf16_fwd", T, H, 0, want_fwd)
     _expect_plan("gate_bf16_bwd", T, H, 0, want_bwd)
     case = _gate_case(T, H, 0.0, True)
-    ref = case[5]
-
-    def check(got):
-        if fwd:
-            assert float((got["scores"].double() - ref[0]).abs().max()) < 2 * EPS_BF16 * float(ref[0].abs().max()), "scores"
-        for name, acc, pterm, _ in _gate_variants(T):
-            assert rel_err(got[name + ".dE"], _gate_ref_dE(case, acc, pterm)) < 5e-3, name + ".dE"
-            for n, r in zip(GRAD_ORDER, ref[2:]):
-                assert rel_err(got[name + "." + n].reshape(r.shape), r) < (1e-5 if n == "dbc" else 5e-3), name + "." + n
-    _strided_vs_contiguous(dev, mode, lambda lay: _run_gate(dev, lay, case, BF, T, H, 0.0, forward=fwd), check)
+    _strided_vs_contiguous(dev, mode, lambda lay: _run_gate(dev, lay, case, BF, T, H, 0.0, forward=fwd), lambda got: _check_gate_b16(case, T, got, fwd))
 
 
 def _image(lay, x, k, pad_rows=0):
@@ -281,38 +297,49 @@ def _image(lay, x, k, pad_rows=0):
 def test_gate_split(dev, mode, T, H):
     """mdl_abmil_gate_fwd_split and mdl_abmil_attnpool_bwd_split: the image of E at a wide e_rsb, dE at a wide ldE; phases 3, and 1
     followed by 2; plain and with the pooling term."""
-    from madeleine_amd import functional as MF
     _expect_plan("gate_split_bwd", T, H, 0, dict(splits=2 if T > 4096 else 1))
     case = _gate_case(T, H, 0.0, False)
-    E, w, ds, _, _, ref, dE0, pool = case
-    variants = [("plain", 0, None, (3,)), ("plain_acc_1_2", 1, None, (1, 2)), ("ragged_acc", 1, True, (3,)), ("ragged_1_2", 0, True, (1, 2))]
+    _strided_vs_contiguous(dev, mode, lambda lay: _run_gate_split(dev, lay, case, T, H), lambda got: _check_gate_split(case, got))
 
-    def run(lay):
-        Ei, esc = _image(lay, E.to(dev), 0)
-        Wa, ba, Wb, bb, wc, bc = [x.to(dev) for x in w]
-        sc, a, b = _nan(dev, T, H), _nan(dev, T, H, 512), _nan(dev, T, H, 512)
-        MF._call("mdl_abmil_gate_fwd_split", Ei, Ei.stride(0) * 4, esc, Wa, ba, Wb, bb, wc, bc, sc, a, b, T, H, 0.0, 11, None, None,
-                 _ws(dev, "mdl_abmil_gate_fwd_split_ws_bytes", T, H), _stream())
-        out = dict(scores=sc, act_a=a.view(T, -1), act_b=b.view(T, -1))
-        for name, acc, pterm, phases in variants:
-            dE = lay.out(T, H * 512, F32, k=1, init=dE0 if acc else None)
-            grads = [_nan(dev, *x.shape) for x in (Wa, Wb, ba, bb, wc, bc)]
-            ws = _ws(dev, "mdl_abmil_gate_bwd_split_ws_bytes", T, H)
-            q = pool[pterm] if pterm is not None else None
-            pt = [q["scores"].to(dev), q["m"].to(dev), q["l"].to(dev), q["dp"].to(dev), q["row_bag"].to(dev), 0] if q else [None] * 5 + [0]
-            for ph in phases:
-                MF._call("mdl_abmil_attnpool_bwd_split", Ei, Ei.stride(0) * 4, esc, Wa, Wb, wc, a, b, ds.to(dev), dE, dE.stride(0), acc,
-                         *grads, T, H, 0.0, 11, None, None, *pt, None, ws, _stream(), ph, 3)
-            out[name + ".dE"] = dE
-            for n, gten in zip(("dWa", "dWb", "dba", "dbb", "dwc", "dbc"), grads):
-                out[name + "." + n] = gten.view(gten.shape[0], -1)
-        return out
 
-    def check(got):
-        for name, acc, pterm, _ in variants:
-            res = [got["scores"], got[name + ".dE"]] + [got[name + "." + n].reshape(r.shape) for n, r in zip(GRAD_ORDER, ref[2:])]
-            _check_gate_fp32(res, [ref[0], _gate_ref_dE(case, acc, pterm)] + list(ref[2:]))
-    _strided_vs_contiguous(dev, mode, run, check)
+SPLIT_VARIANTS = [("plain", 0, None, (3,)), ("plain_acc_1_2", 1, None, (1, 2)), ("ragged_acc", 1, True, (3,)), ("ragged_1_2", 0, True, (1, 2))]
+
+
+def _run_gate_split(dev, lay, case, T, H, forward=True, fwd_contig=False):
+    """mdl_abmil_gate_fwd_split and the SPLIT_VARIANTS of mdl_abmil_attnpool_bwd_split: the image of E is stride argument 0, dE is 1.
+    fwd_contig: the forward that supplies act_a / act_b reads an image at its contiguous row stride (for an e_rsb that only the
+    backward accepts)."""
+    from madeleine_amd import functional as MF
+    E, w, ds, _, _, _, dE0, pool = case
+    Ei, esc = _image(lay, E.to(dev), 0)
+    Ef, fsc = _image(Lay("contig", dev), E.to(dev), 0) if fwd_contig else (Ei, esc)
+    Wa, ba, Wb, bb, wc, bc = [x.to(dev) for x in w]
+    sc, a, b = _nan(dev, T, H), _nan(dev, T, H, 512), _nan(dev, T, H, 512)
+    MF._call("mdl_abmil_gate_fwd_split", Ef, Ef.stride(0) * 4, fsc, Wa, ba, Wb, bb, wc, bc, sc, a, b, T, H, 0.0, 11, None, None,
+             _ws(dev, "mdl_abmil_gate_fwd_split_ws_bytes", T, H), _stream())
+    assert not (forward and fwd_contig)
+    out = dict(scores=sc, act_a=a.view(T, -1), act_b=b.view(T, -1)) if forward else {}
+    for name, acc, pterm, phases in SPLIT_VARIANTS:
+        dE = lay.out(T, H * 512, F32, k=1, init=dE0 if acc else None)
+        grads = [_nan(dev, *x.shape) for x in (Wa, Wb, ba, bb, wc, bc)]
+        ws = _ws(dev, "mdl_abmil_gate_bwd_split_ws_bytes", T, H)
+        q = pool[pterm] if pterm is not None else None
+        pt = [q["scores"].to(dev), q["m"].to(dev), q["l"].to(dev), q["dp"].to(dev), q["row_bag"].to(dev), 0] if q else [None] * 5 + [0]
+        for ph in phases:
+            MF._call("mdl_abmil_attnpool_bwd_split", Ei, Ei.stride(0) * 4, esc, Wa, Wb, wc, a, b, ds.to(dev), dE, dE.stride(0), acc,
+                     *grads, T, H, 0.0, 11, None, None, *pt, None, ws, _stream(), ph, 3)
+        out[name + ".dE"] = dE
+        for n, gten in zip(("dWa", "dWb", "dba", "dbb", "dwc", "dbc"), grads):
+            out[name + "." + n] = gten.view(gten.shape[0], -1)
+    return out
+
+
+def _check_gate_split(case, got, forward=True):
+    ref = case[5]
+    for name, acc, pterm, _ in SPLIT_VARIANTS:
+        res = [got["scores"] if forward else ref[0].float(), got[name + ".dE"]]
+        res += [got[name + "." + n].reshape(r.shape) for n, r in zip(GRAD_ORDER, ref[2:])]
+        _check_gate_fp32(res, [ref[0], _gate_ref_dE(case, acc, pterm)] + list(ref[2:]))
 
 
 # ============================================================================================================================ pooling
@@ -365,6 +392,12 @@ def _check_pool(got, pre, ref, dE0, ds0, bf16, acc):
 @pytest.mark.parametrize("H", [1, 4])
 def test_pool(dev, mode, H, lens, bf16):
     """mdl_abmil_pool_fwd / _bwd and mdl_abmil_wpool_fwd / _bwd (fp32 and bf16 E): dE and d_scores written, then accumulated."""
+    run, check = _pool_runner(dev, H, lens, bf16)
+    _strided_vs_contiguous(dev, mode, run, check)
+
+
+def _pool_runner(dev, H, lens, bf16):
+    """(run, check) of test_pool."""
     from madeleine_amd import functional as MF
     E, s, dp, dE0, ds0, cu, res = _pool_case(H, bf16, lens)
     T, n, C = sum(lens), len(lens), H * 512
@@ -395,7 +428,7 @@ def test_pool(dev, mode, H, lens, bf16):
             for acc in ((0,) if lin else (0, 1)):
                 g = {"pooled": got[pre + "pooled"], "dE": got["%sacc%d.dE" % (pre, acc)], "ds": got["%sacc%d.ds" % (pre, acc)]}
                 _check_pool(g, "", res[lin], dE0, ds0, bf16, acc)
-    _strided_vs_contiguous(dev, mode, run, check)
+    return run, check
 
 
 @functools.lru_cache(maxsize=None)
@@ -433,6 +466,12 @@ def _view_case(H, bf16):
 def test_pool_views(dev, mode, H, bf16):
     """mdl_abmil_pool_view_fwd / _bwd on a 129-index view of the dense bags, mdl_abmil_pool_rview_fwd / _bwd on both half-bag views of the
     ragged bags (an empty bag, a single-token bag whose first view is empty); the backward accumulates onto finite contents."""
+    run, check = _pool_views_runner(dev, H, bf16)
+    _strided_vs_contiguous(dev, mode, run, check)
+
+
+def _pool_views_runner(dev, H, bf16):
+    """(run, check) of test_pool_views."""
     from madeleine_amd import functional as MF
     cases = _view_case(H, bf16)
     dtype, sfx = (BF, "_bf16") if bf16 else (F32, "")
@@ -467,7 +506,7 @@ def test_pool_views(dev, mode, H, bf16):
             lens, _, _, ref = cases[ragged]
             _, _, _, dE0, ds0, _, _ = _pool_case(H, bf16, lens)
             _check_pool(got, pre, ref, dE0, ds0, bf16, 1)
-    _strided_vs_contiguous(dev, mode, run, check)
+    return run, check
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -475,6 +514,12 @@ def test_pool_views(dev, mode, H, bf16):
 @pytest.mark.parametrize("H", [1, 4])
 def test_pool_img(dev, mode, H, lens):
     """mdl_abmil_pool_fwd_img / mdl_abmil_pool_dscores_img on the split image of E at a wide e_rsb; d_scores written and accumulated."""
+    run, check = _pool_img_runner(dev, H, lens)
+    _strided_vs_contiguous(dev, mode, run, check)
+
+
+def _pool_img_runner(dev, H, lens):
+    """(run, check) of test_pool_img."""
     from madeleine_amd import functional as MF
     E, s, dp, _, ds0, cu, res = _pool_case(H, False, lens)
     T, n, C = sum(lens), len(lens), H * 512
@@ -500,7 +545,7 @@ def test_pool_img(dev, mode, H, lens):
         for acc in (0, 1):
             diff = got["ds%d" % acc].double() - (ds0.double() if acc else 0.0)
             assert float((diff - dsc).abs().max()) <= 1e-4 * float(dsc.abs().max()) + 1e-6, acc
-    _strided_vs_contiguous(dev, mode, run, check)
+    return run, check
 
 
 # ============================================================================================================================ Linears
@@ -511,7 +556,7 @@ def _lin_case(T, N, K, bf16):
     return x, W, b, dy, y64, _mm(dy, W), _tn(dy, x), dy.double().sum(0)
 
 
-def _run_linear(dev, lay, case, dtype, T, N, K, forward=True):
+def _run_linear(dev, lay, case, dtype, T, N, K, forward=True, backward=True):
     """mdl_linear_fwd(_bf16) with ldx, ldy and mdl_linear_bwd(_bf16) with ldx, ldy / lddy, lddx (three different pads), with dX and
     dbias and without either."""
     from madeleine_amd import functional as MF
@@ -524,7 +569,7 @@ def _run_linear(dev, lay, case, dtype, T, N, K, forward=True):
         MF._call("mdl_linear_fwd" + sfx, X, X.stride(0), Wd, bd, Y, Y.stride(0), T, N, K, _ws(dev, "mdl_linear_fwd%s_ws_bytes" % sfx, T, N, K),
                  _stream())
         out["Y"] = Y
-    for full in (True, False):
+    for full in ((True, False) if backward else ()):
         X, dY = lay.inp(x.to(dtype), 0), lay.inp(dy.to(dtype), 1)
         dX = lay.out(T, K, dtype, 2) if full else None
         dW, db = _nan(dev, N, K), (_nan(dev, N) if full else None)
@@ -548,15 +593,29 @@ def _run_linear(dev, lay, case, dtype, T, N, K, forward=True):
 def test_linear_fp32(dev, mode, T, N, K, want):
     _expect_plan("linear_fp32_bwd", T, N, K, want)
     case = _lin_case(T, N, K, False)
-    x, W, b, dy, y64, dx64, dw64, db64 = case
+    _strided_vs_contiguous(dev, mode, lambda lay: _run_linear(dev, lay, case, F32, T, N, K), lambda got: _check_linear_f32(case, got))
 
-    def check(got):
+
+def _check_linear_f32(case, got, forward=True, backward=True):
+    x, W, b, dy, y64, dx64, dw64, db64 = case
+    if forward:
         _chain_check(got["Y"], y64, _mm(x.abs(), W.abs().t()) + b.double().abs(), 1e-6, "Y")
+    if backward:
         _chain_check(got["dX"], dx64, _mm(dy.abs(), W.abs()), 1e-6, "dX")
         for k in ("dW", "dW_only"):
             _chain_check(got[k], dw64, _tn(dy.abs(), x.abs()), 1e-6, k)
         _chain_check(got["db"].view(-1), db64, dy.double().abs().sum(0), 1e-6, "dbias")
-    _strided_vs_contiguous(dev, mode, lambda lay: _run_linear(dev, lay, case, F32, T, N, K), check)
+
+
+def _check_linear_b16(case, got, forward=True, backward=True):
+    y64, dx64, dw64, db64 = case[4:]
+    if forward:
+        assert float((got["Y"].double() - y64).abs().max()) <= EPS_BF16 * float(y64.abs().max())
+        assert rel_err(got["Y"], y64) < EPS_BF16
+    if backward:
+        assert rel_err(got["dX"], dx64) < EPS_BF16
+        assert rel_err(got["dW"], dw64) < 1e-5 and rel_err(got["dW_only"], dw64) < 1e-5
+        assert rel_err(got["db"].view(-1), db64) < 1e-5
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -570,16 +629,7 @@ def test_linear_bf16(dev, mode, T, N, K, fwd, want_fwd, want_bwd):
     _expect_plan("linear_bf16_fwd", T, N, K, want_fwd)
     _expect_plan("linear_bf16_bwd", T, N, K, want_bwd)
     case = _lin_case(T, N, K, True)
-    y64, dx64, dw64, db64 = case[4:]
-
-    def check(got):
-        if fwd:
-            assert float((got["Y"].double() - y64).abs().max()) <= EPS_BF16 * float(y64.abs().max())
-            assert rel_err(got["Y"], y64) < EPS_BF16
-        assert rel_err(got["dX"], dx64) < EPS_BF16
-        assert rel_err(got["dW"], dw64) < 1e-5 and rel_err(got["dW_only"], dw64) < 1e-5
-        assert rel_err(got["db"].view(-1), db64) < 1e-5
-    _strided_vs_contiguous(dev, mode, lambda lay: _run_linear(dev, lay, case, BF, T, N, K, forward=fwd), check)
+    _strided_vs_contiguous(dev, mode, lambda lay: _run_linear(dev, lay, case, BF, T, N, K, forward=fwd), lambda got: _check_linear_b16(case, got, fwd))
 
 
 # ======================================================================================================================= split images
@@ -603,6 +653,12 @@ def _check_image(data, scale, x, K):
 def test_split_image(dev, mode, K):
     """mdl_split_image, mdl_split_image_rows (K <= 512 | K <= 1024 | above) and mdl_split_tile_absmax (with and without chunk_max) with a
     wide ldx and a wide rsb: image rows bit-equal to the contiguous build, nothing written past 4 K bytes of a row."""
+    run, check = _split_image_runner(dev, K)
+    _strided_vs_contiguous(dev, mode, run, check)
+
+
+def _split_image_runner(dev, K):
+    """(run, check) of test_split_image: X is stride argument 0, the image of mdl_split_image 1, that of mdl_split_image_rows 2."""
     from madeleine_amd import functional as MF
     rows, pad = 300, 32
     x = _u((rows, K), 9500 + K)
@@ -640,7 +696,7 @@ def test_split_image(dev, mode, K):
         want_cm = torch.stack([ax[i:i + 32].max() for i in range(0, rows, 32)])
         assert torch.equal(got["gate"].view(-1).double(), want_gate) and torch.equal(got["gate_alone"].view(-1).double(), want_gate)
         assert torch.equal(got["chunk_max"].view(-1).double(), want_cm)
-    _strided_vs_contiguous(dev, mode, run, check)
+    return run, check
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -648,9 +704,17 @@ def test_split_image(dev, mode, K):
 def test_split_gemm_nt(dev, mode, M, N, K):
     """mdl_split_gemm_nt on both of its kernels (N <= 128 with M > 256 takes the 512 x 128 tile) with wide a_rsb, b_rsb and ldc: with bias,
     with accumulate + row_gate (which keeps the 256 tile), with absmax_out; mdl_split_gemm_nt_group_bias."""
+    run, check = _split_nt_runner(dev, M, N, K)
+    _strided_vs_contiguous(dev, mode, run, check)
+
+
+def _split_nt_runner(dev, M, N, K, only_plain=False):
+    """(run, check) of test_split_gemm_nt: A is stride argument 0, B 1, C 2.  only_plain: the call with bias and absmax_out alone (the
+    other two keep the 256 tile, whose stride limits differ from those of the narrow-output tile)."""
     from madeleine_amd import functional as MF
     a, bw = _u((M, K), 9600 + M + N), _u((N, K), 9700 + N, K ** -0.5)
-    a[256:] = 0.0                                                                    # the second 256-row tile is all zero: its gate is 0
+    zhi = min(M, 512)
+    a[256:zhi] = 0.0                                                                 # the second 256-row tile is all zero: its gate is 0
     bias, c0 = _u((N,), 9800, 0.1), _u((M, N), 9900)
     gb, rg = _u((3, N), 9950, 0.1), (torch.arange(M) % 3).to(torch.int32)
     p64, mag = _mm(a, bw.t()), _mm(a.abs(), bw.abs().t())
@@ -662,34 +726,45 @@ def test_split_gemm_nt(dev, mode, M, N, K):
         out = {}
         C1, amax = lay.out(M, N, F32, 2), torch.zeros(1, device=dev)
         MF._call("mdl_split_gemm_nt", *geo, C1, C1.stride(0), M, N, K, bias.to(dev), 0, amax, None, None, None, 3, _stream())
+        assert len({A.stride(0) - K, B.stride(0) - K, C1.stride(0) - N}) == (3 if lay.mode != "contig" else 1)
+        out.update(bias=C1, absmax=amax.view(1, 1))
+        if only_plain:
+            return out
         gate = _nan(dev, (M + 255) // 256)
         MF._call("mdl_split_tile_absmax", a.to(dev), K, M, K, gate, None, _stream())
         C2 = lay.out(M, N, F32, 2, init=c0)
         MF._call("mdl_split_gemm_nt", *geo, C2, C2.stride(0), M, N, K, None, 1, None, gate, None, None, 3, _stream())
         C3 = lay.out(M, N, F32, 2)
         MF._call("mdl_split_gemm_nt_group_bias", *geo, C3, C3.stride(0), M, N, K, bias.to(dev), None, None, gb.to(dev), rg.to(dev), 3, _stream())
-        assert len({A.stride(0) - K, B.stride(0) - K, C1.stride(0) - N}) == (3 if lay.mode != "contig" else 1)
-        out.update(bias=C1, absmax=amax.view(1, 1), acc_gate=C2, group=C3)
+        out.update(acc_gate=C2, group=C3)
         return out
 
     def check(got):
         want = p64 + bias.double()
         _chain_check(got["bias"], want, mag + bias.double().abs(), 4e-7, "bias")
         assert abs(float(got["absmax"]) - float(want.abs().max())) <= 1e-6 * float(want.abs().max())
+        if only_plain:
+            return
         _chain_check(got["acc_gate"], p64 + c0.double(), mag + c0.double().abs(), 4e-7, "accumulate + row_gate")
-        assert torch.equal(got["acc_gate"][256:], c0[256:])                          # the gated tile is skipped: contents untouched
+        assert torch.equal(got["acc_gate"][256:zhi], c0[256:zhi])                    # the gated tile is skipped: contents untouched
         wg = want + gb.double()[rg.long()]
         _chain_check(got["group"], wg, mag + bias.double().abs() + gb.double().abs()[rg.long()], 4e-7, "group_bias")
-    _strided_vs_contiguous(dev, mode, run, check)
+    return run, check
 
 
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("T,want", [pytest.param(33, dict(splits=1, tps=64), id="T33"), pytest.param(4097, dict(splits=2), id="T4097_S2")])
 def test_split_gemm_tn(dev, mode, T, want):
     """mdl_split_gemm_tn (the dW product) with wide a_rsb and b_rsb; B carries its 32 zero pad rows inside the strided buffer."""
+    _expect_plan("split_tn", T, 256, 128, want)
+    run, check = _split_tn_runner(dev, T)
+    _strided_vs_contiguous(dev, mode, run, check)
+
+
+def _split_tn_runner(dev, T):
+    """(run, check) of test_split_gemm_tn: A is stride argument 0, B 1."""
     from madeleine_amd import functional as MF
     Mi, N = 256, 128
-    _expect_plan("split_tn", T, Mi, N, want)
     x, dy = _u((T, Mi), 9960 + T), _u((T, N), 9970 + T, 0.5)
 
     def run(lay):
@@ -700,4 +775,4 @@ def test_split_gemm_tn(dev, mode, T, want):
         MF._call("mdl_split_gemm_tn", A, A.stride(0) * 4, asc, Mi, B, B.stride(0) * 4, bsc, N, out, T, None,
                  _ws(dev, "mdl_split_gemm_tn_ws_bytes", T, Mi, N), 3, _stream())
         return dict(dW=out)
-    _strided_vs_contiguous(dev, mode, run, lambda got: _chain_check(got["dW"], _tn(dy, x), _tn(dy.abs(), x.abs()), 4e-7, "dW"))
+    return run, lambda got: _chain_check(got["dW"], _tn(dy, x), _tn(dy.abs(), x.abs()), 4e-7, "dW")

@@ -72,7 +72,10 @@ def test_optimality(name):
     """Every legal problem converges, and the fp64 gradient of the primal objective at the returned W is within max(2 gtol g0, 2 r32):
     the stop rule plus the kernel's own fp32 evaluation error, or twice what the reference iteration reaches in fp32.
     Measured on the MI355X: 2-7 Newton steps and 7-217 CG steps per problem; worst fp64 gradient / g0 4.6e-5 (A), 3.8e-6 (B), 8.3e-5 (L)."""
-    co, out = _cohort_run(name)
+    _optimality(name, *_cohort_run(name))
+
+
+def _optimality(name, co, out):
     X32 = co["X"].float()
     worst = 0.0
     for p, pr in enumerate(co["problems"]):
@@ -93,7 +96,10 @@ def test_decision_values(name):
     training row) the decision values are exactly 0.  The threshold is numpy's median of the training rows' scores as mdl_probe_scores
     gives them, bit for bit: the fit kernel forms its decision values by the same fmaf chain and wave sum.
     Worst E_p measured on the MI355X: A 4.6e-5, B 1.0e-5, L 7.2e-5."""
-    co, out = _cohort_run(name)
+    _decision_values(name, *_cohort_run(name))
+
+
+def _decision_values(name, co, out):
     worst = 0.0
     for p, pr in enumerate(co["problems"]):
         z, z64 = out["z"][p].double(), pr["z64"]
@@ -112,7 +118,10 @@ def test_decision_values(name):
 def test_metrics_equal_the_host_recount(name):
     """c_index, chi2 and all six counts from the device's own z and thr equal the host's recount from the same numbers: the integers bit
     for bit, the two doubles to 1e-12 relative."""
-    co, out = _cohort_run(name)
+    _metrics_equal_the_host_recount(name, *_cohort_run(name))
+
+
+def _metrics_equal_the_host_recount(name, co, out):
     tm, ev = co["time"].numpy(), co["event"].numpy()
     for p, pr in enumerate(co["problems"]):
         test = R.test_mask(ev, pr["idx"].numpy())
@@ -129,7 +138,10 @@ def test_metrics_against_fp64_optimum(name):
     fp64 score gap is below 2 D (never more than 4 % of the comparable pairs), and the risk group differs only for test cases within 2 D
     of the fp64 threshold, the median of z64 over the training rows.  The same D everywhere: the kernel's threshold is the median of the
     device's own z (test_decision_values), so it lies within D of the fp64 one."""
-    co, out = _cohort_run(name)
+    _metrics_against_fp64_optimum(name, *_cohort_run(name))
+
+
+def _metrics_against_fp64_optimum(name, co, out):
     tm, ev = co["time"].numpy(), co["event"].numpy()
     for p, pr in enumerate(co["problems"]):
         test = R.test_mask(ev, pr["idx"].numpy())
