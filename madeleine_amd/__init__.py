@@ -13,9 +13,10 @@ madeleine.utils.loss, madeleine.utils.trainer):
     from madeleine_amd import cross_stain_retrieval  # at which rank a case's own IHC slide comes back for its H&E slide, and the reverse
     from madeleine_amd import survival_probe     # do the embeddings stratify patients: cross-validated Cox fits, C-index, log-rank
     from madeleine_amd import heatmap            # attention heatmaps on the device: render, gaussian_taps, colormap, save_png
+    from madeleine_amd import linear_probe_ci    # bootstrap intervals of the probes' metrics and paired differences between encoders
 
 The numeric work runs in csrc/libmadeleine_amd.so through the C ABI of include/madeleine_amd.h (the heatmap renderer: of
-include/madeleine_amd_view.h).
+include/madeleine_amd_view.h; the bootstrap counts: of include/madeleine_amd_stats.h).
 Importing this package does not load the library (so model construction / state_dict handling works on
 any box); the first forward does, and raises if it is unavailable -- there is no fallback path.
 """
@@ -34,10 +35,11 @@ __all__ = ["MADELEINE", "ABMILEmbedder", "BatchedABMIL", "create_model", "InfoNC
            "load_checkpoint", "create_model_from_pretrained", "AdamW", "DeviceSlideStore", "PackedBags", "probe_splits", "fit_logistic",
            "linear_probe", "device_smooth_rank", "cross_stain_retrieval", "retrieval_metrics", "slide_neighbours",
            "survival_splits", "fit_cox", "survival_probe", "cv_splits", "linear_probe_cv", "heatmap", "render_heatmaps", "gaussian_taps",
-           "colormap", "save_png"]
+           "colormap", "save_png", "bootstrap_summary", "paired_difference", "linear_probe_ci", "survival_probe_ci"]
 __version__ = "0.2"
 _HEATMAP = ("render_heatmaps", "gaussian_taps", "colormap", "save_png")
 _PROBE = ("probe_splits", "fit_logistic", "linear_probe", "cv_splits", "linear_probe_cv")
+_RESAMPLE = ("bootstrap_summary", "paired_difference", "linear_probe_ci", "survival_probe_ci")
 
 
 def __getattr__(name):
@@ -45,6 +47,9 @@ def __getattr__(name):
     if name in _PROBE:
         from . import probe
         return getattr(probe, name)
+    if name in _RESAMPLE:      # imports the probe (above) and binds the third header's #defines: resolved on first use as well
+        from . import resample
+        return getattr(resample, name)
     if name == "heatmap" or name in _HEATMAP:      # the renderer binds the library's #defines: resolved on first use as well
         import importlib
         mod = importlib.import_module(".heatmap", __name__)

@@ -1,4 +1,5 @@
-"""ctypes binding of libmadeleine_amd.so (the C ABI of include/madeleine_amd.h and include/madeleine_amd_view.h).
+"""ctypes binding of libmadeleine_amd.so (the C ABI of include/madeleine_amd.h, include/madeleine_amd_view.h and
+include/madeleine_amd_stats.h).
 
 Single backend: there is no CPU / eager fallback.  `lib()` raises if the shared object cannot be
 loaded (it is built in-tree by `python -m madeleine_amd._build` / __graft_entry__.build(); if it is
@@ -75,6 +76,11 @@ with open(_build.VIEW_HEADER) as _f:
     VIEW_SIGNATURES, VIEW_DEFINES = _parse_header(_f.read())
 if set(VIEW_SIGNATURES) & set(SIGNATURES) or set(VIEW_DEFINES) & set(_DEFINES):
     raise ImportError("madeleine_amd: %s repeats a name of %s" % (_build.VIEW_HEADER, _build.HEADER))
+# the third header (include/madeleine_amd_stats.h: the bootstrap entry points), the same way: a table of its own, no name of the other two
+with open(_build.STATS_HEADER) as _f:
+    STATS_SIGNATURES, STATS_DEFINES = _parse_header(_f.read())
+if (set(STATS_SIGNATURES) & (set(SIGNATURES) | set(VIEW_SIGNATURES))) or (set(STATS_DEFINES) & (set(_DEFINES) | set(VIEW_DEFINES))):
+    raise ImportError("madeleine_amd: %s repeats a name of %s or %s" % (_build.STATS_HEADER, _build.HEADER, _build.VIEW_HEADER))
 
 
 def lib_path() -> str:
@@ -117,7 +123,7 @@ def lib():
         if abi() != ABI_VERSION:
             raise RuntimeError("madeleine_amd: %s implements ABI revision %d, this binding expects %d; rebuild it "
                                "(`python -m madeleine_amd._build --force`)" % (path, abi(), ABI_VERSION))
-        for name, (res, args) in list(SIGNATURES.items()) + list(VIEW_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(STATS_SIGNATURES.items()):
             try:
                 fn = getattr(handle, name)
             except AttributeError:

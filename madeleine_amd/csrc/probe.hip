@@ -21,6 +21,7 @@
 // MDL_LOGIT_MAX_TRAIN columns; the fits of that width are in probe_primal.hip.
 // No workgroup waits on another; every loop has a bound that is an argument or a constant of the header.
 #include "common.hpp"
+#include "probe_score.hpp"
 
 namespace mdl {
 namespace {
@@ -484,10 +485,7 @@ __global__ __launch_bounds__(PB_THREADS) void probe_prepare_kernel(const float* 
     const int32_t* yp = y + (int64_t)p * ldy;
     if (tid < PB_CMAX) m.cnt[(int64_t)p * PB_CMAX + tid] = 0ull;
     if (tid < PB_CMAX * PB_CMAX) s_conf[tid] = 0;
-    for (int s = tid; s < S; s += PB_THREADS) {
-        const int l = yp[s];
-        tcls[s] = (l >= 0 && l < C) ? (int8_t)l : (int8_t)-1;
-    }
+    for (int s = tid; s < S; s += PB_THREADS) tcls[s] = probe_test_class(yp[s], C);
     __syncthreads();
     int n = n_train[p];
     n = n < 0 ? 0 : (n > n_max ? n_max : n);
@@ -499,23 +497,7 @@ __global__ __launch_bounds__(PB_THREADS) void probe_prepare_kernel(const float* 
     for (int s = tid; s < S; s += PB_THREADS) {
         const int t = tcls[s];
         if (t < 0) continue;
-        const float* zs = z + ((int64_t)p * S + s) * cols;
-        int pred;
-        if (cols == 1) {
-            pred = zs[0] > 0.f ? 1 : 0;
-        } else {
-            pred = 0;
-            float best = zs[0];
-            for (int c = 1; c < cols; ++c)
-                if (zs[c] > best) {                 // strictly greater: the lowest index wins a tie
-                    best = zs[c];
-                    pred = c;
-                }
-            double sum = 0.0;
-            for (int c = 0; c < cols; ++c) sum += exp((double)zs[c] - (double)best);
-            const double lse = (double)best + log(sum);
-            for (int c = 0; c < cols; ++c) m.score[((int64_t)p * C + c) * S + s] = (double)zs[c] - lse;
-        }
+        const int pred = probe_predict(z + ((int64_t)p * S + s) * cols, cols, m.score + (int64_t)p * C * S + s, S);
         atomicAdd(&s_conf[t * C + pred], 1);
     }
     __syncthreads();

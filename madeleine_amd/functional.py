@@ -2360,3 +2360,93 @@ def retrieval(Q, K=None, k=0, metric='cosine', paired=True, exclude_diag=False, 
         _call("mdl_retrieval", Q, ldq, K, ldk, n, m, d, RETR_METRICS[metric], int(paired), int(exclude_diag), k, col_chunks, greater, equal,
               pair_sim, ti, tv, ws, _stream(), unsupported=refusal)
     return Retrieval(greater, equal, pair_sim, ti, tv)
+
+
+# ---- B1-B3: the test-set bootstrap of the probes' metrics (include/madeleine_amd_stats.h).  Exact integer counts, no autograd ----
+BOOT_REP_BLOCK = _native.STATS_DEFINES["MDL_BOOT_REP_BLOCK"]
+BOOT_SURV_MAX_TEST = _native.STATS_DEFINES["MDL_BOOT_SURV_MAX_TEST"]
+BOOT_LDS_RAISE_FROM = _native.STATS_DEFINES["MDL_BOOT_LDS_RAISE_FROM"]
+_BOOT_LIMITS = ("bootstrap counts support at most %d cases (survival: %d), %d training cases per problem (survival: %d), 2..%d classes "
+                "and replicates within int32 (got n_max %d, C %d, S %d, R %d)")
+
+
+def _boot_refusal(n_max, C, S, R):
+    d = _native._DEFINES
+    return (_BOOT_LIMITS, d["MDL_PROBE_MAX_CASES"], BOOT_SURV_MAX_TEST, d["MDL_LOGIT_MAX_TRAIN"], d["MDL_COX_MAX_TRAIN"],
+            d["MDL_PROBE_MAX_CLASSES"], n_max, C, S, R)
+
+
+def _boot_group(group, n, what):
+    _require(group, "group", torch.int32)
+    if group.shape != (n,):
+        raise RuntimeError("madeleine_amd: group must be int32 [%d], one entry per %s (got %s)" % (n, what, tuple(group.shape)))
+    return group
+
+
+def _boot_replicates(replicates):
+    R = int(replicates)
+    if R < 0:
+        raise RuntimeError("madeleine_amd: the bootstrap needs replicates >= 0 (got %d)" % R)
+    return R
+
+
+def boot_weights(seed, group, replicates, n_cases):
+    """w [G, R + 1, S] uint16: the resampling weights of the groups group [G] (int32, on the device) -- w[g, r] is the count vector of S
+    draws from [0, S), a function of (seed, group[g], r, S) alone, and w[g, 0] is all ones (B1 of include/madeleine_amd_stats.h).
+    One launch on the current stream, no host read."""
+    R, S = _boot_replicates(replicates), int(n_cases)
+    if group.dim() != 1 or group.numel() < 1 or S < 1:
+        raise RuntimeError("madeleine_amd: boot_weights needs group [G], G >= 1, and n_cases >= 1")
+    G = _boot_group(group, group.numel(), "group").numel()
+    w = torch.empty(G, R + 1, S, device=group.device, dtype=torch.uint16)
+    with _timed("boot_weights"):
+        _call("mdl_boot_weights", int(seed) & 0xFFFFFFFFFFFFFFFF, group, G, R, S, w, _stream(), unsupported=_boot_refusal(0, 2, S, R))
+    return w
+
+
+def boot_class_counts(z, y, train_idx, n_train, n_classes, group, seed, replicates):
+    """(confusion [P, R + 1, C, C] int32, auc_num [P, R + 1, cols] int64) of every problem of probe_metrics / logit_metrics under R
+    resamples of the cohort (B2): per replicate the weighted confusion matrix of the test cases and, per class column (class 1 for two
+    classes), the weighted Mann-Whitney numerator sum w_i w_j (2 [s_i > s_j] + [s_i == s_j]).  Problem p uses the weights of
+    (seed, group[p], r, S): problems of one group are resampled together.  Replicate 0 is the sample itself.  A problem with a NaN test
+    score has auc_num -1.  Three launches on the current stream, no host read."""
+    _require(z, "z")
+    C = int(n_classes)
+    cols = 1 if C == 2 else C
+    if z.dim() != 3 or z.shape[0] < 1 or z.shape[1] < 1 or z.shape[2] != cols:
+        raise RuntimeError("madeleine_amd: z must be [P, S, %d]" % cols)
+    S = z.shape[1]
+    P, n_max, ldy = _probe_problems(y, train_idx, n_train, S)
+    if P != z.shape[0]:
+        raise RuntimeError("madeleine_amd: z holds %d problems, train_idx %d" % (z.shape[0], P))
+    _boot_group(group, P, "problem")
+    R = _boot_replicates(replicates)
+    refusal = _boot_refusal(n_max, C, S, R)
+    ws = _ws_for("mdl_boot_class_ws_bytes", z.device, P, S, C, refusal=refusal)
+    confusion = torch.empty(P, R + 1, C, C, device=z.device, dtype=torch.int32)
+    auc_num = torch.empty(P, R + 1, cols, device=z.device, dtype=torch.int64)
+    with _timed("boot_class_counts"):
+        _call("mdl_boot_class_counts", z, y, ldy, train_idx, n_train, P, n_max, S, C, group, int(seed) & 0xFFFFFFFFFFFFFFFF, R, confusion,
+              auc_num, ws, _stream(), unsupported=refusal)
+    return confusion, auc_num
+
+
+def boot_surv_counts(z, time, event, train_idx, n_train, group, seed, replicates):
+    """counts [P, R + 1, 2] int64 of every problem of survival_metrics under R resamples of the cohort (B3): the weighted concordance
+    numerator and the weighted number of comparable pairs, so that the C-index of a replicate is counts[..., 0] / (2 counts[..., 1]).
+    Replicate 0 equals the first two columns of survival_metrics' counts.  z [P, S]; S <= BOOT_SURV_MAX_TEST.  One launch on the
+    current stream, no host read."""
+    _require(z, "z")
+    if z.dim() != 2 or z.shape[0] < 1 or z.shape[1] < 1:
+        raise RuntimeError("madeleine_amd: z must be [P, S]")
+    S = z.shape[1]
+    P, n_max, ldt, lde = _surv_problems(time, event, train_idx, n_train, S)
+    if P != z.shape[0]:
+        raise RuntimeError("madeleine_amd: z holds %d problems, train_idx %d" % (z.shape[0], P))
+    _boot_group(group, P, "problem")
+    R = _boot_replicates(replicates)
+    counts = torch.empty(P, R + 1, 2, device=z.device, dtype=torch.int64)
+    with _timed("boot_surv_counts"):
+        _call("mdl_boot_surv_counts", z, time, ldt, event, lde, train_idx, n_train, P, n_max, S, group, int(seed) & 0xFFFFFFFFFFFFFFFF, R,
+              counts, _stream(), unsupported=_boot_refusal(n_max, 2, S, R))
+    return counts

@@ -220,11 +220,8 @@ def linear_probe_cv(embeds, labels, folds=5, repeats=1, cost=1.0, seed_base=0, k
     return out
 
 
-def _main(argv=None):
+def _parser():
     import argparse
-    import csv
-    import os
-    import pickle
     ap = argparse.ArgumentParser(description="few-shot linear probing of slide embeddings (the reference's bin/run_linear_probing.py)")
     ap.add_argument("--slide_embedding_pkl", required=True)
     ap.add_argument("--label_path", required=True)
@@ -232,7 +229,49 @@ def _main(argv=None):
     ap.add_argument("--cv_folds", type=int, default=0, help="train on all labels, cross-validated in this many stratified folds, "
                                                             "instead of the few-shot protocol")
     ap.add_argument("--cv_repeats", type=int, default=1)
+    ap.add_argument("--bootstrap", type=int, default=0, metavar="R",
+                    help="also resample the cohort R times: one more line per task with the percentile interval of the metric")
+    ap.add_argument("--versus", default=None, metavar="OTHER.pkl",
+                    help="with --bootstrap: a second embedding pickle over the same slides; the lines add the paired difference and its p")
+    ap.add_argument("--level", type=float, default=0.95, help="with --bootstrap: the level of the intervals")
+    ap.add_argument("--seed", type=int, default=0, help="with --bootstrap: the seed of the resamples")
+    return ap
+
+
+def _parse(argv=None):
+    ap = _parser()
     args = ap.parse_args(argv)
+    if args.bootstrap < 0 or not 0.0 < args.level < 1.0:
+        ap.error("--bootstrap needs R >= 0 and --level a value inside (0, 1)")
+    if not args.bootstrap and (args.versus is not None or args.level != 0.95 or args.seed != 0):
+        ap.error("--versus, --level and --seed belong to --bootstrap R")
+    return args
+
+
+def _bootstrap_lines(results, unit_name, level):
+    """One line per (task, k or cv repeat) of a linear_probe_ci result: the interval of the task's metric and, with a second arm, the
+    paired difference and its p-value."""
+    lines = []
+    for (task, unit), res in results.items():
+        metric = "q_kappa" if task == "isup_grade" else "auc"
+        arms = list(res["arms"])
+        a = res["arms"][arms[0]][metric]
+        line = "{}={}, task={}, bootstrap {} {:g}% interval=[{}, {}] (point {}, {} valid replicates)".format(
+            unit_name, unit, task, "quadratic kappa" if metric == "q_kappa" else "auc", 100 * level, round(a["lo"], 3), round(a["hi"], 3),
+            round(a["point"], 3), a["n_valid"])
+        if len(arms) > 1:
+            d = res["pairs"][(arms[0], arms[1])][metric]
+            line += ", difference to {}={} [{}, {}], p={}".format(arms[1], round(d["diff"], 3), round(d["lo"], 3), round(d["hi"], 3),
+                                                                   round(d["p"], 4))
+        lines.append(line)
+    return lines
+
+
+def _main(argv=None):
+    import csv
+    import os
+    import pickle
+    args = _parse(argv)
     with open(args.slide_embedding_pkl, "rb") as f:
         obj = pickle.load(f)
     with open(args.label_path, newline="") as f:
@@ -240,6 +279,20 @@ def _main(argv=None):
     keep = [i for i, s in enumerate(obj["slide_ids"]) if str(s) in rows]      # the reference's intersection of labels and embeddings
     embeds = np.asarray(obj["embeds"], dtype=np.float32)[keep]
     labels = {t: np.array([int(float(rows[str(obj["slide_ids"][i])][t])) for i in keep]) for t in args.tasks}
+    if args.bootstrap:                              # printed after the usual lines; the pickles below hold what they always held
+        from .resample import linear_probe_ci
+        arms = {"embeds": embeds}
+        if args.versus is not None:
+            with open(args.versus, "rb") as f:
+                other = pickle.load(f)
+            where = {str(s): i for i, s in enumerate(other["slide_ids"])}
+            missing = [str(obj["slide_ids"][i]) for i in keep if str(obj["slide_ids"][i]) not in where]
+            if missing:
+                raise SystemExit("--versus: %d slides of %s are absent from %s (first: %s)" % (
+                    len(missing), args.slide_embedding_pkl, args.versus, missing[0]))
+            arms[os.path.splitext(os.path.basename(args.versus))[0]] = np.asarray(other["embeds"], dtype=np.float32)[
+                [where[str(obj["slide_ids"][i])] for i in keep]]
+        ci = dict(replicates=args.bootstrap, level=args.level, seed=args.seed, kappa="isup_grade" in args.tasks)
     if args.cv_folds:
         results = linear_probe_cv(embeds, labels, folds=args.cv_folds, repeats=args.cv_repeats, kappa="isup_grade" in args.tasks)
         for task in args.tasks:                     # mean +/- std over every fold of every repeat
@@ -247,6 +300,9 @@ def _main(argv=None):
             v = np.concatenate([results[(task, r)][metric] for r in range(args.cv_repeats)])
             print("cv_folds={}, task={}, {}={} +/- {}".format(args.cv_folds, task, "quadratic kappa" if metric == "q_kappa" else "auc",
                                                               round(float(v.mean()), 3), round(float(v.std()), 3)))
+        if args.bootstrap:
+            print("\n".join(_bootstrap_lines(linear_probe_ci(arms, labels, protocol="cv", folds=args.cv_folds, repeats=args.cv_repeats, **ci),
+                                             "cv_repeat", args.level)))
         return
     results = linear_probe(embeds, labels, kappa="isup_grade" in args.tasks)
     name = os.path.splitext(os.path.basename(args.slide_embedding_pkl))[0]
@@ -260,6 +316,8 @@ def _main(argv=None):
         store = {m: res[m].tolist() for m in ("auc", "bacc", "q_kappa") if m in res}
         with open(os.path.join(save, "k=%d_probing_%s.pickle" % (k, task.replace("/", ""))), "wb") as f:
             pickle.dump({"tangle": store}, f, protocol=pickle.HIGHEST_PROTOCOL)
+    if args.bootstrap:
+        print("\n".join(_bootstrap_lines(linear_probe_ci(arms, labels, **ci), "k", args.level)))
 
 
 if __name__ == "__main__":
