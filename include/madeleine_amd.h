@@ -336,12 +336,26 @@ int mdl_linear_bwd(const float* X, int64_t ldx, const float* W, const float* dY,
  * must receive the forward's workspace untouched.
  * ABI 23: for 128 < n <= 256 and 2 * (cases of the launch) <= compute units of the device, every IPOT sweep runs as TWO workgroups per
  * case and branch (row halves) that exchange their column sums once per iteration through 8-byte {value, tag} granules in the workspace
- * (device-scope stores / polls; csrc/got_impl.inc, Xch); MADELEINE_GOT_NOSPLIT=1 keeps the one-workgroup sweeps.  Same results up to the
+ * (device-scope stores / polls; csrc/got_resident.hip, Xch); MADELEINE_GOT_NOSPLIT=1 keeps the one-workgroup sweeps.  Same results up to the
  * association of the column sums; bit-reproducible.  The workspace's global region ends with four floats {pass generation (uint32 bits),
  * exchange time-out flag (0 = none; non-zero voids the pass), 0, 0}, followed by the 64 bytes of padding mdl_got_ws_bytes adds.
  * A voided pass says so in its results: out[0..1] of the forward and dV / dQ of the backward are NaN when the flag is up (a sweep waited
  * ~1 s for a partner workgroup that never became resident -- the device was shared with work the launch did not know about, e.g. a
  * second training process; run those with MADELEINE_GOT_NOSPLIT=1).  The flag is cleared by the extrema kernel of every forward.
+ *
+ * Return codes of every launching mdl_got_* function below (the four families: mdl_got_*, mdl_got_*_multi, mdl_got_tiled_*,
+ * mdl_got_tiled_rect_*), in one order, each step over all problems of a call before the next step:
+ *   1. MDL_E_ARG: np outside [1, MDL_GOT_MAX_BATCH] or a NULL array of a _multi form; k, n or m < 0, d < 1; an empty problem (k or n = 0)
+ *      of a _multi form.
+ *   2. MDL_E_UNSUPPORTED: a size beyond the class (n <= 512, d <= 128; a _multi problem n <= 256; tiled n, m, d <= 4096).
+ *   3. MDL_E_ARG: ws NULL; out (_fwd), minmax_out (_extrema), d_out (_bwd_begin, _bwd) NULL; _extrema of an empty problem; V, Q (_fwd,
+ *      _extrema, _bwd_finish, _bwd) or dV, dQ (_bwd_finish, _bwd) NULL while the tensor has elements -- a tensor of k n d = 0 elements
+ *      (Q, dQ: k m d = 0) may be NULL.
+ *   4. MDL_E_ALIGN: ws is not 16-byte aligned.
+ *   5. An empty problem (k, n or m = 0) is MDL_OK and launches nothing: out = (0, 0), d_minmax = 0 where it is given, dV and dQ cleared
+ *      where they have elements.
+ * The combined _bwd functions are refused on a fault of either stage before the first stage is launched.  The *_ws_bytes queries answer
+ * steps 1 and 2 for their sizes.
  */
 int64_t mdl_got_ws_bytes(int k, int n, int d);
 int mdl_got_fwd(const float* V, const float* Q, float* out, float* minmax_out, const float* minmax_in,
@@ -378,8 +392,8 @@ int mdl_got_bwd_begin_multi(int np, const float* const* d_out, float* const* d_m
 int mdl_got_bwd_finish_multi(int np, const float* const* V, const float* const* Q, float* const* dV, float* const* dQ,
                              const float* const* d_minmax_total, const int* k, const int* n, int d, void* const* ws, void* stream);
 
-/* Tiled class of GOT: the same arguments, return codes, semantics and workspace contract as the six mdl_got_* entry points above, for
- * 1 <= n <= 4096 and 1 <= d <= 4096 at any k (MDL_E_UNSUPPORTED beyond; n = 0 or k = 0 gives zero outputs and gradients).  The shapes
+/* Tiled class of GOT: the same arguments, return codes (the order above), semantics and workspace contract as the six mdl_got_* entry
+ * points above, for 1 <= n <= 4096 and 1 <= d <= 4096 at any k.  The shapes
  * of the resident classes are included, so the two can be compared.  Many workgroups share one case and meet only at kernel
  * boundaries (csrc/got_tiled.hip): the IPOT sweeps run as panels of 16 rows per workgroup with the column sums of an iteration merged
  * by the next launch (two launches per iteration), the products on 128 x 128 matrix-core tiles.  Deterministic (fixed-order merges, no

@@ -1,6 +1,6 @@
 // got_batch.hpp -- up to GOT_MAXP independent GOT problems (one per stain: loss.py:278-302 is called once per stain, trainer.py:40-49)
 // in ONE launch sequence.  Every GOT kernel takes a GotBatch by value; a workgroup finds its problem from blockIdx (got_pick in
-// got_impl.inc).  Round 4: the four stains of a data-parallel rank used to run as four chains on four HIP streams -- a process has four
+// got_resident.hip).  Round 4: the four stains of a data-parallel rank used to run as four chains on four HIP streams -- a process has four
 // hardware queues, and the first stream that is not ours (a prefetcher's, RCCL's) made two chains share one.  One stream,
 // every launch covering all problems, needs no queue at all beyond the caller's.
 #pragma once

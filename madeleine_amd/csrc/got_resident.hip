@@ -1,4 +1,5 @@
-// got.hip -- G0-G3: Graph Optimal Transport token alignment (forward + hand-written reverse sweep).
+// got_resident.hip -- G0-G3: Graph Optimal Transport token alignment (forward + hand-written reverse sweep), the RESIDENT size class:
+// its kernels, its launch sequences and its row of the engine table (got_host.hpp).  The C ABI is in got.hip.
 //
 // Replaces, for k cases with n sub-sampled tokens each (n <= 512, d <= 128; the reference's one call site passes subsample=256):
 //   GOT                                (reference madeleine/utils/loss.py:278-302)
@@ -12,8 +13,8 @@
 // detaches only the RETURNED gamma).  The backward here replays the iterations in reverse from the stored
 // per-iteration plans T_t and scaling vectors (delta_t, sigma_t) -- the same tensors autograd's tape holds.
 //
-// Organisation: one GOT_THREADS-thread workgroup (NW = GOT_THREADS / 64 waves; 1024 threads in the shipped build) per
-// case and branch; the Wasserstein and the Gromov-Wasserstein branch of a case are independent and run as separate
+// Organisation: one 1024-thread workgroup (NW = 16 waves x 128 VGPRs: enough waves to hide the L2 latency of the per-iteration
+// matrix passes; a 512-thread build with 256 VGPRs per wave measured slower at every n, see launch_fwd_sweep) per case and branch; the Wasserstein and the Gromov-Wasserstein branch of a case are independent and run as separate
 // workgroups of the same launch.  For n <= 128 a branch's whole chain is one kernel; for n > 128 it is one launch per
 // phase (thresholds | C_gamma | IPOT sweep | ...), so the register allocation of the sweeps is not shared with the
 // matrix products' accumulators.  Round 6: the IPOT sweeps of those per-phase classes run as TWO workgroups per case and
@@ -26,17 +27,12 @@
 //     (v_mfma_f32_32x32x2_f32): K-chunks of 16 staged through LDS, each wave owns a 64x64 output panel.
 // Cs and Ct are bitwise symmetric here (the same accumulation chain computes <x_i,x_j> and <x_j,x_i>), so the
 // reference's transposes (:233, :240-247) are identities.
-#include "common.hpp"
-#include "got_batch.hpp"
-
-#ifndef GOT_THREADS
-#error "got_impl.inc is compiled through got_t1024.hip, which defines GOT_THREADS and GOT_NS"
-#endif
+#include "got_host.hpp"
 
 namespace mdl {
-namespace GOT_NS {
+namespace got1024 {   // (the workgroup size; the kernel symbols carry it, and the profiles key on them)
 
-constexpr int GOT_MAXN = 256;           // register / one-panel classes (the hot path: trainer.py:44 sub-samples to <= 256 tokens)
+constexpr int GOT_REGN = 256;           // register / one-panel classes (the hot path: trainer.py:44 sub-samples to <= 256 tokens)
 constexpr int GOT_BIGN = 512;           // "big" class (256 < n <= 512): plans and plan gradients in the workspace, blocked matrix products
 constexpr int GOT_MAXD = 128;
 constexpr int WD_ITERS = 30;
@@ -46,9 +42,8 @@ constexpr float WD_INV_BETA = 2.0f;    // beta 0.5 (loss.py:179 default, GOT pas
 constexpr float GW_INV_BETA = 10.0f;   // lamda = 1e-1 (loss.py:269)
 constexpr float THR_BETA = 0.1f;       // loss.py:288, :226
 
-constexpr int GNT = GOT_THREADS;       // threads per workgroup (1024 = 16 waves x 128 VGPRs in the shipped build, see got.hip)
-constexpr int GNW = GNT / 64;
-constexpr int MM_NV = GNW == 16 ? 2 : 4;   // 32-column blocks per wave in the matrix product
+constexpr int GNT = 1024;              // threads per workgroup
+constexpr int GNW = GNT / 64;          // 16 waves
 constexpr int MM_KC = 16;              // K-chunk of the in-block matrix product
 constexpr int MM_LDK = 288;            // k-major LDS tile [kk][256]: +32 floats so the two half-waves (k, k+1) hit disjoint banks
 constexpr int MM_LDI = 17;             // row-major LDS tile [i][kk]: odd stride, conflict-free over 32 rows
@@ -139,7 +134,7 @@ static_assert(GNW * GOT_BIGN <= 2 * MM_TILE, "column buffer of the big class mus
 
 __device__ __forceinline__ Ctx make_ctx(int n, float* smem) {
     const int tid = threadIdx.x;
-    return Ctx{n, tid, tid & 63, tid >> 6, n > GOT_MAXN ? GOT_BIGN : GOT_MAXN, smem, smem, smem + MM_TILE, smem + 2 * MM_TILE};
+    return Ctx{n, tid, tid & 63, tid >> 6, n > GOT_REGN ? GOT_BIGN : GOT_REGN, smem, smem, smem + MM_TILE, smem + 2 * MM_TILE};
 }
 
 // merge per-lane column accumulators of the GNW waves: f(j, sum_w cacc_w[j])
@@ -186,10 +181,10 @@ __device__ __forceinline__ void col_finish(const Ctx& c, const float (&cacc)[QC]
 // column buffer (2 x GNW x 256 floats <= the two matrix-product tiles the buffer aliases; not for the big class).
 template <int QC, class F>
 __device__ __forceinline__ void col_finish2(const Ctx& c, const float (&ca)[QC], const float (&cb)[QC], F&& f) {
-    static_assert(2 * GNW * GOT_MAXN <= 2 * MM_TILE, "two column buffers must fit the matrix-product tiles");
+    static_assert(2 * GNW * GOT_REGN <= 2 * MM_TILE, "two column buffers must fit the matrix-product tiles");
     // compile-time row stride: every access below is one base register + an immediate offset (with the runtime stride of Ctx the 2 x GNW
     // read addresses of the merge were hoisted out of the sweep's iteration loop and spilled)
-    constexpr int CS = GOT_MAXN;
+    constexpr int CS = GOT_REGN;
     float* first = c.colbuf + c.wave * CS + c.lane;
 #pragma unroll
     for (int q = 0; q < QC; ++q) {
@@ -270,7 +265,7 @@ __device__ __forceinline__ float xch_add(Xch& x, int e, int slot, float v) {
 // col_finish / col_finish2 of a split sweep: the workgroup's column partial, then the partner's (exchange e)
 template <int QC, class F>
 __device__ __forceinline__ void col_finish_x(const Ctx& c, Xch& x, int e, const float (&cacc)[QC], F&& f) {
-    constexpr int CS = GOT_MAXN;
+    constexpr int CS = GOT_REGN;
     float* first = c.colbuf + c.wave * CS + c.lane;
 #pragma unroll
     for (int q = 0; q < QC; ++q)
@@ -287,7 +282,7 @@ __device__ __forceinline__ void col_finish_x(const Ctx& c, Xch& x, int e, const 
 }
 template <int QC, class F>
 __device__ __forceinline__ void col_finish2_x(const Ctx& c, Xch& x, int e, const float (&ca)[QC], const float (&cb)[QC], F&& f) {
-    constexpr int CS = GOT_MAXN;
+    constexpr int CS = GOT_REGN;
     float* first = c.colbuf + c.wave * CS + c.lane;
 #pragma unroll
     for (int q = 0; q < QC; ++q) {
@@ -308,14 +303,14 @@ __device__ __forceinline__ void col_finish2_x(const Ctx& c, Xch& x, int e, const
         // both granules are in flight before the first poll
         const uint32_t tag = x.tag0 + (uint32_t)e;
         const int at = (e & 1) * XCH_SLOTS + c.tid;
-        __hip_atomic_store(x.mine + at + GOT_MAXN, ((unsigned long long)tag << 32) | __float_as_uint(z), __ATOMIC_RELAXED,
+        __hip_atomic_store(x.mine + at + GOT_REGN, ((unsigned long long)tag << 32) | __float_as_uint(z), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
         const float st = xch_add(x, e, c.tid, s);
         unsigned long long g = 0;
         if (!x.dead) {
             int spins = 0;
             for (;;) {
-                g = __hip_atomic_load(x.peer + at + GOT_MAXN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                g = __hip_atomic_load(x.peer + at + GOT_REGN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if ((uint32_t)(g >> 32) == tag) break;
                 if (++spins >= XCH_LIMIT) {
                     x.dead = true;
@@ -352,19 +347,18 @@ __device__ __forceinline__ float block_sum_x(const Ctx& c, Xch& x, int e, float 
 // out(i,j) = sum_k Xop(i,k) Yop(k,j), i < M, j < N (both <= 256), k < K, on the fp32 matrix cores.
 //   Xop(i,k) = TA ? X[k*ldx + i] : X[i*ldx + k]        Yop(k,j) = TB ? Y[j*ldy + k] : Y[k*ldy + j]
 // K is walked in chunks of 16 staged through LDS (next chunk prefetched into registers while the current one is
-// multiplied); wave w owns the 64x64 output panel (w/4, w%4) (64x128 panels with 8 waves).  epi(i, j, value) is called once per element.
-// WIDE = false: wave w owns the 64 x (32 MM_NV) panel of a 4 x 4 (2 x ...) grid -- 9 of 16 waves for M, N in (128, 192], and none on
-// the SIMD that holds waves 3, 7, 11, 15.  WIDE = true (M, N <= 192, 16 waves): 12 waves own 32 x 96 strips (6 x 2 grid), three per
+// multiplied); wave w owns the 64x64 output panel (w/4, w%4).  epi(i, j, value) is called once per element.
+// WIDE = false: wave w owns the 64 x 64 panel of a 4 x 4 grid -- 9 of 16 waves for M, N in (128, 192], and none on
+// the SIMD that holds waves 3, 7, 11, 15.  WIDE = true (M, N <= 192): 12 waves own 32 x 96 strips (6 x 2 grid), three per
 // SIMD: 9 instead of 12 tile-products on the busiest SIMD.  Every output element sees the same MFMA sequence over k in both layouts
 // (same bits).
-// LAY = 2 (round 6, 16 waves): M <= 128, N <= 256 -- a 4 x 4 grid of 32 x 64 panels, every wave busy on HALF the rows of a case (the
+// LAY = 2 (round 6): M <= 128, N <= 256 -- a 4 x 4 grid of 32 x 64 panels, every wave busy on HALF the rows of a case (the
 // forward C_gamma products split over two workgroups, gw_cgamma_half); LAY 0 / 1 = the layouts above (WIDE = LAY == 1).
 template <bool TA, bool TB, int LAY, class Epi>
 __device__ __forceinline__ void mm_impl(const Ctx& c, int M, int N, int K, const float* __restrict__ X, int ldx, const float* __restrict__ Y,
                    int ldy, Epi&& epi) {
     constexpr bool WIDE = LAY == 1, HALF = LAY == 2;
-    static_assert(!HALF || GNW == 16, "the half-rows layout is a 16-wave layout");
-    constexpr int UR = (WIDE || HALF) ? 1 : 2, VC = WIDE ? 3 : (HALF ? 2 : MM_NV);
+    constexpr int UR = (WIDE || HALF) ? 1 : 2, VC = WIDE ? 3 : 2;   // 32-row / 32-column blocks per wave
     float* xs = c.xs;
     float* ys = c.ys;
     // opaque thread id per call: the address arithmetic of every inlined product would otherwise be hoisted to the
@@ -373,8 +367,8 @@ __device__ __forceinline__ void mm_impl(const Ctx& c, int M, int N, int K, const
     asm volatile("" : "+v"(tid_));
     const int tid = tid_, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
-    const int bi0 = WIDE ? (wave >> 1) * 32 : HALF ? (wave >> 2) * 32 : (GNW == 16 ? (wave >> 2) : (wave >> 1)) * 64;
-    const int bj0 = WIDE ? (wave & 1) * 96 : HALF ? (wave & 3) * 64 : (GNW == 16 ? (wave & 3) * 64 : (wave & 1) * 128);
+    const int bi0 = WIDE ? (wave >> 1) * 32 : HALF ? (wave >> 2) * 32 : (wave >> 2) * 64;
+    const int bj0 = WIDE ? (wave & 1) * 96 : (wave & 3) * 64;
     const bool active = bi0 < M && bj0 < N && (!WIDE || wave < 12);
     f32x16 acc[UR][VC];
 #pragma unroll
@@ -457,7 +451,7 @@ template <bool TA, bool TB, bool WOK = false, class Epi>
 __device__ __forceinline__ void mm(const Ctx& c, int M, int N, int K, const float* __restrict__ X, int ldx, const float* __restrict__ Y,
                                    int ldy, Epi&& epi) {
 #ifndef MDL_GOT_NO_WIDE_MM   // (A/B switch of tools/ab)
-    if constexpr (WOK && GNW == 16) {
+    if constexpr (WOK) {
         if (M <= 192 && N <= 192 && (M > 128 || N > 128)) {
             mm_impl<TA, TB, 1>(c, M, N, K, X, ldx, Y, ldy, epi);
             return;
@@ -1391,7 +1385,7 @@ __device__ __forceinline__ void gw_fwd_ipot(const Ctx& c, float* ws, const GotWs
 template <int RPW, int QC>
 __global__ __launch_bounds__(GNT) void got_main_kernel(const GotBatch B) {
     __shared__ float smem[GOT_SMEM];
-    __shared__ float sig[GOT_MAXN], del[GOT_MAXN], rs[GOT_MAXN], rt[GOT_MAXN];
+    __shared__ float sig[GOT_REGN], del[GOT_REGN], rs[GOT_REGN], rt[GOT_REGN];
     int bid = blockIdx.x;
     const GotProb P = got_pick(B, 2, bid);
     float* ws = P.ws;
@@ -1421,7 +1415,7 @@ __global__ __launch_bounds__(GNT) void got_main_kernel(const GotBatch B) {
 template <int RPW, int QC, int STAGE, bool BIG = false>
 __global__ __launch_bounds__(GNT) void got_fwd_stage_kernel(const GotBatch B, int o, int mult) {
     __shared__ float smem[GOT_SMEM];
-    __shared__ float va[BIG ? GOT_BIGN : GOT_MAXN], vb[BIG ? GOT_BIGN : GOT_MAXN];
+    __shared__ float va[BIG ? GOT_BIGN : GOT_REGN], vb[BIG ? GOT_BIGN : GOT_REGN];
     int bid = blockIdx.x;
     const GotProb P = got_pick(B, mult, bid);
     float* ws = P.ws;
@@ -1487,7 +1481,7 @@ __global__ __launch_bounds__(GNT) void got_fwd_stage_kernel(const GotBatch B, in
 template <int RPW, int QC>
 __global__ __launch_bounds__(GNT) void got_fwd_sweep_split_kernel(const GotBatch B, int o, int mode) {
     __shared__ float smem[GOT_SMEM];
-    __shared__ float va[GOT_MAXN];
+    __shared__ float va[GOT_REGN];
     int bid = blockIdx.x;
     const GotProb P = got_pick(B, mode == 1 ? 4 : 2, bid);
     float* ws = P.ws;
@@ -1729,7 +1723,7 @@ __device__ __forceinline__ void gw_bwd_final(const Ctx& c, float* ws, const GotW
 template <int RPW, int QC>
 __global__ __launch_bounds__(GNT) void got_main_bwd_kernel(const GotBatch B) {
     __shared__ float smem[GOT_SMEM];
-    __shared__ float gsig[GOT_MAXN], ga[GOT_MAXN], gdel[GOT_MAXN];
+    __shared__ float gsig[GOT_REGN], ga[GOT_REGN], gdel[GOT_REGN];
     int bid = blockIdx.x;
     const GotProb P = got_pick(B, 2, bid);
     float* ws = P.ws;
@@ -1758,7 +1752,7 @@ __global__ __launch_bounds__(GNT) void got_main_bwd_kernel(const GotBatch B) {
 template <int RPW, int QC, int STAGE, bool BIG = false>
 __global__ __launch_bounds__(GNT) void got_bwd_stage_kernel(const GotBatch B, int o, int mult /* 2: blocks >= k = Wasserstein reverses */) {
     __shared__ float smem[GOT_SMEM];
-    constexpr int VN = BIG ? GOT_BIGN : GOT_MAXN;
+    constexpr int VN = BIG ? GOT_BIGN : GOT_REGN;
     __shared__ float gsig[VN], ga[VN], gdel[VN];
     int bid = blockIdx.x;
     const GotProb P = got_pick(B, mult, bid);
@@ -1818,7 +1812,7 @@ __global__ __launch_bounds__(GNT) void got_bwd_stage_kernel(const GotBatch B, in
 template <int RPW, int QC, int HLR>
 __global__ __launch_bounds__(GNT) void got_bwd_sweep_kernel(const GotBatch B, int o, int mult) {
     __shared__ float smem[GOT_SMEM];
-    __shared__ float ga[GOT_MAXN], Rv[GOT_MAXN], Cv[GOT_MAXN];
+    __shared__ float ga[GOT_REGN], Rv[GOT_REGN], Cv[GOT_REGN];
     __shared__ float Hl[(HLR > 0 ? HLR * QC : 1) * GNT];
     int bid = blockIdx.x;
     const GotProb P = got_pick(B, mult, bid);
@@ -1858,7 +1852,7 @@ __global__ __launch_bounds__(GNT) void got_bwd_sweep_kernel(const GotBatch B, in
 template <int RPW, int QC>
 __global__ __launch_bounds__(GNT) void got_bwd_sweep_split_kernel(const GotBatch B, int o, int mode) {
     __shared__ float smem[GOT_SMEM];
-    __shared__ float ga[GOT_MAXN], Rv[GOT_MAXN], Cv[GOT_MAXN];
+    __shared__ float ga[GOT_REGN], Rv[GOT_REGN], Cv[GOT_REGN];
     int bid = blockIdx.x;
     const GotProb P = got_pick(B, mode == 1 ? 4 : 2, bid);
     float* ws = P.ws;
@@ -2029,7 +2023,7 @@ __global__ __launch_bounds__(GNT) void got_cost_bwd_kernel(const GotBatch B) {
 
 
 // ---------------------------------------------------------------------------------------------------------
-// launch sequences (argument checks are done by the C ABI in got.hip)
+// launch sequences (a call gets here through got_run of got_host.hpp, which has checked it)
 // ---------------------------------------------------------------------------------------------------------
 // Every launch covers all problems of the batch: `mult` * sum_p k_p blocks (mult = blocks per case), one block per problem for the
 // bookkeeping kernels.  The size class is the class of the LARGEST n in the batch (a class runs every smaller n).
@@ -2044,9 +2038,10 @@ static inline int batch_nmax(const GotBatch& B) {
     return n;
 }
 
-int launch_prep(const GotBatch& B, hipStream_t s) {
+static int launch_prep(const GotCall& call, hipStream_t s) {
+    const GotBatch& B = call.b;
     const int K = batch_cases(B), n = batch_nmax(B);
-    if (n > GOT_MAXN) hipLaunchKernelGGL(got_prep_kernel<true>, dim3(K), dim3(GNT), 0, s, B);
+    if (n > GOT_REGN) hipLaunchKernelGGL(got_prep_kernel<true>, dim3(K), dim3(GNT), 0, s, B);
     else hipLaunchKernelGGL(got_prep_kernel<false>, dim3(K), dim3(GNT), 0, s, B);
     MDL_LAUNCH_CHECK();
     hipLaunchKernelGGL(got_minmax_kernel, dim3(B.np), dim3(64), 0, s, B);
@@ -2071,16 +2066,16 @@ static int device_cus() {
     return cus;
 }
 // size class of the launch chain for the largest n of a batch: 64 | 128 (one fused kernel), 192 | 256 (per-phase launches; the IPOT
-// sweeps of 192 on 12 x 3 plan registers per lane), 512 (the workspace-resident class, n > GOT_MAXN)
+// sweeps of 192 on 12 x 3 plan registers per lane), 512 (the workspace-resident class, n > GOT_REGN)
 static int got_class(int n) {
     if (n <= 64) return 64;
     if (n <= 128) return 128;
-    if (n > GOT_MAXN) return 512;
-    return (n <= 192 && GNW == 16 && !getenv("MADELEINE_GOT_NO192")) ? 192 : 256;
+    if (n > GOT_REGN) return 512;
+    return (n <= 192 && !getenv("MADELEINE_GOT_NO192")) ? 192 : 256;
 }
-static bool split_sweeps(int K, int cus) { return GNW == 16 && 2 * K <= cus && !getenv("MADELEINE_GOT_NOSPLIT"); }
+static bool split_sweeps(int K, int cus) { return 2 * K <= cus && !getenv("MADELEINE_GOT_NOSPLIT"); }
 static bool split_sweep_4k(int K, int cus) { return 4 * K <= cus; }   // both sweeps of a two-sweep step in ONE launch
-static bool half_products(int K, int cus) { return GNW == 16 && 2 * K <= cus && !getenv("MADELEINE_GOT_NO_HALF_PRODUCTS"); }
+static bool half_products(int K, int cus) { return 2 * K <= cus && !getenv("MADELEINE_GOT_NO_HALF_PRODUCTS"); }
 template <class K3, class K4>
 static void launch_split(K3 k3, K4 k4, const GotBatch& B, int K, int n, int o, int mult, hipStream_t s) {
     auto go = [&](int blocks, int mode) {
@@ -2094,7 +2089,7 @@ static void launch_split(K3 k3, K4 k4, const GotBatch& B, int K, int n, int o, i
         go(2 * K, 0);
     }
 }
-int launch_fwd_sweep(const GotBatch& B, int o, int mult, hipStream_t s) {
+static int launch_fwd_sweep(const GotBatch& B, int o, int mult, hipStream_t s) {
     const int K = batch_cases(B), n = batch_nmax(B);
     constexpr int R = 256 / GNW, R3 = 192 / GNW;
     if (split_sweeps(K, device_cus())) {
@@ -2109,7 +2104,7 @@ int launch_fwd_sweep(const GotBatch& B, int o, int mult, hipStream_t s) {
     MDL_LAUNCH_CHECK();
     return MDL_OK;
 }
-int launch_bwd_sweep(const GotBatch& B, int o, int mult, hipStream_t s) {
+static int launch_bwd_sweep(const GotBatch& B, int o, int mult, hipStream_t s) {
     const int K = batch_cases(B), n = batch_nmax(B);
     constexpr int R = 256 / GNW, R3 = 192 / GNW;
     if (split_sweeps(K, device_cus())) {
@@ -2117,16 +2112,17 @@ int launch_bwd_sweep(const GotBatch& B, int o, int mult, hipStream_t s) {
         MDL_LAUNCH_CHECK();
         return MDL_OK;
     }
-    // accumulator rows in LDS (16-wave build): 2 of 12 (n <= 192), 7 of 16 (n <= 256); the 8-wave build keeps all of them in registers
+    // accumulator rows in LDS: 2 of 12 (n <= 192), 7 of 16 (n <= 256)
     if (got_class(n) == 192)
         hipLaunchKernelGGL((got_bwd_sweep_kernel<R3, 3, MDL_GOT_HLR3>), dim3(mult * K), dim3(GNT), 0, s, B, o, mult);
     else
-        hipLaunchKernelGGL((got_bwd_sweep_kernel<R, 4, (GNW == 16 ? MDL_GOT_HLR4 : 0)>), dim3(mult * K), dim3(GNT), 0, s, B, o, mult);
+        hipLaunchKernelGGL((got_bwd_sweep_kernel<R, 4, MDL_GOT_HLR4>), dim3(mult * K), dim3(GNT), 0, s, B, o, mult);
     MDL_LAUNCH_CHECK();
     return MDL_OK;
 }
 
-int launch_main(const GotBatch& B, hipStream_t s) {
+static int launch_main(const GotCall& call, hipStream_t s) {
+    const GotBatch& B = call.b;
     const int K = batch_cases(B), c = got_class(batch_nmax(B));
     if (c == 64) {
         hipLaunchKernelGGL((got_main_kernel<64 / GNW, 1>), dim3(2 * K), dim3(GNT), 0, s, B);
@@ -2159,7 +2155,8 @@ int launch_main(const GotBatch& B, hipStream_t s) {
     return MDL_OK;
 }
 
-int launch_bwd_begin(const GotBatch& B, hipStream_t s) {
+static int launch_bwd_begin(const GotCall& call, hipStream_t s) {
+    const GotBatch& B = call.b;
     const int K = batch_cases(B), c = got_class(batch_nmax(B));
     if (c == 64) {
         hipLaunchKernelGGL((got_main_bwd_kernel<64 / GNW, 1>), dim3(2 * K), dim3(GNT), 0, s, B);
@@ -2195,19 +2192,20 @@ int launch_bwd_begin(const GotBatch& B, hipStream_t s) {
     return MDL_OK;
 }
 
-int launch_bwd_finish(const GotBatch& B, hipStream_t s) {
+static int launch_bwd_finish(const GotCall& call, hipStream_t s) {
+    const GotBatch& B = call.b;
     const int K = batch_cases(B), n = batch_nmax(B);
-    if (n > GOT_MAXN) hipLaunchKernelGGL(got_cost_bwd_kernel<true>, dim3(2 * K), dim3(GNT), 0, s, B);   // V side | Q side of every case
+    if (n > GOT_REGN) hipLaunchKernelGGL(got_cost_bwd_kernel<true>, dim3(2 * K), dim3(GNT), 0, s, B);   // V side | Q side of every case
     else hipLaunchKernelGGL(got_cost_bwd_kernel<false>, dim3(2 * K), dim3(GNT), 0, s, B);
     MDL_LAUNCH_CHECK();
     return MDL_OK;
 }
 
-int64_t ws_floats(int k, int n, int d) { return got_layout(k, n, d).g_cases; }
+static int64_t ws_floats(int k, int n, int, int d) { return got_layout(k, n, d).g_cases; }
 
 // mdl_dispatch_plan (dispatch_plan.hip): the class, row-half products and split sweeps launch_main / launch_bwd_begin choose for K cases
 // of largest size n on a device of `cus` compute units
-int plan(int K, int n, int cus, int64_t* o) {
+static int plan(int K, int n, int, int cus, int64_t* o) {
     const int c = got_class(n);
     const bool phased = c == 192 || c == 256;
     o[MDL_PLAN_VARIANT] = c;
@@ -2217,5 +2215,17 @@ int plan(int K, int n, int cus, int64_t* o) {
     return MDL_OK;
 }
 
-}  // namespace GOT_NS
+static int launch_fwd(const GotCall& call, hipStream_t s) {
+    if (const int rc = launch_prep(call, s)) return rc;
+    return launch_main(call, s);
+}
+}  // namespace got1024
+
+// the resident row of the engine table (got_host.hpp): Q has the n tokens of V; a _multi call stays within the register classes
+const GotEngine& got_resident_engine() {
+    using namespace got1024;
+    static const GotEngine e = {GOT_BIGN, GOT_BIGN, GOT_MAXD, GOT_MAXP, GOT_REGN, ws_floats,
+                                {launch_prep, launch_fwd, launch_bwd_begin, launch_bwd_finish}, plan};
+    return e;
+}
 }  // namespace mdl

@@ -1,5 +1,5 @@
 // got_tiled.hip -- the TILED size class of GOT (1 <= n, m <= 4096 tokens, 1 <= d <= 4096): the same forward and reverse sweep as
-// got_impl.inc (see its header for the algebra: IPOT, Gromov-Wasserstein, the one-matrix-per-iteration reverse with Y_t = gQ_t . Q_t),
+// got_resident.hip (see its header for the algebra: IPOT, Gromov-Wasserstein, the one-matrix-per-iteration reverse with Y_t = gQ_t . Q_t),
 // organised for shapes where one case holds more work than a workgroup -- or two -- can do.
 //
 // The two token sets may differ in size: V is [k, n, d], Q is [k, m, d] (mdl_got_tiled_rect_*; the square entry points pass m = n).
@@ -25,7 +25,7 @@
 //   * Offsets are 64-bit: one case's tape at n = 4096 is ~2.5e9 floats.
 // The WD and GW branches share the sweep launches where their iterations overlap (the Wasserstein IPOT runs beside the first GW IPOT
 // in the forward, and its reverse beside the last GW reverse).  Cs and Ct are used with the reference's transposes applied literally.
-#include "common.hpp"
+#include "got_host.hpp"
 
 namespace mdl {
 namespace got_tiled {
@@ -634,7 +634,7 @@ __global__ __launch_bounds__(NT) void tl_merge_kernel(const SArgs a, int mode) {
     }
 }
 
-// Reverse row pass (the one-matrix-per-iteration sweep of got_impl.inc, ipot_backward_h, with H in the workspace).
+// Reverse row pass (the one-matrix-per-iteration sweep of got_resident.hip, ipot_backward_h, with H in the workspace).
 //   seed (p == iters + 1): Y = gscale gT_in . T_iters ; H = iters Y ; Rv = rowsum(Y) ; column partials of Y (set 1)
 //   iteration t: Q_t = T_t / (delta_i sigma_j) ; gr_i = -n delta_i^2 (Rv_i / delta_i + sum_j Q ga) ; W = Q . (delta ga^T + gr so^T) ;
 //                H += t W (t == 1: written as dL/dC = -(1/beta) H) ; Rv_i += delta_i (Q ga)_i + gr_i (Q so)_i ;
@@ -993,7 +993,7 @@ __global__ __launch_bounds__(NT) void tl_norm_bwd_kernel(float* ws, const Lay L,
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// launch sequences
+// launch sequences (a call gets here through got_run of got_host.hpp, which has checked it; they read their pointers from its record)
 // ---------------------------------------------------------------------------------------------------------
 struct Ctx {
     float* ws;
@@ -1001,6 +1001,10 @@ struct Ctx {
     int k, n, m, d;
     hipStream_t s;
 };
+static Ctx ctx(const GotCall& g, hipStream_t s) {   // of the one problem of a call
+    const GotProb& p = g.b.p[0];
+    return Ctx{p.ws, layout(p.k, p.n, g.m, g.b.d), p.k, p.n, g.m, g.b.d, s};
+}
 
 static GTerm term(int K, int64_t oA, int64_t lda, bool ta, int64_t oB, int64_t ldb, bool tb, float ca = 0.f, float cb = 0.f) {
     GTerm t{};
@@ -1210,10 +1214,12 @@ static int gw_bwd_products(const Ctx& c, int o) {
     return gemm(c, z, o >= 1 ? 3 : 2);
 }
 
-int launch_prep(const Ctx& c, float* minmax_out, const float* minmax_in, const float* V, const float* Q) {
+static int launch_prep(const GotCall& g, hipStream_t s) {
+    const Ctx c = ctx(g, s);
+    const GotProb& p = g.b.p[0];
     const Lay& L = c.L;
     const int n = c.n, m = c.m, d = c.d;
-    hipLaunchKernelGGL(tl_norm_kernel, tokrows(c), dim3(NT), 0, c.s, V, Q, c.ws, L, n, m, d);
+    hipLaunchKernelGGL(tl_norm_kernel, tokrows(c), dim3(NT), 0, c.s, p.V, p.Q, c.ws, L, n, m, d);
     MDL_LAUNCH_CHECK();
     GJob j[3];
     const int64_t oa[3] = {L.oVh, L.oVh, L.oQh}, ob[3] = {L.oQh, L.oVh, L.oQh}, oc[3] = {L.oC0, L.oCs0, L.oCt0};
@@ -1227,12 +1233,13 @@ int launch_prep(const Ctx& c, float* minmax_out, const float* minmax_in, const f
     }
     int rc = gemm(c, j, 3);
     if (rc) return rc;
-    hipLaunchKernelGGL(tl_minmax_kernel, dim3(1), dim3(NT), 0, c.s, c.ws, L, c.k, minmax_out, minmax_in);
+    hipLaunchKernelGGL(tl_minmax_kernel, dim3(1), dim3(NT), 0, c.s, c.ws, L, c.k, p.mm_out, p.mm_in);
     MDL_LAUNCH_CHECK();
     return MDL_OK;
 }
 
-int launch_main(const Ctx& c, float* out) {
+static int launch_main(const GotCall& g, hipStream_t s) {
+    const Ctx c = ctx(g, s);
     const Lay& L = c.L;
     hipLaunchKernelGGL(tl_thr_kernel, xpanels(c), dim3(NT), 0, c.s, c.ws, L, c.n, c.m);
     MDL_LAUNCH_CHECK();
@@ -1252,12 +1259,14 @@ int launch_main(const Ctx& c, float* out) {
     }
     rc = gw_cgamma(c, GW_OUTER);
     if (rc) return rc;
-    hipLaunchKernelGGL(tl_sum_kernel, dim3(1), dim3(NT), 0, c.s, c.ws, L, c.k, out);
+    hipLaunchKernelGGL(tl_sum_kernel, dim3(1), dim3(NT), 0, c.s, c.ws, L, c.k, g.b.p[0].out);
     MDL_LAUNCH_CHECK();
     return MDL_OK;
 }
 
-int launch_bwd_begin(const Ctx& c, const float* d_out, float* d_minmax) {
+static int launch_bwd_begin(const GotCall& g, hipStream_t s) {
+    const Ctx c = ctx(g, s);
+    const float* d_out = g.b.p[0].d_out;
     const Lay& L = c.L;
     const int n = c.n, m = c.m;
     hipLaunchKernelGGL(tl_gw_seed_kernel, xpanels(c), dim3(NT), 0, c.s, c.ws, L, n, m, d_out);
@@ -1278,18 +1287,20 @@ int launch_bwd_begin(const Ctx& c, const float* d_out, float* d_minmax) {
     }
     hipLaunchKernelGGL(tl_bwd_final_kernel, xpanels(c), dim3(NT), 0, c.s, c.ws, L, n, m, d_out);
     MDL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tl_thr_bwd_kernel, dim3(1), dim3(NT), 0, c.s, c.ws, L, c.k, d_minmax);
+    hipLaunchKernelGGL(tl_thr_bwd_kernel, dim3(1), dim3(NT), 0, c.s, c.ws, L, c.k, g.b.p[0].d_mm);
     MDL_LAUNCH_CHECK();
     return MDL_OK;
 }
 
 // C0 = 1 - V^ Q^T (n x m), Cs0 = 1 - V^ V^T (n x n), Ct0 = 1 - Q^ Q^T (m x m):
 //   gV^ = -(G0 Q^ + Gs V^ + Gs^T V^) (n x d) ;  gQ^ = -(G0^T V^ + Gt Q^ + Gt^T Q^) (m x d)
-int launch_bwd_finish(const Ctx& c, const float* d_minmax_total, float* dV, float* dQ) {
+static int launch_bwd_finish(const GotCall& g, hipStream_t s) {
+    const Ctx c = ctx(g, s);
+    const GotProb& p = g.b.p[0];
     const Lay& L = c.L;
     const int n = c.n, m = c.m, d = c.d;
     const int64_t ldn = L.ldn, ldm = L.ldm;
-    hipLaunchKernelGGL(tl_route_kernel, xpanels(c), dim3(NT), 0, c.s, c.ws, L, n, m, d_minmax_total);
+    hipLaunchKernelGGL(tl_route_kernel, xpanels(c), dim3(NT), 0, c.s, c.ws, L, n, m, p.d_mm_total);
     MDL_LAUNCH_CHECK();
     GJob j[2];
     j[0] = job(GM_STORE, -1.f, n, d, L.ogVh, d);
@@ -1304,143 +1315,36 @@ int launch_bwd_finish(const Ctx& c, const float* d_minmax_total, float* dV, floa
     j[1].nt = 3;
     int rc = gemm(c, j, 2);
     if (rc) return rc;
-    hipLaunchKernelGGL(tl_norm_bwd_kernel, tokrows(c), dim3(NT), 0, c.s, c.ws, L, n, m, d, dV, dQ);
+    hipLaunchKernelGGL(tl_norm_bwd_kernel, tokrows(c), dim3(NT), 0, c.s, c.ws, L, n, m, d, p.dV, p.dQ);
     MDL_LAUNCH_CHECK();
+    return MDL_OK;
+}
+
+static int launch_fwd(const GotCall& g, hipStream_t s) {
+    if (const int rc = launch_prep(g, s)) return rc;
+    return launch_main(g, s);
+}
+
+static int64_t ws_floats(int k, int n, int m, int d) { return layout(k, n, m, d).g_end; }
+
+// mdl_dispatch_plan products 12 (m = n) and 13 (dispatch_plan.hip)
+static int plan(int, int n, int m, int, int64_t* o) {
+    o[MDL_PLAN_VARIANT] = RP;                             // rows of a sweep panel
+    o[MDL_PLAN_PERSIST] = 0;
+    o[MDL_PLAN_SPLITS] = cdiv(n, RP);                     // row panels per case (sweep workgroups per case and branch)
+    o[MDL_PLAN_TPS] = MT;                                 // output tile edge of the products
+    o[MDL_PLAN_EMPTY] = cdiv(n, MT) * cdiv(m, MT);        // product tiles per case of an n x m product
+    o[MDL_PLAN_CHUNK] = CW;                               // columns of a sweep chunk
+    o[MDL_PLAN_EXTRA] = 2;                                // launches per IPOT iteration (row pass + column merge)
     return MDL_OK;
 }
 
 }  // namespace got_tiled
 
-// mdl_dispatch_plan products 12 (m = n) and 13 (dispatch_plan.hip)
-int plan_got_tiled(int64_t k, int n, int m, int d, int64_t* o) {
-    if (k < 1 || n < 1 || m < 1 || d < 1 || k > 0x7fffffff) return MDL_E_ARG;
-    if (n > got_tiled::TMAXN || m > got_tiled::TMAXN || d > got_tiled::TMAXD) return MDL_E_UNSUPPORTED;
-    const int64_t P = got_tiled::cdiv(n, got_tiled::RP), tn = got_tiled::cdiv(n, got_tiled::MT), tm = got_tiled::cdiv(m, got_tiled::MT);
-    o[MDL_PLAN_VARIANT] = got_tiled::RP;      // rows of a sweep panel
-    o[MDL_PLAN_PERSIST] = 0;
-    o[MDL_PLAN_SPLITS] = P;                   // row panels per case (sweep workgroups per case and branch)
-    o[MDL_PLAN_TPS] = got_tiled::MT;          // output tile edge of the products
-    o[MDL_PLAN_EMPTY] = tn * tm;              // product tiles per case of an n x m product
-    o[MDL_PLAN_CHUNK] = got_tiled::CW;        // columns of a sweep chunk
-    o[MDL_PLAN_EXTRA] = 2;                    // launches per IPOT iteration (row pass + column merge)
-    return MDL_OK;
+// the tiled row of the engine table (got_host.hpp): one problem per call, Q with a token count of its own
+const GotEngine& got_tiled_engine() {
+    using namespace got_tiled;
+    static const GotEngine e = {TMAXN, TMAXN, TMAXD, 1, 0, ws_floats, {launch_prep, launch_fwd, launch_bwd_begin, launch_bwd_finish}, plan};
+    return e;
 }
 }  // namespace mdl
-
-using namespace mdl;
-
-static int tl_check(int k, int n, int m, int d) {
-    if (k < 0 || n < 0 || m < 0 || d < 1) return MDL_E_ARG;
-    if (n > got_tiled::TMAXN || m > got_tiled::TMAXN || d > got_tiled::TMAXD) return MDL_E_UNSUPPORTED;
-    return MDL_OK;
-}
-
-static got_tiled::Ctx tl_ctx(void* ws, int k, int n, int m, int d, void* stream) {
-    got_tiled::Ctx c;
-    c.ws = (float*)ws;
-    c.L = got_tiled::layout(k, n, m, d);
-    c.k = k;
-    c.n = n;
-    c.m = m;
-    c.d = d;
-    c.s = (hipStream_t)stream;
-    return c;
-}
-
-// The rectangular entry points: V [k, n, d], Q [k, m, d].  The square ones below are their m = n case.
-extern "C" int64_t mdl_got_tiled_rect_ws_bytes(int k, int n, int m, int d) {
-    const int rc = tl_check(k, n, m, d);
-    if (rc) return rc;
-    return got_tiled::layout(k, n, m, d).g_end * 4 + 64;
-}
-
-extern "C" int mdl_got_tiled_rect_fwd(const float* V, const float* Q, float* out, float* minmax_out, const float* minmax_in, int k,
-                                      int n, int m, int d, void* ws, void* stream) {
-    const int rc = tl_check(k, n, m, d);
-    if (rc) return rc;
-    if (!out || !ws) return MDL_E_ARG;
-    if (!host_aligned16(ws)) return MDL_E_ALIGN;
-    if (k == 0 || n == 0 || m == 0) {   // empty token tensors may have no storage
-        const hipError_t e = hipMemsetAsync(out, 0, 2 * sizeof(float), (hipStream_t)stream);
-        return e == hipSuccess ? MDL_OK : (int)e;
-    }
-    if (!V || !Q) return MDL_E_ARG;
-    const got_tiled::Ctx c = tl_ctx(ws, k, n, m, d, stream);
-    const int r = got_tiled::launch_prep(c, minmax_out, minmax_in, V, Q);
-    if (r) return r;
-    return got_tiled::launch_main(c, out);
-}
-
-extern "C" int mdl_got_tiled_rect_extrema(const float* V, const float* Q, float* minmax_out, int k, int n, int m, int d, void* ws,
-                                          void* stream) {
-    const int rc = tl_check(k, n, m, d);
-    if (rc) return rc;
-    if (!V || !Q || !minmax_out || !ws) return MDL_E_ARG;
-    if (!host_aligned16(ws)) return MDL_E_ALIGN;
-    if (k == 0 || n == 0 || m == 0) return MDL_E_ARG;   // extrema of an empty batch are undefined
-    return got_tiled::launch_prep(tl_ctx(ws, k, n, m, d, stream), minmax_out, nullptr, V, Q);
-}
-
-extern "C" int mdl_got_tiled_rect_bwd_begin(const float* d_out, float* d_minmax, int k, int n, int m, int d, void* ws, void* stream) {
-    const int rc = tl_check(k, n, m, d);
-    if (rc) return rc;
-    if (!d_out || !ws) return MDL_E_ARG;
-    if (!host_aligned16(ws)) return MDL_E_ALIGN;
-    if (k == 0 || n == 0 || m == 0) {
-        if (d_minmax) {
-            const hipError_t e = hipMemsetAsync(d_minmax, 0, 6 * sizeof(float), (hipStream_t)stream);
-            if (e != hipSuccess) return (int)e;
-        }
-        return MDL_OK;
-    }
-    return got_tiled::launch_bwd_begin(tl_ctx(ws, k, n, m, d, stream), d_out, d_minmax);
-}
-
-extern "C" int mdl_got_tiled_rect_bwd_finish(const float* V, const float* Q, float* dV, float* dQ, const float* d_minmax_total, int k,
-                                             int n, int m, int d, void* ws, void* stream) {
-    const int rc = tl_check(k, n, m, d);
-    if (rc) return rc;
-    if (!ws) return MDL_E_ARG;
-    if (!host_aligned16(ws)) return MDL_E_ALIGN;
-    if (k == 0 || n == 0 || m == 0) {   // empty token tensors may have no storage; the other side's gradient is zero
-        const size_t bv = (size_t)k * n * d * sizeof(float), bq = (size_t)k * m * d * sizeof(float);
-        if ((bv && !dV) || (bq && !dQ)) return MDL_E_ARG;
-        hipError_t e = bv ? hipMemsetAsync(dV, 0, bv, (hipStream_t)stream) : hipSuccess;
-        if (e == hipSuccess && bq) e = hipMemsetAsync(dQ, 0, bq, (hipStream_t)stream);
-        return e == hipSuccess ? MDL_OK : (int)e;
-    }
-    if (!V || !Q || !dV || !dQ) return MDL_E_ARG;
-    return got_tiled::launch_bwd_finish(tl_ctx(ws, k, n, m, d, stream), d_minmax_total, dV, dQ);
-}
-
-extern "C" int mdl_got_tiled_rect_bwd(const float* V, const float* Q, const float* d_out, float* dV, float* dQ, int k, int n, int m,
-                                      int d, void* ws, void* stream) {
-    const int rc = mdl_got_tiled_rect_bwd_begin(d_out, nullptr, k, n, m, d, ws, stream);
-    if (rc) return rc;
-    return mdl_got_tiled_rect_bwd_finish(V, Q, dV, dQ, nullptr, k, n, m, d, ws, stream);
-}
-
-extern "C" int64_t mdl_got_tiled_ws_bytes(int k, int n, int d) { return mdl_got_tiled_rect_ws_bytes(k, n, n, d); }
-
-extern "C" int mdl_got_tiled_fwd(const float* V, const float* Q, float* out, float* minmax_out, const float* minmax_in, int k, int n,
-                                 int d, void* ws, void* stream) {
-    return mdl_got_tiled_rect_fwd(V, Q, out, minmax_out, minmax_in, k, n, n, d, ws, stream);
-}
-
-extern "C" int mdl_got_tiled_extrema(const float* V, const float* Q, float* minmax_out, int k, int n, int d, void* ws, void* stream) {
-    return mdl_got_tiled_rect_extrema(V, Q, minmax_out, k, n, n, d, ws, stream);
-}
-
-extern "C" int mdl_got_tiled_bwd_begin(const float* d_out, float* d_minmax, int k, int n, int d, void* ws, void* stream) {
-    return mdl_got_tiled_rect_bwd_begin(d_out, d_minmax, k, n, n, d, ws, stream);
-}
-
-extern "C" int mdl_got_tiled_bwd_finish(const float* V, const float* Q, float* dV, float* dQ, const float* d_minmax_total, int k, int n,
-                                        int d, void* ws, void* stream) {
-    return mdl_got_tiled_rect_bwd_finish(V, Q, dV, dQ, d_minmax_total, k, n, n, d, ws, stream);
-}
-
-extern "C" int mdl_got_tiled_bwd(const float* V, const float* Q, const float* d_out, float* dV, float* dQ, int k, int n, int d, void* ws,
-                                 void* stream) {
-    return mdl_got_tiled_rect_bwd(V, Q, d_out, dV, dQ, k, n, n, d, ws, stream);
-}

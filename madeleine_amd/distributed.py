@@ -51,7 +51,7 @@ def init_from_env(backend: Optional[str] = None):
             torch.cuda.set_device(local_rank)
         if torch.cuda.is_available() and world > torch.cuda.device_count():
             # debug runs with several ranks on one GPU: the processes' launches share the compute units, so the residency bound the split
-            # IPOT sweeps rely on (csrc/got_impl.inc, Xch) does not hold -- keep the one-workgroup sweeps
+            # IPOT sweeps rely on (csrc/got_resident.hip, Xch) does not hold -- keep the one-workgroup sweeps
             os.environ.setdefault("MADELEINE_GOT_NOSPLIT", "1")
         dist.init_process_group(backend=backend, rank=rank, world_size=world)
     return rank, world, local_rank
@@ -396,7 +396,7 @@ class _fan_out:
             # the side lanes depend on what the current stream held BEFORE the fan-out, not on lane 0's own launches
             self.start = torch.cuda.Event()
             self.start.record(self.main)
-            # The split IPOT sweeps (two workgroups per case that wait for each other, csrc/got_impl.inc) size every launch so that all of
+            # The split IPOT sweeps (two workgroups per case that wait for each other, csrc/got_resident.hip) size every launch so that all of
             # its workgroups can be resident together; several chains launched side by side on different streams void that bound: keep the
             # one-workgroup sweeps for launches issued inside a fan-out (the launcher reads the variable at every launch).
             self.nosplit_was = os.environ.get("MADELEINE_GOT_NOSPLIT")

@@ -8,6 +8,7 @@ points; anything else raises (there is no CPU or eager fallback).
 Layouts (see include/madeleine_amd.h): token embeddings are head-major [T, H*512]; scores [T, H].
 """
 import collections
+import contextlib
 import os
 import threading
 from typing import Optional
@@ -1392,7 +1393,46 @@ class _GotFamily:
         """<prefix><stage>(tensors..., sizes..., ws, stream): the argument list of every entry point of a family."""
         _call(self.prefix + stage, *tensors, *sz, ws, _stream())
 
+    # ---- the stages of a call, once for GOTFn, got_extrema and HipGotImpl: each owns its workspace query, its _timed name and its call.
+    # The state of a forward is (V, Q, ws): what the backward stages take.  timer: _timed, or _untimed for a stage that is not timed.
+    def extrema(self, V, Q):
+        sz = self.sizes(V, Q)
+        ws = _ws_for(self.prefix + "_ws_bytes", V.device, *sz)     # (its own scratch; a shape outside the class fails as a workspace query)
+        mm = torch.empty(6, device=V.device, dtype=torch.float32)
+        self.call("_extrema", sz, ws, V, Q, mm)
+        return mm
 
+    def forward(self, V, Q, mm_out, minmax_in):
+        ws = self.workspace(V, Q)
+        out = torch.empty(2, device=V.device, dtype=torch.float32)
+        with _timed(self.timed + "_fwd"):
+            self.call("_fwd", self.sizes(V, Q), ws, V, Q, out, mm_out, minmax_in)
+        return out, (V, Q, ws)
+
+    def backward(self, state, d_out):
+        """Both backward stages in one call: a backward that keeps its own threshold gradients."""
+        V, Q, ws = state
+        dV, dQ = torch.empty_like(V), torch.empty_like(Q)
+        with _timed(self.timed + "_bwd"):
+            self.call("_bwd", self.sizes(V, Q), ws, V, Q, d_out.contiguous(), dV, dQ)
+        return dV, dQ
+
+    def backward_begin(self, state, d_out, timer):
+        V, Q, ws = state
+        dmm = torch.empty(6, device=V.device, dtype=torch.float32)
+        with timer(self.timed + "_bwd"):
+            self.call("_bwd_begin", self.sizes(V, Q), ws, d_out.contiguous(), dmm)
+        return dmm
+
+    def backward_finish(self, state, dmm_total, timer):
+        V, Q, ws = state
+        dV, dQ = torch.empty_like(V), torch.empty_like(Q)
+        with timer(self.timed + "_bwd_finish"):
+            self.call("_bwd_finish", self.sizes(V, Q), ws, V, Q, dV, dQ, dmm_total.contiguous())
+        return dV, dQ
+
+
+_untimed = lambda _name: contextlib.nullcontext()      # noqa: E731  (functional.got's two-stage backward is not timed)
 GOT_RESIDENT = _GotFamily("mdl_got", "got",
                           "madeleine_amd.GOT supports n <= 512 tokens per bag and d <= 128 (got n=%d, d=%d); "
                           "the reference calls it with subsample=256 (trainer.py:44)")
@@ -1418,12 +1458,9 @@ class GOTFn(torch.autograd.Function):
         if V.dim() != 3 or Q.dim() != 3 or (V.shape[0], V.shape[2]) != (Q.shape[0], Q.shape[2]) or (
                 V.shape[1] != Q.shape[1] and not fam.rect):
             raise ValueError("GOT expects two token tensors of identical shape [k, n, d]")
-        ws = fam.workspace(V, Q)
-        out = torch.empty(2, device=V.device, dtype=torch.float32)
         mm = torch.empty(6, device=V.device, dtype=torch.float32)
-        with _timed(fam.timed + "_fwd"):
-            fam.call("_fwd", fam.sizes(V, Q), ws, V, Q, out, mm, minmax_in)
-        ctx.save_for_backward(V, Q, ws)
+        out, state = fam.forward(V, Q, mm, minmax_in)
+        ctx.save_for_backward(*state)
         ctx.reduce_dminmax = reduce_dminmax
         ctx.fam = fam
         ctx.mark_non_differentiable(mm)
@@ -1431,19 +1468,12 @@ class GOTFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_out, _d_mm):
-        V, Q, ws = ctx.saved_tensors
-        fam = ctx.fam
-        sz = fam.sizes(V, Q)
-        dV, dQ = torch.empty_like(V), torch.empty_like(Q)
-        d_out = d_out.contiguous()
+        fam, state = ctx.fam, ctx.saved_tensors
         if ctx.reduce_dminmax is None:
-            with _timed(fam.timed + "_bwd"):
-                fam.call("_bwd", sz, ws, V, Q, d_out, dV, dQ)
+            dV, dQ = fam.backward(state, d_out)
         else:
-            dmm = torch.empty(6, device=V.device, dtype=torch.float32)
-            fam.call("_bwd_begin", sz, ws, d_out, dmm)
-            dmm = ctx.reduce_dminmax(dmm).contiguous()      # e.g. all_reduce(SUM) over ranks
-            fam.call("_bwd_finish", sz, ws, V, Q, dV, dQ, dmm)
+            dmm = ctx.reduce_dminmax(fam.backward_begin(state, d_out, _untimed))      # e.g. all_reduce(SUM) over ranks
+            dV, dQ = fam.backward_finish(state, dmm, _untimed)
         return dV, dQ, None, None, None
 
 
@@ -1451,15 +1481,11 @@ def got_extrema(V, Q):
     """Extrema [6] (cross min,max | intra-V min,max | intra-Q min,max) of this batch's raw GOT cost tensors."""
     _require(V, "v_")
     _require(Q, "q_")
-    fam, sz = GOT_RESIDENT, GOT_RESIDENT.sizes(V, Q)
-    ws = _ws_for(fam.prefix + "_ws_bytes", V.device, *sz)     # (its own scratch; a shape outside the class fails as a workspace query)
-    mm = torch.empty(6, device=V.device, dtype=torch.float32)
-    fam.call("_extrema", sz, ws, V, Q, mm)
-    return mm
+    return GOT_RESIDENT.extrema(V, Q)
 
 
 def got_exchange_timeouts(ws) -> float:
-    """Diagnostic of the split IPOT sweeps (csrc/got_impl.inc, Xch): non-zero when a workgroup gave up waiting for its partner's column
+    """Diagnostic of the split IPOT sweeps (csrc/got_resident.hip, Xch): non-zero when a workgroup gave up waiting for its partner's column
     sums in the last pass on this workspace.  That pass's numbers are void and say so themselves: the distances of a forward and the
     token gradients of a backward on a flagged workspace come back NaN (got_sum_kernel / got_cost_bwd_kernel) -- the flag is for
     diagnosis, nothing has to poll it.  The workspace's global region ends with
@@ -1510,44 +1536,28 @@ class HipGotImpl:
 
     @staticmethod
     def forward(V, Q, minmax):
-        fam = HipGotImpl.FAM
-        ws = fam.workspace(V, Q)
-        out = torch.empty(2, device=V.device, dtype=torch.float32)
-        mm = minmax.contiguous()
-        with _timed("got_fwd"):
-            fam.call("_fwd", fam.sizes(V, Q), ws, V, Q, out, None, mm)
-        return out, (V, Q, ws)
+        return HipGotImpl.FAM.forward(V, Q, None, minmax.contiguous())
 
     @staticmethod
     def backward_begin(state, d_out):
-        V, Q, ws = state
-        fam = HipGotImpl.FAM
-        dmm = torch.empty(6, device=V.device, dtype=torch.float32)
-        with _timed("got_bwd"):
-            fam.call("_bwd_begin", fam.sizes(V, Q), ws, d_out.contiguous(), dmm)
-        return dmm
+        return HipGotImpl.FAM.backward_begin(state, d_out, _timed)
 
     @staticmethod
     def backward_finish(state, dmm_total):
-        V, Q, ws = state
-        fam = HipGotImpl.FAM
-        dV, dQ = torch.empty_like(V), torch.empty_like(Q)
-        dmm_total = dmm_total.contiguous()
-        with _timed("got_bwd_finish"):
-            fam.call("_bwd_finish", fam.sizes(V, Q), ws, V, Q, dV, dQ, dmm_total)
-        return dV, dQ
+        return HipGotImpl.FAM.backward_finish(state, dmm_total, _timed)
 
     # ---- several problems per launch (mdl_got_*_multi): every kernel launch covers all problems, on the caller's stream alone ----
-    MAX_BATCH = 4
+    MAX_BATCH = _native._DEFINES["MDL_GOT_MAX_BATCH"]
+    MAX_BATCH_N = 256      # tokens of a problem of a batched call (the register classes of csrc/got_resident.hip; MDL_E_UNSUPPORTED above)
 
     @staticmethod
     def can_batch(problems) -> bool:
-        """2 .. MAX_BATCH non-empty problems on one ROCm device, every n <= 256, one d."""
+        """2 .. MAX_BATCH non-empty problems on one ROCm device, every n <= MAX_BATCH_N, one d."""
         if not 2 <= len(problems) <= HipGotImpl.MAX_BATCH or os.environ.get("MADELEINE_GOT_NO_BATCH"):
             return False
         d = problems[0][0].shape[2]
-        return all(V.is_cuda and V.dtype == torch.float32 and V.shape[0] >= 1 and 1 <= V.shape[1] <= 256 and V.shape[2] == d
-                   and V.device == problems[0][0].device for V, _ in problems)
+        return all(V.is_cuda and V.dtype == torch.float32 and V.shape[0] >= 1 and 1 <= V.shape[1] <= HipGotImpl.MAX_BATCH_N
+                   and V.shape[2] == d and V.device == problems[0][0].device for V, _ in problems)
 
     @staticmethod
     def _arrays(problems, wss):

@@ -1,7 +1,7 @@
 """GOT at the shapes the 8-GPU configurations give ONE rank (reference madeleine/utils/loss.py:179-193,236-248,278-302):
 
   (a) four problems x k = 32 local cases x n = 256 tokens in ONE batched launch sequence (BASELINE configs[3] with every stain present, and
-      every rank of configs[4]) -- the n in (192, 256] class of the one-pass IPOT reverse sweep (csrc/got_impl.inc, LDS-resident accumulator
+      every rank of configs[4]) -- the n in (192, 256] class of the one-pass IPOT reverse sweep (csrc/got_resident.hip, LDS-resident accumulator
       rows) -- and a mixed batch n = 256 / 200 / 130 / 64, against the fp64 oracle: both distances and the token gradients, twice for
       bit-reproducibility, batched == single-problem for the top size class;
   (b) the config-5 rank shape through calculate_losses_dp: ragged bags with stain tokens -> the first 256 tokens of every bag -> k = 256,
@@ -223,7 +223,7 @@ def test_bench_rank_emulation_equals_oracle_on_the_concatenated_global_batch(dev
 
 def test_split_sweeps_equal_one_workgroup_sweeps_and_do_not_depend_on_timing(dev):
     """Round 6: the IPOT sweeps of the n <= 192 / 256 classes run as TWO workgroups per case and branch that exchange their column sums
-    once per iteration (csrc/got_impl.inc, Xch).  (i) Same numbers as the one-workgroup sweeps (MADELEINE_GOT_NOSPLIT=1) up to the
+    once per iteration (csrc/got_resident.hip, Xch).  (i) Same numbers as the one-workgroup sweeps (MADELEINE_GOT_NOSPLIT=1) up to the
     re-association of the column sums; (ii) bit-identical from run to run while another stream keeps the memory system and the compute
     units busy (the exchange is value-deterministic: a stale or torn granule would change bits); (iii) no exchange timed out."""
     from madeleine_amd import functional as MF
@@ -263,7 +263,7 @@ def test_split_sweeps_equal_one_workgroup_sweeps_and_do_not_depend_on_timing(dev
 
 @pytest.mark.parametrize("k,n", [(6, 256), (5, 150), (4, 100), (3, 40), (2, 300)])
 def test_void_pass_comes_back_as_nan_not_as_numbers(dev, k, n):
-    """A split sweep that gives up on its partner (csrc/got_impl.inc, Xch: e.g. two processes sharing the GPU, each assuming it owns every
+    """A split sweep that gives up on its partner (csrc/got_resident.hip, Xch: e.g. two processes sharing the GPU, each assuming it owns every
     compute unit) raises the workspace's time-out flag.  Nothing polls that flag in a training loop, so the pass itself must say it is
     void: with the flag raised the backward returns NaN token gradients (and a forward NaN distances: got_sum_kernel reads the same
     word).  Every size class defines the flag (cleared by the extrema kernel), so regular passes stay finite in all of them."""

@@ -127,6 +127,23 @@ def test_got_rect_limits(dev):
         assert float(a.grad.abs().sum()) == 0.0 and float(b.grad.abs().sum()) == 0.0
 
 
+@pytest.mark.parametrize("shape", [(0, 8, 8), (2, 0, 8)])
+def test_got_resident_empty_problem(dev, shape):
+    """The resident class (the training path's: got_route(0, 8, 8) and (2, 0, 8) are 'resident') with k = 0 and with n = 0, as the
+    tiled class has it above: tensors of no elements have no storage, the distances are (0, 0) and the gradients are zero."""
+    from madeleine_amd import GOT, functional as MF
+    from madeleine_amd.loss import got_route
+    assert got_route(*shape) == "resident"
+    for fn in (MF.got, lambda a, b: GOT(a, b, subsample=None)):
+        v = torch.zeros(*shape, device=dev, requires_grad=True)
+        q = torch.zeros(*shape, device=dev, requires_grad=True)
+        o = fn(v, q)
+        o.sum().backward()
+        assert torch.equal(o.detach(), torch.zeros_like(o)) and o.numel() in (1, 2)
+        assert v.grad.shape == v.shape and q.grad.shape == q.shape
+        assert float(v.grad.abs().sum()) == 0.0 and float(q.grad.abs().sum()) == 0.0
+
+
 def test_got_rect_square_is_the_same_code(dev):
     """(2, 300, 300, 64) through the mdl_got_tiled_rect_* entry points and through the six square ones: the same bits."""
     from madeleine_amd import functional as MF

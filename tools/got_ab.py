@@ -30,7 +30,7 @@ def run(L, v, q, reps=2):
         rc = L.mdl_got_bwd(v.data_ptr(), q.data_ptr(), go.data_ptr(), dv.data_ptr(), dq.data_ptr(), k, n, d, ws.data_ptr(), st); assert rc == 0, rc
         e[2].record(); torch.cuda.synchronize()
         best = (min(best[0], e[0].elapsed_time(e[1])), min(best[1], e[1].elapsed_time(e[2])))
-    # exchange time-out flag of the split sweeps (got_impl.inc: ws[g_gen + 1]; the global region ends with g_gen[4])
+    # exchange time-out flag of the split sweeps (got_resident.hip: ws[g_gen + 1]; the global region ends with g_gen[4])
     nf = (ws.numel() - 64) // 4
     err = float(ws[:nf * 4].view(torch.float32)[nf - 3]) if nf >= 4 else 0.0
     return out.clone(), dv.clone(), dq.clone(), best, err

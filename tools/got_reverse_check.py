@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""fp64 emulation of the reverse sweep implemented in csrc/got.hip, checked against autograd of the oracle.
+"""fp64 emulation of the reverse sweep implemented in csrc/got_resident.hip, checked against autograd of the oracle.
 Validates the hand derivation (IPOT backward, GW chain, thresholds, normalisation) independent of the GPU."""
 import sys, os
 import torch
@@ -49,7 +49,7 @@ def ipot_bwd(C, inv_beta, iters, Th, dh, sh, gT):
 
 
 def ipot_bwd_onepass(C, inv_beta, iters, Th, dh, sh, gT, dtype=None, q_from_plan=False):
-    """The reverse sweep as csrc/got_impl.inc runs it since round 5 (ipot_backward_h): ONE pass over Q_t = A . T_{t-1} per iteration and
+    """The reverse sweep as csrc/got_resident.hip runs it since round 5 (ipot_backward_h): ONE pass over Q_t = A . T_{t-1} per iteration and
     no matrix-sized state besides the accumulator H.  With Y_t := gQ_t . Q_t (elementwise) the recurrences of ipot_bwd collapse:
         gq_t = gT_t . Q_t = Y_{t+1} / (delta_t,i sigma_t,j)      (A . Q_t = Q_{t+1} / (delta_t sigma_t), gT_t = gQ_{t+1} . A)
         gdel_i = rowsum(Y_{t+1})_i / delta_t,i ;  u_j = colsum(Y_{t+1})_j / sigma_t,j        -> only the row / column SUMS of Y travel
