@@ -899,8 +899,16 @@ int mdl_bag_mean_tiered(const void* store, const void* store_host, int dtype, in
  * counting in integers, S <= MDL_PROBE_MAX_CASES; the order of the atomic additions cannot change a bit of the result.
  *
  * Workspaces: 16-byte aligned, sizes from the *_ws_bytes queries, contents need no initialisation.
- * MDL_E_UNSUPPORTED: n_max > MDL_PROBE_MAX_TRAIN, C outside [2, MDL_PROBE_MAX_CLASSES], S > MDL_PROBE_MAX_CASES (metrics), a launch grid or
- * an output index beyond int32.  MDL_E_ARG: null pointers, ldX < d, sizes < 1, ldy not 0 or >= S, max_iter < 0. */
+ * Refusals, in this order, all before any launch and before any device pointer is touched (one check for every entry point that takes
+ * the problem list: P1, P3, L1, L2, S1, S2 and B2, B3 of madeleine_amd_stats.h).
+ *   (1) MDL_E_ARG: a NULL pointer; P, n_max or S < 1; d < 1 or ldX < d; max_iter < 0, cost not > 0, gtol not >= 0; ldy neither 0 nor >= S.
+ *   (2) MDL_E_UNSUPPORTED: n_max > MDL_PROBE_MAX_TRAIN, C outside [2, MDL_PROBE_MAX_CLASSES], S > MDL_PROBE_MAX_CASES (metrics); S, P,
+ *       P * n_max, P * cols * d or a launch grid beyond int32.
+ *   (3) MDL_E_ALIGN: ws not 16-byte aligned.
+ * A call with a fault of (2) and one of (3) is answered with (2).  (While every entry point carried its own checks, the fits and the
+ * metrics of P, L and S looked at the alignment before the int32 bounds of their grids and answered such a call MDL_E_ALIGN; a call with
+ * one fault gets what it always got.)
+ * mdl_probe_scores takes no problem list and follows the same three steps. */
 #define MDL_PROBE_MAX_TRAIN 256
 #define MDL_PROBE_MAX_CLASSES 8
 #define MDL_PROBE_MAX_CASES 16384
@@ -943,7 +951,8 @@ int mdl_probe_metrics(const float* z, const int32_t* y, int64_t ldy, const int32
  *
  * Workspaces: 16-byte aligned, contents need no initialisation.  MDL_E_UNSUPPORTED: n_max > MDL_LOGIT_MAX_TRAIN, d > MDL_LOGIT_MAX_DIM
  * (fit), C outside [2, MDL_PROBE_MAX_CLASSES], S > MDL_PROBE_MAX_CASES (metrics), a launch grid or an output index beyond int32.
- * MDL_E_ARG, MDL_E_ALIGN: as P1-P3.  All of it is checked before anything is launched. */
+ * MDL_E_ARG, MDL_E_ALIGN: as P1-P3, and in the three steps of P1-P3: (1) MDL_E_ARG, (2) every MDL_E_UNSUPPORTED, (3) MDL_E_ALIGN.  All of
+ * it is checked before anything is launched. */
 #define MDL_LOGIT_MAX_TRAIN 16384
 #define MDL_LOGIT_MAX_DIM 1024
 #define MDL_LOGIT_CG_MAX 400
@@ -1166,7 +1175,8 @@ int mdl_retrieval(const float* Q, int64_t ldq, const float* K, int64_t ldk, int6
  * Workspaces: 16-byte aligned, sizes from the *_ws_bytes queries, contents need no initialisation.
  * MDL_E_UNSUPPORTED: n_max > MDL_COX_MAX_TRAIN, S > MDL_PROBE_MAX_CASES (metrics), a launch grid or an output index beyond int32.
  * MDL_E_ARG: null pointers, ldX < d, sizes < 1, ldt / lde not 0 or >= S, max_iter < 0, cost <= 0, gtol < 0.  MDL_E_ALIGN: ws not
- * 16-byte, c_index_out / chi2_out not 8-byte aligned.  All of it is checked before anything is launched. */
+ * 16-byte, c_index_out / chi2_out not 8-byte aligned.  All of it is checked before anything is launched, in the three steps of P1-P3:
+ * (1) every MDL_E_ARG, (2) every MDL_E_UNSUPPORTED, the int32 bounds of the launch grids included, (3) MDL_E_ALIGN. */
 #define MDL_COX_MAX_TRAIN 1024
 #define MDL_COX_CG_MAX 400
 #define MDL_COX_LS_MAX 24

@@ -54,7 +54,8 @@
  * Pairs are counted per replicate (a workgroup per problem and MDL_BOOT_REP_BLOCK replicates, the problem's cases in LDS), which caps
  * the cohort: the test set is known on the device only, so the cap is on its bound S <= MDL_BOOT_SURV_MAX_TEST.  No workspace.
  *
- * Refusals, in this order, all before any launch and before any device pointer is touched.
+ * Refusals, in this order, all before any launch and before any device pointer is touched (the order of every entry point that takes
+ * a problem list: P1-P3 of madeleine_amd.h state it for the probes).
  *   (1) MDL_E_ARG: a NULL pointer; G, P, n_max or S < 1; R < 0; ldy / ldt / lde neither 0 nor >= S.
  *   (2) MDL_E_UNSUPPORTED: S > MDL_PROBE_MAX_CASES (B3: S > MDL_BOOT_SURV_MAX_TEST); n_max > MDL_LOGIT_MAX_TRAIN (B3: MDL_COX_MAX_TRAIN);
  *       C outside [2, MDL_PROBE_MAX_CLASSES]; G, P, P * n_max, R + 1 or a launch grid beyond int32.  Within these limits no count can

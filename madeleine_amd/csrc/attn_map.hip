@@ -25,8 +25,6 @@ constexpr int AM_RADIX = 256;
 static_assert(MDL_ATTN_ROWS == MDL_ATTN_SORT_KEYS, "the softmax and the sort share the chunk table");
 static_assert(AM_C % AM_THREADS == 0 && AM_C % WAVE == 0 && AM_THREADS == AM_RADIX, "chunk geometry");
 
-inline bool i32(int64_t v) { return v >= 0 && v <= 0x7FFFFFFFLL; }
-inline int64_t up16(int64_t b) { return (b + 15) & ~(int64_t)15; }
 
 // The workspace, carved in one place for the size query and both entry points.
 struct Ws {
@@ -372,7 +370,6 @@ __global__ __launch_bounds__(AM_THREADS) void am_topk_kernel(Plan p, const float
     topk_val[g] = v;
 }
 
-inline bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
 
 // The refusals the two entry points share, in the header's order; `grid` is the widest launch the call needs beyond the chunk grid.
 int check_call(const float* scores, int64_t ld, const int64_t* cu, int64_t T, int64_t R, int H, const void* ws) {
@@ -406,7 +403,8 @@ extern "C" int mdl_attn_softmax(const float* scores, int64_t ld, const int64_t* 
                                 float* l, void* ws, void* stream) {
     if (!attn || !m || !l) return MDL_E_ARG;
     if (const int rc = check_call(scores, ld, cu, T, R, H, ws)) return rc;
-    if (!host_aligned16(ws) || misaligned(cu, 8) || misaligned(scores, 4) || misaligned(attn, 4) || misaligned(m, 4) || misaligned(l, 4))
+    if (!host_aligned16(ws) || !aligned_to(cu, 8) || !aligned_to(scores, 4) || !aligned_to(attn, 4) || !aligned_to(m, 4) ||
+        !aligned_to(l, 4))
         return MDL_E_ALIGN;
     if (R == 0 || T == 0) return MDL_OK;
     const Ws w = carve(ws, T, R, H);
@@ -426,8 +424,8 @@ extern "C" int mdl_attn_rank(const float* scores, int64_t ld, const int64_t* cu,
     if (!order || k < 0 || (k > 0 && (!topk_idx || !topk_val))) return MDL_E_ARG;
     if (const int rc = check_call(scores, ld, cu, T, R, H, ws)) return rc;
     if (!i32(k) || (k > 0 && R * H > 0x7FFFFFFFLL * AM_THREADS / k)) return MDL_E_UNSUPPORTED;      // the top-k grid
-    if (!host_aligned16(ws) || misaligned(cu, 8) || misaligned(scores, 4) || misaligned(order, 4) || misaligned(pct, 4) ||
-        misaligned(topk_idx, 4) || misaligned(topk_val, 4))
+    if (!host_aligned16(ws) || !aligned_to(cu, 8) || !aligned_to(scores, 4) || !aligned_to(order, 4) || !aligned_to(pct, 4) ||
+        !aligned_to(topk_idx, 4) || !aligned_to(topk_val, 4))
         return MDL_E_ALIGN;
     if (R == 0 || T == 0) return MDL_OK;
     const Ws w = carve(ws, T, R, H);

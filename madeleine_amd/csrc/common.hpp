@@ -35,6 +35,10 @@ __device__ __forceinline__ void st4(bf16_t* p, f32x4 v) { *reinterpret_cast<bf16
 
 __device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool host_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// host-side argument checks: alignment to a power of two (NULL is aligned), a count or launch grid within int32, bytes rounded up to 16
+inline bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+inline bool i32(int64_t v) { return v >= 0 && v <= 0x7FFFFFFF; }
+inline int64_t up16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
 
 // A row stride that enters a 32-bit byte offset (the per-lane offset of an LDS-DMA in the saddr form, the lane part of an epilogue
 // address): `stride` in elements of `elem_bytes` bytes, `rows` = the furthest row that expression reaches from its 64-bit base,

@@ -38,8 +38,6 @@ struct Canvas {
     int W, H;
 };
 
-inline bool i32(int64_t v) { return v >= 0 && v <= 0x7FFFFFFFLL; }
-inline int64_t up16(int64_t b) { return (b + 15) & ~(int64_t)15; }
 __host__ __device__ __forceinline__ int tiles_of(int n) { return (n + HV_TILE - 1) / HV_TILE; }
 
 // 0: the record holds; MDL_E_ARG / MDL_E_UNSUPPORTED as the header states.  The host refuses the call with it, the device serves the
@@ -278,7 +276,6 @@ __global__ __launch_bounds__(HV_THREADS) void hv_blur_cols_kernel(const int32_t*
     }
 }
 
-inline bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
 
 // The refusals of the three sizes the query and the entry point share.
 int check_sizes(int64_t P, int64_t R, int C) {
@@ -341,8 +338,8 @@ static int heat_render(const int32_t* xy, const int64_t* cu, const float* values
         widest = fw * fh > widest ? fw * fh : widest;
     }
     if (!i32(n_tiles)) return MDL_E_UNSUPPORTED;
-    if (!host_aligned16(ws) || misaligned(cu, 8) || misaligned(bag, 8) || misaligned(bag_host, 8) || misaligned(xy, 4) ||
-        misaligned(values, 4) || misaligned(taps_host, 4) || misaligned(rgba, 4) || misaligned(level, 2))
+    if (!host_aligned16(ws) || !aligned_to(cu, 8) || !aligned_to(bag, 8) || !aligned_to(bag_host, 8) || !aligned_to(xy, 4) ||
+        !aligned_to(values, 4) || !aligned_to(taps_host, 4) || !aligned_to(rgba, 4) || !aligned_to(level, 2))
         return MDL_E_ALIGN;
     if (R == 0 || P == 0) return MDL_OK;
     int lane_shift = 0;

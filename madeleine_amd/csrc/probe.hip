@@ -20,8 +20,7 @@
 // mdl_logit_metrics (L2 of the header) is the same three metrics kernels behind a launcher that accepts problem tables of up to
 // MDL_LOGIT_MAX_TRAIN columns; the fits of that width are in probe_primal.hip.
 // No workgroup waits on another; every loop has a bound that is an argument or a constant of the header.
-#include "common.hpp"
-#include "probe_score.hpp"
+#include "probe_host.hpp"
 
 namespace mdl {
 namespace {
@@ -29,33 +28,26 @@ namespace {
 constexpr int PB_THREADS = 256;
 constexpr int PB_WAVES = PB_THREADS / WAVE;
 constexpr int PB_NMAX = MDL_PROBE_MAX_TRAIN;
-constexpr int PB_CMAX = MDL_PROBE_MAX_CLASSES;
-constexpr int PB_TILE = 64;             // Gram tile
-constexpr int PB_KC = 32;               // Gram k-chunk
-constexpr float PB_CG_TOL2 = 1e-4f;     // CG stops at |residual|^2 <= 1e-4 |rhs|^2 (forcing term 1e-2)
-constexpr float PB_TIGHT = 0.03f;       // the Newton iteration aims at PB_TIGHT * gtol; `converged` reports the residual against gtol
+constexpr int PB_CMAX = PROBE_CMAX;
 static_assert(PB_NMAX == PB_THREADS, "the fit kernel gives one thread to each training row");
-
-__host__ __device__ __forceinline__ int cols_of(int C) { return C == 2 ? 1 : C; }
-__host__ __device__ __forceinline__ int ldg_of(int n_max) { return (n_max + PB_TILE - 1) / PB_TILE * PB_TILE; }
 
 // ---- Gram -------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(PB_THREADS) void probe_gram_kernel(const float* __restrict__ X, int64_t ldX, int S, int d,
                                                                 const int32_t* __restrict__ train_idx,
                                                                 const int32_t* __restrict__ n_train, int n_max, int ldg,
                                                                 float* __restrict__ G) {
-    const int tps = ldg / PB_TILE;
+    const int tps = ldg / GRAM_TILE;
     const int p = blockIdx.x / (tps * tps), tile = blockIdx.x % (tps * tps);
     const int ti = tile / tps, tj = tile % tps;
     int n = n_train[p];
     if (n < 0 || n > n_max) n = 0;                    // a refused problem: the fit kernel never reads its G
-    if (ti * PB_TILE >= n || tj * PB_TILE >= n) return;
-    __shared__ float sA[PB_KC][PB_TILE + 1], sB[PB_KC][PB_TILE + 1];
-    __shared__ int64_t s_off[2][PB_TILE];             // element offset of the tile's rows in X, -1: a zero row
+    if (ti * GRAM_TILE >= n || tj * GRAM_TILE >= n) return;
+    __shared__ float sA[GRAM_KC][GRAM_TILE + 1], sB[GRAM_KC][GRAM_TILE + 1];
+    __shared__ int64_t s_off[2][GRAM_TILE];           // element offset of the tile's rows in X, -1: a zero row
     const int tid = threadIdx.x;
-    if (tid < 2 * PB_TILE) {
-        const int side = tid / PB_TILE, r = tid % PB_TILE;
-        const int row = (side ? tj : ti) * PB_TILE + r;
+    if (tid < 2 * GRAM_TILE) {
+        const int side = tid / GRAM_TILE, r = tid % GRAM_TILE;
+        const int row = (side ? tj : ti) * GRAM_TILE + r;
         int64_t off = -1;
         if (row < n) {
             const int idx = train_idx[(int64_t)p * n_max + row];
@@ -64,110 +56,10 @@ __global__ __launch_bounds__(PB_THREADS) void probe_gram_kernel(const float* __r
         s_off[side][r] = off;
     }
     __syncthreads();
-    const int tx = tid % 16, ty = tid / 16;
-    float acc[4][4] = {};
-    for (int k0 = 0; k0 < d; k0 += PB_KC) {
-#pragma unroll
-        for (int q = 0; q < PB_TILE * PB_KC / PB_THREADS; ++q) {
-            const int e = q * PB_THREADS + tid, r = e / PB_KC, kk = e % PB_KC;
-            const bool in = k0 + kk < d;
-            const int64_t oa = s_off[0][r], ob = s_off[1][r];
-            sA[kk][r] = (in && oa >= 0) ? X[oa + k0 + kk] : 0.f;
-            sB[kk][r] = (in && ob >= 0) ? X[ob + k0 + kk] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll 8
-        for (int kk = 0; kk < PB_KC; ++kk) {
-            float a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                a[u] = sA[kk][ty + 16 * u];
-                b[u] = sB[kk][tx + 16 * u];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) acc[u][v] = fmaf(a[u], b[v], acc[u][v]);
-        }
-        __syncthreads();
-    }
-    float* Gp = G + (int64_t)p * ldg * ldg;
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) Gp[(int64_t)(ti * PB_TILE + ty + 16 * u) * ldg + tj * PB_TILE + tx + 16 * v] = acc[u][v];
+    gram_tile<PB_THREADS>(X, d, s_off, sA, sB, G + (int64_t)p * ldg * ldg, ldg, ti, tj);
 }
 
 // ---- fit --------------------------------------------------------------------------------------------------------------------------
-// Sum of K per-thread values over the workgroup in one fixed order (xor butterflies, then the four waves left to right); every thread
-// returns the same bits.  Two barriers: the scratch may be reused at once.
-template <int K>
-__device__ __forceinline__ void block_sum(float (&v)[K], float (*s_red)[PB_CMAX + 3]) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
-    if ((tid & (WAVE - 1)) == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) s_red[tid / WAVE][k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = (s_red[0][k] + s_red[1][k]) + (s_red[2][k] + s_red[3][k]);
-    __syncthreads();
-}
-
-__device__ __forceinline__ float block_max(float v, float (*s_red)[PB_CMAX + 3]) {
-    const int tid = threadIdx.x;
-    v = wave_max(v);
-    if ((tid & (WAVE - 1)) == 0) s_red[tid / WAVE][0] = v;
-    __syncthreads();
-    v = fmaxf(fmaxf(s_red[0][0], s_red[1][0]), fmaxf(s_red[2][0], s_red[3][0]));
-    __syncthreads();
-    return v;
-}
-
-// d loss / d f of one training row at decision values f (r = p - onehot) and what the Hessian needs: binary w[0] = p (1 - p),
-// multinomial w = p.
-template <int NC>
-__device__ __forceinline__ void row_residual(const float (&f)[NC], int cols, int label, float (&r)[NC], float (&w)[NC]) {
-    if (cols == 1) {
-        const float s = label ? 1.f : -1.f;
-        const float q = 1.f / (1.f + expf(s * f[0]));       // sigmoid(-s f): 0 when s f overflows
-        r[0] = -s * q;
-        w[0] = q * (1.f - q);
-    } else {
-        float m = f[0];
-#pragma unroll
-        for (int c = 1; c < NC; ++c)
-            if (c < cols) m = fmaxf(m, f[c]);
-        float sum = 0.f;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            w[c] = c < cols ? expf(f[c] - m) : 0.f;
-            sum += w[c];
-        }
-        const float inv = 1.f / sum;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            w[c] *= inv;
-            r[c] = w[c] - (c == label ? 1.f : 0.f);
-        }
-    }
-}
-
-// (D q) of one row: the loss Hessian with respect to its decision values, applied to q
-template <int NC>
-__device__ __forceinline__ void row_hess(const float (&w)[NC], int cols, const float (&q)[NC], float (&out)[NC]) {
-    if (cols == 1) {
-        out[0] = w[0] * q[0];
-    } else {
-        float pq = 0.f;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) pq = fmaf(w[c], q[c], pq);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) out[c] = w[c] * (q[c] - pq);
-    }
-}
-
 // out[c] (column j of X_t^T V) for the columns j = tid, tid + 256, ... handed to `sink`; V = s_v [n][NC]
 template <int NC, class Sink>
 __device__ __forceinline__ void xt_times(const float* __restrict__ X, const int64_t* s_off, int n, int d, const float* s_v, Sink sink) {
@@ -278,14 +170,14 @@ __global__ __launch_bounds__(PB_THREADS) void probe_fit_kernel(const float* __re
         float gb[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) gb[c] = cost * r[c];
-        block_sum<NC>(gb, s_red);                   // its barriers also free s_v
+        block_sum<NC, PB_WAVES>(gb, s_red);                   // its barriers also free s_v
 #pragma unroll
         for (int c = 0; c < NC; ++c) gmax = fmaxf(gmax, fabsf(gb[c]));
-        res = block_max(gmax, s_red);
+        res = block_max<PB_WAVES>(gmax, s_red);
         // The internal stop is tighter than gtol: Newton's last steps square the residual, and stopping at the first residual below
         // gtol leaves the decision values of a k = 1 problem 3e-3 (relative) off the optimum.  Below gtol the iteration also ends as
         // soon as a step no longer halves the residual (the fp32 floor).
-        if (res <= PB_TIGHT * gtol || (res <= gtol && res >= 0.5f * prev)) break;
+        if (res <= PROBE_TIGHT * gtol || (res <= gtol && res >= 0.5f * prev)) break;
         if (it >= max_iter || !(res == res)) break;
         prev = res;
 
@@ -318,7 +210,7 @@ __global__ __launch_bounds__(PB_THREADS) void probe_fit_kernel(const float* __re
             float s[1] = {0.f};
 #pragma unroll
             for (int c = 0; c < NC; ++c) s[0] = fmaf(va[c], Gva[c], s[0]);
-            block_sum<1>(s, s_red);
+            block_sum<1, PB_WAVES>(s, s_red);
 #pragma unroll
             for (int c = 0; c < NC; ++c) s[0] = fmaf(vb[c], vb[c], s[0]);
             return s[0];
@@ -345,7 +237,7 @@ __global__ __launch_bounds__(PB_THREADS) void probe_fit_kernel(const float* __re
                 red[c] = Dq[c];
                 red[NC] = fmaf(Gpd[c], Ma[c], red[NC]);
             }
-            block_sum<NC + 1>(red, s_red);
+            block_sum<NC + 1, PB_WAVES>(red, s_red);
             float pMp = red[NC];
 #pragma unroll
             for (int c = 0; c < NC; ++c) pMp = fmaf(pb[c], cost * red[c], pMp);
@@ -362,7 +254,7 @@ __global__ __launch_bounds__(PB_THREADS) void probe_fit_kernel(const float* __re
             }
             g_times(ra, Gr);
             const float rho_new = norm2(ra, Gr, rb);
-            if (!(rho_new > PB_CG_TOL2 * rho0)) break;
+            if (!(rho_new > PROBE_CG_TOL2 * rho0)) break;
             const float beta = rho_new / rho;
             rho = rho_new;
 #pragma unroll
@@ -382,7 +274,7 @@ __global__ __launch_bounds__(PB_THREADS) void probe_fit_kernel(const float* __re
             lin[1] = fmaf(xa[c], xw[c], lin[1]);
             lin[2] = fmaf(xa[c], Gx[c], lin[2]);
         }
-        block_sum<3>(lin, s_red);
+        block_sum<3, PB_WAVES>(lin, s_red);
         const float dphi0 = lin[0] + lin[1];
         if (!(dphi0 < 0.f)) break;                  // no descent left in fp32: stop here, unconverged
         float t = 1.f;
@@ -396,7 +288,7 @@ __global__ __launch_bounds__(PB_THREADS) void probe_fit_kernel(const float* __re
                 for (int c = 0; c < NC; ++c)
                     if (c < cols) s[0] = fmaf(cost * rt[c], df[c], s[0]);
             }
-            block_sum<1>(s, s_red);
+            block_sum<1, PB_WAVES>(s, s_red);
             const float dphi = s[0] + lin[1] + t * lin[2];
             if (dphi <= -0.5f * dphi0) break;
             t *= 0.5f;
@@ -460,17 +352,16 @@ __global__ __launch_bounds__(PB_THREADS) void probe_scores_kernel(const float* _
 }
 
 // ---- metrics ----------------------------------------------------------------------------------------------------------------------
-// workspace: tcls [P][S8] int8 (test class, -1: not a test case), cnt [P][PB_CMAX] uint64, score [P][C][S] double (C > 2 only)
-__host__ __device__ __forceinline__ int64_t s8_of(int64_t S) { return (S + 15) / 16 * 16; }
+// workspace: tcls [P][S16] int8 (test class, -1: not a test case), cnt [P][PB_CMAX] uint64, score [P][C][S] double (C > 2 only)
 struct MetricsWs {
     int8_t* tcls;
     unsigned long long* cnt;
     double* score;
 };
-__host__ __device__ __forceinline__ MetricsWs metrics_ws(void* ws, int64_t P, int64_t S) {
+inline MetricsWs metrics_ws(void* ws, int64_t P, int64_t S) {
     MetricsWs m;
     m.tcls = reinterpret_cast<int8_t*>(ws);
-    m.cnt = reinterpret_cast<unsigned long long*>(m.tcls + P * s8_of(S));
+    m.cnt = reinterpret_cast<unsigned long long*>(m.tcls + P * s16_of(S));
     m.score = reinterpret_cast<double*>(m.cnt + P * PB_CMAX);
     return m;
 }
@@ -487,12 +378,7 @@ __global__ __launch_bounds__(PB_THREADS) void probe_prepare_kernel(const float* 
     if (tid < PB_CMAX * PB_CMAX) s_conf[tid] = 0;
     for (int s = tid; s < S; s += PB_THREADS) tcls[s] = probe_test_class(yp[s], C);
     __syncthreads();
-    int n = n_train[p];
-    n = n < 0 ? 0 : (n > n_max ? n_max : n);
-    for (int i = tid; i < n; i += PB_THREADS) {
-        const int idx = train_idx[(int64_t)p * n_max + i];
-        if (idx >= 0 && idx < S) tcls[idx] = (int8_t)-1;
-    }
+    strike_training<PB_THREADS>(tcls, train_idx, n_train, p, n_max, S);
     __syncthreads();
     for (int s = tid; s < S; s += PB_THREADS) {
         const int t = tcls[s];
@@ -575,16 +461,10 @@ __global__ __launch_bounds__(PB_THREADS) void probe_auc_kernel(const int32_t* __
     auc[p] = (float)(out / (double)ncls);
 }
 
-inline bool i32(int64_t v) { return v >= 0 && v <= 0x7FFFFFFF; }
-
-// shared argument checks of the entry points that take the problem list
-inline int check_problems(int64_t P, int n_max, int64_t S, int C, int64_t ldy, int n_limit = PB_NMAX) {
-    if (P < 1 || n_max < 1 || S < 1) return MDL_E_ARG;
-    if (ldy != 0 && ldy < S) return MDL_E_ARG;
-    if (n_max > n_limit || C < 2 || C > PB_CMAX) return MDL_E_UNSUPPORTED;
-    if (!i32(S) || !i32(P) || !i32(P * n_max)) return MDL_E_UNSUPPORTED;
-    return MDL_OK;
-}
+// the limits of the entry points: {n_max, d, S, fit, classes}
+constexpr ProbeLimits PROBE_FIT = {PB_NMAX, PROBE_NO_LIMIT, PROBE_NO_LIMIT, true, true};
+constexpr ProbeLimits PROBE_METRICS = {PB_NMAX, PROBE_NO_LIMIT, MDL_PROBE_MAX_CASES, false, true};
+constexpr ProbeLimits LOGIT_METRICS = {MDL_LOGIT_MAX_TRAIN, PROBE_NO_LIMIT, MDL_PROBE_MAX_CASES, false, true};
 
 }  // namespace
 }  // namespace mdl
@@ -592,78 +472,72 @@ inline int check_problems(int64_t P, int n_max, int64_t S, int C, int64_t ldy, i
 using namespace mdl;
 
 extern "C" int64_t mdl_probe_fit_ws_bytes(int64_t P, int n_max, int d, int C) {
-    if (P < 1 || n_max < 1 || d < 1) return MDL_E_ARG;
-    if (n_max > PB_NMAX || C < 2 || C > PB_CMAX || !i32(P)) return MDL_E_UNSUPPORTED;
-    const int64_t ldg = ldg_of(n_max);
+    if (const int rc = probe_check(probe_sizes(P, n_max, 1, C, d), PROBE_FIT, nullptr)) return rc;
+    const int64_t ldg = gram_ld(n_max);
     return P * ldg * ldg * (int64_t)sizeof(float);
 }
 
 extern "C" int mdl_probe_fit(const float* X, int64_t ldX, int64_t S, int d, const int32_t* y, int64_t ldy, const int32_t* train_idx,
                              const int32_t* n_train, int64_t P, int n_max, int C, float cost, float gtol, int max_iter, float* W_out,
                              float* b_out, float* info_out, void* ws, void* stream) {
-    if (!X || !y || !train_idx || !n_train || !W_out || !b_out || !info_out || !ws) return MDL_E_ARG;
-    if (d < 1 || ldX < d || max_iter < 0 || !(cost > 0.f) || !(gtol >= 0.f)) return MDL_E_ARG;
-    if (const int rc = check_problems(P, n_max, S, C, ldy)) return rc;
-    if (!host_aligned16(ws)) return MDL_E_ALIGN;
-    const int ldg = ldg_of(n_max), tps = ldg / PB_TILE, cols = cols_of(C);
-    if (!i32(P * tps * tps) || !i32(P * (int64_t)cols * d)) return MDL_E_UNSUPPORTED;
+    const ProbeTable t = {train_idx, n_train, P, n_max, S, {{y, ldy}}, 1, C, d};
+    const int64_t ldg = gram_ld(n_max), tps = ldg / GRAM_TILE;
+    const int cols = cols_of(C);
+    const ProbeExtra extra = {all_given(X, W_out, b_out, info_out, ws), mul_i32(P, tps, tps) && mul_i32(P, cols, d), host_aligned16(ws), 0,
+                              ldX, max_iter, cost, gtol};
+    if (const int rc = probe_check(t, PROBE_FIT, &extra)) return rc;
     float* G = reinterpret_cast<float*>(ws);
     hipLaunchKernelGGL(probe_gram_kernel, dim3((unsigned)(P * tps * tps)), dim3(PB_THREADS), 0, (hipStream_t)stream, X, ldX, (int)S, d,
-                       train_idx, n_train, n_max, ldg, G);
+                       train_idx, n_train, n_max, (int)ldg, G);
     MDL_LAUNCH_CHECK();
-#define MDL_PROBE_FIT(NC)                                                                                                            \
-    hipLaunchKernelGGL(probe_fit_kernel<NC>, dim3((unsigned)P), dim3(PB_THREADS), 0, (hipStream_t)stream, X, ldX, (int)S, d, y, ldy, \
-                       train_idx, n_train, n_max, C, cost, gtol, max_iter, W_out, b_out, info_out, (const float*)G, ldg)
-    if (cols == 1) MDL_PROBE_FIT(1);
-    else if (cols <= 4) MDL_PROBE_FIT(4);
-    else MDL_PROBE_FIT(8);
-#undef MDL_PROBE_FIT
+    for_nc(cols, [&](auto nc) {
+        hipLaunchKernelGGL(probe_fit_kernel<decltype(nc)::value>, dim3((unsigned)P), dim3(PB_THREADS), 0, (hipStream_t)stream, X, ldX,
+                           (int)S, d, y, ldy, train_idx, n_train, n_max, C, cost, gtol, max_iter, W_out, b_out, info_out, (const float*)G,
+                           (int)ldg);
+        return MDL_OK;
+    });
     MDL_LAUNCH_CHECK();
     return MDL_OK;
 }
 
 extern "C" int mdl_probe_scores(const float* X, int64_t ldX, int64_t S, int d, const float* W, const float* b, int64_t P, int C,
                                 float* z_out, void* stream) {
-    if (!X || !W || !b || !z_out) return MDL_E_ARG;
+    if (!all_given(X, W, b, z_out)) return MDL_E_ARG;
     if (d < 1 || ldX < d || P < 1 || S < 1) return MDL_E_ARG;
     if (C < 2 || C > PB_CMAX) return MDL_E_UNSUPPORTED;
     const int cols = cols_of(C);
-    const int64_t tiles = (S + PB_WAVES * SC_ROWS - 1) / (PB_WAVES * SC_ROWS);
-    if (!i32(S) || !i32(P) || !i32(P * tiles) || !i32(P * (int64_t)cols * d)) return MDL_E_UNSUPPORTED;
-#define MDL_PROBE_SCORES(NC)                                                                                                      \
-    hipLaunchKernelGGL(probe_scores_kernel<NC>, dim3((unsigned)(P * tiles)), dim3(PB_THREADS), 0, (hipStream_t)stream, X, ldX, (int)S, \
-                       d, W, b, cols, (int)tiles, z_out)
-    if (cols == 1) MDL_PROBE_SCORES(1);
-    else if (cols <= 4) MDL_PROBE_SCORES(4);
-    else MDL_PROBE_SCORES(8);
-#undef MDL_PROBE_SCORES
+    const int64_t tiles = ceil_div(S, PB_WAVES * SC_ROWS);
+    if (!i32(S) || !mul_i32(P, tiles) || !mul_i32(P, cols, d)) return MDL_E_UNSUPPORTED;
+    for_nc(cols, [&](auto nc) {
+        hipLaunchKernelGGL(probe_scores_kernel<decltype(nc)::value>, dim3((unsigned)(P * tiles)), dim3(PB_THREADS), 0, (hipStream_t)stream, X,
+                           ldX, (int)S, d, W, b, cols, (int)tiles, z_out);
+        return MDL_OK;
+    });
     MDL_LAUNCH_CHECK();
     return MDL_OK;
 }
 
 extern "C" int64_t mdl_probe_metrics_ws_bytes(int64_t P, int64_t S, int C) {
-    if (P < 1 || S < 1) return MDL_E_ARG;
-    if (C < 2 || C > PB_CMAX || S > MDL_PROBE_MAX_CASES || !i32(P)) return MDL_E_UNSUPPORTED;
-    return P * s8_of(S) + P * PB_CMAX * (int64_t)sizeof(unsigned long long) + (C > 2 ? P * C * S * (int64_t)sizeof(double) : 0);
+    if (const int rc = probe_check(probe_sizes(P, 1, S, C, 0), PROBE_METRICS, nullptr)) return rc;
+    return P * s16_of(S) + P * PB_CMAX * (int64_t)sizeof(unsigned long long) + (C > 2 ? P * C * S * (int64_t)sizeof(double) : 0);
 }
 
 // the three metrics launches behind mdl_probe_metrics and mdl_logit_metrics, which differ in the widest problem table they accept
 static int launch_metrics(const float* z, const int32_t* y, int64_t ldy, const int32_t* train_idx, const int32_t* n_train, int64_t P,
-                          int n_max, int n_limit, int64_t S, int C, int32_t* confusion_out, float* auc_out, void* ws, void* stream) {
-    if (!z || !y || !train_idx || !n_train || !confusion_out || !auc_out || !ws) return MDL_E_ARG;
-    if (const int rc = check_problems(P, n_max, S, C, ldy, n_limit)) return rc;
-    if (S > MDL_PROBE_MAX_CASES) return MDL_E_UNSUPPORTED;
-    if (!host_aligned16(ws)) return MDL_E_ALIGN;
-    const int ncls = C == 2 ? 1 : C;
-    const int64_t slices = (S + PB_THREADS - 1) / PB_THREADS;
-    if (!i32(P * ncls * slices)) return MDL_E_UNSUPPORTED;
+                          int n_max, const ProbeLimits& lim, int64_t S, int C, int32_t* confusion_out, float* auc_out, void* ws,
+                          void* stream) {
+    const ProbeTable t = {train_idx, n_train, P, n_max, S, {{y, ldy}}, 1, C, 0};
+    const int ncls = cols_of(C);
+    const int64_t slices = ceil_div(S, PB_THREADS);
+    const ProbeExtra extra = {all_given(z, confusion_out, auc_out, ws), mul_i32(P, ncls, slices), host_aligned16(ws)};
+    if (const int rc = probe_check(t, lim, &extra)) return rc;
     const MetricsWs m = metrics_ws(ws, P, S);
-    const int64_t S8 = s8_of(S);
+    const int64_t S16 = s16_of(S);
     hipLaunchKernelGGL(probe_prepare_kernel, dim3((unsigned)P), dim3(PB_THREADS), 0, (hipStream_t)stream, z, y, ldy, train_idx, n_train,
-                       n_max, (int)S, C, confusion_out, m, S8);
+                       n_max, (int)S, C, confusion_out, m, S16);
     MDL_LAUNCH_CHECK();
     hipLaunchKernelGGL(probe_pairs_kernel, dim3((unsigned)(P * ncls * slices)), dim3(PB_THREADS), 0, (hipStream_t)stream, z, (int)S, C,
-                       (int)slices, m, S8);
+                       (int)slices, m, S16);
     MDL_LAUNCH_CHECK();
     hipLaunchKernelGGL(probe_auc_kernel, dim3((unsigned)((P + PB_THREADS - 1) / PB_THREADS)), dim3(PB_THREADS), 0, (hipStream_t)stream,
                        (const int32_t*)confusion_out, (int)P, C, m, auc_out);
@@ -673,12 +547,12 @@ static int launch_metrics(const float* z, const int32_t* y, int64_t ldy, const i
 
 extern "C" int mdl_probe_metrics(const float* z, const int32_t* y, int64_t ldy, const int32_t* train_idx, const int32_t* n_train,
                                  int64_t P, int n_max, int64_t S, int C, int32_t* confusion_out, float* auc_out, void* ws, void* stream) {
-    return launch_metrics(z, y, ldy, train_idx, n_train, P, n_max, PB_NMAX, S, C, confusion_out, auc_out, ws, stream);
+    return launch_metrics(z, y, ldy, train_idx, n_train, P, n_max, PROBE_METRICS, S, C, confusion_out, auc_out, ws, stream);
 }
 
 extern "C" int64_t mdl_logit_metrics_ws_bytes(int64_t P, int64_t S, int C) { return mdl_probe_metrics_ws_bytes(P, S, C); }
 
 extern "C" int mdl_logit_metrics(const float* z, const int32_t* y, int64_t ldy, const int32_t* train_idx, const int32_t* n_train,
                                  int64_t P, int n_max, int64_t S, int C, int32_t* confusion_out, float* auc_out, void* ws, void* stream) {
-    return launch_metrics(z, y, ldy, train_idx, n_train, P, n_max, MDL_LOGIT_MAX_TRAIN, S, C, confusion_out, auc_out, ws, stream);
+    return launch_metrics(z, y, ldy, train_idx, n_train, P, n_max, LOGIT_METRICS, S, C, confusion_out, auc_out, ws, stream);
 }

@@ -14,94 +14,21 @@
 //                      evaluated along the line from the stored f and df (O(n cols) per trial, no sweep), is no more than half as
 //                      steep uphill as it was downhill at 0.
 // No workgroup waits on another, no floating-point atomic, every sum in a fixed order; every loop has a bound that is an argument or a
-// constant of the header.  The loss helpers are those of probe.hip, restated here so that file's code objects do not change.
-#include "common.hpp"
+// constant of the header.  The loss helpers and the reductions are those of probe_common.hpp.
+#include "probe_host.hpp"
 
 namespace mdl {
 namespace {
 
 constexpr int LG_THREADS = 256;
 constexpr int LG_WAVES = LG_THREADS / WAVE;
-constexpr int LG_CMAX = MDL_PROBE_MAX_CLASSES;
-constexpr float LG_CG_TOL2 = 1e-4f;     // CG stops at |residual|^2 <= 1e-4 |rhs|^2 (forcing term 1e-2)
-constexpr float LG_TIGHT = 0.03f;       // the Newton iteration aims at LG_TIGHT * gtol; `converged` reports the residual against gtol
-static_assert(LG_WAVES == 4, "block_sum and the sweep's combine add four waves");
+constexpr int LG_CMAX = PROBE_CMAX;
+static_assert(LG_WAVES == 4, "the sweep's combine adds four waves");
 
-__host__ __device__ __forceinline__ int lg_cols_of(int C) { return C == 2 ? 1 : C; }
-__host__ __device__ constexpr int lg_nc_of(int cols) { return cols == 1 ? 1 : (cols <= 4 ? 4 : 8); }      // columns a kernel is built for
 __host__ __device__ __forceinline__ int64_t lg_npad_of(int n_max) { return ((int64_t)n_max + 3) / 4 * 4; }
 // rows a wave holds in registers at a time, by the number of 64-column chunks of a row (and one row where the accumulators alone
 // take 96 registers or more)
 __host__ __device__ constexpr int lg_rows_of(int NC, int DK) { return NC * DK >= 96 ? 1 : (DK <= 2 ? 8 : (DK <= 8 ? 4 : 2)); }
-
-// Sum of K per-thread values over the workgroup in one fixed order (xor butterflies, then the four waves left to right); every thread
-// returns the same bits.  Two barriers: the scratch may be reused at once.
-template <int K>
-__device__ __forceinline__ void lg_block_sum(float (&v)[K], float (*s_red)[LG_CMAX + 3]) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
-    if ((tid & (WAVE - 1)) == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) s_red[tid / WAVE][k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = (s_red[0][k] + s_red[1][k]) + (s_red[2][k] + s_red[3][k]);
-    __syncthreads();
-}
-
-__device__ __forceinline__ float lg_block_max(float v, float (*s_red)[LG_CMAX + 3]) {
-    const int tid = threadIdx.x;
-    v = wave_max(v);
-    if ((tid & (WAVE - 1)) == 0) s_red[tid / WAVE][0] = v;
-    __syncthreads();
-    v = fmaxf(fmaxf(s_red[0][0], s_red[1][0]), fmaxf(s_red[2][0], s_red[3][0]));
-    __syncthreads();
-    return v;
-}
-
-// d loss / d f of one training row at decision values f (r = p - onehot) and what the Hessian needs: binary w[0] = p (1 - p),
-// multinomial w = p.
-template <int NC>
-__device__ __forceinline__ void lg_row_residual(const float (&f)[NC], int cols, int label, float (&r)[NC], float (&w)[NC]) {
-    if (cols == 1) {
-        const float s = label ? 1.f : -1.f;
-        const float q = 1.f / (1.f + expf(s * f[0]));       // sigmoid(-s f): 0 when s f overflows
-        r[0] = -s * q;
-        w[0] = q * (1.f - q);
-    } else {
-        float m = f[0];
-#pragma unroll
-        for (int c = 1; c < NC; ++c)
-            if (c < cols) m = fmaxf(m, f[c]);
-        float sum = 0.f;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            w[c] = c < cols ? expf(f[c] - m) : 0.f;
-            sum += w[c];
-        }
-        const float inv = 1.f / sum;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            w[c] *= inv;
-            r[c] = w[c] - (c == label ? 1.f : 0.f);
-        }
-    }
-}
-
-// (D q) of one row: the loss Hessian with respect to its decision values, applied to q
-template <int NC>
-__device__ __forceinline__ void lg_row_hess(const float (&w)[NC], int cols, const float (&q)[NC], float (&out)[NC]) {
-    if (cols == 1) {
-        out[0] = w[0] * q[0];
-    } else {
-        float pq = 0.f;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) pq = fmaf(w[c], q[c], pq);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) out[c] = w[c] * (q[c] - pq);
-    }
-}
 
 enum { SW_GRAD = 0, SW_HESS = 1, SW_DOT = 2 };
 
@@ -165,7 +92,7 @@ __device__ __forceinline__ void lg_sweep(const LogitRows& rows, float cost, cons
                 } else {
                     if (MODE == SW_GRAD) {
                         float r[NC], w[NC];
-                        lg_row_residual<NC>(z, cols, rows.y[rows.tidx[i]], r, w);
+                        row_residual<NC>(z, cols, rows.y[rows.tidx[i]], r, w);
                         if (lane == 0)
 #pragma unroll
                             for (int c = 0; c < NC; ++c)
@@ -179,7 +106,7 @@ __device__ __forceinline__ void lg_sweep(const LogitRows& rows, float cost, cons
                         float w[NC], Dq[NC];
 #pragma unroll
                         for (int c = 0; c < NC; ++c) w[c] = c < cols ? rows.w[(int64_t)i * cols + c] : 0.f;
-                        lg_row_hess<NC>(w, cols, z, Dq);
+                        row_hess<NC>(w, cols, z, Dq);
 #pragma unroll
                         for (int c = 0; c < NC; ++c) u[c] = c < cols ? cost * Dq[c] : 0.f;
                     }
@@ -230,7 +157,7 @@ __global__ __launch_bounds__(LG_THREADS) void logit_fit_kernel(const float* __re
     extern __shared__ float s_dyn[];
     __shared__ float s_red[LG_WAVES][LG_CMAX + 3];
     const int tid = threadIdx.x;
-    const int p = blockIdx.x, cols = lg_cols_of(C);
+    const int p = blockIdx.x, cols = cols_of(C);
     const int L = d * NC;                           // vectors are [d, NC] in LDS and registers: element j * NC + c, zero at c >= cols
     float* s_v = s_dyn;
     float* s_out = s_dyn + L;
@@ -290,9 +217,9 @@ __global__ __launch_bounds__(LG_THREADS) void logit_fit_kernel(const float* __re
         }
 #pragma unroll
         for (int c = 0; c < NC; ++c) gmax = fmaxf(gmax, fabsf(gb[c]));
-        res = lg_block_max(gmax, s_red);
-        // the stop rule of probe_fit_kernel: aim at LG_TIGHT * gtol, and below gtol end as soon as a step no longer halves the residual
-        if (res <= LG_TIGHT * gtol || (res <= gtol && res >= 0.5f * prev)) break;
+        res = block_max<LG_WAVES>(gmax, s_red);
+        // the stop rule of probe_fit_kernel: aim at PROBE_TIGHT * gtol, and below gtol end as soon as a step no longer halves the residual
+        if (res <= PROBE_TIGHT * gtol || (res <= gtol && res >= 0.5f * prev)) break;
         if (it >= max_iter || !(res == res)) break;
         prev = res;
 
@@ -304,7 +231,7 @@ __global__ __launch_bounds__(LG_THREADS) void logit_fit_kernel(const float* __re
             part[0] = fmaf(rr[m], rr[m], part[0]);
             if (tid + LG_THREADS * m < L) s_v[tid + LG_THREADS * m] = rr[m];
         }
-        lg_block_sum<1>(part, s_red);               // its barriers also publish s_v
+        block_sum<1, LG_WAVES>(part, s_red);               // its barriers also publish s_v
         float rho = part[0];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -323,7 +250,7 @@ __global__ __launch_bounds__(LG_THREADS) void logit_fit_kernel(const float* __re
                 const float pe = e < L ? s_v[e] : 0.f;
                 part[0] = fmaf(pe, e < L ? pe + s_out[e] : 0.f, part[0]);
             }
-            lg_block_sum<1>(part, s_red);
+            block_sum<1, LG_WAVES>(part, s_red);
             float pHp = part[0];
 #pragma unroll
             for (int c = 0; c < NC; ++c) pHp = fmaf(pb[c], Hb[c], pHp);
@@ -339,7 +266,7 @@ __global__ __launch_bounds__(LG_THREADS) void logit_fit_kernel(const float* __re
                 rr[m] = fmaf(-alpha, e < L ? pe + s_out[e] : 0.f, rr[m]);
                 part[0] = fmaf(rr[m], rr[m], part[0]);
             }
-            lg_block_sum<1>(part, s_red);
+            block_sum<1, LG_WAVES>(part, s_red);
             float rho_new = part[0];
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
@@ -347,7 +274,7 @@ __global__ __launch_bounds__(LG_THREADS) void logit_fit_kernel(const float* __re
                 rb[c] = fmaf(-alpha, Hb[c], rb[c]);
                 rho_new = fmaf(rb[c], rb[c], rho_new);
             }
-            if (!(rho_new > LG_CG_TOL2 * rho0)) break;
+            if (!(rho_new > PROBE_CG_TOL2 * rho0)) break;
             const float bt = rho_new / rho;
             rho = rho_new;
 #pragma unroll
@@ -370,7 +297,7 @@ __global__ __launch_bounds__(LG_THREADS) void logit_fit_kernel(const float* __re
             lin[0] = fmaf(e < L ? Ww[e] : 0.f, xs[m], lin[0]);
             lin[1] = fmaf(xs[m], xs[m], lin[1]);
         }
-        lg_block_sum<2>(lin, s_red);
+        block_sum<2, LG_WAVES>(lin, s_red);
         lg_sweep<NC, DK, SW_DOT>(rows, cost, s_v, s_out, s_red, xb, Hb);
         auto line_term = [&](float t) {
             float acc[1] = {0.f};
@@ -381,12 +308,12 @@ __global__ __launch_bounds__(LG_THREADS) void logit_fit_kernel(const float* __re
                     dfr[c] = c < cols ? rows.df[(int64_t)i * cols + c] : 0.f;
                     ft[c] = c < cols ? fmaf(t, dfr[c], rows.f[(int64_t)i * cols + c]) : 0.f;
                 }
-                lg_row_residual<NC>(ft, cols, rows.y[rows.tidx[i]], rt, wt);
+                row_residual<NC>(ft, cols, rows.y[rows.tidx[i]], rt, wt);
 #pragma unroll
                 for (int c = 0; c < NC; ++c)
                     if (c < cols) acc[0] = fmaf(cost * rt[c], dfr[c], acc[0]);
             }
-            lg_block_sum<1>(acc, s_red);
+            block_sum<1, LG_WAVES>(acc, s_red);
             return acc[0];
         };
         const float dphi0 = line_term(0.f) + lin[0];
@@ -426,8 +353,6 @@ __global__ __launch_bounds__(LG_THREADS) void logit_fit_kernel(const float* __re
     }
 }
 
-inline bool lg_i32(int64_t v) { return v >= 0 && v <= 0x7FFFFFFF; }
-
 struct LogitArgs {
     const float* X;
     int64_t ldX;
@@ -454,7 +379,7 @@ int lg_launch(const LogitArgs& a) {
     }
     hipLaunchKernelGGL((logit_fit_kernel<NC, DK>), dim3((unsigned)a.P), dim3(LG_THREADS), lds, a.stream, a.X, a.ldX, a.S, a.d, a.y, a.ldy,
                        a.train_idx, a.n_train, a.n_max, a.C, a.cost, a.gtol, a.max_iter, a.W, a.b, a.info, a.ws, lg_npad_of(a.n_max));
-    static_assert(NC == lg_nc_of(NC), "the kernels are built for the column counts lg_nc_of returns");
+    static_assert(NC == nc_of(NC), "the kernels are built for the column counts lg_nc_of returns");
     return MDL_OK;
 }
 
@@ -469,33 +394,29 @@ int lg_launch_dk(const LogitArgs& a) {
     return lg_launch<NC, 16>(a);
 }
 
+constexpr ProbeLimits LOGIT_FIT = {MDL_LOGIT_MAX_TRAIN, MDL_LOGIT_MAX_DIM, PROBE_NO_LIMIT, true, true};      // {n_max, d, S, fit, classes}
+
 }  // namespace
 }  // namespace mdl
 
 using namespace mdl;
 
 extern "C" int64_t mdl_logit_fit_ws_bytes(int64_t P, int n_max, int d, int C) {
-    if (P < 1 || n_max < 1 || d < 1) return MDL_E_ARG;
-    if (n_max > MDL_LOGIT_MAX_TRAIN || d > MDL_LOGIT_MAX_DIM || C < 2 || C > LG_CMAX || !lg_i32(P)) return MDL_E_UNSUPPORTED;
-    const int cols = lg_cols_of(C);
-    return P * (3 * lg_npad_of(n_max) * cols + (int64_t)d * lg_nc_of(cols)) * (int64_t)sizeof(float);
+    if (const int rc = probe_check(probe_sizes(P, n_max, 1, C, d), LOGIT_FIT, nullptr)) return rc;
+    const int cols = cols_of(C);
+    return P * (3 * lg_npad_of(n_max) * cols + (int64_t)d * nc_of(cols)) * (int64_t)sizeof(float);
 }
 
 extern "C" int mdl_logit_fit(const float* X, int64_t ldX, int64_t S, int d, const int32_t* y, int64_t ldy, const int32_t* train_idx,
                              const int32_t* n_train, int64_t P, int n_max, int C, float cost, float gtol, int max_iter, float* W_out,
                              float* b_out, float* info_out, void* ws, void* stream) {
-    if (!X || !y || !train_idx || !n_train || !W_out || !b_out || !info_out || !ws) return MDL_E_ARG;
-    if (d < 1 || ldX < d || max_iter < 0 || !(cost > 0.f) || !(gtol >= 0.f)) return MDL_E_ARG;
-    if (P < 1 || n_max < 1 || S < 1) return MDL_E_ARG;
-    if (ldy != 0 && ldy < S) return MDL_E_ARG;
-    if (n_max > MDL_LOGIT_MAX_TRAIN || d > MDL_LOGIT_MAX_DIM || C < 2 || C > LG_CMAX) return MDL_E_UNSUPPORTED;
-    if (!lg_i32(S) || !lg_i32(P) || !lg_i32(P * n_max)) return MDL_E_UNSUPPORTED;
-    const int cols = lg_cols_of(C);
-    if (!lg_i32(P * (int64_t)cols * d)) return MDL_E_UNSUPPORTED;
-    if (!host_aligned16(ws)) return MDL_E_ALIGN;
+    const ProbeTable t = {train_idx, n_train, P, n_max, S, {{y, ldy}}, 1, C, d};
+    const int cols = cols_of(C);
+    const ProbeExtra extra = {all_given(X, W_out, b_out, info_out, ws), mul_i32(P, cols, d), host_aligned16(ws), 0, ldX, max_iter, cost, gtol};
+    if (const int rc = probe_check(t, LOGIT_FIT, &extra)) return rc;
     const LogitArgs a = {X, ldX, (int)S, d, y, ldy, train_idx, n_train, P, n_max, C, cost, gtol, max_iter, W_out, b_out, info_out,
                          reinterpret_cast<float*>(ws), (hipStream_t)stream};
-    if (const int rc = cols == 1 ? lg_launch_dk<1>(a) : (cols <= 4 ? lg_launch_dk<4>(a) : lg_launch_dk<8>(a))) return rc;
+    if (const int rc = for_nc(cols, [&](auto nc) { return lg_launch_dk<decltype(nc)::value>(a); })) return rc;
     MDL_LAUNCH_CHECK();
     return MDL_OK;
 }

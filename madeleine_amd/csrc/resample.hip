@@ -4,7 +4,7 @@
 //
 //   boot_weights_kernel   one workgroup per (group, replicate): the S draws as LDS atomics on uint16 pairs, then the counts to global.
 //   boot_prepare_kernel   one workgroup per problem: test class and prediction of every case in one byte, for C > 2 the fp64 log-softmax
-//                         scores (probe_score.hpp: the code of probe_prepare_kernel), the test-set size and the NaN flag.
+//                         scores (probe_common.hpp: the code of probe_prepare_kernel), the test-set size and the NaN flag.
 //   boot_rank_kernel      O(S^2) counting once per problem and class, a thread per test case: lt = #{score below}, eq = #{score equal},
 //                         and the case's position lt + #{equal, lower case index} in the total order; writes the order and the bounds
 //                         [lt, lt + eq) of the tie group at that position.
@@ -14,8 +14,7 @@
 //   boot_surv_kernel      one workgroup per (problem, BT_RB replicates), the problem's cases in LDS: per replicate the draws and the
 //                         O(S^2) weighted pair count of mdl_surv_metrics' rule.
 // No workgroup waits on another; every loop has a bound that is an argument or a constant of the headers.
-#include "common.hpp"
-#include "probe_score.hpp"
+#include "probe_host.hpp"
 
 #include "../../include/madeleine_amd_stats.h"
 
@@ -25,17 +24,13 @@ namespace {
 constexpr int BT_THREADS = 256;
 constexpr int BT_WAVES = BT_THREADS / WAVE;
 constexpr int BT_RB = MDL_BOOT_REP_BLOCK;
-constexpr int BT_CMAX = MDL_PROBE_MAX_CLASSES;
+constexpr int BT_CMAX = PROBE_CMAX;
 constexpr int BT_SURV = MDL_BOOT_SURV_MAX_TEST;
 constexpr uint32_t BT_GOLDEN = 0x9E3779B9U;
 constexpr size_t BT_LDS_DEFAULT = 48 * 1024;       // dynamic LDS a kernel may ask for without raising its limit
 static_assert(MDL_PROBE_MAX_CASES < 65536, "a count has to fit half a word");
 static_assert(BT_CMAX == 8, "class and prediction share a byte, three bits each");
 
-inline bool i32(int64_t v) { return v >= 0 && v <= 0x7FFFFFFF; }
-inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-inline int64_t up16(int64_t v) { return (v + 15) / 16 * 16; }
-__host__ __device__ __forceinline__ int cols_of(int C) { return C == 2 ? 1 : C; }
 __host__ __device__ __forceinline__ int words_of(int S) { return (S + 1) / 2; }
 inline uint32_t key_of(uint64_t seed) { return (uint32_t)(seed * 0x9E3779B97F4A7C15ULL >> 32) ^ (uint32_t)seed; }
 // dynamic LDS of boot_class_kernel: the count words and the uint16 prefix over S + 1 positions
@@ -86,7 +81,6 @@ __global__ __launch_bounds__(BT_THREADS) void boot_weights_kernel(uint32_t key, 
 // workspace: score [P][C][S] double (C > 2 only), ord [P][ncls][S] uint32 (case index | in-class << 15 at every position of the order),
 // bnd [P][ncls][S] uint32 (tie group [lo, hi) of the position: lo | hi << 16), meta [P][2] int32 (test cases, NaN flag), code [P][S16]
 // int8 (-1: not a test case; else class | prediction << 3)
-__host__ __device__ __forceinline__ int64_t s16_of(int64_t S) { return (S + 15) / 16 * 16; }
 struct BootWs {
     double* score;
     uint32_t* ord;
@@ -119,12 +113,7 @@ __global__ __launch_bounds__(BT_THREADS) void boot_prepare_kernel(const float* _
     if (tid < 2) s_meta[tid] = 0;
     for (int s = tid; s < S; s += BT_THREADS) code[s] = probe_test_class(yp[s], C);
     __syncthreads();
-    int n = n_train[p];
-    n = n < 0 ? 0 : (n > n_max ? n_max : n);
-    for (int i = tid; i < n; i += BT_THREADS) {
-        const int idx = train_idx[(int64_t)p * n_max + i];
-        if (idx >= 0 && idx < S) code[idx] = (int8_t)-1;
-    }
+    strike_training<BT_THREADS>(code, train_idx, n_train, p, n_max, S);
     __syncthreads();
     int n_test = 0, nan = 0;
     for (int s = tid; s < S; s += BT_THREADS) {
@@ -286,12 +275,7 @@ __global__ __launch_bounds__(BT_THREADS) void boot_surv_kernel(const float* __re
         s_t[i] = tp[i];
     }
     __syncthreads();
-    int n = n_train[p];
-    n = n < 0 ? 0 : (n > n_max ? n_max : n);
-    for (int i = tid; i < n; i += BT_THREADS) {
-        const int idx = train_idx[(int64_t)p * n_max + i];
-        if (idx >= 0 && idx < S) s_c[idx] = (int8_t)-1;
-    }
+    strike_training<BT_THREADS>(s_c, train_idx, n_train, p, n_max, S);
     __syncthreads();
     const uint32_t a = group_key(key, group[p]);
     for (int r = r0; r < r1; ++r) {
@@ -326,13 +310,11 @@ __global__ __launch_bounds__(BT_THREADS) void boot_surv_kernel(const float* __re
     }
 }
 
-// R to the replicate count R + 1 (replicate 0 included); MDL_E_* when it is negative or leaves int32
-inline int reps_of(int64_t R, int64_t* reps) {
-    if (R < 0) return MDL_E_ARG;
-    if (R > 0x7FFFFFFE) return MDL_E_UNSUPPORTED;
-    *reps = R + 1;
-    return MDL_OK;
-}
+// the limits of the entry points: {n_max, d, S, fit, classes}
+constexpr ProbeLimits BOOT_CLASS = {MDL_LOGIT_MAX_TRAIN, PROBE_NO_LIMIT, MDL_PROBE_MAX_CASES, false, true};
+constexpr ProbeLimits BOOT_SURV = {MDL_COX_MAX_TRAIN, PROBE_NO_LIMIT, BT_SURV, false, false};
+
+inline int64_t rep_blocks(int64_t R) { return R / BT_RB + 1; }      // ceil((R + 1) / BT_RB) workgroups per problem, for any R >= 0
 
 }  // namespace
 }  // namespace mdl
@@ -340,12 +322,11 @@ inline int reps_of(int64_t R, int64_t* reps) {
 using namespace mdl;
 
 extern "C" int mdl_boot_weights(uint64_t seed, const int32_t* group, int64_t G, int64_t R, int64_t S, uint16_t* w_out, void* stream) {
-    if (!group || !w_out) return MDL_E_ARG;
+    if (!all_given(group, w_out)) return MDL_E_ARG;
     if (G < 1 || S < 1 || R < 0) return MDL_E_ARG;
-    int64_t reps = 0;
-    if (const int rc = reps_of(R, &reps)) return rc;
-    if (S > MDL_PROBE_MAX_CASES || !i32(G) || !i32(G * reps)) return MDL_E_UNSUPPORTED;
+    if (R > 0x7FFFFFFE || S > MDL_PROBE_MAX_CASES || !mul_i32(G, R + 1)) return MDL_E_UNSUPPORTED;
     if (!aligned_to(group, 4) || !aligned_to(w_out, 2)) return MDL_E_ALIGN;
+    const int64_t reps = R + 1;
     hipLaunchKernelGGL(boot_weights_kernel, dim3((unsigned)(G * reps)), dim3(BT_THREADS), 4 * (size_t)words_of((int)S), (hipStream_t)stream,
                        key_of(seed), group, (int)reps, (int)S, w_out);
     MDL_LAUNCH_CHECK();
@@ -353,28 +334,21 @@ extern "C" int mdl_boot_weights(uint64_t seed, const int32_t* group, int64_t G, 
 }
 
 extern "C" int64_t mdl_boot_class_ws_bytes(int64_t P, int64_t S, int C) {
-    if (P < 1 || S < 1) return MDL_E_ARG;
-    if (S > MDL_PROBE_MAX_CASES || C < 2 || C > BT_CMAX || !i32(P)) return MDL_E_UNSUPPORTED;
+    if (const int rc = probe_check(probe_sizes(P, 1, S, C, 0), BOOT_CLASS, nullptr)) return rc;
     return boot_ws_bytes(P, S, C, nullptr, nullptr);
 }
 
 extern "C" int mdl_boot_class_counts(const float* z, const int32_t* y, int64_t ldy, const int32_t* train_idx, const int32_t* n_train,
                                      int64_t P, int n_max, int64_t S, int C, const int32_t* group, uint64_t seed, int64_t R,
                                      int32_t* confusion_out, int64_t* auc_num_out, void* ws, void* stream) {
-    if (!z || !y || !train_idx || !n_train || !group || !confusion_out || !auc_num_out || !ws) return MDL_E_ARG;
-    if (P < 1 || n_max < 1 || S < 1 || R < 0) return MDL_E_ARG;
-    if (ldy != 0 && ldy < S) return MDL_E_ARG;
-    int64_t reps = 0;
-    if (const int rc = reps_of(R, &reps)) return rc;
-    if (S > MDL_PROBE_MAX_CASES || n_max > MDL_LOGIT_MAX_TRAIN || C < 2 || C > BT_CMAX) return MDL_E_UNSUPPORTED;
-    if (!i32(P) || !i32(P * n_max)) return MDL_E_UNSUPPORTED;
+    const ProbeTable t = {train_idx, n_train, P, n_max, S, {{y, ldy}}, 1, C, 0};
     const int ncls = cols_of(C);
-    const int64_t slices = (S + BT_THREADS - 1) / BT_THREADS, nblk = (reps + BT_RB - 1) / BT_RB;
-    if (!i32(P * ncls * slices) || !i32(P * nblk)) return MDL_E_UNSUPPORTED;
-    if (!host_aligned16(ws) || !aligned_to(auc_num_out, 8)) return MDL_E_ALIGN;
-    if (!aligned_to(z, 4) || !aligned_to(y, 4) || !aligned_to(train_idx, 4) || !aligned_to(n_train, 4) || !aligned_to(group, 4) ||
-        !aligned_to(confusion_out, 4))
-        return MDL_E_ALIGN;
+    const int64_t slices = ceil_div(S, BT_THREADS), nblk = rep_blocks(R);
+    const ProbeExtra extra = {all_given(z, group, confusion_out, auc_num_out, ws), mul_i32(P, ncls, slices) && mul_i32(P, nblk),
+                              host_aligned16(ws) && aligned_to(auc_num_out, 8) && all_aligned(4, z, y, train_idx, n_train, group, confusion_out),
+                              R};
+    if (const int rc = probe_check(t, BOOT_CLASS, &extra)) return rc;
+    const int64_t reps = R + 1;
     const size_t lds = class_lds((int)S);
     if (lds > BT_LDS_DEFAULT) {                          // S >= MDL_BOOT_LDS_RAISE_FROM: the kernel's limit is raised to its largest need
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&boot_class_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -399,19 +373,12 @@ extern "C" int mdl_boot_class_counts(const float* z, const int32_t* y, int64_t l
 extern "C" int mdl_boot_surv_counts(const float* z, const float* time, int64_t ldt, const int32_t* event, int64_t lde,
                                     const int32_t* train_idx, const int32_t* n_train, int64_t P, int n_max, int64_t S, const int32_t* group,
                                     uint64_t seed, int64_t R, int64_t* counts_out, void* stream) {
-    if (!z || !time || !event || !train_idx || !n_train || !group || !counts_out) return MDL_E_ARG;
-    if (P < 1 || n_max < 1 || S < 1 || R < 0) return MDL_E_ARG;
-    if ((ldt != 0 && ldt < S) || (lde != 0 && lde < S)) return MDL_E_ARG;
-    int64_t reps = 0;
-    if (const int rc = reps_of(R, &reps)) return rc;
-    if (S > BT_SURV || n_max > MDL_COX_MAX_TRAIN) return MDL_E_UNSUPPORTED;
-    if (!i32(P) || !i32(P * n_max)) return MDL_E_UNSUPPORTED;
-    const int64_t nblk = (reps + BT_RB - 1) / BT_RB;
-    if (!i32(P * nblk)) return MDL_E_UNSUPPORTED;
-    if (!aligned_to(counts_out, 8)) return MDL_E_ALIGN;
-    if (!aligned_to(z, 4) || !aligned_to(time, 4) || !aligned_to(event, 4) || !aligned_to(train_idx, 4) || !aligned_to(n_train, 4) ||
-        !aligned_to(group, 4))
-        return MDL_E_ALIGN;
+    const ProbeTable t = {train_idx, n_train, P, n_max, S, {{time, ldt}, {event, lde}}, 2, 0, 0};
+    const int64_t nblk = rep_blocks(R);
+    const ProbeExtra extra = {all_given(z, group, counts_out), mul_i32(P, nblk),
+                              aligned_to(counts_out, 8) && all_aligned(4, z, time, event, train_idx, n_train, group), R};
+    if (const int rc = probe_check(t, BOOT_SURV, &extra)) return rc;
+    const int64_t reps = R + 1;
     hipLaunchKernelGGL(boot_surv_kernel, dim3((unsigned)(P * nblk)), dim3(BT_THREADS), 0, (hipStream_t)stream, z, time, ldt, event, lde,
                        train_idx, n_train, n_max, (int)S, group, key_of(seed), (int)reps, (int)nblk, counts_out);
     MDL_LAUNCH_CHECK();

@@ -339,7 +339,6 @@ __global__ __launch_bounds__(RT_THREADS) void rt_finish_kernel(int64_t n, int64_
     }
 }
 
-inline bool misaligned(const void* p, uintptr_t bytes) { return p && (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
 
 int check_sizes(int64_t n, int64_t m, int64_t d, int k, int col_chunks) {
     if (n < 1 || m < 1 || d < 1 || k < 0 || col_chunks < 0) return MDL_E_ARG;
@@ -373,8 +372,8 @@ extern "C" int mdl_retrieval(const float* Q, int64_t ldq, const float* K, int64_
     if ((paired && exclude_diag) || (paired && n > m) || (!paired && k == 0)) return MDL_E_ARG;
     if (paired && (!greater || !equal || !pair_sim)) return MDL_E_ARG;
     if (k > 0 && (!topk_idx || !topk_val)) return MDL_E_ARG;
-    if (misaligned(Q, 4) || misaligned(K, 4) || misaligned(greater, 4) || misaligned(equal, 4) || misaligned(pair_sim, 4) ||
-        misaligned(topk_idx, 4) || misaligned(topk_val, 4) || !host_aligned16(ws))
+    if (!aligned_to(Q, 4) || !aligned_to(K, 4) || !aligned_to(greater, 4) || !aligned_to(equal, 4) || !aligned_to(pair_sim, 4) ||
+        !aligned_to(topk_idx, 4) || !aligned_to(topk_val, 4) || !host_aligned16(ws))
         return MDL_E_ALIGN;
     if (const int rc = check_sizes(n, m, d, k, col_chunks)) return rc;
     // every offset into Q and K is formed in 64 bits

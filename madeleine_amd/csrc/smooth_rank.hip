@@ -334,7 +334,6 @@ __global__ __launch_bounds__(SR_THREADS) void sr_finish_kernel(const double* __r
     }
 }
 
-inline bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
 
 int check_sizes(int64_t n, int64_t d) {
     if (n < 1 || d < 1) return MDL_E_ARG;
@@ -360,7 +359,7 @@ int check_sizes(int64_t n, int64_t d) {
 int smooth_rank(const float* E, int64_t ldE, int64_t n, int64_t d, uint64_t eps_bits, void* sigma, void* out, void* ws, void* const* marks,
                 void* stream) {
     if (n < 1 || d < 1 || ldE < d || !E || !sigma || !out || !ws) return MDL_E_ARG;
-    if (misaligned(E, 4) || misaligned(sigma, 8) || misaligned(out, 8) || !host_aligned16(ws)) return MDL_E_ALIGN;
+    if (!aligned_to(E, 4) || !aligned_to(sigma, 8) || !aligned_to(out, 8) || !host_aligned16(ws)) return MDL_E_ALIGN;
     if (const int rc = check_sizes(n, d)) return rc;
     // every offset into E is formed in 64 bits, and (rows - 1) * ldE + d has to stay inside them
     if (ldE > (0x7fffffffffffffffLL / 4 - d) / n) return MDL_E_UNSUPPORTED;

@@ -19,7 +19,7 @@
 //                       the concordance counts -- integers, one 64-bit integer atomic per workgroup: no sum depends on an order.
 //   surv_finish_kernel  one workgroup per problem: the log-rank sums in double in a fixed order, c_index, chi2, the counts.
 // No workgroup waits on another; every loop has a bound that is an argument or a constant of the header.
-#include "common.hpp"
+#include "probe_host.hpp"
 
 namespace mdl {
 namespace {
@@ -27,16 +27,10 @@ namespace {
 constexpr int CX_THREADS = 1024;
 constexpr int CX_WAVES = CX_THREADS / WAVE;
 constexpr int CX_NMAX = MDL_COX_MAX_TRAIN;
-constexpr int CX_TILE = 64;             // Gram tile
-constexpr int CX_KC = 32;               // Gram k-chunk
 constexpr int CX_GRAM_THREADS = 256;
-constexpr float CX_CG_TOL2 = 1e-4f;     // CG stops at |residual|^2 <= 1e-4 |rhs|^2 (forcing term 1e-2)
-constexpr float CX_TIGHT = 0.03f;       // the Newton iteration aims at CX_TIGHT * gtol * g0; `converged` reports against gtol * g0
 constexpr int SV_THREADS = 256;
 constexpr int SV_WAVES = SV_THREADS / WAVE;
 static_assert(CX_NMAX == CX_THREADS, "the fit kernel gives one thread to each training row");
-
-__host__ __device__ __forceinline__ int ldg_of(int n_max) { return (n_max + CX_TILE - 1) / CX_TILE * CX_TILE; }
 
 // workspace of the fit: status [P] int32 (1: refused), order [P][n_max] int32 (the sorted case indices), G [P][ldg][ldg] fp32
 struct CoxWs {
@@ -44,8 +38,7 @@ struct CoxWs {
     int32_t* order;
     float* G;
 };
-__host__ __device__ __forceinline__ int64_t up16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
-__host__ __device__ __forceinline__ CoxWs cox_ws(void* ws, int64_t P, int n_max) {
+inline CoxWs cox_ws(void* ws, int64_t P, int n_max) {
     CoxWs c;
     char* base = reinterpret_cast<char*>(ws);
     c.status = reinterpret_cast<int32_t*>(base);
@@ -96,52 +89,21 @@ __global__ __launch_bounds__(CX_THREADS) void cox_order_kernel(const float* __re
 // ---- Gram -------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(CX_GRAM_THREADS) void cox_gram_kernel(const float* __restrict__ X, int64_t ldX, int d,
                                                                   const int32_t* __restrict__ n_train, int n_max, int ldg, CoxWs c) {
-    const int tps = ldg / CX_TILE;
+    const int tps = ldg / GRAM_TILE;
     const int p = blockIdx.x / (tps * tps), tile = blockIdx.x % (tps * tps);
     const int ti = tile / tps, tj = tile % tps;
     const int n = c.status[p] ? 0 : n_train[p];       // a refused problem: the fit kernel never reads its G
-    if (ti * CX_TILE >= n || tj * CX_TILE >= n) return;
-    __shared__ float sA[CX_KC][CX_TILE + 1], sB[CX_KC][CX_TILE + 1];
-    __shared__ int64_t s_off[2][CX_TILE];             // element offset of the tile's rows in X, -1: a zero row
+    if (ti * GRAM_TILE >= n || tj * GRAM_TILE >= n) return;
+    __shared__ float sA[GRAM_KC][GRAM_TILE + 1], sB[GRAM_KC][GRAM_TILE + 1];
+    __shared__ int64_t s_off[2][GRAM_TILE];           // element offset of the tile's rows in X, -1: a zero row
     const int tid = threadIdx.x;
-    if (tid < 2 * CX_TILE) {
-        const int side = tid / CX_TILE, r = tid % CX_TILE;
-        const int row = (side ? tj : ti) * CX_TILE + r;
+    if (tid < 2 * GRAM_TILE) {
+        const int side = tid / GRAM_TILE, r = tid % GRAM_TILE;
+        const int row = (side ? tj : ti) * GRAM_TILE + r;
         s_off[side][r] = row < n ? (int64_t)c.order[(int64_t)p * n_max + row] * ldX : -1;      // the order kernel checked the range
     }
     __syncthreads();
-    const int tx = tid % 16, ty = tid / 16;
-    float acc[4][4] = {};
-    for (int k0 = 0; k0 < d; k0 += CX_KC) {
-#pragma unroll
-        for (int q = 0; q < CX_TILE * CX_KC / CX_GRAM_THREADS; ++q) {
-            const int e = q * CX_GRAM_THREADS + tid, r = e / CX_KC, kk = e % CX_KC;
-            const bool in = k0 + kk < d;
-            const int64_t oa = s_off[0][r], ob = s_off[1][r];
-            sA[kk][r] = (in && oa >= 0) ? X[oa + k0 + kk] : 0.f;
-            sB[kk][r] = (in && ob >= 0) ? X[ob + k0 + kk] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll 8
-        for (int kk = 0; kk < CX_KC; ++kk) {
-            float a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                a[u] = sA[kk][ty + 16 * u];
-                b[u] = sB[kk][tx + 16 * u];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) acc[u][v] = fmaf(a[u], b[v], acc[u][v]);
-        }
-        __syncthreads();
-    }
-    float* Gp = c.G + (int64_t)p * ldg * ldg;
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) Gp[(int64_t)(ti * CX_TILE + ty + 16 * u) * ldg + tj * CX_TILE + tx + 16 * v] = acc[u][v];
+    gram_tile<CX_GRAM_THREADS>(X, d, s_off, sA, sB, c.G + (int64_t)p * ldg * ldg, ldg, ti, tj);
 }
 
 // ---- fit --------------------------------------------------------------------------------------------------------------------------
@@ -153,44 +115,6 @@ struct CoxLds {
     int64_t off[CX_NMAX];
     float red[CX_WAVES][2];
 };
-
-// Sum of K per-thread values over the workgroup in one fixed order (xor butterflies, then the sixteen waves as a balanced tree); every
-// thread returns the same bits.  Two barriers: the scratch may be reused at once.
-template <int K>
-__device__ __forceinline__ void block_sum(float (&v)[K], CoxLds& s) {
-    static_assert(K <= 2, "s.red holds two values per wave");
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
-    if ((tid & (WAVE - 1)) == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) s.red[tid / WAVE][k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        float q[CX_WAVES];
-#pragma unroll
-        for (int w = 0; w < CX_WAVES; ++w) q[w] = s.red[w][k];
-#pragma unroll
-        for (int span = CX_WAVES / 2; span > 0; span >>= 1)
-#pragma unroll
-            for (int w = 0; w < span; ++w) q[w] = q[2 * w] + q[2 * w + 1];
-        v[k] = q[0];
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ float block_max(float v, CoxLds& s) {
-    const int tid = threadIdx.x;
-    v = wave_max(v);
-    if ((tid & (WAVE - 1)) == 0) s.red[tid / WAVE][0] = v;
-    __syncthreads();
-    float m = s.red[0][0];
-#pragma unroll
-    for (int w = 1; w < CX_WAVES; ++w) m = fmaxf(m, s.red[w][0]);
-    __syncthreads();
-    return m;
-}
 
 // Inclusive sum over the sorted positions 0 .. tid (REV: tid .. 1023), read at position `at`: within the wave by shuffles, the waves
 // before (after) it added in position order.  A fixed order: the same bits whatever else runs.  Three barriers.
@@ -226,7 +150,7 @@ struct CoxRow {
 
 // At decision values f: e = exp(f - max f), inv = event / S0, A, and the gradient in f, r = -event + e A.  Rows that are none: all 0.
 __device__ __forceinline__ float cox_residual(float f, const CoxRow& me, float& e, float& inv, float& A, CoxLds& s) {
-    const float m = block_max(me.row ? f : -__builtin_inff(), s);
+    const float m = block_max<CX_WAVES>(me.row ? f : -__builtin_inff(), s.red);
     e = me.row ? expf(f - m) : 0.f;
     const float S0 = scan_at<false>(e, me.ge, s);
     inv = me.ev != 0.f ? 1.f / S0 : 0.f;
@@ -324,11 +248,11 @@ __global__ __launch_bounds__(CX_THREADS) void cox_fit_kernel(const float* __rest
         __syncthreads();
         float gmax = 0.f;
         xt_times(X, s, n, d, [&](int, float acc) { gmax = fmaxf(gmax, fabsf(acc)); });
-        res = block_max(gmax, s);                   // its barriers also free s.v
+        res = block_max<CX_WAVES>(gmax, s.red);                   // its barriers also free s.v
         if (it == 0) g0 = res;                      // a = 0: the gradient at w = 0
         // Relative stop.  The internal target is tighter than gtol: Newton's last steps square the residual.  Below gtol g0 the
         // iteration also ends as soon as a step no longer halves the residual (the fp32 floor).
-        if (res <= CX_TIGHT * gtol * g0 || (res <= gtol * g0 && res >= 0.5f * prev)) break;
+        if (res <= PROBE_TIGHT * gtol * g0 || (res <= gtol * g0 && res >= 0.5f * prev)) break;
         if (it >= max_iter || !(res == res)) break;
         prev = res;
 
@@ -347,7 +271,7 @@ __global__ __launch_bounds__(CX_THREADS) void cox_fit_kernel(const float* __rest
         float xa = 0.f, Gx = 0.f;
         float ra = -u, Gr = g_times(ra);
         float red[1] = {ra * Gr};
-        block_sum<1>(red, s);
+        block_sum<1, CX_WAVES>(red, s.red);
         float rho = red[0];
         const float rho0 = rho;
         float pa = ra, Gpd = Gr;
@@ -355,7 +279,7 @@ __global__ __launch_bounds__(CX_THREADS) void cox_fit_kernel(const float* __rest
             const float Hq = cox_hess(me.row ? Gpd : 0.f, me, e, inv, A, s);
             const float Ma = fmaf(cost, Hq, pa);
             red[0] = Gpd * Ma;
-            block_sum<1>(red, s);
+            block_sum<1, CX_WAVES>(red, s.red);
             const float pMp = red[0];
             if (!(pMp > 0.f)) break;
             const float alpha = rho / pMp;
@@ -365,9 +289,9 @@ __global__ __launch_bounds__(CX_THREADS) void cox_fit_kernel(const float* __rest
             ra = fmaf(-alpha, Ma, ra);
             Gr = g_times(ra);
             red[0] = ra * Gr;
-            block_sum<1>(red, s);
+            block_sum<1, CX_WAVES>(red, s.red);
             const float rho_new = red[0];
-            if (!(rho_new > CX_CG_TOL2 * rho0)) break;
+            if (!(rho_new > PROBE_CG_TOL2 * rho0)) break;
             const float beta = rho_new / rho;
             rho = rho_new;
             pa = fmaf(beta, pa, ra);
@@ -377,10 +301,10 @@ __global__ __launch_bounds__(CX_THREADS) void cox_fit_kernel(const float* __rest
         // ---- step length along xa: phi'(t) = cost sum r(f + t df) df + xa^T G a + t xa^T G xa; (G a)_i = f_i ----
         const float df = me.row ? Gx : 0.f;
         float lin[2] = {cost * r * df, xa * f};
-        block_sum<2>(lin, s);
+        block_sum<2, CX_WAVES>(lin, s.red);
         const float dphi0 = lin[0] + lin[1], xGa = lin[1];
         red[0] = xa * Gx;
-        block_sum<1>(red, s);
+        block_sum<1, CX_WAVES>(red, s.red);
         const float xGx = red[0];
         if (!(dphi0 < 0.f)) break;                  // no descent left in fp32: stop here, unconverged
         float tl = 1.f;
@@ -388,7 +312,7 @@ __global__ __launch_bounds__(CX_THREADS) void cox_fit_kernel(const float* __rest
             float et, invt, At;
             const float rt = cox_residual(fmaf(tl, df, f), me, et, invt, At, s);
             red[0] = cost * rt * df;
-            block_sum<1>(red, s);
+            block_sum<1, CX_WAVES>(red, s.red);
             const float dphi = red[0] + xGa + tl * xGx;
             if (dphi <= -0.5f * dphi0) break;        // a NaN (an overflow along the line) halves too
             tl *= 0.5f;
@@ -425,13 +349,12 @@ __global__ __launch_bounds__(CX_THREADS) void cox_fit_kernel(const float* __rest
 // ---- metrics ----------------------------------------------------------------------------------------------------------------------
 // workspace: cnt [P] uint64 (comparable pairs << 32 | concordance numerator), risk [3][P][S] int32 (n_i, h_i, d_i of the test event
 // cases), tcls [P][S16] int8 (-1: not a test case; else bit 0 = event, bit 1 = high-risk group)
-__host__ __device__ __forceinline__ int64_t s16_of(int64_t S) { return (S + 15) / 16 * 16; }
 struct SurvWs {
     unsigned long long* cnt;
     int32_t* risk;
     int8_t* tcls;
 };
-__host__ __device__ __forceinline__ SurvWs surv_ws(void* ws, int64_t P, int64_t S) {
+inline SurvWs surv_ws(void* ws, int64_t P, int64_t S) {
     SurvWs m;
     char* base = reinterpret_cast<char*>(ws);
     m.cnt = reinterpret_cast<unsigned long long*>(base);
@@ -454,12 +377,7 @@ __global__ __launch_bounds__(SV_THREADS) void surv_prepare_kernel(const float* _
         tcls[i] = (ev == 0 || ev == 1) ? (int8_t)(ev | (z[(int64_t)p * S + i] > th ? 2 : 0)) : (int8_t)-1;
     }
     __syncthreads();
-    int n = n_train[p];
-    n = n < 0 ? 0 : (n > n_max ? n_max : n);
-    for (int i = tid; i < n; i += SV_THREADS) {
-        const int idx = train_idx[(int64_t)p * n_max + i];
-        if (idx >= 0 && idx < S) tcls[idx] = (int8_t)-1;
-    }
+    strike_training<SV_THREADS>(tcls, train_idx, n_train, p, n_max, S);
 }
 
 __global__ __launch_bounds__(SV_THREADS) void surv_pairs_kernel(const float* __restrict__ z, const float* __restrict__ time, int64_t ldt,
@@ -582,17 +500,9 @@ __global__ __launch_bounds__(SV_THREADS) void surv_finish_kernel(int S, const fl
     }
 }
 
-inline bool i32(int64_t v) { return v >= 0 && v <= 0x7FFFFFFF; }
-inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-// shared argument checks of the entry points that take the problem list
-inline int check_problems(int64_t P, int n_max, int64_t S, int64_t ldt, int64_t lde) {
-    if (P < 1 || n_max < 1 || S < 1) return MDL_E_ARG;
-    if ((ldt != 0 && ldt < S) || (lde != 0 && lde < S)) return MDL_E_ARG;
-    if (n_max > CX_NMAX) return MDL_E_UNSUPPORTED;
-    if (!i32(S) || !i32(P) || !i32(P * n_max)) return MDL_E_UNSUPPORTED;
-    return MDL_OK;
-}
+// the limits of the entry points: {n_max, d, S, fit, classes}
+constexpr ProbeLimits COX_FIT = {CX_NMAX, PROBE_NO_LIMIT, PROBE_NO_LIMIT, true, false};
+constexpr ProbeLimits SURV_METRICS = {CX_NMAX, PROBE_NO_LIMIT, MDL_PROBE_MAX_CASES, false, false};
 
 }  // namespace
 }  // namespace mdl
@@ -600,49 +510,45 @@ inline int check_problems(int64_t P, int n_max, int64_t S, int64_t ldt, int64_t 
 using namespace mdl;
 
 extern "C" int64_t mdl_cox_order_fit_ws_bytes(int64_t P, int n_max, int d) {
-    if (P < 1 || n_max < 1 || d < 1) return MDL_E_ARG;
-    if (n_max > CX_NMAX || !i32(P)) return MDL_E_UNSUPPORTED;
-    const int64_t ldg = ldg_of(n_max);
+    if (const int rc = probe_check(probe_sizes(P, n_max, 1, 0, d), COX_FIT, nullptr)) return rc;
+    const int64_t ldg = gram_ld(n_max);
     return up16(P * 4) + up16(P * n_max * 4) + P * ldg * ldg * (int64_t)sizeof(float);
 }
 
 extern "C" int mdl_cox_fit(const float* X, int64_t ldX, int64_t S, int d, const float* time, int64_t ldt, const int32_t* event, int64_t lde,
                            const int32_t* train_idx, const int32_t* n_train, int64_t P, int n_max, float cost, float gtol, int max_iter,
                            float* W_out, float* thr_out, float* info_out, void* ws, void* stream) {
-    if (!X || !time || !event || !train_idx || !n_train || !W_out || !thr_out || !info_out || !ws) return MDL_E_ARG;
-    if (d < 1 || ldX < d || max_iter < 0 || !(cost > 0.f) || !(gtol >= 0.f)) return MDL_E_ARG;
-    if (const int rc = check_problems(P, n_max, S, ldt, lde)) return rc;
-    if (!host_aligned16(ws)) return MDL_E_ALIGN;
-    const int ldg = ldg_of(n_max), tps = ldg / CX_TILE;
-    if (!i32(P * tps * tps) || !i32(P * (int64_t)d)) return MDL_E_UNSUPPORTED;
+    const ProbeTable t = {train_idx, n_train, P, n_max, S, {{time, ldt}, {event, lde}}, 2, 0, d};
+    const int64_t ldg = gram_ld(n_max), tps = ldg / GRAM_TILE;
+    const ProbeExtra extra = {all_given(X, W_out, thr_out, info_out, ws), mul_i32(P, tps, tps) && mul_i32(P, d), host_aligned16(ws), 0,
+                              ldX, max_iter, cost, gtol};
+    if (const int rc = probe_check(t, COX_FIT, &extra)) return rc;
     const CoxWs c = cox_ws(ws, P, n_max);
     hipLaunchKernelGGL(cox_order_kernel, dim3((unsigned)P), dim3(CX_THREADS), 0, (hipStream_t)stream, time, ldt, event, lde, (int)S,
                        train_idx, n_train, n_max, c);
     MDL_LAUNCH_CHECK();
     hipLaunchKernelGGL(cox_gram_kernel, dim3((unsigned)(P * tps * tps)), dim3(CX_GRAM_THREADS), 0, (hipStream_t)stream, X, ldX, d, n_train,
-                       n_max, ldg, c);
+                       n_max, (int)ldg, c);
     MDL_LAUNCH_CHECK();
     hipLaunchKernelGGL(cox_fit_kernel, dim3((unsigned)P), dim3(CX_THREADS), 0, (hipStream_t)stream, X, ldX, d, time, ldt, event, lde,
-                       n_train, n_max, cost, gtol, max_iter, W_out, thr_out, info_out, c, ldg);
+                       n_train, n_max, cost, gtol, max_iter, W_out, thr_out, info_out, c, (int)ldg);
     MDL_LAUNCH_CHECK();
     return MDL_OK;
 }
 
 extern "C" int64_t mdl_surv_metrics_ws_bytes(int64_t P, int64_t S) {
-    if (P < 1 || S < 1) return MDL_E_ARG;
-    if (S > MDL_PROBE_MAX_CASES || !i32(P)) return MDL_E_UNSUPPORTED;
+    if (const int rc = probe_check(probe_sizes(P, 1, S, 0, 0), SURV_METRICS, nullptr)) return rc;
     return up16(P * 8) + up16(3 * P * S * 4) + P * s16_of(S);
 }
 
 extern "C" int mdl_surv_metrics(const float* z, const float* time, int64_t ldt, const int32_t* event, int64_t lde, const int32_t* train_idx,
                                 const int32_t* n_train, int64_t P, int n_max, int64_t S, const float* thr, void* c_index_out,
                                 void* chi2_out, int32_t* counts_out, void* ws, void* stream) {
-    if (!z || !time || !event || !train_idx || !n_train || !thr || !c_index_out || !chi2_out || !counts_out || !ws) return MDL_E_ARG;
-    if (const int rc = check_problems(P, n_max, S, ldt, lde)) return rc;
-    if (S > MDL_PROBE_MAX_CASES) return MDL_E_UNSUPPORTED;
-    if (!host_aligned16(ws) || !aligned_to(c_index_out, 8) || !aligned_to(chi2_out, 8)) return MDL_E_ALIGN;
-    const int64_t slices = (S + SV_THREADS - 1) / SV_THREADS;
-    if (!i32(P * slices)) return MDL_E_UNSUPPORTED;
+    const ProbeTable t = {train_idx, n_train, P, n_max, S, {{time, ldt}, {event, lde}}, 2, 0, 0};
+    const int64_t slices = ceil_div(S, SV_THREADS);
+    const ProbeExtra extra = {all_given(z, thr, c_index_out, chi2_out, counts_out, ws), mul_i32(P, slices),
+                              host_aligned16(ws) && all_aligned(8, c_index_out, chi2_out)};
+    if (const int rc = probe_check(t, SURV_METRICS, &extra)) return rc;
     const SurvWs m = surv_ws(ws, P, S);
     const int64_t S16 = s16_of(S);
     hipLaunchKernelGGL(surv_prepare_kernel, dim3((unsigned)P), dim3(SV_THREADS), 0, (hipStream_t)stream, z, event, lde, train_idx, n_train,

@@ -1871,9 +1871,9 @@ def bag_mean_tiered(store_rows, host_rows, off, bag, chunk_cu, n_chunks, host_wg
 _PROBE_LIMITS = "linear probe supports at most %d training cases per problem, 2..%d classes and %d cases (got n_max %d, C %d, S %d)"
 
 
-def _probe_refusal(n_max, C, S):
-    d = _native._DEFINES
-    return (_PROBE_LIMITS, d["MDL_PROBE_MAX_TRAIN"], d["MDL_PROBE_MAX_CLASSES"], d["MDL_PROBE_MAX_CASES"], n_max, C, S)
+def _probe_refusal(n_max, d, C, S):      # (the signature of _logit_refusal; no limit on d)
+    lim = _native._DEFINES
+    return (_PROBE_LIMITS, lim["MDL_PROBE_MAX_TRAIN"], lim["MDL_PROBE_MAX_CLASSES"], lim["MDL_PROBE_MAX_CASES"], n_max, C, S)
 
 
 def _probe_matrix(X):
@@ -1887,37 +1887,81 @@ def _probe_matrix(X):
     return S, d, (X.stride(0) if S > 1 else d)
 
 
-def _probe_problems(y, train_idx, n_train, S):
-    """(P, n_max, ldy) of a problem list: y [S] (shared) or [P, S] int32, train_idx [P, n_max] int32, n_train [P] int32."""
-    _require(y, "y", torch.int32)
+def _problem_table(train_idx, n_train):
+    """(P, n_max) of a problem table: train_idx [P, n_max] int32, n_train [P] int32."""
     _require(train_idx, "train_idx", torch.int32)
     _require(n_train, "n_train", torch.int32)
     if train_idx.dim() != 2 or train_idx.shape[0] < 1 or train_idx.shape[1] < 1 or n_train.shape != (train_idx.shape[0],):
         raise RuntimeError("madeleine_amd: train_idx must be [P, n_max] and n_train [P], P >= 1, n_max >= 1")
-    P, n_max = train_idx.shape
-    if y.shape == (S,):
-        return P, n_max, 0
-    if y.shape == (P, S):
-        return P, n_max, S
-    raise RuntimeError("madeleine_amd: y must be [S] or [P, S] = [%d, %d] (got %s)" % (P, S, tuple(y.shape)))
+    return train_idx.shape
+
+
+def _case_column(v, name, dtype, P, S):
+    """Row stride of a per-case column: 0 for [S] (shared by all problems), S for [P, S]."""
+    _require(v, name, dtype)
+    if v.shape == (S,):
+        return 0
+    if v.shape == (P, S):
+        return S
+    raise RuntimeError("madeleine_amd: %s must be [S] or [P, S] = [%d, %d] (got %s)" % (name, P, S, tuple(v.shape)))
+
+
+def _probe_problems(y, train_idx, n_train, S):
+    """(P, n_max, ldy) of a problem list: y [S] (shared) or [P, S] int32, train_idx [P, n_max] int32, n_train [P] int32."""
+    P, n_max = _problem_table(train_idx, n_train)
+    return P, n_max, _case_column(y, "y", torch.int32, P, S)
+
+
+def _class_scores(z, C):
+    """(S, cols) of the decision values z [P, S, cols] of a C-class problem table."""
+    _require(z, "z")
+    cols = 1 if C == 2 else C
+    if z.dim() != 3 or z.shape[0] < 1 or z.shape[1] < 1 or z.shape[2] != cols:
+        raise RuntimeError("madeleine_amd: z must be [P, S, %d]" % cols)
+    return z.shape[1], cols
+
+
+def _same_problems(z, P):
+    if P != z.shape[0]:
+        raise RuntimeError("madeleine_amd: z holds %d problems, train_idx %d" % (z.shape[0], P))
+
+
+def _logistic_fit(prefix, refusal_of, X, y, train_idx, n_train, n_classes, cost, gtol, max_iter):
+    """probe_fit and logit_fit: mdl_<prefix>_fit behind its workspace query."""
+    S, d, ldX = _probe_matrix(X)
+    P, n_max, ldy = _probe_problems(y, train_idx, n_train, S)
+    C = int(n_classes)
+    refusal = refusal_of(n_max, d, C, S)
+    ws = _ws_for("mdl_%s_fit_ws_bytes" % prefix, X.device, P, n_max, d, C, refusal=refusal)
+    cols = 1 if C == 2 else C
+    W = torch.empty(P, cols, d, device=X.device, dtype=torch.float32)
+    b = torch.empty(P, cols, device=X.device, dtype=torch.float32)
+    info = torch.empty(P, 4, device=X.device, dtype=torch.float32)
+    with _timed(prefix + "_fit"):
+        _call("mdl_%s_fit" % prefix, X, ldX, S, d, y, ldy, train_idx, n_train, P, n_max, C, float(cost), float(gtol), int(max_iter), W, b,
+              info, ws, _stream(), unsupported=refusal)
+    return W, b, info
+
+
+def _class_metrics(prefix, refusal_of, z, y, train_idx, n_train, n_classes):
+    """probe_metrics and logit_metrics: mdl_<prefix>_metrics behind its workspace query."""
+    C = int(n_classes)
+    S, _ = _class_scores(z, C)
+    P, n_max, ldy = _probe_problems(y, train_idx, n_train, S)
+    _same_problems(z, P)
+    refusal = refusal_of(n_max, 1, C, S)
+    ws = _ws_for("mdl_%s_metrics_ws_bytes" % prefix, z.device, P, S, C, refusal=refusal)
+    confusion = torch.empty(P, C, C, device=z.device, dtype=torch.int32)
+    auc = torch.empty(P, device=z.device, dtype=torch.float32)
+    with _timed(prefix + "_metrics"):
+        _call("mdl_%s_metrics" % prefix, z, y, ldy, train_idx, n_train, P, n_max, S, C, confusion, auc, ws, _stream(), unsupported=refusal)
+    return confusion, auc
 
 
 def probe_fit(X, y, train_idx, n_train, n_classes, cost=1.0, gtol=1e-4, max_iter=100):
     """(W [P, cols, d], b [P, cols], info [P, 4]) of P regularised logistic fits (P1 of the header; cols = 1 for two classes).
     info columns: Newton steps, converged, inf-norm of the gradient, CG steps.  Asynchronous, no host read."""
-    S, d, ldX = _probe_matrix(X)
-    P, n_max, ldy = _probe_problems(y, train_idx, n_train, S)
-    C = int(n_classes)
-    refusal = _probe_refusal(n_max, C, S)
-    ws = _ws_for("mdl_probe_fit_ws_bytes", X.device, P, n_max, d, C, refusal=refusal)
-    cols = 1 if C == 2 else C
-    W = torch.empty(P, cols, d, device=X.device, dtype=torch.float32)
-    b = torch.empty(P, cols, device=X.device, dtype=torch.float32)
-    info = torch.empty(P, 4, device=X.device, dtype=torch.float32)
-    with _timed("probe_fit"):
-        _call("mdl_probe_fit", X, ldX, S, d, y, ldy, train_idx, n_train, P, n_max, C, float(cost), float(gtol), int(max_iter), W, b, info,
-              ws, _stream(), unsupported=refusal)
-    return W, b, info
+    return _logistic_fit("probe", _probe_refusal, X, y, train_idx, n_train, n_classes, cost, gtol, max_iter)
 
 
 def probe_scores(X, W, b, n_classes):
@@ -1932,28 +1976,13 @@ def probe_scores(X, W, b, n_classes):
     P = W.shape[0]
     z = torch.empty(P, S, cols, device=X.device, dtype=torch.float32)
     with _timed("probe_scores", ("flop", 2.0 * P * S * cols * d)):
-        _call("mdl_probe_scores", X, ldX, S, d, W, b, P, C, z, _stream(), unsupported=_probe_refusal(0, C, S))
+        _call("mdl_probe_scores", X, ldX, S, d, W, b, P, C, z, _stream(), unsupported=_probe_refusal(0, d, C, S))
     return z
 
 
 def probe_metrics(z, y, train_idx, n_train, n_classes):
     """(confusion [P, C, C] int32, auc [P] fp32) over the test cases of every problem (P3): the labeled cases outside its train_idx."""
-    _require(z, "z")
-    C = int(n_classes)
-    cols = 1 if C == 2 else C
-    if z.dim() != 3 or z.shape[0] < 1 or z.shape[1] < 1 or z.shape[2] != cols:
-        raise RuntimeError("madeleine_amd: z must be [P, S, %d]" % cols)
-    S = z.shape[1]
-    P, n_max, ldy = _probe_problems(y, train_idx, n_train, S)
-    if P != z.shape[0]:
-        raise RuntimeError("madeleine_amd: z holds %d problems, train_idx %d" % (z.shape[0], P))
-    refusal = _probe_refusal(n_max, C, S)
-    ws = _ws_for("mdl_probe_metrics_ws_bytes", z.device, P, S, C, refusal=refusal)
-    confusion = torch.empty(P, C, C, device=z.device, dtype=torch.int32)
-    auc = torch.empty(P, device=z.device, dtype=torch.float32)
-    with _timed("probe_metrics"):
-        _call("mdl_probe_metrics", z, y, ldy, train_idx, n_train, P, n_max, S, C, confusion, auc, ws, _stream(), unsupported=refusal)
-    return confusion, auc
+    return _class_metrics("probe", _probe_refusal, z, y, train_idx, n_train, n_classes)
 
 
 # ---- L1-L2: the full-label linear probe (mdl_logit_fit / mdl_logit_metrics; the scores between them are probe_scores).  No autograd ----
@@ -1971,40 +2000,13 @@ def logit_fit(X, y, train_idx, n_train, n_classes, cost=1.0, gtol=1e-4, max_iter
     """(W [P, cols, d], b [P, cols], info [P, 4]) of P regularised logistic fits in the primal unknowns (L1 of the header): the objective,
     the stop rule and the info columns of probe_fit, for up to MDL_LOGIT_MAX_TRAIN training cases per problem.  Asynchronous, no host
     read."""
-    S, d, ldX = _probe_matrix(X)
-    P, n_max, ldy = _probe_problems(y, train_idx, n_train, S)
-    C = int(n_classes)
-    refusal = _logit_refusal(n_max, d, C, S)
-    ws = _ws_for("mdl_logit_fit_ws_bytes", X.device, P, n_max, d, C, refusal=refusal)
-    cols = 1 if C == 2 else C
-    W = torch.empty(P, cols, d, device=X.device, dtype=torch.float32)
-    b = torch.empty(P, cols, device=X.device, dtype=torch.float32)
-    info = torch.empty(P, 4, device=X.device, dtype=torch.float32)
-    with _timed("logit_fit"):
-        _call("mdl_logit_fit", X, ldX, S, d, y, ldy, train_idx, n_train, P, n_max, C, float(cost), float(gtol), int(max_iter), W, b, info,
-              ws, _stream(), unsupported=refusal)
-    return W, b, info
+    return _logistic_fit("logit", _logit_refusal, X, y, train_idx, n_train, n_classes, cost, gtol, max_iter)
 
 
 def logit_metrics(z, y, train_idx, n_train, n_classes):
     """probe_metrics for problem tables of up to MDL_LOGIT_MAX_TRAIN columns (L2): (confusion [P, C, C] int32, auc [P] fp32) over the
     test cases of every problem."""
-    _require(z, "z")
-    C = int(n_classes)
-    cols = 1 if C == 2 else C
-    if z.dim() != 3 or z.shape[0] < 1 or z.shape[1] < 1 or z.shape[2] != cols:
-        raise RuntimeError("madeleine_amd: z must be [P, S, %d]" % cols)
-    S = z.shape[1]
-    P, n_max, ldy = _probe_problems(y, train_idx, n_train, S)
-    if P != z.shape[0]:
-        raise RuntimeError("madeleine_amd: z holds %d problems, train_idx %d" % (z.shape[0], P))
-    refusal = _logit_refusal(n_max, 1, C, S)
-    ws = _ws_for("mdl_logit_metrics_ws_bytes", z.device, P, S, C, refusal=refusal)
-    confusion = torch.empty(P, C, C, device=z.device, dtype=torch.int32)
-    auc = torch.empty(P, device=z.device, dtype=torch.float32)
-    with _timed("logit_metrics"):
-        _call("mdl_logit_metrics", z, y, ldy, train_idx, n_train, P, n_max, S, C, confusion, auc, ws, _stream(), unsupported=refusal)
-    return confusion, auc
+    return _class_metrics("logit", _logit_refusal, z, y, train_idx, n_train, n_classes)
 
 
 # ---- S1-S2: the survival probe (mdl_cox_fit / mdl_surv_metrics; the scores between them are probe_scores).  No autograd ----
@@ -2019,22 +2021,8 @@ def _surv_refusal(n_max, S):
 def _surv_problems(time, event, train_idx, n_train, S):
     """(P, n_max, ldt, lde) of a problem list: time fp32 and event int32, each [S] (shared) or [P, S]; train_idx [P, n_max] int32,
     n_train [P] int32."""
-    _require(time, "time")
-    _require(event, "event", torch.int32)
-    _require(train_idx, "train_idx", torch.int32)
-    _require(n_train, "n_train", torch.int32)
-    if train_idx.dim() != 2 or train_idx.shape[0] < 1 or train_idx.shape[1] < 1 or n_train.shape != (train_idx.shape[0],):
-        raise RuntimeError("madeleine_amd: train_idx must be [P, n_max] and n_train [P], P >= 1, n_max >= 1")
-    P, n_max = train_idx.shape
-    strides = []
-    for name, v in (("time", time), ("event", event)):
-        if v.shape == (S,):
-            strides.append(0)
-        elif v.shape == (P, S):
-            strides.append(S)
-        else:
-            raise RuntimeError("madeleine_amd: %s must be [S] or [P, S] = [%d, %d] (got %s)" % (name, P, S, tuple(v.shape)))
-    return P, n_max, strides[0], strides[1]
+    P, n_max = _problem_table(train_idx, n_train)
+    return P, n_max, _case_column(time, "time", torch.float32, P, S), _case_column(event, "event", torch.int32, P, S)
 
 
 def cox_fit(X, time, event, train_idx, n_train, cost=1.0, gtol=1e-3, max_iter=100):
@@ -2064,8 +2052,7 @@ def survival_metrics(z, time, event, train_idx, n_train, thr):
         raise RuntimeError("madeleine_amd: z must be [P, S] and thr [P]")
     S = z.shape[1]
     P, n_max, ldt, lde = _surv_problems(time, event, train_idx, n_train, S)
-    if P != z.shape[0]:
-        raise RuntimeError("madeleine_amd: z holds %d problems, train_idx %d" % (z.shape[0], P))
+    _same_problems(z, P)
     refusal = _surv_refusal(n_max, S)
     ws = _ws_for("mdl_surv_metrics_ws_bytes", z.device, P, S, refusal=refusal)
     c_index = torch.empty(P, device=z.device, dtype=torch.float64)
@@ -2420,15 +2407,10 @@ def boot_class_counts(z, y, train_idx, n_train, n_classes, group, seed, replicat
     classes), the weighted Mann-Whitney numerator sum w_i w_j (2 [s_i > s_j] + [s_i == s_j]).  Problem p uses the weights of
     (seed, group[p], r, S): problems of one group are resampled together.  Replicate 0 is the sample itself.  A problem with a NaN test
     score has auc_num -1.  Three launches on the current stream, no host read."""
-    _require(z, "z")
     C = int(n_classes)
-    cols = 1 if C == 2 else C
-    if z.dim() != 3 or z.shape[0] < 1 or z.shape[1] < 1 or z.shape[2] != cols:
-        raise RuntimeError("madeleine_amd: z must be [P, S, %d]" % cols)
-    S = z.shape[1]
+    S, cols = _class_scores(z, C)
     P, n_max, ldy = _probe_problems(y, train_idx, n_train, S)
-    if P != z.shape[0]:
-        raise RuntimeError("madeleine_amd: z holds %d problems, train_idx %d" % (z.shape[0], P))
+    _same_problems(z, P)
     _boot_group(group, P, "problem")
     R = _boot_replicates(replicates)
     refusal = _boot_refusal(n_max, C, S, R)
@@ -2451,8 +2433,7 @@ def boot_surv_counts(z, time, event, train_idx, n_train, group, seed, replicates
         raise RuntimeError("madeleine_amd: z must be [P, S]")
     S = z.shape[1]
     P, n_max, ldt, lde = _surv_problems(time, event, train_idx, n_train, S)
-    if P != z.shape[0]:
-        raise RuntimeError("madeleine_amd: z holds %d problems, train_idx %d" % (z.shape[0], P))
+    _same_problems(z, P)
     _boot_group(group, P, "problem")
     R = _boot_replicates(replicates)
     counts = torch.empty(P, R + 1, 2, device=z.device, dtype=torch.int64)
