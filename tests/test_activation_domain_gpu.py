@@ -36,6 +36,7 @@ import pytest
 import torch
 
 from tests import _act_ref as R
+from tests._bf16_bounds import bf16_half_ulp
 from tests.test_ln_kinds_gpu import ln_bwd, ln_bwd_split, ln_fwd, ln_fwd_split, same_bits
 from tests.test_split_gpu import _decode
 
@@ -72,13 +73,6 @@ def check(entry, quantity, got, ref, bound, t):
                                                                        float(bound[i])))
     assert bool((err <= bound).all()), (entry, quantity, float(err[i]), float(t[i]), float(bound[i]))
     return float(err[i])
-
-
-def bf16_half_ulp(ref, slack=0.0):
-    """Half the bf16 spacing at |ref| + slack, the most that storing a value within `slack` of ref in bf16 adds to its error: 2^(e - 8) in
-    [2^e, 2^(e+1)): between 2^-9 and 2^-8 of the value (8 significant bits)."""
-    mag = (ref.double().abs() + slack).clamp_min(2.0 ** -126)
-    return torch.exp2(torch.floor(torch.log2(mag)) - 8)
 
 
 def at(values, grid, point):
