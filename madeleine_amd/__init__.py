@@ -14,13 +14,16 @@ madeleine.utils.loss, madeleine.utils.trainer):
     from madeleine_amd import survival_probe     # do the embeddings stratify patients: cross-validated Cox fits, C-index, log-rank
     from madeleine_amd import heatmap            # attention heatmaps on the device: render, gaussian_taps, colormap, save_png
     from madeleine_amd import linear_probe_ci    # bootstrap intervals of the probes' metrics and paired differences between encoders
+    from madeleine_amd import attn_contrib, contrib_stats   # which patches made a probe's decision (DeviceSlideStore.contributions)
 
 The numeric work runs in csrc/libmadeleine_amd.so through the C ABI of include/madeleine_amd.h (the heatmap renderer: of
-include/madeleine_amd_view.h; the bootstrap counts: of include/madeleine_amd_stats.h).
+include/madeleine_amd_view.h; the bootstrap counts: of include/madeleine_amd_stats.h; the patch contributions: of
+include/madeleine_amd_explain.h).
 Importing this package does not load the library (so model construction / state_dict handling works on
 any box); the first forward does, and raises if it is unavailable -- there is no fallback path.
 """
 from .abmil import BatchedABMIL
+from .functional import attn_contrib, contrib_stats
 from .loss import GOT, InfoNCE, info_nce, init_intra_wsi_loss_function
 from .model import ABMILEmbedder, MADELEINE, create_model
 from .optim import AdamW
@@ -35,7 +38,8 @@ __all__ = ["MADELEINE", "ABMILEmbedder", "BatchedABMIL", "create_model", "InfoNC
            "load_checkpoint", "create_model_from_pretrained", "AdamW", "DeviceSlideStore", "PackedBags", "probe_splits", "fit_logistic",
            "linear_probe", "device_smooth_rank", "cross_stain_retrieval", "retrieval_metrics", "slide_neighbours",
            "survival_splits", "fit_cox", "survival_probe", "cv_splits", "linear_probe_cv", "heatmap", "render_heatmaps", "gaussian_taps",
-           "colormap", "save_png", "bootstrap_summary", "paired_difference", "linear_probe_ci", "survival_probe_ci"]
+           "colormap", "save_png", "bootstrap_summary", "paired_difference", "linear_probe_ci", "survival_probe_ci", "attn_contrib",
+           "contrib_stats"]
 __version__ = "0.2"
 _HEATMAP = ("render_heatmaps", "gaussian_taps", "colormap", "save_png")
 _PROBE = ("probe_splits", "fit_logistic", "linear_probe", "cv_splits", "linear_probe_cv")

@@ -1,5 +1,5 @@
-"""ctypes binding of libmadeleine_amd.so (the C ABI of include/madeleine_amd.h, include/madeleine_amd_view.h and
-include/madeleine_amd_stats.h).
+"""ctypes binding of libmadeleine_amd.so (the C ABI of include/madeleine_amd.h, include/madeleine_amd_view.h,
+include/madeleine_amd_stats.h and include/madeleine_amd_explain.h).
 
 Single backend: there is no CPU / eager fallback.  `lib()` raises if the shared object cannot be
 loaded (it is built in-tree by `python -m madeleine_amd._build` / __graft_entry__.build(); if it is
@@ -81,6 +81,13 @@ with open(_build.STATS_HEADER) as _f:
     STATS_SIGNATURES, STATS_DEFINES = _parse_header(_f.read())
 if (set(STATS_SIGNATURES) & (set(SIGNATURES) | set(VIEW_SIGNATURES))) or (set(STATS_DEFINES) & (set(_DEFINES) | set(VIEW_DEFINES))):
     raise ImportError("madeleine_amd: %s repeats a name of %s or %s" % (_build.STATS_HEADER, _build.HEADER, _build.VIEW_HEADER))
+# the fourth header (include/madeleine_amd_explain.h: the patch contributions of a probe's decision), the same way again
+with open(_build.EXPLAIN_HEADER) as _f:
+    EXPLAIN_SIGNATURES, EXPLAIN_DEFINES = _parse_header(_f.read())
+if (set(EXPLAIN_SIGNATURES) & (set(SIGNATURES) | set(VIEW_SIGNATURES) | set(STATS_SIGNATURES))) or \
+        (set(EXPLAIN_DEFINES) & (set(_DEFINES) | set(VIEW_DEFINES) | set(STATS_DEFINES))):
+    raise ImportError("madeleine_amd: %s repeats a name of %s, %s or %s"
+                      % (_build.EXPLAIN_HEADER, _build.HEADER, _build.VIEW_HEADER, _build.STATS_HEADER))
 
 
 def lib_path() -> str:
@@ -123,7 +130,8 @@ def lib():
         if abi() != ABI_VERSION:
             raise RuntimeError("madeleine_amd: %s implements ABI revision %d, this binding expects %d; rebuild it "
                                "(`python -m madeleine_amd._build --force`)" % (path, abi(), ABI_VERSION))
-        for name, (res, args) in list(SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(STATS_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(STATS_SIGNATURES.items()) + \
+                list(EXPLAIN_SIGNATURES.items()):
             try:
                 fn = getattr(handle, name)
             except AttributeError:

@@ -2441,3 +2441,65 @@ def boot_surv_counts(z, time, event, train_idx, n_train, group, seed, replicates
         _call("mdl_boot_surv_counts", z, time, ldt, event, lde, train_idx, n_train, P, n_max, S, group, int(seed) & 0xFFFFFFFFFFFFFFFF, R,
               counts, _stream(), unsupported=_boot_refusal(n_max, 2, S, R))
     return counts
+
+
+# ---- X1-X2: patch contributions of a linear probe's decision (include/madeleine_amd_explain.h).  Forward only, no autograd ----
+CONTRIB_MAX_C = _native.EXPLAIN_DEFINES["MDL_CONTRIB_MAX_C"]
+CONTRIB_ROWS = _native.EXPLAIN_DEFINES["MDL_CONTRIB_ROWS"]
+CONTRIB_STATS = ("sum", "pos", "neg", "absmax")      # the second axis of contrib_stats' result
+if any(_native.EXPLAIN_DEFINES["MDL_CONTRIB_" + s.upper()] != i for i, s in enumerate(CONTRIB_STATS)):
+    raise ImportError("madeleine_amd: CONTRIB_STATS does not match the MDL_CONTRIB_* indices of %s" % _native._build.EXPLAIN_HEADER)
+_CONTRIB_LIMITS = ("patch contributions support 1, 2, 4 or 8 heads of %d channels, 1..%d decision columns and T, R and the launch grids "
+                   "within int32 (got T %d, R %d, H %d, C %d)")
+
+
+def _unit_cols(t, name, fn):
+    """(rows, cols, row stride) of a 2-D device tensor with unit column stride (any row stride)."""
+    if t.dim() != 2 or not t.is_cuda or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise RuntimeError("madeleine_amd: %s needs %s [rows, cols] on a ROCm device with unit column stride" % (fn, name))
+    return t.shape[0], t.shape[1], (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def attn_contrib(E, attn, U, per_head=False):
+    """contribution [T, C] (with per_head=True: (contribution, per_head [T, H, C])) of the head-major token embeddings E [T, H * 512]
+    (fp32 or bf16, unit column stride, any row stride), the attention weights attn [T, H] fp32 (likewise) and the decision directions
+    U [C, H * 512] fp32 (MADELEINE.slide_directions): per_head[t, h, c] = attn[t, h] <U[c, h], E[t, h]>, contribution = the heads added
+    in ascending order (X1 of include/madeleine_amd_explain.h; row-local, fixed summation order).  One launch on the current stream, no
+    host read."""
+    if E.dtype not in ACT_DTYPES:
+        raise RuntimeError("madeleine_amd: E must be float32 or bfloat16 (got %s)" % E.dtype)
+    T, HW, ldE = _unit_cols(E, "E", "attn_contrib")
+    Ta, H, ldA = _unit_cols(attn, "attn", "attn_contrib")
+    _require(U, "U")
+    if attn.dtype != torch.float32 or Ta != T or H < 1 or HW != H * HID or U.dim() != 2 or U.shape[0] < 1 or U.shape[1] != HW:
+        raise RuntimeError("madeleine_amd: attn_contrib needs E [T, H * %d], attn [T, H] float32 and U [C, H * %d] (got %s, %s, %s)"
+                           % (HID, HID, tuple(E.shape), tuple(attn.shape), tuple(U.shape)))
+    C, dev = U.shape[0], E.device
+    total = torch.empty(T, C, device=dev, dtype=torch.float32)
+    heads = torch.empty(T, H, C, device=dev, dtype=torch.float32) if per_head else None
+    with _timed("attn_contrib", ("byte", float(T) * (HW * E.element_size() + 4 * H + 4 * C * (1 + (H if per_head else 0))))):
+        _call("mdl_attn_contrib", E, ldE, 1 if E.dtype == torch.bfloat16 else 0, attn, ldA, U, T, H, HID, C, heads, total, C, _stream(),
+              unsupported=(_CONTRIB_LIMITS, HID, CONTRIB_MAX_C, T, 0, H, C))
+    return (total, heads) if per_head else total
+
+
+def contrib_stats(contrib, cu):
+    """stats [R, 4, C] fp32 of contrib [T, C] (fp32, unit column stride, any row stride) over the bags of cu int64 [R + 1] on the device:
+    per bag and column the sum, the sum of the positive terms, the sum of the negative terms and max |.| (CONTRIB_STATS; X2 of include/
+    madeleine_amd_explain.h: chunks of CONTRIB_ROWS rows combined in ascending order, a bag's bits depend on the bag alone, an empty
+    bag gives zeros).  Three launches on the current stream, no host read."""
+    T, C, ld = _unit_cols(contrib, "contrib", "contrib_stats")
+    if contrib.dtype != torch.float32 or C < 1:
+        raise RuntimeError("madeleine_amd: contrib_stats needs contrib [T, C] float32, C >= 1")
+    _require(cu, "cu_seqlens", torch.int64)
+    if cu.dim() != 1 or cu.numel() < 1:
+        raise RuntimeError("madeleine_amd: cu_seqlens must be [R + 1]")
+    R, dev = cu.numel() - 1, contrib.device
+    if R == 0 or T == 0:      # nothing is launched: the zeros of empty bags are written here
+        return torch.zeros(R, 4, C, device=dev, dtype=torch.float32)
+    refusal = (_CONTRIB_LIMITS, HID, CONTRIB_MAX_C, T, R, 0, C)
+    stats = torch.empty(R, 4, C, device=dev, dtype=torch.float32)
+    ws = _ws_for("mdl_contrib_stats_ws_bytes", dev, T, R, C, refusal=refusal)
+    with _timed("contrib_stats", ("byte", 4.0 * T * C)):
+        _call("mdl_contrib_stats", contrib, ld, cu, T, R, C, stats, ws, _stream(), unsupported=refusal)
+    return stats

@@ -588,6 +588,105 @@ class MADELEINE(nn.Module):
         pooled, scores = emb.pool_headmajor_ragged(E, cu_d, max(lens), e_img=e_img)
         return self._project_slide(pooled), scores.reshape(tokens.shape[0], H)
 
+    def decision_rows(self, W, b=None):
+        """(W [C, d] fp32, b [C] fp32) on the projector's device from what slide_directions accepts.  ValueError for another shape, a
+        width other than the projector's output, or a bias that is not one value per row."""
+        proj = self.projector
+        d, dev = proj.out_features, proj.weight.device
+        W = torch.as_tensor(W, dtype=torch.float32, device=dev)
+        if W.dim() == 1:
+            W = W.unsqueeze(0)
+        if W.dim() != 2 or W.shape[0] < 1:
+            raise ValueError("slide_directions needs W [d] or [C, d] (got %s)" % (tuple(W.shape),))
+        if W.shape[1] != d:
+            raise ValueError("slide_directions: W is %d wide, the projector's output is %d" % (W.shape[1], d))
+        C = W.shape[0]
+        bias = torch.zeros(C, device=dev) if b is None else torch.as_tensor(b, dtype=torch.float32, device=dev).reshape(-1)
+        if bias.numel() == 1 and C > 1:
+            bias = bias.expand(C)
+        if bias.numel() != C:
+            raise ValueError("slide_directions: b must hold one value per row of W (%d, got %d)" % (C, bias.numel()))
+        return W.contiguous(), bias.contiguous()
+
+    def slide_directions(self, W, b=None):
+        """(U [C, H * 512] head-major, const [C]) of the linear decision z = W . slide_embedding + b: U = W . P_hm with P_hm the
+        projector's weight with head-major columns, const = W . projector.bias + b, so that z_c = sum_t sum_h a[t, h] <U[c, h], E[t, h]>
+        + const_c exactly (include/madeleine_amd_explain.h).  W: [d], [C, d] or a slice of probe.fit_logistic's [P, cols, d] /
+        survival.fit_cox's [P, d] weights, d the projector's output width; b: None, a number, [C] or the matching slice of the
+        biases.  fp32, without autograd, through functional.linear (no library GEMM).  ValueError for another shape or width."""
+        W, bias = self.decision_rows(W, b)
+        proj, d = self.projector, self.projector.out_features
+        with torch.no_grad(), torch.autocast(device_type="cuda", enabled=False):
+            # one product for both: the rows of [P_hm^T ; projector.bias ; 0 0 0] against W (zero rows: a row count in fours)
+            p_hm = self.wsi_embedders.permuted(proj.weight, 1)
+            rows = torch.cat([p_hm.t(), proj.bias.unsqueeze(0), proj.bias.new_zeros(3, d)]).contiguous()
+            out = MF.linear(W.contiguous(), rows)
+            n = proj.in_features
+            return out[:, :n].contiguous(), out[:, n] + bias
+
+    def explain_packed(self, packed, device, U, stain_idx=None, per_head=False):
+        """attend_packed with the token embeddings contracted against the decision directions U [C, H * 512] of slide_directions where
+        they are produced: -> (embeds [R, 512], raw scores [T, H], attention [T, H], contribution [T, C][, per_head [T, H, C]]), with
+        contribution[t, c] the signed share of packed token t in decision column c (functional.attn_contrib), so that per bag
+        sum_t contribution + const = W . embeds + b.  The routes, the stain rule and the argument checks are attend_packed's; E is asked
+        for itself (fp32, or bf16 under autocast) and dropped when the call returns.  The attention is formed from the scores of this
+        call: functional.attn_softmax over the pack's cu_seqlens (built from the lengths where the bag-by-bag route got none), or
+        abmil.activate for the relu, leaky_relu and sigmoid activations.  `embeds` are the embeddings the contributions decompose."""
+        tokens, cu_d, lens = (packed.tokens, packed.cu_seqlens, packed.lens) if hasattr(packed, "tokens") else packed
+        lens = [int(n) for n in lens]
+        if tokens.dim() != 2 or not lens or min(lens) < 1 or tokens.shape[0] != sum(lens):
+            raise ValueError("explain_packed needs tokens [sum(lens), D] and at least one bag, every bag of at least one row")
+        tokens = tokens.to(device)
+        emb = self.wsi_embedders
+        R, H = len(lens), emb.n_heads
+        if U.dim() != 2 or U.shape[1] != H * MF.HID:
+            raise ValueError("explain_packed needs U [C, %d] (slide_directions; got %s)" % (H * MF.HID, tuple(U.shape)))
+        key = 0 if stain_idx is None else int(stain_idx)
+        if self.stain_encoding and not 0 <= key < len(self.modalities):
+            raise IndexError("explain_packed: stain_idx must be in [0, %d) (got %r)" % (len(self.modalities), stain_idx))
+        act = emb.attn[0].activation
+        by_bag = self._encodes_bag_by_bag(R)
+        if cu_d is None and by_bag:
+            cu = torch.zeros(R + 1, dtype=torch.int64)
+            cu[1:] = torch.cumsum(torch.tensor(lens, dtype=torch.int64), 0)
+            cu_d = MF.h2d(cu, device)
+        if cu_d is None or cu_d.numel() != R + 1:
+            raise ValueError("explain_packed needs cu_seqlens [len(lens) + 1] on the device")
+        cu_d = cu_d.to(device)
+
+        def weights(scores, cu):
+            return MF.attn_softmax(scores, cu)[0] if act == 'softmax' else activate(scores, act)
+
+        if by_bag:
+            embeds, raws, attns, outs = [], [], [], []
+            for r, (n, e) in enumerate(zip(lens, np.cumsum(lens).tolist())):
+                stain = self._stain_groups(torch.full((1,), key, dtype=torch.long), 1, n, device) if self.stain_encoding else None
+                E, e_img = emb.embed_tokens_headmajor(tokens[e - n:e].unsqueeze(0), return_image=True, want_fp32=True, stain=stain)
+                pooled, _, scores = emb.forward_headmajor_from_tokens(E, 1, e_img)
+                scores = scores.reshape(n, H).float().contiguous()
+                attn = weights(scores, cu_d[r:r + 2] - cu_d[r:r + 1])      # a bag's softmax depends on its own scores alone
+                embeds.append(self._project_slide(pooled))
+                raws.append(scores)
+                attns.append(attn)
+                outs.append(MF.attn_contrib(E.detach().view(n, -1), attn, U, per_head))
+                del E, e_img
+            res = (torch.cat(embeds), torch.cat(raws), torch.cat(attns))
+            if per_head:
+                return res + (torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]))
+            return res + (torch.cat(outs),)
+        stain = None
+        if self.stain_encoding:
+            row_bag = getattr(packed, "row_bag", None)
+            if row_bag is None:
+                row_bag = MF.h2d(torch.repeat_interleave(torch.arange(R, dtype=torch.int32), torch.tensor(lens)), device)
+            stain = (self.embedding(MF.h2d(torch.full((R,), key, dtype=torch.long), device)), row_bag.to(device), cu_d)
+        E, e_img = emb.embed_tokens_headmajor(tokens, return_image=True, want_fp32=True, stain=stain)
+        pooled, scores = emb.pool_headmajor_ragged(E, cu_d, max(lens), e_img=e_img)
+        scores = scores.reshape(tokens.shape[0], H).float().contiguous()
+        attn = weights(scores, cu_d)
+        out = MF.attn_contrib(E.detach(), attn, U, per_head)
+        return (self._project_slide(pooled), scores, attn) + (out if per_head else (out,))
+
     def forward_ragged(self, bags, device, n_loss_tokens=None, n_views=1, modality_labels=None):
         """Variable-length bags (BASELINE config 5) -- NEW functionality: the reference can only torch.stack equal-N
         bags (wsi_dataset.py:89-92).  `bags` is a list over cases of lists over modalities of [N_bm, D] tensors.

@@ -652,6 +652,128 @@ class DeviceSlideStore:
         res.update(out, values=values)
         return res
 
+    @staticmethod
+    def _column_blocks(C):
+        """C columns as blocks of 8, 4, 2 and 1: the widths functional.attn_rank serves, read in place through its row stride."""
+        blocks, c0 = [], 0
+        for w in (8, 4, 2, 1):
+            while C - c0 >= w:
+                blocks.append((c0, w))
+                c0 += w
+        return blocks
+
+    def contributions(self, model, W, b=None, modality=0, case_indices=None, topk=0, per_head=False, bags_per_launch=None,
+                      precision=None, host_wgs=0) -> dict:
+        """Which patches made the linear decision z = W . embedding + b of one stain's bag of every case asked for: the exact split of z
+        into one signed term per patch (include/madeleine_amd_explain.h), with attention()'s planning, grouping, eval mode under
+        torch.no_grad() (the training flag is restored), autocast rule and stain rule, through model.explain_packed.  W, b: as
+        MADELEINE.slide_directions ([d], [C, d], or a slice of fit_logistic's / fit_cox's weights and biases), at most
+        functional.CONTRIB_MAX_C rows.  The token embeddings of one group are dropped before the next group is packed.  Returns, on the
+        device unless said otherwise,
+          embeds, cases, slide_ids, cu_seqlens, lens, raw, attention      as attention()
+          contribution [T, C]                           the share of every patch in every decision column
+          per_head [T, H, C] or None                    the same per attention head (contribution = the heads added in ascending order)
+          const [C]                                     W . projector.bias + b: what no patch accounts for
+          decision [n, C]                               embeds . W^T + b, so that stats[:, 0] + const = decision up to rounding
+          stats [n, 4, C]                               per bag and column: sum, sum of the positive terms, sum of the negative terms,
+                                                        max |.| (functional.CONTRIB_STATS)
+          top_pos_idx, top_pos_val [n, C, topk]         the topk most positive patches per bag and column: the row inside the bag and
+          top_neg_idx, top_neg_val [n, C, topk]         its contribution; likewise the most negative.  Ties: the lower row first; a
+                                                        bag shorter than topk is padded with -1 and -inf / +inf.  None for topk == 0
+        The statistics and the top-k of the whole result come from one launch sequence each (functional.contrib_stats / attn_rank);
+        the loop reads nothing back and the result does not depend on bags_per_launch."""
+        self._require_device("contributions")
+        cases, _, lens = self._modality_plan(case_indices, modality)
+        reduced = precision in (torch.bfloat16, torch.float16)
+        groups = self._launch_groups(cases, lens, bags_per_launch, reduced)
+        stain_idx = modality if getattr(model, "stain_encoding", False) else None
+        rows, bias = model.decision_rows(W, b)
+        U, const = model.slide_directions(rows, bias)
+        C, H = U.shape[0], model.wsi_embedders.n_heads
+        was_training = model.training
+        model.eval()
+        parts = [[], [], [], [], []]      # embeds, raw, attention, contribution, per_head
+        try:
+            with torch.no_grad():
+                for group in groups:
+                    packed = self.pack_modality(group, modality, host_wgs=host_wgs)
+                    with torch.autocast(device_type="cuda", dtype=precision if reduced else None, enabled=reduced):
+                        out = model.explain_packed(packed, self.device, U, stain_idx=stain_idx, per_head=per_head)
+                    for acc, t in zip(parts, out):
+                        acc.append(t.float())
+        finally:
+            model.train(was_training)
+        n = cases.numel()
+        cu = torch.zeros(n + 1, dtype=torch.int64)
+        torch.cumsum(lens, 0, out=cu[1:])
+        cu_d = MF.h2d(cu, self.device)
+
+        def joined(acc, *shape):
+            return torch.cat(acc).contiguous() if acc else torch.zeros(*shape, dtype=torch.float32, device=self.device)
+
+        res = self._embedding_result(joined(parts[0], 0, 512), cases)
+        contribution = joined(parts[3], 0, C)
+        with torch.no_grad(), torch.autocast(device_type="cuda", enabled=False):
+            rows4 = torch.cat([rows, rows.new_zeros(-C % 4, rows.shape[1])]).contiguous()      # functional.linear: row counts in fours
+            decision = torch.cat([MF.linear(e, rows4)[:, :C] for e in res["embeds"].split(256)]) + bias if n else \
+                torch.zeros(0, C, dtype=torch.float32, device=self.device)
+        res.update(cu_seqlens=cu_d, lens=lens.tolist(), raw=joined(parts[1], 0, H), attention=joined(parts[2], 0, H),
+                   contribution=contribution, per_head=joined(parts[4], 0, H, C) if per_head else None, const=const, decision=decision,
+                   stats=MF.contrib_stats(contribution, cu_d), top_pos_idx=None, top_pos_val=None, top_neg_idx=None, top_neg_val=None)
+        k = int(topk)
+        if k > 0:
+            negated = -contribution
+            for name, src, sign in (("top_pos", contribution, 1.0), ("top_neg", negated, -1.0)):
+                idx, val = [], []
+                for c0, w in self._column_blocks(C):
+                    _, _, ti, tv = MF.attn_rank(src[:, c0:c0 + w], cu_d, k=k, percentile=False)
+                    idx.append(ti)
+                    val.append(tv * sign)
+                res[name + "_idx"], res[name + "_val"] = torch.cat(idx, 1), torch.cat(val, 1)
+        return res
+
+    def contribution_maps(self, model, W, b=None, modality=0, case_indices=None, columns=None, downsample=None, sigma=0.0,
+                          cmap='coolwarm', alpha=255, thumbnails=None, crop=False, max_bytes=None, bags_per_launch=None, precision=None,
+                          host_wgs=0) -> dict:
+        """Signed evidence maps of the linear decision z = W . embedding + b: contributions(), then heatmap.render over the store's
+        coordinates exactly as heatmaps() calls it, one channel per decision column (columns: a list of column indices, None: all).
+        The value of a patch is 0.5 + 0.5 c / max_t |c| per bag and column, so that no evidence is the midpoint of a diverging
+        colour map ('coolwarm': evidence against is blue, for is red), the strongest patch of the bag reaches one end, and a bag
+        without any evidence is 0.5 everywhere.  A NaN contribution stays NaN (the renderer leaves such a patch out); it makes
+        max |.| of its bag and column NaN too, so that whole channel of the bag is left out.  Returns contributions()'s bag-level keys
+        (embeds, cases, slide_ids, cu_seqlens, lens, const, decision, stats) plus render's rgba, level, covered, canvas and
+        downsample, and values [T, len(columns)]."""
+        from . import heatmap as HM
+        self._require_device("contribution_maps")
+        if self.coords is None:
+            raise RuntimeError("DeviceSlideStore.contribution_maps: the store holds no coordinates (set_coords)")
+        con = self.contributions(model, W, b, modality, case_indices, bags_per_launch=bags_per_launch, precision=precision,
+                                 host_wgs=host_wgs)
+        cases, cu = con["cases"], con["cu_seqlens"]
+        c, amax = con["contribution"], con["stats"][:, MF.CONTRIB_STATS.index("absmax")]
+        if columns is not None:
+            cols = [int(j) for j in columns]
+            if not cols or min(cols) < 0 or max(cols) >= c.shape[1]:
+                raise IndexError("DeviceSlideStore.contribution_maps: columns must name decision columns in [0, %d) (got %r)"
+                                 % (c.shape[1], columns))
+            sel = MF.h2d(torch.tensor(cols, dtype=torch.long), self.device)
+            c, amax = c.index_select(1, sel), amax.index_select(1, sel)
+        scale = torch.repeat_interleave(amax, cu[1:] - cu[:-1], dim=0, output_size=c.shape[0])
+        values = torch.where(scale == 0, torch.full_like(c, 0.5), 0.5 + 0.5 * c / scale)
+        bag = self.bag_table[:, modality].index_select(0, cases).long()
+        sizes = self.patch_sizes.index_select(0, bag)
+        if downsample is None:
+            if sizes.numel() and int(sizes.min()) != int(sizes.max()):
+                raise ValueError("DeviceSlideStore.contribution_maps: downsample None means the patch size, and the bags asked for have "
+                                 "patch sizes %d .. %d" % (int(sizes.min()), int(sizes.max())))
+            downsample = int(sizes[0]) if sizes.numel() else 1
+        out = HM.render(self.coords_of(cases, modality), cu, values, sizes, downsample, sigma, cmap, alpha, thumbnails, crop,
+                        extents=self.coord_extents.index_select(0, bag), max_bytes=HM.RENDER_BYTES if max_bytes is None else max_bytes,
+                        lens=con["lens"])
+        res = {k: con[k] for k in ("embeds", "cases", "slide_ids", "cu_seqlens", "lens", "const", "decision", "stats")}
+        res.update(out, values=values)
+        return res
+
     def packed_batches(self, batch_size, max_tokens=None, shuffle=True, drop_last=False, seed=0, rank=0, world_size=1, prefetch=None):
         """Re-iterable over {'packed': PackedBags, 'modality_labels', 'slide_ids'}: the ragged batches of ragged_batches() in packed
         form, from a store of any dtype, every bag cut to at most max_tokens rows.  Plan, sharding, set_epoch and the draw counter are
