@@ -491,8 +491,9 @@ extern "C" int mdl_split_image(const float* X, int64_t ldx, int64_t rows, int K,
     return MDL_OK;
 }
 
-/* Row-scaled split image of X [rows, K]: row r scaled by its own power of two s_r (max |s_r X[r][:]| in [2^13, 2^14); 1 for a zero row);
- * row_inv (device float[rows]) receives 1 / s_r, scale = {1, max |X|}.  As the A operand of mdl_split_gemm_nt pass a_row_mul = row_inv. */
+/* Row-scaled split image of X [rows, K]: row r scaled by its own power of two s_r (max |s_r X[r][:]| in [2^13, 2^14)); row_inv (device
+ * float[rows]) receives 1 / s_r -- 0 for an all-zero row, which has no scale: its image row is zero -- and scale, where given, = {1, max |X|}.
+ * As the A operand of mdl_split_gemm_nt pass a_row_mul = row_inv. */
 extern "C" int mdl_split_image_rows(const float* X, int64_t ldx, int64_t rows, int K, void* img, int64_t rsb, int64_t pad_rows,
                                     float* row_inv, float* scale, void* stream) {
     if (!X || !img || !row_inv || rows < 0 || K < 32 || (K % 32) || ldx < K || (ldx & 3) || rsb < (int64_t)K * 4 || (rsb & 15) ||
