@@ -367,21 +367,46 @@ __global__ __launch_bounds__(SP_THREADS) void sp_gate_dx_kernel(const char* __re
         __syncthreads();
     }
     const float* dpb = pt.d_pooled + n0;
-    auto emit = [&](int row, int col, const f32x4& v) {
-        f32x4* o = reinterpret_cast<f32x4*>(ob + (int64_t)row * ld4 + (uint32_t)col * 4u);
-        f32x4 r = v * inv;
-        if (pt.scores) {  // + w[t,c] * d_pooled[bag(t), c, :]  (cache-resident row)
-            const float w = rw_s[row];
-            const f32x4 dp = *reinterpret_cast<const f32x4*>(dpb + (ro_s[row] + col));
+    // One epilogue per mode (sp_epilogue_rows_ld, split_engine.hpp): no pooling term | the tile inside ONE bag (bags are contiguous: its
+    // first and last valid rows share a bag), the lane's d_pooled vector loaded once | rows of several bags, the d_pooled vectors of a
+    // group of rows loaded ahead of the group; the old dE likewise.  No memory wait between the stores of a group.
+    const int rows_valid = t0 + SPM <= T ? SPM : (int)(T - t0);
+    constexpr int DX_ACC = 1, DX_POOL = 2, DX_ONE_BAG = 4;
+    int mode = accumulate ? DX_ACC : 0;
+    if (pt.scores) mode |= __builtin_amdgcn_readfirstlane(ro_s[0] == ro_s[rows_valid - 1]) ? DX_POOL | DX_ONE_BAG : DX_POOL;
+    static_assert(SPNCT == 2, "one column vector per lane");
+    const int lcol = wn * SP_WCOLS + (lane & 15) * 4;
+    sp_mode_switch<3>(mode, [&](auto tag) {
+        constexpr int MD = decltype(tag)::value;
+        if constexpr (!(MD & DX_ONE_BAG) || (MD & DX_POOL)) {   // (one bag without a pooling term: no such mode)
+            f32x4 dp1 = {};
+            if constexpr (MD & DX_ONE_BAG) dp1 = *reinterpret_cast<const f32x4*>(dpb + (ro_s[0] + lcol));
+            f32x4 dpv[2], oc[2];
+            auto pre = [&](int j, int row, int col, int, bool valid) {   // (an invalid row reads row 0 instead; its value is dropped)
+                const int rl = valid ? row : 0;
+                if constexpr ((MD & DX_POOL) && !(MD & DX_ONE_BAG)) dpv[j] = *reinterpret_cast<const f32x4*>(dpb + (ro_s[rl] + col));
+                if constexpr (MD & DX_ACC) oc[j] = *reinterpret_cast<const f32x4*>(ob + (int64_t)rl * ld4 + (uint32_t)col * 4u);
+            };
+            auto emit = [&](int j, int row, int col, int, const f32x4& v, bool valid) {
+#pragma clang fp contract(off)
+                f32x4 r = v * inv;
+                if constexpr (MD & DX_POOL) {  // + w[t,c] * d_pooled[bag(t), c, :]  (cache-resident row)
+                    const float w = rw_s[row];
+                    const f32x4 dp = (MD & DX_ONE_BAG) ? dp1 : dpv[j];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) r[i] = fmaf(w, dp[i], r[i]);
+                    for (int i = 0; i < 4; ++i) r[i] = fmaf(w, dp[i], r[i]);
+                }
+                if constexpr (MD & DX_ACC) r += oc[j];
+                sp_keep(r);
+                if (valid) {
+                    *reinterpret_cast<f32x4*>(ob + (int64_t)row * ld4 + (uint32_t)col * 4u) = r;
+                    amax = fmaxf(fmaxf(amax, fmaxf(fabsf(r.x), fabsf(r.y))), fmaxf(fabsf(r.z), fabsf(r.w)));
+                }
+            };
+            if (rows_valid == SPM) sp_epilogue_rows_ld<true, 2>(acc, sm, wave, wm, wn, lane, SPM, pre, emit);
+            else sp_epilogue_rows_ld<false, 2>(acc, sm, wave, wm, wn, lane, rows_valid, pre, emit);
         }
-        if (accumulate) r += *o;
-        *o = r;
-        amax = fmaxf(fmaxf(amax, fmaxf(fabsf(r.x), fabsf(r.y))), fmaxf(fabsf(r.z), fabsf(r.w)));
-    };
-    if (t0 + SPM <= T) sp_epilogue_rows<true, 2>(acc, sm, wave, wm, wn, lane, SPM, emit);
-    else sp_epilogue_rows<false, 2>(acc, sm, wave, wm, wn, lane, (int)(T - t0), emit);
+    });
     if (absmax_out) sp_block_absmax(absmax_out, amax, reinterpret_cast<float*>(&sm.B[1][0]));   // B[0] holds the row factors
 }
 

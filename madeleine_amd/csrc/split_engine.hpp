@@ -438,9 +438,11 @@ __device__ __forceinline__ void sp_nt_tall_mainloop(SmemSPT& sm, SpAccT& acc, in
     __syncthreads();   // staging memory is free for the epilogue
 #undef SPT_SET
 }
-// the wave's 64 x 128 sub-tile as row-contiguous float4s: emit(row, col, v) in tile coordinates (sp_epilogue_rows for the tall tile)
-template <bool FULL, int INFLIGHT = 4, class Emit>
-__device__ __forceinline__ void sp_epilogue_rows_tall(const SpAccT& acc, SmemSPT& sm, int wave, int lane, int rows_valid, Emit&& emit) {
+// the wave's 64 x 128 sub-tile as row-contiguous float4s (sp_epilogue_rows_ld / sp_epilogue_rows for the tall tile; cp = 0 | 1 is the
+// lane's column pass, col = cp * 64 + (lane & 15) * 4)
+template <bool FULL, int INFLIGHT = 4, class Pre, class Emit>
+__device__ __forceinline__ void sp_epilogue_rows_tall_ld(const SpAccT& acc, SmemSPT& sm, int wave, int lane, int rows_valid, Pre&& pre,
+                                                         Emit&& emit) {
     float* tile = reinterpret_cast<float*>(&sm) + wave * (32 * 64);
     const int l32 = lane & 31, rl = lane >> 4, c4 = lane & 15;
 #pragma unroll
@@ -453,6 +455,11 @@ __device__ __forceinline__ void sp_epilogue_rows_tall(const SpAccT& acc, SmemSPT
                 for (int c2 = 0; c2 < 2; ++c2) tile[acc_row(r, lane) * 64 + c2 * 32 + l32] = acc[rt][cp * 2 + c2][r];
 #pragma unroll
             for (int h = 0; h < 8 / INFLIGHT; ++h) {
+#pragma unroll
+                for (int j = 0; j < INFLIGHT; ++j) {
+                    const int row = wave * 64 + rt * 32 + (h * INFLIGHT + j) * 4 + rl;
+                    pre(j, row, cp * 64 + c4 * 4, cp, FULL || row < rows_valid);
+                }
                 f32x4 v[INFLIGHT];
 #pragma unroll
                 for (int j = 0; j < INFLIGHT; ++j)
@@ -460,11 +467,19 @@ __device__ __forceinline__ void sp_epilogue_rows_tall(const SpAccT& acc, SmemSPT
 #pragma unroll
                 for (int j = 0; j < INFLIGHT; ++j) {
                     const int row = wave * 64 + rt * 32 + (h * INFLIGHT + j) * 4 + rl;
-                    if (FULL || row < rows_valid) emit(row, cp * 64 + c4 * 4, v[j]);
+                    emit(j, row, cp * 64 + c4 * 4, cp, v[j], FULL || row < rows_valid);
                 }
                 SP_SB();
             }
         }
+}
+template <bool FULL, int INFLIGHT = 4, class Emit>
+__device__ __forceinline__ void sp_epilogue_rows_tall(const SpAccT& acc, SmemSPT& sm, int wave, int lane, int rows_valid, Emit&& emit) {
+    sp_epilogue_rows_tall_ld<FULL, INFLIGHT>(
+        acc, sm, wave, lane, rows_valid, [](int, int, int, int, bool) {},
+        [&](int, int row, int col, int, const f32x4& v, bool valid) {
+            if (valid) emit(row, col, v);
+        });
 }
 
 // ---- TN ---------------------------------------------------------------------------------------------------------------------------
@@ -718,9 +733,21 @@ __device__ __forceinline__ void sp_tn_mainloop3(SmemSP3& sm, SpAcc& acc, int64_t
 // Hands the wave's 128 x SP_WCOLS sub-tile to emit(row, col, v) as row-contiguous float4s: columns col .. col + 3 of tile row `row` (tile
 // coordinates); 16 lanes cover 256 contiguous bytes of a row.  FULL = false skips rows >= rows_valid.  Call after the main loop
 // returned (staging memory free); wave-private LDS regions ([32][64] floats per wave), no block barrier inside.
-template <bool FULL, int INFLIGHT = 4, class Emit>
-__device__ __forceinline__ void sp_epilogue_rows(const SpAcc& acc, SmemSP& sm, int wave, int wm, int wn, int lane, int rows_valid,
-                                                 Emit&& emit) {
+//
+// sp_epilogue_rows_ld is the form for epilogues that read global memory per element (an old C, a bias row per row group): the rows go
+// out in groups of INFLIGHT, and pre(j, row, col, cp, valid) -- slot j < INFLIGHT of the group, cp the lane's column pass (always 0 on
+// this tile), valid = the row is below rows_valid -- is called for every row of a group BEFORE the group's LDS reads,
+// emit(j, row, col, cp, v, valid) after them.  A kernel issues its per-element loads into slot j's registers in pre and uses them in
+// emit: the loads of a group are then in flight together and their wait falls once per group, ahead of the group's stores, never
+// between two stores (vmcnt counts stores as well as loads here: a wait between two stores also waits for the first one's
+// acknowledgement).  Both are called for invalid rows too, so that a kernel can keep its loads and arithmetic free of branches (an
+// address clamped to a valid element, the value dropped) and predicate the store alone: behind a lane-dependent branch the compiler
+// waits for ALL memory operations again.  Operands that depend on the column alone belong in registers
+// loaded before the call, operands that depend on the row alone in LDS (staging memory past the transpose area); which operands exist
+// is decided by the caller around the whole call (sp_mode_switch), never per store.
+template <bool FULL, int INFLIGHT = 4, class Pre, class Emit>
+__device__ __forceinline__ void sp_epilogue_rows_ld(const SpAcc& acc, SmemSP& sm, int wave, int wm, int wn, int lane, int rows_valid,
+                                                    Pre&& pre, Emit&& emit) {
     float* tile = reinterpret_cast<float*>(&sm) + wave * (32 * 64);
     const int l32 = lane & 31, rl = lane >> 4, c4 = lane & 15;
 #pragma unroll
@@ -733,6 +760,11 @@ __device__ __forceinline__ void sp_epilogue_rows(const SpAcc& acc, SmemSP& sm, i
                 for (int c2 = 0; c2 < 2; ++c2) tile[acc_row(r, lane) * 64 + c2 * 32 + l32] = acc[rt][cp * 2 + c2][r];
 #pragma unroll
             for (int h = 0; h < 8 / INFLIGHT; ++h) {   // INFLIGHT reads in flight, then their consumers (bounds the VGPRs)
+#pragma unroll
+                for (int j = 0; j < INFLIGHT; ++j) {
+                    const int row = wm * 128 + rt * 32 + (h * INFLIGHT + j) * 4 + rl;
+                    pre(j, row, wn * SP_WCOLS + cp * 64 + c4 * 4, cp, FULL || row < rows_valid);
+                }
                 f32x4 v[INFLIGHT];
 #pragma unroll
                 for (int j = 0; j < INFLIGHT; ++j)
@@ -740,11 +772,37 @@ __device__ __forceinline__ void sp_epilogue_rows(const SpAcc& acc, SmemSP& sm, i
 #pragma unroll
                 for (int j = 0; j < INFLIGHT; ++j) {
                     const int row = wm * 128 + rt * 32 + (h * INFLIGHT + j) * 4 + rl;
-                    if (FULL || row < rows_valid) emit(row, wn * SP_WCOLS + cp * 64 + c4 * 4, v[j]);
+                    emit(j, row, wn * SP_WCOLS + cp * 64 + c4 * 4, cp, v[j], FULL || row < rows_valid);
                 }
                 SP_SB();
             }
         }
+}
+template <bool FULL, int INFLIGHT = 4, class Emit>
+__device__ __forceinline__ void sp_epilogue_rows(const SpAcc& acc, SmemSP& sm, int wave, int wm, int wn, int lane, int rows_valid,
+                                                 Emit&& emit) {
+    sp_epilogue_rows_ld<FULL, INFLIGHT>(
+        acc, sm, wave, wm, wn, lane, rows_valid, [](int, int, int, int, bool) {},
+        [&](int, int row, int col, int, const f32x4& v, bool valid) {
+            if (valid) emit(row, col, v);
+        });
+}
+// Pins the arithmetic that produced x where it stands: without it the compiler sinks an epilogue's arithmetic into the lane-predicated
+// block of the store, the wait for the operands' loads with it, and behind a lane-dependent branch that wait is a full one again.
+__device__ __forceinline__ void sp_keep(const f32x4& x) { asm volatile("" ::"v"(x)); }
+// Calls f(SpTag<m>{}) with m = the low NB bits of `mode` as a compile-time constant: one wave-uniform branch tree around whatever f
+// does, so that an epilogue is compiled once per set of optional operands instead of testing each pointer at every store.
+// (the optional operands of the NT epilogues, as bits of such a mode)
+constexpr int SP_EP_ROWMUL = 1, SP_EP_COLMUL = 2, SP_EP_BIAS = 4, SP_EP_ACC = 8, SP_EP_GROUP = 16;
+template <int V>
+struct SpTag {
+    static constexpr int value = V;
+};
+template <int NB, int BASE = 0, class F>
+__device__ __forceinline__ void sp_mode_switch(int mode, F&& f) {
+    if constexpr (NB == 0) f(SpTag<BASE>{});
+    else if (mode & (1 << (NB - 1))) sp_mode_switch<NB - 1, BASE | (1 << (NB - 1))>(mode, f);
+    else sp_mode_switch<NB - 1, BASE>(mode, f);
 }
 
 // absmax bookkeeping: non-negative floats order like their bit patterns

@@ -257,6 +257,13 @@ __global__ __launch_bounds__(SP_THREADS) void sp_nt_kernel(const char* __restric
         voA[i] = (uint32_t)(ra * a_rsb + c * 16);
         voB[i] = (uint32_t)(rb * b_rsb + c * 16);
     }
+    // the row operands of the epilogue, ONCE per tile row (thread r < 256 owns row r; the loads fly behind the main loop)
+    float row_mul = 0.f;
+    int row_grp = 0;
+    if (tid < SPM && m0 + tid < M) {
+        if (a_row_mul) row_mul = a_row_mul[m0 + tid];
+        if (group_bias) row_grp = row_group[m0 + tid];
+    }
     SpAcc acc;
     sp_zero(acc);
     auto dma = [&](int st, int f, int piece) {
@@ -277,22 +284,61 @@ __global__ __launch_bounds__(SP_THREADS) void sp_nt_kernel(const char* __restric
     char* cb = reinterpret_cast<char*>(C + m0 * ldc + n0);
     const uint32_t ldc4 = (uint32_t)ldc * 4u;
     const int cols_valid = N - n0;
-    auto emit = [&](int row, int col, const f32x4& v) {
-        if (col >= cols_valid) return;
-        f32x4 r = v * (a_row_mul ? inv * a_row_mul[m0 + row] : inv);   // row-scaled A image: its row factor (a power of two) comes back here
-        if (b_col_mul) r *= *reinterpret_cast<const f32x4*>(b_col_mul + n0 + col);   // row-scaled B image (a weight: one factor per output column)
-        if (bias) r += *reinterpret_cast<const f32x4*>(bias + n0 + col);
-        if (group_bias) r += *reinterpret_cast<const f32x4*>(group_bias + (int64_t)row_group[m0 + row] * N + n0 + col);
-        f32x4* o = reinterpret_cast<f32x4*>(cb + (int64_t)row * ldc4 + (uint32_t)col * 4u);
-        if (accumulate) r += *o;
-        *o = r;   // (nontemporal stores here: null, 21.60-21.62 vs 21.63-21.64 ms, profiles/r06zc_*)
-        amax = fmaxf(fmaxf(amax, fmaxf(fabsf(r.x), fabsf(r.y))), fmaxf(fabsf(r.z), fabsf(r.w)));
-    };
-    // (Round 6: storing straight from the MFMA accumulator layout -- one dword store of a wave = two whole 128-B lines, no LDS transpose --
-    // measured SLOWER: 262144 x 2048 x 512 1.62 -> 1.84 ms, profiles/r06zb_*: the epilogue is bound by store issue, and 128 dword stores
-    // per wave cost more than 32 dwordx4 ones.)
-    if (m0 + SPM <= M) sp_epilogue_rows<true>(acc, sm, wave, wm, wn, lane, SPM, emit);
-    else sp_epilogue_rows<false>(acc, sm, wave, wm, wn, lane, (int)(M - m0), emit);
+    // row operands -> LDS behind the epilogue's transpose area (the first 64 KiB of the staging memory, free after the main loop): the row
+    // factor of a row-scaled A image (a power of two) already times inv, as every element of the row takes it
+    float* rs_s = reinterpret_cast<float*>(&sm.B[0][0]);
+    int* rg_s = reinterpret_cast<int*>(&sm.B[0][SPM * 4]);
+    if (a_row_mul || group_bias) {   // block-uniform
+        if (tid < SPM) {
+            rs_s[tid] = inv * row_mul;
+            rg_s[tid] = row_grp;
+        }
+        __syncthreads();
+    }
+    // One epilogue per set of optional operands (sp_epilogue_rows_ld): the lane's column operands are loaded once, the row operands come
+    // from LDS, the per-element ones (group-bias row, old C) a group of rows at a time; per element the same operations in the same order
+    // as ever, none contracted into an fma.  (Before: each pointer tested at each store, a load and a full memory wait behind each test,
+    // so that every store also waited for the one before it: DESIGN.md 3.20.)
+    static_assert(SPNCT == 2, "one column vector per lane");
+    const int lcol = wn * SP_WCOLS + (lane & 15) * 4;
+    const int rows_valid = m0 + SPM <= M ? SPM : (int)(M - m0);
+    const int mode = (a_row_mul ? SP_EP_ROWMUL : 0) | (b_col_mul ? SP_EP_COLMUL : 0) | (bias ? SP_EP_BIAS : 0) |
+                     (group_bias ? SP_EP_GROUP : 0) | (accumulate ? SP_EP_ACC : 0);
+    sp_mode_switch<5>(mode, [&](auto tag) {
+        constexpr int MD = decltype(tag)::value;
+        f32x4 cm = {}, cbias = {};
+        const int lcl = lcol < cols_valid ? lcol : 0;
+        if constexpr (MD & SP_EP_COLMUL) cm = *reinterpret_cast<const f32x4*>(b_col_mul + n0 + lcl);   // row-scaled B image (a weight: one factor per output column)
+        if constexpr (MD & SP_EP_BIAS) cbias = *reinterpret_cast<const f32x4*>(bias + n0 + lcl);
+        f32x4 gb[4], oc[4];
+        // (the loads of a row or column outside the tile read a valid element instead; only the store and the absmax are predicated)
+        auto pre = [&](int j, int row, int col, int, bool valid) {
+            const int rl = valid ? row : 0, cl = col < cols_valid ? col : 0;
+            if constexpr (MD & SP_EP_GROUP) gb[j] = *reinterpret_cast<const f32x4*>(group_bias + (int64_t)rg_s[rl] * N + n0 + cl);
+            if constexpr (MD & SP_EP_ACC) oc[j] = *reinterpret_cast<const f32x4*>(cb + (int64_t)rl * ldc4 + (uint32_t)cl * 4u);
+        };
+        auto emit = [&](int j, int row, int col, int, const f32x4& v, bool valid) {
+#pragma clang fp contract(off)
+            const bool ok = valid && col < cols_valid;
+            f32x4 r;
+            if constexpr (MD & SP_EP_ROWMUL) r = v * rs_s[row];
+            else r = v * inv;
+            if constexpr (MD & SP_EP_COLMUL) r *= cm;
+            if constexpr (MD & SP_EP_BIAS) r += cbias;
+            if constexpr (MD & SP_EP_GROUP) r += gb[j];
+            if constexpr (MD & SP_EP_ACC) r += oc[j];
+            sp_keep(r);
+            if (ok) {   // (nontemporal stores here: null, 21.60-21.62 vs 21.63-21.64 ms, profiles/r06zc_*)
+                *reinterpret_cast<f32x4*>(cb + (int64_t)row * ldc4 + (uint32_t)col * 4u) = r;
+                amax = fmaxf(fmaxf(amax, fmaxf(fabsf(r.x), fabsf(r.y))), fmaxf(fabsf(r.z), fabsf(r.w)));
+            }
+        };
+        // (Round 6: storing straight from the MFMA accumulator layout -- one dword store of a wave = two whole 128-B lines, no LDS transpose
+        // -- measured SLOWER: 262144 x 2048 x 512 1.62 -> 1.84 ms, profiles/r06zb_*: 128 dword stores per wave cost more than 32 dwordx4
+        // ones.)
+        if (rows_valid == SPM) sp_epilogue_rows_ld<true>(acc, sm, wave, wm, wn, lane, SPM, pre, emit);
+        else sp_epilogue_rows_ld<false>(acc, sm, wave, wm, wn, lane, rows_valid, pre, emit);
+    });
     if (absmax_out) sp_block_absmax(absmax_out, amax, reinterpret_cast<float*>(&sm.B[1][0]));   // (B stages: outside the epilogue's transpose areas)
 #ifdef MDL_SP_PROBE
     if (tid == 0 && blockIdx.x < 8192) {
@@ -341,6 +387,9 @@ __global__ __launch_bounds__(SP_THREADS) void sp_nt_tall_kernel(const char* __re
         if (row > N - 1) row = N - 1;
         voB[j] = (uint32_t)((int64_t)row * b_rsb + c * 16);
     }
+    static_assert(SP_THREADS == SPT_M, "thread r owns tile row r");
+    float row_mul = 0.f;   // the row factor of every tile row, once (the load flies behind the main loop)
+    if (a_row_mul && m0 + tid < M) row_mul = a_row_mul[m0 + tid];
     SpAccT acc;
     sp_zero(acc);
     sp_nt_tall_mainloop<TERMS>(
@@ -351,18 +400,51 @@ __global__ __launch_bounds__(SP_THREADS) void sp_nt_tall_kernel(const char* __re
     float amax = 0.f;
     char* cb = reinterpret_cast<char*>(C + m0 * ldc);
     const uint32_t ldc4 = (uint32_t)ldc * 4u;
-    auto emit = [&](int row, int col, const f32x4& v) {
-        if (col >= N) return;
-        f32x4 r = v * (a_row_mul ? inv * a_row_mul[m0 + row] : inv);
-        if (b_col_mul) r *= *reinterpret_cast<const f32x4*>(b_col_mul + col);
-        if (bias) r += *reinterpret_cast<const f32x4*>(bias + col);
-        f32x4* o = reinterpret_cast<f32x4*>(cb + (int64_t)row * ldc4 + (uint32_t)col * 4u);
-        if (accumulate) r += *o;
-        *o = r;
-        amax = fmaxf(fmaxf(amax, fmaxf(fabsf(r.x), fabsf(r.y))), fmaxf(fabsf(r.z), fabsf(r.w)));
-    };
-    if (m0 + SPT_M <= M) sp_epilogue_rows_tall<true>(acc, sm, wave, lane, SPT_M, emit);
-    else sp_epilogue_rows_tall<false>(acc, sm, wave, lane, (int)(M - m0), emit);
+    // the epilogue as in sp_nt_kernel: row factors in LDS behind the transpose area (A[0]), two column vectors per lane, one body per mode
+    float* rs_s = reinterpret_cast<float*>(&sm.A[1][0]);
+    if (a_row_mul) {   // block-uniform
+        rs_s[tid] = inv * row_mul;
+        __syncthreads();
+    }
+    const int rows_valid = m0 + SPT_M <= M ? SPT_M : (int)(M - m0);
+    const int mode = (a_row_mul ? SP_EP_ROWMUL : 0) | (b_col_mul ? SP_EP_COLMUL : 0) | (bias ? SP_EP_BIAS : 0) | (accumulate ? SP_EP_ACC : 0);
+    sp_mode_switch<4>(mode, [&](auto tag) {
+        constexpr int MD = decltype(tag)::value;
+        f32x4 cm[2] = {}, cbias[2] = {};
+#pragma unroll
+        for (int cp = 0; cp < 2; ++cp) {
+            const int col = cp * 64 + (lane & 15) * 4, cl = col < N ? col : 0;
+            if constexpr (MD & SP_EP_COLMUL) cm[cp] = *reinterpret_cast<const f32x4*>(b_col_mul + cl);
+            if constexpr (MD & SP_EP_BIAS) cbias[cp] = *reinterpret_cast<const f32x4*>(bias + cl);
+        }
+#pragma unroll
+        for (int cp = 0; cp < 2; ++cp) {   // (both column passes' operands are waited for here, not in front of the second pass's stores)
+            if constexpr (MD & SP_EP_COLMUL) sp_keep(cm[cp]);
+            if constexpr (MD & SP_EP_BIAS) sp_keep(cbias[cp]);
+        }
+        f32x4 oc[4];
+        auto pre = [&](int j, int row, int col, int, bool valid) {
+            const int rl = valid ? row : 0, cl = col < N ? col : 0;
+            if constexpr (MD & SP_EP_ACC) oc[j] = *reinterpret_cast<const f32x4*>(cb + (int64_t)rl * ldc4 + (uint32_t)cl * 4u);
+        };
+        auto emit = [&](int j, int row, int col, int cp, const f32x4& v, bool valid) {
+#pragma clang fp contract(off)
+            const bool ok = valid && col < N;
+            f32x4 r;
+            if constexpr (MD & SP_EP_ROWMUL) r = v * rs_s[row];
+            else r = v * inv;
+            if constexpr (MD & SP_EP_COLMUL) r *= cm[cp];
+            if constexpr (MD & SP_EP_BIAS) r += cbias[cp];
+            if constexpr (MD & SP_EP_ACC) r += oc[j];
+            sp_keep(r);
+            if (ok) {
+                *reinterpret_cast<f32x4*>(cb + (int64_t)row * ldc4 + (uint32_t)col * 4u) = r;
+                amax = fmaxf(fmaxf(amax, fmaxf(fabsf(r.x), fabsf(r.y))), fmaxf(fabsf(r.z), fabsf(r.w)));
+            }
+        };
+        if (rows_valid == SPT_M) sp_epilogue_rows_tall_ld<true>(acc, sm, wave, lane, SPT_M, pre, emit);
+        else sp_epilogue_rows_tall_ld<false>(acc, sm, wave, lane, rows_valid, pre, emit);
+    });
     if (absmax_out) sp_block_absmax(absmax_out, amax, reinterpret_cast<float*>(&sm.B[1][0]));
 }
 

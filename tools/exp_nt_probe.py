@@ -1,6 +1,7 @@
 """Where a tile's time goes in the split NT product: s_memtime stamps of every workgroup (variant library built with -DMDL_SP_PROBE:
 entry | main loop start | main loop end | exit | hardware id), grouped by compute unit: set-up, main loop, epilogue, and the gap between a
-workgroup's exit and the next workgroup's entry on the same unit.  Run with MADELEINE_LIB=tools/ab/probe.so."""
+workgroup's exit and the next workgroup's entry on the same unit.  Run with MADELEINE_LIB=tools/ab/probe.so.  B is a weight image (row-scaled:
+the epilogue takes b_col_mul, as every Linear of the step); with the argument `rows` A is a row-scaled image too (a_row_mul, as in block 1)."""
 import ctypes
 import os
 import sys
@@ -18,9 +19,10 @@ torch.manual_seed(0)
 for (N, K) in [(512, 512), (2048, 512), (512, 2048)]:
     a = torch.randn(T, K, device=dev)
     b = 0.05 * torch.randn(N, K, device=dev)
-    A, B = MF.split_image(a), MF.weight_image(b)
+    B = MF.weight_image(b)
+    A, arm = MF.split_image_rows(a) if "rows" in sys.argv[1:] else (MF.split_image(a), None)
     for _ in range(3):
-        MF.split_gemm_nt(A, B)
+        MF.split_gemm_nt(A, B, a_row_mul=arm)
     torch.cuda.synchronize()
     n_wg = min(8192, (T // 256) * (N // 256))
     buf = np.zeros((n_wg, 5), dtype=np.uint64)
@@ -37,7 +39,7 @@ for (N, K) in [(512, 512), (2048, 512), (512, 2048)]:
         gaps += list(t[order[1:], 0] - t[order[:-1], 3])
     gaps = np.array(gaps)
     span = t[:, 3].max() - t[:, 0].min()
-    print("N %4d K %4d: %d workgroups on %d units; ticks (median): set-up %d, main loop %d (%d per chunk), epilogue %d, exit->next entry on the unit %d "
+    print(("a_row_mul " if arm is not None else "") + "N %4d K %4d: %d workgroups on %d units; ticks (median): set-up %d, main loop %d (%d per chunk), epilogue %d, exit->next entry on the unit %d "
           "(p10 %d p90 %d); kernel span %d ticks = %.1f rounds x %d" % (N, K, n_wg, len(np.unique(cu)), np.median(setup), np.median(loop), np.median(loop) // (K // 32),
           np.median(epi), np.median(gaps) if len(gaps) else -1, np.percentile(gaps, 10) if len(gaps) else -1, np.percentile(gaps, 90) if len(gaps) else -1, span,
           n_wg / max(1, len(np.unique(cu))), np.median(t[:, 3] - t[:, 0])), flush=True)
