@@ -265,7 +265,8 @@ int mdl_infonce_fwd(const float* Q, const float* P, const int32_t* cnt, float* l
  * d_row_loss [S,Kmax] != NULL, the gradients of the per-sample losses (d_loss is then ignored and may be NULL); dQ,dP [S,Kmax,D] (rows
  * >= cnt[s] are zeroed).  ws must be the forward's.
  * Default: staged launches (normalise | similarity | log-sum-exp | loss ; coefficients | products | normalize backward), all stains per
- * launch.  MADELEINE_INFONCE_FUSED=1 with Kmax <= 256 and D <= 512: ONE launch forward and ONE backward producing the same bits
+ * launch.  Switch MDL_SW_INFONCE_FUSED ("Behaviour switches" below; the same value for a forward and its backward) with Kmax <= 256
+ * and D <= 512: ONE launch forward and ONE backward producing the same bits
  * (measured slower on MI355X: the problem is latency-bound and fusing gives up wave-level parallelism; csrc/infonce.hip). */
 int mdl_infonce_bwd(const float* Q, const float* P, const float* d_loss, const float* d_row_loss, const int32_t* cnt, float* dQ,
                     float* dP, int S, int Kmax, int D, float temperature, int symmetric, void* ws, void* stream);
@@ -336,12 +337,13 @@ int mdl_linear_bwd(const float* X, int64_t ldx, const float* W, const float* dY,
  * must receive the forward's workspace untouched.
  * ABI 23: for 128 < n <= 256 and 2 * (cases of the launch) <= compute units of the device, every IPOT sweep runs as TWO workgroups per
  * case and branch (row halves) that exchange their column sums once per iteration through 8-byte {value, tag} granules in the workspace
- * (device-scope stores / polls; csrc/got_resident.hip, Xch); MADELEINE_GOT_NOSPLIT=1 keeps the one-workgroup sweeps.  Same results up to the
+ * (device-scope stores / polls; csrc/got_resident.hip, Xch); the switch MDL_SW_GOT_NOSPLIT ("Behaviour switches" below; one value for all
+ * stages of a call) keeps the one-workgroup sweeps.  Same results up to the
  * association of the column sums; bit-reproducible.  The workspace's global region ends with four floats {pass generation (uint32 bits),
  * exchange time-out flag (0 = none; non-zero voids the pass), 0, 0}, followed by the 64 bytes of padding mdl_got_ws_bytes adds.
  * A voided pass says so in its results: out[0..1] of the forward and dV / dQ of the backward are NaN when the flag is up (a sweep waited
  * ~1 s for a partner workgroup that never became resident -- the device was shared with work the launch did not know about, e.g. a
- * second training process; run those with MADELEINE_GOT_NOSPLIT=1).  The flag is cleared by the extrema kernel of every forward.
+ * second training process; run those with MDL_SW_GOT_NOSPLIT set).  The flag is cleared by the extrema kernel of every forward.
  *
  * Return codes of every launching mdl_got_* function below (the four families: mdl_got_*, mdl_got_*_multi, mdl_got_tiled_*,
  * mdl_got_tiled_rect_*), in one order, each step over all problems of a call before the next step:
@@ -640,8 +642,8 @@ int mdl_abmil_attnpool_bwd_split(const void* E_img, int64_t e_rsb, const float* 
 
 /* Dispatch plan (ABI 25): what the launcher of `product` chooses for a problem of T tokens (GOT: T = cases k of the launch), WITHOUT
  * launching anything -- host only, no device, no device memory.  Every answer comes from the launcher's own selection functions
- * (splits_for and the per-product split / tile / persistence predicates, the GOT class selection), under the same MADELEINE_*
- * environment switches the launchers read.  `cus`: compute units of the device the plan is for (only the GOT sweeps depend on it;
+ * (splits_for and the per-product split / tile / persistence predicates, the GOT class selection), under the switch values the
+ * calling thread's launches would see ("Behaviour switches" below).  `cus`: compute units of the device the plan is for (only the GOT sweeps depend on it;
  * the gate / Linear launchers are sized for the 256 CUs of an MI355X).  out[0 .. n_out) receives up to MDL_PLAN_FIELDS fields
  * (the rest set to 0); returns MDL_E_ARG for an unknown product, bad sizes or n_out < 1, MDL_E_UNSUPPORTED where the launcher
  * would refuse the geometry.
@@ -693,6 +695,63 @@ int mdl_abmil_attnpool_bwd_split(const void* E_img, int64_t e_rsb, const float* 
 #define MDL_PLAN_EXTRA 6
 #define MDL_PLAN_FIELDS 7
 int mdl_dispatch_plan(int product, int64_t T, int a, int b, int cus, int64_t* out_host, int n_out);
+
+/* Behaviour switches (additive, ABI 26): the A/B and opt-in switches of the launchers, one table (csrc/switches.hip).  Each has an id
+ * below, a process-wide value and, per thread, an optional override.  The library reads the environment ONCE, on the first access to any
+ * switch (the first launch, plan or mdl_switch_* call of the process), and never again: setting a variable afterwards changes nothing.
+ * To change a switch later call mdl_switch_set (the process value) or mdl_switch_set_thread / mdl_switch_clear_thread (the calling
+ * thread's override, which wins over the process value for launches issued by that thread).  No value is range-checked; what a number
+ * means is decided where the launcher uses it.  All five calls are host only and thread-safe.
+ *
+ * Two kinds at the first read.  PRESENCE: 1 when the variable exists, whatever its text ("" and "0" included: =0 still means ON), else 0;
+ * a launcher tests value != 0.  INTEGER: atoll of the text when the variable exists ("abc" gives 0), else the default.
+ *
+ *   id                           variable                         kind      default  meaning
+ *   MDL_SW_INFONCE_FUSED         MADELEINE_INFONCE_FUSED          presence  0        the one-launch InfoNCE kernels (Kmax <= 256, D <= 512)
+ *   MDL_SW_BF16_GATE128          MADELEINE_BF16_GATE128           presence  0        bf16 gate forward on the 128 x 256 tile throughout
+ *   MDL_SW_DROP_16BIT            MADELEINE_DROP_16BIT             presence  0        one 16-bit hash per element where p allows the byte hash
+ *   MDL_SW_GOT_NO192             MADELEINE_GOT_NO192              presence  0        GOT: 128 < n <= 192 runs in the 256 class
+ *   MDL_SW_GOT_NOSPLIT           MADELEINE_GOT_NOSPLIT            presence  0        GOT: one-workgroup IPOT sweeps (no exchange)
+ *   MDL_SW_GOT_NO_HALF_PRODUCTS  MADELEINE_GOT_NO_HALF_PRODUCTS   presence  0        GOT: forward C_gamma products as one workgroup per case
+ *   MDL_SW_BF16_GATE_PERSIST     MADELEINE_BF16_GATE_PERSIST      integer   1        persistent mode 0 | 1 | 2 of the bf16 256-tile gate forward
+ *   MDL_SW_GATE_PERSIST          MADELEINE_GATE_PERSIST           integer   0        persistent mode 0 | 1 | 2 of the split gate forward
+ *   MDL_SW_BF16_LIN_PERSIST      MADELEINE_BF16_LIN_PERSIST       integer   1        0: bf16 Linear 256-tile, one column tile per workgroup
+ *   MDL_SW_BF16_LIN256_MINK      MADELEINE_BF16_LIN256_MINK       integer   512      smallest contraction of the bf16 Linear 256-tile
+ *   MDL_SW_BF16_TN256            MADELEINE_BF16_TN256             integer   1        0: bf16 dW products on the 128 x 256 x 32 tile
+ *   MDL_SW_SPLIT_TOKENS          MADELEINE_SPLIT_TOKENS           integer   32768    tokens per split of the dW-type contractions
+ *   MDL_SW_SP_NT_STAGES          MADELEINE_SP_NT_STAGES           integer   3        2: the two-stage NT loop of the split engine
+ *   MDL_SW_SP_TN_STAGES          MADELEINE_SP_TN_STAGES           integer   3        other than 3: the two-stage TN loop of the split engine
+ *   MDL_SW_BF16_STAGES           MADELEINE_BF16_STAGES            integer   3        2: the two-stage loops of the bf16 gate products
+ *   MDL_SW_BF16_LIN_STAGES       MADELEINE_BF16_LIN_STAGES        integer   31       2 | 3 | 31 (NT only) | 32 (TN only): bf16 Linear loops
+ *
+ * Precondition (it held before the table as well): calls that share a workspace run under the same switch values -- a *_ws_bytes query
+ * and the launches it sizes, a forward and its backward (mdl_infonce_fwd / _bwd; mdl_abmil_* forward / backward with dropout), and the
+ * stages of one GOT call (_extrema, _fwd, _bwd_begin, _bwd_finish).  Nothing checks it: change a switch between steps, not inside one.
+ *
+ * mdl_switch_get: *value = what the calling thread sees.  mdl_switch_name: the variable's name (a static string), NULL for an id outside
+ * 0 .. MDL_SW_COUNT - 1.  The others return MDL_E_ARG for such an id (mdl_switch_get also for value == NULL), MDL_OK otherwise. */
+#define MDL_SW_INFONCE_FUSED 0
+#define MDL_SW_BF16_GATE128 1
+#define MDL_SW_DROP_16BIT 2
+#define MDL_SW_GOT_NO192 3
+#define MDL_SW_GOT_NOSPLIT 4
+#define MDL_SW_GOT_NO_HALF_PRODUCTS 5
+#define MDL_SW_BF16_GATE_PERSIST 6
+#define MDL_SW_GATE_PERSIST 7
+#define MDL_SW_BF16_LIN_PERSIST 8
+#define MDL_SW_BF16_LIN256_MINK 9
+#define MDL_SW_BF16_TN256 10
+#define MDL_SW_SPLIT_TOKENS 11
+#define MDL_SW_SP_NT_STAGES 12
+#define MDL_SW_SP_TN_STAGES 13
+#define MDL_SW_BF16_STAGES 14
+#define MDL_SW_BF16_LIN_STAGES 15
+#define MDL_SW_COUNT 16
+int mdl_switch_get(int id, int64_t* value);
+int mdl_switch_set(int id, int64_t value);
+int mdl_switch_set_thread(int id, int64_t value);
+int mdl_switch_clear_thread(int id);
+const char* mdl_switch_name(int id);
 
 /* ------------------------------------------------------------------------------------------------
  * O1 -- multi-tensor fp32 AdamW that skips a step with a non-finite gradient and clips by the global gradient norm in-stream.

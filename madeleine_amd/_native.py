@@ -6,6 +6,7 @@ loaded (it is built in-tree by `python -m madeleine_amd._build` / __graft_entry_
 missing or stale and hipcc is present it is rebuilt once), and every op raises RuntimeError on a
 non-zero return code.
 """
+import contextlib
 import ctypes
 import os
 import re
@@ -168,3 +169,48 @@ def dispatch_plan(product: str, T: int, a: int, b: int = 0, cus: int = 256) -> d
     check(lib().mdl_dispatch_plan(PLAN_PRODUCTS[product], T, a, b, cus, ctypes.addressof(out), len(PLAN_FIELDS)),
           "mdl_dispatch_plan(%s, T=%d, %d, %d)" % (product, T, a, b))
     return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
+
+
+# The library's behaviour switches (include/madeleine_amd.h, "Behaviour switches"), by their environment names.  The library reads the
+# environment once, at its first use; these calls are how a switch changes afterwards.
+SWITCH_COUNT = _DEFINES["MDL_SW_COUNT"]
+_SWITCH_IDS = {}
+
+
+def switch_names() -> tuple:
+    """The environment names of the switches, in the order of their ids."""
+    return tuple(lib().mdl_switch_name(i).decode() for i in range(SWITCH_COUNT))
+
+
+def _switch_id(name: str) -> int:
+    if not _SWITCH_IDS:
+        _SWITCH_IDS.update({n: i for i, n in enumerate(switch_names())})
+    try:
+        return _SWITCH_IDS[name]
+    except KeyError:
+        raise KeyError("madeleine_amd: %r is not a library switch (%s)" % (name, ", ".join(_SWITCH_IDS))) from None
+
+
+def switch_get(name: str) -> int:
+    """The value the calling thread's launches see: its override if it holds one, the process value otherwise."""
+    out = ctypes.c_int64()
+    check(lib().mdl_switch_get(_switch_id(name), ctypes.addressof(out)), "mdl_switch_get(%s)" % name)
+    return out.value
+
+
+def switch_set(name: str, value: int) -> None:
+    """Set the process value (every thread without an override of its own sees it from its next launch on)."""
+    check(lib().mdl_switch_set(_switch_id(name), int(value)), "mdl_switch_set(%s)" % name)
+
+
+@contextlib.contextmanager
+def switch_override(name: str, value: int):
+    """Within the block the launches the calling thread issues see `value`; other threads and the process value are untouched -- autograd's
+    device thread included, which issues the launches of a `.backward()`.  The exit clears the thread's override: blocks for one switch do
+    not nest."""
+    sid = _switch_id(name)
+    check(lib().mdl_switch_set_thread(sid, int(value)), "mdl_switch_set_thread(%s)" % name)
+    try:
+        yield
+    finally:
+        check(lib().mdl_switch_clear_thread(sid), "mdl_switch_clear_thread(%s)" % name)

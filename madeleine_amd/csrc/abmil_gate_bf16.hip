@@ -173,10 +173,8 @@ __global__ __launch_bounds__(256, 2) void gate_fwd_bf16_kernel(const bf16_t* __r
 // first chunk's memory latency -- with the previous tile, and K = 512 is only 8 chunks.  A persistent workgroup runs several tiles back
 // to back and requests the NEXT tile's first chunk into stage 0 before the epilogue of the current one; the epilogue stages through
 // stage 1's memory (waves 0-3: A[1], waves 4-7: B[1]) and the row sums have their own 4 KiB.  PMODE as in abmil_gate_split.hip:
-// 0 = one tile per workgroup, 1 = the GATE_JT column tiles of a token tile, 2 = GATE_PT16 token tiles of one column tile.
-#ifndef MDL_GATE_BF16_PMODE
-#define MDL_GATE_BF16_PMODE 1
-#endif
+// 0 = one tile per workgroup, 1 = the GATE_JT column tiles of a token tile, 2 = GATE_PT16 token tiles of one column tile (default
+// MDL_GATE_BF16_PMODE, switches.hpp).
 constexpr int GATE_PT16 = 4;
 template <int DM, bool SAVE, int PMODE>
 __global__ __launch_bounds__(512) void gate_fwd256_bf16_kernel(const bf16_t* __restrict__ E, int64_t ldE, const bf16_t* __restrict__ WK,
@@ -612,16 +610,12 @@ __global__ __launch_bounds__(512) void gate_dw256_bf16_kernel(const bf16_t* __re
 // the forward on the 256 x 256 x 64 tile from 4096 tokens (MADELEINE_BF16_GATE128: the 128 x 256 tile throughout, A/B switch), and its
 // persistent workgroups (round 5, see gate_fwd256_bf16_kernel): MADELEINE_BF16_GATE_PERSIST = 0 | 1 | 2 picks the mode (A/B switch), kept
 // only where gate_persist_pays
-static inline bool gate_fwd_use_q(int64_t T) { return T >= 4096 && !getenv("MADELEINE_BF16_GATE128"); }
+static inline bool gate_fwd_use_q(int64_t T) { return T >= 4096 && !sw(MDL_SW_BF16_GATE128); }
 static inline int gate_fwd256_pmode(int64_t T, int H) {
-    static const int pmode_env = getenv("MADELEINE_BF16_GATE_PERSIST") ? atoi(getenv("MADELEINE_BF16_GATE_PERSIST")) : MDL_GATE_BF16_PMODE;
-    return gate_pmode(pmode_env, T, H, QM, 0.93, GATE_PT16);
+    return gate_pmode((int)sw(MDL_SW_BF16_GATE_PERSIST), T, H, QM, 0.93, GATE_PT16);
 }
 static inline bool gate_dx_use_q(int64_t T) { return T >= 4096; }   // long contraction (K = 1024): the 256 x 256 x 64 tile
-static inline bool gate_dw_use_q(int64_t T) {
-    static const bool off = getenv("MADELEINE_BF16_TN256") && atoi(getenv("MADELEINE_BF16_TN256")) == 0;   // A/B switch
-    return !off && T >= 16384;
-}
+static inline bool gate_dw_use_q(int64_t T) { return sw(MDL_SW_BF16_TN256) != 0 && T >= 16384; }   // (0: A/B switch)
 
 static GateFwdGeom fwd_geom(int64_t T, int H) {
     const int pmode = gate_fwd256_pmode(T, H);

@@ -74,9 +74,7 @@ __global__ void sp_bound_scale_kernel(const float* __restrict__ in, float mult, 
 //   PMODE 1: the GATE_JT column tiles of one (token tile, head): the E tile is re-read by the same CU GATE_JT times in a row
 //   PMODE 2: GATE_PT consecutive token tiles of one (column tile, head): the weight tile stays, and the GATE_JT workgroups of the same
 //            token tiles still run side by side on one XCD (they share each E tile through its L2, as in PMODE 0)
-#ifndef MDL_GATE_SP_PMODE
-#define MDL_GATE_SP_PMODE 0
-#endif
+// (default MDL_GATE_SP_PMODE, switches.hpp)
 constexpr int GATE_PT = 4;
 // NA = 3 (round 6; one tile per workgroup only): sp_nt_mainloop3 on SmemSP3 -- the LDS-DMA pieces spread over the chunk; the epilogue's
 // transposes then use A[0] / A[1] and the row sums B[0] of the drained ring (160 KiB leave no room for a separate array).
@@ -481,8 +479,7 @@ static inline int sp_dz_rows(int64_t T) { return T >= 131072 ? MDL_DZ_ROWS_BIG :
 // persistent workgroups of the forward (round 5, see sp_gate_fwd_kernel): MADELEINE_GATE_PERSIST = 0 | 1 | 2 picks the mode (A/B switch),
 // kept only where gate_persist_pays
 static inline int sp_gate_fwd_pmode(int64_t T, int H) {
-    static const int pmode_env = getenv("MADELEINE_GATE_PERSIST") ? atoi(getenv("MADELEINE_GATE_PERSIST")) : MDL_GATE_SP_PMODE;
-    return gate_pmode(pmode_env, T, H, SPM, 0.96, GATE_PT);
+    return gate_pmode((int)sw(MDL_SW_GATE_PERSIST), T, H, SPM, 0.96, GATE_PT);
 }
 
 static GateFwdGeom fwd_geom(int64_t T, int H) { return gate_fwd_grid(T, H, SPM, sp_gate_fwd_pmode(T, H), GATE_PT); }

@@ -27,7 +27,10 @@
 //     (v_mfma_f32_32x32x2_f32): K-chunks of 16 staged through LDS, each wave owns a 64x64 output panel.
 // Cs and Ct are bitwise symmetric here (the same accumulation chain computes <x_i,x_j> and <x_j,x_i>), so the
 // reference's transposes (:233, :240-247) are identities.
+#include <atomic>
+
 #include "got_host.hpp"
+#include "switches.hpp"
 
 namespace mdl {
 namespace got1024 {   // (the workgroup size; the kernel symbols carry it, and the profiles key on them)
@@ -2056,12 +2059,16 @@ static int launch_prep(const GotCall& call, hipStream_t s) {
 // 4.65 ms.  What the 16-wave sweep of the 256 class still waits for is its scratch reloads: every one is an s_waitcnt vmcnt(0) in front
 // of the plan rows in flight.)
 // split sweeps (see Xch): only while every workgroup of the launch can be resident at once -- 2 K (4 K) workgroups <= compute units
+// (of the calling thread's current device; cached per ordinal: 0 = not asked yet, -1 = the query failed)
 static int device_cus() {
-    static int cus = 0;
+    constexpr int MAX_DEV = 64;
+    static std::atomic<int> cache[MAX_DEV];
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return -1;
+    int cus = cache[dev].load(std::memory_order_relaxed);
     if (cus == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-        else cus = -1;
+        cus = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : -1;
+        cache[dev].store(cus, std::memory_order_relaxed);
     }
     return cus;
 }
@@ -2071,11 +2078,11 @@ static int got_class(int n) {
     if (n <= 64) return 64;
     if (n <= 128) return 128;
     if (n > GOT_REGN) return 512;
-    return (n <= 192 && !getenv("MADELEINE_GOT_NO192")) ? 192 : 256;
+    return (n <= 192 && !sw(MDL_SW_GOT_NO192)) ? 192 : 256;
 }
-static bool split_sweeps(int K, int cus) { return 2 * K <= cus && !getenv("MADELEINE_GOT_NOSPLIT"); }
+static bool split_sweeps(int K, int cus) { return 2 * K <= cus && !sw(MDL_SW_GOT_NOSPLIT); }
 static bool split_sweep_4k(int K, int cus) { return 4 * K <= cus; }   // both sweeps of a two-sweep step in ONE launch
-static bool half_products(int K, int cus) { return 2 * K <= cus && !getenv("MADELEINE_GOT_NO_HALF_PRODUCTS"); }
+static bool half_products(int K, int cus) { return 2 * K <= cus && !sw(MDL_SW_GOT_NO_HALF_PRODUCTS); }
 template <class K3, class K4>
 static void launch_split(K3 k3, K4 k4, const GotBatch& B, int K, int n, int o, int mult, hipStream_t s) {
     auto go = [&](int blocks, int mode) {

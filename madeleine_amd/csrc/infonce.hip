@@ -13,9 +13,8 @@
 //   Qn,Pn [S,Kp,D] | rq,rp [S,Kp] | Z [S,Kp,Kp] = logits | m0,l0,m1,l1 [S,Kp] | coef [S,Kp,Kp] | dQn,dPn [S,Kp,D]
 // (m, l) = (max, log sum exp(z - max)) per row (0) / column (1), kept SEPARATE like torch's log_softmax: at
 // T = 0.001 the logits are O(100) and lse - z_ii is O(1e-6), below fp32 resolution at 100.
-#include <cstdlib>
-
 #include "common.hpp"
+#include "switches.hpp"
 
 namespace mdl {
 
@@ -465,7 +464,7 @@ using namespace mdl;
 // (tools/exp_infonce.py, forward / backward in us: S=3 k=32 58 / 39 against 54 / 24; S=4 k=256 97 / 199 against 63 / 61) -- the
 // problem is latency-bound, launches on one stream pipeline (~5 us each), and fusing trades 4-16x of the wave-level parallelism for
 // them (64 workgroups at k = 256 where the staged gradient product runs 1024 waves).
-static bool nce_fused(int Kp, int D) { return Kp <= NCE_FK && D <= NCE_FD && getenv("MADELEINE_INFONCE_FUSED"); }
+static bool nce_fused(int Kp, int D) { return Kp <= NCE_FK && D <= NCE_FD && sw(MDL_SW_INFONCE_FUSED); }
 
 extern "C" int64_t mdl_infonce_ws_bytes(int S, int Kmax, int D) {
     if (S < 0 || Kmax < 0 || D < 8 || (D % 32)) return MDL_E_ARG;

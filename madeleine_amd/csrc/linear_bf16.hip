@@ -178,8 +178,7 @@ __global__ __launch_bounds__(512) void linb_nt256_kernel(const bf16_t* __restric
 // 0.61 -> 0.67 ms: the 1-MiB A tile is re-read in sequence instead of side by side) -- so PER = 4 below 1024, 1 from there on.
 // MADELEINE_BF16_LIN_PERSIST=0 forces PER = 1 (A/B switch).
 static inline int linb_nt256_per(int Kc, int n_ct) {
-    static const bool persist = !(getenv("MADELEINE_BF16_LIN_PERSIST") && atoi(getenv("MADELEINE_BF16_LIN_PERSIST")) == 0);
-    return (persist && Kc < 1024 && n_ct % 4 == 0) ? 4 : 1;
+    return (sw(MDL_SW_BF16_LIN_PERSIST) != 0 && Kc < 1024 && n_ct % 4 == 0) ? 4 : 1;
 }
 static inline void linb_launch_nt256(hipStream_t s, const bf16_t* A, int64_t lda, const bf16_t* B, const float* bias, bf16_t* C, int64_t ldc,
                                      int64_t T, int Kc, int n_ct, int64_t tiles) {
@@ -387,8 +386,7 @@ struct LinbWs {
 };
 // the 256-tile TN kernel: output rows (N) in whole 256-row tiles and enough tokens to amortise one workgroup per CU
 static inline bool linb_tn_use_q(int64_t T, int N) {
-    static const bool off = getenv("MADELEINE_BF16_TN256") && atoi(getenv("MADELEINE_BF16_TN256")) == 0;   // A/B switch
-    return !off && T >= 16384 && N % 256 == 0;
+    return sw(MDL_SW_BF16_TN256) != 0 && T >= 16384 && N % 256 == 0;   // (0: A/B switch)
 }
 static inline LinbWs linb_ws(int64_t T, int N, int K) {
     LinbWs w;
@@ -414,7 +412,7 @@ static inline LinbWs linb_ws(int64_t T, int N, int K) {
 // linb_launch_nt256 -- contractions of 512..1023 when the output has a multiple of 4 column tiles.  MADELEINE_BF16_LIN256_MINK=1024
 // restores the round-4 rule (A/B switch).
 static inline bool linb_use_q(int64_t T, int64_t Kc, int64_t n_out) {
-    static const int64_t mink = getenv("MADELEINE_BF16_LIN256_MINK") ? atoll(getenv("MADELEINE_BF16_LIN256_MINK")) : 512;
+    const int64_t mink = sw(MDL_SW_BF16_LIN256_MINK);
     if (T < 4096 || (Kc % QK) != 0 || (n_out % QN) != 0) return false;
     return Kc >= 1024 || (Kc >= mink && (n_out / QN) % 4 == 0);
 }

@@ -66,22 +66,10 @@ typedef SmemSPn<3> SmemSP3;
 #ifndef MDL_SP_TN_BSPREAD
 #define MDL_SP_TN_BSPREAD 0   // TN: both operands stream from HBM: B keeps the full chunk of flight time
 #endif
-// which NT main loop the launchers pick: MADELEINE_SP_NT_STAGES = 2 | 3 (A/B switch), default MDL_SP_NT_STAGES
-#ifndef MDL_SP_NT_STAGES
-#define MDL_SP_NT_STAGES 3
-#endif
+// which NT main loop the launchers pick: MADELEINE_SP_NT_STAGES = 2 | 3 (A/B switch), default MDL_SP_NT_STAGES (switches.hpp);
 // the TN (dW) loops: MADELEINE_SP_TN_STAGES = 2 | 3 (sp_tn_mainloop3), default MDL_SP_TN_STAGES
-#ifndef MDL_SP_TN_STAGES
-#define MDL_SP_TN_STAGES 3
-#endif
-static inline int sp_tn_stages() {
-    static const int v = getenv("MADELEINE_SP_TN_STAGES") ? atoi(getenv("MADELEINE_SP_TN_STAGES")) : MDL_SP_TN_STAGES;
-    return v == 3 ? 3 : 2;
-}
-static inline int sp_nt_stages() {
-    static const int v = getenv("MADELEINE_SP_NT_STAGES") ? atoi(getenv("MADELEINE_SP_NT_STAGES")) : MDL_SP_NT_STAGES;
-    return v == 2 ? 2 : 3;
-}
+static inline int sp_tn_stages() { return sw(MDL_SW_SP_TN_STAGES) == 3 ? 3 : 2; }
+static inline int sp_nt_stages() { return sw(MDL_SW_SP_NT_STAGES) == 2 ? 2 : 3; }
 
 // a wave-uniform pointer the compiler can keep in SGPRs (saddr operand of the LDS-DMA)
 __device__ __forceinline__ const char* sp_uniform(const char* p) {

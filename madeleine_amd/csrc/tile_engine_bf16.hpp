@@ -4,7 +4,6 @@
 //   NT: C[m][n] = sum_k A[m][k] B[n][k]  both operands K-contiguous rows; LDS image = XOR-swizzled 64-B rows, ds_read_b128.
 //   TN: C[m][n] = sum_k A[k][m] B[k][n]  both operands K-major; fragments gathered by ds_read_b64_tr_b16.
 #pragma once
-#include <cstdlib>
 #include "gate_common.hpp"
 
 namespace mdl {
@@ -177,22 +176,11 @@ struct __attribute__((aligned(16))) SmemQ3 {
     char A[3][Q_STAGE];
     char B[2][Q_STAGE];
 };
-#ifndef MDL_BF16_STAGES
-#define MDL_BF16_STAGES 3
-#endif
 // the Linears' 256-tile kernels separately (MADELEINE_BF16_LIN_STAGES = 2 | 3 | 31 (NT only) | 32 (TN only)): measured at config 2
 // (profiles/r06r_*, r06s_*) the gate's dX / dW gain 5 %; of the Linears the dX (NT) gains 1 %, the dW (TN) loses 4 % -- default 31
-#ifndef MDL_BF16_LIN_STAGES
-#define MDL_BF16_LIN_STAGES 31
-#endif
-static inline int bf16_lin_stages() {
-    static const int v = getenv("MADELEINE_BF16_LIN_STAGES") ? atoi(getenv("MADELEINE_BF16_LIN_STAGES")) : MDL_BF16_LIN_STAGES;
-    return v;
-}
-static inline int bf16_stages() {
-    static const int v = getenv("MADELEINE_BF16_STAGES") ? atoi(getenv("MADELEINE_BF16_STAGES")) : MDL_BF16_STAGES;
-    return v == 2 ? 2 : 3;
-}
+// (MDL_BF16_LIN_STAGES and MDL_BF16_STAGES, switches.hpp)
+static inline int bf16_lin_stages() { return (int)sw(MDL_SW_BF16_LIN_STAGES); }
+static inline int bf16_stages() { return sw(MDL_SW_BF16_STAGES) == 2 ? 2 : 3; }
 // LDS-DMA piece i (0..3) of wave w for either operand: 8 rows x 128 B; this lane fetches global 16-B chunk c of row `row` (tile-relative)
 // and the DMA deposits it at LDS slot (wave*4 + i)*1024 + lane*16 = row*128 + (c ^ ((row >> 1) & 7))*16.
 __device__ __forceinline__ void nt256_slot(int wave, int i, int lane, int& row, int& c) {

@@ -29,6 +29,8 @@ from typing import Dict, Optional, Sequence
 import torch
 import torch.distributed as dist
 
+from . import _native
+
 
 def init_from_env(backend: Optional[str] = None):
     """torchrun-style init (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the environment). Returns (rank, world, local_rank).
@@ -52,7 +54,7 @@ def init_from_env(backend: Optional[str] = None):
         if torch.cuda.is_available() and world > torch.cuda.device_count():
             # debug runs with several ranks on one GPU: the processes' launches share the compute units, so the residency bound the split
             # IPOT sweeps rely on (csrc/got_resident.hip, Xch) does not hold -- keep the one-workgroup sweeps
-            os.environ.setdefault("MADELEINE_GOT_NOSPLIT", "1")
+            _native.switch_set("MADELEINE_GOT_NOSPLIT", 1)
         dist.init_process_group(backend=backend, rank=rank, world_size=world)
     return rank, world, local_rank
 
@@ -398,9 +400,11 @@ class _fan_out:
             self.start.record(self.main)
             # The split IPOT sweeps (two workgroups per case that wait for each other, csrc/got_resident.hip) size every launch so that all of
             # its workgroups can be resident together; several chains launched side by side on different streams void that bound: keep the
-            # one-workgroup sweeps for launches issued inside a fan-out (the launcher reads the variable at every launch).
-            self.nosplit_was = os.environ.get("MADELEINE_GOT_NOSPLIT")
-            os.environ["MADELEINE_GOT_NOSPLIT"] = "1"
+            # one-workgroup sweeps for launches issued inside a fan-out.  Every launch of a fan-out is issued by the thread that entered it
+            # (lanes are streams, not threads), so the switch is this thread's override: the environment and other threads' launches
+            # are untouched.
+            self.nosplit = _native.switch_override("MADELEINE_GOT_NOSPLIT", 1)
+            self.nosplit.__enter__()
         return self._lane
 
     def _lane(self, i):
@@ -414,10 +418,7 @@ class _fan_out:
 
     def __exit__(self, *exc):
         if self.on:
-            if self.nosplit_was is None:
-                os.environ.pop("MADELEINE_GOT_NOSPLIT", None)
-            else:
-                os.environ["MADELEINE_GOT_NOSPLIT"] = self.nosplit_was
+            self.nosplit.__exit__(None, None, None)
             for i in self.used:
                 self.main.wait_stream(self.streams[i])
         return False

@@ -138,6 +138,11 @@ EXEMPT = {
     "mdl_abi_version": "Returns a constant; host only.",
     "mdl_linear_bf16_supported": "A host-only predicate on sizes.",
     "mdl_dispatch_plan": "Host only: writes a host array and launches nothing.",
+    "mdl_switch_get": "Host only: writes one host integer.",
+    "mdl_switch_set": "Host only: stores a process-wide value, takes no buffer.",
+    "mdl_switch_set_thread": "Host only: stores the calling thread's override, takes no buffer.",
+    "mdl_switch_clear_thread": "Host only: clears the calling thread's override, takes no buffer.",
+    "mdl_switch_name": "Returns a static string; host only.",
     "mdl_pool_timer_arm": "Measurement only: arms a process-wide timer slot, takes no buffer.",
     "mdl_pool_timer_read": "Measurement only: blocks on events and writes three floats to a host array.",
     "mdl_stream_create_cu_mask": "Creates a stream from a host mask; no device buffer.",

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from oracle import restatement as R
+from tests._switches import switch  # noqa: F401  (a fixture)
 from tests._util import MODS5, golden, max_rel, rel_err, t
 from tests.test_hip_kernels import _gate_weights, _oracle_scores
 from tests.test_model_gpu import build, grads_match
@@ -416,7 +417,7 @@ def test_train_step_is_reproducible(dev, config):
 C4_SHAPE = [(23, 112), (27, 180), (25, 185), (24, 188)]   # (cases this rank owns, n = min(k_global, 256)) per stain
 
 
-def test_got_multi_c4_rank_shape_vs_fp64_oracle(dev):
+def test_got_multi_c4_rank_shape_vs_fp64_oracle(dev, switch):
     """what a rank of the 8-GPU config runs -- FOUR GOT problems (one per stain) of k = 23..27 local cases
     at n = min(k_global, 256) = 112 / 180 / 185 / 188 tokens, concurrently on four side streams (got_multi's fan-out: per-phase
     launches and workspace-resident plan gradients for n > 128), with supplied threshold extrema -- against the fp64 oracle
@@ -472,11 +473,8 @@ def test_got_multi_c4_rank_shape_vs_fp64_oracle(dev):
         o3, g3 = run()
     finally:
         del os.environ["MADELEINE_GOT_NO_BATCH"]
-    os.environ["MADELEINE_GOT_NOSPLIT"] = "1"
-    try:
-        o4, g4 = run()
-    finally:
-        del os.environ["MADELEINE_GOT_NOSPLIT"]
+    switch("MADELEINE_GOT_NOSPLIT", 1)
+    o4, g4 = run()
     for s in range(len(C4_SHAPE)):
         if C4_SHAPE[s][1] > 128:
             assert torch.equal(o3[s], o4[s]) and torch.equal(g3[s][0], g4[s][0]) and torch.equal(g3[s][1], g4[s][1]), s

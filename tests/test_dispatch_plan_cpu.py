@@ -2,15 +2,20 @@
 persistence, token splits of the dW-type contractions, GOT size class and split sweeps.  No GPU: these run with -m "not gpu" and catch a
 retune of a split rule or a tile threshold that breaks an invariant of the kernels before any GPU run.  tests/test_dispatch_edges_gpu.py
 uses the same query to assert that each of its shapes reaches the branch it is named after."""
-import os
-
 import pytest
 
-# switches that change the answers pinned below (the invariants hold for any of their values)
-_SWITCHES = ("MADELEINE_SPLIT_TOKENS", "MADELEINE_BF16_TN256", "MADELEINE_BF16_GATE128", "MADELEINE_BF16_GATE_PERSIST",
-             "MADELEINE_BF16_LIN_PERSIST", "MADELEINE_BF16_LIN256_MINK", "MADELEINE_GATE_PERSIST", "MADELEINE_GOT_NOSPLIT",
-             "MADELEINE_GOT_NO192", "MADELEINE_GOT_NO_HALF_PRODUCTS")
-defaults_only = pytest.mark.skipif(any(k in os.environ for k in _SWITCHES), reason="pinned values are those of the default switches")
+from tests import _switches
+
+
+@pytest.fixture
+def _default_switches():
+    """The pinned values are those of the default switches (the invariants hold for any of their values)."""
+    changed = _switches.non_default()
+    if changed:
+        pytest.skip("pinned values are those of the default switches; the library sees %r" % changed)
+
+
+defaults_only = pytest.mark.usefixtures("_default_switches")
 
 # (product, a, b) of the token-split products: heads for the gates, (Mi, N) / (N, K) for the products
 SPLIT_PRODUCTS = [("gate_fp32_bwd", 4, 0), ("gate_fp32_bwd", 1, 0), ("gate_split_bwd", 4, 0), ("gate_split_bwd", 8, 0),

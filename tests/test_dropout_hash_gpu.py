@@ -38,6 +38,7 @@ import torch
 
 from tests import _drop_ref as D
 from tests import test_ln_kinds_gpu as K
+from tests._switches import switch  # noqa: F401  (a fixture)
 from tests._util import MODS5, t
 from tests.test_ln_kinds_gpu import ln_bwd, ln_bwd_split, ln_fwd, ln_fwd_split, same_bits
 
@@ -67,8 +68,8 @@ def _export(T, H, which, p, seed, dev, out=None):
 # ---------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("p", [0.25, 0.5, 0.1, 0.3, 1e-6, 0.99999])
 @pytest.mark.parametrize("H", [1, 2, 4, 8])
-def test_exported_gate_mask_equals_the_model(dev, monkeypatch, H, p):
-    monkeypatch.delenv("MADELEINE_DROP_16BIT", raising=False)      # (the library reads it at every launch)
+def test_exported_gate_mask_equals_the_model(dev, switch, H, p):
+    switch("MADELEINE_DROP_16BIT", 0)
     for T in (1, 130):
         for seed in SEEDS:
             want = [D.gate_keep(T, H, which, p, seed) for which in (0, 1)]
@@ -82,14 +83,14 @@ def test_exported_gate_mask_equals_the_model(dev, monkeypatch, H, p):
 
 
 @pytest.mark.parametrize("H", [1, 2, 4, 8])
-def test_exported_gate_mask_with_the_byte_fields_switched_off(dev, monkeypatch, H):
+def test_exported_gate_mask_with_the_byte_fields_switched_off(dev, switch, H):
     """p = 0.25 under MADELEINE_DROP_16BIT=1: the 16-bit rule, another mask than the byte rule gives."""
     for T in (1, 130):
         for seed in SEEDS:
             for which in (0, 1):
-                monkeypatch.setenv("MADELEINE_DROP_16BIT", "1")
+                switch("MADELEINE_DROP_16BIT", 1)
                 got16 = _export(T, H, which, 0.25, seed, dev).cpu().numpy()
-                monkeypatch.delenv("MADELEINE_DROP_16BIT")
+                switch("MADELEINE_DROP_16BIT", 0)
                 got8 = _export(T, H, which, 0.25, seed, dev).cpu().numpy()
                 assert np.array_equal(got16, D.gate_keep(T, H, which, 0.25, seed, force16=True)), (T, H, which, seed)
                 assert np.array_equal(got8, D.gate_keep(T, H, which, 0.25, seed)), (T, H, which, seed)
@@ -99,14 +100,14 @@ def test_exported_gate_mask_with_the_byte_fields_switched_off(dev, monkeypatch, 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # (b) the high word of the element index
 # ---------------------------------------------------------------------------------------------------------------------------------
-def test_exported_gate_mask_across_index_2_pow_32(dev, monkeypatch):
+def test_exported_gate_mask_across_index_2_pow_32(dev, switch):
     """T = 2^20 + 8 tokens at H = 8: 2^32 + 32768 elements (4.3 GB of uint8), the smallest shape whose indices cross 2^32 -- token 2^20
     starts exactly there.  Token rows [0, 8) and [2^20 - 8, 2^20 + 8) against the model at p = 0.1 (16-bit fields) and, into the same
     buffer, p = 0.25 (byte fields), both masks.  This is the only test that executes drop_row_key's high-word term: the gate forward /
     backward kernels and the LayerNorm kernels (act_row_key) are not run there -- their operands would be tens of GB -- so a wrong high
     word in those is not seen by any test (the wide strides of tests/test_stride_limits_gpu.py move addresses past 2^32, not the hash
     index, which depends on T alone)."""
-    monkeypatch.delenv("MADELEINE_DROP_16BIT", raising=False)
+    switch("MADELEINE_DROP_16BIT", 0)
     free = torch.cuda.mem_get_info(dev)[0]
     if free < 6 * 2 ** 30:
         pytest.skip("needs one 4.3 GB buffer: %.1f GB of device memory are free, 6 GB asked for" % (free / 2 ** 30))
@@ -284,12 +285,12 @@ MODEL_CASES = [(e, 4, "dense") for e in ENGINES] + [(e, 1, "dense") for e in ENG
 
 
 @pytest.mark.parametrize("engine,H,kind", MODEL_CASES, ids=["%s-H%d-%s" % c for c in MODEL_CASES])
-def test_model_step_from_seeds_equals_step_from_the_models_masks(dev, monkeypatch, engine, H, kind):
+def test_model_step_from_seeds_equals_step_from_the_models_masks(dev, monkeypatch, switch, engine, H, kind):
     """(e): 'split' = the split engine (the default; more than 256 token rows), 'fp32' = the exact-fp32 engine, 'bf16' = under autocast;
     'stain' = with stain encodings (the grouped LayerNorm path; on the split engine the per-group bias and the split-grouped backward),
     'ragged' = forward_ragged on packed bags of unequal lengths."""
     from madeleine_amd import functional as MF
-    monkeypatch.delenv("MADELEINE_DROP_16BIT", raising=False)
+    switch("MADELEINE_DROP_16BIT", 0)
     monkeypatch.setattr(MF, "GEMM_MODE", "fp32" if engine == "fp32" else "split")
     model = _model(dev, H, kind == "stain")
     if kind == "ragged":

@@ -36,7 +36,8 @@ def test_every_export_is_covered_or_exempt_and_never_both(protos):
 
 def test_exempt_holds_only_host_and_measurement_entry_points():
     allowed = {"mdl_version", "mdl_abi_version", "mdl_linear_bf16_supported", "mdl_dispatch_plan", "mdl_abmil_gate_dropout_mask",
-               "mdl_pool_timer_arm", "mdl_pool_timer_read", "mdl_stream_create_cu_mask", "mdl_stream_destroy"}
+               "mdl_pool_timer_arm", "mdl_pool_timer_read", "mdl_stream_create_cu_mask", "mdl_stream_destroy",
+               "mdl_switch_get", "mdl_switch_set", "mdl_switch_set_thread", "mdl_switch_clear_thread", "mdl_switch_name"}
     assert set(C.EXEMPT) <= allowed, sorted(set(C.EXEMPT) - allowed)
     for name, reason in C.EXEMPT.items():
         assert reason.strip().endswith(".") and reason.count(".") == 1, "one sentence: %s" % name

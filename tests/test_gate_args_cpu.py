@@ -14,7 +14,6 @@ call: it used to zero the pad rows of dz first and then return MDL_E_UNSUPPORTED
 memset's HIP error.  The bf16 and split backwards and the forwards refused it up front already."""
 import ctypes
 import math
-import os
 
 import pytest
 
@@ -232,7 +231,7 @@ def test_dropout_mask_checks(lib):
 # ---- the workspace layouts, restated ----
 def _splits_for(T, tiles, slots=768):
     """Token splits of a dW-type contraction (csrc/gate_common.hpp splits_for)."""
-    quantum = int(os.environ.get("MADELEINE_SPLIT_TOKENS", 32768))
+    quantum = _native.switch_get("MADELEINE_SPLIT_TOKENS")
     s = min(max(-(-T // 4096), 1), 64)
     if quantum > 4096:
         fill, sq = -(-slots // tiles), -(-T // quantum)
@@ -257,7 +256,7 @@ def _bwd_bytes(T, H, S, wn_elem, dz_elem, pad, dz_rows, scale_bytes):
 
 
 def _layouts(T, H):
-    wide = T >= 16384 and os.environ.get("MADELEINE_BF16_TN256", "1") != "0"   # the bf16 dW kernel on 256 x 256 tiles
+    wide = T >= 16384 and _native.switch_get("MADELEINE_BF16_TN256") != 0   # the bf16 dW kernel on 256 x 256 tiles
     return {
         "mdl_abmil_gate_fwd_ws_bytes": _fwd_bytes(T, H, 4, 0),
         "mdl_abmil_gate_fwd_bf16_ws_bytes": _fwd_bytes(T, H, 2, 0),

@@ -13,7 +13,6 @@ Shapes: T = 1 (less than a tile) and 130 (a full 128-row tile and a tail of 2) w
 Levels: measured on the library before gate_host.hpp and the same after: every comparison of (i) - (iv) is equal to the bit at every
 shape, engine and mode (1156 whole tensors over the 54 cases; the kernels of a pair differ in a template argument or in the launch
 sequence, never in the order of a floating-point operation), so every assertion is torch.equal."""
-import os
 
 import pytest
 import torch
@@ -156,15 +155,16 @@ def run_case(gate, dev, T, H, mode):
 
 @pytest.mark.parametrize("engine,T,H,mode", CASES, ids=["%s-T%d-H%d-%s" % c for c in CASES])
 def test_gate_kinds_agree(dev, engine, T, H, mode):
-    assert mode != "bytes" or "MADELEINE_DROP_16BIT" not in os.environ, "the byte-field hash is switched off: p = 0.25 would run the 16-bit one"
+    from madeleine_amd import _native
+    assert mode != "bytes" or not _native.switch_get("MADELEINE_DROP_16BIT"), "the byte-field hash is switched off: p = 0.25 would run the 16-bit one"
     assert run_case(Gate(engine), dev, T, H, mode) > 0
 
 
 def test_shapes_take_their_kernels():
     """The small shapes run the 128-row bf16 kernels, 4100 tokens the 256-row forward and dX tiles, 16390 the wide dW kernel too."""
     from madeleine_amd import _native
-    wide_fwd = "MADELEINE_BF16_GATE128" not in os.environ
-    wide_dw = os.environ.get("MADELEINE_BF16_TN256", "1").strip() not in ("0", "+0", "-0", "00")   # the switch is atoi(value) == 0
+    wide_fwd = not _native.switch_get("MADELEINE_BF16_GATE128")
+    wide_dw = _native.switch_get("MADELEINE_BF16_TN256") != 0
     for T in sorted({c[1] for c in CASES}):
         fwd, bwd = _native.dispatch_plan("gate_bf16_fwd", T, 1), _native.dispatch_plan("gate_bf16_bwd", T, 1)
         assert fwd["variant"] == (256 if T >= 4096 and wide_fwd else 128), (T, fwd)

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from oracle import restatement as R
+from tests._switches import switch  # noqa: F401  (a fixture)
 from tests._util import MODS5, rel_err, t
 
 pytestmark = pytest.mark.gpu
@@ -221,7 +222,7 @@ def test_bench_rank_emulation_equals_oracle_on_the_concatenated_global_batch(dev
             assert tk[m].grad is None or float(tk[m].grad.abs().max()) == 0.0, m
 
 
-def test_split_sweeps_equal_one_workgroup_sweeps_and_do_not_depend_on_timing(dev):
+def test_split_sweeps_equal_one_workgroup_sweeps_and_do_not_depend_on_timing(dev, switch):
     """Round 6: the IPOT sweeps of the n <= 192 / 256 classes run as TWO workgroups per case and branch that exchange their column sums
     once per iteration (csrc/got_resident.hip, Xch).  (i) Same numbers as the one-workgroup sweeps (MADELEINE_GOT_NOSPLIT=1) up to the
     re-association of the column sums; (ii) bit-identical from run to run while another stream keeps the memory system and the compute
@@ -230,11 +231,9 @@ def test_split_sweeps_equal_one_workgroup_sweeps_and_do_not_depend_on_timing(dev
     for name, shape in (("4x32x256", [(32, 256)] * 4), ("3x20x180", [(20, 180)] * 3)):
         probs_cpu, _ = _problems(shape, "split:" + name)
         o1, g1 = _run_batched(dev, probs_cpu)
-        os.environ["MADELEINE_GOT_NOSPLIT"] = "1"
-        try:
-            o0, g0 = _run_batched(dev, probs_cpu)
-        finally:
-            del os.environ["MADELEINE_GOT_NOSPLIT"]
+        switch("MADELEINE_GOT_NOSPLIT", 1)      # (process-wide: the backward's launches come from autograd's thread)
+        o0, g0 = _run_batched(dev, probs_cpu)
+        switch("MADELEINE_GOT_NOSPLIT", 0)
         assert rel_err(o1, o0) < 1e-6, (name, rel_err(o1, o0))
         for (a1, b1), (a0, b0) in zip(g1, g0):
             assert rel_err(a1, a0) < 2e-6 and rel_err(b1, b0) < 2e-6, (name, rel_err(a1, a0), rel_err(b1, b0))
@@ -259,6 +258,47 @@ def test_split_sweeps_equal_one_workgroup_sweeps_and_do_not_depend_on_timing(dev
     assert MF.got_exchange_timeouts(state[2]) == 0.0
     MF.HipGotImpl.backward_begin(state, torch.ones(2, device=dev))
     assert MF.got_exchange_timeouts(state[2]) == 0.0 and torch.isfinite(out).all()
+
+
+def test_thread_override_of_nosplit_equals_the_process_switch(dev, switch):
+    """MADELEINE_GOT_NOSPLIT as the calling thread's override (what distributed._fan_out sets) selects the same one-workgroup sweeps as
+    the process-wide switch: functional.got and its gradients equal to the bit (those sweeps are deterministic).  With the switch back
+    at its default the split sweeps run again: values within 1e-6, gradients within 2e-6 (relative, as in the test above), no exchange
+    timed out.  k = 2 cases of n = 129 tokens, d = 32: the smallest shape of the 192 class, where the split sweeps engage (2 k <= CUs).
+    An override reaches the launches its own thread issues, and autograd runs a device's backward nodes on a thread of its own: under
+    the override the stages that functional.got runs (GOTFn) are called here directly; under the process switch through autograd."""
+    from madeleine_amd import _native
+    from madeleine_amd import functional as MF
+    k, n, d = 2, 129, 32
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    plan = lambda: _native.dispatch_plan("got", k, n, cus=cus)      # noqa: E731
+    v = t((k, n, d), "got:override:v")
+    q = (t((k, n, d), "got:override:q") + 0.7 * v).to(dev)
+    v = v.to(dev)
+    ones = torch.ones(2, device=dev)
+
+    def stages():
+        out, state = MF.GOT_RESIDENT.forward(v, q, torch.empty(6, device=dev), None)
+        dV, dQ = MF.GOT_RESIDENT.backward(state, ones)
+        assert MF.got_exchange_timeouts(state[2]) == 0.0
+        return out, dV, dQ
+
+    switch("MADELEINE_GOT_NOSPLIT", 0)
+    assert plan()["variant"] == 192 and plan()["extra"] >= 1
+    with _native.switch_override("MADELEINE_GOT_NOSPLIT", 1):
+        assert plan()["extra"] == 0
+        mine = stages()
+    assert plan()["extra"] >= 1
+    switch("MADELEINE_GOT_NOSPLIT", 1)
+    vd, qd = v.clone().requires_grad_(), q.clone().requires_grad_()
+    out = MF.got(vd, qd)
+    out.backward(ones)
+    switch("MADELEINE_GOT_NOSPLIT", 0)
+    for a, b in zip(mine, (out.detach(), vd.grad, qd.grad)):
+        assert torch.isfinite(a).all() and torch.equal(a, b)
+    split = stages()
+    print("split against one-workgroup sweeps: out %.3g dV %.3g dQ %.3g" % tuple(rel_err(a, b) for a, b in zip(split, mine)))
+    assert rel_err(split[0], mine[0]) < 1e-6 and rel_err(split[1], mine[1]) < 2e-6 and rel_err(split[2], mine[2]) < 2e-6
 
 
 @pytest.mark.parametrize("k,n", [(6, 256), (5, 150), (4, 100), (3, 40), (2, 300)])

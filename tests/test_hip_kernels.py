@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import restatement as R
+from tests._switches import switch  # noqa: F401  (a fixture)
 from tests._util import max_rel, rel_err, t
 
 pytestmark = pytest.mark.gpu
@@ -282,7 +283,7 @@ def test_infonce_staged_path(dev, k, d, sym):
 
 
 @pytest.mark.parametrize("sym", [False, True])
-def test_infonce_fused_equals_staged_bitwise(dev, sym, monkeypatch):
+def test_infonce_fused_equals_staged_bitwise(dev, sym, switch):
     """The opt-in one-launch kernels (MADELEINE_INFONCE_FUSED=1; k <= 256, d <= 512) normalise on the fly with the staged path's
     products and summation orders: same bits for the losses and both gradients, ragged problem sizes and padding rows included."""
     from madeleine_amd import functional as MF
@@ -293,8 +294,7 @@ def test_infonce_fused_equals_staged_bitwise(dev, sym, monkeypatch):
     Q[1, 77:] = float("nan")     # padding rows may hold anything
     res = []
     for fused in (False, True):
-        if fused:
-            monkeypatch.setenv("MADELEINE_INFONCE_FUSED", "1")
+        switch("MADELEINE_INFONCE_FUSED", int(fused))
         q, p = Q.clone().requires_grad_(), P.clone().requires_grad_()
         loss = MF.info_nce_batched(q, p, cnt, 0.001, sym)
         (loss * torch.tensor([1.0, 2.0, 3.0], device=dev)).sum().backward()

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from tests import _nce_bounds as B
+from tests._switches import switch  # noqa: F401  (a fixture)
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
@@ -162,40 +163,40 @@ def _fusable(spec):
 
 
 @pytest.mark.parametrize("spec", INBATCH, ids=_id)
-def test_inbatch_staged(dev, spec, monkeypatch):
-    monkeypatch.delenv("MADELEINE_INFONCE_FUSED", raising=False)
+def test_inbatch_staged(dev, spec, switch):
+    switch("MADELEINE_INFONCE_FUSED", 0)
     Kmax, D, T, sym, family, form = spec
     case = B.inbatch_case((Kmax, B.mid_count(Kmax), 1), Kmax, D, T, sym, family, form)
     _check_inbatch(_run_inbatch(dev, case), case, "staged[%s]." % _id(spec))
 
 
 @pytest.mark.parametrize("spec", [s for s in INBATCH if _fusable(s)], ids=_id)
-def test_inbatch_fused(dev, spec, monkeypatch):
+def test_inbatch_fused(dev, spec, switch):
     """The opt-in one-launch kernels against fp64, independently of what the staged kernels give."""
-    monkeypatch.setenv("MADELEINE_INFONCE_FUSED", "1")
+    switch("MADELEINE_INFONCE_FUSED", 1)
     Kmax, D, T, sym, family, form = spec
     case = B.inbatch_case((Kmax, B.mid_count(Kmax), 1), Kmax, D, T, sym, family, form)
     _check_inbatch(_run_inbatch(dev, case), case, "fused[%s]." % _id(spec))
 
 
 @pytest.mark.parametrize("fused", [0, 1], ids=["staged", "fused"])
-def test_inbatch_single_empty_stain(dev, fused, monkeypatch):
+def test_inbatch_single_empty_stain(dev, fused, switch):
     """One problem with cnt = 0: loss 0, every row of row_loss, dQ and dP exactly 0."""
     if fused:
-        monkeypatch.setenv("MADELEINE_INFONCE_FUSED", "1")
+        switch("MADELEINE_INFONCE_FUSED", 1)
     else:
-        monkeypatch.delenv("MADELEINE_INFONCE_FUSED", raising=False)
+        switch("MADELEINE_INFONCE_FUSED", 0)
     case = B.inbatch_case((0,), 33, 64, 0.07, 1, "uniform", "d_loss", "empty")
     _check_inbatch(_run_inbatch(dev, case), case, "empty[%s]." % ("fused" if fused else "staged"))
 
 
 @pytest.mark.parametrize("fused", [0, 1], ids=["staged", "fused"])
-def test_inbatch_clamped_rows_are_rn_times_dxhat(dev, fused, monkeypatch):
+def test_inbatch_clamped_rows_are_rn_times_dxhat(dev, fused, switch):
     """On a clamped row (|x| < 1e-12) dX = rn dX^ within its bound: the dot of normalize()'s backward is dropped."""
     if fused:
-        monkeypatch.setenv("MADELEINE_INFONCE_FUSED", "1")
+        switch("MADELEINE_INFONCE_FUSED", 1)
     else:
-        monkeypatch.delenv("MADELEINE_INFONCE_FUSED", raising=False)
+        switch("MADELEINE_INFONCE_FUSED", 0)
     case = B.inbatch_case((33,), 33, 64, 0.07, 1, "degenerate", "d_row_loss", "clamped")
     got = _run_inbatch(dev, case)
     r = B._stain_ref(case["Q"][0], case["P"][0], B.t32(case["T"]), 1, case["g"][0], False, 64, False)

@@ -3,13 +3,14 @@ sum stayed at 58 ms): is the variance in the leg (host / GOT exchange) or in wha
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-if len(sys.argv) > 2 and sys.argv[2] == "nosplit":
-    os.environ["MADELEINE_GOT_NOSPLIT"] = "1"
 import torch
 import bench
 from madeleine_amd import InfoNCE, MADELEINE
 from madeleine_amd import distributed as D
-from madeleine_amd import functional as MF
+from madeleine_amd import _native, functional as MF
+
+if len(sys.argv) > 2 and sys.argv[2] == "nosplit":
+    _native.switch_set("MADELEINE_GOT_NOSPLIT", 1)
 
 dev = torch.device("cuda:0")
 torch.cuda.set_device(dev)

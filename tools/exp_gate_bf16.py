@@ -2,7 +2,7 @@
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from madeleine_amd import functional as MF
+from madeleine_amd import _native, functional as MF
 
 dev = torch.device("cuda:0")
 T, H = int(os.environ.get("TOKENS", 262144)), 4
@@ -38,7 +38,7 @@ os.environ["MADELEINE_GATE_LAB"] = "0"
 for p, save in ((0.0, True), (0.25, False), (0.0, False)):
     ms = run(p, save)
     print("p=%.2f save=%d: %.3f ms  %.3f PF" % (p, save, ms, fl / ms / 1e12))
-os.environ["MADELEINE_BF16_GATE128"] = "1"
+_native.switch_set("MADELEINE_BF16_GATE128", 1)
 print("128-tile p=.25 save: %.3f ms" % run(0.25, True))
 for n in os.environ.get("SLEEPS", "0 1 2 3 4 6").split():
     os.environ["MADELEINE_GATE_SLEEP"] = n

@@ -1,8 +1,8 @@
-"""InfoNCE forward + backward, fused (one launch each) (MADELEINE_INFONCE_FUSED=1) against the staged kernels, torch events."""
+"""InfoNCE forward + backward, fused (one launch each) (the switch MADELEINE_INFONCE_FUSED) against the staged kernels, torch events."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from madeleine_amd import functional as MF
+from madeleine_amd import _native, functional as MF
 
 dev = torch.device("cuda:0")
 for S, k in ((3, 32), (4, 64), (4, 256)):
@@ -10,10 +10,7 @@ for S, k in ((3, 32), (4, 64), (4, 256)):
     P = (torch.randn(S, k, 512, device=dev) + 0.2 * Q.detach()).requires_grad_()
     cnt = torch.full((S,), k, dtype=torch.int32, device=dev)
     for staged in (False, True):
-        if not staged:
-            os.environ["MADELEINE_INFONCE_FUSED"] = "1"
-        else:
-            os.environ.pop("MADELEINE_INFONCE_FUSED", None)
+        _native.switch_set("MADELEINE_INFONCE_FUSED", 0 if staged else 1)
         def step():
             Q.grad = P.grad = None
             MF.info_nce_batched(Q, P, cnt, 0.001, True).sum().backward()

@@ -7,7 +7,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from madeleine_amd import functional as MF  # noqa: E402
+from madeleine_amd import _native, functional as MF  # noqa: E402
 
 dev = torch.device("cuda:0")
 T, H = 262144, 4
@@ -35,10 +35,7 @@ def run(n=8):
 
 flop = T * H * 2 * 512 * 1024
 for tile in ("256", "128"):
-    if tile == "128":
-        os.environ["MADELEINE_BF16_GATE128"] = "1"
-    else:
-        os.environ.pop("MADELEINE_BF16_GATE128", None)
+    _native.switch_set("MADELEINE_BF16_GATE128", 1 if tile == "128" else 0)
     for st in ([0] if tile == "256" else [0, 0, 127, 254, 30000, -127, -254, -508, -30000, 0]):
         os.environ["MADELEINE_GATE_STAGGER"] = str(st)
         ms, chk = run()

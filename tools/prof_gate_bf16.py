@@ -7,7 +7,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from madeleine_amd import functional as MF  # noqa: E402
+from madeleine_amd import _native, functional as MF  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--tile", default="256")
@@ -16,7 +16,7 @@ ap.add_argument("--p", type=float, default=0.25)
 ap.add_argument("--split", action="store_true", help="the split-fp16 engine's gate forward (fp32 E image) instead of the bf16 one")
 a = ap.parse_args()
 if a.tile == "128":
-    os.environ["MADELEINE_BF16_GATE128"] = "1"
+    _native.switch_set("MADELEINE_BF16_GATE128", 1)
 dev = torch.device("cuda:0")
 T, H = 262144, 4
 g = torch.Generator(device=dev).manual_seed(0)
