@@ -15,10 +15,11 @@ madeleine.utils.loss, madeleine.utils.trainer):
     from madeleine_amd import heatmap            # attention heatmaps on the device: render, gaussian_taps, colormap, save_png
     from madeleine_amd import linear_probe_ci    # bootstrap intervals of the probes' metrics and paired differences between encoders
     from madeleine_amd import attn_contrib, contrib_stats   # which patches made a probe's decision (DeviceSlideStore.contributions)
+    from madeleine_amd import regression_probe   # continuous targets: batched ridge fits, Pearson, Spearman, R^2 on held-out cases
 
 The numeric work runs in csrc/libmadeleine_amd.so through the C ABI of include/madeleine_amd.h (the heatmap renderer: of
 include/madeleine_amd_view.h; the bootstrap counts: of include/madeleine_amd_stats.h; the patch contributions: of
-include/madeleine_amd_explain.h).
+include/madeleine_amd_explain.h; the regression probe: of include/madeleine_amd_regress.h).
 Importing this package does not load the library (so model construction / state_dict handling works on
 any box); the first forward does, and raises if it is unavailable -- there is no fallback path.
 """
@@ -39,11 +40,12 @@ __all__ = ["MADELEINE", "ABMILEmbedder", "BatchedABMIL", "create_model", "InfoNC
            "linear_probe", "device_smooth_rank", "cross_stain_retrieval", "retrieval_metrics", "slide_neighbours",
            "survival_splits", "fit_cox", "survival_probe", "cv_splits", "linear_probe_cv", "heatmap", "render_heatmaps", "gaussian_taps",
            "colormap", "save_png", "bootstrap_summary", "paired_difference", "linear_probe_ci", "survival_probe_ci", "attn_contrib",
-           "contrib_stats"]
+           "contrib_stats", "regression_splits", "fit_ridge", "regression_probe"]
 __version__ = "0.2"
 _HEATMAP = ("render_heatmaps", "gaussian_taps", "colormap", "save_png")
 _PROBE = ("probe_splits", "fit_logistic", "linear_probe", "cv_splits", "linear_probe_cv")
 _RESAMPLE = ("bootstrap_summary", "paired_difference", "linear_probe_ci", "survival_probe_ci")
+_REGRESS = ("regression_splits", "fit_ridge", "regression_probe")
 
 
 def __getattr__(name):
@@ -54,6 +56,9 @@ def __getattr__(name):
     if name in _RESAMPLE:      # imports the probe (above) and binds the third header's #defines: resolved on first use as well
         from . import resample
         return getattr(resample, name)
+    if name in _REGRESS:       # binds the fifth header's #defines: resolved on first use as well
+        from . import regress
+        return getattr(regress, name)
     if name == "heatmap" or name in _HEATMAP:      # the renderer binds the library's #defines: resolved on first use as well
         import importlib
         mod = importlib.import_module(".heatmap", __name__)

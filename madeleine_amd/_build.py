@@ -1,7 +1,7 @@
 """Builds libmadeleine_amd.so (gfx950) in-tree with hipcc.  No torch headers, no libtorch linkage:
 the library is a plain C-ABI shared object (include/madeleine_amd.h and, for the viewing side, include/madeleine_amd_view.h; for the
 bootstrap of the probes' metrics, include/madeleine_amd_stats.h; for the patch contributions of a probe's decision,
-include/madeleine_amd_explain.h)."""
+include/madeleine_amd_explain.h; for the regression probe, include/madeleine_amd_regress.h)."""
 import contextlib
 import fcntl
 import os
@@ -17,6 +17,7 @@ HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "madeleine_amd.h")
 VIEW_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "madeleine_amd_view.h"))      # csrc/heat_map.hip's entry points
 STATS_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "madeleine_amd_stats.h"))    # csrc/resample.hip's entry points
 EXPLAIN_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "madeleine_amd_explain.h"))  # csrc/contrib.hip's entry points
+REGRESS_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "madeleine_amd_regress.h"))  # csrc/ridge.hip's entry points
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
 
@@ -25,7 +26,7 @@ def sources():
 
 
 def _deps():
-    headers = [HEADER, VIEW_HEADER, STATS_HEADER, EXPLAIN_HEADER]
+    headers = [HEADER, VIEW_HEADER, STATS_HEADER, EXPLAIN_HEADER, REGRESS_HEADER]
     return headers + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))]
 
 

@@ -1,5 +1,5 @@
 // probe_host.hpp -- host side shared by the entry points that take a problem table (probe.hip, probe_primal.hip, survival.hip,
-// resample.hip): the record of the table, the limits of an entry point and the one function that refuses a call.  No kernel and no
+// resample.hip, ridge.hip): the record of the table, the limits of an entry point and the one function that refuses a call.  No kernel and no
 // device function lives here.
 #pragma once
 #include <type_traits>
@@ -24,6 +24,8 @@ struct ProbeTable {
     int ncol;
     int C;                // 0 where there are no classes
     int d;                // 0 where there is no X
+    int64_t T = 1;        // target columns of a shared Y [S, T] (the regression probe), 1 elsewhere
+    int A = 1;            // penalties per problem (the regression probe), 1 elsewhere
 };
 // the sizes alone, for a *_ws_bytes query (a size the query does not take: 1)
 inline ProbeTable probe_sizes(int64_t P, int n_max, int64_t S, int C, int d) { return {nullptr, nullptr, P, n_max, S, {}, 0, C, d}; }
@@ -36,6 +38,10 @@ struct ProbeLimits {
     int S;          // MDL_PROBE_MAX_CASES, MDL_BOOT_SURV_MAX_TEST or none
     bool fit;       // takes X [S, d]: d >= 1
     bool classes;   // takes C in 2 .. MDL_PROBE_MAX_CLASSES
+    int sys = PROBE_NO_LIMIT;   // MDL_RIDGE_MAX_SYS: the order min(n_max, d) of a direct solve, or none
+    int T = PROBE_NO_LIMIT;     // MDL_RIDGE_MAX_TARGETS or none
+    int A = PROBE_NO_LIMIT;     // MDL_RIDGE_MAX_ALPHAS or none
+    bool table = true;          // takes train_idx and n_train (false: a scoring call over P lists, n_max = 1)
 };
 
 // ---- what an entry point adds to its table.  The caller states facts; probe_check alone decides what is refused and in which order.
@@ -47,6 +53,7 @@ struct ProbeExtra {
     int64_t ldX = 0;     // row stride of X and the solver's arguments (fit entry points)
     int max_iter = 0;
     float cost = 0.f, gtol = 0.f;
+    bool values = true;  // every further argument the entry point states is in its range (ldY >= T, each alpha finite and > 0)
 };
 
 // a * b * c within int32, with every factor within int32 (so no 64-bit product can overflow on the way)
@@ -60,21 +67,24 @@ inline bool all_aligned(uintptr_t bytes, const Ptr*... p) { return (aligned_to(p
 
 // The only place that refuses a call of this family, before any launch and before a device pointer is touched:
 //   1. MDL_E_ARG: a NULL pointer; P, n_max or S < 1; d < 1 or ldX < d; max_iter < 0, cost not > 0, gtol not >= 0; R < 0; a column
-//      stride neither 0 nor >= S
-//   2. MDL_E_UNSUPPORTED: n_max, d or S beyond the entry point's row of limits, C outside 2 .. MDL_PROBE_MAX_CLASSES; R + 1 beyond int32;
+//      stride neither 0 nor >= S; T or A < 1, or a further argument outside the range its entry point states
+//   2. MDL_E_UNSUPPORTED: n_max, d, S, min(n_max, d), T or A beyond the entry point's row of limits, C outside
+//      2 .. MDL_PROBE_MAX_CLASSES; R + 1 beyond int32;
 //      S, P, P * n_max or one of the entry point's grids and element counts beyond int32
 //   3. MDL_E_ALIGN.
 // extra == nullptr is a *_ws_bytes query: the sizes it takes, the row of limits and P within int32.
 inline int probe_check(const ProbeTable& t, const ProbeLimits& lim, const ProbeExtra* extra) {
-    if (extra && (!t.train_idx || !t.n_train || !extra->pointers)) return MDL_E_ARG;
-    if (t.P < 1 || t.n_max < 1 || t.S < 1 || (lim.fit && t.d < 1)) return MDL_E_ARG;
+    if (extra && ((lim.table && (!t.train_idx || !t.n_train)) || !extra->pointers)) return MDL_E_ARG;
+    if (t.P < 1 || t.n_max < 1 || t.S < 1 || (lim.fit && t.d < 1) || t.T < 1 || t.A < 1) return MDL_E_ARG;
     if (extra) {
+        if (!extra->values) return MDL_E_ARG;
         if (lim.fit && (extra->ldX < t.d || extra->max_iter < 0 || !(extra->cost > 0.f) || !(extra->gtol >= 0.f))) return MDL_E_ARG;
         if (extra->R < 0) return MDL_E_ARG;
         for (int c = 0; c < t.ncol; ++c)
             if (!t.col[c].ptr || (t.col[c].ld != 0 && t.col[c].ld < t.S)) return MDL_E_ARG;
     }
     if (t.n_max > lim.n_max || t.d > lim.d || t.S > lim.S || !i32(t.P)) return MDL_E_UNSUPPORTED;
+    if ((t.n_max < t.d ? t.n_max : t.d) > lim.sys || t.T > lim.T || t.A > lim.A) return MDL_E_UNSUPPORTED;
     if (lim.classes && (t.C < 2 || t.C > PROBE_CMAX)) return MDL_E_UNSUPPORTED;
     if (!extra) return MDL_OK;
     if (extra->R > 0x7FFFFFFE || !mul_i32(t.P, t.n_max) || !extra->grids) return MDL_E_UNSUPPORTED;

@@ -9,6 +9,7 @@ Layouts (see include/madeleine_amd.h): token embeddings are head-major [T, H*512
 """
 import collections
 import contextlib
+import ctypes
 import os
 import threading
 from typing import Optional
@@ -2062,6 +2063,90 @@ def survival_metrics(z, time, event, train_idx, n_train, thr):
         _call("mdl_surv_metrics", z, time, ldt, event, lde, train_idx, n_train, P, n_max, S, thr, c_index, chi2, counts, ws, _stream(),
               unsupported=refusal)
     return c_index, chi2, counts
+
+
+# ---- R1-R3: the regression probe (mdl_ridge_fit / mdl_ridge_scores / mdl_regress_metrics, include/madeleine_amd_regress.h).  No autograd ----
+_RIDGE_LIMITS = ("regression probe supports min(n_max, d) <= %d, at most %d training cases per problem, %d targets, %d penalties and "
+                 "%d cases (got n_max %d, d %d, T %d, A %d, S %d)")
+REG_COLUMNS = ("n_test", "pearson", "spearman", "r2", "mae", "rmse")      # the columns of regress_metrics, in the MDL_REG_* order
+if [_native.REGRESS_DEFINES["MDL_REG_" + c.upper().replace("_", "")] for c in REG_COLUMNS] != list(range(6)):
+    raise ImportError("madeleine_amd: REG_COLUMNS does not match the MDL_REG_* indices of %s" % _native._build.REGRESS_HEADER)
+
+
+def _ridge_refusal(n_max, d, T, A, S):
+    lim = _native.REGRESS_DEFINES
+    return (_RIDGE_LIMITS, lim["MDL_RIDGE_MAX_SYS"], lim["MDL_RIDGE_MAX_TRAIN"], lim["MDL_RIDGE_MAX_TARGETS"], lim["MDL_RIDGE_MAX_ALPHAS"],
+            _native._DEFINES["MDL_PROBE_MAX_CASES"], n_max, d, T, A, S)
+
+
+def _target_matrix(Y, S):
+    """(T, ldY) of the targets Y [S, T] float32 with unit column stride."""
+    if Y.dim() != 2 or Y.dtype != torch.float32 or Y.shape[0] != S or Y.shape[1] < 1 or (Y.shape[1] > 1 and Y.stride(1) != 1):
+        raise RuntimeError("madeleine_amd: Y must be [S, T] = [%d, T] float32 with unit column stride" % S)
+    if not Y.is_cuda:
+        raise RuntimeError("madeleine_amd: Y must live on a ROCm device (got %s); there is no CPU fallback" % Y.device)
+    T = Y.shape[1]
+    return T, (Y.stride(0) if S > 1 else T)
+
+
+def _alpha_array(alphas):
+    """(host float array, A) of a sequence of penalties; the library refuses the values it does not take."""
+    values = [float(a) for a in alphas]
+    return (ctypes.c_float * max(len(values), 1))(*values), len(values)
+
+
+def ridge_fit(X, Y, train_idx, n_train, alphas):
+    """(W [P, A, T, d], b [P, A, T], info [P, A, 2]) of P x A x T ridge fits with an unpenalised intercept (R1 of the regression header):
+    X [S, d], Y [S, T] (NaN: no value), alphas a host sequence of A penalties > 0.  info columns: factorised (1 / 0), smallest pivot over
+    largest diagonal entry.  Asynchronous, no host read."""
+    S, d, ldX = _probe_matrix(X)
+    T, ldY = _target_matrix(Y, S)
+    P, n_max = _problem_table(train_idx, n_train)
+    arr, A = _alpha_array(alphas)
+    refusal = _ridge_refusal(n_max, d, T, A, S)
+    ws = _ws_for("mdl_ridge_fit_ws_bytes", X.device, P, n_max, d, T, A, refusal=refusal)
+    W = torch.empty(P, A, T, d, device=X.device, dtype=torch.float32)
+    b = torch.empty(P, A, T, device=X.device, dtype=torch.float32)
+    info = torch.empty(P, A, 2, device=X.device, dtype=torch.float32)
+    with _timed("ridge_fit"):
+        _call("mdl_ridge_fit", X, ldX, S, d, Y, ldY, T, train_idx, n_train, P, n_max, arr, A, W, b, info, ws, _stream(), unsupported=refusal)
+    return W, b, info
+
+
+def ridge_scores(X, W, b):
+    """Z [..., S] = X W^T + b for W [..., d] and b [...] (R2): the decision values of all S cases under every fit, each list contiguous."""
+    S, d, ldX = _probe_matrix(X)
+    _require(W, "W")
+    _require(b, "b")
+    if W.dim() < 2 or W.shape[-1] != d or b.shape != W.shape[:-1] or b.numel() < 1:
+        raise RuntimeError("madeleine_amd: W must be [..., %d] and b its leading shape" % d)
+    L = b.numel()
+    Z = torch.empty(*b.shape, S, device=X.device, dtype=torch.float32)
+    with _timed("ridge_scores", ("flop", 2.0 * L * S * d)):
+        _call("mdl_ridge_scores", X, ldX, S, d, W, b, L, Z, _stream())
+    return Z
+
+
+def regress_metrics(Z, Y, train_idx, n_train, return_sums=False):
+    """metrics [P, A, T, 6] fp64 over the test cases of every (p, t) -- Y[i, t] finite and i outside train_idx[p] -- for every penalty
+    (R3); columns REG_COLUMNS.  Z [P, A, T, S].  return_sums: also the int64 [P, A, T, 6] n, sum Rz, sum Ry, sum Rz^2, sum Ry^2, sum Rz Ry
+    of the doubled average ranks Spearman's rho is formed from."""
+    _require(Z, "Z")
+    if Z.dim() != 4 or min(Z.shape) < 1:
+        raise RuntimeError("madeleine_amd: Z must be [P, A, T, S]")
+    P, A, T, S = Z.shape
+    Ty, ldY = _target_matrix(Y, S)
+    Pt, n_max = _problem_table(train_idx, n_train)
+    _same_problems(Z, Pt)
+    if Ty != T:
+        raise RuntimeError("madeleine_amd: Z holds %d targets, Y %d" % (T, Ty))
+    refusal = _ridge_refusal(n_max, 1, T, A, S)
+    ws = _ws_for("mdl_regress_metrics_ws_bytes", Z.device, P, S, T, refusal=refusal)
+    metrics = torch.empty(P, A, T, 6, device=Z.device, dtype=torch.float64)
+    sums = torch.empty(P, A, T, 6, device=Z.device, dtype=torch.int64) if return_sums else None
+    with _timed("regress_metrics"):
+        _call("mdl_regress_metrics", Z, Y, ldY, T, train_idx, n_train, P, n_max, S, A, metrics, sums, ws, _stream(), unsupported=refusal)
+    return (metrics, sums) if return_sums else metrics
 
 
 # ---- A-map: the attention read-out (mdl_attn_softmax / mdl_attn_rank).  Forward only, no autograd: raw scores are inputs ----

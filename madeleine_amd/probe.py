@@ -235,6 +235,10 @@ def _parser():
                     help="with --bootstrap: a second embedding pickle over the same slides; the lines add the paired difference and its p")
     ap.add_argument("--level", type=float, default=0.95, help="with --bootstrap: the level of the intervals")
     ap.add_argument("--seed", type=int, default=0, help="with --bootstrap: the seed of the resamples")
+    ap.add_argument("--regress", nargs="+", default=None, metavar="COL",
+                    help="instead of the class tasks: read these columns as floats (empty or non-numeric: no value) and print the "
+                         "cross-validated ridge regression metrics (--cv_folds, default 5; --cv_repeats)")
+    ap.add_argument("--alphas", nargs="+", type=float, default=None, help="with --regress: the ridge penalties (default 1.0)")
     return ap
 
 
@@ -245,7 +249,32 @@ def _parse(argv=None):
         ap.error("--bootstrap needs R >= 0 and --level a value inside (0, 1)")
     if not args.bootstrap and (args.versus is not None or args.level != 0.95 or args.seed != 0):
         ap.error("--versus, --level and --seed belong to --bootstrap R")
+    if args.alphas is not None and (args.regress is None or any(not 0.0 < a < float("inf") for a in args.alphas)):
+        ap.error("--alphas belongs to --regress and takes finite penalties > 0")
+    if args.regress is not None and args.bootstrap:
+        ap.error("--bootstrap does not cover --regress")
     return args
+
+
+def _float_or_nan(text):
+    try:
+        return float(text)
+    except (TypeError, ValueError):
+        return float("nan")
+
+
+def _regress_lines(results, names, repeats, alphas):
+    """One line per (column, penalty): mean +/- std of every metric over every fold of every repeat."""
+    lines = []
+    for name in names:
+        for a, alpha in enumerate(alphas):
+            parts = []
+            for m in ("pearson", "spearman", "r2", "mae", "rmse"):
+                v = np.concatenate([results[(name, r)][m][:, a] for r in range(repeats)])
+                parts.append("{}={} +/- {}".format(m, round(float(np.nanmean(v)), 3), round(float(np.nanstd(v)), 3)))
+            n_test = int(sum(results[(name, r)]["n_test"].sum() for r in range(repeats)) // repeats)
+            lines.append("regress={}, alpha={:g}, cases={}, {}".format(name, alpha, n_test, ", ".join(parts)))
+    return lines
 
 
 def _bootstrap_lines(results, unit_name, level):
@@ -278,6 +307,13 @@ def _main(argv=None):
         rows = {str(r["slide_id"]): r for r in csv.DictReader(f)}
     keep = [i for i, s in enumerate(obj["slide_ids"]) if str(s) in rows]      # the reference's intersection of labels and embeddings
     embeds = np.asarray(obj["embeds"], dtype=np.float32)[keep]
+    if args.regress is not None:                    # continuous targets: the regression probe, and nothing of the class tasks
+        from .regress import regression_probe
+        targets = {c: np.array([_float_or_nan(rows[str(obj["slide_ids"][i])].get(c)) for i in keep], dtype=np.float32) for c in args.regress}
+        alphas = tuple(args.alphas or (1.0,))
+        results = regression_probe(embeds, targets, folds=args.cv_folds or 5, repeats=args.cv_repeats, alphas=alphas)
+        print("\n".join(_regress_lines(results, args.regress, args.cv_repeats, alphas)))
+        return
     labels = {t: np.array([int(float(rows[str(obj["slide_ids"][i])][t])) for i in keep]) for t in args.tasks}
     if args.bootstrap:                              # printed after the usual lines; the pickles below hold what they always held
         from .resample import linear_probe_ci
