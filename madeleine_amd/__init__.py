@@ -40,12 +40,13 @@ __all__ = ["MADELEINE", "ABMILEmbedder", "BatchedABMIL", "create_model", "InfoNC
            "linear_probe", "device_smooth_rank", "cross_stain_retrieval", "retrieval_metrics", "slide_neighbours",
            "survival_splits", "fit_cox", "survival_probe", "cv_splits", "linear_probe_cv", "heatmap", "render_heatmaps", "gaussian_taps",
            "colormap", "save_png", "bootstrap_summary", "paired_difference", "linear_probe_ci", "survival_probe_ci", "attn_contrib",
-           "contrib_stats", "regression_splits", "fit_ridge", "regression_probe"]
+           "contrib_stats", "regression_splits", "fit_ridge", "regression_probe", "fit_kmeans", "assign_kmeans"]
 __version__ = "0.2"
 _HEATMAP = ("render_heatmaps", "gaussian_taps", "colormap", "save_png")
 _PROBE = ("probe_splits", "fit_logistic", "linear_probe", "cv_splits", "linear_probe_cv")
 _RESAMPLE = ("bootstrap_summary", "paired_difference", "linear_probe_ci", "survival_probe_ci")
 _REGRESS = ("regression_splits", "fit_ridge", "regression_probe")
+_CLUSTER = ("fit_kmeans", "assign_kmeans", "KMeansResult")
 
 
 def __getattr__(name):
@@ -59,6 +60,9 @@ def __getattr__(name):
     if name in _REGRESS:       # binds the fifth header's #defines: resolved on first use as well
         from . import regress
         return getattr(regress, name)
+    if name in _CLUSTER:       # binds the sixth header's #defines: resolved on first use as well
+        from . import cluster
+        return getattr(cluster, name)
     if name == "heatmap" or name in _HEATMAP:      # the renderer binds the library's #defines: resolved on first use as well
         import importlib
         mod = importlib.import_module(".heatmap", __name__)

@@ -1,7 +1,8 @@
 """Builds libmadeleine_amd.so (gfx950) in-tree with hipcc.  No torch headers, no libtorch linkage:
 the library is a plain C-ABI shared object (include/madeleine_amd.h and, for the viewing side, include/madeleine_amd_view.h; for the
 bootstrap of the probes' metrics, include/madeleine_amd_stats.h; for the patch contributions of a probe's decision,
-include/madeleine_amd_explain.h; for the regression probe, include/madeleine_amd_regress.h)."""
+include/madeleine_amd_explain.h; for the regression probe, include/madeleine_amd_regress.h; for k-means over the slide store,
+include/madeleine_amd_cluster.h)."""
 import contextlib
 import fcntl
 import os
@@ -18,6 +19,7 @@ VIEW_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "madeleine_am
 STATS_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "madeleine_amd_stats.h"))    # csrc/resample.hip's entry points
 EXPLAIN_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "madeleine_amd_explain.h"))  # csrc/contrib.hip's entry points
 REGRESS_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "madeleine_amd_regress.h"))  # csrc/ridge.hip's entry points
+CLUSTER_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "madeleine_amd_cluster.h"))  # csrc/kmeans.hip's entry points
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
 
@@ -26,7 +28,7 @@ def sources():
 
 
 def _deps():
-    headers = [HEADER, VIEW_HEADER, STATS_HEADER, EXPLAIN_HEADER, REGRESS_HEADER]
+    headers = [HEADER, VIEW_HEADER, STATS_HEADER, EXPLAIN_HEADER, REGRESS_HEADER, CLUSTER_HEADER]
     return headers + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))]
 
 

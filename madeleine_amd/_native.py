@@ -1,5 +1,5 @@
 """ctypes binding of libmadeleine_amd.so (the C ABI of include/madeleine_amd.h, include/madeleine_amd_view.h,
-include/madeleine_amd_stats.h, include/madeleine_amd_explain.h and include/madeleine_amd_regress.h).
+include/madeleine_amd_stats.h, include/madeleine_amd_explain.h, include/madeleine_amd_regress.h and include/madeleine_amd_cluster.h).
 
 Single backend: there is no CPU / eager fallback.  `lib()` raises if the shared object cannot be
 loaded (it is built in-tree by `python -m madeleine_amd._build` / __graft_entry__.build(); if it is
@@ -95,6 +95,13 @@ with open(_build.REGRESS_HEADER) as _f:
 if (set(REGRESS_SIGNATURES) & (set(SIGNATURES) | set(VIEW_SIGNATURES) | set(STATS_SIGNATURES) | set(EXPLAIN_SIGNATURES))) or \
         (set(REGRESS_DEFINES) & (set(_DEFINES) | set(VIEW_DEFINES) | set(STATS_DEFINES) | set(EXPLAIN_DEFINES))):
     raise ImportError("madeleine_amd: %s repeats a name of the other four headers" % _build.REGRESS_HEADER)
+# the sixth header (include/madeleine_amd_cluster.h: k-means over the slide store), the same way again: no name of the other five
+with open(_build.CLUSTER_HEADER) as _f:
+    CLUSTER_SIGNATURES, CLUSTER_DEFINES = _parse_header(_f.read())
+if (set(CLUSTER_SIGNATURES) & (set(SIGNATURES) | set(VIEW_SIGNATURES) | set(STATS_SIGNATURES) | set(EXPLAIN_SIGNATURES) |
+                               set(REGRESS_SIGNATURES))) or \
+        (set(CLUSTER_DEFINES) & (set(_DEFINES) | set(VIEW_DEFINES) | set(STATS_DEFINES) | set(EXPLAIN_DEFINES) | set(REGRESS_DEFINES))):
+    raise ImportError("madeleine_amd: %s repeats a name of the other five headers" % _build.CLUSTER_HEADER)
 
 
 def lib_path() -> str:
@@ -138,7 +145,7 @@ def lib():
             raise RuntimeError("madeleine_amd: %s implements ABI revision %d, this binding expects %d; rebuild it "
                                "(`python -m madeleine_amd._build --force`)" % (path, abi(), ABI_VERSION))
         for name, (res, args) in list(SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(STATS_SIGNATURES.items()) + \
-                list(EXPLAIN_SIGNATURES.items()) + list(REGRESS_SIGNATURES.items()):
+                list(EXPLAIN_SIGNATURES.items()) + list(REGRESS_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()):
             try:
                 fn = getattr(handle, name)
             except AttributeError:

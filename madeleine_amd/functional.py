@@ -2588,3 +2588,117 @@ def contrib_stats(contrib, cu):
     with _timed("contrib_stats", ("byte", 4.0 * T * C)):
         _call("mdl_contrib_stats", contrib, ld, cu, T, R, C, stats, ws, _stream(), unsupported=refusal)
     return stats
+
+
+# ---- K1-K4: k-means over the rows of the slide store (include/madeleine_amd_cluster.h).  No autograd: features are inputs ----
+KM_ROWS = _native.CLUSTER_DEFINES["MDL_KM_ROWS"]
+KM_MAX_K = _native.CLUSTER_DEFINES["MDL_KM_MAX_K"]
+_KM_LIMITS = "k-means supports 1..%d clusters and fewer than 2^31 rows per call (got k %d, T %d)"
+
+
+def _km_source(store_rows, off, bag, cu, chunk_cu, fn):
+    """The row source of K1-K3: store_rows [T_total, D] in a store dtype on the device, off int64 [n_bags + 1], bag int32 [R], cu and
+    (unless None) chunk_cu int64 [R + 1], all on the device.  Returns the leading arguments of the entry points."""
+    _require_store(store_rows)
+    _require_draw_tables(off, bag, None, "bag")
+    _require(cu, "cu", torch.int64)
+    R = bag.numel()
+    if cu.numel() != R + 1:
+        raise RuntimeError("madeleine_amd: %s needs cu [R + 1] = [%d]" % (fn, R + 1))
+    if chunk_cu is not None:
+        _require(chunk_cu, "chunk_cu", torch.int64)
+        if chunk_cu.numel() != R + 1:
+            raise RuntimeError("madeleine_amd: %s needs chunk_cu [R + 1] = [%d]" % (fn, R + 1))
+    D = store_rows.shape[1]
+    return (store_rows, STORE_DTYPES[store_rows.dtype], store_rows.stride(0) if store_rows.shape[0] > 1 else D, store_rows.shape[0], off,
+            off.numel() - 1, bag, cu)
+
+
+def _km_centroids(C, D, name="centroids"):
+    _require(C, name)
+    if C.dim() != 2 or C.shape[1] != D or C.shape[0] < 1:
+        raise RuntimeError("madeleine_amd: %s must be [k, D] = [k, %d] float32 (got %s)" % (name, D, tuple(C.shape)))
+    return C.shape[0]
+
+
+def _km_vector(t, name, dtype, n):
+    _require(t, name, dtype)
+    if t.dim() != 1 or t.numel() != n:
+        raise RuntimeError("madeleine_amd: %s must be [%d] %s (got %s)" % (name, n, dtype, tuple(t.shape)))
+    return t
+
+
+def kmeans_assign(store_rows, off, bag, cu, chunk_cu, n_chunks, n_rows, centroids, labels=None, dist=None, stats=None, ws=None):
+    """(labels [T] int32, dist [T] fp32, stats [2] int64) <- the nearest of centroids [k, D] for every row of the listed bags (K1 of
+    include/madeleine_amd_cluster.h): the rows are read where they lie on the exact-fp32 MFMA, ties go to the lowest centroid, a row
+    with a non-finite element gets label -1 and dist NaN.  labels is IN and OUT (None: a fresh vector of -2, so every finite row
+    counts as changed); stats[0] is the number of rows whose label changed and stats[1] holds the bits of the fp64 inertia
+    (stats.view(torch.float64)[1]).  n_chunks = chunk_cu[R] and n_rows = cu[R] = T as host integers; chunk_cu counts chunks of KM_ROWS
+    rows.  ws: a workspace of at least mdl_kmeans_assign_ws_bytes (None: allocated here).  No host read."""
+    src = _km_source(store_rows, off, bag, cu, chunk_cu, "kmeans_assign")
+    T, D, dev = int(n_rows), store_rows.shape[1], store_rows.device
+    k = _km_centroids(centroids, D)
+    labels = torch.full((T,), -2, device=dev, dtype=torch.int32) if labels is None else _km_vector(labels, "labels", torch.int32, T)
+    dist = torch.empty(T, device=dev, dtype=torch.float32) if dist is None else _km_vector(dist, "dist", torch.float32, T)
+    stats = torch.empty(2, device=dev, dtype=torch.int64) if stats is None else _km_vector(stats, "stats", torch.int64, 2)
+    refusal = (_KM_LIMITS, KM_MAX_K, k, T)
+    if ws is None:
+        ws = _ws_for("mdl_kmeans_assign_ws_bytes", dev, int(n_chunks), k, D, refusal=refusal)
+    with _timed("kmeans_assign", ("flop", 2.0 * T * k * D)):
+        _call("mdl_kmeans_assign", *src, chunk_cu, bag.numel(), int(n_chunks), T, D, centroids, k, labels, dist, stats, ws, _stream(),
+              unsupported=refusal)
+    return labels, dist, stats
+
+
+def kmeans_update(store_rows, off, bag, cu, n_rows, labels, centroids, out=None, counts=None, ws=None):
+    """(C_out [k, D] fp32, counts [k] int64) <- the mean of the rows of every label (K2): a stable counting sort of the call positions by
+    label and S5's summation over each cluster's member list, combined in fp64.  A cluster with no member keeps its row of `centroids`.
+    Five launches, no atomics on floats, no host read."""
+    src = _km_source(store_rows, off, bag, cu, None, "kmeans_update")
+    T, D, dev = int(n_rows), store_rows.shape[1], store_rows.device
+    k = _km_centroids(centroids, D)
+    _km_vector(labels, "labels", torch.int32, T)
+    if out is None:
+        out = torch.empty(k, D, device=dev, dtype=torch.float32)
+    elif _km_centroids(out, D, "out") != k:
+        raise RuntimeError("madeleine_amd: kmeans_update needs out [k, D] like centroids")
+    counts = torch.empty(k, device=dev, dtype=torch.int64) if counts is None else _km_vector(counts, "counts", torch.int64, k)
+    refusal = (_KM_LIMITS, KM_MAX_K, k, T)
+    if ws is None:
+        ws = _ws_for("mdl_kmeans_update_ws_bytes", dev, T, k, D, refusal=refusal)
+    with _timed("kmeans_update", ("byte", float(T) * D * store_rows.element_size())):
+        _call("mdl_kmeans_update", *src, bag.numel(), T, D, labels, centroids, k, out, counts, ws, _stream(), unsupported=refusal)
+    return out, counts
+
+
+def kmeans_seed(store_rows, off, bag, cu, chunk_cu, n_chunks, n_rows, u):
+    """(positions [k] int64, centroids [k, D] fp32) <- k-means++ seeding from u [k] fp64 uniforms in [0, 1) on the device (K3): D^2
+    sampling in-stream, two launches per centre, no host read."""
+    src = _km_source(store_rows, off, bag, cu, chunk_cu, "kmeans_seed")
+    T, D, dev = int(n_rows), store_rows.shape[1], store_rows.device
+    _require(u, "u", torch.float64)
+    if u.dim() != 1 or u.numel() < 1:
+        raise RuntimeError("madeleine_amd: u must be [k] float64")
+    k = u.numel()
+    refusal = (_KM_LIMITS, KM_MAX_K, k, T)
+    pos = torch.empty(k, device=dev, dtype=torch.int64)
+    C = torch.empty(k, D, device=dev, dtype=torch.float32)
+    ws = _ws_for("mdl_kmeans_seed_ws_bytes", dev, int(n_chunks), T, refusal=refusal)
+    with _timed("kmeans_seed", ("byte", float(T) * D * store_rows.element_size() * k)):
+        _call("mdl_kmeans_seed", *src, chunk_cu, bag.numel(), int(n_chunks), T, D, u, k, pos, C, ws, _stream(), unsupported=refusal)
+    return pos, C
+
+
+def kmeans_hist(labels, cu, k):
+    """counts [R, k] int32 <- per bag of cu int64 [R + 1] (device), the number of its call positions with each label in [0, k); any other
+    label -- the -1 of a non-finite row -- is counted nowhere (K4).  One launch, no host read."""
+    _require(labels, "labels", torch.int32)
+    _require(cu, "cu", torch.int64)
+    if labels.dim() != 1 or labels.numel() < 1 or cu.dim() != 1 or cu.numel() < 1:
+        raise RuntimeError("madeleine_amd: kmeans_hist needs labels [T], T >= 1, and cu [R + 1]")
+    R, k = cu.numel() - 1, int(k)
+    counts = torch.empty(R, max(k, 0), device=labels.device, dtype=torch.int32)
+    with _timed("kmeans_hist", ("byte", 4.0 * labels.numel())):
+        _call("mdl_kmeans_hist", labels, cu, R, labels.numel(), k, counts if counts.numel() else labels, _stream(),
+              unsupported=(_KM_LIMITS, KM_MAX_K, k, labels.numel()))
+    return counts

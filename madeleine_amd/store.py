@@ -480,6 +480,48 @@ class DeviceSlideStore:
                                                host_wgs=host_wgs))
         return self._embedding_result(outs[0] if k == 1 else torch.cat(outs), cases, rank)
 
+    def _prototype_source(self, what, modality, case_indices):
+        """(cases, the cluster.RowSource over one stain's bags) for the k-means read-outs: whole bags, read where they lie.  Resident
+        tier only: Lloyd re-reads every row twice per iteration, and PCIe is not the place for that."""
+        from . import cluster
+        self._require_device(what)
+        cases, bag, lens = self._modality_plan(case_indices, modality)
+        ends = self.off_cpu.index_select(0, bag.long() + 1)
+        if bool((ends > self.resident_rows).any()):
+            c = int(cases[int((ends > self.resident_rows).nonzero()[0])])
+            raise NotImplementedError("DeviceSlideStore.%s: the %s bag of case %d (%s) lies in the pinned host tier; k-means reads "
+                                      "resident bags only" % (what, self.modalities[modality], c, self.slide_ids[c]))
+        if bag.numel() == 0:
+            raise ValueError("DeviceSlideStore.%s: no case has a %s bag" % (what, self.modalities[modality]))
+        return cases, cluster.RowSource(self.rows, self.off, bag, lens, self.off_cpu.index_select(0, bag.long()))
+
+    def prototypes(self, k, modality=0, case_indices=None, **fit) -> dict:
+        """k morphological prototypes of one stain: cluster.fit_kmeans(k, **fit) over ALL rows of the bags of the cases asked for (None:
+        every case that has the stain), read where they lie in any store dtype -- no packed copy.  Returns the KMeansResult's fields
+        ("centroids" [k, D], "labels" [T], "dist" [T], "counts" [k], "inertia", "n_iter", "converged") plus "cu" (int64 [n + 1] on the
+        device: bag r of the list is call positions cu[r] .. cu[r + 1] - 1 of labels), "cases" and "slide_ids"; bit for bit what
+        fit_kmeans gives on the packed rows of the same bags.  One O(n) table upload.  NotImplementedError naming the first case whose
+        bag lies in the pinned host tier; ValueError / IndexError as pack_modality."""
+        from . import cluster
+        cases, src = self._prototype_source("prototypes", modality, case_indices)
+        res = cluster.fit_kmeans(src, k, **fit)
+        out = res._asdict()
+        out.update(cu=src.cu, cases=cases, slide_ids=[self.slide_ids[c] for c in cases.tolist()])
+        return out
+
+    def prototype_histograms(self, centroids, modality=0, case_indices=None, normalize=True) -> dict:
+        """The bag of prototypes of every case asked for: {"embeds" [n, k] fp32 on the device, "cases", "slide_ids"}, mean_embeddings'
+        shape, so it feeds linear_probe, linear_probe_cv, the *_ci functions and slide_neighbours unchanged.  embeds[r, j] is the number
+        of rows of the case's bag whose nearest centroid is j (one assign pass and functional.kmeans_hist; a row with a non-finite
+        element is counted nowhere), divided by the row's total when normalize (a bag of no countable row stays zeros)."""
+        from . import cluster
+        cases, src = self._prototype_source("prototype_histograms", modality, case_indices)
+        labels, _ = cluster.assign_kmeans(src, centroids)
+        hist = MF.kmeans_hist(labels, src.cu, centroids.shape[0]).to(torch.float32)
+        if normalize:
+            hist = hist / hist.sum(1, keepdim=True).clamp(min=1.0)
+        return self._embedding_result(hist, cases)
+
     def embed(self, model, modality=0, case_indices=None, bags_per_launch=None, max_tokens=None, precision=None, host_wgs=0,
               rank=False) -> dict:
         """The slide embedding of one stain's bag of every case asked for (None: every case that has the stain), from `model`'s H&E
